@@ -245,6 +245,33 @@ def coarse_solve_parity(problem, iters=5, **kw):
             "bound": "1e-10 * conv + 2 * eps * ||u||_spacetime", "within_bound": bool(len(a) == len(b) and np.all(dev <= bound))}
 
 
+DUMP_ROW_BYTES = 48 * 2 ** 20     # --dump-outputs: level-0 rows of the sample; with the small arrays the dump stays under 64 MB
+
+
+def dump_outputs(mg, out_dir):
+    """--dump-outputs DIR: what the last timed step computed, as a caller of Mgrit.iteration + convergence_criterion reads it, one
+    float64 .npy file per array: conv (the stopping value of the step), residual_norms (the per-C-point norms it reduces),
+    u_level0_sample (the level-0 solution in natural order at a fixed sample of time points: all of them where they fit, else the
+    first, the last and a seeded draw of the others, sorted) and u_level0_sample_index (those time points). The same arguments
+    give the same sample, so two builds can be compared array for array. Outside every timed region."""
+    os.makedirs(out_dir, exist_ok=True)
+    u = mg.u[0]
+    n_pts = len(u)
+    first = np.asarray(u[0].get_values(), dtype=np.float64).ravel()
+    rows = max(1, min(n_pts, DUMP_ROW_BYTES // (8 * first.size)))
+    if rows >= n_pts:
+        idx = np.arange(n_pts)
+    else:
+        draw = np.random.default_rng(0).choice(np.arange(1, n_pts - 1), size=rows - 2, replace=False)
+        idx = np.sort(np.concatenate(([0, n_pts - 1], draw)))
+    sample = np.stack([first if i == 0 else np.asarray(u[int(i)].get_values(), dtype=np.float64).ravel() for i in idx])
+    arrays = {"conv": np.array([mg.conv[1]], dtype=np.float64),
+              "residual_norms": np.asarray(mg.compute_residual(), dtype=np.float64).ravel(),
+              "u_level0_sample": sample, "u_level0_sample_index": idx.astype(np.float64)}
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
+
+
 FP64_MFMA_PEAK_TFLOPS = 78.6  # AMD MI355X datasheet, FP64 matrix (the on-box guide lists no f64 MFMA row)
 
 
@@ -277,6 +304,8 @@ def bench_heat2d(args):
         cycle(1)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t_start
+    if args.dump_outputs:
+        dump_outputs(mg, args.dump_outputs)
     f_runs = mg._f_runs(0)
     n_f = sum(r[1] for r in f_runs)
     be.set_timing(True)
@@ -354,6 +383,8 @@ def bench_advection(args):
         cycle(1)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t_start
+    if args.dump_outputs:
+        dump_outputs(mg, args.dump_outputs)
     f_runs = mg._f_runs(0)
     n_f = sum(r[1] for r in f_runs)
     be.set_timing(True)
@@ -916,7 +947,15 @@ def main():
                          "its residual history against the one-rank run")
     ap.add_argument("--nx2d", type=int, default=512)
     ap.add_argument("--nt2d", type=int, default=16385)
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last of them computed to DIR/<name>.npy (float64, under 64 MB; "
+                         "one GPU, one process)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.gpus > 1 or args.emulate_rank or args.emulate_solve or "WORLD_SIZE" in os.environ
+                              and int(os.environ["WORLD_SIZE"]) > 1):
+        ap.error("--dump-outputs: one GPU, one process only")
     if args.emulate_rank:
         return bench_emulated(args)
     if args.emulate_solve:
@@ -1028,6 +1067,8 @@ def main():
         getattr(be, "materialise", lambda: None)()
         fence()
     elapsed = time.perf_counter() - t_start
+    if args.dump_outputs:
+        dump_outputs(mg, args.dump_outputs)
     stats_timed = {k: comm_stats[k] - stats0[k] for k in comm_stats} if comm_stats is not None and stats0 is not None else None
     # several ranks: the same steps once more through the reference's own loop (mgrit.py:621-646: the stopping value examined after
     # every cycle, a blocking gather) -- what a solve costs when nothing may lag; outside `value`

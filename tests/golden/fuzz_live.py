@@ -1,11 +1,13 @@
-"""Exchange fuzz against the LIVE reference (this container only: imports /root/reference and the thread-backed MPI stand-in):
+"""Exchange fuzz against the LIVE reference (needs the reference's source tree, PYMGRIT_REFERENCE, and imports the thread-backed MPI stand-in):
 python tests/golden/fuzz_live.py LO HI runs tests/fuzz_cases.py seeds LO..HI-1 on the reference and on pymgrit_amd at the same
 rank count and reports every difference (solution values bit for bit, stopping values to 1e-14). Cases in which the reference
 trips over one of its two defects are skipped and counted. Round 1: seeds 7200..9300, 0 differences,
 24 skipped. Nothing here is imported by the product or by the tests."""
 import sys, os
-sys.path.insert(0, '/root/repo/tests/golden/_mpi_stub'); sys.path.insert(0, '/root/reference/src')
-sys.path.insert(0,'/root/repo/tests'); sys.path.insert(0,'/root/repo')
+HERE = os.path.dirname(os.path.abspath(__file__))
+REF = os.environ.get("PYMGRIT_REFERENCE") or sys.exit("set PYMGRIT_REFERENCE to the reference's source tree")
+sys.path.insert(0, os.path.join(HERE, '_mpi_stub')); sys.path.insert(0, os.path.join(REF, 'src'))
+sys.path.insert(0, os.path.dirname(HERE)); sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 import numpy as np, logging, warnings
 warnings.filterwarnings("ignore")
 logging.disable(logging.WARNING)

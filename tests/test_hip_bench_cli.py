@@ -34,6 +34,44 @@ def test_bench_single_gpu_line():
     assert "workload" in b["config"]
 
 
+def test_bench_dump_outputs_match_the_oracle(tmp_path, oracle):
+    """--dump-outputs: the arrays of the last timed step (one leading cycle, --warmup 1, --steps 3) as float64 .npy files under
+    64 MB, the same on a second run with the same arguments, and bit for bit the oracle's after the same five cycles"""
+    if not torch.cuda.is_available():
+        pytest.fail("GPU test selected but no GPU visible")
+    import numpy as np
+    import cases
+    from pymgrit_amd.core.mgrit import time_norm
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nx", "1024", "--nt", "1025", "--steps", "3", "--warmup",
+                            "1", "--no-cpu-baseline", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        b = _last_json(r.stdout)
+        assert b["steps"] == 3 and b["ms_per_step"] > 0
+        names = sorted(os.listdir(out))
+        assert names == ["conv.npy", "residual_norms.npy", "u_level0_sample.npy", "u_level0_sample_index.npy"], names
+        arrs = {n[:-4]: np.load(out / n) for n in names}
+        assert all(a.dtype == np.float64 for a in arrs.values()) and sum(a.nbytes for a in arrs.values()) <= 64 * 2 ** 20
+        dumps.append(arrs)
+    for name, a in dumps[0].items():
+        assert np.array_equal(a, dumps[1][name]), name
+    d = dumps[0]
+    nt0 = 1025
+    t0 = np.linspace(0, 2.0 * (nt0 - 1) / 65536, nt0)
+    op = oracle.OracleProblem([cases.heat_level_spec(1024, g) for g in (t0, t0[::4], t0[::16])], variant=1, cf_iter=1,
+                              nested_iteration=False, max_iter=5, tol=0.0)
+    for it in (0, 1, 1, 1, 1):
+        op.iteration(0, 'V', it, True)
+    want = op.residual_norms()
+    assert np.array_equal(d["residual_norms"], want)
+    assert d["conv"][0] == time_norm(want, None)
+    idx = d["u_level0_sample_index"].astype(np.int64)
+    assert np.array_equal(idx, np.arange(nt0))       # 1025 rows of 1022 values fit: every time point
+    assert np.array_equal(d["u_level0_sample"], op.state("u", 0)[idx])
+
+
 def test_bench_two_ranks_line():
     if not torch.cuda.is_available():
         pytest.fail("GPU test selected but no GPU visible")
