@@ -31,8 +31,11 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <set>
 #include <string>
 #include <thread>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "mgrit_hip.h"
@@ -828,21 +831,10 @@ enum { ROLE_F = 0, ROLE_C = 1, ROLE_C_WEIGHTED = 2, ROLE_FC = 3 };
 // kernel's time is that wave's chain of dependent instructions. Compiled for 1024 threads the kernels keep to 128 VGPRs and spill
 // 100-350 SGPRs and up to 90 VGPRs, whose reloads sit in that chain in every Phi; the TB = 64 instances (512 VGPRs, no VGPR spill)
 // take the launches of such levels and know at compile time that the state is ONE group (heat_solve<.., ONE>): config 2's five
-// sweeps 17-32 us -> 11-20 us each. Same source; the values of the 1024-thread instances (MGRIT_HIP_SMALL_WG=0 launches those
-// everywhere), up to the sign of a zero.
-bool small_wg_instances() {
-    const char *s = std::getenv("MGRIT_HIP_SMALL_WG");      // (read per launch: a test compares the two families in one process)
-    return !(s && s[0] == '0' && s[1] == 0);
-}
+// sweeps 17-32 us -> 11-20 us each. Same source; the values of the 1024-thread instances, up to the sign of a zero.
 // ... and TB = 512 for states of up to 8192 values (workgroups of 128 .. 512 threads): 256 VGPRs, no VGPR spills -- these sweeps are
 // bound by memory bandwidth and by Phi's issue slots, and spill traffic costs both (heat_1d 8192 x 16385: 1.14 -> 1.01 ms per cycle).
-// MGRIT_HIP_MID_WG=0: the 1024-thread instances for them.
-bool mid_wg_instances() {
-    const char *s = std::getenv("MGRIT_HIP_MID_WG");
-    return !(s && s[0] == '0' && s[1] == 0);
-}
-// the instance (its TB) that takes a launch of T threads
-int sweep_tb(int T) { return T == LANES ? (small_wg_instances() ? LANES : 1024) : T <= 512 ? (mid_wg_instances() ? 512 : 1024) : 1024; }
+// The host picks the instance by the launch size (instance_tb).
 
 template <int KIND, int FORCE, bool USE_G, int ROLE, int TB = 1024>
 __global__ void __launch_bounds__(TB) relax_kernel(LevelDev L, const int32_t *__restrict__ run_start,
@@ -1030,7 +1022,7 @@ __global__ void __launch_bounds__(1024) fas_coarse_kernel(LevelDev L, const int3
 // are loaded into LDS once per workgroup instead of twice per C-point: phase 1 applies the fine Phi to all of the
 // workgroup's points (writes u, v and the partial g of the coarse level), phase 2 the coarse Phi (reads u^l_{ip} and the
 // partial g it wrote itself). 4-5 vectors read, 4 written per C-point instead of 11-12.
-template <int KIND, int FORCE, int TB = 1024>   // (TB = 512: the instance for states of up to 8192 values, sweep_tb; 46-100 spilled VGPRs otherwise)
+template <int KIND, int FORCE, int TB = 1024>   // (TB = 512: the instance for states of up to 8192 values, instance_tb; 46-100 spilled VGPRs otherwise)
 __global__ void __launch_bounds__(TB) fas_fused_kernel(LevelDev L, LevelDev Lc, const int32_t *__restrict__ fine_idx,
                                                          const int32_t *__restrict__ prev_idx,
                                                          const int32_t *__restrict__ coarse_idx, int n_items, int use_g) {
@@ -1894,105 +1886,235 @@ size_t blk_smem_bytes(int G) { return smem_bytes(G); }
 constexpr int MAX_G2 = MGRIT_HIP_MAX_N_2PTS / GROUP;  // two-point steppers: waves per half
 size_t smem2_bytes(int G) { return (size_t)2 * (8 * G * LANES + 2 * 512) * sizeof(double2) + (12 * MAX_G + 2 * LANES) * sizeof(double); }
 
-template <typename K>
-int allow_big_lds(K kernel, size_t bytes = smem_bytes(MAX_G)) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+// ---------------------------------------------------------------------------------------------------------------
+// Kernel selection. One function per templated kernel family maps the run-time parameters of a launch (stepper kind, forcing
+// mode, use of g, role, BDF order, launch size) to the compiled instance, and returns null where none exists. The LDS limits
+// (register_lds_limits) are raised by walking the same functions, so every instance a level can launch is covered.
+// ---------------------------------------------------------------------------------------------------------------
+template <int V> using IntC = std::integral_constant<int, V>;
+
+// f(IntC<v>{}) for the run-time value v among the compiled values V0, Vs...; null for any other value
+template <int V0, int... Vs, typename Fn>
+auto pick(int v, Fn f) -> decltype(f(IntC<V0>{})) {
+    decltype(f(IntC<V0>{})) r = v == V0 ? f(IntC<V0>{}) : nullptr;
+    ((r = v == Vs ? f(IntC<Vs>{}) : r), ...);
+    return r;
+}
+
+// the 1-D one-point steppers: Heat1D in forcing modes 0..3 (force_mode), Advection1D without forcing
+template <typename Fn>
+auto by_stepper(int kind, int fm, Fn f) -> decltype(f(IntC<MGRIT_HIP_STEPPER_HEAT1D>{}, IntC<0>{})) {
+    if (kind == MGRIT_HIP_STEPPER_HEAT1D) return pick<0, 1, 2, 3>(fm, [&](auto F) { return f(IntC<MGRIT_HIP_STEPPER_HEAT1D>{}, F); });
+    if (kind == MGRIT_HIP_STEPPER_ADVECTION1D) return pick<0>(fm, [&](auto F) { return f(IntC<MGRIT_HIP_STEPPER_ADVECTION1D>{}, F); });
+    return nullptr;
+}
+
+// the two-point steppers: BDF order 1, 2 x forcing mode 0..2
+template <typename Fn>
+auto by_order(int order, int fm, Fn f) -> decltype(f(IntC<1>{}, IntC<0>{})) {
+    return pick<1, 2>(order, [&](auto O) { return pick<0, 1, 2>(fm, [&](auto F) { return f(O, F); }); });
+}
+
+// The workgroup size TB an instance is compiled for, by the launch size T = lv.dev.T: one wave
+// (families with a TB = 64 instance: the Heat1D sweeps of a cycle), up to 512 threads, else 1024. The smaller instances have no
+// VGPR spills and give the same bits.
+int instance_tb(int T, bool one_wave) { return one_wave && T == LANES ? LANES : T <= 512 ? 512 : 1024; }
+
+// The forcing mode of a level (force_mode: 0 none, 1 one separable term, 2 several, 3 rows) -> the FORCE an instance is compiled for.
+// Heat1D sweeps of a cycle: one term keeps its space factor in LDS (4), several are streamed (2).
+int cycle_force(int fm) { return fm == 0 ? 0 : fm == 1 ? 4 : 2; }
+// cfas_kernel and the two-point wide pass: every term streamed
+int streamed_force(int fm) { return fm == 0 ? 0 : 2; }
+// time-parallel forward solve: one term in LDS (4), the other modes as they are
+int blk_force(int fm) { return fm == 1 ? 4 : fm; }
+// wide Heat1D states: forcing rows (3) as they are, terms streamed
+int wide_force(int fm) { return fm == 0 || fm == 3 ? fm : 2; }
+
+using RelaxFn = decltype(&relax_kernel<MGRIT_HIP_STEPPER_HEAT1D, 0, false, ROLE_F>);
+RelaxFn relax_fn(int kind, int fm, bool use_g, int role, int T) {
+    return by_stepper(kind, fm, [&](auto K, auto F) -> RelaxFn {
+        switch (role) {
+        case ROLE_F: return use_g ? &relax_kernel<K, F, true, ROLE_F> : &relax_kernel<K, F, false, ROLE_F>;
+        case ROLE_C: return use_g ? &relax_kernel<K, F, true, ROLE_C> : &relax_kernel<K, F, false, ROLE_C>;
+        case ROLE_C_WEIGHTED: return use_g ? &relax_kernel<K, F, true, ROLE_C_WEIGHTED> : &relax_kernel<K, F, false, ROLE_C_WEIGHTED>;
+        case ROLE_FC:   // (levels > 0: it reads g)
+            if (!use_g) return nullptr;
+            if constexpr (K == MGRIT_HIP_STEPPER_HEAT1D && F <= 2)
+                return pick<LANES, 512, 1024>(instance_tb(T, true), [&](auto TB) { return &relax_kernel<K, F, true, ROLE_FC, TB>; });
+            return &relax_kernel<K, F, true, ROLE_FC>;
+        }
+        return nullptr;
+    });
+}
+
+using EcfFn = decltype(&ecf_kernel<MGRIT_HIP_STEPPER_HEAT1D, 0, false>);
+EcfFn ecf_fn(int kind, int fm, bool use_g, int T) {
+    return by_stepper(kind, fm, [&](auto K, auto F) -> EcfFn {
+        if constexpr (K == MGRIT_HIP_STEPPER_HEAT1D && F <= 2)
+            if (use_g) return pick<LANES, 512, 1024>(instance_tb(T, true), [&](auto TB) { return &ecf_kernel<K, F, true, TB>; });
+        return use_g ? &ecf_kernel<K, F, true> : &ecf_kernel<K, F, false>;
+    });
+}
+
+auto residual_fn(int kind, int fm) { return by_stepper(kind, fm, [](auto K, auto F) { return &residual_kernel<K, F>; }); }
+auto fas_fine_fn(int kind, int fm) { return by_stepper(kind, fm, [](auto K, auto F) { return &fas_fine_kernel<K, F>; }); }
+auto fas_coarse_fn(int kind, int fm) { return by_stepper(kind, fm, [](auto K, auto F) { return &fas_coarse_kernel<K, F>; }); }
+auto at_fn(int kind, int fm) { return by_stepper(kind, fm, [](auto K, auto F) { return &at_kernel<K, F>; }); }
+
+auto fas_fused_fn(int kind, int fm, int T) {
+    return by_stepper(kind, fm, [&](auto K, auto F) {
+        return pick<512, 1024>(instance_tb(T, false), [&](auto TB) { return &fas_fused_kernel<K, F, TB>; });
+    });
+}
+
+auto fas_fused1_fn(int fm, bool prop, int T) {
+    return pick<0, 2, 4>(cycle_force(fm), [&](auto F) {
+        return pick<LANES, 512, 1024>(instance_tb(T, true), [&](auto TB) {
+            return prop ? &fas_fused1_kernel<F, true, TB> : &fas_fused1_kernel<F, false, TB>;
+        });
+    });
+}
+
+auto cfas_fn(int fm, int T) {
+    return pick<0, 2>(streamed_force(fm), [&](auto F) {
+        return pick<LANES, 512, 1024>(instance_tb(T, true), [&](auto TB) { return &cfas_kernel<F, TB>; });
+    });
+}
+
+// use_g: the coarser levels' form (rows of g, no residual); else level 0's, with the residual
+auto ecfr_fn(int fm, bool use_g, int T) {
+    return pick<0, 2, 4>(cycle_force(fm), [&](auto F) {
+        return pick<LANES, 512, 1024>(instance_tb(T, true), [&](auto TB) {
+            return use_g ? &ecfr_kernel<F, true, false, TB> : &ecfr_kernel<F, false, true, TB>;
+        });
+    });
+}
+
+auto gen_down_fn(int kind, int fm, bool use_g, int T) {
+    return by_stepper(kind, fm, [&](auto K, auto F) {
+        return pick<512, 1024>(instance_tb(T, false), [&](auto TB) {
+            return use_g ? &gen_down_kernel<K, F, true, TB> : &gen_down_kernel<K, F, false, TB>;
+        });
+    });
+}
+
+using GenUpFn = decltype(&gen_up_kernel<MGRIT_HIP_STEPPER_HEAT1D, 0, false, false>);
+GenUpFn gen_up_fn(int kind, int fm, bool use_g, bool res, int T) {
+    if (use_g && res) return nullptr;   // (the residual check belongs to level 0)
+    return by_stepper(kind, fm, [&](auto K, auto F) {
+        return pick<512, 1024>(instance_tb(T, false), [&](auto TB) {
+            return use_g ? &gen_up_kernel<K, F, true, false, TB> : res ? &gen_up_kernel<K, F, false, true, TB> : &gen_up_kernel<K, F, false, false, TB>;
+        });
+    });
+}
+
+// single: the state is one group
+auto chain_fn(int kind, int fm, bool use_g, bool single) {
+    return by_stepper(kind, fm, [&](auto K, auto F) {
+        return use_g ? (single ? &chain_kernel<K, F, true, true> : &chain_kernel<K, F, true, false>)
+                     : (single ? &chain_kernel<K, F, false, true> : &chain_kernel<K, F, false, false>);
+    });
+}
+
+// split: four waves per group (launched for Advection1D states of up to CHAIN_SPLIT_MAX_G groups)
+auto chain_local_fn(int kind, int fm, bool use_g, bool split) {
+    return by_stepper(kind, fm, [&](auto K, auto F) {
+        return use_g ? (split ? &chain_local_kernel<K, F, true, true> : &chain_local_kernel<K, F, true, false>)
+                     : (split ? &chain_local_kernel<K, F, false, true> : &chain_local_kernel<K, F, false, false>);
+    });
+}
+
+auto chain2_fn(int fm, bool use_g) {
+    return pick<0, 1>(fm, [&](auto F) { return use_g ? &chain2_kernel<F, true> : &chain2_kernel<F, false>; });
+}
+
+// the two passes of the six-launch form: the blocks' local solves, and (finish) the second pass from the corrected block ends
+auto blk_pass_fn(int kind, int fm, bool finish) {
+    auto pass = [&](auto K, auto F) { return finish ? &blk_finish_kernel<K, F> : &blk_local_kernel<K, F>; };
+    if (kind == MGRIT_HIP_STEPPER_ADVECTION1D) return pick<0>(fm, [&](auto F) { return pass(IntC<MGRIT_HIP_STEPPER_ADVECTION1D>{}, F); });
+    return pick<0, 2, 3, 4>(kind == MGRIT_HIP_STEPPER_HEAT1D ? blk_force(fm) : -1, [&](auto F) { return pass(IntC<MGRIT_HIP_STEPPER_HEAT1D>{}, F); });
+}
+auto blk_one_fn(int fm) { return pick<0, 2, 3, 4>(blk_force(fm), [](auto F) { return &blk_one_kernel<F>; }); }
+
+auto relax2_fn(int order, int fm, bool use_g, bool weighted) {
+    return by_order(order, fm, [&](auto O, auto F) {
+        return use_g ? (weighted ? &relax2_kernel<O, F, true, true> : &relax2_kernel<O, F, true, false>)
+                     : (weighted ? &relax2_kernel<O, F, false, true> : &relax2_kernel<O, F, false, false>);
+    });
+}
+auto residual2_fn(int order, int fm) { return by_order(order, fm, [](auto O, auto F) { return &residual2_kernel<O, F>; }); }
+auto fas_fine2_fn(int order, int fm) { return by_order(order, fm, [](auto O, auto F) { return &fas_fine2_kernel<O, F>; }); }
+auto fas_coarse2_fn(int order, int fm) { return by_order(order, fm, [](auto O, auto F) { return &fas_coarse2_kernel<O, F>; }); }
+auto at2_fn(int order, int fm) { return by_order(order, fm, [](auto O, auto F) { return &at2_kernel<O, F>; }); }
+
+auto wide_local_fn(int fm) { return pick<0, 2, 3>(wide_force(fm), [](auto F) { return &wide_local_kernel<F>; }); }
+auto wide2_local_fn(int order, int fm) {
+    return pick<1, 2>(order, [&](auto O) { return pick<0, 2>(streamed_force(fm), [&](auto F) { return &wide2_local_kernel<O, F>; }); });
+}
+
+// Launches the selected instance (null: none exists for the level) and checks the launch.
+template <typename... P, typename... A>
+int launch(void (*fn)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, A &&...args) {
+    if (!fn) return fail(MGRIT_HIP_EUNSUPPORTED, "no kernel instance for this level's stepper and forcing");
+    hipLaunchKernelGGL(fn, grid, block, lds, st, std::forward<A>(args)...);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
-// Dispatch tables over the template space: kind (heat1d, advection1d) x forcing mode (0, 1, 2; advection has none).
-#define FOR_EACH_STEPPER(X) X(MGRIT_HIP_STEPPER_HEAT1D, 0) X(MGRIT_HIP_STEPPER_HEAT1D, 1) X(MGRIT_HIP_STEPPER_HEAT1D, 2) \
-    X(MGRIT_HIP_STEPPER_HEAT1D, 3) X(MGRIT_HIP_STEPPER_ADVECTION1D, 0)
-
-// two-point steppers: BDF order (1, 2) x forcing mode (0, 1, 2)
-#define FOR_EACH_2PTS(X) X(1, 0) X(1, 1) X(1, 2) X(2, 0) X(2, 1) X(2, 2)
-
-bool g_attr_done = false;
-int setup_kernel_attrs() {
-    if (g_attr_done) return 0;
-    int rc;
-#define ATTR_RELAX(K, F, G_, R) if ((rc = allow_big_lds(relax_kernel<K, F, G_, R>))) return rc;
-#define ATTR_ALL(K, F)                                                                                              \
-    ATTR_RELAX(K, F, false, ROLE_F) ATTR_RELAX(K, F, true, ROLE_F) ATTR_RELAX(K, F, false, ROLE_C)                   \
-    ATTR_RELAX(K, F, true, ROLE_C) ATTR_RELAX(K, F, false, ROLE_C_WEIGHTED) ATTR_RELAX(K, F, true, ROLE_C_WEIGHTED)  \
-    ATTR_RELAX(K, F, true, ROLE_FC)                                                                                  \
-    if ((rc = allow_big_lds(residual_kernel<K, F>))) return rc;                                                      \
-    if ((rc = allow_big_lds(fas_fine_kernel<K, F>))) return rc;                                                      \
-    if ((rc = allow_big_lds(fas_coarse_kernel<K, F>))) return rc;                                                    \
-    if ((rc = allow_big_lds(fas_fused_kernel<K, F>))) return rc;                                                     \
-    if ((rc = allow_big_lds(fas_fused_kernel<K, F, 512>))) return rc;                                                \
-    if ((rc = allow_big_lds(ecf_kernel<K, F, false>))) return rc;                                                    \
-    if ((rc = allow_big_lds(ecf_kernel<K, F, true>))) return rc;                                                     \
-    if ((rc = allow_big_lds(at_kernel<K, F>))) return rc;                                                           \
-    if ((rc = allow_big_lds(gen_down_kernel<K, F, false>))) return rc;                                               \
-    if ((rc = allow_big_lds(gen_down_kernel<K, F, true>))) return rc;                                                \
-    if ((rc = allow_big_lds(gen_up_kernel<K, F, false, false>))) return rc;                                          \
-    if ((rc = allow_big_lds(gen_up_kernel<K, F, false, true>))) return rc;                                           \
-    if ((rc = allow_big_lds(gen_up_kernel<K, F, true, false>))) return rc;                                           \
-    if ((rc = allow_big_lds(gen_down_kernel<K, F, false, 512>))) return rc;                                          \
-    if ((rc = allow_big_lds(gen_down_kernel<K, F, true, 512>))) return rc;                                           \
-    if ((rc = allow_big_lds(gen_up_kernel<K, F, false, false, 512>))) return rc;                                     \
-    if ((rc = allow_big_lds(gen_up_kernel<K, F, false, true, 512>))) return rc;                                      \
-    if ((rc = allow_big_lds(gen_up_kernel<K, F, true, false, 512>))) return rc;
-    FOR_EACH_STEPPER(ATTR_ALL)
-#define ATTR_CHAIN_LOCAL(K, F)                                                                                       \
-    if ((rc = allow_big_lds(chain_local_kernel<K, F, false>, chain_local_lds(CHAIN_LOCAL_MAX_G)))) return rc;          \
-    if ((rc = allow_big_lds(chain_local_kernel<K, F, true>, chain_local_lds(CHAIN_LOCAL_MAX_G)))) return rc;           \
-    if (K == MGRIT_HIP_STEPPER_ADVECTION1D) {                                                                          \
-        if ((rc = allow_big_lds(chain_local_kernel<K, F, false, true>, chain_local_lds(CHAIN_LOCAL_MAX_G)))) return rc;  \
-        if ((rc = allow_big_lds(chain_local_kernel<K, F, true, true>, chain_local_lds(CHAIN_LOCAL_MAX_G)))) return rc;   \
-    }
-    FOR_EACH_STEPPER(ATTR_CHAIN_LOCAL)
-    if ((rc = allow_big_lds(cfas_kernel<0>))) return rc;
-    if ((rc = allow_big_lds(cfas_kernel<2>))) return rc;
-    if ((rc = allow_big_lds(ecfr_kernel<0, false, true>))) return rc;
-    if ((rc = allow_big_lds(ecfr_kernel<2, false, true>))) return rc;
-    if ((rc = allow_big_lds(ecfr_kernel<4, false, true>))) return rc;
-    if ((rc = allow_big_lds(ecfr_kernel<0, true, false>))) return rc;
-    if ((rc = allow_big_lds(ecfr_kernel<2, true, false>))) return rc;
-    if ((rc = allow_big_lds(ecfr_kernel<4, true, false>))) return rc;
-    if ((rc = allow_big_lds(fas_fused1_kernel<0, false>))) return rc;
-    if ((rc = allow_big_lds(fas_fused1_kernel<2, false>))) return rc;
-    if ((rc = allow_big_lds(fas_fused1_kernel<0, true>))) return rc;
-    if ((rc = allow_big_lds(fas_fused1_kernel<2, true>))) return rc;
-    if ((rc = allow_big_lds(fas_fused1_kernel<4, false>))) return rc;
-    if ((rc = allow_big_lds(fas_fused1_kernel<4, true>))) return rc;
-    if ((rc = allow_big_lds(jump_kernel))) return rc;
-    // the sweeps' instances compiled for 512 threads (sweep_tb): up to 83 KB of LDS
-#define ATTR_MID(F)                                                                                                                    \
-    if ((rc = allow_big_lds(relax_kernel<MGRIT_HIP_STEPPER_HEAT1D, F, true, ROLE_FC, 512>))) return rc;                                \
-    if ((rc = allow_big_lds(ecf_kernel<MGRIT_HIP_STEPPER_HEAT1D, F, true, 512>))) return rc;
-    ATTR_MID(0) ATTR_MID(1) ATTR_MID(2)
-#define ATTR_MID2(F)                                                                                                                   \
-    if ((rc = allow_big_lds(ecfr_kernel<F, false, true, 512>))) return rc;                                                             \
-    if ((rc = allow_big_lds(ecfr_kernel<F, true, false, 512>))) return rc;                                                             \
-    if ((rc = allow_big_lds(fas_fused1_kernel<F, false, 512>))) return rc;                                                             \
-    if ((rc = allow_big_lds(fas_fused1_kernel<F, true, 512>))) return rc;
-    ATTR_MID2(0) ATTR_MID2(2) ATTR_MID2(4)
-    if ((rc = allow_big_lds(cfas_kernel<0, 512>))) return rc;
-    if ((rc = allow_big_lds(cfas_kernel<2, 512>))) return rc;
-#define ATTR_BLK(F)                                                                                                   \
-    if ((rc = allow_big_lds(blk_local_kernel<MGRIT_HIP_STEPPER_HEAT1D, F>, blk_smem_bytes(MAX_G)))) return rc;        \
-    if ((rc = allow_big_lds(blk_finish_kernel<MGRIT_HIP_STEPPER_HEAT1D, F>, blk_smem_bytes(MAX_G)))) return rc;
-    ATTR_BLK(0) ATTR_BLK(2) ATTR_BLK(3) ATTR_BLK(4)
-    if ((rc = allow_big_lds(blk_local_kernel<MGRIT_HIP_STEPPER_ADVECTION1D, 0>, blk_smem_bytes(MAX_G)))) return rc;
-    if ((rc = allow_big_lds(blk_finish_kernel<MGRIT_HIP_STEPPER_ADVECTION1D, 0>, blk_smem_bytes(MAX_G)))) return rc;
-    if ((rc = allow_big_lds(adv_fft_rows_kernel, (size_t)BLK_FOURIER_MAX_N * sizeof(double2)))) return rc;
-    if ((rc = allow_big_lds(adv_dft_fwd_kernel, (size_t)BLK_FOURIER_MAX_N * sizeof(double2)))) return rc;
-    if ((rc = allow_big_lds(adv_dft_inv_kernel, (size_t)BLK_FOURIER_MAX_N * sizeof(double2)))) return rc;
-#define ATTR_2PTS(O, F)                                                                                              \
-    if ((rc = allow_big_lds(relax2_kernel<O, F, false, false>, smem2_bytes(MAX_G2)))) return rc;                     \
-    if ((rc = allow_big_lds(relax2_kernel<O, F, true, false>, smem2_bytes(MAX_G2)))) return rc;                      \
-    if ((rc = allow_big_lds(relax2_kernel<O, F, false, true>, smem2_bytes(MAX_G2)))) return rc;                      \
-    if ((rc = allow_big_lds(relax2_kernel<O, F, true, true>, smem2_bytes(MAX_G2)))) return rc;                       \
-    if ((rc = allow_big_lds(residual2_kernel<O, F>, smem2_bytes(MAX_G2)))) return rc;                                \
-    if ((rc = allow_big_lds(fas_fine2_kernel<O, F>, smem2_bytes(MAX_G2)))) return rc;                                \
-    if ((rc = allow_big_lds(fas_coarse2_kernel<O, F>, smem2_bytes(MAX_G2)))) return rc;                              \
-    if ((rc = allow_big_lds(at2_kernel<O, F>, smem2_bytes(MAX_G2)))) return rc;
-    FOR_EACH_2PTS(ATTR_2PTS)
-    if ((rc = allow_big_lds(jump2_kernel, smem2_bytes(MAX_G2)))) return rc;
-    g_attr_done = true;
-    return 0;
+// Raises the dynamic-LDS limit (64 KB by default) of every instance a selector can return to the most its family asks for. The
+// families that launch with little or no dynamic LDS -- chain, chain2, blk_one, the wide passes -- are not walked. Runs once per
+// process, before any level is described: not at a first launch, which may sit inside a stream capture.
+int register_lds_limits() {
+    static const std::string err = [] {
+        std::set<const void *> done;   // (the walks below reach most instances more than once)
+        int rc = 0;
+        auto allow = [&](auto fn, size_t bytes) {
+            if (rc || !fn || !done.insert(reinterpret_cast<const void *>(fn)).second) return;
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+            if (e != hipSuccess) rc = fail(MGRIT_HIP_EHIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize, %zu): %s", bytes, hipGetErrorString(e));
+        };
+        const size_t big = smem_bytes(MAX_G), big2 = smem2_bytes(MAX_G2), chain = chain_local_lds(CHAIN_LOCAL_MAX_G);
+        for (int fm = 0; fm <= 3; ++fm)
+            for (bool g : {false, true})
+                for (int T : {LANES, 512, 1024}) {
+                    for (int kind : {MGRIT_HIP_STEPPER_HEAT1D, MGRIT_HIP_STEPPER_ADVECTION1D}) {
+                        for (int role : {ROLE_F, ROLE_C, ROLE_C_WEIGHTED, ROLE_FC}) allow(relax_fn(kind, fm, g, role, T), big);
+                        allow(ecf_fn(kind, fm, g, T), big);
+                        allow(fas_fused_fn(kind, fm, T), big);
+                        allow(gen_down_fn(kind, fm, g, T), big);
+                        allow(gen_up_fn(kind, fm, g, false, T), big);
+                        allow(gen_up_fn(kind, fm, g, true, T), big);
+                        allow(chain_local_fn(kind, fm, g, false), chain);
+                        allow(chain_local_fn(kind, fm, g, true), chain);
+                    }
+                    allow(fas_fused1_fn(fm, g, T), big);   // (g walks PROP)
+                    allow(cfas_fn(fm, T), big);
+                    allow(ecfr_fn(fm, g, T), big);
+                }
+        for (int kind : {MGRIT_HIP_STEPPER_HEAT1D, MGRIT_HIP_STEPPER_ADVECTION1D})
+            for (int fm = 0; fm <= 3; ++fm) {
+                allow(residual_fn(kind, fm), big);
+                allow(fas_fine_fn(kind, fm), big);
+                allow(fas_coarse_fn(kind, fm), big);
+                allow(at_fn(kind, fm), big);
+                allow(blk_pass_fn(kind, fm, false), blk_smem_bytes(MAX_G));
+                allow(blk_pass_fn(kind, fm, true), blk_smem_bytes(MAX_G));
+            }
+        for (int order : {1, 2})
+            for (int fm = 0; fm <= 2; ++fm) {
+                for (bool g : {false, true})
+                    for (bool w : {false, true}) allow(relax2_fn(order, fm, g, w), big2);
+                allow(residual2_fn(order, fm), big2);
+                allow(fas_fine2_fn(order, fm), big2);
+                allow(fas_coarse2_fn(order, fm), big2);
+                allow(at2_fn(order, fm), big2);
+            }
+        allow(&jump_kernel, big);
+        allow(&jump2_kernel, big2);
+        for (auto fn : {&adv_fft_rows_kernel, &adv_dft_fwd_kernel, &adv_dft_inv_kernel}) allow(fn, (size_t)BLK_FOURIER_MAX_N * sizeof(double2));
+        return rc ? g_err : std::string();
+    }();
+    return err.empty() ? 0 : fail(MGRIT_HIP_EHIP, "%s", err.c_str());
 }
 
 int check_level(mgrit_hip_engine *e, int lvl, bool need_set = true) {
@@ -2012,7 +2134,7 @@ int level_common(mgrit_hip_engine *e, int lvl, int kind, int n_pts, const double
     if (ld != mgrit_hip_row_stride(n)) return fail(MGRIT_HIP_EINVAL, "ld=%d must equal mgrit_hip_row_stride(n=%d)=%d", ld, n, mgrit_hip_row_stride(n));
     if (n_pts < 0 || (n_pts > 0 && !t_local)) return fail(MGRIT_HIP_EINVAL, "bad local time grid");
     if (K < 0 || K > 8 || (K > 0 && (!s || (n_pts > 0 && !tau)))) return fail(MGRIT_HIP_EINVAL, "bad forcing description (K=%d)", K);
-    if ((rc = setup_kernel_attrs())) return rc;
+    if ((rc = register_lds_limits())) return rc;
     Level &lv = e->L[lvl];
     if (lv.set) return fail(MGRIT_HIP_EINVAL, "level %d already described", lvl);
     const int G = (n + GROUP - 1) / GROUP, T = G * LANES;
@@ -2120,7 +2242,7 @@ int level_heat1d_2pts(mgrit_hip_engine *e, int lvl, int n_pts, const double *t_l
     if (order != 1 && order != 2) return fail(MGRIT_HIP_EINVAL, "BDF order must be 1 or 2");
     if (n_pts < 0 || (n_pts > 0 && !t_local)) return fail(MGRIT_HIP_EINVAL, "bad local time grid");
     if (K < 0 || K > 8 || (K > 0 && (!s || (n_pts > 0 && (!tau || !tau2))))) return fail(MGRIT_HIP_EINVAL, "bad forcing description (K=%d)", K);
-    if ((rc = setup_kernel_attrs())) return rc;
+    if ((rc = register_lds_limits())) return rc;
     Level &lv = e->L[lvl];
     if (lv.set) return fail(MGRIT_HIP_EINVAL, "level %d already described", lvl);
     const int G = (n + GROUP - 1) / GROUP, T = G * LANES;
@@ -2642,12 +2764,6 @@ int check_bound(const Level &lv, bool need_vg) {
 // grid of persistent workgroups: as many as stay resident on the chip (LDS- and thread-limited), at most one per item
 bool is_2pts(const Level &lv) { return lv.dev.kind == MGRIT_HIP_STEPPER_HEAT1D_2PTS; }
 
-// MGRIT_HIP_GEN_512=0: the general whole-level passes in their 1024-thread instances everywhere (measurement and comparison; same bits)
-bool gen_half_instances() {
-    const char *s = std::getenv("MGRIT_HIP_GEN_512");
-    return !(s && s[0] == '0' && s[1] == 0);
-}
-
 int wgs_per_cu(const Level &lv) {
     const size_t lds = is_2pts(lv) ? smem2_bytes(lv.G) : smem_bytes(lv.G, lv.dev.kind);
     return std::max(1, std::min((int)(160 * 1024 / lds), 2048 / lv.dev.T));
@@ -2716,10 +2832,8 @@ int wide_phi(mgrit_hip_engine *e, Level &lv, const H2DPlan &pl, const double *in
     const int fm = force_mode(lv);
     if (lv.dev.kind == MGRIT_HIP_STEPPER_HEAT1D_2PTS) {   // two half-solves; the second one's scanned rows and carries are what wide_finish takes
         for (int hf = 0; hf < 2; ++hf) {
-#define WIDE2_LOCAL(O_, F_)                                                                                                         \
-    if (lv.order == O_ && (fm != 0) == (F_ != 0))                                                                                  \
-        hipLaunchKernelGGL((wide2_local_kernel<O_, F_>), grid, block, 0, e->stream, lv.dev, hf, in_slab, pl.d_in, pl.d_step, h.T0, h.W, h.tot);
-            WIDE2_LOCAL(1, 0) WIDE2_LOCAL(1, 2) WIDE2_LOCAL(2, 0) WIDE2_LOCAL(2, 2)
+            if ((rc = launch(wide2_local_fn(lv.order, fm), grid, block, 0, e->stream, lv.dev, hf, in_slab, pl.d_in, pl.d_step, h.T0, h.W, h.tot)))
+                return rc;
             hipLaunchKernelGGL(wide_carry_kernel, dim3(pl.count), dim3(64), 0, e->stream, lv.dev, pl.d_step, h.tot, h.car, h.z0, hf);
             if (hf == 0)
                 hipLaunchKernelGGL(wide2_finish_kernel, grid, block, 0, e->stream, lv.dev, 0, h.W, pl.d_step, h.car, h.z0, h.T0, (double *)nullptr, 0,
@@ -2729,9 +2843,7 @@ int wide_phi(mgrit_hip_engine *e, Level &lv, const H2DPlan &pl, const double *in
         HIP_TRY(hipGetLastError());
         return 0;
     }
-    if (fm == 0) hipLaunchKernelGGL((wide_local_kernel<0>), grid, block, 0, e->stream, lv.dev, in_slab, pl.d_in, pl.d_step, h.W, h.tot);
-    else if (fm == 3) hipLaunchKernelGGL((wide_local_kernel<3>), grid, block, 0, e->stream, lv.dev, in_slab, pl.d_in, pl.d_step, h.W, h.tot);
-    else hipLaunchKernelGGL((wide_local_kernel<2>), grid, block, 0, e->stream, lv.dev, in_slab, pl.d_in, pl.d_step, h.W, h.tot);
+    if ((rc = launch(wide_local_fn(fm), grid, block, 0, e->stream, lv.dev, in_slab, pl.d_in, pl.d_step, h.W, h.tot))) return rc;
     hipLaunchKernelGGL(wide_carry_kernel, dim3(pl.count), dim3(64), 0, e->stream, lv.dev, pl.d_step, h.tot, h.car, h.z0, -1);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -2853,31 +2965,6 @@ int no_wide(const Level &a, const Level *b, const char *what) {
     return 0;
 }
 
-// two-point kernels: template space BDF order x forcing mode
-#define LAUNCH2_CASE(kernel, O_, F_, lv, grid, ...)                                                              \
-    if ((lv).order == O_ && force_mode(lv) == F_)                                                                 \
-        hipLaunchKernelGGL((kernel<O_, F_>), dim3(grid), dim3((lv).dev.T), smem2_bytes((lv).G), e->stream, __VA_ARGS__);
-#define LAUNCH2_BY_ORDER(kernel, lv, grid, ...)                                                                  \
-    do {                                                                                                         \
-        LAUNCH2_CASE(kernel, 1, 0, lv, grid, __VA_ARGS__) LAUNCH2_CASE(kernel, 1, 1, lv, grid, __VA_ARGS__)       \
-        LAUNCH2_CASE(kernel, 1, 2, lv, grid, __VA_ARGS__) LAUNCH2_CASE(kernel, 2, 0, lv, grid, __VA_ARGS__)       \
-        LAUNCH2_CASE(kernel, 2, 1, lv, grid, __VA_ARGS__) LAUNCH2_CASE(kernel, 2, 2, lv, grid, __VA_ARGS__)       \
-        HIP_TRY(hipGetLastError());                                                                              \
-    } while (0)
-
-#define LAUNCH_CASE(kernel, K_, F_, lv, grid, ...)                                                               \
-    if ((lv).dev.kind == K_ && force_mode(lv) == F_)                                                              \
-        hipLaunchKernelGGL((kernel<K_, F_>), dim3(grid), dim3((lv).dev.T), smem_bytes((lv).G, (lv).dev.kind), e->stream, __VA_ARGS__);
-#define LAUNCH_BY_KIND(kernel, lv, grid, ...)                                                                    \
-    do {                                                                                                         \
-        LAUNCH_CASE(kernel, MGRIT_HIP_STEPPER_HEAT1D, 0, lv, grid, __VA_ARGS__)                                   \
-        LAUNCH_CASE(kernel, MGRIT_HIP_STEPPER_HEAT1D, 1, lv, grid, __VA_ARGS__)                                   \
-        LAUNCH_CASE(kernel, MGRIT_HIP_STEPPER_HEAT1D, 2, lv, grid, __VA_ARGS__)                                   \
-        LAUNCH_CASE(kernel, MGRIT_HIP_STEPPER_HEAT1D, 3, lv, grid, __VA_ARGS__)                                   \
-        LAUNCH_CASE(kernel, MGRIT_HIP_STEPPER_ADVECTION1D, 0, lv, grid, __VA_ARGS__)                              \
-        HIP_TRY(hipGetLastError());                                                                              \
-    } while (0)
-
 int ensure_sched(mgrit_hip_engine *e) {
     if (e->sched) return 0;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -2957,18 +3044,14 @@ bool blk_one_launch_enabled() {
 
 int blk_launch(mgrit_hip_engine *e, Level &lv, int phases) {
     BlkDev &bk = lv.blk;
-    const int fm = force_mode(lv), F = fm == 1 ? 4 : fm;
+    const int fm = force_mode(lv);
+    int rc;
     const size_t lds = blk_smem_bytes(lv.G);
     if (lv.blk_err && *lv.blk_err)
         return fail(MGRIT_HIP_EHIP, "time-parallel forward solve in one launch: a device-wide barrier gave up (workgroups not resident together)");
     if (phases == 7 && lv.blk_qt && bk.first_real && !bk.project_last) {
-        const dim3 grid(bk.B), block(LANES);
-        if (F == 0) hipLaunchKernelGGL((blk_one_kernel<0>), grid, block, lds, e->stream, lv.dev, bk, reinterpret_cast<const double2 *>(lv.blk_qt), lv.blk_sync, lv.blk_err);
-        else if (F == 2) hipLaunchKernelGGL((blk_one_kernel<2>), grid, block, lds, e->stream, lv.dev, bk, reinterpret_cast<const double2 *>(lv.blk_qt), lv.blk_sync, lv.blk_err);
-        else if (F == 3) hipLaunchKernelGGL((blk_one_kernel<3>), grid, block, lds, e->stream, lv.dev, bk, reinterpret_cast<const double2 *>(lv.blk_qt), lv.blk_sync, lv.blk_err);
-        else hipLaunchKernelGGL((blk_one_kernel<4>), grid, block, lds, e->stream, lv.dev, bk, reinterpret_cast<const double2 *>(lv.blk_qt), lv.blk_sync, lv.blk_err);
-        HIP_TRY(hipGetLastError());
-        return 0;
+        return launch(blk_one_fn(fm), dim3(bk.B), dim3(LANES), lds, e->stream, lv.dev, bk, reinterpret_cast<const double2 *>(lv.blk_qt),
+                      lv.blk_sync, lv.blk_err);
     }
     const int cap = 256 * blk_wgs_per_cu(lv);
     const dim3 block(lv.dev.T);
@@ -2978,12 +3061,7 @@ int blk_launch(mgrit_hip_engine *e, Level &lv, int phases) {
     const size_t dft_lds = (size_t)n * sizeof(double2);                          // the table of all n roots of unity
     const unsigned dft_gy = (unsigned)(((n + 15) / 16 + DFT_WAVES - 1) / DFT_WAVES);   // DFT_WAVES tiles of 16 per workgroup
     if (phases & 1) {
-        const dim3 grid(std::min(bk.B, cap));
-        if (adv) hipLaunchKernelGGL((blk_local_kernel<MGRIT_HIP_STEPPER_ADVECTION1D, 0>), grid, block, lds, e->stream, lv.dev, bk);
-        else if (F == 0) hipLaunchKernelGGL((blk_local_kernel<MGRIT_HIP_STEPPER_HEAT1D, 0>), grid, block, lds, e->stream, lv.dev, bk);
-        else if (F == 2) hipLaunchKernelGGL((blk_local_kernel<MGRIT_HIP_STEPPER_HEAT1D, 2>), grid, block, lds, e->stream, lv.dev, bk);
-        else if (F == 3) hipLaunchKernelGGL((blk_local_kernel<MGRIT_HIP_STEPPER_HEAT1D, 3>), grid, block, lds, e->stream, lv.dev, bk);
-        else hipLaunchKernelGGL((blk_local_kernel<MGRIT_HIP_STEPPER_HEAT1D, 4>), grid, block, lds, e->stream, lv.dev, bk);
+        if ((rc = launch(blk_pass_fn(lv.dev.kind, fm, false), dim3(std::min(bk.B, cap)), block, lds, e->stream, lv.dev, bk))) return rc;
         const int cnt = bk.B - 1 + (bk.project_last ? 1 : 0);     // blocks whose amplitudes the recurrence reads
         if (adv) {   // what_b = FFT(W_b)
             if (cnt > 0 && dft) hipLaunchKernelGGL(adv_dft_fwd_kernel, dim3((cnt + 15) / 16, dft_gy), dim3(64 * DFT_WAVES), dft_lds, e->stream, lv.dev, bk, 0, cnt);
@@ -3012,13 +3090,7 @@ int blk_launch(mgrit_hip_engine *e, Level &lv, int phases) {
         }
         else hipLaunchKernelGGL(blk_correct_kernel, dim3((bk.B + 15) / 16, lv.dev.ld / 64), dim3(64), 0, e->stream, lv.dev, bk,
                                 bk.B - (bk.project_last ? 1 : 0));
-        const int items = bk.B;
-        const dim3 grid(std::min(items, cap));
-        if (adv) hipLaunchKernelGGL((blk_finish_kernel<MGRIT_HIP_STEPPER_ADVECTION1D, 0>), grid, block, lds, e->stream, lv.dev, b2);
-        else if (F == 0) hipLaunchKernelGGL((blk_finish_kernel<MGRIT_HIP_STEPPER_HEAT1D, 0>), grid, block, lds, e->stream, lv.dev, b2);
-        else if (F == 2) hipLaunchKernelGGL((blk_finish_kernel<MGRIT_HIP_STEPPER_HEAT1D, 2>), grid, block, lds, e->stream, lv.dev, b2);
-        else if (F == 3) hipLaunchKernelGGL((blk_finish_kernel<MGRIT_HIP_STEPPER_HEAT1D, 3>), grid, block, lds, e->stream, lv.dev, b2);
-        else hipLaunchKernelGGL((blk_finish_kernel<MGRIT_HIP_STEPPER_HEAT1D, 4>), grid, block, lds, e->stream, lv.dev, b2);
+        if ((rc = launch(blk_pass_fn(lv.dev.kind, fm, true), dim3(std::min(bk.B, cap)), block, lds, e->stream, lv.dev, b2))) return rc;
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -3577,17 +3649,8 @@ int mgrit_hip_relax(mgrit_hip_engine *e, int lvl, int runs_id, int mode, double 
     if (is_2pts(lv)) {
         const bool use_g = lvl > 0, weighted = mode == MGRIT_HIP_RELAX_C && weight_c != 1.0;
         const double w = weight_c, w1 = 1.0 - weight_c;
-        const dim3 grid(persistent_grid(lv, rl->n)), block(lv.dev.T);
-        const int fm = force_mode(lv);
-#define RELAX2_CASE(O, F, G_, W_)                                                                                  \
-    if (lv.order == O && fm == F && use_g == G_ && weighted == W_)                                                  \
-        hipLaunchKernelGGL((relax2_kernel<O, F, G_, W_>), grid, block, smem2_bytes(lv.G), e->stream, lv.dev, rl->d_start, \
-                           rl->d_len, rl->n, w, w1);
-#define RELAX2_CASES(O, F) RELAX2_CASE(O, F, false, false) RELAX2_CASE(O, F, true, false) RELAX2_CASE(O, F, false, true) \
-    RELAX2_CASE(O, F, true, true)
-        FOR_EACH_2PTS(RELAX2_CASES)
-        HIP_TRY(hipGetLastError());
-        return 0;
+        return launch(relax2_fn(lv.order, force_mode(lv), use_g, weighted), dim3(persistent_grid(lv, rl->n)), dim3(lv.dev.T),
+                      smem2_bytes(lv.G), e->stream, lv.dev, rl->d_start, rl->d_len, rl->n, w, w1);
     }
     if (whole_chain) {
         if (lv.blk.r > 0) {
@@ -3615,12 +3678,9 @@ int mgrit_hip_relax(mgrit_hip_engine *e, int lvl, int runs_id, int mode, double 
             if (lv.dev.chT && lv.chain_overlapped && use_g && fm <= 1 && !plain_chain()) {   // (level 0 = a one-level hierarchy: plain)   // one coefficient set, several groups: the overlapped chain
                 const int resume = (lv.chain_resume && r == 0) ? 1 : 0;
                 lv.chain_resume = false;
-                double *state = lv.chain_state;
-                if (fm == 0 && !use_g) hipLaunchKernelGGL((chain2_kernel<0, false>), grid, block, 0, e->stream, lv.dev, st, ln, e->chain_gran, e->chain_err, state, resume, e->sched, sel);
-                if (fm == 0 && use_g) hipLaunchKernelGGL((chain2_kernel<0, true>), grid, block, 0, e->stream, lv.dev, st, ln, e->chain_gran, e->chain_err, state, resume, e->sched, sel);
-                if (fm == 1 && !use_g) hipLaunchKernelGGL((chain2_kernel<1, false>), grid, block, 0, e->stream, lv.dev, st, ln, e->chain_gran, e->chain_err, state, resume, e->sched, sel);
-                if (fm == 1 && use_g) hipLaunchKernelGGL((chain2_kernel<1, true>), grid, block, 0, e->stream, lv.dev, st, ln, e->chain_gran, e->chain_err, state, resume, e->sched, sel);
-                HIP_TRY(hipGetLastError());
+                if ((rc = launch(chain2_fn(fm, use_g), grid, block, 0, e->stream, lv.dev, st, ln, e->chain_gran, e->chain_err, lv.chain_state,
+                                 resume, e->sched, sel)))
+                    return rc;
 #ifdef MGRIT_EXPERIMENT_COUNT_SPINS
                 HIP_TRY(hipStreamSynchronize(e->stream));
                 std::fprintf(stderr, "chain2 polls per step:");
@@ -3631,26 +3691,15 @@ int mgrit_hip_relax(mgrit_hip_engine *e, int lvl, int runs_id, int mode, double 
             }
             lv.chain_resume = false;
             if (lv.G >= 2 && lv.G <= chain_local_max_g()) {   // a few groups: all workers in one workgroup, totals through LDS
-#define CHAIN_LOCAL_CASE(K, F, G_)                                                                            \
-    if (lv.dev.kind == K && fm == F && use_g == G_)                                                            \
-    {                                                                                                          \
-        if (K == MGRIT_HIP_STEPPER_ADVECTION1D && lv.G <= CHAIN_SPLIT_MAX_G)                                   \
-            hipLaunchKernelGGL((chain_local_kernel<K, F, G_, true>), dim3(1), dim3(4 * lv.G * LANES), chain_local_lds(lv.G), e->stream, lv.dev, st, ln, e->chain_err); \
-        else                                                                                                   \
-            hipLaunchKernelGGL((chain_local_kernel<K, F, G_, false>), dim3(1), dim3(2 * lv.G * LANES), chain_local_lds(lv.G), e->stream, lv.dev, st, ln, e->chain_err); \
-    }
-#define CHAIN_LOCAL_CASES(K, F) CHAIN_LOCAL_CASE(K, F, false) CHAIN_LOCAL_CASE(K, F, true)
-                FOR_EACH_STEPPER(CHAIN_LOCAL_CASES)
-                HIP_TRY(hipGetLastError());
+                const bool split = lv.dev.kind == MGRIT_HIP_STEPPER_ADVECTION1D && lv.G <= CHAIN_SPLIT_MAX_G;
+                if ((rc = launch(chain_local_fn(lv.dev.kind, fm, use_g, split), dim3(1), dim3((split ? 4 : 2) * lv.G * LANES), chain_local_lds(lv.G),
+                                 e->stream, lv.dev, st, ln, e->chain_err)))
+                    return rc;
                 continue;
             }
-#define CHAIN_CASE(K, F, G_, S_)                                                                              \
-    if (lv.dev.kind == K && fm == F && use_g == G_ && (lv.G == 1) == S_)                                       \
-        hipLaunchKernelGGL((chain_kernel<K, F, G_, S_>), grid, dim3(3 * LANES), 0, e->stream, lv.dev, st, ln, e->chain_gran, e->chain_err, e->sched, sel);
-#define CHAIN_CASES(K, F) CHAIN_CASE(K, F, false, false) CHAIN_CASE(K, F, true, false) CHAIN_CASE(K, F, false, true) \
-    CHAIN_CASE(K, F, true, true)
-            FOR_EACH_STEPPER(CHAIN_CASES)
-            HIP_TRY(hipGetLastError());
+            if ((rc = launch(chain_fn(lv.dev.kind, fm, use_g, lv.G == 1), grid, dim3(3 * LANES), 0, e->stream, lv.dev, st, ln, e->chain_gran,
+                             e->chain_err, e->sched, sel)))
+                return rc;
         }
         return 0;
     }
@@ -3659,30 +3708,9 @@ int mgrit_hip_relax(mgrit_hip_engine *e, int lvl, int runs_id, int mode, double 
         const int role = mode == MGRIT_HIP_RELAX_F ? ROLE_F : mode == MGRIT_HIP_RELAX_FC ? ROLE_FC : (weight_c != 1.0) ? ROLE_C_WEIGHTED : ROLE_C;
         const double w = weight_c, w1 = 1.0 - weight_c;
         // persistent grid: as many workgroups as stay resident (LDS- and thread-limited), at most one per run
-        const size_t lds = smem_bytes(lv.G, lv.dev.kind);
-        const dim3 grid(persistent_grid(lv, rl->n)), block(lv.dev.T);
-        const int fm = force_mode(lv);
-#define RELAX_CASE(K, F, G_, R)                                                                                    \
-    if (lv.dev.kind == K && fm == F && use_g == G_ && role == R)                                                    \
-        hipLaunchKernelGGL((relax_kernel<K, F, G_, R>), grid, block, lds, e->stream, sched_dev(e, lv), rl->d_start, rl->d_len, rl->n, \
-                           w, w1);
-#define RELAX_CASES(K, F)                                                                                          \
-    RELAX_CASE(K, F, false, ROLE_F) RELAX_CASE(K, F, true, ROLE_F) RELAX_CASE(K, F, false, ROLE_C)                  \
-    RELAX_CASE(K, F, true, ROLE_C) RELAX_CASE(K, F, false, ROLE_C_WEIGHTED) RELAX_CASE(K, F, true, ROLE_C_WEIGHTED) \
-    RELAX_CASE(K, F, true, ROLE_FC)
-        // (one-group Heat1D levels: the F+C pass of a cycle compiled for ONE wave per workgroup, see small_wg_instances)
-        const int tb = sweep_tb(lv.dev.T);
-        if (tb != 1024 && lv.dev.kind == MGRIT_HIP_STEPPER_HEAT1D && use_g && role == ROLE_FC && fm <= 2) {
-#define RELAX_SMALL(F, TB_)                                                                                                           \
-    if (fm == F && tb == TB_) hipLaunchKernelGGL((relax_kernel<MGRIT_HIP_STEPPER_HEAT1D, F, true, ROLE_FC, TB_>), grid, block, lds, e->stream, \
-                                                 sched_dev(e, lv), rl->d_start, rl->d_len, rl->n, w, w1);
-            RELAX_SMALL(0, LANES) RELAX_SMALL(1, LANES) RELAX_SMALL(2, LANES) RELAX_SMALL(0, 512) RELAX_SMALL(1, 512) RELAX_SMALL(2, 512)
-        } else {
-            FOR_EACH_STEPPER(RELAX_CASES)
-        }
-        HIP_TRY(hipGetLastError());
+        return launch(relax_fn(lv.dev.kind, force_mode(lv), use_g, role, lv.dev.T), dim3(persistent_grid(lv, rl->n)), dim3(lv.dev.T),
+                      smem_bytes(lv.G, lv.dev.kind), e->stream, sched_dev(e, lv), rl->d_start, rl->d_len, rl->n, w, w1);
     }
-    return 0;
 }
 
 int mgrit_hip_residual(mgrit_hip_engine *e, int lvl, int runs_id, double *sumsq_out) {
@@ -3696,9 +3724,11 @@ int mgrit_hip_residual(mgrit_hip_engine *e, int lvl, int runs_id, double *sumsq_
     Timed timed(e, MGRIT_HIP_T_RESIDUAL, lvl);
     if (lv.h2d) return h2d_points_sumsq(e, lvl, rl, nullptr, sumsq_out);
     if (lv.wide) return wide_points_sumsq(e, lvl, rl, nullptr, sumsq_out);
-    if (is_2pts(lv)) LAUNCH2_BY_ORDER(residual2_kernel, lv, persistent_grid(lv, rl->n), lv.dev, rl->d_start, rl->n, sumsq_out);
-    else LAUNCH_BY_KIND(residual_kernel, lv, persistent_grid(lv, rl->n), sched_dev(e, lv), rl->d_start, rl->n, sumsq_out);
-    return 0;
+    const dim3 grid(persistent_grid(lv, rl->n)), block(lv.dev.T);
+    if (is_2pts(lv))
+        return launch(residual2_fn(lv.order, force_mode(lv)), grid, block, smem2_bytes(lv.G), e->stream, lv.dev, rl->d_start, rl->n, sumsq_out);
+    return launch(residual_fn(lv.dev.kind, force_mode(lv)), grid, block, smem_bytes(lv.G, lv.dev.kind), e->stream, sched_dev(e, lv),
+                  rl->d_start, rl->n, sumsq_out);
 }
 
 int mgrit_hip_jump(mgrit_hip_engine *e, int lvl, int runs_id, const double *prev, double *sumsq_out) {
@@ -3712,12 +3742,8 @@ int mgrit_hip_jump(mgrit_hip_engine *e, int lvl, int runs_id, const double *prev
     Timed timed(e, MGRIT_HIP_T_JUMP, lvl);
     if (lv.h2d) return h2d_points_sumsq(e, lvl, rl, prev, sumsq_out);
     if (lv.wide) return wide_points_sumsq(e, lvl, rl, prev, sumsq_out);
-    if (is_2pts(lv))
-        hipLaunchKernelGGL(jump2_kernel, dim3(rl->n), dim3(lv.dev.T), smem2_bytes(lv.G), e->stream, lv.dev, rl->d_start, prev, sumsq_out);
-    else
-        hipLaunchKernelGGL(jump_kernel, dim3(rl->n), dim3(lv.dev.T), smem_bytes(lv.G, lv.dev.kind), e->stream, lv.dev, rl->d_start, prev, sumsq_out);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    if (is_2pts(lv)) return launch(&jump2_kernel, dim3(rl->n), dim3(lv.dev.T), smem2_bytes(lv.G), e->stream, lv.dev, rl->d_start, prev, sumsq_out);
+    return launch(&jump_kernel, dim3(rl->n), dim3(lv.dev.T), smem_bytes(lv.G, lv.dev.kind), e->stream, lv.dev, rl->d_start, prev, sumsq_out);
 }
 
 static int caller_transfer(const Level &lf, int lvl) {
@@ -3779,8 +3805,8 @@ int mgrit_hip_fas_fine_rows(mgrit_hip_engine *e, int lvl, int pairs_id, double *
     if ((rc = no_wide(e->L[lvl], &e->L[lvl + 1], "FAS right-hand side around a caller's transfer"))) return rc;
     if (pl->n == 0) return 0;
     Timed timed(e, MGRIT_HIP_T_FAS_RHS, lvl);
-    LAUNCH_BY_KIND(fas_fine_kernel, lf, pl->n, lf.dev, pl->d_fine, pl->d_iota, rows, ld_rows, lvl > 0 ? 1 : 0);
-    return 0;
+    return launch(fas_fine_fn(lf.dev.kind, force_mode(lf)), dim3(pl->n), dim3(lf.dev.T), smem_bytes(lf.G, lf.dev.kind), e->stream, lf.dev,
+                  pl->d_fine, pl->d_iota, rows, ld_rows, lvl > 0 ? 1 : 0);
 }
 
 int mgrit_hip_fas_coarse(mgrit_hip_engine *e, int lvl, int pairs_id) {
@@ -3806,8 +3832,8 @@ int mgrit_hip_fas_coarse(mgrit_hip_engine *e, int lvl, int pairs_id) {
     if ((rc = no_wide(e->L[lvl], &e->L[lvl + 1], "FAS right-hand side around a caller's transfer"))) return rc;
     if (pl->n == 0) return 0;
     Timed timed(e, MGRIT_HIP_T_FAS_RHS, lvl);
-    LAUNCH_BY_KIND(fas_coarse_kernel, lc, pl->n, lc.dev, pl->d_coarse, 0);
-    return 0;
+    return launch(fas_coarse_fn(lc.dev.kind, force_mode(lc)), dim3(pl->n), dim3(lc.dev.T), smem_bytes(lc.G, lc.dev.kind), e->stream, lc.dev,
+                  pl->d_coarse, 0);
 }
 
 int mgrit_hip_fas_rhs(mgrit_hip_engine *e, int lvl, int pairs_id) {
@@ -3827,15 +3853,18 @@ int mgrit_hip_fas_rhs(mgrit_hip_engine *e, int lvl, int pairs_id) {
     if (is_2pts(lf) || is_2pts(lc)) {
         if (!is_2pts(lf) || !is_2pts(lc) || lf.transfer != MGRIT_HIP_TRANSFER_COPY)
             return fail(MGRIT_HIP_EUNSUPPORTED, "two-point levels pair with two-point levels through the copy transfer only");
-        if (lf.wide) { if ((rc = wide_fas_fine(e, lvl, pl, lc.dev.g, lc.dev.ld, false))) return rc; }
-        else { LAUNCH2_BY_ORDER(fas_fine2_kernel, lf, pl->n, lf.dev, pl->d_fine, pl->d_coarse, lc.dev.g, lc.dev.ld, lvl > 0 ? 1 : 0); }
+        if (lf.wide) rc = wide_fas_fine(e, lvl, pl, lc.dev.g, lc.dev.ld, false);
+        else rc = launch(fas_fine2_fn(lf.order, force_mode(lf)), dim3(pl->n), dim3(lf.dev.T), smem2_bytes(lf.G), e->stream, lf.dev, pl->d_fine,
+                         pl->d_coarse, lc.dev.g, lc.dev.ld, lvl > 0 ? 1 : 0);
+        if (rc) return rc;
         if (lc.wide) return wide_fas_coarse(e, lvl, pl);
-        LAUNCH2_BY_ORDER(fas_coarse2_kernel, lc, pl->n, lc.dev, pl->d_coarse);
-        return 0;
+        return launch(fas_coarse2_fn(lc.order, force_mode(lc)), dim3(pl->n), dim3(lc.dev.T), smem2_bytes(lc.G), e->stream, lc.dev, pl->d_coarse);
     }
     if (lf.transfer == MGRIT_HIP_TRANSFER_COPY) {
-        if (lf.wide) { if ((rc = wide_fas_fine(e, lvl, pl, lc.dev.g, lc.dev.ld, false))) return rc; }
-        else { LAUNCH_BY_KIND(fas_fine_kernel, lf, pl->n, lf.dev, pl->d_fine, pl->d_coarse, lc.dev.g, lc.dev.ld, lvl > 0 ? 1 : 0); }
+        if (lf.wide) rc = wide_fas_fine(e, lvl, pl, lc.dev.g, lc.dev.ld, false);
+        else rc = launch(fas_fine_fn(lf.dev.kind, force_mode(lf)), dim3(pl->n), dim3(lf.dev.T), smem_bytes(lf.G, lf.dev.kind), e->stream, lf.dev,
+                         pl->d_fine, pl->d_coarse, lc.dev.g, lc.dev.ld, lvl > 0 ? 1 : 0);
+        if (rc) return rc;
     } else {
         if (lf.scratch_rows < (size_t)pl->n) {
             // a bigger list than any before: a NEW slab; the old one stays alive until the engine goes (lf.allocs) -- a captured
@@ -3846,16 +3875,18 @@ int mgrit_hip_fas_rhs(mgrit_hip_engine *e, int lvl, int pairs_id) {
             HIP_TRY(hipMalloc(reinterpret_cast<void **>(&lf.scratch), sizeof(double) * (size_t)pl->n * lf.dev.ld));
             lf.scratch_rows = pl->n;
         }
-        if (lf.wide) { if ((rc = wide_fas_fine(e, lvl, pl, lf.scratch, lf.dev.ld, true))) return rc; }
-        else { LAUNCH_BY_KIND(fas_fine_kernel, lf, pl->n, lf.dev, pl->d_fine, pl->d_iota, lf.scratch, lf.dev.ld, lvl > 0 ? 1 : 0); }
+        if (lf.wide) rc = wide_fas_fine(e, lvl, pl, lf.scratch, lf.dev.ld, true);
+        else rc = launch(fas_fine_fn(lf.dev.kind, force_mode(lf)), dim3(pl->n), dim3(lf.dev.T), smem_bytes(lf.G, lf.dev.kind), e->stream, lf.dev,
+                         pl->d_fine, pl->d_iota, lf.scratch, lf.dev.ld, lvl > 0 ? 1 : 0);
+        if (rc) return rc;
         dim3 grid(pl->n, (lc.dev.ld + 255) / 256);
         hipLaunchKernelGGL(restrict_rows_kernel, grid, dim3(256), 0, e->stream, lf.scratch, lf.dev.ld, lf.dev.T, pl->d_iota,
                            lc.dev.g, lc.dev.ld, lc.dev.T, pl->d_coarse, lc.dev.n, lf.transfer);
         HIP_TRY(hipGetLastError());
     }
     if (lc.wide) return wide_fas_coarse(e, lvl, pl);
-    LAUNCH_BY_KIND(fas_coarse_kernel, lc, pl->n, lc.dev, pl->d_coarse, 0);
-    return 0;
+    return launch(fas_coarse_fn(lc.dev.kind, force_mode(lc)), dim3(pl->n), dim3(lc.dev.T), smem_bytes(lc.G, lc.dev.kind), e->stream, lc.dev,
+                  pl->d_coarse, 0);
 }
 
 int mgrit_hip_triples_create(mgrit_hip_engine *e, int lvl, int n, const int32_t *fine_idx, const int32_t *prev_fine_idx,
@@ -3889,7 +3920,6 @@ int mgrit_hip_fas_fused_opts(mgrit_hip_engine *e, int lvl, int triples_id, int o
     Timed timed(e, (opts & MGRIT_HIP_FAS_WITH_F_RELAX) ? MGRIT_HIP_T_F_FAS : MGRIT_HIP_T_FAS_FUSED, lvl);
     const int use_g = lvl > 0 ? 1 : 0;
     if (lf.dev.kind == MGRIT_HIP_STEPPER_HEAT1D && force_mode(lf) != 3) {   // one pass per C-point, coarse tables from L2
-        const dim3 grid(persistent_grid(lf, pl->n)), block(lf.dev.T);
         const int fm = force_mode(lf);
         // forcing factors of both levels are streamed (FORCE 2, the same fma per term): one Phi per point does not pay for
         // keeping them in registers, and the registers are needed for the partial g that stays live across the coarse Phi
@@ -3897,37 +3927,12 @@ int mgrit_hip_fas_fused_opts(mgrit_hip_engine *e, int lvl, int triples_id, int o
         // level's factor is the same vector (same spatial grid, same rhs), so the coarse Phi takes it from there too
         if (lf.same_factor_below < 0) lf.same_factor_below = (fm == 1 && lf.s_host == lc.s_host) ? 1 : 0;   // (131 KB compared once)
         const int kopts = opts | (lf.same_factor_below ? 4 : 0);
-        const int tb = sweep_tb(lf.dev.T);
-#define FAS1_CASE(F_, P_)                                                                                                  \
-    if ((fm == 0 ? 0 : fm == 1 ? 4 : 2) == F_ && ((opts & MGRIT_HIP_FAS_WITH_F_RELAX) != 0) == P_) {                        \
-        if (tb == LANES)                                                                                                   \
-            hipLaunchKernelGGL((fas_fused1_kernel<F_, P_, LANES>), grid, block, smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), \
-                               lc.dev, pl->d_fine, pl->d_prev, pl->d_coarse, pl->n, use_g, kopts);                          \
-        else if (tb == 512)                                                                                                \
-            hipLaunchKernelGGL((fas_fused1_kernel<F_, P_, 512>), grid, block, smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), \
-                               lc.dev, pl->d_fine, pl->d_prev, pl->d_coarse, pl->n, use_g, kopts);                          \
-        else                                                                                                               \
-            hipLaunchKernelGGL((fas_fused1_kernel<F_, P_>), grid, block, smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), \
-                               lc.dev, pl->d_fine, pl->d_prev, pl->d_coarse, pl->n, use_g, kopts);                          \
-    }
-        FAS1_CASE(0, false) FAS1_CASE(2, false) FAS1_CASE(4, false) FAS1_CASE(0, true) FAS1_CASE(2, true) FAS1_CASE(4, true)
-        HIP_TRY(hipGetLastError());
-        return 0;
+        return launch(fas_fused1_fn(fm, (opts & MGRIT_HIP_FAS_WITH_F_RELAX) != 0, lf.dev.T), dim3(persistent_grid(lf, pl->n)), dim3(lf.dev.T),
+                      smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, pl->d_fine, pl->d_prev, pl->d_coarse, pl->n, use_g, kopts);
     }
     if (opts) return fail(MGRIT_HIP_EUNSUPPORTED, "fused FAS residual with options: Heat1D levels (one-pass form) only");
-    const bool mid = lf.dev.T <= 512 && mid_wg_instances();
-#define FUSED_CASE(K_, F_)                                                                                         \
-    if (lf.dev.kind == K_ && force_mode(lf) == F_) {                                                                \
-        if (mid)                                                                                                   \
-            hipLaunchKernelGGL((fas_fused_kernel<K_, F_, 512>), dim3(persistent_grid(lf, pl->n)), dim3(lf.dev.T), smem_bytes(lf.G, lf.dev.kind), \
-                               e->stream, lf.dev, lc.dev, pl->d_fine, pl->d_prev, pl->d_coarse, pl->n, use_g);       \
-        else                                                                                                       \
-            hipLaunchKernelGGL((fas_fused_kernel<K_, F_>), dim3(persistent_grid(lf, pl->n)), dim3(lf.dev.T), smem_bytes(lf.G, lf.dev.kind), \
-                               e->stream, lf.dev, lc.dev, pl->d_fine, pl->d_prev, pl->d_coarse, pl->n, use_g);       \
-    }
-    FOR_EACH_STEPPER(FUSED_CASE)
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return launch(fas_fused_fn(lf.dev.kind, force_mode(lf), lf.dev.T), dim3(persistent_grid(lf, pl->n)), dim3(lf.dev.T), smem_bytes(lf.G, lf.dev.kind),
+                  e->stream, lf.dev, lc.dev, pl->d_fine, pl->d_prev, pl->d_coarse, pl->n, use_g);
 }
 
 int mgrit_hip_copy_pairs_u_to_v(mgrit_hip_engine *e, int lvl, int pairs_id) {
@@ -4026,9 +4031,9 @@ int mgrit_hip_at_solve(mgrit_hip_engine *e, int lvl, int k) {
     }
     if (lv.h2d || lv.wide) return at_batched(e, lvl, k);
     HIP_TRY(hipMemcpyAsync(lv.scratch, lv.dev.u, sizeof(double) * rows * lv.dev.ld, hipMemcpyDeviceToDevice, e->stream));
-    if (is_2pts(lv)) { LAUNCH2_BY_ORDER(at2_kernel, lv, persistent_grid(lv, lv.dev.n_pts - 1), lv.dev, lv.scratch, k); }
-    else { LAUNCH_BY_KIND(at_kernel, lv, persistent_grid(lv, lv.dev.n_pts - 1), lv.dev, lv.scratch, k); }
-    return 0;
+    const dim3 grid(persistent_grid(lv, lv.dev.n_pts - 1)), block(lv.dev.T);
+    if (is_2pts(lv)) return launch(at2_fn(lv.order, force_mode(lv)), grid, block, smem2_bytes(lv.G), e->stream, lv.dev, lv.scratch, k);
+    return launch(at_fn(lv.dev.kind, force_mode(lv)), grid, block, smem_bytes(lv.G, lv.dev.kind), e->stream, lv.dev, lv.scratch, k);
 }
 
 int mgrit_hip_ec_runs_create(mgrit_hip_engine *e, int lvl, int n_runs, const int32_t *start, const int32_t *len,
@@ -4057,25 +4062,8 @@ int mgrit_hip_ec_relax(mgrit_hip_engine *e, int lvl, int ec_runs_id) {
     if ((rc = no_wide(lf, &lc, "fused correction + F-relaxation"))) return rc;
     if (rl->n == 0) return 0;
     Timed timed(e, MGRIT_HIP_T_EC_RELAX, lvl);
-    const bool use_g = lvl > 0;
-    const int fm = force_mode(lf);
-    const dim3 grid(persistent_grid(lf, rl->n)), block(lf.dev.T);
-#define ECF_CASE(K, F, G_)                                                                                          \
-    if (lf.dev.kind == K && fm == F && use_g == G_)                                                                 \
-        hipLaunchKernelGGL((ecf_kernel<K, F, G_>), grid, block, smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, rl->d_start,  \
-                           rl->d_len, rl->d_ec, rl->n);
-#define ECF_CASES(K, F) ECF_CASE(K, F, false) ECF_CASE(K, F, true)
-    const int tb = sweep_tb(lf.dev.T);
-    if (tb != 1024 && lf.dev.kind == MGRIT_HIP_STEPPER_HEAT1D && use_g && fm <= 2) {
-#define ECF_SMALL(F, TB_)                                                                                                             \
-    if (fm == F && tb == TB_) hipLaunchKernelGGL((ecf_kernel<MGRIT_HIP_STEPPER_HEAT1D, F, true, TB_>), grid, block, smem_bytes(lf.G, lf.dev.kind), \
-                                                 e->stream, sched_dev(e, lf), lc.dev, rl->d_start, rl->d_len, rl->d_ec, rl->n);
-        ECF_SMALL(0, LANES) ECF_SMALL(1, LANES) ECF_SMALL(2, LANES) ECF_SMALL(0, 512) ECF_SMALL(1, 512) ECF_SMALL(2, 512)
-    } else {
-        FOR_EACH_STEPPER(ECF_CASES)
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return launch(ecf_fn(lf.dev.kind, force_mode(lf), lvl > 0, lf.dev.T), dim3(persistent_grid(lf, rl->n)), dim3(lf.dev.T),
+                  smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, rl->d_start, rl->d_len, rl->d_ec, rl->n);
 }
 
 // Host read-back of per-run scalars without any copy command: the kernels store straight into pinned, device-mapped
@@ -4240,16 +4228,8 @@ int mgrit_hip_cf_fas(mgrit_hip_engine *e, int lvl, int ivals_id, int pre_relaxed
     const IntervalsDev &I = lf.ivals[ivals_id];
     if (I.n_chunks == 0) return 0;
     Timed timed(e, MGRIT_HIP_T_CF_FAS, lvl);
-    const dim3 grid(persistent_grid(lf, I.n_chunks)), block(lf.dev.T);
-    const int tb = sweep_tb(lf.dev.T);   // (one wave per state / up to 512 threads: the instances compiled for it)
-    if (force_mode(lf) == 0 && tb == LANES) hipLaunchKernelGGL((cfas_kernel<0, LANES>), grid, block, smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, I, pre_relaxed ? 1 : 0);
-    else if (tb == LANES) hipLaunchKernelGGL((cfas_kernel<2, LANES>), grid, block, smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, I, pre_relaxed ? 1 : 0);
-    else if (force_mode(lf) == 0 && tb == 512) hipLaunchKernelGGL((cfas_kernel<0, 512>), grid, block, smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, I, pre_relaxed ? 1 : 0);
-    else if (tb == 512) hipLaunchKernelGGL((cfas_kernel<2, 512>), grid, block, smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, I, pre_relaxed ? 1 : 0);
-    else if (force_mode(lf) == 0) hipLaunchKernelGGL((cfas_kernel<0>), grid, block, smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, I, pre_relaxed ? 1 : 0);
-    else hipLaunchKernelGGL((cfas_kernel<2>), grid, block, smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, I, pre_relaxed ? 1 : 0);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return launch(cfas_fn(force_mode(lf), lf.dev.T), dim3(persistent_grid(lf, I.n_chunks)), dim3(lf.dev.T), smem_bytes(lf.G, lf.dev.kind),
+                  e->stream, sched_dev(e, lf), lc.dev, I, pre_relaxed ? 1 : 0);
 }
 
 static int ec_relax_res_impl(mgrit_hip_engine *e, int lvl, int ivals_id, int store_all_f, double *out_caller);
@@ -4272,33 +4252,16 @@ static int ec_relax_res_impl(mgrit_hip_engine *e, int lvl, int ivals_id, int sto
     const dim3 grid(persistent_grid(lf, I.n_chunks)), block(lf.dev.T);
     if (lvl > 0) {   // coarser level: rows of g, every F-point stored (the finer level's correction reads them), no residual
         Timed timed(e, MGRIT_HIP_T_EC_RELAX, lvl);
-        const int fme = force_mode(lf) == 0 ? 0 : force_mode(lf) == 1 ? 4 : 2;   // (one term: its space factor in LDS)
-        const int tb = sweep_tb(lf.dev.T);
-#define ECFR_UP(F, ...)                                                                                                               \
-    if (fme == F) hipLaunchKernelGGL((ecfr_kernel<F, true, false, ##__VA_ARGS__>), grid, block, smem_bytes(lf.G, lf.dev.kind), e->stream, \
-                                     sched_dev(e, lf), lc.dev, I, (double *)nullptr, 1, (double *const *)nullptr, 0);
-        if (tb == LANES) { ECFR_UP(0, LANES) ECFR_UP(4, LANES) ECFR_UP(2, LANES) }
-        else if (tb == 512) { ECFR_UP(0, 512) ECFR_UP(4, 512) ECFR_UP(2, 512) }
-        else { ECFR_UP(0) ECFR_UP(4) ECFR_UP(2) }
-        HIP_TRY(hipGetLastError());
-        return 0;
+        return launch(ecfr_fn(force_mode(lf), true, lf.dev.T), grid, block, smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, I,
+                      (double *)nullptr, 1, (double *const *)nullptr, 0);
     }
     if (store_all_f < 0 || store_all_f > 2) return fail(MGRIT_HIP_EINVAL, "store_all_f %d outside 0..2", store_all_f);
     if (!out_caller && (rc = ensure_pinned(e, lf.ivals_n[ivals_id]))) return rc;
     double *out = out_caller ? out_caller : e->pinned;
     Timed timed(e, MGRIT_HIP_T_EC_RELAX_RES, lvl);
     double *const *mirror = e->mirror_cur;   // null until mgrit_hip_cpoint_mirror has been called
-    const int row0 = e->mirror_row0;
-    const int fme = force_mode(lf) == 0 ? 0 : force_mode(lf) == 1 ? 4 : 2;
-    const int tb = sweep_tb(lf.dev.T);
-#define ECFR_RES(F, ...)                                                                                                              \
-    if (fme == F) hipLaunchKernelGGL((ecfr_kernel<F, false, true, ##__VA_ARGS__>), grid, block, smem_bytes(lf.G, lf.dev.kind), e->stream, \
-                                     sched_dev(e, lf), lc.dev, I, out, store_all_f, mirror, row0);
-    if (tb == LANES) { ECFR_RES(0, LANES) ECFR_RES(4, LANES) ECFR_RES(2, LANES) }
-    else if (tb == 512) { ECFR_RES(0, 512) ECFR_RES(4, 512) ECFR_RES(2, 512) }
-    else { ECFR_RES(0) ECFR_RES(4) ECFR_RES(2) }
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return launch(ecfr_fn(force_mode(lf), false, lf.dev.T), grid, block, smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, I,
+                  out, store_all_f, mirror, e->mirror_row0);
 }
 
 static int gen_check(mgrit_hip_engine *e, int lvl, int ivals_id, const char *what) {
@@ -4346,21 +4309,12 @@ int mgrit_hip_gen_down_part(mgrit_hip_engine *e, int lvl, int ivals_id, int part
     double *Cb = lf.gen_rows;
     const int tk = lf.transfer;
     Timed timed(e, MGRIT_HIP_T_GEN_DOWN, lvl);
-    if (parts & 1) {
-    const dim3 grid(persistent_grid(lf, I.n_chunks)), block(lf.dev.T);
-    const bool use_g = lvl > 0;
-    const int fm = force_mode(lf);
-    const bool half = lf.dev.T <= 512 && gen_half_instances();   // (states of <= 8192 values: the instances compiled for 512 threads)
-#define GEN_DOWN_CASE(K, F, G_)                                                                                     \
-    if (lf.dev.kind == K && fm == F && use_g == G_) {                                                               \
-        if (half) hipLaunchKernelGGL((gen_down_kernel<K, F, G_, 512>), grid, block, smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, I, Cb, tk); \
-        else hipLaunchKernelGGL((gen_down_kernel<K, F, G_>), grid, block, smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, I, Cb, tk); \
-    }
-#define GEN_DOWN_CASES(K, F) GEN_DOWN_CASE(K, F, false) GEN_DOWN_CASE(K, F, true)
-    FOR_EACH_STEPPER(GEN_DOWN_CASES)
-    HIP_TRY(hipGetLastError());
-    }
-    if (parts & 2) { LAUNCH_BY_KIND(fas_coarse_kernel, lc, n_iv, lc.dev, I.cend_coarse, 1); }
+    if ((parts & 1) && (rc = launch(gen_down_fn(lf.dev.kind, force_mode(lf), lvl > 0, lf.dev.T), dim3(persistent_grid(lf, I.n_chunks)),
+                                    dim3(lf.dev.T), smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, I, Cb, tk)))
+        return rc;
+    if (parts & 2)
+        return launch(fas_coarse_fn(lc.dev.kind, force_mode(lc)), dim3(n_iv), dim3(lc.dev.T), smem_bytes(lc.G, lc.dev.kind), e->stream, lc.dev,
+                      I.cend_coarse, 1);
     return 0;
 }
 
@@ -4380,19 +4334,8 @@ int mgrit_hip_gen_up(mgrit_hip_engine *e, int lvl, int ivals_id, int with_residu
         out = sumsq_out ? sumsq_out : e->pinned;
     }
     Timed timed(e, MGRIT_HIP_T_GEN_UP, lvl);
-    const dim3 grid(persistent_grid(lf, I.n_chunks)), block(lf.dev.T);
-    const bool use_g = lvl > 0, res = with_residual != 0;
-    const int fm = force_mode(lf), tk = lf.transfer;
-    const bool half = lf.dev.T <= 512 && gen_half_instances();
-#define GEN_UP_CASE(K, F, G_, R_)                                                                                    \
-    if (lf.dev.kind == K && fm == F && use_g == G_ && res == R_) {                                                    \
-        if (half) hipLaunchKernelGGL((gen_up_kernel<K, F, G_, R_, 512>), grid, block, smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, I, Cb, out, tk); \
-        else hipLaunchKernelGGL((gen_up_kernel<K, F, G_, R_>), grid, block, smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, I, Cb, out, tk); \
-    }
-#define GEN_UP_CASES(K, F) GEN_UP_CASE(K, F, false, false) GEN_UP_CASE(K, F, false, true) GEN_UP_CASE(K, F, true, false)
-    FOR_EACH_STEPPER(GEN_UP_CASES)
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return launch(gen_up_fn(lf.dev.kind, force_mode(lf), lvl > 0, with_residual != 0, lf.dev.T), dim3(persistent_grid(lf, I.n_chunks)),
+                  dim3(lf.dev.T), smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, I, Cb, out, lf.transfer);
 }
 
 int mgrit_hip_residual_fetch(mgrit_hip_engine *e, int n, double *sumsq_host) {

@@ -165,8 +165,8 @@ __device__ __forceinline__ void gen_restrict_store(const double (&fb)[E], const 
 
 // TB: the workgroup size an instance is compiled for. States of up to 8192 values run in workgroups of at most 512 threads, and
 // compiled for 1024 these passes keep to 128 VGPRs by spilling 16-81 of them -- scratch traffic in kernels that are bound by memory
-// bandwidth. The TB = 512 instances (149-182 VGPRs, no VGPR spill) take the launches of such levels (gen_half_instances): config 5
-// 5.4 -> 4.9 ms per F-cycle. Same source, same operations, same bits (MGRIT_HIP_GEN_512=0: the 1024-thread instances everywhere).
+// bandwidth. The TB = 512 instances (149-182 VGPRs, no VGPR spill) take the launches of such levels (instance_tb): config 5
+// 5.4 -> 4.9 ms per F-cycle. Same source, same operations, same bits as the 1024-thread instances.
 template <int KIND, int FORCE, bool USE_G, int TB = 1024>
 __global__ void __launch_bounds__(TB) gen_down_kernel(LevelDev L, LevelDev Lc, IntervalsDev I, double *__restrict__ Cb, int tkind) {
     WG_PROLOGUE;
