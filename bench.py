@@ -8,10 +8,13 @@ over the ranks by time blocks (strong scaling) and ghost time points travel over
 One "step" = one steady-state MGRIT V-cycle on level 0 (C-relax, F-relax, FAS residual, recursion, error correction,
 F-relax) + the residual-norm convergence check -- exactly what Mgrit.solve() does per iteration after the first.
 value = time-point-DOF updates per second = (Phi applications of the cycle, SURVEY 3.5 work model) x DOFs / wall time,
-inputs resident in HBM. "sweeps" lists every sweep of the cycle with its device time (HIP events around every entry point on
-the engine's stream, three extra cycles in program order) and SURVEY 8d's algorithmic bytes; "roofline" is the row with the
-largest share of the cycle. "other_configs": BASELINE configs[1], [3], [4] on the same GPU, measured in child
-processes after the headline numbers (full lines: --all-configs).
+inputs resident in HBM.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the headline line; nothing else. Everything
+else is measured only with --full, after the headline numbers: "sweeps" lists every sweep of the cycle with its device time
+(HIP events around every entry point on the engine's stream, three extra cycles in program order) and SURVEY 8d's algorithmic
+bytes; "roofline" is the row with the largest share of the cycle; "cpu_baseline", "iters_to_tol" and
+"parity"; "other_configs": BASELINE configs[1], [3], [4] on the same GPU, measured in child processes (full lines: --all-configs).
 """
 import argparse
 import json
@@ -306,6 +309,15 @@ def bench_heat2d(args):
     elapsed = time.perf_counter() - t_start
     if args.dump_outputs:
         dump_outputs(mg, args.dump_outputs)
+    out = {"metric": "time-point-DOF updates/sec per MGRIT V-cycle", "value": sum(c * dof for c in counts) * args.steps / elapsed,
+           "unit": "time-point-DOF updates/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+           "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+           "dtype": "f64", "data": "synthetic",
+           "config": {"workload": f"heat_2d nx=ny={nx} nt={nt0} 2-level m=8 FCF V-cycle + residual check (BASELINE configs[3])",
+                      "phi_per_cycle_by_level": counts, "dof": dof}}
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        return
     f_runs = mg._f_runs(0)
     n_f = sum(r[1] for r in f_runs)
     be.set_timing(True)
@@ -318,18 +330,12 @@ def bench_heat2d(args):
     HP = (((nx - 2 + 1) // 2 + 63) // 64) * 64      # padded half size of an axis; P = 2 HP slots
     flops_per_phi = 4.0 * (2 * HP) * (2 * HP) * (HP + HP)   # four half-size transforms: 2 MACs x P x P x HP each way per axis
     tflops = n_f * flops_per_phi / (f_ms * 1e-3) / 1e12
-    out = {"metric": "time-point-DOF updates/sec per MGRIT V-cycle", "value": sum(c * dof for c in counts) * args.steps / elapsed,
-           "unit": "time-point-DOF updates/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-           "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-           "dtype": "f64", "data": "synthetic",
-           "config": {"workload": f"heat_2d nx=ny={nx} nt={nt0} 2-level m=8 FCF V-cycle + residual check (BASELINE configs[3])",
-                      "phi_per_cycle_by_level": counts, "dof": dof},
-           "roofline": {"bound": "mfma", "achieved": tflops, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                        "frac": tflops / FP64_MFMA_PEAK_TFLOPS, "traffic": None,
-                        "kernel": "level-0 F-relax = per Phi 2 x h2d_fwd_kernel (the first reads the state rows: no rhs launch for the "
-                                  "homogeneous step) + 2 x h2d_inv_kernel (f64 MFMA, half-size transforms; the sweep's arithmetic in the last one) + rim",
-                        "flops_per_phi": flops_per_phi,
-                        "launch_ms": f_ms, "us_per_phi": 1e3 * f_ms / n_f}}
+    out["roofline"] = {"bound": "mfma", "achieved": tflops, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                       "frac": tflops / FP64_MFMA_PEAK_TFLOPS, "traffic": None,
+                       "kernel": "level-0 F-relax = per Phi 2 x h2d_fwd_kernel (the first reads the state rows: no rhs launch for the "
+                                 "homogeneous step) + 2 x h2d_inv_kernel (f64 MFMA, half-size transforms; the sweep's arithmetic in the last one) + rim",
+                       "flops_per_phi": flops_per_phi,
+                       "launch_ms": f_ms, "us_per_phi": 1e3 * f_ms / n_f}
     out["sweeps"] = timed_sweeps(mg, be, cycle, cycles=1)
     out["cycle"] = {"sum_of_sweep_ms_in_program_order": sum(r["ms_per_cycle"] for r in out["sweeps"].values())}
     # the roofline row = the launch kind with the largest share of the cycle's device time, priced with the Phi it applies
@@ -385,6 +391,17 @@ def bench_advection(args):
     elapsed = time.perf_counter() - t_start
     if args.dump_outputs:
         dump_outputs(mg, args.dump_outputs)
+    out = {"metric": "time-point-DOF updates/sec per MGRIT F-cycle", "value": None, "unit": "time-point-DOF updates/s",
+           "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
+           "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+           "config": {"workload": f"advection_1d nx={nxs[0]} nt={nt0} 4-level m=2 F-cycle, spatial coarsening on the first two "
+                                  f"level pairs + residual check (BASELINE configs[4])", "dof_by_level": [n - 1 for n in nxs]}}
+    counts = cycle_phi_counts([len(p.t) for p in prob], [2, 2, 2], 'F')
+    out["config"]["phi_per_cycle_by_level"] = counts
+    out["value"] = sum(c * d for c, d in zip(counts, out["config"]["dof_by_level"])) * args.steps / elapsed
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        return
     f_runs = mg._f_runs(0)
     n_f = sum(r[1] for r in f_runs)
     be.set_timing(True)
@@ -396,17 +413,9 @@ def bench_advection(args):
     f_ms = float(np.mean(ms[1:]))
     dof = nxs[0] - 1
     achieved = n_f * 16.0 * dof / (f_ms * 1e-3) / 1e9
-    out = {"metric": "time-point-DOF updates/sec per MGRIT F-cycle", "value": None, "unit": "time-point-DOF updates/s",
-           "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
-           "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-           "config": {"workload": f"advection_1d nx={nxs[0]} nt={nt0} 4-level m=2 F-cycle, spatial coarsening on the first two "
-                                  f"level pairs + residual check (BASELINE configs[4])", "dof_by_level": [n - 1 for n in nxs]},
-           "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                        "traffic": None, "kernel": "relax_kernel<ADVECTION1D,false,ROLE_F> (level-0 F-relax)", "launch_ms": f_ms,
-                        "algorithmic_bytes_per_launch": n_f * 16.0 * dof}}
-    counts = cycle_phi_counts([len(p.t) for p in prob], [2, 2, 2], 'F')
-    out["config"]["phi_per_cycle_by_level"] = counts
-    out["value"] = sum(c * d for c, d in zip(counts, out["config"]["dof_by_level"])) * args.steps / elapsed
+    out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                       "traffic": None, "kernel": "relax_kernel<ADVECTION1D,false,ROLE_F> (level-0 F-relax)", "launch_ms": f_ms,
+                       "algorithmic_bytes_per_launch": n_f * 16.0 * dof}
     out["sweeps"] = timed_sweeps(mg, be, cycle)
     out["cycle"] = {"sum_of_sweep_ms_in_program_order": sum(r["ms_per_cycle"] for r in out["sweeps"].values())}
     # SURVEY 8d algorithmic bytes per launch of every sweep kind (Phi = 16 n B on level 0, 24 n B on coarser levels; residual
@@ -627,12 +636,14 @@ OTHER_CONFIGS = (["--nx", "1024", "--nt", "4097", "--steps", "200", "--warmup", 
 
 
 def other_configs(timeout=150):
-    """BASELINE configs[1], [3], [4] on this GPU, one child process each: workload, ms per cycle, updates/s, the roofline row"""
+    """BASELINE configs[1], [3], [4] on this GPU, one child process each (--full: the roofline row is among its figures):
+    workload, ms per cycle, updates/s, the roofline row"""
     import subprocess
     rows = []
     for extra in OTHER_CONFIGS:
         try:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__)] + extra, capture_output=True, text=True, timeout=timeout)
+            r = subprocess.run([sys.executable, os.path.abspath(__file__)] + extra + ["--full"], capture_output=True, text=True,
+                               timeout=timeout)
             line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
             b = json.loads(line)
             rf = b.get("roofline", {})
@@ -890,6 +901,114 @@ def sharded_emulation(ms_one_gpu, timeout=150):
     return rows
 
 
+def cycle_figures(mg, be, nts, nx, nt0, dof, cycle, world, backend, ms_step):
+    """--full, heat1d: the per-sweep table of the cycle with its bytes, the roofline row (the sweep with the largest share of
+    the cycle) and the level-0 FCF figure. Every rank takes part (the FCF figure is the maximum over the ranks)."""
+    import torch
+    import torch.distributed as dist
+
+    # --- per-sweep device times: HIP events around EVERY sweep entry point (mgrit_hip_set_timing), measured live on the
+    # engine's stream over three more cycles in PROGRAM order (one full-width launch per sweep and level, nothing beside it:
+    # these are the kernel times a rocprofv3 --kernel-trace --stats run of `bench.py --plan-blocks 1` shows per kernel)
+    table = sweep_table(mg, be, nts, [4, 4], dof, cycle)
+    local_share = 1.0 / world      # the table holds THIS rank's launches: its share of the job's bytes
+    pmc, pmc_src, pmc_stale = pmc_traffic(nx, nt0, world)
+
+    def pmc_bytes(sym):
+        """HBM bytes per launch of a table row's kernel(s) from the PMC file; a row of several kernels (the time-parallel solve): their sum"""
+        if not pmc:
+            return None
+        parts = [p.strip() for p in sym.split(" + ")]
+        tot, hit = 0.0, 0
+        for part in parts:
+            for name, rec in pmc.items():
+                if name == part or (len(parts) > 1 and name.startswith(part)):
+                    tot += rec["hbm_bytes_per_launch"]
+                    hit += 1
+        return tot if hit >= len(parts) else None
+
+    for row in table.values():
+        # algorithmic = SURVEY 8d's bytes of the SWEEPS a launch stands for (a whole-level pass stands for two or three of them
+        # and keeps the state in registers between them, so it moves far fewer bytes than that); physical = what the HBM
+        # counters saw. Only physical bytes are priced against the HBM roofline.
+        row["algorithmic_bytes_per_cycle"] *= local_share
+        per_launch = pmc_bytes(row["kernel_symbol"])
+        phys = per_launch * row["launches_per_cycle"] if per_launch else None
+        row["physical_bytes_per_cycle"] = phys
+        row["physical_GBps"] = phys / (row["ms_per_cycle"] * 1e-3) / 1e9 if (phys and row["ms_per_cycle"]) else None
+        row["physical_frac"] = row["physical_GBps"] / HBM_PEAK_GBS if row["physical_GBps"] else None
+        row["fused_vs_unfused_bytes"] = row["algorithmic_bytes_per_cycle"] / phys if phys else None
+        row["algorithmic_GBps"] = row["algorithmic_bytes_per_cycle"] / (row["ms_per_cycle"] * 1e-3) / 1e9 if row["ms_per_cycle"] else None
+    # the north_star's sweep-only figure: level-0 F-relax + C-relax + F-relax as launches of their own (inside a cycle they
+    # may be part of a whole-level pass)
+    be.set_timing(True)
+    be.timing_drain()
+    for _ in range(4):
+        be.relax(0, mg._f_runs(0), 'F')
+    for _ in range(4):
+        be.relax(0, mg._c_runs(0), 'C')
+    recs = be.timing_drain()
+    be.set_timing(False)
+    f_ms = float(np.mean([ms for k, _, ms in recs if k == "relax_f"][1:]))
+    c_ms = float(np.mean([ms for k, _, ms in recs if k == "relax_c"][1:]))
+    fcf_ms = 2 * f_ms + c_ms
+    if world > 1:
+        red = torch.tensor([fcf_ms], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
+        dist.all_reduce(red, op=dist.ReduceOp.MAX)
+        fcf_ms = float(red.item())
+    N0 = nts[0] - 1
+    fcf_bytes = (2 * (N0 * 3 // 4) + N0 // 4) * 16.0 * dof          # whole job: (2 F_0 + C_0) x 16 B x DOF  (SURVEY 8d)
+    fcf_gbs = fcf_bytes / (fcf_ms * 1e-3) / 1e9
+    dominant = max(table, key=lambda k: table[k]["ms_per_cycle"])
+    dom = table[dominant]
+    cycle_bytes = sum(r["algorithmic_bytes_per_cycle"] for r in table.values()) / local_share
+    traffic = pmc_bytes(dom["kernel_symbol"])
+    traffic_src = pmc_src
+    phys_cycle = sum(r["physical_bytes_per_cycle"] or 0.0 for r in table.values()) if pmc else None
+    # The roofline entry: the kernel with the largest share of the cycle's device time. For a whole-level pass the ALGORITHMIC bytes
+    # are the rows the pass itself has to move (DESIGN.md 4: it stands for three sweeps of the reference's cycle but keeps the state
+    # in registers between them -- the sweeps' own 8d bytes are listed beside it as `unfused_algorithmic_bytes_per_launch`)
+    dom_unfused = dom["algorithmic_bytes_per_cycle"] / max(dom["launches_per_cycle"], 1)
+    kind = dominant.split()[0]
+    n_int = ((nts[0] - 1) // 4) * local_share
+    row_b = 8.0 * dof
+    if kind == "cf_fas":       # per interval: 1 row read (the pre-relaxed C-point); written: the C-point, g^{l+1}, u^{l+1} at the coarse
+                               # level's C-points (1 in 4), v^{l+1} where a chunk of the way up starts (1 in 4)
+        dom_alg = n_int * 3.5 * row_b
+    elif kind == "ec_relax_res":   # per interval: u^{l+1} and the fine C-point read (+ v^{l+1} at chunk starts); the C-point and the last F-point written
+        dom_alg = n_int * 4.25 * row_b
+    else:
+        dom_alg = dom_unfused
+    dom_gbs = dom_alg / (dom["ms_per_launch"] * 1e-3) / 1e9
+    return {
+        # the kernel that takes the largest share of the cycle's device time (this rank), priced against the HBM roofline with
+        # SURVEY 8d's algorithmic bytes; `limited_by` says what really bounds it
+        "roofline": {"bound": "hbm", "achieved": dom_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": dom_gbs / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src, "stale": bool(pmc_stale),
+                     "unfused_algorithmic_bytes_per_launch": dom_unfused,
+                     "kernel": f"{dom['kernel_symbol']} ({dominant})", "launch_ms": dom["ms_per_launch"],
+                     "launches_per_cycle": dom["launches_per_cycle"], "ms_per_cycle": dom["ms_per_cycle"],
+                     "algorithmic_bytes_per_launch": dom_alg, "limited_by": dom["limited_by"]},
+        "sweeps": table,
+        "cycle": {"algorithmic_bytes": cycle_bytes, "physical_bytes": phys_cycle,
+                  "physical_GBps": phys_cycle / (ms_step * 1e-3) / 1e9 if phys_cycle else None,
+                  "physical_frac": phys_cycle / (ms_step * 1e-3) / 1e9 / (HBM_PEAK_GBS * world) if phys_cycle else None,
+                  "fused_vs_unfused_bytes": cycle_bytes / phys_cycle if phys_cycle else None,
+                  "physical_bytes_source": pmc_src,
+                  "sum_of_sweep_ms_in_program_order": sum(r["ms_per_cycle"] for r in table.values()),
+                  "note": "whole V-cycle + residual check. algorithmic = SURVEY 8d bytes of every sweep of the reference's cycle; "
+                          "physical = HBM bytes of the kernels that run (PMC); physical_frac = physical bytes / wall time of a "
+                          "step / 8 TB/s. In a planned cycle the chain runs beside the sweeps, so a step is shorter than the "
+                          "sum of its sweeps"},
+        "fcf_relax_level0": {"ms": fcf_ms, "algorithmic_GBps": fcf_gbs,
+                             "frac_of_hbm_peak": fcf_gbs / (HBM_PEAK_GBS * world),
+                             "updates_per_s": (2 * (N0 * 3 // 4) + N0 // 4) * dof / (fcf_ms * 1e-3),
+                             "c_relax_ms": c_ms, "f_relax_ms": f_ms,
+                             "note": "kernel time of the level-0 F-relax + C-relax + F-relax launches (max over ranks), "
+                                     "whole-job bytes; the sweep-only figure of the north_star (bar: 0.60)"},
+    }
+
+
 def self_launch(n):
     """`python bench.py --gpus N` with no launcher environment: run the same command line under torch.distributed.run
     (one rank per GPU, rendezvous on 127.0.0.1 at a free port) as a CHILD process and pass its output and exit code on."""
@@ -916,7 +1035,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--nx", type=int, default=16384)
     ap.add_argument("--nt", type=int, default=65537)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline numbers, measure everything else as well: per-sweep device times, roofline, the "
+                         "level-0 FCF figure; heat1d on one GPU also the CPU baseline, iterations and time to tolerance, parity, "
+                         "the other configurations and the sharded-rank emulation (child processes); several ranks also the "
+                         "steps with a stopping test after every cycle. Off: the headline line alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline, iterations to "
+                    "tolerance, parity, the other configurations and the sharded-rank emulation")
     ap.add_argument("--no-ramp", action="store_true", help="skip the one-second clock ramp (profiling runs: it would "
                     "fill the kernel summary with its own F-relax launches)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl = RCCL; gloo only to "
@@ -935,7 +1060,7 @@ def main():
     ap.add_argument("--all-configs", dest="all_configs", action="store_true",
                     help="after the headline line (BASELINE configs[2]) print one more JSON line per other GPU configuration: "
                          "configs[1] heat_1d 1024 x 4097, configs[3] heat_2d 512^2, configs[4] advection_1d (each in a child "
-                         "process of its own)")
+                         "process of its own, with --full if this run has it)")
     ap.add_argument("--workload", default="heat1d", choices=["heat1d", "heat2d", "advection"],
                     help="heat1d = BASELINE configs[2] (default, the driver's run); heat2d = configs[3] on one GPU")
     ap.add_argument("--emulate-rank", dest="emulate_rank", default=None,
@@ -1071,9 +1196,9 @@ def main():
         dump_outputs(mg, args.dump_outputs)
     stats_timed = {k: comm_stats[k] - stats0[k] for k in comm_stats} if comm_stats is not None and stats0 is not None else None
     # several ranks: the same steps once more through the reference's own loop (mgrit.py:621-646: the stopping value examined after
-    # every cycle, a blocking gather) -- what a solve costs when nothing may lag; outside `value`
+    # every cycle, a blocking gather) -- what a solve costs when nothing may lag; outside `value`, --full only
     ms_checked = None
-    if pipelined:
+    if pipelined and args.full:
         cycle(1)
         fence()
         t_c = time.perf_counter()
@@ -1088,66 +1213,7 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
 
-    # --- per-sweep device times: HIP events around EVERY sweep entry point (mgrit_hip_set_timing), measured live on the
-    # engine's stream over three more cycles in PROGRAM order (one full-width launch per sweep and level, nothing beside it:
-    # these are the kernel times a rocprofv3 --kernel-trace --stats run of `bench.py --plan-blocks 1` shows per kernel)
-    table = sweep_table(mg, be, nts, [4, 4], dof, cycle)
-    local_share = 1.0 / world      # the table holds THIS rank's launches: its share of the job's bytes
-    pmc, pmc_src, pmc_stale = pmc_traffic(nx, nt0, world)
-
-    def pmc_bytes(sym):
-        """HBM bytes per launch of a table row's kernel(s) from the PMC file; a row of several kernels (the time-parallel solve): their sum"""
-        if not pmc:
-            return None
-        parts = [p.strip() for p in sym.split(" + ")]
-        tot, hit = 0.0, 0
-        for part in parts:
-            for name, rec in pmc.items():
-                if name == part or (len(parts) > 1 and name.startswith(part)):
-                    tot += rec["hbm_bytes_per_launch"]
-                    hit += 1
-        return tot if hit >= len(parts) else None
-
-    for row in table.values():
-        # algorithmic = SURVEY 8d's bytes of the SWEEPS a launch stands for (a whole-level pass stands for two or three of them
-        # and keeps the state in registers between them, so it moves far fewer bytes than that); physical = what the HBM
-        # counters saw. Only physical bytes are priced against the HBM roofline.
-        row["algorithmic_bytes_per_cycle"] *= local_share
-        per_launch = pmc_bytes(row["kernel_symbol"])
-        phys = per_launch * row["launches_per_cycle"] if per_launch else None
-        row["physical_bytes_per_cycle"] = phys
-        row["physical_GBps"] = phys / (row["ms_per_cycle"] * 1e-3) / 1e9 if (phys and row["ms_per_cycle"]) else None
-        row["physical_frac"] = row["physical_GBps"] / HBM_PEAK_GBS if row["physical_GBps"] else None
-        row["fused_vs_unfused_bytes"] = row["algorithmic_bytes_per_cycle"] / phys if phys else None
-        row["algorithmic_GBps"] = row["algorithmic_bytes_per_cycle"] / (row["ms_per_cycle"] * 1e-3) / 1e9 if row["ms_per_cycle"] else None
-    # the north_star's sweep-only figure: level-0 F-relax + C-relax + F-relax as launches of their own (inside a cycle they
-    # may be part of a whole-level pass)
-    be.set_timing(True)
-    be.timing_drain()
-    for _ in range(4):
-        be.relax(0, mg._f_runs(0), 'F')
-    for _ in range(4):
-        be.relax(0, mg._c_runs(0), 'C')
-    recs = be.timing_drain()
-    be.set_timing(False)
-    f_ms = float(np.mean([ms for k, _, ms in recs if k == "relax_f"][1:]))
-    c_ms = float(np.mean([ms for k, _, ms in recs if k == "relax_c"][1:]))
-    fcf_ms = 2 * f_ms + c_ms
-    if world > 1:
-        red = torch.tensor([fcf_ms], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
-        dist.all_reduce(red, op=dist.ReduceOp.MAX)
-        fcf_ms = float(red.item())
-    N0 = nts[0] - 1
-    fcf_bytes = (2 * (N0 * 3 // 4) + N0 // 4) * 16.0 * dof          # whole job: (2 F_0 + C_0) x 16 B x DOF  (SURVEY 8d)
-    fcf_gbs = fcf_bytes / (fcf_ms * 1e-3) / 1e9
-    dominant = max(table, key=lambda k: table[k]["ms_per_cycle"])
-    dom = table[dominant]
-    cycle_bytes = sum(r["algorithmic_bytes_per_cycle"] for r in table.values()) / local_share
     ms_step = 1e3 * elapsed / args.steps
-
-    traffic = pmc_bytes(dom["kernel_symbol"])
-    traffic_src = pmc_src
-    phys_cycle = sum(r["physical_bytes_per_cycle"] or 0.0 for r in table.values()) if pmc else None
     # Phi applications the ENGINE performs per cycle (the work model behind `value` counts the sweeps of the reference's cycle,
     # SURVEY 3.5): with pre-relaxed C-points (DESIGN.md 5) the level-0 C-relaxation's Phi is the residual check's of the cycle before;
     # the time-parallel coarsest-level solve (DESIGN.md 3.8) applies two Phi per step (less block 0's second pass and one per block)
@@ -1157,21 +1223,6 @@ def main():
     if getattr(be, "block_r", {}).get(len(nts) - 1):
         n_c = nts[-1] - 1
         applied[-1] += n_c - 16 - (n_c // 16 - 1)
-    # The roofline entry: the kernel with the largest share of the cycle's device time. For a whole-level pass the ALGORITHMIC bytes
-    # are the rows the pass itself has to move (it stands for three sweeps of the reference's cycle but keeps the state
-    # in registers between them -- the sweeps' own 8d bytes are listed beside it as `unfused_algorithmic_bytes_per_launch`)
-    dom_unfused = dom["algorithmic_bytes_per_cycle"] / max(dom["launches_per_cycle"], 1)
-    kind = dominant.split()[0]
-    n_int = ((nts[0] - 1) // 4) * local_share
-    row_b = 8.0 * dof
-    if kind == "cf_fas":       # per interval: 1 row read (the pre-relaxed C-point); written: the C-point, g^{l+1}, u^{l+1} at the coarse
-                               # level's C-points (1 in 4), v^{l+1} where a chunk of the way up starts (1 in 4)
-        dom_alg = n_int * 3.5 * row_b
-    elif kind == "ec_relax_res":   # per interval: u^{l+1} and the fine C-point read (+ v^{l+1} at chunk starts); the C-point and the last F-point written
-        dom_alg = n_int * 4.25 * row_b
-    else:
-        dom_alg = dom_unfused
-    dom_gbs = dom_alg / (dom["ms_per_launch"] * 1e-3) / 1e9
     applied_updates = float(sum(c * dof for c in applied))
 
     out = {
@@ -1188,32 +1239,9 @@ def main():
                    "phi_per_cycle_by_level": counts, "phi_applied_by_level": applied, "dof": dof, "pipeline_depth": mg.pipeline_depth(),
                    "plan_blocks": mg.plan_blocks(), "chain_shader_mhz": chain_clock[0], "chain_us_per_step": chain_clock[1],
                    "cycle_graph": any(p is not None and getattr(p, "_hip", {}).get("graph") is not None for p in mg._plans.values())},
-        # the kernel that takes the largest share of the cycle's device time (this rank), priced against the HBM roofline with
-        # SURVEY 8d's algorithmic bytes; `limited_by` says what really bounds it
-        "roofline": {"bound": "hbm", "achieved": dom_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": dom_gbs / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src, "stale": bool(pmc_stale),
-                     "unfused_algorithmic_bytes_per_launch": dom_unfused,
-                     "kernel": f"{dom['kernel_symbol']} ({dominant})", "launch_ms": dom["ms_per_launch"],
-                     "launches_per_cycle": dom["launches_per_cycle"], "ms_per_cycle": dom["ms_per_cycle"],
-                     "algorithmic_bytes_per_launch": dom_alg, "limited_by": dom["limited_by"]},
-        "sweeps": table,
-        "cycle": {"algorithmic_bytes": cycle_bytes, "physical_bytes": phys_cycle,
-                  "physical_GBps": phys_cycle / (ms_step * 1e-3) / 1e9 if phys_cycle else None,
-                  "physical_frac": phys_cycle / (ms_step * 1e-3) / 1e9 / (HBM_PEAK_GBS * world) if phys_cycle else None,
-                  "fused_vs_unfused_bytes": cycle_bytes / phys_cycle if phys_cycle else None,
-                  "physical_bytes_source": pmc_src,
-                  "sum_of_sweep_ms_in_program_order": sum(r["ms_per_cycle"] for r in table.values()),
-                  "note": "whole V-cycle + residual check. algorithmic = SURVEY 8d bytes of every sweep of the reference's cycle; "
-                          "physical = HBM bytes of the kernels that run (PMC); physical_frac = physical bytes / wall time of a "
-                          "step / 8 TB/s. In a planned cycle the chain runs beside the sweeps, so a step is shorter than the "
-                          "sum of its sweeps"},
-        "fcf_relax_level0": {"ms": fcf_ms, "algorithmic_GBps": fcf_gbs,
-                             "frac_of_hbm_peak": fcf_gbs / (HBM_PEAK_GBS * world),
-                             "updates_per_s": (2 * (N0 * 3 // 4) + N0 // 4) * dof / (fcf_ms * 1e-3),
-                             "c_relax_ms": c_ms, "f_relax_ms": f_ms,
-                             "note": "kernel time of the level-0 F-relax + C-relax + F-relax launches (max over ranks), "
-                                     "whole-job bytes; the sweep-only figure of the north_star (bar: 0.60)"},
     }
+    if args.full:
+        out.update(cycle_figures(mg, be, nts, nx, nt0, dof, cycle, world, args.backend, ms_step))
     if world > 1:
         comm = mg.comm_time
         st = stats_timed
@@ -1234,7 +1262,7 @@ def main():
                                        "SURVEY 2b counts 24-27 per V-cycle at P=4"}
         out["nccl_ranks"] = dist.get_world_size() if args.backend == "nccl" else 0
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(nx)
             out["iters_to_tol"] = iters_to_tol(problem, nx)
             out["time_to_solution_ms"] = out["iters_to_tol"].pop("time_to_solution_ms", None)
@@ -1274,7 +1302,7 @@ def main():
         torch.cuda.empty_cache()
         me = os.path.abspath(__file__)
         for extra in OTHER_CONFIGS:
-            r = subprocess.run([sys.executable, me] + extra, capture_output=True, text=True)
+            r = subprocess.run([sys.executable, me] + extra + (["--full"] if args.full else []), capture_output=True, text=True)
             lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
             print(lines[-1] if lines and r.returncode == 0 else json.dumps({"config": {"workload": " ".join(extra)}, "error": r.stderr[-400:]}),
                   flush=True)

@@ -1,5 +1,6 @@
-"""bench.py end to end on small instances: one JSON line with the fields the harness reads (metric, value, roofline,
-cpu_baseline, iters_to_tol) on one GPU, and through torch.distributed.run on two ranks (gloo, both on the one GPU)."""
+"""bench.py end to end on small instances: one JSON line with the fields the harness reads (metric, value, ms_per_step; with
+--full also roofline, cpu_baseline, iters_to_tol) on one GPU, and through torch.distributed.run on two ranks (gloo, both on
+the one GPU)."""
 import json
 import os
 import subprocess
@@ -21,8 +22,8 @@ def _last_json(out):
 def test_bench_single_gpu_line():
     if not torch.cuda.is_available():
         pytest.fail("GPU test selected but no GPU visible")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nx", "1024", "--nt", "1025", "--steps", "3", "--warmup", "1"],
-                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nx", "1024", "--nt", "1025", "--steps", "3", "--warmup", "1",
+                        "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     b = _last_json(r.stdout)
     assert b["metric"].startswith("time-point-DOF updates/sec") and b["n_gpus"] == 1 and b["steps"] == 3 and b["dtype"] == "f64"
@@ -32,6 +33,23 @@ def test_bench_single_gpu_line():
     assert set(b["cpu_baseline"]) >= {"value", "unit", "cores", "kind", "sample"} and b["cpu_baseline"]["kind"] == "port"
     assert b["iters_to_tol"]["sample_nt1025"]["gpu_iters"] == b["iters_to_tol"]["sample_nt1025"]["cpu_iters"]
     assert "workload" in b["config"]
+
+
+def test_bench_plain_line_is_the_headline_alone():
+    """without --full: the headline fields and nothing measured after the timed steps (no per-sweep times, roofline, CPU
+    baseline, iterations to tolerance, other configurations)"""
+    if not torch.cuda.is_available():
+        pytest.fail("GPU test selected but no GPU visible")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nx", "1024", "--nt", "1025", "--steps", "3", "--warmup", "1"],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    b = _last_json(r.stdout)
+    assert b["metric"].startswith("time-point-DOF updates/sec") and b["unit"] == "time-point-DOF updates/s" and b["dtype"] == "f64"
+    assert b["value"] > 0 and b["ms_per_step"] > 0 and b["higher_is_better"] is True and b["steps"] == 3 and b["warmup"] == 1
+    assert "workload" in b["config"]
+    moved = {"roofline", "sweeps", "cycle", "fcf_relax_level0", "cpu_baseline", "iters_to_tol", "time_to_solution_ms", "parity",
+             "other_configs", "sharded_rank_emulation"}
+    assert not moved & set(b), sorted(moved & set(b))
 
 
 def test_bench_dump_outputs_match_the_oracle(tmp_path, oracle):
@@ -81,7 +99,7 @@ def test_bench_two_ranks_line():
     # no launcher around it: `python bench.py --gpus 2` starts its own ranks (torch.distributed.run as a child process, before
     # anything touches the GPU) and relays rank 0's line
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--nx", "1024",
-                        "--nt", "2049", "--steps", "3", "--warmup", "1", "--backend", "gloo"],
+                        "--nt", "2049", "--steps", "3", "--warmup", "1", "--backend", "gloo", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     b = _last_json(r.stdout)

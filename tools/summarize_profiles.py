@@ -119,14 +119,14 @@ def main(tag):
     with open(os.path.join(out, f"{tag}_traffic.json"), "w") as f:
         json.dump({"build": stamp(),
                    "note": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) around "
-                           "`python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-ramp --plan-blocks 1` (tools/profile_round.sh); KiB units; read side doubled "
+                           "`python3 bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-ramp --plan-blocks 1` (tools/profile_round.sh); KiB units; read side doubled "
                            "(gfx950 FETCH_SIZE tallies 128-B requests at 64 B). Every kernel name of the headline cycle belongs to one (sweep, level): cfas/ecfr = level 0, the <.., true, ..> kernels and fas_fused1 = level 1, chain2 = level 2; relax_kernel<1, 1, false, 0|1> = the stand-alone level-0 F-/C-relax launches of the fcf_relax_level0 figure.",
                    "kernels": summary}, f, indent=1)
     adv = traffic_summary(tag, "_advection", True)
     if adv:
         with open(os.path.join(out, f"{tag}_traffic_advection.json"), "w") as f:
             json.dump({"build": stamp(),
-                       "note": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) around `python3 bench.py --workload advection "
+                       "note": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) around `python3 bench.py --full --workload advection "
                                "--steps 3 --warmup 2` (tools/profile_round.sh); KiB units; read side doubled (gfx950 FETCH_SIZE tallies 128-B "
                                "requests at 64 B). Keys: kernel@workgroup size -- 512 threads = level 0 (8192 values), 256 = level 1, "
                                "128 = levels 2 and 3 (2048 values).", "kernels": adv}, f, indent=1)
