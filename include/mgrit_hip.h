@@ -35,7 +35,7 @@ typedef struct mgrit_hip_engine mgrit_hip_engine;
 
 enum { MGRIT_HIP_OK = 0, MGRIT_HIP_EINVAL = -1, MGRIT_HIP_EHIP = -2, MGRIT_HIP_ENODEV = -3, MGRIT_HIP_EUNSUPPORTED = -4 };
 enum { MGRIT_HIP_STEPPER_HEAT1D = 1, MGRIT_HIP_STEPPER_ADVECTION1D = 2, MGRIT_HIP_STEPPER_HEAT2D = 3,
-       MGRIT_HIP_STEPPER_HEAT1D_2PTS = 4 };
+       MGRIT_HIP_STEPPER_HEAT1D_2PTS = 4, MGRIT_HIP_STEPPER_ALLENCAHN2D = 5 };
 enum { MGRIT_HIP_TRANSFER_COPY = 0, MGRIT_HIP_TRANSFER_HEAT1D = 1, MGRIT_HIP_TRANSFER_PERIODIC1D = 2,
        /* the caller applies restriction / interpolation itself (a user's GridTransfer, reference core/grid_transfer.py:31-55:
           any Python code): mgrit_hip_restrict_u / _fas_rhs / _error_correction / _interpolate refuse the level pair, the FAS
@@ -97,6 +97,16 @@ int mgrit_hip_level_heat2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const 
  * theta*dt*rhs(t_i) + (1-theta)*dt*rhs(t_{i-1}). Caller-owned like the state slabs; NULL switches it off. +8 B per DOF and Phi. */
 int mgrit_hip_heat2d_padded(mgrit_hip_engine *e, int lvl, int *Mi, int *Mj);
 int mgrit_hip_level_heat2d_forcing_rows(mgrit_hip_engine *e, int lvl, const double *rows);
+/* AllenCahn with method = 'IMEX' (reference allen_cahn/allen_cahn.py:145-170 constructor, 172-189 compute_matrix, 201-205 the step):
+ * the periodic nx x nx grid, rows of ld >= nx*nx doubles in natural row-major order (no lane blocking, no rim), ld a multiple of
+ * 16; 4 <= nx <= 2048. inv_dx2 = 1/dx^2, inv_eps2 = 1/eps^2. Phi(u) = (I - dt L)^-1 (u + dt inv_eps2 u (1 - u^nu)): the
+ * reference's SuperLU solve is replaced by the eigen-decomposition of the periodic Laplacian in the discrete Hartley basis, four
+ * batched products with the full nx x nx Hartley table on the FP64 matrix cores per step. Such a level runs through
+ * the Heat2D entry points (copy transfer or the caller's); its Phi is non-linear, so the time-parallel forward solve is never
+ * taken (mgrit_hip_block_solve_config with r < 0 leaves it step by step, r > 0 is MGRIT_HIP_EUNSUPPORTED). The methods 'IMPL'
+ * and 'CN' (allen_cahn.py:206-228, Newton) have no device form. */
+int mgrit_hip_level_allencahn2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld,
+                                double inv_dx2, double inv_eps2, int nu);
 /* Device slabs u, v, g of Mgrit.create_u_v_g (mgrit.py:840-858); v and g may be NULL on level 0. */
 int mgrit_hip_level_bind(mgrit_hip_engine *e, int lvl, double *u, double *v, double *g);
 /* Hand-over state of forward_solve (mgrit.py:459-486) between the owners of a level (op 5, mgrit.py:468-485): a level whose

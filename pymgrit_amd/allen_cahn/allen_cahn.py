@@ -1,0 +1,185 @@
+"""2-D Allen-Cahn equation with periodic boundary conditions: state vector and application.
+
+    u_t = u_xx + u_yy + (1 / eps^2) u (1 - u^nu)   on [-0.5, 0.5]^2 x (t_start, t_end],
+    u(x, 0) = tanh((radius - |x|) / (sqrt(2) eps)).
+
+Drop-in for ``pymgrit.allen_cahn.allen_cahn`` (reference src/pymgrit/allen_cahn/allen_cahn.py:16-260): same constructor,
+attributes and helpers. Three time integrators:
+
+``method='IMEX'``
+    ``Phi(u) = (I - dt L)^-1 (u + dt/eps^2 u (1 - u^nu))``, L the periodic 5-point Laplacian / dx^2. The reference factorises
+    ``I - dt L`` with SuperLU on every step; here the solve is the eigen-decomposition of L in the discrete Hartley basis
+    ``T[i][k] = (cos(2 pi i k / n) + sin(2 pi i k / n)) / sqrt(n)`` (symmetric, orthogonal, ``T T = I``):
+    ``Phi = T ((T b T) / (1 + dt (lam_i + lam_j))) T`` with ``lam_k = (4 / dx^2) sin^2(pi k / n)``. This is the method that
+    runs on the MI355X: ``device_stepper()`` describes it (kind ``"allencahn2d"``) and the engine applies the four products on the
+    FP64 matrix cores (csrc/mgrit_hip_allencahn.inc). ``step`` is the same formula in numpy (plugin path).
+``method='IMPL'`` and ``method='CN'``
+    Newton's method with a sparse direct solve per iteration, on the host only: ``device_stepper()`` returns ``None`` and a
+    hierarchy that holds such a level runs through ``step`` on the plugin path like any host application. The Newton Jacobian
+    ``I - fac (L + diag((1 - (nu + 1) u^nu) / eps^2))`` changes with the iterate and is not diagonal in any fixed basis, so the
+    fast diagonalisation does not carry over.
+"""
+import numpy as np
+import scipy.sparse as sp
+from scipy.sparse.linalg import spsolve
+
+from pymgrit_amd.core.application import Application
+from pymgrit_amd.core.vector import Vector
+
+
+class VectorAllenCahn2D(Vector):
+    """nx x ny grid values of one time point; the norm is the 2-norm over all of them"""
+
+    def __init__(self, nx, ny):
+        super().__init__()
+        self.nx = nx
+        self.ny = ny
+        self.values = np.zeros((nx, ny))
+
+    def _like(self, values):
+        out = VectorAllenCahn2D(self.nx, self.ny)
+        out.set_values(values)
+        return out
+
+    def __add__(self, other):
+        return self._like(self.get_values() + other.get_values())
+
+    def __sub__(self, other):
+        return self._like(self.get_values() - other.get_values())
+
+    def __mul__(self, other):
+        return self._like(self.get_values() * other)
+
+    def norm(self):
+        return np.linalg.norm(self.values)
+
+    def clone(self):
+        return self._like(self.get_values())
+
+    def clone_zero(self):
+        return VectorAllenCahn2D(self.nx, self.ny)
+
+    def clone_rand(self):
+        return self._like(np.random.rand(self.nx, self.ny))
+
+    def set_values(self, values):
+        self.values = values
+
+    def get_values(self):
+        return self.values
+
+    def pack(self):
+        return self.values
+
+    def unpack(self, values):
+        self.values = values
+
+
+def hartley_matrix(n):
+    """T[i][k] = (cos(2 pi i k / n) + sin(2 pi i k / n)) / sqrt(n); the angle is reduced exactly, (i k) mod n"""
+    r = np.outer(np.arange(n, dtype=np.int64), np.arange(n, dtype=np.int64)) % n
+    a = 2.0 * np.pi * r / n
+    return (np.cos(a) + np.sin(a)) / np.sqrt(n)
+
+
+def periodic_laplacian_eigenvalues(n, dx):
+    """eigenvalues of -(periodic [1 -2 1] / dx^2), mode k of the Hartley (or Fourier) basis"""
+    return (4.0 / dx ** 2) * np.sin(np.pi * np.arange(n) / n) ** 2
+
+
+class AllenCahn(Application):
+    """Allen-Cahn in 2-D space with periodic boundary conditions (module docstring). ``method='IMEX'`` has a device form;
+    ``'IMPL'`` and ``'CN'`` are host-side Newton solves and send their hierarchy to the plugin path."""
+
+    def __init__(self, nx=128, nu=2, eps=0.04, newton_maxiter=100, newton_tol=1e-12, lin_tol=1e-12, lin_maxiter=100,
+                 radius=0.25, method='IMPL', *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.nu = nu
+        self.eps = eps
+        self.newton_maxiter = newton_maxiter
+        self.newton_tol = newton_tol
+        self.lin_tol = lin_tol
+        self.lin_maxiter = lin_maxiter
+        self.radius = radius
+        self.nx = nx
+        self.ny = nx
+        self.method = method
+        if method not in ('IMPL', 'IMEX', 'CN'):
+            raise Exception("Unknown method. Choose IMPL (implicit), IMEX (implicit-explicit) or CN (Crank-Nicolson")
+        self.dx = 1.0 / self.nx
+        self.space_disc = self.compute_matrix()
+        self.id = sp.eye(self.nx * self.ny)
+        self.x = np.linspace(start=-0.5, stop=0.5, num=self.nx)   # (nx points INCLUDING both ends, although dx = 1 / nx: as the reference)
+        self._hartley = None
+        self._lam = None
+        self.vector_t_start = self.initial_guess()
+        self.vector_template = VectorAllenCahn2D(nx=self.nx, ny=self.ny)
+
+    def compute_matrix(self):
+        """periodic 5-point Laplacian / dx^2 on the row-major nx x ny grid (sparse, csc)"""
+        n = self.nx
+        one = np.ones(n)
+        lap = sp.diags([-2.0 * one, one[:-1], one[:-1], [1.0], [1.0]], [0, 1, -1, n - 1, 1 - n], shape=(n, n), format='csc')
+        out = sp.kron(lap, sp.eye(n)) + sp.kron(sp.eye(n), lap)
+        return sp.csc_matrix(out * (1.0 / self.dx ** 2))
+
+    def _reaction(self, u):
+        """u (1 - u^nu), u^nu by nu - 1 multiplications p = p * u (the device kernel's order)"""
+        p = u.copy()
+        for _ in range(1, int(self.nu)):
+            p = p * u
+        return u * (1.0 - p)
+
+    def _step_imex(self, u, dt):
+        if self._hartley is None:
+            self._hartley = hartley_matrix(self.nx)
+            self._lam = periodic_laplacian_eigenvalues(self.nx, self.dx)
+        T = self._hartley
+        c = dt * (1.0 / self.eps ** 2)
+        b = c * self._reaction(u) + u
+        dinv = 1.0 / (1.0 + dt * (self._lam[:, None] + self._lam[None, :]))
+        return T @ (((T @ b) @ T) * dinv) @ T
+
+    def _step_newton(self, u, dt):
+        old = u.ravel()
+        new = old.copy()
+        inv_eps2 = 1.0 / self.eps ** 2
+        if self.method == 'CN':
+            fac = dt / 2
+            rhs = old + fac * (self.space_disc.dot(old) + inv_eps2 * self._reaction(old))
+        else:
+            fac = dt
+            rhs = old
+        for _ in range(int(self.newton_maxiter)):
+            g = new - fac * (self.space_disc.dot(new) + inv_eps2 * self._reaction(new)) - rhs
+            if np.linalg.norm(g, np.inf) < self.newton_tol:
+                break
+            jac = self.id - fac * (self.space_disc + inv_eps2 * sp.diags(1.0 - (self.nu + 1) * new ** self.nu, offsets=0))
+            new = new - spsolve(sp.csc_matrix(jac), g)
+        return new.reshape(self.nx, self.ny)
+
+    def step(self, u_start: VectorAllenCahn2D, t_start: float, t_stop: float) -> VectorAllenCahn2D:
+        u = np.asarray(u_start.get_values(), dtype=np.float64)
+        dt = t_stop - t_start
+        ret = VectorAllenCahn2D(self.nx, self.ny)
+        ret.set_values(self._step_imex(u, dt) if self.method == 'IMEX' else self._step_newton(u, dt))
+        return ret
+
+    def device_stepper(self):
+        """description of Phi for the HIP engine: ``method='IMEX'`` only (``None`` otherwise: plugin path)"""
+        if self.method != 'IMEX':
+            return None
+        return {"kind": "allencahn2d", "n": self.nx * self.ny, "nx": self.nx, "inv_dx2": 1.0 / self.dx ** 2,
+                "inv_eps2": 1.0 / self.eps ** 2, "nu": int(self.nu)}
+
+    def initial_guess(self):
+        initial = VectorAllenCahn2D(nx=self.nx, ny=self.ny)
+        r = np.sqrt(self.x[:, None] ** 2 + self.x[None, :] ** 2)
+        initial.set_values(np.tanh((self.radius - r) / (np.sqrt(2) * self.eps)))
+        return initial
+
+    def exact_radius(self, t):
+        return np.sqrt(max(self.radius ** 2 - 2.0 * t, 0))
+
+    def compute_radius(self, u):
+        return np.sqrt(np.count_nonzero(u.get_values() >= 0.0) / np.pi) * self.dx

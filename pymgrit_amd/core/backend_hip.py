@@ -116,6 +116,9 @@ class SlabVectorList:
         return (self[k] for k in range(len(self)))
 
 
+GRID_2D = ("heat2d", "allencahn2d")   # states are whole 2-D grids in natural row-major order; the engine's Heat2D route
+
+
 class HipBackend:
     name = "hip"
 
@@ -130,16 +133,18 @@ class HipBackend:
         # one spare level index: the work level of AT-MGRIT on several ranks (at_forward_solve), described on first use
         check(self.lib.mgrit_hip_create(C.byref(self.h), mg.lvl_max + 1, C.c_void_p(self.stream.cuda_stream)))
         self.desc = [p.device_stepper() for p in mg.problem]
+        if any(d["kind"] == "allencahn2d" for d in self.desc):
+            self._check_allencahn(mg)
         self.n = [int(d["n"]) for d in self.desc]
         # 1-D steppers: lane-blocked rows; Heat2D: the nx x ny grid in natural row-major order
         # two-point states: the row is [first | second], each half lane-blocked like a 1-D row of n values
-        self.ld = [((n + 15) // 16) * 16 if d["kind"] == "heat2d" else
+        self.ld = [((n + 15) // 16) * 16 if d["kind"] in GRID_2D else
                    (2 if d["kind"] == "heat1d_2pts" else 1) * hip_lib.row_stride(n) for n, d in zip(self.n, self.desc)]
         self.perm, made = [], {}
         for n, d in zip(self.n, self.desc):     # (levels of one spatial size share the tensor: one upload, in front of the slabs' zero fills)
             key = (n, d["kind"])
             if key not in made:
-                if d["kind"] == "heat2d":
+                if d["kind"] in GRID_2D:
                     perm = np.arange(n)
                 elif d["kind"] == "heat1d_2pts":
                     half = hip_lib.row_permutation(n)
@@ -166,6 +171,19 @@ class HipBackend:
                 self.h = C.c_void_p()
         except Exception:
             pass
+
+    def _check_allencahn(self, mg):
+        """what the Allen-Cahn device path does not cover is refused by name, never run differently"""
+        from pymgrit_amd.core.at_mgrit import AtMgrit
+        if any(d["kind"] != "allencahn2d" for d in self.desc):
+            raise MgritHipError("Allen-Cahn (IMEX) levels on the HIP engine: every level of the hierarchy must be an AllenCahn "
+                                "application with method='IMEX'")
+        if mg.comm_time_size > 1:
+            raise MgritHipError("Allen-Cahn (IMEX) levels on the HIP engine: one time rank only")
+        if isinstance(mg, AtMgrit):
+            raise MgritHipError("Allen-Cahn (IMEX) levels on the HIP engine: AT-MGRIT is not supported, use Mgrit")
+        if not mg.global_conv_crit:
+            raise MgritHipError("Allen-Cahn (IMEX) levels on the HIP engine: the global convergence criteria only (conv_crit 0 or 1)")
 
     # -- state (mgrit.py:840-858) -------------------------------------------------------------------
     def _describe_heat1d(self, engine_lvl, d, t_local, n, ld):
@@ -237,6 +255,9 @@ class HipBackend:
                     rows[a:z].copy_(torch.from_numpy(host.reshape(z - a, Mi * Mj)))
                 self.FB[lvl] = rows
                 check(self.lib.mgrit_hip_level_heat2d_forcing_rows(self.h, lvl, C.c_void_p(rows.data_ptr())))
+        elif d["kind"] == "allencahn2d":
+            check(self.lib.mgrit_hip_level_allencahn2d(self.h, lvl, n_pts, _ptr(t_local), int(d["nx"]), ld, float(d["inv_dx2"]),
+                                                       float(d["inv_eps2"]), int(d["nu"])))
         else:
             raise MgritHipError(f"unknown device stepper kind {d['kind']!r}")
         u = torch.zeros((n_pts, ld), dtype=torch.float64, device=self.device)
@@ -293,6 +314,12 @@ class HipBackend:
         self.block_sharded = getattr(self, "block_sharded", {})
         self.block_uh = getattr(self, "block_uh", {})
         r = C.c_int(0)
+        if d["kind"] == "allencahn2d":
+            # non-linear Phi: the time-parallel forward solve superposes block defects and holds for linear steppers only -- the
+            # coarsest level is solved step by step whatever options.coarse_solve says
+            check(self.lib.mgrit_hip_block_solve_config(self.h, lvl, 0, 1, 0, None, None))
+            self.block_r[lvl], self.block_sharded[lvl] = 0, False
+            return
         if d["kind"] == "heat2d":
             # Heat2D (backward Euler or Crank-Nicolson, one rank): the engine's own rule (level > 0, theta = 1 or 1/2, >= 64 steps), full sine spectrum
             want = (lvl > 0 and lvl == mg.lvl_max - 1 and options.coarse_solve != "sequential" and mg.comm_time_size == 1 and
@@ -360,7 +387,7 @@ class HipBackend:
         for lvl in range(mg.lvl_max - 1):
             tr = mg.transfer_objects[lvl]
             kind = int(tr.device_transfer()) if self._device_transfer(lvl) else hip_lib.TRANSFER_CALLER
-            if kind == hip_lib.TRANSFER_CALLER and self.desc[lvl]["kind"] not in ("heat1d", "advection1d", "heat2d"):
+            if kind == hip_lib.TRANSFER_CALLER and self.desc[lvl]["kind"] not in ("heat1d", "advection1d") + GRID_2D:
                 raise MgritHipError(f"transfer {type(tr).__name__} is applied through its Python methods, which the "
                                     f"{self.desc[lvl]['kind']} levels do not support (they take GridTransferCopy)")
             check(self.lib.mgrit_hip_level_transfer(self.h, lvl, kind))
@@ -1028,7 +1055,7 @@ class HipBackend:
     def _resident(self, lvl):
         """both levels of the pair hold a state in one workgroup's registers (n <= 16384): the fused passes' precondition; wider
         Heat1D states run sweep by sweep through the three-launch Phi (csrc/mgrit_hip_wide.inc)"""
-        return max(self.n[lvl], self.n[min(lvl + 1, len(self.n) - 1)]) <= hip_lib.MAX_N or self.desc[lvl]["kind"] == "heat2d"
+        return max(self.n[lvl], self.n[min(lvl + 1, len(self.n) - 1)]) <= hip_lib.MAX_N or self.desc[lvl]["kind"] in GRID_2D
 
     def can_fuse_fas(self, lvl):
         tr = self.mg.transfer_objects[lvl]

@@ -13,6 +13,7 @@ TIMED_KINDS = ("relax_f", "relax_c", "chain", "residual", "jump", "restrict", "c
                "error_correction", "interpolate", "ec_relax", "at_solve", "cf_fas", "ec_relax_res", "relax_fc", "f_fas", "exchange",
                "gen_down", "gen_up")
 STEPPER_HEAT1D, STEPPER_ADVECTION1D = 1, 2
+STEPPER_ALLENCAHN2D = 5
 TRANSFER_COPY, TRANSFER_HEAT1D, TRANSFER_CALLER = 0, 1, 3
 MAX_N = 16384
 MAX_LINKS = 16
@@ -42,6 +43,8 @@ EXPORTS = {
                                          C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "mgrit_hip_heat2d_padded": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mgrit_hip_level_heat2d_forcing_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "mgrit_hip_level_allencahn2d": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double,
+                                              C.c_int]),
     "mgrit_hip_level_bind": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgrit_hip_chain_enable": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "mgrit_hip_chain_state_len": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),

@@ -1477,6 +1477,8 @@ __global__ void interp_rows_kernel(double *__restrict__ uf, int f_ld, int T_f, c
 
 #include "mgrit_hip_heat2d.inc"
 
+#include "mgrit_hip_allencahn.inc"
+
 #include "mgrit_hip_wide.inc"
 
 #include "mgrit_hip_gen.inc"
@@ -1522,6 +1524,11 @@ struct H2DHost {
         unsigned *rim_flag = nullptr;   // pinned, device-mapped (theta < 1): set when an error at a block end has a non-zero rim
         hipEvent_t rim_ev = nullptr;
     } blk;
+    // Allen-Cahn IMEX (mgrit_hip_allencahn.inc) runs through this route with its own transforms: the full Hartley table [P][P]
+    // (P = Mi = Mj = nx padded to 64), lx = ly = the periodic Laplacian's eigenvalues in natural mode order, no rim, no fold
+    bool ac = false;
+    double *acT = nullptr, ac_inv_eps2 = 0.0;
+    int ac_nu = 0, ac_KP = 0;
     double *Wc0 = nullptr, *Wc1 = nullptr;   // one item each: the work buffers of the coarsest-level chain, which in a planned
                                              // cycle steps on a second stream BESIDE sweeps that apply this level's Phi too (the
                                              // coarse half of the FAS right-hand side of another block of time points)
@@ -2392,6 +2399,16 @@ int h2d_dinv(mgrit_hip_engine *e, Level &lv, uint64_t dtbits, double **out) {
     std::memcpy(&dt, &dtbits, 8);
     const double thdt = h.dev.theta * dt;
     std::vector<double> tab((size_t)h.dev.Mi * h.dev.Mj, 0.0);   // spectral slot order on both axes, 0 where no mode lives
+    if (h.ac) {   // natural mode order, modes 0 .. nx - 1 on both axes
+        for (int a = 0; a < h.dev.nx; ++a)
+            for (int b = 0; b < h.dev.nx; ++b) tab[(size_t)a * h.dev.Mj + b] = 1.0 / (1.0 + dt * (h.lx[a] + h.ly[b]));
+        double *d = nullptr;
+        int rc = dev_upload(lv, e->stream, tab, &d);
+        if (rc) return rc;
+        h.dinv[dtbits] = d;
+        *out = d;
+        return 0;
+    }
     const int hxe = (h.dev.mi + 1) / 2, hxo = h.dev.mi / 2, hye = (h.dev.mj + 1) / 2, hyo = h.dev.mj / 2;
     for (int a = 0; a < h.dev.Mi; ++a) {
         if (!((a < hxe) || (a >= h.HPx && a < h.HPx + hxo))) continue;
@@ -2426,6 +2443,28 @@ int h2d_phi_batch(mgrit_hip_engine *e, Level &lv, const H2DPlan &pl, const doubl
     double *const W0 = chain ? h.Wc0 : h.W0, *const W1 = chain ? h.Wc1 : h.W1;
     double *dinv = nullptr;
     if ((rc = h2d_dinv(e, lv, pl.dtbits, &dinv))) return rc;
+    if (h.ac) {   // Allen-Cahn IMEX: four products with the full Hartley table, the non-linear right-hand side formed while staging the first
+        double dt;
+        std::memcpy(&dt, &pl.dtbits, 8);
+        const ACPre pre{dt * h.ac_inv_eps2, h.ac_nu};
+        const int P = H.Mi;
+        const dim3 g(P / 64, P / 64, pl.count);
+        const H2DFin none{};
+        hipLaunchKernelGGL((ac_gemm_kernel<AC_FIRST>), g, dim3(256), 0, e->stream, h.acT, P, h.ac_KP, H.nx, in_slab, W1, nullptr, per,
+                           pl.d_in, H.ld, pre, H, none);
+        hipLaunchKernelGGL((ac_gemm_kernel<AC_SCALE>), g, dim3(256), 0, e->stream, h.acT, P, h.ac_KP, H.nx, W1, W0, dinv, per, nullptr, 0,
+                           pre, H, none);
+        hipLaunchKernelGGL((ac_gemm_kernel<AC_PLAIN>), g, dim3(256), 0, e->stream, h.acT, P, h.ac_KP, H.nx, W0, W1, nullptr, per, nullptr, 0,
+                           pre, H, none);
+        if (fin)
+            hipLaunchKernelGGL((ac_gemm_kernel<AC_FIN>), g, dim3(256), 0, e->stream, h.acT, P, h.ac_KP, H.nx, W1, W0, nullptr, per, nullptr,
+                               0, pre, H, *fin);
+        else
+            hipLaunchKernelGGL((ac_gemm_kernel<AC_PLAIN>), g, dim3(256), 0, e->stream, h.acT, P, h.ac_KP, H.nx, W1, W0, nullptr, per, nullptr,
+                               0, pre, H, none);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
     // W1[j][i'] = x to spectral slots ; W0[i'][j'] = y to spectral slots, o D ; W1[j'][i] = x back ; W0[i][j] = y back = U
     const dim3 fx(H.Mj / 64, H.Mi / 64, pl.count), fy(H.Mi / 64, H.Mj / 64, pl.count);        // (n tiles, slot tiles, items)
     const dim3 ix(H.Mj / 64, h.HPx / 64, pl.count), iy(H.Mi / 64, h.HPy / 64, pl.count);      // (n tiles, i tiles, items)
@@ -2463,7 +2502,7 @@ int h2d_phi_op(mgrit_hip_engine *e, Level &lv, const H2DPlan &pl, const double *
     int rc;
     // (the sequential coarsest-level solve keeps the epilogue kernel: fused, one step of one state took 107 instead of 92 us --
     // the last transform's 64 tiles then also carry the sweep's loads and the rim is a launch of its own)
-    if (lv.h2d->dev.theta != 0.0 && !chain) {
+    if (lv.h2d->dev.theta != 0.0 && (!chain || lv.h2d->ac)) {   // (Allen-Cahn has no epilogue kernel: always fused)
         const H2DFin fin{dst_slab, dst_ld, pl.d_dst, a_slab, pl.d_a, b_slab, pl.d_b, op, use_g, w, 1.0 - w};
         return h2d_phi_batch(e, lv, pl, in_slab, chain, &fin);
     }
@@ -2517,7 +2556,8 @@ int h2d_relax(mgrit_hip_engine *e, int lvl, RunList *rl, int mode, double weight
 bool h2d_block_ok(const Level &lv, int lvl) {
     // backward Euler, and (round 5) Crank-Nicolson: the explicit half of a step is diagonal in the same sine basis for an error
     // whose rim is zero -- every state of the level carries the boundary values there --, which h2d_block_solve checks per solve
-    if (!lv.h2d || lvl == 0 || !(lv.h2d->dev.theta == 1.0 || lv.h2d->dev.theta == 0.5)) return false;
+    // Never for Allen-Cahn: the block solve superposes block defects, which holds for a linear Phi only.
+    if (!lv.h2d || lv.h2d->ac || lvl == 0 || !(lv.h2d->dev.theta == 1.0 || lv.h2d->dev.theta == 0.5)) return false;
     const int N = lv.dev.n_pts - 1;
     return N >= 4 * MGRIT_HIP_BLOCK_K && N / MGRIT_HIP_BLOCK_K <= H2D_MAX_BATCH;
 }
@@ -2676,10 +2716,14 @@ int h2d_points_sumsq(mgrit_hip_engine *e, int lvl, RunList *rl, const double *pr
         if ((rc = h2d_reserve(lv, std::min(H2D_MAX_BATCH, pl.count)))) return rc;
         if (!prev) {
             if ((rc = h2d_phi_batch(e, lv, pl, lv.dev.u))) return rc;
-            hipLaunchKernelGGL(h2d_rowsq_kernel, dim3((H.nx + 63) / 64, pl.count), dim3(64), 0, e->stream, H, lv.h2d->W0, lv.dev.u,
-                               pl.d_in, pl.d_step, lv.dev.u, pl.d_dst, H2D_OP_RESIDUAL, lv.h2d->rowsq);
+            if (lv.h2d->ac)
+                hipLaunchKernelGGL((h2d_rowsq_kernel<true>), dim3((H.nx + 63) / 64, pl.count), dim3(64), 0, e->stream, H, lv.h2d->W0, lv.dev.u,
+                                   pl.d_in, pl.d_step, lv.dev.u, pl.d_dst, H2D_OP_RESIDUAL, lv.h2d->rowsq);
+            else
+                hipLaunchKernelGGL((h2d_rowsq_kernel<false>), dim3((H.nx + 63) / 64, pl.count), dim3(64), 0, e->stream, H, lv.h2d->W0, lv.dev.u,
+                                   pl.d_in, pl.d_step, lv.dev.u, pl.d_dst, H2D_OP_RESIDUAL, lv.h2d->rowsq);
         } else {
-            hipLaunchKernelGGL(h2d_rowsq_kernel, dim3((H.nx + 63) / 64, pl.count), dim3(64), 0, e->stream, H, lv.h2d->W0, lv.dev.u,
+            hipLaunchKernelGGL((h2d_rowsq_kernel<false>), dim3((H.nx + 63) / 64, pl.count), dim3(64), 0, e->stream, H, lv.h2d->W0, lv.dev.u,
                                pl.d_dst, pl.d_step, prev, pl.d_dst, H2D_OP_JUMP, lv.h2d->rowsq);
         }
         hipLaunchKernelGGL(h2d_rowsum_kernel, dim3((pl.count + 63) / 64), dim3(64), 0, e->stream, lv.h2d->rowsq, H.nx, pl.count,
@@ -3438,6 +3482,52 @@ int mgrit_hip_level_heat2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const 
     return 0;
 }
 
+int mgrit_hip_level_allencahn2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld, double inv_dx2,
+                                double inv_eps2, int nu) {
+    int rc = check_level(e, lvl, false);
+    if (rc) return rc;
+    if (nx < 4 || nx > 2048) return fail(MGRIT_HIP_EUNSUPPORTED, "Allen-Cahn grid %dx%d outside [4,2048]^2", nx, nx);
+    if (ld < nx * nx || (ld % 16) != 0) return fail(MGRIT_HIP_EINVAL, "ld=%d must be a multiple of 16 and >= nx*nx=%d", ld, nx * nx);
+    if (nu < 1 || nu > 64 || !(inv_dx2 > 0.0) || !(inv_eps2 > 0.0)) return fail(MGRIT_HIP_EINVAL, "bad Allen-Cahn parameters (nu=%d)", nu);
+    if (n_pts_local < 0 || (n_pts_local > 0 && !t_local)) return fail(MGRIT_HIP_EINVAL, "bad arguments");
+    Level &lv = e->L[lvl];
+    if (lv.set) return fail(MGRIT_HIP_EINVAL, "level %d already described", lvl);
+    H2DHost *h = new H2DHost();
+    lv.h2d = h;
+    h->ac = true; h->ac_inv_eps2 = inv_eps2; h->ac_nu = nu;
+    H2DDev &H = h->dev;
+    const int P = ((nx + 63) / 64) * 64;
+    H.nx = H.ny = H.mi = H.mj = nx; H.Mi = H.Mj = P;
+    h->HPx = h->HPy = P / 2;
+    h->ac_KP = ((nx + H2D_BK - 1) / H2D_BK) * H2D_BK;
+    H.K = 0; H.n_pts = n_pts_local; H.ld = ld; H.fx = H.fy = 0.0; H.theta = 1.0; H.has_w = 0;
+    h->dts.assign(n_pts_local > 0 ? n_pts_local : 0, 0.0);
+    for (int i = 1; i < n_pts_local; ++i) h->dts[i] = t_local[i] - t_local[i - 1];
+    // Hartley table (the angle reduced exactly: (i k) mod nx) and the eigenvalues of the periodic 5-point Laplacian
+    std::vector<double> tab((size_t)P * P, 0.0);
+    const long double two_pi = 6.283185307179586476925286766559L, s = 1.0L / sqrtl((long double)nx);
+    for (int i = 0; i < nx; ++i)
+        for (int k = 0; k < nx; ++k) {
+            const long double a = two_pi * (long double)(((long long)i * k) % nx) / (long double)nx;
+            tab[(size_t)i * P + k] = (double)((cosl(a) + sinl(a)) * s);
+        }
+    h->lx.assign(P, 0.0);
+    for (int k = 0; k < nx; ++k) {
+        const long double sn = sinl(two_pi * 0.5L * (long double)k / (long double)nx);
+        h->lx[k] = (double)(4.0L * (long double)inv_dx2 * sn * sn);
+    }
+    h->ly = h->lx;
+    double *d_dt;
+    if ((rc = dev_upload(lv, e->stream, tab, &h->acT))) return rc;
+    if ((rc = dev_upload(lv, e->stream, h->dts, &d_dt))) return rc;
+    H.dt = d_dt;
+    lv.dev.kind = MGRIT_HIP_STEPPER_ALLENCAHN2D;
+    lv.dev.n = nx * nx; lv.dev.ld = ld; lv.dev.T = 0; lv.dev.n_pts = n_pts_local; lv.dev.K = 0; lv.dev.stream_rows = 0;
+    lv.G = 0;
+    lv.set = true;
+    return 0;
+}
+
 int mgrit_hip_level_bind(mgrit_hip_engine *e, int lvl, double *u, double *v, double *g) {
     int rc = check_level(e, lvl);
     if (rc) return rc;
@@ -3468,7 +3558,7 @@ int mgrit_hip_level_heat2d_forcing_rows(mgrit_hip_engine *e, int lvl, const doub
     int rc = check_level(e, lvl);
     if (rc) return rc;
     Level &lv = e->L[lvl];
-    if (!lv.h2d) return fail(MGRIT_HIP_EUNSUPPORTED, "level %d is not a Heat2D level", lvl);
+    if (!lv.h2d || lv.h2d->ac) return fail(MGRIT_HIP_EUNSUPPORTED, "level %d is not a Heat2D level", lvl);
     if (rows && lv.h2d->dev.K != 0) return fail(MGRIT_HIP_EINVAL, "level %d already has %d separable forcing terms", lvl, lv.h2d->dev.K);
     lv.h2d->dev.fb = rows;
     return 0;

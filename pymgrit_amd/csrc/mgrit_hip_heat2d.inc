@@ -52,10 +52,13 @@ constexpr int H2D_BK = 32, H2D_LDT = 80;
 // from the state, rows >= m_real and columns >= n_real as the zeros the padded slab holds there, and the rhs launch with its
 // 2 x 8 B per point of HBM traffic falls away. The interior starts one point into a row, so these loads are 8-byte aligned only.
 typedef double d2u_t __attribute__((ext_vector_type(2), aligned(8)));
-template <bool FOLD, bool GRID = false>
+// PRE (with GRID): a pointwise map applied to every value staged from the state row before it enters the product -- the identity for
+// Heat2D, the non-linear right-hand side of the Allen-Cahn IMEX step (mgrit_hip_allencahn.inc)
+struct H2DIdentity { __device__ __forceinline__ double operator()(double x) const { return x; } };
+template <bool FOLD, bool GRID = false, class PRE = H2DIdentity>
 __device__ __forceinline__ void h2d_kloop(d4_t (&acc)[2][2], double *smem, const double *__restrict__ A, int lda, int m0,
                                           const double *__restrict__ Bb, int N, int n0, int KP, int m_real, int hO, double sign,
-                                          int tid, int lane, int w, int n_real = 0) {
+                                          int tid, int lane, int w, int n_real = 0, PRE pre = PRE()) {
     double(*As)[H2D_LDT] = reinterpret_cast<double(*)[H2D_LDT]>(smem);
     double(*Bs)[H2D_LDT] = reinterpret_cast<double(*)[H2D_LDT]>(smem + H2D_BK * H2D_LDT);
     const int wm = (w & 1) * 32, wn = (w >> 1) * 32;
@@ -87,8 +90,8 @@ __device__ __forceinline__ void h2d_kloop(d4_t (&acc)[2][2], double *smem, const
             d2_t bv = rb[h];
             if (GRID) {
                 const bool rv = (k0 + sr + 8 * h) < m_real;
-                bv.x = rv && cv0 ? bv.x : 0.0;
-                bv.y = rv && cv1 ? bv.y : 0.0;
+                bv.x = rv && cv0 ? pre(bv.x) : 0.0;
+                bv.y = rv && cv1 ? pre(bv.y) : 0.0;
             }
             if (FOLD) {
                 const double mult = (k0 + sr + 8 * h) < hO ? sign : 0.0;
@@ -358,6 +361,8 @@ __global__ void h2d_rim_kernel(H2DDev H, H2DFin F) {
 // through LDS to the lane that owns the row, which adds them in column order -- the chain of the oracle. (Round 4; as a thread
 // per row reading its row on its own, 64 rows 4 KB apart per load instruction, the residual check of config 4 took 18.4 us per
 // point against 10.5 for the Phi alone.)
+// FULL: U holds Phi on the whole grid, no rim (Allen-Cahn: periodic)
+template <bool FULL>
 __global__ void __launch_bounds__(64) h2d_rowsq_kernel(H2DDev H, const double *__restrict__ U, const double *__restrict__ in_slab,
                                                        const int32_t *__restrict__ in_idx, const int32_t *__restrict__ step_idx,
                                                        const double *__restrict__ cmp_slab, const int32_t *__restrict__ cmp_idx, int op,
@@ -375,7 +380,8 @@ __global__ void __launch_bounds__(64) h2d_rowsq_kernel(H2DDev H, const double *_
             double r = 0.0;
             if (gi < H.nx && gj < H.ny) {
                 const size_t p = (size_t)gi * H.ny + gj;
-                r = op == H2D_OP_RESIDUAL ? h2d_phi_value(H, U, uin, step, b, gi, gj) - cmp[p] : uin[p] - cmp[p];
+                r = op == H2D_OP_RESIDUAL ? (FULL ? U[((size_t)b * H.Mi + gi) * H.Mj + gj] : h2d_phi_value(H, U, uin, step, b, gi, gj)) - cmp[p]
+                                             : uin[p] - cmp[p];
             }
             tile[rr][lane] = r;
         }

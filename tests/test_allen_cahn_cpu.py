@@ -1,0 +1,179 @@
+"""AllenCahn on the host (no GPU): the three steppers against steps recorded from the reference (tests/golden/allen_cahn.*, written by
+tests/golden/make_golden_allen_cahn.py), the Hartley table, the plugin-path solves against the reference's residual histories, the
+device description and the package exports.
+
+Tolerances of an IMEX step, none of them measured on the code under test:
+  * ours: a product with an orthogonal n x n matrix is off by at most n eps (1 - n eps)^-1 times the vector's 2-norm, the spectral scale
+    is <= 1, so four products give  norm_F(error) <= (4 nx + 8) eps norm_F(b)  per Phi (the 8: pointwise right-hand side and scale);
+  * the reference's SuperLU solve: forward error <= cond * rho, cond = 1 + 8 dt / dx^2 (exact for I - dt L), rho its own relative
+    residual as recorded in the fixture; allowed: 4 * cond * rho * norm_inf(x_ref).
+"""
+import logging
+
+import numpy as np
+import pytest
+
+import cases
+
+META = cases.load_json("allen_cahn.json")
+ARR = np.load(cases.GOLDEN + "/allen_cahn.npz")
+EPS = cases.EPS
+
+
+def ours_bound(app, u, dt):
+    """(4 nx + 8) eps norm_F(b), b the right-hand side of the implicit solve"""
+    b = u + dt / app.eps ** 2 * u * (1.0 - u ** app.nu)
+    return (4 * app.nx + 8) * EPS * float(np.linalg.norm(b))
+
+
+def step_input(app, rec):
+    return np.asarray(app.initial_guess().get_values()) if rec["src"] == "init" else ARR[f"rand_nx{rec['nx']}"]
+
+
+def reference_bound(rec, x_ref):
+    cond = 1.0 + 8.0 * rec["dt"] * rec["nx"] ** 2
+    return 4.0 * cond * rec["rho"] * float(np.abs(x_ref).max())
+
+
+def apply_step(app, u, dt):
+    from pymgrit_amd import VectorAllenCahn2D
+    vec = VectorAllenCahn2D(app.nx, app.ny)
+    vec.set_values(np.array(u, dtype=np.float64))
+    return np.asarray(app.step(vec, 0.0, dt).get_values())
+
+
+@pytest.mark.parametrize("name", sorted(META["steps"]))
+def test_imex_step_matches_the_reference(name):
+    from pymgrit_amd import AllenCahn
+    rec = META["steps"][name]
+    app = AllenCahn(nx=rec["nx"], nu=rec["nu"], eps=rec["eps"], method="IMEX", t_start=0, t_stop=1, nt=2)
+    u, ref = step_input(app, rec), ARR["out_" + name]
+    got = apply_step(app, u, rec["dt"])
+    err, tol = float(np.abs(got - ref).max()), reference_bound(rec, ref) + ours_bound(app, u, rec["dt"])
+    print(f"{name}: err {err:.3e} allowed {tol:.3e} ({err / (EPS * (1 + 8 * rec['dt'] * rec['nx'] ** 2)):.1f} eps*cond)")
+    assert got.shape == ref.shape and err <= tol, (name, err, tol)
+
+
+@pytest.mark.parametrize("name", sorted(META["newton_steps"]))
+def test_newton_step_matches_the_reference(name):
+    """IMPL / CN: both sides stop Newton at norm_inf(g) < newton_tol = 1e-12. The Jacobian J = I - fac (L + diag((1 - (nu+1) u^nu) / eps^2))
+    is symmetric with eigenvalues >= 1 - fac / eps^2 (L is negative semi-definite, the diagonal term at most 1 / eps^2), so two iterates
+    whose residuals are below tol differ by at most  2 tol sqrt(N) / (1 - fac / eps^2)  in the 2-norm, N = nx^2 (second-order terms of
+    the cubic are far below that at this distance)."""
+    from pymgrit_amd import AllenCahn
+    rec = META["newton_steps"][name]
+    app = AllenCahn(nx=rec["nx"], nu=rec["nu"], eps=rec["eps"], method=rec["method"], t_start=0, t_stop=1, nt=2)
+    got = apply_step(app, np.asarray(app.initial_guess().get_values()), rec["dt"])
+    fac = rec["dt"] * (0.5 if rec["method"] == "CN" else 1.0)
+    tol = 2 * app.newton_tol * rec["nx"] / (1.0 - fac / rec["eps"] ** 2)
+    err = float(np.linalg.norm(got - ARR["out_" + name]))
+    print(f"{name}: err {err:.3e} allowed {tol:.3e}")
+    assert err <= tol, (name, err, tol)
+
+
+@pytest.mark.parametrize("n", [4, 9, 32, 63, 64, 130])
+def test_hartley_table_is_symmetric_and_its_own_inverse(n):
+    from pymgrit_amd.allen_cahn.allen_cahn import hartley_matrix
+    T = hartley_matrix(n)
+    assert np.array_equal(T, T.T)
+    assert np.abs(T @ T - np.eye(n)).max() <= n * EPS
+
+
+def test_laplacian_matrix_is_diagonal_in_the_hartley_basis():
+    from pymgrit_amd import AllenCahn
+    from pymgrit_amd.allen_cahn.allen_cahn import hartley_matrix, periodic_laplacian_eigenvalues
+    app = AllenCahn(nx=12, method="IMEX", t_start=0, t_stop=1, nt=2)
+    T, lam = hartley_matrix(12), periodic_laplacian_eigenvalues(12, app.dx)
+    K = np.kron(T, T)
+    D = K @ app.space_disc.toarray() @ K
+    want = -(lam[:, None] + lam[None, :]).ravel()
+    assert np.abs(D - np.diag(want)).max() <= 144 * EPS * np.abs(want).max()
+
+
+def _problem(rec, cls=None):
+    from pymgrit_amd import AllenCahn
+    cls = cls or AllenCahn
+    return [cls(nx=rec["nx"], method=rec["method"], t_start=0, t_stop=META["t_stop"], nt=nt) for nt in rec["nts"]]
+
+
+def check_history(name, conv, norm_u):
+    """|conv - reference| <= 1e-10 * reference + BLK_K * eps * norm(u) (tests/cases.py: histories whose Phi passes through SuperLU on
+    the reference side); prints the multiple of eps * norm(u) each history needs"""
+    ref = np.asarray(META["solve"][name]["conv"])
+    assert len(conv) == len(ref), (name, conv, ref)
+    dev = np.abs(np.asarray(conv) - ref)
+    unit = EPS * norm_u
+    print(f"{name}: largest deviation {np.max(dev / unit):.2f} units of eps*norm(u); beyond 1e-10 relative: "
+          f"{np.max(np.maximum(dev - 1e-10 * ref, 0.0) / unit):.2f}")
+    assert np.all(dev <= 1e-10 * ref + cases.BLK_K * unit), (name, conv, ref)
+
+
+@pytest.mark.parametrize("name", sorted(META["solve"]))
+def test_plugin_path_solves_match_the_reference_histories(name, caplog):
+    """the host steppers under pymgrit_amd's Mgrit (plugin path: a subclass that overrides step, or IMPL which has no device form)"""
+    from pymgrit_amd import AllenCahn, Mgrit
+
+    class HostAllenCahn(AllenCahn):
+        def step(self, u_start, t_start, t_stop):
+            return super().step(u_start, t_start, t_stop)
+
+    rec = META["solve"][name]
+    with caplog.at_level(logging.WARNING):
+        mg = Mgrit(_problem(rec, HostAllenCahn), logging_lvl=30, **rec["opts"])
+    assert type(mg.backend).__name__ == "PluginBackend"
+    conv = mg.solve()["conv"]
+    u = np.array([np.asarray(v.get_values()) for v in mg.u[0]])
+    check_history(name, conv, cases.spacetime_norm(u))
+    last = ARR["last_" + name]
+    assert np.abs(u[-1] - last).max() <= 1e-9 * np.abs(last).max()
+
+
+def test_device_stepper_describes_imex_only():
+    from pymgrit_amd import AllenCahn
+    d = AllenCahn(nx=16, nu=4, method="IMEX", t_start=0, t_stop=1, nt=3).device_stepper()
+    assert d["kind"] == "allencahn2d" and d["n"] == 256 and d["nx"] == 16 and d["nu"] == 4
+    assert d["inv_dx2"] == 1.0 / (1.0 / 16) ** 2 and d["inv_eps2"] == 1.0 / 0.04 ** 2
+    for method in ("IMPL", "CN"):
+        assert AllenCahn(nx=16, method=method, t_start=0, t_stop=1, nt=3).device_stepper() is None
+    assert AllenCahn(nx=16, t_start=0, t_stop=1, nt=3).method == "IMPL"
+
+
+def test_impl_hierarchy_selects_the_plugin_path():
+    from pymgrit_amd import AllenCahn, Mgrit
+    prob = [AllenCahn(nx=8, method="IMPL", t_start=0, t_stop=0.001, nt=nt) for nt in (5, 3)]
+    mg = Mgrit(prob, logging_lvl=30, max_iter=1)
+    assert type(mg.backend).__name__ == "PluginBackend"
+
+
+def test_unknown_method_raises_the_reference_text():
+    from pymgrit_amd import AllenCahn
+    with pytest.raises(Exception, match=r"Unknown method\. Choose IMPL \(implicit\), IMEX \(implicit-explicit\) or CN \(Crank-Nicolson"):
+        AllenCahn(nx=8, method="RK4", t_start=0, t_stop=1, nt=3)
+
+
+def test_package_exports():
+    import pymgrit_amd
+    from pymgrit_amd import AllenCahn, VectorAllenCahn2D, VectorHeat1D2Pts  # noqa: F401
+    for name in ("AllenCahn", "VectorAllenCahn2D", "VectorHeat1D2Pts"):
+        assert name in pymgrit_amd.__all__
+
+
+def test_vector_and_attributes():
+    from pymgrit_amd import AllenCahn, VectorAllenCahn2D
+    app = AllenCahn(nx=16, method="IMEX", t_start=0, t_stop=1, nt=3)
+    assert app.dx == 1.0 / 16 and app.ny == 16 and np.array_equal(app.x, np.linspace(-0.5, 0.5, 16))
+    assert app.space_disc.shape == (256, 256) and app.exact_radius(0.02) == np.sqrt(0.25 ** 2 - 0.04) and app.exact_radius(1.0) == 0.0
+    a, b = VectorAllenCahn2D(3, 3), VectorAllenCahn2D(3, 3)
+    a.set_values(np.full((3, 3), 2.0)); b.set_values(np.ones((3, 3)))
+    assert np.array_equal((a + b).get_values(), np.full((3, 3), 3.0)) and np.array_equal((a - b * 0.5).get_values(), np.full((3, 3), 1.5))
+    assert a.norm() == 6.0 and a.clone_zero().norm() == 0.0 and a.clone().get_values() is not None
+    assert a.clone_rand().get_values().shape == (3, 3) and a.pack() is a.get_values()
+
+
+@pytest.mark.parametrize("nx", [64, 128])
+def test_radius_of_the_initial_condition(nx):
+    from pymgrit_amd import AllenCahn
+    app = AllenCahn(nx=nx, method="IMEX", t_start=0, t_stop=1, nt=3)
+    assert abs(app.compute_radius(app.initial_guess()) - app.radius) <= app.dx
+    ref = ARR["out_imex_init_nx64_nu2_dt0.0001"]
+    assert ref.shape == (64, 64)
