@@ -1,12 +1,14 @@
 """AllenCahn on the host (no GPU): the three steppers against steps recorded from the reference (tests/golden/allen_cahn.*, written by
 tests/golden/make_golden_allen_cahn.py), the Hartley table, the plugin-path solves against the reference's residual histories, the
-device description and the package exports.
+device description and the package exports; and the host IMEX step against an independent high-precision solve that uses no transform
+(tests/allen_cahn_reference.py: sparse LU start, iterative refinement in long double), itself checked against the recorded steps.
 
 Tolerances of an IMEX step, none of them measured on the code under test:
   * ours: a product with an orthogonal n x n matrix is off by at most n eps (1 - n eps)^-1 times the vector's 2-norm, the spectral scale
     is <= 1, so four products give  norm_F(error) <= (4 nx + 8) eps norm_F(b)  per Phi (the 8: pointwise right-hand side and scale);
   * the reference's SuperLU solve: forward error <= cond * rho, cond = 1 + 8 dt / dx^2 (exact for I - dt L), rho its own relative
-    residual as recorded in the fixture; allowed: 4 * cond * rho * norm_inf(x_ref).
+    residual as recorded in the fixture; allowed: 4 * cond * rho * norm_inf(x_ref);
+  * reference_phi (allen_cahn_reference.py): EPS norm_F(b), the rounding of its long-double solution to float64.
 """
 import logging
 
@@ -52,6 +54,53 @@ def test_imex_step_matches_the_reference(name):
     err, tol = float(np.abs(got - ref).max()), reference_bound(rec, ref) + ours_bound(app, u, rec["dt"])
     print(f"{name}: err {err:.3e} allowed {tol:.3e} ({err / (EPS * (1 + 8 * rec['dt'] * rec['nx'] ** 2)):.1f} eps*cond)")
     assert got.shape == ref.shape and err <= tol, (name, err, tol)
+
+
+@pytest.mark.parametrize("name", sorted(META["steps"]))
+def test_reference_phi_matches_the_recorded_steps(name):
+    """the transform-free long-double solve against the reference's recorded SuperLU steps: the recorded side's own bound plus
+    EPS norm_F(b) for the rounding of reference_phi's result"""
+    from pymgrit_amd import AllenCahn
+    from allen_cahn_reference import reference_phi
+    rec = META["steps"][name]
+    app = AllenCahn(nx=rec["nx"], nu=rec["nu"], eps=rec["eps"], method="IMEX", t_start=0, t_stop=1, nt=2)
+    u, ref = step_input(app, rec), ARR["out_" + name]
+    got = reference_phi(u, rec["dt"], rec["nx"], rec["nu"], rec["eps"])
+    b = u + rec["dt"] / rec["eps"] ** 2 * u * (1.0 - u ** rec["nu"])
+    err, tol = float(np.abs(got - ref).max()), reference_bound(rec, ref) + EPS * float(np.linalg.norm(b))
+    print(f"{name}: err {err:.3e} allowed {tol:.3e}")
+    assert got.shape == ref.shape and got.dtype == np.float64 and err <= tol, (name, err, tol)
+
+
+REF_NX = [4, 9, 20, 33, 63, 64, 66, 96, 97, 129, 130, 200]   # the smallest grid, K steps and tiles of the device product +- 1, KP < P (96)
+REF_DT = [1.25e-4, 3.1e-4, 1e-3]
+
+
+@pytest.mark.parametrize("nu", [1, 2, 3, 4])
+@pytest.mark.parametrize("nx", REF_NX)
+def test_host_imex_step_matches_the_high_precision_solve(nx, nu):
+    """_step_imex (Hartley table, lam_k, T((TbT) o D)T) against reference_phi, which shares none of it: a wrong eigenvalue, mode order
+    or reaction term for this nu shows here. norm_F(error) <= (4 nx + 8) EPS norm_F(b) for the step + EPS norm_F(b) for the reference."""
+    from pymgrit_amd import AllenCahn
+    from allen_cahn_reference import reference_phi
+    app = AllenCahn(nx=nx, nu=nu, method="IMEX", t_start=0, t_stop=1, nt=2)
+    rng = np.random.default_rng(1000 * nx + nu)
+    worst = 0.0
+    for dt in REF_DT:
+        inputs = [(f"uniform[-{a}, {a}]", rng.uniform(-a, a, size=(nx, nx))) for a in (1.0, 1.5)]
+        inputs += [(f"constant {v}", np.full((nx, nx), v)) for v in (0.0, 1.0, -1.0)]
+        for what, u in inputs:
+            got, ref = apply_step(app, u, dt), reference_phi(u, dt, nx, nu, app.eps)
+            b_norm = float(np.linalg.norm(u + dt / app.eps ** 2 * u * (1.0 - u ** nu)))
+            err, tol = float(np.linalg.norm(got - ref)), ours_bound(app, u, dt) + EPS * b_norm
+            ratio = err / tol if tol > 0.0 else 0.0
+            worst = max(worst, ratio)
+            print(f"nx={nx} nu={nu} dt={dt} {what}: error/bound {ratio:.4f}")
+            assert got.shape == ref.shape == (nx, nx) and err <= tol, (nx, nu, dt, what, err, tol)
+            if what.startswith("constant") and (u[0, 0] >= 0.0 or nu % 2 == 0):
+                # constants are mode 0 with D = 1, and u (1 - u^nu) = 0 at 0, at 1 and (even nu) at -1: Phi(u) = b = u
+                assert np.array_equal(ref, u), (nx, nu, dt, what)
+    print(f"nx={nx} nu={nu}: worst error/bound {worst:.4f}")
 
 
 @pytest.mark.parametrize("name", sorted(META["newton_steps"]))

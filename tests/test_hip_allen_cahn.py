@@ -1,7 +1,9 @@
 """GPU tests of the Allen-Cahn IMEX stepper (csrc/mgrit_hip_allencahn.inc): every sweep of the device path against the SAME hierarchy on
 the plugin path (the host ``step``), single steps against the reference fixtures (tests/golden/allen_cahn.*), solves against the
-reference's residual histories. The oracle has no Allen-Cahn variant, so nothing here is bit for bit against another implementation;
-the bounds are derived (test_allen_cahn_cpu.py states them):
+reference's residual histories. The oracle has no Allen-Cahn variant, so nothing here is bit for bit against another implementation:
+the host step of this file is the same formula as the device's. The second implementation the device path is held against is the
+transform-free long-double solve of tests/allen_cahn_reference.py, in tests/test_hip_allen_cahn_reference.py (size edges, other
+exponents, several step sizes per level, sweeps of more than one batch). The bounds are derived (test_allen_cahn_cpu.py states them):
 
   per Phi, one evaluation:                 norm_F(error) <= (4 nx + 8) eps norm_F(b)
   two independent evaluations (host, device):   twice that                                                          = TOL
@@ -96,6 +98,7 @@ def _compare(dev, host, lvl, allowed, what):
         worst = max(worst, err)
         assert err <= allowed, (what, name, lvl, err, allowed)
     print(f"{what} level {lvl}: worst row error {worst:.3e}, allowed {allowed:.3e}")
+    return worst
 
 
 SIZES = [9, 20, 63, 64, 66, 130, 200]
