@@ -40,7 +40,12 @@ enum { MGRIT_HIP_TRANSFER_COPY = 0, MGRIT_HIP_TRANSFER_HEAT1D = 1, MGRIT_HIP_TRA
        /* the caller applies restriction / interpolation itself (a user's GridTransfer, reference core/grid_transfer.py:31-55:
           any Python code): mgrit_hip_restrict_u / _fas_rhs / _error_correction / _interpolate refuse the level pair, the FAS
           right-hand side is taken in two halves around the caller's restriction (mgrit_hip_fas_fine_rows / _fas_coarse) */
-       MGRIT_HIP_TRANSFER_CALLER = 3 };
+       MGRIT_HIP_TRANSFER_CALLER = 3,
+       /* 2-D grids halved per axis (no reference class; arithmetic: DESIGN.md 3.10, csrc/mgrit_hip_transfer2d.inc): between two Heat2D
+          levels, grids with their rim, fine nx = 2*coarse nx - 1 and fine ny = 2*coarse ny - 1 (rim injected, interior 9-point full
+          weighting, bilinear interpolation); between two Allen-Cahn levels, periodic, fine nx = 2*coarse nx (the same stencils with
+          wrap-around). The sizes are those of the level descriptions; any other pairing is MGRIT_HIP_EUNSUPPORTED. */
+       MGRIT_HIP_TRANSFER_HEAT2D = 4, MGRIT_HIP_TRANSFER_PERIODIC2D = 5 };
 enum { MGRIT_HIP_RELAX_F = 0, MGRIT_HIP_RELAX_C = 1, MGRIT_HIP_RELAX_CHAIN = 2,
        /* f_relax + c_relax (mgrit.py:270-275) of a level > 0 in one pass, valid right after the finer level's FAS sweep has
           filled the level (u == v): a run = the F-points of an interval and the C-point closing it, started from v of the
@@ -165,7 +170,8 @@ int mgrit_hip_block_solve_state(mgrit_hip_engine *e, int lvl, int *r_out);
 int mgrit_hip_block_solve_form(mgrit_hip_engine *e, int lvl, int *form_out);
 /* Spatial transfer between lvl and lvl+1: GridTransferCopy (core/grid_transfer_copy.py:23-47) or the full-weighting
  * / linear-interpolation pair of examples/example_spatial_coarsening.py:33-82 (fine n = 2*coarse n + 1), or its periodic
- * analogue for Advection1D grids (fine n = 2*coarse n; no reference class exists, BASELINE config 5). */
+ * analogue for Advection1D grids (fine n = 2*coarse n; no reference class exists, BASELINE config 5), or one of the 2-D pairs
+ * MGRIT_HIP_TRANSFER_HEAT2D / _PERIODIC2D between two Heat2D / two Allen-Cahn levels. */
 int mgrit_hip_level_transfer(mgrit_hip_engine *e, int lvl, int kind);
 
 /*

@@ -15,6 +15,7 @@ TIMED_KINDS = ("relax_f", "relax_c", "chain", "residual", "jump", "restrict", "c
 STEPPER_HEAT1D, STEPPER_ADVECTION1D = 1, 2
 STEPPER_ALLENCAHN2D = 5
 TRANSFER_COPY, TRANSFER_HEAT1D, TRANSFER_CALLER = 0, 1, 3
+TRANSFER_HEAT2D, TRANSFER_PERIODIC2D = 4, 5
 MAX_N = 16384
 MAX_LINKS = 16
 BLOCK_K, BLOCK_RMAX = 16, 256     # time-parallel forward solve

@@ -1479,6 +1479,8 @@ __global__ void interp_rows_kernel(double *__restrict__ uf, int f_ld, int T_f, c
 
 #include "mgrit_hip_allencahn.inc"
 
+#include "mgrit_hip_transfer2d.inc"
+
 #include "mgrit_hip_wide.inc"
 
 #include "mgrit_hip_gen.inc"
@@ -3661,6 +3663,16 @@ int mgrit_hip_level_transfer(mgrit_hip_engine *e, int lvl, int kind) {
         if (nf != 2 * nc) return fail(MGRIT_HIP_EINVAL, "periodic transfer needs n_fine = 2*n_coarse (%d vs %d)", nf, nc);
     } else if (kind == MGRIT_HIP_TRANSFER_CALLER) {
         if (!e->L[lvl].h2d != !e->L[lvl + 1].h2d) return fail(MGRIT_HIP_EUNSUPPORTED, "a caller's transfer joins two Heat2D levels or two 1-D levels");
+    } else if (kind == MGRIT_HIP_TRANSFER_HEAT2D || kind == MGRIT_HIP_TRANSFER_PERIODIC2D) {
+        const H2DHost *hf = e->L[lvl].h2d, *hc = e->L[lvl + 1].h2d;
+        const bool per = kind == MGRIT_HIP_TRANSFER_PERIODIC2D;
+        if (!hf || !hc || hf->ac != per || hc->ac != per)
+            return fail(MGRIT_HIP_EUNSUPPORTED, per ? "the periodic 2-D transfer joins two Allen-Cahn levels" : "the Heat2D transfer joins two Heat2D levels");
+        const int off = per ? 0 : 1;
+        if (2 * hc->dev.nx - off != hf->dev.nx || 2 * hc->dev.ny - off != hf->dev.ny)
+            return fail(MGRIT_HIP_EINVAL, per ? "periodic 2-D transfer needs n_fine = 2*n_coarse per axis (%dx%d vs %dx%d)"
+                                              : "Heat2D transfer needs n_fine = 2*n_coarse-1 per axis (%dx%d vs %dx%d)",
+                        hf->dev.nx, hf->dev.ny, hc->dev.nx, hc->dev.ny);
     } else return fail(MGRIT_HIP_EINVAL, "unknown transfer kind %d", kind);
     e->L[lvl].transfer = kind;
     return 0;
@@ -3687,6 +3699,18 @@ int mgrit_hip_runs_create(mgrit_hip_engine *e, int lvl, int n_runs, const int32_
     return 0;
 }
 
+// rows of the level's scratch slab: a bigger need than any before gets a NEW slab, the old one stays alive until the engine goes
+// (lf.allocs) -- a captured cycle that ran a sweep on a block's shorter list still launches with its address
+static int scratch_reserve(Level &lf, size_t rows) {
+    if (lf.scratch_rows >= rows) return 0;
+    if (lf.scratch) lf.allocs.push_back(lf.scratch);
+    lf.scratch = nullptr;
+    lf.scratch_rows = 0;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&lf.scratch), sizeof(double) * rows * lf.dev.ld));
+    lf.scratch_rows = rows;
+    return 0;
+}
+
 int mgrit_hip_pairs_create(mgrit_hip_engine *e, int lvl, int n_pairs, const int32_t *fine_idx, const int32_t *coarse_idx,
                            int *id_out) {
     int rc = check_level(e, lvl);
@@ -3708,6 +3732,10 @@ int mgrit_hip_pairs_create(mgrit_hip_engine *e, int lvl, int n_pairs, const int3
     if ((rc = dev_upload(lv, e->stream, hf, &pl.d_fine))) return rc;
     if ((rc = dev_upload(lv, e->stream, hc, &pl.d_coarse))) return rc;
     if ((rc = dev_upload(lv, e->stream, iota, &pl.d_iota))) return rc;
+    // a 2-D library transfer takes the fine half of the FAS right-hand side through scratch rows of the level (h2d_fas_rhs_2d): the
+    // slab is sized here, where lists are made, so that the sweep itself -- possibly part of a captured or replayed cycle -- never allocates
+    if ((lv.transfer == MGRIT_HIP_TRANSFER_HEAT2D || lv.transfer == MGRIT_HIP_TRANSFER_PERIODIC2D) && (rc = scratch_reserve(lv, (size_t)n_pairs)))
+        return rc;
     lv.pairs.push_back(pl);
     *id_out = (int)lv.pairs.size() - 1;
     return 0;
@@ -3842,6 +3870,58 @@ static int caller_transfer(const Level &lf, int lvl) {
     return 0;
 }
 
+// the 2-D library transfers (mgrit_hip_transfer2d.inc); mgrit_hip_level_transfer has checked the pairing and the sizes
+static bool transfer_2d(const Level &lf) {
+    return lf.transfer == MGRIT_HIP_TRANSFER_HEAT2D || lf.transfer == MGRIT_HIP_TRANSFER_PERIODIC2D;
+}
+
+static T2DGeom t2d_geom(const Level &lf, const Level &lc) {
+    return T2DGeom{lf.h2d->dev.nx, lf.h2d->dev.ny, lc.h2d->dev.nx, lc.h2d->dev.ny, lf.transfer == MGRIT_HIP_TRANSFER_PERIODIC2D ? 1 : 0};
+}
+
+static int restrict2d_launch(mgrit_hip_engine *e, const Level &lf, const Level &lc, const double *src, const int32_t *s_idx, double *dst,
+                             const PairList *pl) {
+    const dim3 grid(pl->n, (lc.dev.ld + 255) / 256);
+    hipLaunchKernelGGL(restrict2d_rows_kernel, grid, dim3(256), 0, e->stream, src, lf.dev.ld, s_idx, dst, lc.dev.ld, pl->d_coarse,
+                       t2d_geom(lf, lc));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+static int interp2d_launch(mgrit_hip_engine *e, const Level &lf, const Level &lc, const PairList *pl, int mode, double *rows_out, int ld_out) {
+    const dim3 grid(pl->n, (lf.dev.n + 255) / 256);
+    hipLaunchKernelGGL(interp2d_rows_kernel, grid, dim3(256), 0, e->stream, lf.dev.u, lf.dev.ld, pl->d_fine, lc.dev.u, lc.dev.v, lc.dev.ld,
+                       pl->d_coarse, t2d_geom(lf, lc), mode, rows_out, ld_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// FAS right-hand side around a 2-D library transfer: the fine half through the batched Phi into the level's scratch rows (one per
+// pair), their restriction into g^{l+1}, the coarse half -- the composition mgrit_hip_fas_fine_rows / the caller's restriction /
+// mgrit_hip_fas_coarse, with the restriction as a kernel. The slab is sized when the pair list is made (mgrit_hip_pairs_create); the
+// call here finds it large enough.
+static int h2d_fas_rhs_2d(mgrit_hip_engine *e, int lvl, PairList *pl) {
+    Level &lf = e->L[lvl], &lc = e->L[lvl + 1];
+    int rc;
+    if ((rc = scratch_reserve(lf, (size_t)pl->n))) return rc;
+    if (pl->h2d_rows.empty()) {
+        std::vector<H2DItem> fine;
+        for (int p = 0; p < pl->n; ++p) fine.push_back({pl->h_fine[p] - 1, pl->h_fine[p], p, pl->h_fine[p], pl->h_fine[p]});
+        if ((rc = h2d_make_plans(e, lf, fine, pl->h2d_rows))) return rc;
+    }
+    if (pl->h2d_coarse.empty()) {
+        std::vector<H2DItem> coarse;
+        for (int p = 0; p < pl->n; ++p) { const int j = pl->h_coarse[p]; coarse.push_back({j - 1, j, j, j, j}); }
+        if ((rc = h2d_make_plans(e, lc, coarse, pl->h2d_coarse))) return rc;
+    }
+    for (const H2DPlan &q : pl->h2d_rows)
+        if ((rc = h2d_phi_op(e, lf, q, lf.dev.u, lf.scratch, lf.dev.ld, lf.dev.g, lf.dev.u, H2D_OP_FAS_FINE, lvl > 0 ? 1 : 0, 1.0))) return rc;
+    if ((rc = restrict2d_launch(e, lf, lc, lf.scratch, pl->d_iota, lc.dev.g, pl))) return rc;
+    for (const H2DPlan &q : pl->h2d_coarse)
+        if ((rc = h2d_phi_op(e, lc, q, lc.dev.v, lc.dev.g, lc.dev.ld, lc.dev.g, lc.dev.v, H2D_OP_FAS_COARSE, 1, 1.0))) return rc;
+    return 0;
+}
+
 int mgrit_hip_restrict_u(mgrit_hip_engine *e, int lvl, int pairs_id) {
     PairList *pl;
     int rc = get_pairs(e, lvl, pairs_id, &pl);
@@ -3851,6 +3931,7 @@ int mgrit_hip_restrict_u(mgrit_hip_engine *e, int lvl, int pairs_id) {
     if ((rc = check_bound(lf, false)) || (rc = check_bound(lc, false))) return rc;
     if (pl->n == 0) return 0;
     Timed timed(e, MGRIT_HIP_T_RESTRICT, lvl);
+    if (transfer_2d(lf)) return restrict2d_launch(e, lf, lc, lf.dev.u, pl->d_fine, lc.dev.u, pl);
     dim3 grid(pl->n, (lc.dev.ld + 255) / 256);
     hipLaunchKernelGGL(restrict_rows_kernel, grid, dim3(256), 0, e->stream, lf.dev.u, lf.dev.ld, lf.dev.T, pl->d_fine, lc.dev.u,
                        lc.dev.ld, lc.dev.T, pl->d_coarse, lc.dev.n, lf.transfer);
@@ -3936,6 +4017,7 @@ int mgrit_hip_fas_rhs(mgrit_hip_engine *e, int lvl, int pairs_id) {
     if (pl->n == 0) return 0;
     Timed timed(e, MGRIT_HIP_T_FAS_RHS, lvl);
     if (lf.h2d || lc.h2d) {
+        if (transfer_2d(lf)) return h2d_fas_rhs_2d(e, lvl, pl);
         if (!lf.h2d || !lc.h2d || lf.transfer != MGRIT_HIP_TRANSFER_COPY)
             return fail(MGRIT_HIP_EUNSUPPORTED, "Heat2D levels need Heat2D on both levels and the copy transfer");
         return h2d_fas_rhs(e, lvl, pl);
@@ -4049,6 +4131,7 @@ static int interp_common(mgrit_hip_engine *e, int lvl, int pairs_id, int mode) {
     if ((rc = check_bound(lf, false)) || (rc = check_bound(lc, mode == 1))) return rc;
     if (pl->n == 0) return 0;
     Timed timed(e, mode == 1 ? MGRIT_HIP_T_ERROR_CORRECTION : MGRIT_HIP_T_INTERPOLATE, lvl);
+    if (transfer_2d(lf)) return interp2d_launch(e, lf, lc, pl, mode, nullptr, 0);
     dim3 grid(pl->n, (lf.dev.ld + 255) / 256);
     hipLaunchKernelGGL(interp_rows_kernel, grid, dim3(256), 0, e->stream, lf.dev.u, lf.dev.ld, lf.dev.T, pl->d_fine, lc.dev.u,
                        lc.dev.v, lc.dev.ld, lc.dev.T, pl->d_coarse, lf.dev.n, lc.dev.n, lf.transfer, mode, (double *)nullptr, 0);

@@ -452,9 +452,11 @@ int mgrit_hip_error_correction_to(mgrit_hip_engine *e, int lvl, int pairs_id, do
     if ((rc = caller_transfer(lf, lvl))) return rc;
     if ((rc = check_bound(lf, false)) || (rc = check_bound(lc, true))) return rc;
     if (!rows_out || ld_out < lf.dev.ld) return fail(MGRIT_HIP_EINVAL, "bad output rows");
-    if (lf.h2d || is_2pts(lf)) return fail(MGRIT_HIP_EUNSUPPORTED, "error correction into caller rows: 1-D one-point steppers");
+    if ((lf.h2d && !transfer_2d(lf)) || is_2pts(lf))
+        return fail(MGRIT_HIP_EUNSUPPORTED, "error correction into caller rows: 1-D one-point steppers, or 2-D levels joined by a 2-D library transfer");
     if (pl->n == 0) return 0;
     Timed timed(e, MGRIT_HIP_T_ERROR_CORRECTION, lvl);
+    if (transfer_2d(lf)) return interp2d_launch(e, lf, lc, pl, 1, rows_out, ld_out);
     dim3 grid(pl->n, (lf.dev.ld + 255) / 256);
     hipLaunchKernelGGL(interp_rows_kernel, grid, dim3(256), 0, e->stream, lf.dev.u, lf.dev.ld, lf.dev.T, pl->d_fine, lc.dev.u,
                        lc.dev.v, lc.dev.ld, lc.dev.T, pl->d_coarse, lf.dev.n, lc.dev.n, lf.transfer, 1, rows_out, ld_out);
