@@ -1490,20 +1490,21 @@ __global__ void interp_rows_kernel(double *__restrict__ uf, int f_ld, int T_f, c
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-struct H2DPlan { int count = 0; uint64_t dtbits = 0; int32_t *d_in = nullptr, *d_step = nullptr, *d_dst = nullptr, *d_a = nullptr, *d_b = nullptr; };
+// the batched route (Heat2D, Allen-Cahn and wide 1-D levels): one batch of a sweep, and a sweep's batches, built on first use
+// (batch_plans_once)
+struct BatchPlan { int count = 0; uint64_t dtbits = 0; int32_t *d_in = nullptr, *d_step = nullptr, *d_dst = nullptr, *d_a = nullptr, *d_b = nullptr; };
+struct BatchPlans { std::vector<BatchPlan> plans; bool built = false; };
 struct RunList {
     int n = 0;
     int32_t *d_start = nullptr, *d_len = nullptr, *d_ec = nullptr;  // d_ec: mgrit_hip_ec_runs_create only
     std::vector<int32_t> h_start, h_len;
-    std::vector<H2DPlan> h2d_relax, h2d_points;  // Heat2D batch plans (built on first use)
-    bool h2d_relax_built = false, h2d_points_built = false;
+    BatchPlans relax, points;
 };
 struct PairList {
     int n = 0;
     int32_t *d_fine = nullptr, *d_coarse = nullptr, *d_iota = nullptr, *d_prev = nullptr;
     std::vector<int32_t> h_fine, h_coarse;
-    std::vector<H2DPlan> h2d_fine, h2d_coarse, h2d_rows;   // (h2d_rows: the fine half into caller rows, mgrit_hip_fas_fine_rows)
-    bool h2d_built = false;
+    BatchPlans fine_to_coarse, fine_to_rows, coarse;   // fine half into g^{l+1} (dst: the coarse slot) or into rows (dst: the pair's position)
 };
 
 struct H2DHost {
@@ -1520,7 +1521,7 @@ struct H2DHost {
     struct Blk {
         bool built = false;
         int B = 0;
-        std::vector<std::vector<H2DPlan>> p1, p3;
+        std::vector<std::vector<BatchPlan>> p1, p3;
         int32_t *d_iota = nullptr, *d_end_all = nullptr, *d_end_tail = nullptr, *d_dsel = nullptr;   // 0 .. B-1; rows e_0 .. e_{B-1}; e_1 .. e_{B-1}; table of block b
         double *spec = nullptr, *Dtab = nullptr, *X = nullptr, *Y = nullptr;   // spectra; propagator tables; the blocks' errors x and inputs u + x
         unsigned *rim_flag = nullptr;   // pinned, device-mapped (theta < 1): set when an error at a block end has a non-zero rim
@@ -1610,7 +1611,7 @@ struct Level {
                                        // the LDS copy of the kernels that keep the factor there (FORCE 4)
     double *scratch = nullptr;
     size_t scratch_rows = 0;
-    struct AtPlans { int32_t *d_src = nullptr, *d_own = nullptr; int count = 0; std::vector<std::vector<H2DPlan>> steps; };
+    struct AtPlans { int32_t *d_src = nullptr, *d_own = nullptr; int count = 0; BatchPlans steps; };
     std::map<int, AtPlans> at_plans;   // batched truncated solves (mgrit_hip_at_solve on Heat2D / wide levels), by distance k
     double *gen_rows = nullptr;      // mgrit_hip_gen_down / _up: [res_len][ld] uncorrected chunk-end C-points
     size_t gen_len = 0;              // res_len they were sized for
@@ -2331,9 +2332,10 @@ int level_heat1d_2pts(mgrit_hip_engine *e, int lvl, int n_pts, const double *t_l
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Heat2D host side: tables, batch plans, the batched Phi pipeline
+// Batch plans of the batched route (Heat2D, Allen-Cahn, wide 1-D); Heat2D host side: tables, the batched Phi pipeline
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int H2D_MAX_BATCH = 1024;  // items per GEMM batch (work buffers: 2 x 1024 x Mi x Mj doubles; 2048 measured no faster)
+constexpr int WIDE_MAX_BATCH = 2048;   // wide 1-D levels: items per batch (work slab: 2048 rows of up to 512 KB)
 
 uint64_t dbl_bits(double v) { uint64_t b; std::memcpy(&b, &v, 8); return b; }
 
@@ -2343,27 +2345,29 @@ int dev_upload_raw(Level &lv, hipStream_t st, const T *h, size_t n, T **out) {
     return dev_upload(lv, st, tmp, out);
 }
 
-// group batch items by the time-step size of their step index (one D table per group)
-struct H2DItem { int32_t in, step, dst, a, b; };
+// One item of a batch: row `in` of the input slab takes step `step`; the sweep's arithmetic writes row `dst` from rows `a`, `b`.
+struct BatchItem { int32_t in, step, dst, a, b; };
+using BatchItems = std::vector<std::vector<BatchItem>>;   // the item lists of a sweep, in launch order
 
-int h2d_make_plans(mgrit_hip_engine *e, Level &lv, const std::vector<H2DItem> &items, std::vector<H2DPlan> &plans) {
-    H2DHost &h = *lv.h2d;
-    std::vector<uint64_t> keys;
-    for (const H2DItem &it : items) {
-        const uint64_t k = dbl_bits(h.dts[it.step]);
-        bool seen = false;
-        for (uint64_t q : keys) seen = seen || q == k;
-        if (!seen) keys.push_back(k);
+// Plans of one item list: grouped by key in first-seen key order -- Heat2D / Allen-Cahn: the time-step size of the item's step
+// (one D table per group); wide: one key, so item order is kept (wide_points_sumsq relies on it) --, each group in batches
+int batch_make_plans(mgrit_hip_engine *e, Level &lv, const std::vector<BatchItem> &items, std::vector<BatchPlan> &out) {
+    const size_t max_batch = lv.h2d ? H2D_MAX_BATCH : WIDE_MAX_BATCH;
+    std::vector<uint64_t> item_key, keys;
+    for (const BatchItem &it : items) {
+        item_key.push_back(lv.h2d ? dbl_bits(lv.h2d->dts[it.step]) : 0);
+        if (std::find(keys.begin(), keys.end(), item_key.back()) == keys.end()) keys.push_back(item_key.back());
     }
     for (uint64_t k : keys) {
         std::vector<int32_t> vin, vst, vds, va, vb;
-        for (const H2DItem &it : items)
-            if (dbl_bits(h.dts[it.step]) == k) {
+        for (size_t q = 0; q < items.size(); ++q)
+            if (item_key[q] == k) {
+                const BatchItem &it = items[q];
                 vin.push_back(it.in); vst.push_back(it.step); vds.push_back(it.dst); va.push_back(it.a); vb.push_back(it.b);
             }
-        for (size_t off = 0; off < vin.size(); off += H2D_MAX_BATCH) {
-            const size_t cnt = std::min<size_t>(H2D_MAX_BATCH, vin.size() - off);
-            H2DPlan pl;
+        for (size_t off = 0; off < vin.size(); off += max_batch) {
+            const size_t cnt = std::min(max_batch, vin.size() - off);
+            BatchPlan pl;
             pl.count = (int)cnt;
             pl.dtbits = k;
             int rc;
@@ -2372,10 +2376,71 @@ int h2d_make_plans(mgrit_hip_engine *e, Level &lv, const std::vector<H2DItem> &i
             if ((rc = dev_upload_raw(lv, e->stream, vds.data() + off, cnt, &pl.d_dst))) return rc;
             if ((rc = dev_upload_raw(lv, e->stream, va.data() + off, cnt, &pl.d_a))) return rc;
             if ((rc = dev_upload_raw(lv, e->stream, vb.data() + off, cnt, &pl.d_b))) return rc;
-            plans.push_back(pl);
+            out.push_back(pl);
         }
     }
     return 0;
+}
+
+// The one "built once" rule of the route: the plans of a sweep are made on its first use and never appended to afterwards.
+template <typename MakeItems>
+int batch_plans_once(mgrit_hip_engine *e, Level &lv, BatchPlans &bp, MakeItems make_items) {
+    if (bp.built) return 0;
+    std::vector<BatchPlan> plans;
+    for (const std::vector<BatchItem> &items : make_items()) {
+        const int rc = batch_make_plans(e, lv, items, plans);
+        if (rc) return rc;
+    }
+    bp.plans = std::move(plans);
+    bp.built = true;
+    return 0;
+}
+
+// The four item generators. Step k of every run that is long enough is one list: u_i = g_i + Phi(u_{i-1}) in run order
+BatchItems run_step_items(const RunList &rl) {
+    BatchItems out;
+    for (int k = 0;; ++k) {
+        std::vector<BatchItem> items;
+        for (int r = 0; r < rl.n; ++r)
+            if (rl.h_len[r] > k) {
+                const int i = rl.h_start[r] + k;
+                items.push_back({i - 1, i, i, i, i});
+            }
+        if (items.empty()) return out;
+        out.push_back(items);
+    }
+}
+
+// the runs' first points (residual, jump). The kernels of the two routes differ in where a point's sum goes: the Heat2D row sum
+// scatters through d_b, so b is the point's position in the list; the wide kernels take b = i as a row of u and write the sums
+// in plan order
+BatchItems point_items(const Level &lv, const RunList &rl) {
+    std::vector<BatchItem> items;
+    for (int r = 0; r < rl.n; ++r) {
+        const int i = rl.h_start[r];
+        items.push_back({i - 1, i, i, i, lv.h2d ? r : i});
+    }
+    return {items};
+}
+
+// fine half of the FAS right-hand side: in = u_{i-1}, a = g^l_i, b = u^l_i; dst = the pair's position or the coarse slot g^{l+1}_j
+BatchItems fas_fine_items(const PairList &pl, bool by_pair) {
+    std::vector<BatchItem> items;
+    for (int p = 0; p < pl.n; ++p) {
+        const int i = pl.h_fine[p];
+        items.push_back({i - 1, i, by_pair ? p : pl.h_coarse[p], i, i});
+    }
+    return {items};
+}
+
+// coarse half: in = v_{j-1}, dst = g_j, a = g_j, b = v_j
+BatchItems fas_coarse_items(const PairList &pl) {
+    std::vector<BatchItem> items;
+    for (int p = 0; p < pl.n; ++p) {
+        const int j = pl.h_coarse[p];
+        items.push_back({j - 1, j, j, j, j});
+    }
+    return {items};
 }
 
 int h2d_reserve(Level &lv, int count) {
@@ -2429,7 +2494,7 @@ int h2d_dinv(mgrit_hip_engine *e, Level &lv, uint64_t dtbits, double **out) {
 // U (in W0) = interior of Phi applied to the rows in_slab[plan.d_in[b]] for the steps plan.d_step[b]  (theta > 0)
 // fin: the sweep's arithmetic is applied by the last transform itself (h2d_inv_kernel<true> + h2d_rim_kernel): no epilogue
 // launch, and the interior of U is neither written to nor read from the work slab
-int h2d_phi_batch(mgrit_hip_engine *e, Level &lv, const H2DPlan &pl, const double *in_slab, bool chain = false,
+int h2d_phi_batch(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const double *in_slab, bool chain = false,
                   const H2DFin *fin = nullptr) {
     H2DHost &h = *lv.h2d;
     const H2DDev &H = h.dev;
@@ -2496,10 +2561,10 @@ int h2d_phi_batch(mgrit_hip_engine *e, Level &lv, const H2DPlan &pl, const doubl
 
 // Phi of the batch followed by the sweep's arithmetic: fused into the last transform for the implicit schemes, the epilogue
 // kernel (which evaluates the explicit stencil itself) for theta = 0.
-int h2d_finish(mgrit_hip_engine *e, Level &lv, const H2DPlan &pl, const double *in_slab, double *dst_slab, int dst_ld,
+int h2d_finish(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const double *in_slab, double *dst_slab, int dst_ld,
                const double *a_slab, const double *b_slab, int op, int use_g, double w, bool chain);
 
-int h2d_phi_op(mgrit_hip_engine *e, Level &lv, const H2DPlan &pl, const double *in_slab, double *dst_slab, int dst_ld,
+int h2d_phi_op(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const double *in_slab, double *dst_slab, int dst_ld,
                const double *a_slab, const double *b_slab, int op, int use_g, double w, bool chain = false) {
     int rc;
     // (the sequential coarsest-level solve keeps the epilogue kernel: fused, one step of one state took 107 instead of 92 us --
@@ -2512,40 +2577,13 @@ int h2d_phi_op(mgrit_hip_engine *e, Level &lv, const H2DPlan &pl, const double *
     return h2d_finish(e, lv, pl, in_slab, dst_slab, dst_ld, a_slab, b_slab, op, use_g, w, chain);
 }
 
-int h2d_finish(mgrit_hip_engine *e, Level &lv, const H2DPlan &pl, const double *in_slab, double *dst_slab, int dst_ld,
+int h2d_finish(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const double *in_slab, double *dst_slab, int dst_ld,
                const double *a_slab, const double *b_slab, int op, int use_g, double w, bool chain) {
     const H2DDev &H = lv.h2d->dev;
     hipLaunchKernelGGL(h2d_finish_kernel, dim3((H.ny + 127) / 128, H.nx, pl.count), dim3(128), 0, e->stream, H,
                        (chain && pl.count == 1 && lv.h2d->Wc0) ? lv.h2d->Wc0 : lv.h2d->W0, in_slab,
                        pl.d_in, pl.d_step, dst_slab, dst_ld, pl.d_dst, a_slab, pl.d_a, b_slab, pl.d_b, op, use_g, w, 1.0 - w);
     HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int h2d_relax(mgrit_hip_engine *e, int lvl, RunList *rl, int mode, double weight_c) {
-    Level &lv = e->L[lvl];
-    int rc;
-    if (!rl->h2d_relax_built) {
-        int maxlen = 0;
-        for (int r = 0; r < rl->n; ++r) maxlen = std::max(maxlen, (int)rl->h_len[r]);
-        for (int k = 0; k < maxlen; ++k) {  // step k of every run that is long enough: one batch
-            std::vector<H2DItem> items;
-            for (int r = 0; r < rl->n; ++r)
-                if (rl->h_len[r] > k) {
-                    const int i = rl->h_start[r] + k;
-                    items.push_back({i - 1, i, i, i, i});
-                }
-            std::vector<H2DPlan> plans;
-            if ((rc = h2d_make_plans(e, lv, items, plans))) return rc;
-            for (H2DPlan &p : plans) rl->h2d_relax.push_back(p);
-        }
-        rl->h2d_relax_built = true;
-    }
-    const int op = mode == MGRIT_HIP_RELAX_C ? H2D_OP_C : H2D_OP_F;
-    const bool chain = mode == MGRIT_HIP_RELAX_CHAIN && lv.h2d->dev.theta != 0.0;   // its own work buffers (H2DHost::Wc0)
-    for (const H2DPlan &pl : rl->h2d_relax) {
-        if ((rc = h2d_phi_op(e, lv, pl, lv.dev.u, lv.dev.u, lv.dev.ld, lv.dev.g, lv.dev.u, op, lvl > 0 ? 1 : 0, weight_c, chain))) return rc;
-    }
     return 0;
 }
 
@@ -2577,7 +2615,7 @@ int h2d_block_build(mgrit_hip_engine *e, Level &lv) {
     for (int b = 0; b < B; ++b) maxlen = std::max(maxlen, last(b) - first(b) + 1);
     k.p1.resize(maxlen); k.p3.resize(maxlen);
     for (int s = 0; s < maxlen; ++s) {
-        std::vector<H2DItem> it1, it3;
+        std::vector<BatchItem> it1, it3;
         for (int b = 0; b < B; ++b) {
             const int i = first(b) + s;
             if (i > last(b)) continue;
@@ -2585,8 +2623,8 @@ int h2d_block_build(mgrit_hip_engine *e, Level &lv) {
             it1.push_back({s == 0 ? i - 1 : b, i, b, i, i});
             if (i < last(b)) it3.push_back({i - 1, i, i, i, i});
         }
-        if (!it1.empty() && (rc = h2d_make_plans(e, lv, it1, k.p1[s]))) return rc;
-        if (!it3.empty() && (rc = h2d_make_plans(e, lv, it3, k.p3[s]))) return rc;
+        if (!it1.empty() && (rc = batch_make_plans(e, lv, it1, k.p1[s]))) return rc;
+        if (!it3.empty() && (rc = batch_make_plans(e, lv, it3, k.p3[s]))) return rc;
     }
     std::vector<int32_t> iota(B), end_all, end_tail, dsel(B, 0);
     for (int b = 0; b < B; ++b) { iota[b] = b; end_all.push_back(last(b)); }
@@ -2657,7 +2695,7 @@ int h2d_block_solve(mgrit_hip_engine *e, int lvl, bool *stepped) {
     const size_t per = (size_t)H.Mi * H.Mj;
     // first pass: x_b = (g_i + Phi(u_{i-1} + x_b)) - u_i, step s of every block as one batch
     for (size_t s = 0; s < k.p1.size(); ++s)
-        for (const H2DPlan &pl : k.p1[s]) {
+        for (const BatchPlan &pl : k.p1[s]) {
             if (s > 0)   // Y[b] = u_{i-1} + X[b]  (d_in = b, d_a = i)
                 hipLaunchKernelGGL(h2d_sum_rows_kernel, dim3((n + 255) / 256, pl.count), dim3(256), 0, e->stream, ld, n, k.Y, pl.d_in,
                                    lv.dev.u, pl.d_a, -1, k.X, pl.d_in);
@@ -2695,7 +2733,7 @@ int h2d_block_solve(mgrit_hip_engine *e, int lvl, bool *stepped) {
     HIP_TRY(hipGetLastError());
     // second pass: every block's interior from its (corrected) start
     for (size_t s = 0; s < k.p3.size(); ++s)
-        for (const H2DPlan &pl : k.p3[s])
+        for (const BatchPlan &pl : k.p3[s])
             if ((rc = h2d_phi_op(e, lv, pl, lv.dev.u, lv.dev.u, ld, lv.dev.g, lv.dev.u, H2D_OP_F, 1, 1.0))) return rc;
     return 0;
 }
@@ -2705,16 +2743,8 @@ int h2d_points_sumsq(mgrit_hip_engine *e, int lvl, RunList *rl, const double *pr
     Level &lv = e->L[lvl];
     const H2DDev &H = lv.h2d->dev;
     int rc;
-    if (!rl->h2d_points_built) {
-        std::vector<H2DItem> items;
-        for (int r = 0; r < rl->n; ++r) {
-            const int i = rl->h_start[r];
-            items.push_back({i - 1, i, i, i, r});   // (b: the point's position in the list = where its sum goes)
-        }
-        if ((rc = h2d_make_plans(e, lv, items, rl->h2d_points))) return rc;
-        rl->h2d_points_built = true;
-    }
-    for (const H2DPlan &pl : rl->h2d_points) {
+    if ((rc = batch_plans_once(e, lv, rl->points, [&] { return point_items(lv, *rl); }))) return rc;
+    for (const BatchPlan &pl : rl->points.plans) {
         if ((rc = h2d_reserve(lv, std::min(H2D_MAX_BATCH, pl.count)))) return rc;
         if (!prev) {
             if ((rc = h2d_phi_batch(e, lv, pl, lv.dev.u))) return rc;
@@ -2731,29 +2761,6 @@ int h2d_points_sumsq(mgrit_hip_engine *e, int lvl, RunList *rl, const double *pr
         hipLaunchKernelGGL(h2d_rowsum_kernel, dim3((pl.count + 63) / 64), dim3(64), 0, e->stream, lv.h2d->rowsq, H.nx, pl.count,
                            out, pl.d_b);
         HIP_TRY(hipGetLastError());
-    }
-    return 0;
-}
-
-int h2d_fas_rhs(mgrit_hip_engine *e, int lvl, PairList *pl) {
-    Level &lf = e->L[lvl], &lc = e->L[lvl + 1];
-    int rc;
-    if (!pl->h2d_built) {
-        std::vector<H2DItem> fine, coarse;
-        for (int p = 0; p < pl->n; ++p) {
-            const int i = pl->h_fine[p], j = pl->h_coarse[p];
-            fine.push_back({i - 1, i, j, i, i});      // dst = g^{l+1}_j, a = g^l_i, b = u^l_i
-            coarse.push_back({j - 1, j, j, j, j});    // in = v_{j-1}, dst = g_j, a = g_j, b = v_j
-        }
-        if ((rc = h2d_make_plans(e, lf, fine, pl->h2d_fine))) return rc;
-        if ((rc = h2d_make_plans(e, lc, coarse, pl->h2d_coarse))) return rc;
-        pl->h2d_built = true;
-    }
-    for (const H2DPlan &q : pl->h2d_fine) {
-        if ((rc = h2d_phi_op(e, lf, q, lf.dev.u, lc.dev.g, lc.dev.ld, lf.dev.g, lf.dev.u, H2D_OP_FAS_FINE, lvl > 0 ? 1 : 0, 1.0))) return rc;
-    }
-    for (const H2DPlan &q : pl->h2d_coarse) {
-        if ((rc = h2d_phi_op(e, lc, q, lc.dev.v, lc.dev.g, lc.dev.ld, lc.dev.g, lc.dev.v, H2D_OP_FAS_COARSE, 1, 1.0))) return rc;
     }
     return 0;
 }
@@ -2825,10 +2832,8 @@ int force_mode(const Level &lv) {
 
 
 // ---------------------------------------------------------------------------------------------------------------
-// Wide Heat1D states (mgrit_hip_wide.inc): batch plans and the three-launch Phi, in the scheme of the Heat2D path
+// Wide Heat1D states (mgrit_hip_wide.inc): the three-launch Phi on a batch and its work slabs
 // ---------------------------------------------------------------------------------------------------------------
-constexpr int WIDE_MAX_BATCH = 2048;   // items per batch (work slab: 2048 rows of up to 512 KB)
-
 int wide_reserve(Level &lv, int count) {
     WideHost &h = *lv.wide;
     if ((size_t)count <= h.cap) return 0;
@@ -2847,29 +2852,8 @@ int wide_reserve(Level &lv, int count) {
     return 0;
 }
 
-int wide_make_plans(mgrit_hip_engine *e, Level &lv, const std::vector<H2DItem> &items, std::vector<H2DPlan> &plans) {
-    for (size_t off = 0; off < items.size(); off += WIDE_MAX_BATCH) {
-        const size_t cnt = std::min<size_t>(WIDE_MAX_BATCH, items.size() - off);
-        std::vector<int32_t> vin(cnt), vst(cnt), vds(cnt), va(cnt), vb(cnt);
-        for (size_t k = 0; k < cnt; ++k) {
-            const H2DItem &it = items[off + k];
-            vin[k] = it.in; vst[k] = it.step; vds[k] = it.dst; va[k] = it.a; vb[k] = it.b;
-        }
-        H2DPlan pl;
-        pl.count = (int)cnt;
-        int rc;
-        if ((rc = dev_upload_raw(lv, e->stream, vin.data(), cnt, &pl.d_in))) return rc;
-        if ((rc = dev_upload_raw(lv, e->stream, vst.data(), cnt, &pl.d_step))) return rc;
-        if ((rc = dev_upload_raw(lv, e->stream, vds.data(), cnt, &pl.d_dst))) return rc;
-        if ((rc = dev_upload_raw(lv, e->stream, va.data(), cnt, &pl.d_a))) return rc;
-        if ((rc = dev_upload_raw(lv, e->stream, vb.data(), cnt, &pl.d_b))) return rc;
-        plans.push_back(pl);
-    }
-    return 0;
-}
-
 // the scanned rows of Phi(in_slab[plan.d_in[b]]) for the steps plan.d_step[b] in the work slab, and their carries
-int wide_phi(mgrit_hip_engine *e, Level &lv, const H2DPlan &pl, const double *in_slab) {
+int wide_phi(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const double *in_slab) {
     int rc;
     if ((rc = wide_reserve(lv, std::min(WIDE_MAX_BATCH, std::max(pl.count, 1))))) return rc;
     WideHost &h = *lv.wide;
@@ -2895,7 +2879,7 @@ int wide_phi(mgrit_hip_engine *e, Level &lv, const H2DPlan &pl, const double *in
     return 0;
 }
 
-int wide_finish(mgrit_hip_engine *e, Level &lv, const H2DPlan &pl, double *dst_slab, int dst_ld, const double *a_slab,
+int wide_finish(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, double *dst_slab, int dst_ld, const double *a_slab,
                 const double *b_slab, int op, int use_g, double w) {
     WideHost &h = *lv.wide;
     const int G = lv.dev.T / LANES;
@@ -2903,53 +2887,19 @@ int wide_finish(mgrit_hip_engine *e, Level &lv, const H2DPlan &pl, double *dst_s
         hipLaunchKernelGGL(wide2_finish_kernel, dim3((G + 15) / 16, pl.count), dim3(1024), 0, e->stream, lv.dev, 1, h.W, pl.d_step, h.car, h.z0,
                            h.T0, dst_slab, dst_ld, pl.d_dst, a_slab, pl.d_a, b_slab, pl.d_b, op, use_g, w, 1.0 - w, h.red);
     else
-    hipLaunchKernelGGL(wide_finish_kernel, dim3((G + 15) / 16, pl.count), dim3(1024), 0, e->stream, lv.dev, h.W, pl.d_step, h.car, h.z0,
-                       dst_slab, dst_ld, pl.d_dst, a_slab, pl.d_a, b_slab, pl.d_b, op, use_g, w, 1.0 - w, h.red);
+        hipLaunchKernelGGL(wide_finish_kernel, dim3((G + 15) / 16, pl.count), dim3(1024), 0, e->stream, lv.dev, h.W, pl.d_step, h.car, h.z0,
+                           dst_slab, dst_ld, pl.d_dst, a_slab, pl.d_a, b_slab, pl.d_b, op, use_g, w, 1.0 - w, h.red);
     HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int wide_relax(mgrit_hip_engine *e, int lvl, RunList *rl, int mode, double weight_c) {
-    Level &lv = e->L[lvl];
-    int rc;
-    if (mode == MGRIT_HIP_RELAX_FC) return fail(MGRIT_HIP_EUNSUPPORTED, "relax mode FC: states of at most %d values", MGRIT_HIP_MAX_N);
-    if (!rl->h2d_relax_built) {
-        int maxlen = 0;
-        for (int r = 0; r < rl->n; ++r) maxlen = std::max(maxlen, (int)rl->h_len[r]);
-        for (int k = 0; k < maxlen; ++k) {   // step k of every run that is long enough: one batch
-            std::vector<H2DItem> items;
-            for (int r = 0; r < rl->n; ++r)
-                if (rl->h_len[r] > k) {
-                    const int i = rl->h_start[r] + k;
-                    items.push_back({i - 1, i, i, i, i});
-                }
-            if ((rc = wide_make_plans(e, lv, items, rl->h2d_relax))) return rc;
-        }
-        rl->h2d_relax_built = true;
-    }
-    const int op = mode == MGRIT_HIP_RELAX_C ? WIDE_OP_C : WIDE_OP_F;
-    for (const H2DPlan &pl : rl->h2d_relax) {
-        if ((rc = wide_phi(e, lv, pl, lv.dev.u))) return rc;
-        if ((rc = wide_finish(e, lv, pl, lv.dev.u, lv.dev.ld, lv.dev.g, lv.dev.u, op, lvl > 0 ? 1 : 0, weight_c))) return rc;
-    }
     return 0;
 }
 
 int wide_points_sumsq(mgrit_hip_engine *e, int lvl, RunList *rl, const double *prev, double *out) {
     Level &lv = e->L[lvl];
     int rc;
-    if (!rl->h2d_points_built) {
-        std::vector<H2DItem> items;
-        for (int r = 0; r < rl->n; ++r) {
-            const int i = rl->h_start[r];
-            items.push_back({i - 1, i, i, i, i});
-        }
-        if ((rc = wide_make_plans(e, lv, items, rl->h2d_points))) return rc;
-        rl->h2d_points_built = true;
-    }
+    if ((rc = batch_plans_once(e, lv, rl->points, [&] { return point_items(lv, *rl); }))) return rc;
     const int G = lv.dev.T / LANES, halves = lv.dev.kind == MGRIT_HIP_STEPPER_HEAT1D_2PTS ? 2 : 1;
     int off = 0;
-    for (const H2DPlan &pl : rl->h2d_points) {
+    for (const BatchPlan &pl : rl->points.plans) {
         if ((rc = wide_reserve(lv, std::min(WIDE_MAX_BATCH, std::max(pl.count, 1))))) return rc;
         if (!prev) {
             if ((rc = wide_phi(e, lv, pl, lv.dev.u))) return rc;
@@ -2966,42 +2916,36 @@ int wide_points_sumsq(mgrit_hip_engine *e, int lvl, RunList *rl, const double *p
     return 0;
 }
 
-// fine half of the FAS right-hand side for a wide fine level: rows into dst_slab (g^{l+1} itself for the copy transfer, the
-// level's scratch rows -- one per pair -- for a spatial transfer that follows)
-int wide_fas_fine(mgrit_hip_engine *e, int lvl, PairList *pl, double *dst_slab, int dst_ld, bool by_pair) {
-    Level &lf = e->L[lvl];
+// ---------------------------------------------------------------------------------------------------------------
+// The batched route: what Heat2D, Allen-Cahn and wide 1-D levels share. One operation on a batch -- Phi of the rows
+// in_slab[plan.d_in[b]] and the sweep's arithmetic `op` on top -- and the sweeps made of it
+// ---------------------------------------------------------------------------------------------------------------
+static_assert(H2D_OP_F == WIDE_OP_F && H2D_OP_C == WIDE_OP_C && H2D_OP_FAS_FINE == WIDE_OP_FAS_FINE && H2D_OP_FAS_COARSE == WIDE_OP_FAS_COARSE &&
+              H2D_OP_RESIDUAL == WIDE_OP_RESIDUAL && H2D_OP_JUMP == WIDE_OP_JUMP, "batch_phi_op passes one op code to either route");
+
+bool batched(const Level &lv) { return lv.h2d || lv.wide; }
+
+int batch_phi_op(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const double *in_slab, double *dst_slab, int dst_ld,
+                 const double *a_slab, const double *b_slab, int op, int use_g, double w, bool chain = false) {
+    if (lv.h2d) return h2d_phi_op(e, lv, pl, in_slab, dst_slab, dst_ld, a_slab, b_slab, op, use_g, w, chain);
+    const int rc = wide_phi(e, lv, pl, in_slab);
+    return rc ? rc : wide_finish(e, lv, pl, dst_slab, dst_ld, a_slab, b_slab, op, use_g, w);
+}
+
+int batch_relax(mgrit_hip_engine *e, int lvl, RunList *rl, int mode, double weight_c) {
+    Level &lv = e->L[lvl];
     int rc;
-    if (pl->h2d_fine.empty()) {
-        std::vector<H2DItem> fine;
-        for (int p = 0; p < pl->n; ++p) {
-            const int i = pl->h_fine[p];
-            fine.push_back({i - 1, i, by_pair ? p : pl->h_coarse[p], i, i});
-        }
-        if ((rc = wide_make_plans(e, lf, fine, pl->h2d_fine))) return rc;
-    }
-    for (const H2DPlan &q : pl->h2d_fine) {
-        if ((rc = wide_phi(e, lf, q, lf.dev.u))) return rc;
-        if ((rc = wide_finish(e, lf, q, dst_slab, dst_ld, lf.dev.g, lf.dev.u, WIDE_OP_FAS_FINE, lvl > 0 ? 1 : 0, 1.0))) return rc;
-    }
+    if (lv.wide && mode == MGRIT_HIP_RELAX_FC) return fail(MGRIT_HIP_EUNSUPPORTED, "relax mode FC: states of at most %d values", MGRIT_HIP_MAX_N);
+    if ((rc = batch_plans_once(e, lv, rl->relax, [&] { return run_step_items(*rl); }))) return rc;
+    const int op = mode == MGRIT_HIP_RELAX_C ? H2D_OP_C : H2D_OP_F;
+    const bool chain = lv.h2d && mode == MGRIT_HIP_RELAX_CHAIN && lv.h2d->dev.theta != 0.0;   // its own work buffers (H2DHost::Wc0)
+    for (const BatchPlan &pl : rl->relax.plans)
+        if ((rc = batch_phi_op(e, lv, pl, lv.dev.u, lv.dev.u, lv.dev.ld, lv.dev.g, lv.dev.u, op, lvl > 0 ? 1 : 0, weight_c, chain))) return rc;
     return 0;
 }
 
-int wide_fas_coarse(mgrit_hip_engine *e, int lvl, PairList *pl) {
-    Level &lc = e->L[lvl + 1];
-    int rc;
-    if (pl->h2d_coarse.empty()) {
-        std::vector<H2DItem> coarse;
-        for (int p = 0; p < pl->n; ++p) {
-            const int j = pl->h_coarse[p];
-            coarse.push_back({j - 1, j, j, j, j});
-        }
-        if ((rc = wide_make_plans(e, lc, coarse, pl->h2d_coarse))) return rc;
-    }
-    for (const H2DPlan &q : pl->h2d_coarse) {
-        if ((rc = wide_phi(e, lc, q, lc.dev.v))) return rc;
-        if ((rc = wide_finish(e, lc, q, lc.dev.g, lc.dev.ld, lc.dev.g, lc.dev.v, WIDE_OP_FAS_COARSE, 1, 1.0))) return rc;
-    }
-    return 0;
+int batch_points_sumsq(mgrit_hip_engine *e, int lvl, RunList *rl, const double *prev, double *out) {
+    return e->L[lvl].h2d ? h2d_points_sumsq(e, lvl, rl, prev, out) : wide_points_sumsq(e, lvl, rl, prev, out);
 }
 
 // entry points that hold a state in one workgroup refuse wide levels
@@ -3699,8 +3643,10 @@ int mgrit_hip_runs_create(mgrit_hip_engine *e, int lvl, int n_runs, const int32_
     return 0;
 }
 
-// rows of the level's scratch slab: a bigger need than any before gets a NEW slab, the old one stays alive until the engine goes
-// (lf.allocs) -- a captured cycle that ran a sweep on a block's shorter list still launches with its address
+// rows of the level's scratch slab, grown here and nowhere else: a bigger need than any before gets a NEW slab, the old one stays
+// alive until the engine goes (lf.allocs) -- a captured cycle that ran a sweep on a block's shorter list still launches with its
+// address (found by the state fuzz: a whole-level fas_residual by hand between two replays of a two-block plan freed the slab
+// under the graph)
 static int scratch_reserve(Level &lf, size_t rows) {
     if (lf.scratch_rows >= rows) return 0;
     if (lf.scratch) lf.allocs.push_back(lf.scratch);
@@ -3732,7 +3678,7 @@ int mgrit_hip_pairs_create(mgrit_hip_engine *e, int lvl, int n_pairs, const int3
     if ((rc = dev_upload(lv, e->stream, hf, &pl.d_fine))) return rc;
     if ((rc = dev_upload(lv, e->stream, hc, &pl.d_coarse))) return rc;
     if ((rc = dev_upload(lv, e->stream, iota, &pl.d_iota))) return rc;
-    // a 2-D library transfer takes the fine half of the FAS right-hand side through scratch rows of the level (h2d_fas_rhs_2d): the
+    // a 2-D library transfer takes the fine half of the FAS right-hand side through scratch rows of the level (mgrit_hip_fas_rhs): the
     // slab is sized here, where lists are made, so that the sweep itself -- possibly part of a captured or replayed cycle -- never allocates
     if ((lv.transfer == MGRIT_HIP_TRANSFER_HEAT2D || lv.transfer == MGRIT_HIP_TRANSFER_PERIODIC2D) && (rc = scratch_reserve(lv, (size_t)n_pairs)))
         return rc;
@@ -3762,8 +3708,7 @@ int mgrit_hip_relax(mgrit_hip_engine *e, int lvl, int runs_id, int mode, double 
         rc = h2d_block_solve(e, lvl, &stepped);
         if (rc || !stepped) return rc;
     }
-    if (lv.h2d) return h2d_relax(e, lvl, rl, mode, weight_c);
-    if (lv.wide) return wide_relax(e, lvl, rl, mode, weight_c);
+    if (batched(lv)) return batch_relax(e, lvl, rl, mode, weight_c);
     if (is_2pts(lv)) {
         const bool use_g = lvl > 0, weighted = mode == MGRIT_HIP_RELAX_C && weight_c != 1.0;
         const double w = weight_c, w1 = 1.0 - weight_c;
@@ -3840,8 +3785,7 @@ int mgrit_hip_residual(mgrit_hip_engine *e, int lvl, int runs_id, double *sumsq_
     if (rl->n == 0) return 0;
     if (!sumsq_out) return fail(MGRIT_HIP_EINVAL, "null output");
     Timed timed(e, MGRIT_HIP_T_RESIDUAL, lvl);
-    if (lv.h2d) return h2d_points_sumsq(e, lvl, rl, nullptr, sumsq_out);
-    if (lv.wide) return wide_points_sumsq(e, lvl, rl, nullptr, sumsq_out);
+    if (batched(lv)) return batch_points_sumsq(e, lvl, rl, nullptr, sumsq_out);
     const dim3 grid(persistent_grid(lv, rl->n)), block(lv.dev.T);
     if (is_2pts(lv))
         return launch(residual2_fn(lv.order, force_mode(lv)), grid, block, smem2_bytes(lv.G), e->stream, lv.dev, rl->d_start, rl->n, sumsq_out);
@@ -3858,8 +3802,7 @@ int mgrit_hip_jump(mgrit_hip_engine *e, int lvl, int runs_id, const double *prev
     if (rl->n == 0) return 0;
     if (!sumsq_out || !prev) return fail(MGRIT_HIP_EINVAL, "null argument");
     Timed timed(e, MGRIT_HIP_T_JUMP, lvl);
-    if (lv.h2d) return h2d_points_sumsq(e, lvl, rl, prev, sumsq_out);
-    if (lv.wide) return wide_points_sumsq(e, lvl, rl, prev, sumsq_out);
+    if (batched(lv)) return batch_points_sumsq(e, lvl, rl, prev, sumsq_out);
     if (is_2pts(lv)) return launch(&jump2_kernel, dim3(rl->n), dim3(lv.dev.T), smem2_bytes(lv.G), e->stream, lv.dev, rl->d_start, prev, sumsq_out);
     return launch(&jump_kernel, dim3(rl->n), dim3(lv.dev.T), smem_bytes(lv.G, lv.dev.kind), e->stream, lv.dev, rl->d_start, prev, sumsq_out);
 }
@@ -3896,30 +3839,52 @@ static int interp2d_launch(mgrit_hip_engine *e, const Level &lf, const Level &lc
     return 0;
 }
 
-// FAS right-hand side around a 2-D library transfer: the fine half through the batched Phi into the level's scratch rows (one per
-// pair), their restriction into g^{l+1}, the coarse half -- the composition mgrit_hip_fas_fine_rows / the caller's restriction /
-// mgrit_hip_fas_coarse, with the restriction as a kernel. The slab is sized when the pair list is made (mgrit_hip_pairs_create); the
-// call here finds it large enough.
-static int h2d_fas_rhs_2d(mgrit_hip_engine *e, int lvl, PairList *pl) {
-    Level &lf = e->L[lvl], &lc = e->L[lvl + 1];
-    int rc;
-    if ((rc = scratch_reserve(lf, (size_t)pl->n))) return rc;
-    if (pl->h2d_rows.empty()) {
-        std::vector<H2DItem> fine;
-        for (int p = 0; p < pl->n; ++p) fine.push_back({pl->h_fine[p] - 1, pl->h_fine[p], p, pl->h_fine[p], pl->h_fine[p]});
-        if ((rc = h2d_make_plans(e, lf, fine, pl->h2d_rows))) return rc;
+// The two halves of the FAS right-hand side, each for every kind of level: the batched route, resident two-point, resident one-point.
+// Fine half: row dst = (g^l_i + Phi_l(u^l_{i-1})) - u^l_i of dst_slab; dst is the pair's position (by_pair: rows that a restriction
+// follows) or the coarse slot (g^{l+1} itself, the copy transfer). On the batched route a half runs the plans that its entry point
+// has had built by fas_fine_plans / fas_coarse_plans, the only builders (nothing to build on a resident level): mgrit_hip_fas_rhs
+// asks for both before the first launch, so that a list's first call uploads, and allocates, ahead of its sweeps.
+static int fas_fine_plans(mgrit_hip_engine *e, int lvl, PairList *pl, bool by_pair) {
+    Level &lf = e->L[lvl];
+    if (!batched(lf)) return 0;
+    return batch_plans_once(e, lf, by_pair ? pl->fine_to_rows : pl->fine_to_coarse, [&] { return fas_fine_items(*pl, by_pair); });
+}
+
+static int fas_coarse_plans(mgrit_hip_engine *e, int lvl, PairList *pl) {
+    Level &lc = e->L[lvl + 1];
+    return batched(lc) ? batch_plans_once(e, lc, pl->coarse, [&] { return fas_coarse_items(*pl); }) : 0;
+}
+
+static int fas_fine_half(mgrit_hip_engine *e, int lvl, PairList *pl, double *dst_slab, int dst_ld, bool by_pair) {
+    Level &lf = e->L[lvl];
+    const int use_g = lvl > 0 ? 1 : 0;
+    if (batched(lf)) {
+        int rc = 0;
+        for (const BatchPlan &bp : (by_pair ? pl->fine_to_rows : pl->fine_to_coarse).plans)
+            if ((rc = batch_phi_op(e, lf, bp, lf.dev.u, dst_slab, dst_ld, lf.dev.g, lf.dev.u, H2D_OP_FAS_FINE, use_g, 1.0))) break;
+        return rc;
     }
-    if (pl->h2d_coarse.empty()) {
-        std::vector<H2DItem> coarse;
-        for (int p = 0; p < pl->n; ++p) { const int j = pl->h_coarse[p]; coarse.push_back({j - 1, j, j, j, j}); }
-        if ((rc = h2d_make_plans(e, lc, coarse, pl->h2d_coarse))) return rc;
+    const int32_t *d_dst = by_pair ? pl->d_iota : pl->d_coarse;
+    if (is_2pts(lf))
+        return launch(fas_fine2_fn(lf.order, force_mode(lf)), dim3(pl->n), dim3(lf.dev.T), smem2_bytes(lf.G), e->stream, lf.dev, pl->d_fine,
+                      d_dst, dst_slab, dst_ld, use_g);
+    return launch(fas_fine_fn(lf.dev.kind, force_mode(lf)), dim3(pl->n), dim3(lf.dev.T), smem_bytes(lf.G, lf.dev.kind), e->stream, lf.dev,
+                  pl->d_fine, d_dst, dst_slab, dst_ld, use_g);
+}
+
+// Coarse half: g^{l+1}_j = (g^{l+1}_j + v^{l+1}_j) - Phi_{l+1}(v^{l+1}_{j-1})
+static int fas_coarse_half(mgrit_hip_engine *e, int lvl, PairList *pl) {
+    Level &lc = e->L[lvl + 1];
+    if (batched(lc)) {
+        int rc = 0;
+        for (const BatchPlan &bp : pl->coarse.plans)
+            if ((rc = batch_phi_op(e, lc, bp, lc.dev.v, lc.dev.g, lc.dev.ld, lc.dev.g, lc.dev.v, H2D_OP_FAS_COARSE, 1, 1.0))) break;
+        return rc;
     }
-    for (const H2DPlan &q : pl->h2d_rows)
-        if ((rc = h2d_phi_op(e, lf, q, lf.dev.u, lf.scratch, lf.dev.ld, lf.dev.g, lf.dev.u, H2D_OP_FAS_FINE, lvl > 0 ? 1 : 0, 1.0))) return rc;
-    if ((rc = restrict2d_launch(e, lf, lc, lf.scratch, pl->d_iota, lc.dev.g, pl))) return rc;
-    for (const H2DPlan &q : pl->h2d_coarse)
-        if ((rc = h2d_phi_op(e, lc, q, lc.dev.v, lc.dev.g, lc.dev.ld, lc.dev.g, lc.dev.v, H2D_OP_FAS_COARSE, 1, 1.0))) return rc;
-    return 0;
+    if (is_2pts(lc))
+        return launch(fas_coarse2_fn(lc.order, force_mode(lc)), dim3(pl->n), dim3(lc.dev.T), smem2_bytes(lc.G), e->stream, lc.dev, pl->d_coarse);
+    return launch(fas_coarse_fn(lc.dev.kind, force_mode(lc)), dim3(pl->n), dim3(lc.dev.T), smem_bytes(lc.G, lc.dev.kind), e->stream, lc.dev,
+                  pl->d_coarse, 0);
 }
 
 int mgrit_hip_restrict_u(mgrit_hip_engine *e, int lvl, int pairs_id) {
@@ -3958,26 +3923,15 @@ int mgrit_hip_fas_fine_rows(mgrit_hip_engine *e, int lvl, int pairs_id, double *
     if ((rc = check_bound(lf, lvl > 0))) return rc;
     if (is_2pts(lf)) return fail(MGRIT_HIP_EUNSUPPORTED, "split FAS right-hand side: one-point steppers only");
     if (pl->n > 0 && (!rows || ld_rows < lf.dev.ld)) return fail(MGRIT_HIP_EINVAL, "rows buffer missing or narrower than the level's rows");
-    if (lf.h2d) {   // Heat2D: the batched Phi, the fine half written to the caller's rows (one per pair)
-        if (pl->n == 0) return 0;
-        Timed timed(e, MGRIT_HIP_T_FAS_RHS, lvl);
-        if (pl->h2d_rows.empty()) {
-            std::vector<H2DItem> fine;
-            for (int p = 0; p < pl->n; ++p) fine.push_back({pl->h_fine[p] - 1, pl->h_fine[p], p, pl->h_fine[p], pl->h_fine[p]});
-            if ((rc = h2d_make_plans(e, lf, fine, pl->h2d_rows))) return rc;
-            if (pl->h2d_rows.size() > (size_t)((pl->n + H2D_MAX_BATCH - 1) / H2D_MAX_BATCH))
-                return fail(MGRIT_HIP_EUNSUPPORTED, "Heat2D FAS rows for a caller's transfer: one time-step size per level");
-        }
-        for (const H2DPlan &q : pl->h2d_rows) {
-            if ((rc = h2d_phi_op(e, lf, q, lf.dev.u, rows, ld_rows, lf.dev.g, lf.dev.u, H2D_OP_FAS_FINE, lvl > 0 ? 1 : 0, 1.0))) return rc;
-        }
-        return 0;
-    }
-    if ((rc = no_wide(e->L[lvl], &e->L[lvl + 1], "FAS right-hand side around a caller's transfer"))) return rc;
+    if (!lf.h2d && (rc = no_wide(e->L[lvl], &e->L[lvl + 1], "FAS right-hand side around a caller's transfer"))) return rc;
     if (pl->n == 0) return 0;
     Timed timed(e, MGRIT_HIP_T_FAS_RHS, lvl);
-    return launch(fas_fine_fn(lf.dev.kind, force_mode(lf)), dim3(pl->n), dim3(lf.dev.T), smem_bytes(lf.G, lf.dev.kind), e->stream, lf.dev,
-                  pl->d_fine, pl->d_iota, rows, ld_rows, lvl > 0 ? 1 : 0);
+    if ((rc = fas_fine_plans(e, lvl, pl, true))) return rc;
+    if (lf.h2d) {   // Heat2D: the batched Phi, the fine half written to the caller's rows (one per pair)
+        if (pl->fine_to_rows.plans.size() > (size_t)((pl->n + H2D_MAX_BATCH - 1) / H2D_MAX_BATCH))
+            return fail(MGRIT_HIP_EUNSUPPORTED, "Heat2D FAS rows for a caller's transfer: one time-step size per level");
+    }
+    return fas_fine_half(e, lvl, pl, rows, ld_rows, true);
 }
 
 int mgrit_hip_fas_coarse(mgrit_hip_engine *e, int lvl, int pairs_id) {
@@ -3987,26 +3941,15 @@ int mgrit_hip_fas_coarse(mgrit_hip_engine *e, int lvl, int pairs_id) {
     Level &lc = e->L[lvl + 1];
     if ((rc = check_bound(lc, true))) return rc;
     if (is_2pts(lc)) return fail(MGRIT_HIP_EUNSUPPORTED, "split FAS right-hand side: one-point steppers only");
-    if (lc.h2d) {
-        if (pl->n == 0) return 0;
-        Timed timed(e, MGRIT_HIP_T_FAS_RHS, lvl);
-        if (pl->h2d_coarse.empty()) {
-            std::vector<H2DItem> coarse;
-            for (int p = 0; p < pl->n; ++p) { const int j = pl->h_coarse[p]; coarse.push_back({j - 1, j, j, j, j}); }
-            if ((rc = h2d_make_plans(e, lc, coarse, pl->h2d_coarse))) return rc;
-        }
-        for (const H2DPlan &q : pl->h2d_coarse) {
-            if ((rc = h2d_phi_op(e, lc, q, lc.dev.v, lc.dev.g, lc.dev.ld, lc.dev.g, lc.dev.v, H2D_OP_FAS_COARSE, 1, 1.0))) return rc;
-        }
-        return 0;
-    }
-    if ((rc = no_wide(e->L[lvl], &e->L[lvl + 1], "FAS right-hand side around a caller's transfer"))) return rc;
+    if (!lc.h2d && (rc = no_wide(e->L[lvl], &e->L[lvl + 1], "FAS right-hand side around a caller's transfer"))) return rc;
     if (pl->n == 0) return 0;
     Timed timed(e, MGRIT_HIP_T_FAS_RHS, lvl);
-    return launch(fas_coarse_fn(lc.dev.kind, force_mode(lc)), dim3(pl->n), dim3(lc.dev.T), smem_bytes(lc.G, lc.dev.kind), e->stream, lc.dev,
-                  pl->d_coarse, 0);
+    if ((rc = fas_coarse_plans(e, lvl, pl))) return rc;
+    return fas_coarse_half(e, lvl, pl);
 }
 
+// the fine half into g^{l+1} (copy transfer) or into the level's scratch rows, one per pair, and their restriction into g^{l+1};
+// then the coarse half -- what a caller's transfer composes from mgrit_hip_fas_fine_rows, its restriction and mgrit_hip_fas_coarse
 int mgrit_hip_fas_rhs(mgrit_hip_engine *e, int lvl, int pairs_id) {
     PairList *pl;
     int rc = get_pairs(e, lvl, pairs_id, &pl);
@@ -4017,48 +3960,29 @@ int mgrit_hip_fas_rhs(mgrit_hip_engine *e, int lvl, int pairs_id) {
     if (pl->n == 0) return 0;
     Timed timed(e, MGRIT_HIP_T_FAS_RHS, lvl);
     if (lf.h2d || lc.h2d) {
-        if (transfer_2d(lf)) return h2d_fas_rhs_2d(e, lvl, pl);
-        if (!lf.h2d || !lc.h2d || lf.transfer != MGRIT_HIP_TRANSFER_COPY)
+        if (!transfer_2d(lf) && (!lf.h2d || !lc.h2d || lf.transfer != MGRIT_HIP_TRANSFER_COPY))
             return fail(MGRIT_HIP_EUNSUPPORTED, "Heat2D levels need Heat2D on both levels and the copy transfer");
-        return h2d_fas_rhs(e, lvl, pl);
+    } else if ((is_2pts(lf) || is_2pts(lc)) && (!is_2pts(lf) || !is_2pts(lc) || lf.transfer != MGRIT_HIP_TRANSFER_COPY)) {
+        return fail(MGRIT_HIP_EUNSUPPORTED, "two-point levels pair with two-point levels through the copy transfer only");
     }
-    if (is_2pts(lf) || is_2pts(lc)) {
-        if (!is_2pts(lf) || !is_2pts(lc) || lf.transfer != MGRIT_HIP_TRANSFER_COPY)
-            return fail(MGRIT_HIP_EUNSUPPORTED, "two-point levels pair with two-point levels through the copy transfer only");
-        if (lf.wide) rc = wide_fas_fine(e, lvl, pl, lc.dev.g, lc.dev.ld, false);
-        else rc = launch(fas_fine2_fn(lf.order, force_mode(lf)), dim3(pl->n), dim3(lf.dev.T), smem2_bytes(lf.G), e->stream, lf.dev, pl->d_fine,
-                         pl->d_coarse, lc.dev.g, lc.dev.ld, lvl > 0 ? 1 : 0);
-        if (rc) return rc;
-        if (lc.wide) return wide_fas_coarse(e, lvl, pl);
-        return launch(fas_coarse2_fn(lc.order, force_mode(lc)), dim3(pl->n), dim3(lc.dev.T), smem2_bytes(lc.G), e->stream, lc.dev, pl->d_coarse);
-    }
-    if (lf.transfer == MGRIT_HIP_TRANSFER_COPY) {
-        if (lf.wide) rc = wide_fas_fine(e, lvl, pl, lc.dev.g, lc.dev.ld, false);
-        else rc = launch(fas_fine_fn(lf.dev.kind, force_mode(lf)), dim3(pl->n), dim3(lf.dev.T), smem_bytes(lf.G, lf.dev.kind), e->stream, lf.dev,
-                         pl->d_fine, pl->d_coarse, lc.dev.g, lc.dev.ld, lvl > 0 ? 1 : 0);
-        if (rc) return rc;
+    const bool copy = lf.transfer == MGRIT_HIP_TRANSFER_COPY;
+    // (a 2-D transfer's slab is sized when the pair list is made, mgrit_hip_pairs_create: the call here finds it large enough)
+    if (!copy && (rc = scratch_reserve(lf, (size_t)pl->n))) return rc;
+    if ((rc = fas_fine_plans(e, lvl, pl, !copy)) || (rc = fas_coarse_plans(e, lvl, pl))) return rc;
+    if (copy) {
+        if ((rc = fas_fine_half(e, lvl, pl, lc.dev.g, lc.dev.ld, false))) return rc;
     } else {
-        if (lf.scratch_rows < (size_t)pl->n) {
-            // a bigger list than any before: a NEW slab; the old one stays alive until the engine goes (lf.allocs) -- a captured
-            // cycle that ran this sweep on a block's shorter list still launches with its address (found by the state fuzz: a
-            // whole-level fas_residual by hand between two replays of a two-block plan freed the slab under the graph)
-            if (lf.scratch) lf.allocs.push_back(lf.scratch);
-            lf.scratch = nullptr;
-            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&lf.scratch), sizeof(double) * (size_t)pl->n * lf.dev.ld));
-            lf.scratch_rows = pl->n;
+        if ((rc = fas_fine_half(e, lvl, pl, lf.scratch, lf.dev.ld, true))) return rc;
+        if (transfer_2d(lf)) {
+            if ((rc = restrict2d_launch(e, lf, lc, lf.scratch, pl->d_iota, lc.dev.g, pl))) return rc;
+        } else {
+            dim3 grid(pl->n, (lc.dev.ld + 255) / 256);
+            hipLaunchKernelGGL(restrict_rows_kernel, grid, dim3(256), 0, e->stream, lf.scratch, lf.dev.ld, lf.dev.T, pl->d_iota,
+                               lc.dev.g, lc.dev.ld, lc.dev.T, pl->d_coarse, lc.dev.n, lf.transfer);
+            HIP_TRY(hipGetLastError());
         }
-        if (lf.wide) rc = wide_fas_fine(e, lvl, pl, lf.scratch, lf.dev.ld, true);
-        else rc = launch(fas_fine_fn(lf.dev.kind, force_mode(lf)), dim3(pl->n), dim3(lf.dev.T), smem_bytes(lf.G, lf.dev.kind), e->stream, lf.dev,
-                         pl->d_fine, pl->d_iota, lf.scratch, lf.dev.ld, lvl > 0 ? 1 : 0);
-        if (rc) return rc;
-        dim3 grid(pl->n, (lc.dev.ld + 255) / 256);
-        hipLaunchKernelGGL(restrict_rows_kernel, grid, dim3(256), 0, e->stream, lf.scratch, lf.dev.ld, lf.dev.T, pl->d_iota,
-                           lc.dev.g, lc.dev.ld, lc.dev.T, pl->d_coarse, lc.dev.n, lf.transfer);
-        HIP_TRY(hipGetLastError());
     }
-    if (lc.wide) return wide_fas_coarse(e, lvl, pl);
-    return launch(fas_coarse_fn(lc.dev.kind, force_mode(lc)), dim3(pl->n), dim3(lc.dev.T), smem_bytes(lc.G, lc.dev.kind), e->stream, lc.dev,
-                  pl->d_coarse, 0);
+    return fas_coarse_half(e, lvl, pl);
 }
 
 int mgrit_hip_triples_create(mgrit_hip_engine *e, int lvl, int n, const int32_t *fine_idx, const int32_t *prev_fine_idx,
@@ -4151,35 +4075,30 @@ static int at_batched(mgrit_hip_engine *e, int lvl, int k) {
     int rc;
     const int n_pts = lv.dev.n_pts, ld = lv.dev.ld;
     Level::AtPlans &ap = lv.at_plans[k];
-    if (ap.steps.empty() && ap.count == 0) {
+    if (!ap.d_own) {   // d_own, uploaded last, marks both index arrays as made (a failed upload is made again on the next call)
         std::vector<int32_t> src, own;
-        for (int p = 1; p < n_pts; ++p) { src.push_back(p - k + 1 > 0 ? p - k + 1 : 0); own.push_back(p); }
+        for (int p = 1; p < n_pts; ++p) { src.push_back(std::max(p - k + 1, 0)); own.push_back(p); }
         ap.count = (int)own.size();
         if ((rc = dev_upload(lv, e->stream, src, &ap.d_src)) || (rc = dev_upload(lv, e->stream, own, &ap.d_own))) return rc;
-        for (int d = 1; d < k; ++d) {
-            std::vector<H2DItem> items;
-            for (int p = 1; p < n_pts; ++p) {
-                const int i = (p - k + 1 > 0 ? p - k + 1 : 0) + d;
-                if (i <= p) items.push_back({p, i, p, i, i});
-            }
-            std::vector<H2DPlan> plans;
-            if (!items.empty() && (rc = lv.h2d ? h2d_make_plans(e, lv, items, plans) : wide_make_plans(e, lv, items, plans))) return rc;
-            ap.steps.push_back(plans);
-        }
     }
+    rc = batch_plans_once(e, lv, ap.steps, [&] {   // step distance d of every point that still has one to take: one list
+        BatchItems out;
+        for (int d = 1; d < k; ++d) {
+            out.emplace_back();
+            for (int p = 1; p < n_pts; ++p) {
+                const int i = std::max(p - k + 1, 0) + d;
+                if (i <= p) out.back().push_back({p, i, p, i, i});
+            }
+        }
+        return out;
+    });
+    if (rc) return rc;
     double *X = lv.scratch;
     const dim3 grid(ap.count, (ld + 255) / 256);
     hipLaunchKernelGGL(restrict_rows_kernel, grid, dim3(256), 0, e->stream, lv.dev.u, ld, lv.dev.T, ap.d_src, X, ld, lv.dev.T, ap.d_own,
                        lv.dev.n, MGRIT_HIP_TRANSFER_COPY);
-    for (const std::vector<H2DPlan> &plans : ap.steps)
-        for (const H2DPlan &pl : plans) {
-            if (lv.h2d) {
-                if ((rc = h2d_phi_op(e, lv, pl, X, X, ld, lv.dev.g, X, H2D_OP_F, 1, 1.0))) return rc;
-            } else {
-                if ((rc = wide_phi(e, lv, pl, X))) return rc;
-                if ((rc = wide_finish(e, lv, pl, X, ld, lv.dev.g, X, WIDE_OP_F, 1, 1.0))) return rc;
-            }
-        }
+    for (const BatchPlan &pl : ap.steps.plans)
+        if ((rc = batch_phi_op(e, lv, pl, X, X, ld, lv.dev.g, X, H2D_OP_F, 1, 1.0))) return rc;
     hipLaunchKernelGGL(restrict_rows_kernel, grid, dim3(256), 0, e->stream, X, ld, lv.dev.T, ap.d_own, lv.dev.u, ld, lv.dev.T, ap.d_own,
                        lv.dev.n, MGRIT_HIP_TRANSFER_COPY);
     HIP_TRY(hipGetLastError());
@@ -4196,13 +4115,8 @@ int mgrit_hip_at_solve(mgrit_hip_engine *e, int lvl, int k) {
     if (lv.dev.n_pts < 2) return 0;
     Timed timed(e, MGRIT_HIP_T_AT, lvl);
     const size_t rows = (size_t)lv.dev.n_pts;
-    if (lv.scratch_rows < rows) {
-        if (lv.scratch) lv.allocs.push_back(lv.scratch);   // (kept until the engine goes: see mgrit_hip_fas_rhs)
-        lv.scratch = nullptr;
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&lv.scratch), sizeof(double) * rows * lv.dev.ld));
-        lv.scratch_rows = rows;
-    }
-    if (lv.h2d || lv.wide) return at_batched(e, lvl, k);
+    if ((rc = scratch_reserve(lv, rows))) return rc;
+    if (batched(lv)) return at_batched(e, lvl, k);
     HIP_TRY(hipMemcpyAsync(lv.scratch, lv.dev.u, sizeof(double) * rows * lv.dev.ld, hipMemcpyDeviceToDevice, e->stream));
     const dim3 grid(persistent_grid(lv, lv.dev.n_pts - 1)), block(lv.dev.T);
     if (is_2pts(lv)) return launch(at2_fn(lv.order, force_mode(lv)), grid, block, smem2_bytes(lv.G), e->stream, lv.dev, lv.scratch, k);

@@ -1,7 +1,7 @@
 """The C ABI of include/mgrit_hip.h driven directly -- raw device pointers, plain ints and doubles, the way the binding stub
 of INTEGRATION.md does it, without the pymgrit_amd host layer: one F-relaxation + C-relaxation + residual of a Heat1D level
-against the oracle, and the error behaviour of the entry points (negative return code + mgrit_hip_last_error, no exceptions,
-no crash on misuse)."""
+against the oracle, the error behaviour of the entry points (negative return code + mgrit_hip_last_error, no exceptions,
+no crash on misuse), and an order of FAS calls that the ABI allows and the Python driver never issues."""
 import ctypes as C
 
 import numpy as np
@@ -114,3 +114,53 @@ def test_abi_misuse_returns_error_codes(lib):
     finally:
         assert lib.mgrit_hip_destroy(eng) == 0
     lib.mgrit_hip_destroy(C.c_void_p(0))   # a null engine must not crash
+
+
+def test_fas_coarse_before_fas_rhs_leaves_no_trace(lib):
+    """Two Heat2D levels (9x9, backward Euler, copy transfer) on a non-uniform time grid, so that every plan list of the pair list
+    holds two step-size groups. mgrit_hip_fas_rhs overwrites g_j before it reads it, so a mgrit_hip_fas_coarse on the same pair
+    list before it must not change what it leaves in the coarse g: the coarse half's batch plans are built once, whichever entry
+    point comes first (built twice, every coarse half was applied twice)."""
+    nx = ny = 9
+    ld = 96
+    t_fine = np.ascontiguousarray(np.concatenate(([0.0], np.cumsum(0.01 * (1.0 + 0.25 * np.arange(8))))))
+    grids = [t_fine, np.ascontiguousarray(t_fine[::4])]
+    assert t_fine[4] - t_fine[3] != t_fine[8] - t_fine[7] and grids[1][1] - grids[1][0] != grids[1][2] - grids[1][1]
+    bc = np.zeros(nx * ny)
+    fine_idx, coarse_idx = np.array([4, 8], dtype=np.int32), np.array([1, 2], dtype=np.int32)
+    rng = np.random.default_rng(11)
+    host = [[rng.standard_normal((t.size, ld)) for _ in range(3)] for t in grids]     # u, v, g per level
+    stream = torch.cuda.current_stream()
+
+    def coarse_g(coarse_first):
+        eng = C.c_void_p()
+        assert lib.mgrit_hip_create(C.byref(eng), 2, C.c_void_p(stream.cuda_stream)) == 0
+        try:
+            slabs = [[torch.from_numpy(a).cuda() for a in lvl] for lvl in host]
+            for lvl, t in enumerate(grids):
+                assert lib.mgrit_hip_level_heat2d(eng, lvl, t.size, _ptr(t), nx, ny, ld, 64.0, 64.0, 1.0, _ptr(bc), 0, C.c_void_p(0),
+                                                  C.c_void_p(0)) == 0
+                assert lib.mgrit_hip_level_bind(eng, lvl, *[_dev(s) for s in slabs[lvl]]) == 0
+            assert lib.mgrit_hip_level_transfer(eng, 0, 0) == 0      # MGRIT_HIP_TRANSFER_COPY
+            pid = C.c_int(-1)
+            assert lib.mgrit_hip_pairs_create(eng, 0, 2, _ptr(fine_idx), _ptr(coarse_idx), C.byref(pid)) == 0
+            if coarse_first:
+                assert lib.mgrit_hip_fas_coarse(eng, 0, pid.value) == 0
+            assert lib.mgrit_hip_fas_rhs(eng, 0, pid.value) == 0
+            assert lib.mgrit_hip_sync(eng) == 0
+            g = slabs[1][2].cpu().numpy()
+            # the split form's fine half into rows takes one step size per level: refused on every call, not only the one that
+            # builds the plans, and nothing is launched
+            rows = torch.zeros((2, ld), dtype=torch.float64, device="cuda")
+            for _ in range(2):
+                assert lib.mgrit_hip_fas_fine_rows(eng, 0, pid.value, _dev(rows), ld) < 0
+                assert "one time-step size" in lib.mgrit_hip_last_error().decode()
+            assert lib.mgrit_hip_sync(eng) == 0 and not rows.any()
+            return g
+        finally:
+            assert lib.mgrit_hip_destroy(eng) == 0
+
+    g_a, g_b = coarse_g(False), coarse_g(True)
+    assert np.isfinite(g_a).all() and all(not np.array_equal(g_a[j], host[1][2][j]) for j in coarse_idx)   # both slots written
+    print("max |g_A - g_B| =", np.abs(g_a - g_b).max(), "on max |g_A| =", np.abs(g_a).max())
+    assert np.array_equal(g_a, g_b)

@@ -7,7 +7,7 @@ cases are chosen for:
   a. the size edges of the tile product: nx = 4 (smallest grid), 33 / 97 (just past a K step of 32), 96 (KP = 96 < P = 128), 129 (just
      past a tile of 64);
   b. exponents nu = 1, 3, 4 in every sweep (odd nu: only sweeps in which every Phi acts on a stored state -- u = -1 is unstable then);
-  c. several step sizes on one level: h2d_make_plans groups a sweep's items by the bit pattern of dt, one D table and one c = dt / eps^2
+  c. several step sizes on one level: batch_make_plans groups a sweep's items by the bit pattern of dt, one D table and one c = dt / eps^2
      per group. Coarsening 4 puts F-points of one interval into different groups;
   d. sweeps of more than H2D_MAX_BATCH = 1024 items: several launches with blockIdx.z restarting and the index arrays offset per plan.
      A uniform grid given as nt = / linspace holds a dozen bit patterns of dt (the differences k h - (k - 1) h round differently), so no
