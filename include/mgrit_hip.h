@@ -224,6 +224,18 @@ int mgrit_hip_fas_fused(mgrit_hip_engine *e, int lvl, int triples_id);
  *       every point but the first before anything reads it). */
 enum { MGRIT_HIP_FAS_WITH_F_RELAX = 1, MGRIT_HIP_FAS_SKIP_COARSE_U = 2 };
 int mgrit_hip_fas_fused_opts(mgrit_hip_engine *e, int lvl, int triples_id, int opts);
+/* How mgrit_hip_fas_fused_opts(MGRIT_HIP_FAS_WITH_F_RELAX) walks a triples list on Heat1D levels with separable forcing: in chunks of
+ * consecutive items (an item that starts from the C-point the item before it ends on takes that point from registers), chunk = 0:
+ * the length by the library's rule (4, 2 or 1 by the list's items per workgroup the chip holds; levels of one group of values,
+ * n <= 1024, stay item by item: measured slower in chunks), chunk = n > 0: up to n items on every level;
+ * chunk = -1: item by item, the kernel of before. Same values either way, bit for bit. Applies to the lists that exist (their chunk
+ * views are made again here, never at a launch) and to those created later. The engine starts with 0, or with what the environment
+ * variable MGRIT_HIP_FFAS says (0: item by item, n > 0: chunks of n; anything that is not a number counts as unset). A view is made once per list and length and kept for the engine's life. chunk < -1: MGRIT_HIP_EINVAL. */
+int mgrit_hip_set_fas_chunk(mgrit_hip_engine *e, int chunk);
+/* How many chunks the next mgrit_hip_fas_fused_opts(MGRIT_HIP_FAS_WITH_F_RELAX) of this list launches over: the number of chunks of
+ * its current view, or 0 when the sweep goes item by item (set_fas_chunk(-1), the rule's one-group levels, levels the chunked
+ * kernel does not take). */
+int mgrit_hip_fas_chunks(mgrit_hip_engine *e, int lvl, int triples_id, int *n_chunks);
 /* v^{l+1}_j = u^{l+1}_j for the coarse slots of a pair list (row-wise part of mgrit.py:520) */
 int mgrit_hip_copy_pairs_u_to_v(mgrit_hip_engine *e, int lvl, int pairs_id);
 

@@ -1073,14 +1073,27 @@ class HipBackend:
         self._settle(lvl)
         if not triples:
             return
+        opts = (hip_lib.FAS_WITH_F_RELAX if with_f_relax else 0) | (hip_lib.FAS_SKIP_COARSE_U if skip_coarse_u else 0)
+        check(self.lib.mgrit_hip_fas_fused_opts(self.h, lvl, self._triples_id(lvl, triples), opts))
 
+    def _triples_id(self, lvl, triples):
         def create():
             tid = C.c_int(-1)
             fi, pr, co = _cols(triples, 3)
             check(self.lib.mgrit_hip_triples_create(self.h, lvl, len(triples), _ptr(fi), _ptr(pr), _ptr(co), C.byref(tid)))
             return tid.value
-        opts = (hip_lib.FAS_WITH_F_RELAX if with_f_relax else 0) | (hip_lib.FAS_SKIP_COARSE_U if skip_coarse_u else 0)
-        check(self.lib.mgrit_hip_fas_fused_opts(self.h, lvl, self._handle(self._pairs, lvl, triples, "triples", create), opts))
+        return self._handle(self._pairs, lvl, triples, "triples", create)
+
+    def fas_chunks(self, lvl, triples):
+        """mgrit_hip_fas_chunks: the chunks fas_fused(with_f_relax=True) launches over for this list, 0 = item by item"""
+        n = C.c_int(-1)
+        check(self.lib.mgrit_hip_fas_chunks(self.h, lvl, self._triples_id(lvl, triples), C.byref(n)))
+        return n.value
+
+    def set_fas_chunk(self, chunk):
+        """mgrit_hip_set_fas_chunk: -1 the item-by-item kernel of fas_fused(with_f_relax=True), 0 chunks by the library's rule, n > 0
+        chunks of n (same values; a cycle that has been captured already keeps the kernel it was captured with)"""
+        check(self.lib.mgrit_hip_set_fas_chunk(self.h, int(chunk)))
 
     def copy_pairs_u_to_v(self, lvl, pairs):
         if pairs:

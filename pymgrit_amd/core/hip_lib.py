@@ -69,6 +69,8 @@ EXPORTS = {
                                            C.POINTER(C.c_int)]),
     "mgrit_hip_fas_fused": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "mgrit_hip_fas_fused_opts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "mgrit_hip_set_fas_chunk": (C.c_int, [C.c_void_p, C.c_int]),
+    "mgrit_hip_fas_chunks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "mgrit_hip_copy_pairs_u_to_v": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "mgrit_hip_error_correction": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "mgrit_hip_interpolate": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),

@@ -1414,6 +1414,90 @@ __global__ void __launch_bounds__(TB) fas_fused1_kernel(LevelDev L, LevelDev Lc,
     wq.end(t);
 }
 
+// fas_fused1_kernel<.., PROP = true> over CHUNKS of consecutive items, built from cfas_kernel's parts (round 6). The items of a
+// triples list whose starting C-point is the closing C-point of the item before them are walked in time order by one workgroup
+// (I.cstart = previous fine C slot, I.cend = fine slot, I.cend_coarse = coarse slot; chunks by mgrit_hip_triples_create), so
+//   - the C-point an item ends on stays in registers as the next item's start: one row read per CHUNK instead of per item;
+//   - the coarse Phi comes FIRST, from the very registers the F-steps start from, and q = Phi_{l+1}(u_cs) waits in LDS (every Phi
+//     here is taken in closed form, sm.tab is free): u_cs is not fetched a second time for it;
+//   - u_ce is fetched ONCE, behind the last fine Phi (fas_fused1_kernel reads it in front of that Phi, for w = g_ce - u_ce, and
+//     again behind it). In front of it, a third vector beside x and the row of g that is in flight is what made a straight port
+//     of that kernel spill 62-67 VGPRs in the 1024-thread instances; see `touch` below for how the row is still on its way by then.
+// Rows through HBM per item: m of g, u_ce, and the stores of g^{l+1}, v^{l+1} and (unless opts bit 1) u^{l+1}; one more per chunk.
+// Values and operation order per item are fas_fused1_kernel's: x = g_k + Phi_l(x) for the F-points, then
+// x = ((g_ce - u_ce) + Phi_l(x)) + u_ce, x = x - q. ONE inlined call site of the fine Phi and one of the coarse Phi.
+// Spilled VGPRs of the 1024-thread instances: 21 (no forcing) / 14 (forcing) against 73 in fas_fused1_kernel; none at 512 and 64.
+template <int FORCE, int TB = 1024>
+__global__ void __launch_bounds__(TB) ffas_kernel(LevelDev L, LevelDev Lc, IntervalsDev I, int opts) {
+    constexpr int KIND = MGRIT_HIP_STEPPER_HEAT1D;
+    WG_PROLOGUE_TB(TB);
+    (void)lane;
+    constexpr bool ONE = TB == LANES;   // one wave per state: Phi without the cross-group exchange (heat_solve)
+    stage_other_level(sm, Lc, t);
+    for (wq.begin(L.sched, L.xcc0_limit, wgq_slot, t); wq.cur < I.n_chunks; wq.advance(t)) {
+        const int k = wq.cur;
+        wq.prefetch(t);
+        const int i0 = I.chunk_first[k], cnt = I.chunk_len[k];
+        double x[E];
+        load_row_nt(L.u + (size_t)I.cstart[i0] * L.ld, sl, x, L.stream_rows);
+        for (int it = i0; it < i0 + cnt; ++it) {
+            const int cs = I.cstart[it], ce = I.cend[it], jc = I.cend_coarse[it];
+            // the thread index of this item, opaque to the compiler: everything a lane derives from it (row offsets, the lane's
+            // padding masks and table addresses of both levels) is then worked out where it is used instead of once in front of the
+            // chunk loop, where ~25 more VGPRs of such values stayed live -- and spilled -- across every Phi (38 spilled against 14)
+            int ti = t;
+            asm volatile("" : "+v"(ti));
+            const int li = ti & 63;
+            const unsigned si = slot0(ti);
+            {   // q = Phi_{l+1}(u_cs) with the coarse forcing. u_cs waits in LDS meanwhile (this lane's own slots: no barrier), then
+                // q takes its place there: one vector live across each Phi of the item
+#pragma unroll
+                for (int q = 0; q < 8; ++q) sm.tab[si + q * 64] = make_double2(x[2 * q], x[2 * q + 1]);
+                phi_other_level<FORCE, false, ONE>(x, ctx, Lc, jc, sm, si, ti, li, wave, G);
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    const double2 xv = sm.tab[si + q * 64];
+                    sm.tab[si + q * 64] = make_double2(x[2 * q], x[2 * q + 1]);
+                    x[2 * q] = xv.x;
+                    x[2 * q + 1] = xv.y;
+                }
+            }
+            load_coef(ctx.c, L.cs + (ctx.cur >= 0 ? ctx.cur : 0));   // back to this level's set (ctx.cur < 0: any set, phi_apply loads the right one)
+            double w[E];
+            int touch = 0;
+            for (int i = cs + 1; i <= ce; ++i) {
+                load_row_nt(L.g + (size_t)i * L.ld, si, w, L.stream_rows);   // in flight while Phi runs
+                // u_ce is wanted right behind the last Phi and not before it (a third vector in registers across that Phi costs
+                // ~50 spilled VGPRs): in front of it every lane reads ONE word of the row, 128 bytes apart -- the wave's 8 KB share
+                // line by line --, so the row comes into L2 under the Phi for the price of one register
+                if (i == ce) touch = reinterpret_cast<const int *>(L.u + (size_t)ce * L.ld)[(wave << 11) + (li << 5)];
+                phi_apply<KIND, FORCE, true, 0, false, ONE>(x, ctx, L, i, sm, ti, li, wave, G);
+                if (i < ce) {
+#pragma unroll
+                    for (int e = 0; e < E; ++e) x[e] = w[e] + x[e];
+                }
+            }
+            asm volatile("" : : "v"(touch));   // (keeps the load above)
+            double ui[E];
+            load_row(L.u + (size_t)ce * L.ld, si, ui);
+#pragma unroll
+            for (int e = 0; e < E; ++e) x[e] = ((w[e] - ui[e]) + x[e]) + ui[e];
+            if (!(opts & 2)) store_row_nt(Lc.u + (size_t)jc * Lc.ld, si, ui, Lc.stream_rows);
+            store_row_nt(Lc.v + (size_t)jc * Lc.ld, si, ui, Lc.stream_rows);
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {   // q, parked above by this very lane
+                const double2 qv = sm.tab[si + q * 64];
+                x[2 * q] = x[2 * q] - qv.x;
+                x[2 * q + 1] = x[2 * q + 1] - qv.y;
+            }
+            store_row_nt(Lc.g + (size_t)jc * Lc.ld, si, x, Lc.stream_rows);
+#pragma unroll
+            for (int e = 0; e < E; ++e) x[e] = ui[e];   // the next item of the chunk starts from u_ce
+        }
+    }
+    wq.end(t);
+}
+
 // --- spatial transfer kernels (bandwidth-bound, elementwise over ROW POSITIONS of the destination) ---------------
 // restriction: dst row d_idx[p] <- R(src row s_idx[p]). kind 0 copy (same T: position-wise copy); kind 1 full
 // weighting (examples/example_spatial_coarsening.py:33-55: sol[2i]*1/4 + sol[2i+1]*1/2 + sol[2i+2]*1/4).
@@ -1503,7 +1587,11 @@ struct RunList {
 struct PairList {
     int n = 0;
     int32_t *d_fine = nullptr, *d_coarse = nullptr, *d_iota = nullptr, *d_prev = nullptr;
-    std::vector<int32_t> h_fine, h_coarse;
+    std::vector<int32_t> h_fine, h_coarse, h_prev;   // h_prev: mgrit_hip_triples_create only
+    IntervalsDev chunks{};   // a triples list as chunks of consecutive items (ffas_kernel): cstart = d_prev, cend = d_fine, cend_coarse = d_coarse
+    int chunks_of = 0;       // the chunk length they were cut for (0: none made; -1: this list goes item by item -- the rule's word
+                             // for one-group levels, and every list ffas_kernel cannot take: triples_chunks)
+    std::map<int, IntervalsDev> chunk_views;   // the views made so far, by chunk length: a length asked for again uploads nothing
     BatchPlans fine_to_coarse, fine_to_rows, coarse;   // fine half into g^{l+1} (dst: the coarse slot) or into rows (dst: the pair's position)
 };
 
@@ -1654,6 +1742,7 @@ struct mgrit_hip_engine {
     std::vector<TimeRec> trecs;              // one per timed entry-point call since the last drain
     std::vector<hipEvent_t> ev_pool;         // events of drained records, reused
     hipEvent_t last0 = nullptr, last1 = nullptr;   // events of the most recent timed call (mgrit_hip_last_kernel_ms)
+    int fas_chunk = 0;            // mgrit_hip_set_fas_chunk: -1 fas_fused1_kernel, 0 chunks by the library's rule, n > 0 chunks of n
     int reserve = 0;              // mgrit_hip_set_reserve: CUs of XCD 0 the sweeps leave to the chain workers (0: program order)
     int *sched = nullptr;         // device counter block (1 KB, allocated with the first chain / planned launch): [0..2] {next, xcc0,
                                   // done} of the sweeps' item queue, [4..5] {tickets, done} of the chain's worker selection (both
@@ -1935,6 +2024,19 @@ int instance_tb(int T, bool one_wave) { return one_wave && T == LANES ? LANES : 
 int cycle_force(int fm) { return fm == 0 ? 0 : fm == 1 ? 4 : 2; }
 // cfas_kernel and the two-point wide pass: every term streamed
 int streamed_force(int fm) { return fm == 0 ? 0 : 2; }
+// an engine's first word on the FAS sweep with its F-relaxation (mgrit_hip_set_fas_chunk), from the measurement switch MGRIT_HIP_FFAS,
+// read once: 0 (or a negative number) = fas_fused1_kernel as before round 6, n > 0 = chunks of n, unset or not a number = the library's rule
+int ffas_env() {
+    static const int v = [] {
+        const char *s = std::getenv("MGRIT_HIP_FFAS");
+        if (!s) return 0;
+        char *end = nullptr;
+        const long n = std::strtol(s, &end, 10);
+        if (end == s || *end != '\0') return 0;   // not a number: as if unset (a typo must not switch the kernel off)
+        return n > 0 ? (int)std::min(n, 1L << 20) : -1;
+    }();
+    return v;
+}
 // time-parallel forward solve: one term in LDS (4), the other modes as they are
 int blk_force(int fm) { return fm == 1 ? 4 : fm; }
 // wide Heat1D states: forcing rows (3) as they are, terms streamed
@@ -1988,6 +2090,12 @@ auto fas_fused1_fn(int fm, bool prop, int T) {
 auto cfas_fn(int fm, int T) {
     return pick<0, 2>(streamed_force(fm), [&](auto F) {
         return pick<LANES, 512, 1024>(instance_tb(T, true), [&](auto TB) { return &cfas_kernel<F, TB>; });
+    });
+}
+
+auto ffas_fn(int fm, int T) {
+    return pick<0, 2>(streamed_force(fm), [&](auto F) {
+        return pick<LANES, 512, 1024>(instance_tb(T, true), [&](auto TB) { return &ffas_kernel<F, TB>; });
     });
 }
 
@@ -2099,6 +2207,7 @@ int register_lds_limits() {
                     }
                     allow(fas_fused1_fn(fm, g, T), big);   // (g walks PROP)
                     allow(cfas_fn(fm, T), big);
+                    allow(ffas_fn(fm, T), big);
                     allow(ecfr_fn(fm, g, T), big);
                 }
         for (int kind : {MGRIT_HIP_STEPPER_HEAT1D, MGRIT_HIP_STEPPER_ADVECTION1D})
@@ -3290,6 +3399,7 @@ int mgrit_hip_create(mgrit_hip_engine **out, int n_levels, void *stream) {
     if (mgrit_hip_device_count() < 1) return fail(MGRIT_HIP_ENODEV, "no HIP device visible: the MI355X engine has no CPU fallback");
     mgrit_hip_engine *e = new mgrit_hip_engine();
     e->n_levels = n_levels;
+    e->fas_chunk = ffas_env();
     e->stream = static_cast<hipStream_t>(stream);
     e->L.resize(n_levels);
     for (auto &lv : e->L) lv.arena = &e->arena;
@@ -3985,6 +4095,60 @@ int mgrit_hip_fas_rhs(mgrit_hip_engine *e, int lvl, int pairs_id) {
     return fas_coarse_half(e, lvl, pl);
 }
 
+// The chunk view of a triples list for ffas_kernel: consecutive items join while the C-point an item starts from is the one
+// the item before it ends on, up to `chunk` items (0: the rule of mgrit_hip_intervals_create by the list's items per workgroup
+// slot -- 4, 2 or 1: a list with fewer items than the chip holds workgroups wants every one of them running at once). Items are
+// independent, so where a run is cut has no effect on the values: a list -- one block of a planned cycle, one rank's share -- is
+// cut at its own ends, and a gap between two items ends a chunk.
+// (round 6, config 3's level 1 -- 4096 items, 16 per workgroup -- through ffas_kernel, the sweep alone / the cycle, three runs each:
+// chunks of 1 -> 1.00 ms / -, 4 -> 0.930 / 6.42-6.43, 8 -> 0.928 / 6.43-6.60, 16 -> 0.907 / 6.38-6.49, 32 -> 1.27 / 6.80-6.83 -- at 32
+// half the workgroups have no chunk; 16 is 0.02 ms ahead in the sweep and inside the cycle's run-to-run spread: the rule stays at 4)
+// The rule leaves levels of ONE group of values (one wave per state) to fas_fused1_kernel -- chunks_of = -1 --: config 2's 256 items
+// are one per workgroup either way, and the lone wave's chain of dependent instructions is longer here (the coarse Phi in front of
+// the F-steps instead of beside the row loads; 13.9 -> 20.4 us per sweep). A forced length takes ffas_kernel on such levels too.
+namespace {
+// Views are made only for the lists ffas_kernel can take -- Heat1D with separable forcing on both levels of the pair, the copy
+// transfer, a level > 0 (the sweep with its F-relaxation reads g) --: every other list (Heat2D, Allen-Cahn, two-point, Advection1D,
+// forcing rows, level 0) keeps chunks_of = -1 and goes the way it went before, whatever mgrit_hip_fas_fused_opts then says to it.
+bool ffas_can_take(const mgrit_hip_engine *e, int lvl) {
+    if (lvl < 1 || lvl + 1 >= e->n_levels) return false;
+    const Level &lf = e->L[lvl], &lc = e->L[lvl + 1];
+    return lf.set && lc.set && !lf.h2d && !lc.h2d && !lf.wide && !lc.wide && lf.dev.kind == MGRIT_HIP_STEPPER_HEAT1D &&
+           lc.dev.kind == MGRIT_HIP_STEPPER_HEAT1D && lf.transfer == MGRIT_HIP_TRANSFER_COPY && lf.dev.n == lc.dev.n && lf.dev.T >= LANES &&
+           force_mode(lf) == force_mode(lc) && force_mode(lf) != 3;
+}
+
+int triples_chunks(mgrit_hip_engine *e, int lvl, PairList &pl, int chunk) {
+    Level &lv = e->L[lvl];
+    if (!ffas_can_take(e, lvl)) { pl.chunks_of = -1; return 0; }
+    if (chunk <= 0) {
+        if (lv.dev.T == LANES) { pl.chunks_of = -1; return 0; }
+        const int per_slot = pl.n / (2 * 256 * wgs_per_cu(lv));
+        chunk = per_slot >= 4 ? 4 : per_slot >= 2 ? 2 : 1;
+    }
+    if (pl.chunks_of == chunk) return 0;
+    const auto seen = pl.chunk_views.find(chunk);
+    if (seen != pl.chunk_views.end()) { pl.chunks = seen->second; pl.chunks_of = chunk; return 0; }
+    std::vector<int32_t> cf, cl;
+    for (int i = 0; i < pl.n;) {
+        int len = 1;
+        while (i + len < pl.n && len < chunk && pl.h_prev[i + len] == pl.h_fine[i + len - 1]) ++len;
+        cf.push_back(i); cl.push_back(len);
+        i += len;
+    }
+    int32_t *d_cf = nullptr, *d_cl = nullptr;
+    int rc;
+    if ((rc = dev_upload(lv, e->stream, cf, &d_cf)) || (rc = dev_upload(lv, e->stream, cl, &d_cl))) return rc;
+    IntervalsDev d{};
+    d.cstart = pl.d_prev; d.cend = pl.d_fine; d.cend_coarse = pl.d_coarse; d.chunk_first = d_cf; d.chunk_len = d_cl;
+    d.n_chunks = (int)cf.size();
+    pl.chunks = d;
+    pl.chunks_of = chunk;
+    pl.chunk_views[chunk] = d;
+    return 0;
+}
+}  // namespace
+
 int mgrit_hip_triples_create(mgrit_hip_engine *e, int lvl, int n, const int32_t *fine_idx, const int32_t *prev_fine_idx,
                              const int32_t *coarse_idx, int *id_out) {
     int rc = mgrit_hip_pairs_create(e, lvl, n, fine_idx, coarse_idx, id_out);
@@ -3993,8 +4157,36 @@ int mgrit_hip_triples_create(mgrit_hip_engine *e, int lvl, int n, const int32_t 
     for (int p = 0; p < n; ++p)
         if (!prev_fine_idx || prev_fine_idx[p] < 0 || prev_fine_idx[p] >= fine_idx[p] || fine_idx[p] < 1)
             return fail(MGRIT_HIP_EINVAL, "triple %d: previous fine C slot must be a local slot below the fine slot", p);
-    std::vector<int32_t> hp(prev_fine_idx, prev_fine_idx + n);
-    return dev_upload(lv, e->stream, hp, &lv.pairs[*id_out].d_prev);
+    PairList &pl = lv.pairs[*id_out];
+    pl.h_prev.assign(prev_fine_idx, prev_fine_idx + n);
+    if ((rc = dev_upload(lv, e->stream, pl.h_prev, &pl.d_prev))) return rc;
+    // the chunk view of the list is made here, not at a launch: a launch may sit inside a stream capture, which takes no uploads
+    return e->fas_chunk >= 0 ? triples_chunks(e, lvl, pl, e->fas_chunk) : 0;
+}
+
+int mgrit_hip_set_fas_chunk(mgrit_hip_engine *e, int chunk) {
+    if (!e) return fail(MGRIT_HIP_EINVAL, "null engine");
+    if (chunk < -1) return fail(MGRIT_HIP_EINVAL, "FAS chunk %d: -1 (item by item), 0 (the library's rule) or a length", chunk);
+    e->fas_chunk = chunk;
+    if (chunk < 0) return 0;
+    // the lists that exist already take the view of the new length: made once per list and length and kept (a captured cycle may
+    // still read the arrays of an earlier length, and a caller that goes back and forth between lengths uploads nothing new)
+    for (int lvl = 0; lvl < e->n_levels; ++lvl)
+        for (PairList &pl : e->L[lvl].pairs) {
+            const int rc = pl.d_prev ? triples_chunks(e, lvl, pl, chunk) : 0;
+            if (rc) return rc;
+        }
+    return 0;
+}
+
+int mgrit_hip_fas_chunks(mgrit_hip_engine *e, int lvl, int triples_id, int *n_chunks) {
+    PairList *pl;
+    int rc = get_pairs(e, lvl, triples_id, &pl);
+    if (rc) return rc;
+    if (!n_chunks) return fail(MGRIT_HIP_EINVAL, "null output");
+    if (!pl->d_prev) return fail(MGRIT_HIP_EINVAL, "list %d was not created by mgrit_hip_triples_create", triples_id);
+    *n_chunks = (e->fas_chunk >= 0 && pl->chunks_of > 0) ? pl->chunks.n_chunks : 0;
+    return 0;
 }
 
 int mgrit_hip_fas_fused(mgrit_hip_engine *e, int lvl, int triples_id) { return mgrit_hip_fas_fused_opts(e, lvl, triples_id, 0); }
@@ -4021,6 +4213,14 @@ int mgrit_hip_fas_fused_opts(mgrit_hip_engine *e, int lvl, int triples_id, int o
         // keeping them in registers, and the registers are needed for the partial g that stays live across the coarse Phi
         // one forcing term: its space factor lives in LDS (FORCE 4, closed-form Phi); bit 2 tells the kernel that the coarse
         // level's factor is the same vector (same spatial grid, same rhs), so the coarse Phi takes it from there too
+        // with its F-relaxation the sweep walks chunks of consecutive items (ffas_kernel, round 6) unless mgrit_hip_set_fas_chunk(-1)
+        // or MGRIT_HIP_FFAS=0 ask for the item-by-item kernel, or the rule leaves the list to it (one-group levels, triples_chunks);
+        // the timing kind is the same for both
+        if ((opts & MGRIT_HIP_FAS_WITH_F_RELAX) && e->fas_chunk >= 0 && pl->chunks_of >= 0) {
+            if (pl->chunks_of == 0) return fail(MGRIT_HIP_EINVAL, "list %d has no chunk view", triples_id);
+            return launch(ffas_fn(fm, lf.dev.T), dim3(persistent_grid(lf, pl->chunks.n_chunks)), dim3(lf.dev.T), smem_bytes(lf.G, lf.dev.kind),
+                          e->stream, sched_dev(e, lf), lc.dev, pl->chunks, opts & MGRIT_HIP_FAS_SKIP_COARSE_U);
+        }
         if (lf.same_factor_below < 0) lf.same_factor_below = (fm == 1 && lf.s_host == lc.s_host) ? 1 : 0;   // (131 KB compared once)
         const int kopts = opts | (lf.same_factor_below ? 4 : 0);
         return launch(fas_fused1_fn(fm, (opts & MGRIT_HIP_FAS_WITH_F_RELAX) != 0, lf.dev.T), dim3(persistent_grid(lf, pl->n)), dim3(lf.dev.T),
