@@ -291,11 +291,14 @@ class Mgrit(RankSchedules, PipelinedLoop):
     # ------------------------------------------------------------------------------------------------
     def _cached(self, key, build):
         """index-derived lists are built once per (kind, level) and reused by every sweep (they also carry the
-        backend's device-side handle, see IndexList)"""
+        backend's device-side handle, see IndexList). build() returns a list or, for a route of the cycle (rank_schedules.py),
+        None (no such route on this level: remembered as well) or a tuple of the route's lists and flags"""
         store = self.__dict__.setdefault('_index_lists', {})
         if key not in store:
+            def keep(x):
+                return x if isinstance(x, (IndexArray, bool, int)) else IndexList(x)
             got = build()
-            store[key] = got if isinstance(got, IndexArray) else IndexList(got)
+            store[key] = None if got is None else tuple(keep(x) for x in got) if isinstance(got, tuple) else keep(got)
         return store[key]
 
     def _f_runs(self, lvl):
@@ -390,10 +393,7 @@ class Mgrit(RankSchedules, PipelinedLoop):
             want = int(options.plan_blocks)
         else:
             want = int(getattr(self.backend, "plan_blocks", lambda: 1)() or 1)
-        own = all(getattr(type(self), name) is getattr(Mgrit, name) for name in
-                  ("iteration", "f_relax", "c_relax", "fas_residual", "error_correction", "forward_solve", "_exchange",
-                   "_ec_f_relax", "_fas_residual_fused", "_relax_f"))
-        usable = (self._one_rank_like() and self.lvl_max > 1 and own and self._dry is None and
+        usable = (self._one_rank_like() and self.lvl_max > 1 and self._own('plan') and self._dry is None and
                   not getattr(self, "_sweep_timing", False) and     # per-sweep debug timing reports the sweeps in program order
                   getattr(self.backend, "plan_allowed", lambda: True)())
         if probe_usable:
@@ -445,130 +445,133 @@ class Mgrit(RankSchedules, PipelinedLoop):
             self.forward_solve(lvl=lvl)
             return
         fresh, self._fresh_level = getattr(self, "_fresh_level", None) == lvl, None
-        coarse = self._coarse_down(lvl) if (fresh and first_f and lvl > 0) else None
-        crank = self._coarse_down_rank(lvl) if (coarse is None and fresh and first_f and lvl > 0 and self.comm_time_size > 1) else None
-        if crank is not None:
-            # several ranks: the two coarse-level passes on the rank's complete intervals; the first local C-point, the partial
-            # intervals at the two ends and every exchange point as in the sweep-by-sweep form
-            fc_runs, c0_run, edge_runs = crank
-            self.f_relax(lvl=lvl, runs=edge_runs)                        # first F-relaxation: ops 0 / 1, partial intervals
-            self._exchange(lvl, send_idx=self._last_slot(lvl) if self.last_is_f_point[lvl] else None,
-                           recv_idx=0 if self.first_is_c_point[lvl] else None, dest=self.send_to[lvl], src=self.get_from[lvl], op=2)
-            self.backend.relax(lvl, c0_run, 'C')
-            self.backend.relax(lvl, fc_runs, 'FC')                       # ... and C-relaxation, complete intervals
-            self.f_relax(lvl=lvl, runs=edge_runs)                        # second F-relaxation: ops 0 / 1, partial intervals
-            self._fas_residual_fused(lvl, with_f_relax=True)             # ... folded into the FAS pass for the complete intervals
-            self._fresh_level = lvl + 1
-            self.iteration(lvl=lvl + 1, cycle_type=cycle_type, iteration=iteration, first_f=True)
-            self._up(lvl, None)
-            if cycle_type == 'F':
-                self.iteration(lvl=lvl, cycle_type='V', iteration=iteration, first_f=False)
-            return
-        if coarse is not None:
-            # a level the finer level's FAS sweep has just filled (u == v): F-relaxation + C-relaxation in one pass, then the
-            # F-relaxation folded into the FAS sweep (the F-points of the way down are stored by neither)
-            fc_runs, triples, head, skip_u = coarse
-            ranks = self.comm_time_size > 1     # aligned ranks: the exchange points of the sweeps this pass stands for
-            # (op 0 of the first F-relaxation, mgrit.py:271, would carry the last point of the rank before as the finer level's FAS
-            # sweep has just injected it -- the very row op 4 of that sweep has put into the ghost slot already (Mgrit._x4; the
-            # level is `fresh`): not sent a second time)
-            if self.cf_iter[lvl] == 1:
-                self.backend.relax(lvl, fc_runs, 'FC')
-                if ranks:
-                    self._x0(lvl)               # f_relax (mgrit.py:275), behind the C-relaxation
-            self._head(lvl, head, 'u')
-            self.backend.fas_fused(lvl, triples, with_f_relax=True, skip_coarse_u=skip_u)
-            self._head(lvl, head, 'v')
-            if ranks:
-                if skip_u and self.send_to[lvl + 1] >= 0:   # the one row of u^{l+1} that op 4 sends
-                    self.backend.restrict_u(lvl, self._cached(('pair_last', lvl), lambda: [self._xpairs(lvl)[-1]]))
-                self._x4(lvl)                   # fas_residual (mgrit.py:511-520)
-            self._fresh_level = lvl + 1
-            self.iteration(lvl=lvl + 1, cycle_type=cycle_type, iteration=iteration, first_f=True)
-            self._up(lvl, None)
-            if cycle_type == 'F':
-                self.iteration(lvl=lvl, cycle_type='V', iteration=iteration, first_f=False)
-            return
-        if first_f and (lvl > 0 or iteration == 0):
+        route, lists = self._route(lvl, fresh and first_f)
+        if first_f and (lvl > 0 or iteration == 0) and route not in ('coarse', 'coarse_rank'):    # (those two fold it in)
             # (tried in round 3: this F-relaxation as part of the general way-down pass on a level the finer level's FAS sweep has
             # just filled -- per interval the F-points from v, not stored. Bit-identical and slower: config 5's level-1 pass 0.44 ->
             # 0.76 ms for the 0.17 ms launch it replaces; the extra Phi per interval costs more than the rows it saves.)
             self.f_relax(lvl=lvl)
-        fused = self._level_intervals(lvl)     # whole-level sweeps in one pass (device backend, one rank), or None
-        shard = self._rank_intervals(lvl) if (fused is None and self.comm_time_size > 1 and self.cf_iter[lvl] >= 1) else None
-        if shard is not None:
-            # several ranks: the same down pass on the rank's COMPLETE intervals (both C-points local); the first local C-point,
-            # the partial intervals at the two ends and every exchange point as in the sweep-by-sweep form
-            intervals, c0_run, edge_runs = shard
-            for _ in range(self.cf_iter[lvl] - 1):
-                self.backend.f_relax_follows = True
-                try:
-                    self.c_relax(lvl=lvl)
-                finally:
-                    self.backend.f_relax_follows = False
-                self.f_relax(lvl=lvl)
-            self._exchange(lvl, send_idx=self._last_slot(lvl) if self.last_is_f_point[lvl] else None,
-                           recv_idx=0 if self.first_is_c_point[lvl] else None, dest=self.send_to[lvl], src=self.get_from[lvl], op=2)
-            self.backend.relax(lvl, c0_run, 'C')                    # the first local C-point (its interval began on the rank before)
-            self.backend.cf_fas(lvl, intervals)                     # C-relaxation, F-relaxation, FAS residual of the complete intervals
-            self.f_relax(lvl=lvl, runs=edge_runs)                   # ops 0 / 1 and the partial intervals
-            self._fas_residual_fused(lvl, skip_triples=True)        # ops 3 / 4 and the first local C-point
-            self._fresh_level = lvl + 1
-            self.iteration(lvl=lvl + 1, cycle_type=cycle_type, iteration=iteration, first_f=True)
-            self._up(lvl, None)
-            return
-        down = fused is not None and self.cf_iter[lvl] >= 1
-        gen = self._gen_intervals(lvl) if (fused is None and self.cf_iter[lvl] >= 1) else None
-        for _ in range(self.cf_iter[lvl] - (1 if (down or gen is not None) else 0)):
+        getattr(self, '_down_' + route)(lvl, lists)
+        self._fresh_level = lvl + 1      # the next level starts from what the FAS sweep has just written (u == v there)
+        self.iteration(lvl=lvl + 1, cycle_type=cycle_type, iteration=iteration, first_f=True)
+        # (the whole-level lists: the way up of level 0 takes them also where cf_iter = 0 has sent the way down sweep by sweep)
+        self._up(lvl, self._level_intervals(lvl), lists if route == 'gen' else None)
+        if lvl != 0 and cycle_type == 'F':
+            self.iteration(lvl=lvl, cycle_type='V', iteration=iteration, first_f=False)
+
+    # the ways down a level in order of precedence: (route, builder of its lists in rank_schedules.py, for several ranks only);
+    # the first two on a level the finer level's FAS sweep has just filled, the others where there is a C-relaxation to take
+    # (cf_iter >= 1); where none applies: sweep by sweep
+    _FRESH = (('coarse', '_coarse_down', False), ('coarse_rank', '_coarse_down_rank', True))
+    _PASSES = (('level', '_level_intervals', False), ('shard', '_rank_intervals', True), ('gen', '_gen_intervals', False))
+
+    def _route(self, lvl, fresh):
+        """(route, lists) of the way down of level lvl (Mgrit._down_<route>); fresh: the finer level's FAS sweep has just filled
+        the level (u == v) and the cycle opens it with an F-relaxation"""
+        ranks = self.comm_time_size > 1
+        for route, builder, sharded in (self._FRESH if fresh and lvl > 0 else ()) + (self._PASSES if self.cf_iter[lvl] >= 1 else ()):
+            lists = getattr(self, builder)(lvl) if (ranks or not sharded) else None
+            if lists is not None:
+                return route, lists
+        return 'plain', None
+
+    def _cf_sweeps(self, lvl, count):
+        """C-relaxation + F-relaxation, `count` times"""
+        for _ in range(count):
             self.backend.f_relax_follows = True     # (the F-relaxation below rewrites every F-point: nothing to put in place first)
             try:
                 self.c_relax(lvl=lvl)
             finally:
                 self.backend.f_relax_follows = False
             self.f_relax(lvl=lvl)
-        if down:      # the last C-relaxation + F-relaxation + the FAS residual: one pass
-            head = self._cached(('pair_head_x', lvl), lambda: self._pairs(lvl, skip_first=False)[:1] if self.comm_time_rank == 0 else [])
-            if self.comm_time_size > 1:
-                # aligned ranks: op 0 of the F-relaxation inside the pass (mgrit.py:306-310) wants the RELAXED last C-point, which
-                # the pass itself computes. With pre-relaxed C-points (backend_hip._f_stale == 2) the cycle before has left exactly
-                # that value in the row of the last F-point; otherwise it is computed up front by a C-relaxation of that one
-                # point (the pass recomputes the same bits from the same F-point)
-                last = self._last_slot(lvl)
-                if getattr(self.backend, "_cycle_pre", False) and lvl == 0:
-                    self._x0(lvl, send_row=last - 1)
-                else:
-                    if self.last_is_c_point[lvl]:
-                        self.backend.relax(lvl, self._cached(('c_last', lvl), lambda: [(last, 1)]), 'C')
-                    self._x0(lvl)
-            self._head(lvl, head, 'u')
-            self.backend.cf_fas(lvl, fused)
-            self._head(lvl, head, 'v')
-            if self.comm_time_size > 1:
-                self._x4(lvl)
-        elif gen is not None:      # any 1-D stepper pair, any of the library's transfers: the same sweeps as three launches
-            head = self._cached(('pair_head_x', lvl), lambda: self._pairs(lvl, skip_first=False)[:1] if self.comm_time_rank == 0 else [])
-            if self.comm_time_size > 1:
-                # aligned ranks: op 0 of the F-relaxation inside the pass (mgrit.py:306-310) carries the RELAXED last C-point: computed
-                # up front by a C-relaxation of that one point (the pass recomputes the same bits from the same F-point)
-                last = self._last_slot(lvl)
-                if self.last_is_c_point[lvl]:
-                    self.backend.relax(lvl, self._cached(('c_last', lvl), lambda: [(last, 1)]), 'C')
-                self._x0(lvl)
-            self._head(lvl, head, 'u')
-            self._head(lvl, head, 'v')      # (the coarse half of the first interval starts from v^{l+1}_0)
-            if self.comm_time_size > 1:     # op 4 (mgrit.py:511-520) between the restriction and the coarse half, which reads v of the ghost
-                self.backend.gen_down(lvl, gen, 1)
-                self._x4(lvl)
-                self.backend.gen_down(lvl, gen, 2)
-            else:
-                self.backend.gen_down(lvl, gen)
+
+    def _down_plain(self, lvl, _):
+        """sweep by sweep (mgrit.py:276-279)"""
+        self._cf_sweeps(lvl, self.cf_iter[lvl])
+        self.fas_residual(lvl=lvl)
+
+    def _down_coarse(self, lvl, lists):
+        """a level the finer level's FAS sweep has just filled (u == v): F-relaxation + C-relaxation in one pass, then the
+        F-relaxation folded into the FAS sweep (the F-points of the way down are stored by neither)"""
+        fc_runs, triples, head, skip_u = lists
+        ranks = self.comm_time_size > 1     # aligned ranks: the exchange points of the sweeps this pass stands for
+        # (op 0 of the first F-relaxation, mgrit.py:271, would carry the last point of the rank before as the finer level's FAS
+        # sweep has just injected it -- the very row op 4 of that sweep has put into the ghost slot already (Mgrit._x4; the
+        # level is `fresh`): not sent a second time)
+        if self.cf_iter[lvl] == 1:
+            self.backend.relax(lvl, fc_runs, 'FC')
+            if ranks:
+                self._x0(lvl)               # f_relax (mgrit.py:275), behind the C-relaxation
+        self._head(lvl, head, 'u')
+        self.backend.fas_fused(lvl, triples, with_f_relax=True, skip_coarse_u=skip_u)
+        self._head(lvl, head, 'v')
+        if ranks:
+            if skip_u and self.send_to[lvl + 1] >= 0:   # the one row of u^{l+1} that op 4 sends
+                self.backend.restrict_u(lvl, self._last_pair(lvl))
+            self._x4(lvl)                   # fas_residual (mgrit.py:511-520)
+
+    def _down_coarse_rank(self, lvl, lists):
+        """several ranks: the two coarse-level passes on the rank's complete intervals, the rest as in _down_shard"""
+        fc_runs, c0_run, edge_runs = lists
+        self.f_relax(lvl=lvl, runs=edge_runs)                        # first F-relaxation: ops 0 / 1, partial intervals
+        self._refresh_ghost(lvl, 2)
+        self.backend.relax(lvl, c0_run, 'C')
+        self.backend.relax(lvl, fc_runs, 'FC')                       # ... and C-relaxation, complete intervals
+        self.f_relax(lvl=lvl, runs=edge_runs)                        # second F-relaxation: ops 0 / 1, partial intervals
+        self._fas_residual_fused(lvl, with_f_relax=True)             # ... folded into the FAS pass for the complete intervals
+
+    def _down_shard(self, lvl, lists):
+        """several ranks, level 0: the whole-level down pass on the rank's COMPLETE intervals (both C-points local); the first
+        local C-point, the partial intervals at the two ends and every exchange point as in the sweep-by-sweep form"""
+        intervals, c0_run, edge_runs = lists
+        self._cf_sweeps(lvl, self.cf_iter[lvl] - 1)
+        self._refresh_ghost(lvl, 2)
+        self.backend.relax(lvl, c0_run, 'C')                    # the first local C-point (its interval began on the rank before)
+        self.backend.cf_fas(lvl, intervals)                     # C-relaxation, F-relaxation, FAS residual of the complete intervals
+        self.f_relax(lvl=lvl, runs=edge_runs)                   # ops 0 / 1 and the partial intervals
+        self._fas_residual_fused(lvl, skip_triples=True)        # ops 3 / 4 and the first local C-point
+
+    def _down_level(self, lvl, fused):
+        """one rank, aligned ranks: the last C-relaxation + F-relaxation + the FAS residual in one pass"""
+        self._cf_sweeps(lvl, self.cf_iter[lvl] - 1)
+        head = self._first_pair(lvl)
+        if self.comm_time_size > 1:
+            self._x0_relaxed(lvl, pre=getattr(self.backend, "_cycle_pre", False) and lvl == 0)
+        self._head(lvl, head, 'u')
+        self.backend.cf_fas(lvl, fused)
+        self._head(lvl, head, 'v')
+        if self.comm_time_size > 1:
+            self._x4(lvl)
+
+    def _down_gen(self, lvl, gen):
+        """one rank, aligned ranks; any 1-D stepper pair, any of the library's transfers: the same sweeps as three launches"""
+        self._cf_sweeps(lvl, self.cf_iter[lvl] - 1)
+        head = self._first_pair(lvl)
+        if self.comm_time_size > 1:
+            self._x0_relaxed(lvl)
+        self._head(lvl, head, 'u')
+        self._head(lvl, head, 'v')      # (the coarse half of the first interval starts from v^{l+1}_0)
+        if self.comm_time_size > 1:     # op 4 (mgrit.py:511-520) between the restriction and the coarse half, which reads v of the ghost
+            self.backend.gen_down(lvl, gen, 1)
+            self._x4(lvl)
+            self.backend.gen_down(lvl, gen, 2)
         else:
-            self.fas_residual(lvl=lvl)
-        self._fresh_level = lvl + 1      # the next level starts from what the FAS sweep has just written (u == v there)
-        self.iteration(lvl=lvl + 1, cycle_type=cycle_type, iteration=iteration, first_f=True)
-        self._up(lvl, fused, gen)
-        if lvl != 0 and cycle_type == 'F':
-            self.iteration(lvl=lvl, cycle_type='V', iteration=iteration, first_f=False)
+            self.backend.gen_down(lvl, gen)
+
+    def _first_pair(self, lvl):
+        """the first point of the time grid as a one-pair list for _head (empty on the ranks that do not own it)"""
+        return self._cached(('pair_head_x', lvl), lambda: self._pairs(lvl, skip_first=False)[:1] if self.comm_time_rank == 0 else [])
+
+    def _refresh_ghost(self, lvl, op):
+        """ops 2 / 3 / 7: the last local F-point to the next owner's ghost slot (the point in front of its first C-point)"""
+        self._exchange(lvl, send_idx=self._last_slot(lvl) if self.last_is_f_point[lvl] else None,
+                       recv_idx=0 if self.first_is_c_point[lvl] else None, dest=self.send_to[lvl], src=self.get_from[lvl], op=op)
+
+    def _hand_over(self, lvl):
+        """op 4 (mgrit.py:511-517): the last local point of lvl+1 to the next owner's ghost slot"""
+        up = lvl + 1
+        self._exchange(up, send_idx=int(self.index_local[up][-1]) if self.send_to[up] >= 0 else None,
+                       recv_idx=0 if self.get_from[up] >= 0 else None, dest=self.send_to[up], src=self.get_from[up], op=4)
 
     def f_relax(self, lvl: int, ec: bool = False, runs=None) -> None:
         """F-relaxation (mgrit.py:292-333): every F-interval is propagated from its preceding point. Exchange:
@@ -627,8 +630,7 @@ class Mgrit(RankSchedules, PipelinedLoop):
     def c_relax(self, lvl: int) -> None:
         """C-relaxation (mgrit.py:335-370); op 2 = last local F-point to the next owner's ghost."""
         t0 = time.time()
-        self._exchange(lvl, send_idx=self._last_slot(lvl) if self.last_is_f_point[lvl] else None,
-                       recv_idx=0 if self.first_is_c_point[lvl] else None, dest=self.send_to[lvl], src=self.get_from[lvl], op=2)
+        self._refresh_ghost(lvl, 2)
         self.backend.relax(lvl, self._c_runs(lvl), 'C')
         self._log_sweep("C-relax", t0)
 
@@ -638,8 +640,7 @@ class Mgrit(RankSchedules, PipelinedLoop):
 
     def compute_residual(self) -> list:
         """Per-C-point norms of r_i = Phi(u_{i-1}) - u_i on level 0 (mgrit.py:387-413); op 7 ghost refresh."""
-        self._exchange(0, send_idx=self._last_slot(0) if self.last_is_f_point[0] else None,
-                       recv_idx=0 if self.first_is_c_point[0] else None, dest=self.send_to[0], src=self.get_from[0], op=7)
+        self._refresh_ghost(0, 7)
         return self.backend.residual_norms(self._c_points(0))
 
     def convergence_criterion(self, iteration: int) -> None:
@@ -682,8 +683,7 @@ class Mgrit(RankSchedules, PipelinedLoop):
         """the step-by-step forward solve (mgrit.py:459-486) overwrites every point of the coarsest level but the first before
         anything reads it, so the sweeps above need not store u there; the time-parallel form works on the defect
         of the level's CURRENT values and reads them all"""
-        return (type(self).forward_solve is Mgrit.forward_solve and
-                not getattr(self.backend, "block_r", {}).get(self.lvl_max - 1))
+        return self._own('coarsest_u_unread') and not getattr(self.backend, "block_r", {}).get(self.lvl_max - 1)
 
     def forward_solve(self, lvl: int) -> None:
         """Sequential time stepping on level ``lvl`` (mgrit.py:459-486); op 5 = pipeline hand-off between owners."""
@@ -724,12 +724,8 @@ class Mgrit(RankSchedules, PipelinedLoop):
             self._log_sweep("Fas residual", t0)
             return
         self.backend.restrict_u(lvl, self._pairs(lvl, skip_first=False))
-        self._exchange(lvl, send_idx=self._last_slot(lvl) if self.last_is_f_point[lvl] else None,
-                       recv_idx=0 if self.first_is_c_point[lvl] else None, dest=self.send_to[lvl], src=self.get_from[lvl], op=3)
-        self._exchange(lvl + 1,
-                       send_idx=int(self.index_local[lvl + 1][-1]) if self.send_to[lvl + 1] >= 0 else None,
-                       recv_idx=0 if self.get_from[lvl + 1] >= 0 else None,
-                       dest=self.send_to[lvl + 1], src=self.get_from[lvl + 1], op=4)
+        self._refresh_ghost(lvl, 3)
+        self._hand_over(lvl)
         self.backend.copy_u_to_v(lvl + 1)
         self.backend.fas_rhs(lvl, self._pairs(lvl, skip_first=True))
         self._log_sweep("Fas residual", t0)
@@ -746,18 +742,14 @@ class Mgrit(RankSchedules, PipelinedLoop):
             P = as_index_array(all_pairs, 2)
             return IndexArray(np.column_stack((P[1:, 0], P[:-1, 0], P[1:, 1])), width=3)
         triples = self._cached(('triples', lvl), build_triples)
-        self._exchange(lvl, send_idx=self._last_slot(lvl) if self.last_is_f_point[lvl] else None,
-                       recv_idx=0 if self.first_is_c_point[lvl] else None, dest=self.send_to[lvl], src=self.get_from[lvl], op=3)
+        self._refresh_ghost(lvl, 3)
         be.restrict_u(lvl, head)
         if not skip_triples:      # (skip: the whole-level pass of the rank's complete intervals has done exactly these)
             if with_f_relax:      # the F-relaxation of the triples' intervals is part of the pass (their F-points are not stored)
                 be.fas_fused(lvl, triples, with_f_relax=True)
             else:
                 be.fas_fused(lvl, triples)
-        self._exchange(lvl + 1,
-                       send_idx=int(self.index_local[lvl + 1][-1]) if self.send_to[lvl + 1] >= 0 else None,
-                       recv_idx=0 if self.get_from[lvl + 1] >= 0 else None,
-                       dest=self.send_to[lvl + 1], src=self.get_from[lvl + 1], op=4)
+        self._hand_over(lvl)
         be.copy_pairs_u_to_v(lvl, head)
         if self._ghost[lvl + 1]:  # v ghost = clone of the received u ghost; then the first local pair, unfused
             be.copy_pairs_u_to_v(lvl, self._cached(('pair_ghost', lvl), lambda: [(all_pairs[0][0], 0)] if all_pairs else []))
