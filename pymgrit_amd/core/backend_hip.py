@@ -8,7 +8,6 @@ is what output_fcn callbacks and subclasses of the reference read (SURVEY sectio
 No CPU fallback: constructing this backend without libmgrit_hip.so or without a GPU raises MgritHipError.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import torch
@@ -16,10 +15,6 @@ import torch
 from pymgrit_amd.core import hip_lib
 from pymgrit_amd.core.options import options
 from pymgrit_amd.core.hip_lib import MgritHipError, check
-
-
-def _i32(a):
-    return np.ascontiguousarray(np.asarray(a, dtype=np.int32))
 
 
 def _cols(items, k):
@@ -153,16 +148,36 @@ class HipBackend:
                     perm = hip_lib.row_permutation(n)
                 made[key] = torch.from_numpy(np.asarray(perm, dtype=np.int64)).to(self.device)
             self.perm.append(made[key])
-        self._U, self.V, self.G, self.FB = [], [], [], {}
+        self._U, self.V, self.G, self.FB = [], [], [], {}     # the slabs per level; FB: the rows of a general forcing
         self._f_stale = 0         # level-0 F-points: 0 all in place; 1 all but the last of every interval await materialise();
                                   # 2 as 1, and the last one's row holds Phi of it (the next C-relaxation's value, cf_fas pre)
         self._cycle_pre = False   # the state at the start of the running cycle was 2 (begin_cycle)
+        self.f_relax_follows = False   # set by Mgrit.iteration around its own C-relaxations (_before_c_write)
+        self._residual_cache = None    # the level-0 points whose residual sums the engine's pinned buffer holds (residual_ready)
+        self._write_gen = 0            # write_generation()
+        self._res_ring, self._res_next = [], 0      # pinned host buffers the residual kernels write into, handed out in turn
+        self._res_open = None          # (points, n_head, buffer): the slot the way up pre-fills (residual_reserve)
+        # device-side index lists (_list_id), tag -> (export, index columns, the store for lists that cannot carry attributes)
         self._runs, self._pairs = {}, {}
-        self._described = [False] * mg.lvl_max
+        self._lists = {"runs": (self.lib.mgrit_hip_runs_create, 2, self._runs), "pts": (self.lib.mgrit_hip_runs_create, 1, self._runs),
+                       "ecruns": (self.lib.mgrit_hip_ec_runs_create, 3, self._runs),
+                       "ivals": (self.lib.mgrit_hip_intervals_create, 6, self._runs),
+                       "pairs": (self.lib.mgrit_hip_pairs_create, 2, self._pairs),
+                       "triples": (self.lib.mgrit_hip_triples_create, 3, self._pairs)}
+        # per level: the overlapped chain and the time-parallel forward solve (3.8, _config_block_solve)
         self.chain_state, self.chain_handover, self._handover = {}, {}, {}
-        self.prev = None
-        self._sumsq = None
-        self._cur_stream, self._chain_stream = self.stream, None
+        self.block_r, self.block_sharded, self.block_uh = {}, {}, {}
+        self.device_links, self.link_error = False, None     # finalize()
+        self._stage = {}               # level -> the row exchange_staged sends
+        self._at = None                # AT-MGRIT on several ranks: neighbours, halo and the work level's slabs (at_forward_solve)
+        self.prev = None               # level 0 as save_last() / jump_norms() left it
+        # C-point snapshots of level 0 (pipelined solve) and the mirror that fills one of them from the way up
+        self._snap, self._snap_idx = {}, None
+        self._mirror_on, self._mirror_slot, self._mirror_hit, self._mirror_row0 = False, None, False, 0
+        # planned cycle: the stream the engine launches on now, the chain's stream, the pair on CU partitions (() = not asked
+        # yet, None = not available), the event both are forked from, the stream a cycle is captured on
+        self._cur_stream, self._chain_stream, self._masked, self._fork, self._capture_stream = self.stream, None, (), None, None
+        self._timing_on = False        # set_timing(): timed sweeps are not replayed as a graph
 
     def __del__(self):
         try:
@@ -186,14 +201,21 @@ class HipBackend:
             raise MgritHipError("Allen-Cahn (IMEX) levels on the HIP engine: the global convergence criteria only (conv_crit 0 or 1)")
 
     # -- state (mgrit.py:840-858) -------------------------------------------------------------------
+    @staticmethod
+    def _forcing_tables(space, time_fns, width, *grids):
+        """a separable forcing as the library takes it: (K, s[K][width], one tau[K][points] per time grid given), tau[k][i] = the
+        k-th term's time factor at the grid's i-th point"""
+        s = np.ascontiguousarray(np.asarray(space, dtype=np.float64).reshape(-1, width))
+        K = s.shape[0]
+        taus = [np.zeros((K, t.size)) for t in grids]
+        for k in range(K):
+            for tau, t in zip(taus, grids):
+                tau[k] = _time_factor(time_fns[k], t)
+        return (K, s) + tuple(np.ascontiguousarray(tau) for tau in taus)
+
     def _describe_heat1d(self, engine_lvl, d, t_local, n, ld):
         n_pts = t_local.size
-        s = np.ascontiguousarray(np.asarray(d.get("forcing_space", np.zeros((0, n))), dtype=np.float64).reshape(-1, n))
-        K = s.shape[0]
-        tau = np.zeros((K, n_pts))
-        for k in range(K):
-            tau[k] = _time_factor(d["forcing_time"][k], t_local)
-        tau = np.ascontiguousarray(tau)
+        K, s, tau = self._forcing_tables(d.get("forcing_space", np.zeros((0, n))), d.get("forcing_time"), n, t_local)
         check(self.lib.mgrit_hip_level_heat1d(self.h, engine_lvl, n_pts, _ptr(t_local), n, ld, float(d["fac"]), K,
                                               _ptr(s), _ptr(tau)))
         if d.get("forcing_rows") is not None:
@@ -210,61 +232,59 @@ class HipBackend:
             self.FB[engine_lvl] = rows
             check(self.lib.mgrit_hip_level_forcing_rows(self.h, engine_lvl, C.c_void_p(rows.data_ptr())))
 
-    def create_u_v_g(self, lvl):
-        mg = self.mg
-        d, n, ld = self.desc[lvl], self.n[lvl], self.ld[lvl]
-        t_local = np.ascontiguousarray(np.asarray(mg.t[lvl], dtype=np.float64))
-        n_pts = t_local.size
-        if d["kind"] == "heat1d":
-            self._describe_heat1d(lvl, d, t_local, n, ld)
-        elif d["kind"] == "heat1d_2pts":
-            s = np.ascontiguousarray(np.asarray(d.get("forcing_space", np.zeros((0, n))), dtype=np.float64).reshape(-1, n))
-            K = s.shape[0]
-            tau, tau2 = np.zeros((K, n_pts)), np.zeros((K, n_pts))
-            for k in range(K):
-                tau[k] = _time_factor(d["forcing_time"][k], t_local)
-                tau2[k] = _time_factor(d["forcing_time"][k], t_local + d["dtau"])      # (t + dtau elementwise: the same sums)
-            check(self.lib.mgrit_hip_level_heat1d_2pts(self.h, lvl, n_pts, _ptr(t_local), n, ld, float(d["fac"]),
-                                                       float(d["dtau"]), int(d["order"]), K, _ptr(s),
-                                                       _ptr(np.ascontiguousarray(tau)), _ptr(np.ascontiguousarray(tau2))))
-        elif d["kind"] == "advection1d":
-            check(self.lib.mgrit_hip_level_advection1d(self.h, lvl, n_pts, _ptr(t_local), n, ld, float(d["fac"])))
-        elif d["kind"] == "heat2d":
-            nx, ny = int(d["nx"]), int(d["ny"])
-            S = np.ascontiguousarray(np.asarray(d["forcing_space"], dtype=np.float64).reshape(-1, (nx - 2) * (ny - 2)))
-            K = S.shape[0]
-            tau = np.zeros((K, n_pts))
-            for k in range(K):
-                tau[k] = _time_factor(d["forcing_time"][k], t_local)
-            tau = np.ascontiguousarray(tau)
-            bc = np.ascontiguousarray(np.asarray(d["bc"], dtype=np.float64).ravel())
-            check(self.lib.mgrit_hip_level_heat2d(self.h, lvl, n_pts, _ptr(t_local), nx, ny, ld, float(d["fx"]), float(d["fy"]),
-                                                  float(d["theta"]), _ptr(bc), K, _ptr(S), _ptr(tau)))
-            if d.get("forcing_rows") is not None:
-                # general forcing: rhs(x, y, t_i) on the padded interior for every local point (the theta-scheme weighs the two
-                # ends of a step itself), uploaded in blocks
-                Mi, Mj = C.c_int(0), C.c_int(0)
-                check(self.lib.mgrit_hip_heat2d_padded(self.h, lvl, C.byref(Mi), C.byref(Mj)))
-                Mi, Mj = Mi.value, Mj.value
-                rows = torch.zeros((max(n_pts, 1), Mi * Mj), dtype=torch.float64, device=self.device)
-                for a in range(0, n_pts, 256):
-                    z = min(n_pts, a + 256)
-                    host = np.zeros((z - a, Mi, Mj))
-                    for i in range(a, z):
-                        host[i - a, :nx - 2, :ny - 2] = d["forcing_rows"](float(t_local[i]))
-                    rows[a:z].copy_(torch.from_numpy(host.reshape(z - a, Mi * Mj)))
-                self.FB[lvl] = rows
-                check(self.lib.mgrit_hip_level_heat2d_forcing_rows(self.h, lvl, C.c_void_p(rows.data_ptr())))
-        elif d["kind"] == "allencahn2d":
-            check(self.lib.mgrit_hip_level_allencahn2d(self.h, lvl, n_pts, _ptr(t_local), int(d["nx"]), ld, float(d["inv_dx2"]),
-                                                       float(d["inv_eps2"]), int(d["nu"])))
-        else:
+    def _describe_heat1d_2pts(self, engine_lvl, d, t_local, n, ld):
+        K, s, tau, tau2 = self._forcing_tables(d.get("forcing_space", np.zeros((0, n))), d.get("forcing_time"), n,
+                                               t_local, t_local + d["dtau"])      # (t + dtau elementwise: the same sums)
+        check(self.lib.mgrit_hip_level_heat1d_2pts(self.h, engine_lvl, t_local.size, _ptr(t_local), n, ld, float(d["fac"]),
+                                                   float(d["dtau"]), int(d["order"]), K, _ptr(s), _ptr(tau), _ptr(tau2)))
+
+    def _describe_advection1d(self, engine_lvl, d, t_local, n, ld):
+        check(self.lib.mgrit_hip_level_advection1d(self.h, engine_lvl, t_local.size, _ptr(t_local), n, ld, float(d["fac"])))
+
+    def _describe_heat2d(self, engine_lvl, d, t_local, n, ld):
+        n_pts, nx, ny = t_local.size, int(d["nx"]), int(d["ny"])
+        K, S, tau = self._forcing_tables(d["forcing_space"], d.get("forcing_time"), (nx - 2) * (ny - 2), t_local)
+        bc = np.ascontiguousarray(np.asarray(d["bc"], dtype=np.float64).ravel())
+        check(self.lib.mgrit_hip_level_heat2d(self.h, engine_lvl, n_pts, _ptr(t_local), nx, ny, ld, float(d["fx"]), float(d["fy"]),
+                                              float(d["theta"]), _ptr(bc), K, _ptr(S), _ptr(tau)))
+        if d.get("forcing_rows") is not None:
+            # general forcing: rhs(x, y, t_i) on the padded interior for every local point (the theta-scheme weighs the two
+            # ends of a step itself), uploaded in blocks
+            Mi, Mj = C.c_int(0), C.c_int(0)
+            check(self.lib.mgrit_hip_heat2d_padded(self.h, engine_lvl, C.byref(Mi), C.byref(Mj)))
+            Mi, Mj = Mi.value, Mj.value
+            rows = torch.zeros((max(n_pts, 1), Mi * Mj), dtype=torch.float64, device=self.device)
+            for a in range(0, n_pts, 256):
+                z = min(n_pts, a + 256)
+                host = np.zeros((z - a, Mi, Mj))
+                for i in range(a, z):
+                    host[i - a, :nx - 2, :ny - 2] = d["forcing_rows"](float(t_local[i]))
+                rows[a:z].copy_(torch.from_numpy(host.reshape(z - a, Mi * Mj)))
+            self.FB[engine_lvl] = rows
+            check(self.lib.mgrit_hip_level_heat2d_forcing_rows(self.h, engine_lvl, C.c_void_p(rows.data_ptr())))
+
+    def _describe_allencahn2d(self, engine_lvl, d, t_local, n, ld):
+        check(self.lib.mgrit_hip_level_allencahn2d(self.h, engine_lvl, t_local.size, _ptr(t_local), int(d["nx"]), ld,
+                                                   float(d["inv_dx2"]), float(d["inv_eps2"]), int(d["nu"])))
+
+    _DESCRIBE = {"heat1d": _describe_heat1d, "heat1d_2pts": _describe_heat1d_2pts, "advection1d": _describe_advection1d,
+                 "heat2d": _describe_heat2d, "allencahn2d": _describe_allencahn2d}
+
+    def _describe(self, engine_lvl, lvl, t_local):
+        """tell the engine what level engine_lvl is: the stepper of level lvl on the time points t_local"""
+        d = self.desc[lvl]
+        if d["kind"] not in self._DESCRIBE:
             raise MgritHipError(f"unknown device stepper kind {d['kind']!r}")
+        self._DESCRIBE[d["kind"]](self, engine_lvl, d, t_local, self.n[lvl], self.ld[lvl])
+
+    def _allocate(self, lvl, n_pts):
+        """the level's slabs, zero (level 0: the random initial guess where asked for), bound to the engine"""
+        mg, ld = self.mg, self.ld[lvl]
         u = torch.zeros((n_pts, ld), dtype=torch.float64, device=self.device)
-        tmpl = mg.problem[lvl].vector_template
         if lvl == 0 and mg.random_init_guess and n_pts:
             host = np.zeros((n_pts, ld))
             perm = self.perm[lvl].cpu().numpy()
+            tmpl = mg.problem[lvl].vector_template
             for i in range(n_pts):  # clone_rand per time point, in time order (heat_1d.py:88-96)
                 host[i, perm] = np.asarray(tmpl.clone_rand().pack(), dtype=np.float64).ravel()
             u.copy_(torch.from_numpy(host))
@@ -276,10 +296,13 @@ class HipBackend:
         check(self.lib.mgrit_hip_level_bind(self.h, lvl, C.c_void_p(u.data_ptr()),
                                             C.c_void_p(v.data_ptr() if v is not None else 0),
                                             C.c_void_p(g.data_ptr() if g is not None else 0)))
-        # Overlapped chain: every owner of the level must take the same form of the forward solve and exchange
-        # the same hand-over (op 5: the last point + the chain's running state), so the decision comes from the level's GLOBAL
-        # time grid -- the engine only sees this rank's points
-        gt = np.asarray(mg.global_t[lvl], dtype=np.float64)
+        return u, v, g
+
+    def _config_chain(self, lvl, d, n, gt):
+        """Overlapped chain: every owner of the level must take the same form of the forward solve and exchange
+        the same hand-over (op 5: the last point + the chain's running state), so the decision comes from the level's GLOBAL
+        time grid -- the engine only sees this rank's points"""
+        ld = self.ld[lvl]
         dts = np.diff(gt)
         n_terms = np.asarray(d.get("forcing_space", np.zeros((0, n)))).reshape(-1, n).shape[0] if d["kind"] == "heat1d" else 0
         wide = (lvl > 0 and d["kind"] == "heat1d" and 1024 < n <= hip_lib.MAX_N and n_terms <= 1 and d.get("forcing_rows") is None and dts.size > 0
@@ -293,14 +316,23 @@ class HipBackend:
             assert slen.value == self.chain_handover[lvl]
             self.chain_state[lvl] = torch.zeros(slen.value, dtype=torch.float64, device=self.device)
             check(self.lib.mgrit_hip_chain_bind(self.h, lvl, C.c_void_p(self.chain_state[lvl].data_ptr())))
+
+    def create_u_v_g(self, lvl):
+        mg = self.mg
+        d, n = self.desc[lvl], self.n[lvl]
+        t_local = np.ascontiguousarray(np.asarray(mg.t[lvl], dtype=np.float64))
+        self._describe(lvl, lvl, t_local)
+        u, v, g = self._allocate(lvl, t_local.size)
+        gt = np.asarray(mg.global_t[lvl], dtype=np.float64)
+        self._config_chain(lvl, d, n, gt)
         self._config_block_solve(lvl, d, n, gt)
-        mg.u.append(SlabVectorList(u, n, tmpl, self.perm[lvl], on_write=self._before_write if lvl == 0 else self._forget_residual,
+        tmpl = mg.problem[lvl].vector_template
+        mg.u.append(SlabVectorList(u, n, tmpl, self.perm[lvl], on_write=self._before_write if lvl == 0 else self._outside_write,
                                    on_read=self.materialise if lvl == 0 else None))
         mg.v.append(SlabVectorList(v, n, tmpl, self.perm[lvl]) if v is not None else None)
         mg.g.append(SlabVectorList(g, n, tmpl, self.perm[lvl]) if g is not None else None)
-        if mg.comm_time_rank == 0 and n_pts:
+        if mg.comm_time_rank == 0 and t_local.size:
             mg.u[lvl][0] = mg.problem[lvl].vector_t_start
-        self._described[lvl] = True
 
     def _config_block_solve(self, lvl, d, n, gt):
         """Time-parallel forward solve (csrc/mgrit_hip_blk.inc): the rule is applied to the level's GLOBAL time
@@ -310,9 +342,6 @@ class HipBackend:
         then carries the BLOCK_RMAX mode amplitudes behind the point instead of a chain state."""
         from pymgrit_amd.core.layout import compute_layout
         mg = self.mg
-        self.block_r = getattr(self, "block_r", {})
-        self.block_sharded = getattr(self, "block_sharded", {})
-        self.block_uh = getattr(self, "block_uh", {})
         r = C.c_int(0)
         if d["kind"] == "allencahn2d":
             # non-linear Phi: the time-parallel forward solve superposes block defects and holds for linear steppers only -- the
@@ -371,7 +400,7 @@ class HipBackend:
     def block_solve(self, lvl, phases):
         """phases of the time-parallel forward solve on a rank of a sharded level (mgrit_hip_block_solve): 1 = first pass,
         2 = recurrence over the blocks (+ the corrected last point when a successor waits for it), 4 = corrections + second pass"""
-        self._settle(lvl)
+        self._enter(lvl, clear=None)
         check(self.lib.mgrit_hip_block_solve(self.h, lvl, int(phases)))
 
     def block_solve_form(self, lvl):
@@ -393,7 +422,6 @@ class HipBackend:
             check(self.lib.mgrit_hip_level_transfer(self.h, lvl, kind))
         # ghost rows as stream operations of the engine (mgrit_hip_exchange) when the time communicator offers links
         # (RcclTimeComm, LoopbackComm): opening them is collective -- every rank is in its constructor at this point
-        self.device_links = False
         comm = mg.comm_time
         if mg.comm_time_size > 1 and getattr(comm, "device_exchange", False) and \
                 options.exchange != "torch":
@@ -434,7 +462,7 @@ class HipBackend:
         if recv_idx is not None:
             (rl, rs), fin = self._xlink(src, 'recv', ch, ordinals[1])
             done.append(fin)
-            self._residual_cache = None
+            self._invalidate()
         check(self.lib.mgrit_hip_exchange(self.h, lvl, op, sl, -1 if send_idx is None else int(send_idx), ss, rl,
                                           -1 if recv_idx is None else int(recv_idx), rs,
                                           int(self.chain_handover.get(lvl, 0) or 0) if op == 5 else 0))
@@ -448,19 +476,17 @@ class HipBackend:
         that corrects it in place has run (Mgrit._x0)"""
         from pymgrit_amd.core.comm import CH_SWEEP
         ld = self.ld[lvl]
-        if not hasattr(self, "_stage"):
-            self._stage = {}
         if lvl not in self._stage:
             self._stage[lvl] = torch.zeros(ld, dtype=torch.float64, device=self.device)
         stage = self._stage[lvl]
-        check(self.lib.mgrit_hip_error_correction_to(self.h, lvl, self._pair_id(lvl, pair), C.c_void_p(stage.data_ptr()), ld))
+        check(self.lib.mgrit_hip_error_correction_to(self.h, lvl, self._list_id("pairs", lvl, pair), C.c_void_p(stage.data_ptr()), ld))
         (sl, ss), fin = self._xlink(dest, 'send', CH_SWEEP, ordinals[0])
         check(self.lib.mgrit_hip_send(self.h, sl, ss, C.c_void_p(stage.data_ptr()), ld))
         if fin is not None:
             fin()
         if recv_idx is not None:
             (rl, rs), fin = self._xlink(src, 'recv', CH_SWEEP, ordinals[1])
-            self._residual_cache = None
+            self._invalidate()
             check(self.lib.mgrit_hip_recv(self.h, rl, rs, C.c_void_p(self._U[lvl][int(recv_idx)].data_ptr()), ld))
             if fin is not None:
                 fin()
@@ -481,16 +507,28 @@ class HipBackend:
         replaces one row of a complete solution, as it does in the reference; rebuilt afterwards they would overwrite a written
         F-point, or follow a written C-point"""
         self.materialise()
-        self._forget_residual()
+        self._outside_write()
 
-    def _forget_residual(self):
+    def _invalidate(self, outside=False):
+        """the residual sums the engine holds are no longer those of the level-0 state. outside: slab contents have been written
+        from outside the sweeps (mgrit.u[lvl][i] = vec, set_natural), which write_generation() reports"""
         self._residual_cache = None
-        self._write_gen = getattr(self, "_write_gen", 0) + 1      # a Vector has been written into a slab from outside
+        if outside:
+            self._write_gen += 1
+
+    def _outside_write(self):
+        self._invalidate(outside=True)
+
+    def _cached(self, points):
+        """the residual cache holds exactly these points (compared by identity first: Mgrit hands over the same cached list
+        every time)"""
+        cache = self._residual_cache
+        return cache is not None and len(cache) == len(points) and (cache is points or tuple(cache) == tuple(points))
 
     def write_generation(self):
         """changes whenever slab contents have been written from outside the sweeps (mgrit.u[lvl][i] = vec, set_natural):
         Mgrit._head re-injects the first time point then"""
-        return getattr(self, "_write_gen", 0)
+        return self._write_gen
 
     @property
     def U(self):
@@ -531,8 +569,7 @@ class HipBackend:
 
     def set_natural(self, which, lvl, values):
         """upload a [n_local_points][n] host array given in natural x order"""
-        self._residual_cache = None
-        self._write_gen = getattr(self, "_write_gen", 0) + 1
+        self._invalidate(outside=True)
         if which == "u" and lvl == 0:
             self._f_stale = 0      # every row replaced: nothing of the last cycle's C-point storage is left to rebuild
         slab = {"u": self._U, "v": self.V, "g": self.G}[which][lvl]
@@ -561,7 +598,7 @@ class HipBackend:
         return self._U[lvl][idx]
 
     def commit(self, lvl, idx, got, op=None):
-        self._residual_cache = None
+        self._invalidate()
         if op == 5 and self.block_sharded.get(lvl):
             ld = self._U[lvl].shape[1]
             self._U[lvl][idx].copy_(got[:ld])
@@ -592,34 +629,23 @@ class HipBackend:
                     store[key] = hid
         return hid
 
-    def _run_id(self, lvl, runs):
+    def _list_id(self, tag, lvl, items, extra=None):
+        """handle of the device-side copy of an index list, created on first use by the export of self._lists[tag] from the
+        list's index columns; extra(columns) -> the export's arguments between the count and the handle where they are more
+        than the columns"""
+        create_fn, k, store = self._lists[tag]
+
         def create():
-            rid = C.c_int(-1)
-            st, ln = _cols(runs, 2)
-            check(self.lib.mgrit_hip_runs_create(self.h, lvl, len(runs), _ptr(st), _ptr(ln), C.byref(rid)))
-            return rid.value
-        return self._handle(self._runs, lvl, runs, "runs", create)
+            hid = C.c_int(-1)
+            cols = list(_cols(items, k))
+            args = cols if extra is None else extra(cols)
+            check(create_fn(self.h, lvl, len(items), *[_ptr(a) if isinstance(a, np.ndarray) else a for a in args], C.byref(hid)))
+            return hid.value
+        return self._handle(store, lvl, items, tag, create)
 
     def _point_run_id(self, lvl, points):
-        def create():
-            rid = C.c_int(-1)
-            st, ln = _cols(points, 1)[0], np.ones(len(points), dtype=np.int32)
-            check(self.lib.mgrit_hip_runs_create(self.h, lvl, len(points), _ptr(st), _ptr(ln), C.byref(rid)))
-            return rid.value
-        return self._handle(self._runs, lvl, points, "pts", create)
-
-    def _pair_id(self, lvl, pairs):
-        def create():
-            pid = C.c_int(-1)
-            fi, co = _cols(pairs, 2)
-            check(self.lib.mgrit_hip_pairs_create(self.h, lvl, len(pairs), _ptr(fi), _ptr(co), C.byref(pid)))
-            return pid.value
-        return self._handle(self._pairs, lvl, pairs, "pairs", create)
-
-    def _sumsq_buf(self, n):
-        if self._sumsq is None or self._sumsq.numel() < n:
-            self._sumsq = torch.zeros(max(n, 1), dtype=torch.float64, device=self.device)
-        return self._sumsq
+        """single points as runs of length one"""
+        return self._list_id("pts", lvl, points, lambda cols: cols + [np.ones(len(points), dtype=np.int32)])
 
     # -- sweeps ----------------------------------------------------------------------------------------
     def _before_c_write(self, lvl):
@@ -628,19 +654,28 @@ class HipBackend:
         they are put in place first -- rebuilt afterwards they would follow the new C-points, which is not what the reference's
         state holds (found by tests/test_hip_state_fuzz.py). Mgrit.iteration's own C-relaxations are followed by an F-relaxation
         that rewrites every F-point anyway (f_relax_follows)."""
-        if lvl == 0 and self._f_stale and not getattr(self, "f_relax_follows", False):
+        if lvl == 0 and self._f_stale and not self.f_relax_follows:
             self.materialise()
 
-    def relax(self, lvl, runs, mode):
-        self._settle(lvl)
-        if mode == 'C':
+    def _enter(self, lvl, settle=True, c_write=False, clear="level 0"):
+        """what a sweep entry point does before it looks at its list, in this order: settle -- level-0 rows in state 2 are put
+        in place (_settle); c_write -- the sweep writes C-points on its own (_before_c_write); clear -- the residual cache is
+        dropped when the sweep runs on "level 0", on "every" level, or not at all (None). Every sweep states its own
+        steps: the whole-level passes cf_fas and gen_up read or leave the pending rows themselves and do not settle, an error
+        correction or interpolation by hand does not either, and cf_fas alone drops the cache on whatever level it is given"""
+        if settle:
+            self._settle(lvl)
+        if c_write:
             self._before_c_write(lvl)
-        if lvl == 0:
-            self._residual_cache = None
+        if clear == "every" or (clear == "level 0" and lvl == 0):
+            self._invalidate()
+
+    def relax(self, lvl, runs, mode):
+        self._enter(lvl, c_write=mode == 'C')
         if not runs:
             return
         code = {'F': hip_lib.RELAX_F, 'C': hip_lib.RELAX_C, 'CHAIN': hip_lib.RELAX_CHAIN, 'FC': hip_lib.RELAX_FC}[mode]
-        check(self.lib.mgrit_hip_relax(self.h, lvl, self._run_id(lvl, runs), code, float(self.mg.weight_c)))
+        check(self.lib.mgrit_hip_relax(self.h, lvl, self._list_id("runs", lvl, runs), code, float(self.mg.weight_c)))
 
     def relax_chain_part(self, lvl, runs, resume):
         """one block of the coarsest-level solve (cycle_plan.py); resume: it continues the chain of the block before it from
@@ -714,7 +749,7 @@ class HipBackend:
         captured from exactly those launches and replayed with a single call: a cycle of a small hierarchy is a dozen kernels
         of 5-20 us each, and without the graph their launch cost, not their run time, is what a cycle takes.
         PYMGRIT_AMD_PLAN_GRAPH=0 keeps the launch-by-launch form."""
-        graph_ok = options.plan_graph != "0" and not getattr(self, "_timing_on", False)
+        graph_ok = options.plan_graph != "0" and not self._timing_on
         if any(d["kind"] == "heat2d" for d in self.desc):
             graph_ok = False     # (six launches per step of the coarsest-level solve: tens of thousands of nodes per cycle)
         comm = self.mg.comm_time if getattr(plan, "sends", None) or getattr(plan, "recvs", None) else None
@@ -733,11 +768,7 @@ class HipBackend:
     def _plan_run(self, plan, graph_ok):
         state = plan.__dict__.setdefault("_hip", {"runs": 0, "graph": None, "failed": False})
         if state["graph"] is not None and graph_ok:
-            with torch.cuda.stream(self.stream):      # (the engine's stream, whatever the caller has made current since)
-                state["graph"].replay()
-            self._f_stale = max(self._f_stale, state.get("f_stale", 0))   # what the replayed launches did to the F-points
-            if state.get("mirror_hit") and getattr(self, "_mirror_on", False):
-                self._mirror_hit = True
+            self._replay(state)
             return
         if graph_ok and state["runs"] >= 2 and not state["failed"]:
             import gc
@@ -745,7 +776,7 @@ class HipBackend:
             try:
                 self.sync()
                 graph = torch.cuda.CUDAGraph()
-                cap = self._capture_stream = getattr(self, "_capture_stream", None) or torch.cuda.Stream(device=self.device)
+                cap = self._capture_stream = self._capture_stream or torch.cuda.Stream(device=self.device)
                 gc.collect()
                 gc.disable()     # a collection inside the capture could run the destructor of an old engine (hipFree,
                                  # hipStreamSynchronize): calls that invalidate a capture in progress
@@ -758,11 +789,7 @@ class HipBackend:
                     if gc_was_on:
                         gc.enable()
                 state["graph"] = graph
-                with torch.cuda.stream(self.stream):
-                    graph.replay()
-                self._f_stale = max(self._f_stale, state.get("f_stale", 0))
-                if state.get("mirror_hit") and getattr(self, "_mirror_on", False):
-                    self._mirror_hit = True
+                self._replay(state)
                 return
             except Exception as exc:   # noqa: BLE001 - capture is an optimisation: any refusal falls back to plain launches
                 state["failed"] = True
@@ -780,15 +807,22 @@ class HipBackend:
         try:
             self._plan_issue(plan, self.stream)
             state["f_stale"] = self._f_stale          # does this cycle leave level-0 F-points to materialise()?
-            state["mirror_hit"] = bool(getattr(self, "_mirror_hit", False))
+            state["mirror_hit"] = bool(self._mirror_hit)
         finally:
             self._f_stale = max(self._f_stale, was)   # (also when a launch failed: rows that awaited materialise() still do)
+
+    def _replay(self, state):
+        with torch.cuda.stream(self.stream):      # (the engine's stream, whatever the caller has made current since)
+            state["graph"].replay()
+        self._f_stale = max(self._f_stale, state.get("f_stale", 0))   # what the replayed launches did to the F-points
+        if state.get("mirror_hit") and self._mirror_on:
+            self._mirror_hit = True
 
     def _masked_streams(self):
         """Heat2D planned cycle with a step-by-step coarsest-level solve (theta < 1, or fewer than 64 coarsest steps: DESIGN.md 3.8
         covers the rest): (sweep stream, chain stream) on disjoint sets of CUs (mgrit_hip_stream_create_masked), or None. 32 CUs =
         one XCD for the solve (measured in round 3 on config 4: 16 CUs 676-696 ms, 24 620, 32 501, 40 517-539, 64 528-569)."""
-        if not hasattr(self, "_masked"):
+        if self._masked == ():
             self._masked = None
             n_chain = 32
             total = torch.cuda.get_device_properties(self.device).multi_processor_count
@@ -803,53 +837,34 @@ class HipBackend:
         return self._masked
 
     def _plan_issue(self, plan, main):
-        masked = self._masked_streams() if (plan.has_chain and plan.n_blocks > 1) else None
+        two = plan.has_chain and plan.n_blocks > 1
+        masked = self._masked_streams() if two else None
+        reserve = 0
         if masked is not None:
             # sweeps and chain on CU partitions of their own: fork both from the caller's stream, join both at the end
             sweep, side = masked
-            if not hasattr(self, "_fork"):
+            if self._fork is None:
                 self._fork = torch.cuda.Event()
+            forked = (sweep, side)
+        else:
+            if self._chain_stream is None:
+                self._chain_stream = torch.cuda.Stream(device=self.device, priority=-1)
+                self._fork = torch.cuda.Event()
+            sweep, side, forked = main, self._chain_stream, (self._chain_stream,)
+        if two:
             self._fork.record(main)
-            sweep.wait_event(self._fork)
-            side.wait_event(self._fork)
-            last = {}
-            try:
-                for node in plan.order:
-                    st = side if node.stream == "chain" else sweep
-                    for p in node.cross_preds:
-                        st.wait_event(p.event)
-                    self._use_stream(st)
-                    node.fn()
-                    if node.needs_event:
-                        if node.event is None:
-                            node.event = torch.cuda.Event()
-                        node.event.record(st)
-                    last[st] = node
-            finally:
-                self._use_stream(self.stream)
-            for st in (sweep, side):
-                ev = torch.cuda.Event()
-                ev.record(st)
-                main.wait_event(ev)
-            return
-        if self._chain_stream is None:
-            self._chain_stream = torch.cuda.Stream(device=self.device, priority=-1)
-            self._fork = torch.cuda.Event()
-        side = self._chain_stream
-        reserve = 0
-        if plan.has_chain and plan.n_blocks > 1:
-            self._fork.record(main)
-            side.wait_event(self._fork)
-            # the sweeps leave one CU of XCD 0 per chain worker (one worker per group of 1024 values) to the chain
-            groups = max(self.ld[lvl] // 1024 for lvl in {n.lvl for n in plan.order if n.stream == "chain"})
-            reserve = int(min(32, max(1, groups)))
-        two = plan.has_chain and plan.n_blocks > 1
+            for st in forked:
+                st.wait_event(self._fork)
+            if masked is None:
+                # the sweeps leave one CU of XCD 0 per chain worker (one worker per group of 1024 values) to the chain
+                groups = max(self.ld[lvl] // 1024 for lvl in {n.lvl for n in plan.order if n.stream == "chain"})
+                reserve = int(min(32, max(1, groups)))
         last_side = None
         try:
             if reserve:
                 check(self.lib.mgrit_hip_set_reserve(self.h, reserve))
-            for node in plan.order:
-                st = side if (two and node.stream == "chain") else main
+            for node in plan.order:      # (one stream and no events where the plan has nothing to run beside the sweeps)
+                st = side if (two and node.stream == "chain") else sweep
                 if two:
                     for p in node.cross_preds:
                         st.wait_event(p.event)
@@ -865,7 +880,12 @@ class HipBackend:
             self._use_stream(self.stream)
             if reserve:
                 check(self.lib.mgrit_hip_set_reserve(self.h, 0))
-        if last_side is not None:      # whatever follows on the engine's stream sees the whole cycle
+        if masked is not None:
+            for st in forked:
+                ev = torch.cuda.Event()
+                ev.record(st)
+                main.wait_event(ev)
+        elif last_side is not None:      # whatever follows on the engine's stream sees the whole cycle
             if last_side.event is None:
                 last_side.event = torch.cuda.Event()
             if not last_side.needs_event:
@@ -873,25 +893,22 @@ class HipBackend:
             main.wait_event(last_side.event)
 
     def residual_norms(self, points):
-        if getattr(self, "_res_open", None) is not None:      # several ranks: the way up has pre-filled most of the values
+        if self._res_open is not None:      # several ranks: the way up has pre-filled most of the values
             handle = self.residual_begin(points)
             return self.residual_end(handle)
-        cache = getattr(self, "_residual_cache", None)
-        if not (cache is not None and len(cache) == len(points) and (cache is points or tuple(cache) == tuple(points))):
+        hit = self._cached(points)      # (settling rewrites identical values: materialise() keeps the cache)
+        if not hit:
             self._settle(0)     # the residual kernel reads the last F-points
         if not len(points):
             return []
         host = np.empty(len(points), dtype=np.float64)
-        cache = getattr(self, "_residual_cache", None)
-        if cache is not None and len(cache) == len(points) and (cache is points or tuple(cache) == tuple(points)):
+        if hit:
             check(self.lib.mgrit_hip_residual_fetch(self.h, len(points), _ptr(host)))
-            return np.sqrt(host)
-        check(self.lib.mgrit_hip_residual_host(self.h, 0, self._point_run_id(0, points), _ptr(host)))
+        else:
+            check(self.lib.mgrit_hip_residual_host(self.h, 0, self._point_run_id(0, points), _ptr(host)))
         return np.sqrt(host)
 
     def _ring_slot(self, n):
-        if not hasattr(self, "_res_ring"):
-            self._res_ring, self._res_next = [], 0
         if len(self._res_ring) < 8:
             self._res_ring.append(torch.empty(n, dtype=torch.float64, pin_memory=True))
         buf = self._res_ring[self._res_next % len(self._res_ring)]
@@ -908,7 +925,7 @@ class HipBackend:
 
     def _open_slot(self, points):
         """(buffer, head points still to compute) when the way up has pre-filled a slot for exactly these points"""
-        op, self._res_open = getattr(self, "_res_open", None), None
+        op, self._res_open = self._res_open, None
         if op is not None and op[0] == tuple(points):
             return op[2], list(points[:op[1]])
         return None, None
@@ -916,8 +933,7 @@ class HipBackend:
     def residual_begin(self, points):
         """launch the residual kernel and return at once; the per-point sums of squares land in pinned host memory that the
         kernel writes directly (no copy command), residual_end() waits for the event recorded behind the kernel"""
-        cache = getattr(self, "_residual_cache", None)
-        if len(points) and cache is not None and len(cache) == len(points) and (cache is points or tuple(cache) == tuple(points)):
+        if len(points) and self._cached(points):
             # the way up (ec_relax_res) has left exactly these values in the engine's pinned buffer: a copy of their own for a
             # solver that looks at them some cycles late -- the next cycle overwrites the engine's buffer
             buf = self._ring_slot(len(points))
@@ -940,7 +956,7 @@ class HipBackend:
     def _wait_event(self, ev):
         """several ranks on RCCL links: a neighbour that never sends or never receives must end in an ERROR of this rank (and with
         it of the job), not in a silent stall -- bounded wait, then the links are aborted (ncclCommAbort)"""
-        if not getattr(self, "device_links", False):
+        if not self.device_links:
             ev.synchronize()
             return
         import time
@@ -948,13 +964,20 @@ class HipBackend:
         t0 = time.perf_counter()
         while not ev.query():
             if time.perf_counter() - t0 > limit:
-                self.lib.mgrit_hip_links_close(self.h, 1)      # ncclCommAbort: the waiting kernels end, the stream drains
-                abort_all = getattr(self.mg.comm_time, "abort_all", None)
-                if abort_all is not None:
-                    abort_all()                                 # ... and the communicator object holds none of them any longer
+                self._abort_links()
                 raise MgritHipError(f"rank {self.mg.comm_time_rank}: the cycle did not finish within {limit} s (a neighbouring rank "
                                     f"never sent or never received): exchange links aborted")
             time.sleep(2e-5)
+
+    def _abort_links(self, closed=False):
+        """give up on the neighbours: the links are closed with abort (ncclCommAbort: the waiting kernels end, the stream drains)
+        unless the library has done that itself (closed: a failed mgrit_hip_sync_bounded), and the communicator object is told,
+        which must not keep their handles"""
+        if not closed:
+            self.lib.mgrit_hip_links_close(self.h, 1)
+        abort_all = getattr(self.mg.comm_time, "abort_all", None)
+        if abort_all is not None:
+            abort_all()
 
     def residual_end(self, handle):
         if handle is None:
@@ -971,8 +994,8 @@ class HipBackend:
 
     # -- C-point snapshots of level 0 (pipelined solve, Mgrit._solve_pipelined): rows copied inside HBM ------------
     def _snap_slot(self, slot, points):
-        if not hasattr(self, "_snap"):
-            self._snap, self._snap_idx = {}, torch.as_tensor(np.asarray(points, dtype=np.int64), device=self.device)
+        if self._snap_idx is None:
+            self._snap_idx = torch.as_tensor(np.asarray(points, dtype=np.int64), device=self.device)
         if slot not in self._snap:
             self._snap[slot] = torch.empty((len(points), self.ld[0]), dtype=torch.float64, device=self.device)
             if len(points):   # every row valid from the start: the mirror never writes a point nobody corrects (the first time point)
@@ -984,7 +1007,7 @@ class HipBackend:
         slot `slot` as well (mgrit_hip_cpoint_mirror): snapshot_cpoints(slot) after that cycle then has nothing left to copy.
         slot None: off."""
         if slot is None:
-            if getattr(self, "_mirror_on", False):
+            if self._mirror_on:
                 check(self.lib.mgrit_hip_cpoint_mirror(self.h, None, self._mirror_row0))
             self._mirror_on, self._mirror_slot, self._mirror_hit = False, None, False
             return
@@ -998,14 +1021,14 @@ class HipBackend:
         self._mirror_on, self._mirror_slot, self._mirror_hit = True, slot, False
 
     def snapshot_cpoints(self, slot, points):
-        if getattr(self, "_mirror_slot", None) == slot and getattr(self, "_mirror_hit", False) and slot in getattr(self, "_snap", {}):
+        if self._mirror_slot == slot and self._mirror_hit and slot in self._snap:
             return     # the cycle's own pass has written them there
         self._snap_slot(slot, points)
         if len(points):
             torch.index_select(self._U[0], 0, self._snap_idx, out=self._snap[slot])
 
     def restore_cpoints(self, slot, points):
-        self._residual_cache = None
+        self._invalidate()
         if len(points):
             self._U[0].index_copy_(0, self._snap_idx, self._snap[slot])
 
@@ -1028,19 +1051,19 @@ class HipBackend:
             for i, j in pairs:
                 mg.u[lvl + 1][j] = mg.restriction[lvl](mg.u[lvl][i])
             return
-        check(self.lib.mgrit_hip_restrict_u(self.h, lvl, self._pair_id(lvl, pairs)))
+        check(self.lib.mgrit_hip_restrict_u(self.h, lvl, self._list_id("pairs", lvl, pairs)))
 
     def copy_u_to_v(self, lvl):
         check(self.lib.mgrit_hip_copy_u_to_v(self.h, lvl))
 
     def fas_rhs(self, lvl, pairs):
-        self._settle(lvl)
+        self._enter(lvl, clear=None)
         if not pairs:
             return
         if not self._device_transfer(lvl):
             # mgrit.py:524-547 around the user's restriction: fine half on the device (one row per pair), the rows through
             # restriction() into g of the coarse level, coarse half on the device
-            mg, pid = self.mg, self._pair_id(lvl, pairs)
+            mg, pid = self.mg, self._list_id("pairs", lvl, pairs)
             rows = torch.zeros(len(pairs), self.ld[lvl], dtype=torch.float64, device=self.device)
             check(self.lib.mgrit_hip_fas_fine_rows(self.h, lvl, pid, C.c_void_p(rows.data_ptr()), self.ld[lvl]))
             self.sync()
@@ -1049,7 +1072,7 @@ class HipBackend:
                 mg.g[lvl + 1][j] = mg.restriction[lvl](defects[p])
             check(self.lib.mgrit_hip_fas_coarse(self.h, lvl, pid))
             return
-        check(self.lib.mgrit_hip_fas_rhs(self.h, lvl, self._pair_id(lvl, pairs)))
+        check(self.lib.mgrit_hip_fas_rhs(self.h, lvl, self._list_id("pairs", lvl, pairs)))
 
     # fused FAS residual (identity transfer, like steppers on both levels): see include/mgrit_hip.h
     def _resident(self, lvl):
@@ -1057,37 +1080,31 @@ class HipBackend:
         Heat1D states run sweep by sweep through the three-launch Phi (csrc/mgrit_hip_wide.inc)"""
         return max(self.n[lvl], self.n[min(lvl + 1, len(self.n) - 1)]) <= hip_lib.MAX_N or self.desc[lvl]["kind"] in GRID_2D
 
-    def can_fuse_fas(self, lvl):
-        tr = self.mg.transfer_objects[lvl]
-        da, db = self.desc[lvl], self.desc[lvl + 1]
-        if not self._resident(lvl):
-            return False
-        same_forcing = len(da.get("forcing_time", [])) == len(db.get("forcing_time", []))
+    def _like_pair(self, lvl, kinds=("heat1d", "advection1d"), forcing_terms=True, no_rows=False):
+        """lvl and lvl+1 are joined by the library's copy transfer and hold the same stepper kind (one of kinds) on the same n;
+        forcing_terms: with the same number of separable forcing terms; no_rows: and neither with a general forcing"""
+        tr, da, db = self.mg.transfer_objects[lvl], self.desc[lvl], self.desc[lvl + 1]
         return (self._device_transfer(lvl) and int(tr.device_transfer()) == hip_lib.TRANSFER_COPY and
-                da["kind"] == db["kind"] and da["kind"] in ("heat1d", "advection1d") and
-                self.n[lvl] == self.n[lvl + 1] and same_forcing)
+                da["kind"] == db["kind"] and da["kind"] in kinds and self.n[lvl] == self.n[lvl + 1] and
+                (not forcing_terms or len(da.get("forcing_time", [])) == len(db.get("forcing_time", []))) and
+                (not no_rows or (da.get("forcing_rows") is None and db.get("forcing_rows") is None)))
+
+    def can_fuse_fas(self, lvl):
+        return self._resident(lvl) and self._like_pair(lvl)
 
     def fas_fused(self, lvl, triples, with_f_relax=False, skip_coarse_u=False):
         """fused FAS sweep (mgrit_hip_fas_fused_opts): with_f_relax folds the F-relaxation in front of it into the pass (F-points
         not stored), skip_coarse_u leaves u of a coarsest level that forward_solve overwrites unwritten"""
-        self._settle(lvl)
+        self._enter(lvl, clear=None)
         if not triples:
             return
         opts = (hip_lib.FAS_WITH_F_RELAX if with_f_relax else 0) | (hip_lib.FAS_SKIP_COARSE_U if skip_coarse_u else 0)
-        check(self.lib.mgrit_hip_fas_fused_opts(self.h, lvl, self._triples_id(lvl, triples), opts))
-
-    def _triples_id(self, lvl, triples):
-        def create():
-            tid = C.c_int(-1)
-            fi, pr, co = _cols(triples, 3)
-            check(self.lib.mgrit_hip_triples_create(self.h, lvl, len(triples), _ptr(fi), _ptr(pr), _ptr(co), C.byref(tid)))
-            return tid.value
-        return self._handle(self._pairs, lvl, triples, "triples", create)
+        check(self.lib.mgrit_hip_fas_fused_opts(self.h, lvl, self._list_id("triples", lvl, triples), opts))
 
     def fas_chunks(self, lvl, triples):
         """mgrit_hip_fas_chunks: the chunks fas_fused(with_f_relax=True) launches over for this list, 0 = item by item"""
         n = C.c_int(-1)
-        check(self.lib.mgrit_hip_fas_chunks(self.h, lvl, self._triples_id(lvl, triples), C.byref(n)))
+        check(self.lib.mgrit_hip_fas_chunks(self.h, lvl, self._list_id("triples", lvl, triples), C.byref(n)))
         return n.value
 
     def set_fas_chunk(self, chunk):
@@ -1097,7 +1114,7 @@ class HipBackend:
 
     def copy_pairs_u_to_v(self, lvl, pairs):
         if pairs:
-            check(self.lib.mgrit_hip_copy_pairs_u_to_v(self.h, lvl, self._pair_id(lvl, pairs)))
+            check(self.lib.mgrit_hip_copy_pairs_u_to_v(self.h, lvl, self._list_id("pairs", lvl, pairs)))
 
     def at_forward_solve(self, lvl, k):
         """AtMgrit.forward_solve (at_mgrit.py:37-87): truncated, mutually independent coarsest-level solves. One rank: one
@@ -1114,8 +1131,8 @@ class HipBackend:
         if self.desc[lvl]["kind"] not in ("heat1d", "advection1d"):
             raise MgritHipError("AT-MGRIT on several ranks of the HIP engine: 1-D single-point steppers only")
         own_g = [int(i) for i in mg.cpts[lvl]]                 # global indices of the owned points
-        counts = mg.comm_time.allgather_object(len(own_g)) if not hasattr(self, "_at") else None
-        if not hasattr(self, "_at"):
+        if self._at is None:
+            counts = mg.comm_time.allgather_object(len(own_g))
             rank, size = mg.comm_time_rank, mg.comm_time_size
             holders = [r for r in range(size) if counts[r] > 0]
             prev = max([r for r in holders if r < rank], default=None) if own_g else None
@@ -1130,14 +1147,10 @@ class HipBackend:
             at = {"prev": prev, "next": nxt, "halo": halo, "give": give, "n_own": len(own_g)}
             if own_g:
                 t_at = np.ascontiguousarray(mg.global_t[lvl][own_g[0] - halo:own_g[-1] + 1])
-                n, ld = self.n[lvl], self.ld[lvl]
-                at["u"] = torch.zeros((t_at.size, ld), dtype=torch.float64, device=self.device)
+                at["u"] = torch.zeros((t_at.size, self.ld[lvl]), dtype=torch.float64, device=self.device)
                 at["g"] = torch.zeros_like(at["u"])
                 work = mg.lvl_max
-                if self.desc[lvl]["kind"] == "heat1d":
-                    self._describe_heat1d(work, self.desc[lvl], t_at, n, ld)
-                else:
-                    check(self.lib.mgrit_hip_level_advection1d(self.h, work, t_at.size, _ptr(t_at), n, ld, float(self.desc[lvl]["fac"])))
+                self._describe(work, lvl, t_at)
                 check(self.lib.mgrit_hip_level_bind(self.h, work, C.c_void_p(at["u"].data_ptr()), C.c_void_p(at["u"].data_ptr()),
                                                     C.c_void_p(at["g"].data_ptr())))
             self._at = at
@@ -1156,51 +1169,30 @@ class HipBackend:
         U[own].copy_(at["u"][at["halo"]:])
 
     def can_fuse_ec(self, lvl):
-        tr = self.mg.transfer_objects[lvl]
-        da, db = self.desc[lvl], self.desc[lvl + 1]
-        if not self._resident(lvl):
-            return False
-        return (self._device_transfer(lvl) and int(tr.device_transfer()) == hip_lib.TRANSFER_COPY and
-                da["kind"] == db["kind"] and da["kind"] in ("heat1d", "advection1d") and self.n[lvl] == self.n[lvl + 1])
+        return self._resident(lvl) and self._like_pair(lvl, forcing_terms=False)     # (the correction reads no forcing)
 
     def ec_relax(self, lvl, triples):
         """error correction of the C-point in front of each run + the run's F-relaxation in one launch"""
-        self._settle(lvl)
-        self._before_c_write(lvl)
-        if lvl == 0:
-            self._residual_cache = None
+        self._enter(lvl, c_write=True)
         if not triples:
             return
-
-        def create():
-            rid = C.c_int(-1)
-            st, ln, co = _cols(triples, 3)
-            check(self.lib.mgrit_hip_ec_runs_create(self.h, lvl, len(triples), _ptr(st), _ptr(ln), _ptr(co), C.byref(rid)))
-            return rid.value
-        check(self.lib.mgrit_hip_ec_relax(self.h, lvl, self._handle(self._runs, lvl, triples, "ecruns", create)))
+        check(self.lib.mgrit_hip_ec_relax(self.h, lvl, self._list_id("ecruns", lvl, triples)))
 
     # -- whole-level sweeps in one pass (include/mgrit_hip.h: mgrit_hip_cf_fas / mgrit_hip_ec_relax_res) -------------------
     def can_fuse_level(self, lvl):
         """level 0, Heat1D with a separable forcing on both levels, identity transfer (weight and layout: the caller)"""
-        tr = self.mg.transfer_objects[lvl]
-        da, db = self.desc[lvl], self.desc[lvl + 1]
-        return (lvl == 0 and self._resident(lvl) and not options.no_level_fusion and self._device_transfer(lvl) and
-                int(tr.device_transfer()) == hip_lib.TRANSFER_COPY and da["kind"] == db["kind"] == "heat1d" and
-                self.n[lvl] == self.n[lvl + 1] and da.get("forcing_rows") is None and db.get("forcing_rows") is None and
-                len(da.get("forcing_time", [])) == len(db.get("forcing_time", [])))
+        return (lvl == 0 and self._resident(lvl) and not options.no_level_fusion and
+                self._like_pair(lvl, kinds=("heat1d",), no_rows=True))
 
     def can_fuse_coarse_down(self, lvl):
         """lvl > 0, Heat1D with a separable forcing on lvl and lvl+1, identity transfer: the way down of the level as two
         passes -- F-relaxation + C-relaxation (relax mode FC), F-relaxation + FAS residual (fas_fused with_f_relax)"""
-        da = self.desc[lvl]
-        return (lvl > 0 and not options.no_level_fusion and self.can_fuse_fas(lvl) and
-                da["kind"] == "heat1d" and da.get("forcing_rows") is None and self.desc[lvl + 1].get("forcing_rows") is None)
+        return (lvl > 0 and not options.no_level_fusion and self._resident(lvl) and
+                self._like_pair(lvl, kinds=("heat1d",), no_rows=True))
 
     def can_fuse_level_up(self, lvl):
         """any level pair of Heat1D with a separable forcing and the identity transfer: error correction + F-relaxation in one
         pass (mgrit_hip_ec_relax_res; with the rows of g and without the residual on lvl > 0)"""
-        tr = self.mg.transfer_objects[lvl]
-        da, db = self.desc[lvl], self.desc[lvl + 1]
         # Its intervals correct the C-point they END on, so in a planned cycle a block waits for the chain part of its own block
         # only (ecf_kernel: of the next block too). The launch itself is slower than ecf_kernel (every interval reads its two
         # boundary corrections), so it pays only together with the merged launch of the first blocks' way up (cycle_plan.py,
@@ -1212,34 +1204,24 @@ class HipBackend:
             # the next block, and the rank has few blocks to hide that behind)
             blocks = self.mg.plan_blocks()
             want = "1" if (blocks >= 5 or (blocks >= 2 and self.mg.comm_time_size > 1)) else "0"
-        return (want == "1" and self._resident(lvl) and
-                not options.no_level_fusion and self._device_transfer(lvl) and
-                int(tr.device_transfer()) == hip_lib.TRANSFER_COPY and da["kind"] == db["kind"] == "heat1d" and
-                self.n[lvl] == self.n[lvl + 1] and da.get("forcing_rows") is None and db.get("forcing_rows") is None and
-                len(da.get("forcing_time", [])) == len(db.get("forcing_time", [])))
+        return (want == "1" and self._resident(lvl) and not options.no_level_fusion and
+                self._like_pair(lvl, kinds=("heat1d",), no_rows=True))
 
     def _intervals_id(self, lvl, intervals, chunk=None):
-        def create():
-            iid = C.c_int(-1)
-            cols = _cols(intervals, 6)
-            # level 0: chunks of 4 intervals (one extra row + Phi per chunk start); coarser levels: one interval per item --
-            # a block of a planned cycle holds only a few hundred of their intervals, and 4 in a row would leave CUs idle
-            # (0 = chosen by the library from the level's size: 4 on config 3, 1 where the level has fewer intervals than the chip
-            # holds workgroups)
-            ch = chunk
-            if ch is None:      # the Heat1D whole-level passes: level 0 by the library's rule for them (up to 16 intervals in a row)
-                ch = hip_lib.CHUNK_LONG if lvl == 0 else 1
-            res_len = len(self.mg._c_points(lvl))
-            check(self.lib.mgrit_hip_intervals_create(self.h, lvl, len(intervals), _ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]),
-                                                      _ptr(cols[3]), _ptr(cols[4]), res_len, ch, _ptr(cols[5]), C.byref(iid)))
-            return iid.value
-        return self._handle(self._runs, lvl, intervals, "ivals", create)
+        # level 0: chunks of 4 intervals (one extra row + Phi per chunk start); coarser levels: one interval per item --
+        # a block of a planned cycle holds only a few hundred of their intervals, and 4 in a row would leave CUs idle
+        # (0 = chosen by the library from the level's size: 4 on config 3, 1 where the level has fewer intervals than the chip
+        # holds workgroups)
+        if chunk is None:      # the Heat1D whole-level passes: level 0 by the library's rule for them (up to 16 intervals in a row)
+            chunk = hip_lib.CHUNK_LONG if lvl == 0 else 1
+        # (the length of the residual buffer and the chunk stand in front of the last column, keep)
+        return self._list_id("ivals", lvl, intervals, lambda cols: cols[:5] + [len(self.mg._c_points(lvl)), chunk, cols[5]])
 
     def cf_fas(self, lvl, intervals):
         """c_relax + f_relax + fas_residual of level lvl for the intervals (cstart, cend, cstart_coarse, cend_coarse, res_pos,
         keep): keep = which rows of lvl+1 the closing C-point needs (bit 0: u, bit 1: v; include/mgrit_hip.h)"""
         if intervals:
-            self._residual_cache = None
+            self._enter(lvl, settle=False, clear="every")
             check(self.lib.mgrit_hip_cf_fas(self.h, lvl, self._intervals_id(lvl, intervals), 1 if (lvl == 0 and self._cycle_pre) else 0))
 
     def ec_relax_res_to(self, lvl, intervals, buf):
@@ -1258,7 +1240,7 @@ class HipBackend:
             # IS the next reader of the level (cf_iter = 1: no plain C-relaxation in front of it)
             mode = 1 if not lazy else (2 if (self.mg.cf_iter[0] == 1 and not options.no_pre_relax) else 0)
             check(self.lib.mgrit_hip_ec_relax_res(self.h, lvl, self._intervals_id(lvl, intervals), mode))
-            if lvl == 0 and getattr(self, "_mirror_on", False):
+            if lvl == 0 and self._mirror_on:
                 self._mirror_hit = True
             if lazy:
                 self._f_stale = max(self._f_stale, 2 if mode == 2 else 1)
@@ -1282,53 +1264,44 @@ class HipBackend:
     def gen_down(self, lvl, intervals, parts=3):
         """c_relax + f_relax + fas_residual of level lvl for the intervals (cstart, cend, cstart_coarse, cend_coarse, res_pos, keep);
         parts: 1 = the fine level's pass with the restriction, 2 = the coarse half (a rank's op 4 sits between them), 3 = both"""
-        self._settle(lvl)
+        self._enter(lvl, clear="level 0" if intervals else None)
         if intervals:
-            if lvl == 0:
-                self._residual_cache = None
             check(self.lib.mgrit_hip_gen_down_part(self.h, lvl, self._intervals_id(lvl, intervals, chunk=self._gen_chunk()), int(parts)))
 
     def gen_up(self, lvl, intervals, residual=False):
         """error_correction + f_relax (+ compute_residual on level 0, values kept for residual_norms) of level lvl"""
         if intervals:
-            if lvl == 0:
-                self._residual_cache = None
+            self._enter(lvl, settle=False)
             check(self.lib.mgrit_hip_gen_up(self.h, lvl, self._intervals_id(lvl, intervals, chunk=self._gen_chunk()), 1 if residual else 0, None))
 
     def residual_ready(self, points):
         """the residual of exactly these level-0 points has been produced by the last ec_relax_res sweep(s) and level 0 has not
         been touched since (Mgrit._ec_f_relax sets it, every other sweep on level 0 clears it)"""
-        self._residual_cache = points      # (compared by identity first: Mgrit hands over the same cached list every time)
+        self._residual_cache = points
 
     def error_correction(self, lvl, pairs):
-        self._before_c_write(lvl)
-        if lvl == 0:
-            self._residual_cache = None
+        self._enter(lvl, settle=False, c_write=True)
         if pairs and not self._device_transfer(lvl):     # mgrit.py:724-726 through the user's interpolation
             mg = self.mg
             for i, j in pairs:
                 mg.u[lvl][i] = mg.u[lvl][i] + mg.interpolation[lvl](mg.u[lvl + 1][j] - mg.v[lvl + 1][j])
         elif pairs:
-            check(self.lib.mgrit_hip_error_correction(self.h, lvl, self._pair_id(lvl, pairs)))
+            check(self.lib.mgrit_hip_error_correction(self.h, lvl, self._list_id("pairs", lvl, pairs)))
 
     def interpolate(self, lvl, pairs):
-        self._before_c_write(lvl)
-        if lvl == 0:
-            self._residual_cache = None
+        self._enter(lvl, settle=False, c_write=True)
         if pairs and not self._device_transfer(lvl):     # mgrit.py:559-563
             mg = self.mg
             for i, j in pairs:
                 mg.u[lvl][i] = mg.interpolation[lvl](u=mg.u[lvl + 1][j])
         elif pairs:
-            check(self.lib.mgrit_hip_interpolate(self.h, lvl, self._pair_id(lvl, pairs)))
+            check(self.lib.mgrit_hip_interpolate(self.h, lvl, self._list_id("pairs", lvl, pairs)))
 
     def sync(self):
-        if getattr(self, "device_links", False):   # a neighbour that never sends or never receives must end in an error here
+        if self.device_links:   # a neighbour that never sends or never receives must end in an error here
             rc = self.lib.mgrit_hip_sync_bounded(self.h, float(getattr(self.mg.comm_time, "timeout_s", 120.0)))
             if rc != 0:     # the library has aborted this engine's links: the communicator object must not keep their handles
-                abort_all = getattr(self.mg.comm_time, "abort_all", None)
-                if abort_all is not None:
-                    abort_all()
+                self._abort_links(closed=True)
             check(rc)
         else:
             check(self.lib.mgrit_hip_sync(self.h))
