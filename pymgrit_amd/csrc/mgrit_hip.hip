@@ -1624,6 +1624,17 @@ struct H2DHost {
                                              // cycle steps on a second stream BESIDE sweeps that apply this level's Phi too (the
                                              // coarse half of the FAS right-hand side of another block of time points)
 };
+// What the two structs own outside the level's allocs and the upload arena (the engine's streams are idle)
+void h2d_blk_release(H2DHost::Blk &k) {
+    if (k.rim_flag) (void)hipHostFree(k.rim_flag);
+    if (k.rim_ev) (void)hipEventDestroy(k.rim_ev);
+}
+void h2d_release(H2DHost *h) {
+    for (double *p : {h->W0, h->W1, h->rowsq, h->Wc0, h->Wc1})
+        if (p) (void)hipFree(p);
+    h2d_blk_release(h->blk);
+    delete h;
+}
 
 // Heat1D states of more than MGRIT_HIP_MAX_N values (mgrit_hip_wide.inc): work slabs of the three-launch Phi
 struct WideHost {
@@ -1631,6 +1642,11 @@ struct WideHost {
     double *T0 = nullptr;   // two-point levels: the new first values of a batch (half rows)
     size_t cap = 0;
 };
+void wide_release(WideHost *w) {
+    for (double *p : {w->W, w->tot, w->car, w->z0, w->red, w->T0})
+        if (p) (void)hipFree(p);
+    delete w;
+}
 
 // Small uploads (index lists, coefficient sets, time factors) without a stream synchronisation: device memory carved from 8 MB
 // chunks, the source copied into a pinned mirror of the chunk that lives as long as the engine, the copy enqueued on the engine's
@@ -1933,27 +1949,49 @@ void build_cset_advection1d(CSet &c, std::vector<double> &tab, int n, double fac
     c.pi_last = c.pw[(n - 1) % E + 1];   // the power at the last unknown's position inside its lane (the periodic closure reads it)
 }
 
+// n values of h (borrowed for the call only) as device memory of the level: small ones through the arena, the rest as an allocation of
+// the level's, copied before the call returns
 template <typename T>
-int dev_upload(Level &lv, hipStream_t st, const std::vector<T> &h, T **out) {
+int dev_upload(Level &lv, hipStream_t st, const T *h, size_t n, T **out) {
     void *d = nullptr;
-    const size_t bytes = sizeof(T) * (h.empty() ? 1 : h.size());
+    const size_t bytes = sizeof(T) * (n == 0 ? 1 : n);
     if (lv.arena && bytes <= UploadArena::SMALL) {
         char *dv = nullptr, *hs = nullptr;
         if (lv.arena->take(bytes, &dv, &hs)) return fail(MGRIT_HIP_EHIP, "no memory for an upload of %zu bytes", bytes);
-        if (!h.empty()) {
-            std::memcpy(hs, h.data(), sizeof(T) * h.size());
-            HIP_TRY(hipMemcpyAsync(dv, hs, sizeof(T) * h.size(), hipMemcpyHostToDevice, st));
+        if (n != 0) {
+            std::memcpy(hs, h, sizeof(T) * n);
+            HIP_TRY(hipMemcpyAsync(dv, hs, sizeof(T) * n, hipMemcpyHostToDevice, st));
         }
         *out = reinterpret_cast<T *>(dv);
         return 0;
     }
     HIP_TRY(hipMalloc(&d, bytes));
     lv.allocs.push_back(d);
-    if (!h.empty()) {
-        HIP_TRY(hipMemcpyAsync(d, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice, st));
+    if (n != 0) {
+        HIP_TRY(hipMemcpyAsync(d, h, sizeof(T) * n, hipMemcpyHostToDevice, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
     *out = static_cast<T *>(d);
+    return 0;
+}
+template <typename T>
+int dev_upload(Level &lv, hipStream_t st, const std::vector<T> &h, T **out) { return dev_upload(lv, st, h.data(), h.size(), out); }
+
+// Device memory owned by the level (freed with the engine), zero-filled on the engine's stream
+template <typename T>
+int level_zeros(mgrit_hip_engine *e, Level &lv, size_t count, T **out) {
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(out), sizeof(T) * count));
+    lv.allocs.push_back(*out);
+    HIP_TRY(hipMemsetAsync(*out, 0, sizeof(T) * count, e->stream));
+    return 0;
+}
+
+// A slab that has to grow while a captured cycle may still launch with its old address (the state fuzz found it: a whole-level
+// fas_residual by hand between two replays of a two-block plan): the old slab is retired to the level's allocs, the owner frees the last
+int slab_regrow(Level &lv, double **slab, size_t count) {
+    if (*slab) lv.allocs.push_back(*slab);
+    *slab = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(slab), sizeof(double) * count));
     return 0;
 }
 
@@ -2243,6 +2281,48 @@ int check_level(mgrit_hip_engine *e, int lvl, bool need_set = true) {
     return 0;
 }
 
+// What the four level descriptors share. Each runs check_level first and level_fresh last, and its own argument checks between the
+// two in its own order (a call with several bad arguments reports the first of them): the 1-D descriptors test ld and the forcing
+// description and register the LDS limits in front of level_fresh, the 2-D ones never register any.
+bool no_time_grid(int n_pts, const double *t_local) { return n_pts < 0 || (n_pts > 0 && !t_local); }
+// separable forcing: K space factors s and, per factor, the time factors on the local grid (have_tau: every array of them is there)
+int check_forcing(int K, int n_pts, const double *s, bool have_tau) {
+    const bool bad = K < 0 || K > 8 || (K > 0 && (!s || (n_pts > 0 && !have_tau)));
+    return bad ? fail(MGRIT_HIP_EINVAL, "bad forcing description (K=%d)", K) : 0;
+}
+int level_fresh(const mgrit_hip_engine *e, int lvl) { return e->L[lvl].set ? fail(MGRIT_HIP_EINVAL, "level %d already described", lvl) : 0; }
+
+// step sizes of a local time grid: dts[i] = t[i] - t[i-1], dts[0] = 0
+std::vector<double> step_sizes(int n_pts, const double *t_local) {
+    std::vector<double> dts(n_pts > 0 ? n_pts : 0, 0.0);
+    for (int i = 1; i < n_pts; ++i) dts[i] = t_local[i] - t_local[i - 1];
+    return dts;
+}
+
+// One Heat1D coefficient set for the step size dt: c, its rank-one table in row storage order (tabT, E * T doubles) and the power
+// scans of a full group and of the last one (ptT, 2 * GROUP doubles, row storage order). tab, pt, pt_last: the same three in
+// natural order (pt, pt_last: GROUP doubles), which build_chain_tables goes on from.
+void heat1d_cset_tables(CSet &c, double *tabT, double *ptT, int n, double fac, double dt, std::vector<double> &tab, double *pt,
+                        double *pt_last) {
+    std::memset(&c, 0, sizeof(CSet));
+    build_cset_heat1d(c, tab, n, fac, dt);
+    build_pt(c, GROUP, pt);
+    c.pi_full = pt[0];
+    for (int j = 0; j < GROUP; ++j) ptT[row_pos(j)] = pt[j];
+    build_pt(c, n - ((n - 1) / GROUP) * GROUP, pt_last);
+    c.pi_last = pt_last[0];
+    for (int j = 0; j < GROUP; ++j) ptT[GROUP + row_pos(j)] = pt_last[j];
+    for (int j = 0; j < n; ++j) tabT[row_pos(j)] = tab[j];
+}
+
+// the K forcing space factors s[k][n] in row storage order, E * T doubles each
+std::vector<double> space_factors(int K, int n, int T, const double *s) {
+    std::vector<double> sT((size_t)(K > 0 ? K : 0) * E * T, 0.0);
+    for (int kk = 0; kk < K; ++kk)
+        for (int j = 0; j < n; ++j) sT[(size_t)kk * E * T + row_pos(j)] = s[(size_t)kk * n + j];
+    return sT;
+}
+
 int level_common(mgrit_hip_engine *e, int lvl, int kind, int n_pts, const double *t_local, int n, int ld, double fac,
                  int K, const double *s, const double *tau) {
     int rc = check_level(e, lvl, false);
@@ -2251,11 +2331,11 @@ int level_common(mgrit_hip_engine *e, int lvl, int kind, int n_pts, const double
     if (n < 1 || n > n_max)
         return fail(MGRIT_HIP_EUNSUPPORTED, "n=%d DOFs per time point outside [1,%d] (register-resident up to 16384, three-launch Phi above)", n, n_max);
     if (ld != mgrit_hip_row_stride(n)) return fail(MGRIT_HIP_EINVAL, "ld=%d must equal mgrit_hip_row_stride(n=%d)=%d", ld, n, mgrit_hip_row_stride(n));
-    if (n_pts < 0 || (n_pts > 0 && !t_local)) return fail(MGRIT_HIP_EINVAL, "bad local time grid");
-    if (K < 0 || K > 8 || (K > 0 && (!s || (n_pts > 0 && !tau)))) return fail(MGRIT_HIP_EINVAL, "bad forcing description (K=%d)", K);
+    if (no_time_grid(n_pts, t_local)) return fail(MGRIT_HIP_EINVAL, "bad local time grid");
+    if ((rc = check_forcing(K, n_pts, s, tau != nullptr))) return rc;
     if ((rc = register_lds_limits())) return rc;
+    if ((rc = level_fresh(e, lvl))) return rc;
     Level &lv = e->L[lvl];
-    if (lv.set) return fail(MGRIT_HIP_EINVAL, "level %d already described", lvl);
     const int G = (n + GROUP - 1) / GROUP, T = G * LANES;
     lv.G = G;
     lv.fac = fac;
@@ -2264,12 +2344,12 @@ int level_common(mgrit_hip_engine *e, int lvl, int kind, int n_pts, const double
     d.n = n; d.ld = ld; d.T = T; d.n_pts = n_pts; d.K = K; d.kind = kind;
     d.stream_rows = (size_t)n_pts * (size_t)ld * sizeof(double) > ((size_t)256 << 20) ? 1 : 0;
     // coefficient sets keyed by the bit pattern of dt = t[i] - t[i-1] (the reference uses each step's own dt)
-    std::vector<double> dts(n_pts > 0 ? n_pts : 0, 0.0), uniq;
+    const std::vector<double> dts = step_sizes(n_pts, t_local);
+    std::vector<double> uniq;
     std::vector<int32_t> cidx(n_pts > 0 ? n_pts : 0, 0);
     std::map<uint64_t, int> seen;   // bit pattern of dt -> coefficient set
     for (int i = 1; i < n_pts; ++i) {
-        const double dt = t_local[i] - t_local[i - 1];
-        dts[i] = dt;
+        const double dt = dts[i];
         uint64_t bits;
         std::memcpy(&bits, &dt, sizeof(double));
         auto it = seen.find(bits);
@@ -2293,22 +2373,17 @@ int level_common(mgrit_hip_engine *e, int lvl, int kind, int n_pts, const double
     const bool overlapped = kind == MGRIT_HIP_STEPPER_HEAT1D && G >= 2 && G <= MAX_G && uniq.size() == 1 && K <= 1;
     if (n > MGRIT_HIP_MAX_N) lv.wide = new WideHost();
     for (size_t q = 0; q < uniq.size(); ++q) {
-        std::memset(&cs[q], 0, sizeof(CSet));
+        double *const tabq = tabT.data() + q * (size_t)E * T;
         if (kind == MGRIT_HIP_STEPPER_HEAT1D) {
-            build_cset_heat1d(cs[q], tab, n, fac, uniq[q]);
-            build_pt(cs[q], GROUP, pt.data());
-            cs[q].pi_full = pt[0];
-            for (int j = 0; j < GROUP; ++j) ptT[q * (size_t)2 * GROUP + row_pos(j)] = pt[j];
-            build_pt(cs[q], n - ((n - 1) / GROUP) * GROUP, pt_last.data());
-            cs[q].pi_last = pt_last[0];
-            for (int j = 0; j < GROUP; ++j) ptT[q * (size_t)2 * GROUP + GROUP + row_pos(j)] = pt_last[j];
+            heat1d_cset_tables(cs[q], tabq, ptT.data() + q * (size_t)2 * GROUP, n, fac, uniq[q], tab, pt.data(), pt_last.data());
             if (overlapped) build_chain_tables(cs[q], tab, pt.data(), pt_last.data(), n, ld, chT);
-        } else build_cset_advection1d(cs[q], tab, n, fac, uniq[q]);
-        for (int j = 0; j < n; ++j) tabT[q * (size_t)E * T + row_pos(j)] = tab[j];
+        } else {
+            std::memset(&cs[q], 0, sizeof(CSet));
+            build_cset_advection1d(cs[q], tab, n, fac, uniq[q]);
+            for (int j = 0; j < n; ++j) tabq[row_pos(j)] = tab[j];
+        }
     }
-    std::vector<double> sT((size_t)(K > 0 ? K : 0) * E * T, 0.0), tauv;
-    for (int kk = 0; kk < K; ++kk)
-        for (int j = 0; j < n; ++j) sT[(size_t)kk * E * T + row_pos(j)] = s[(size_t)kk * n + j];
+    std::vector<double> sT = space_factors(K, n, T, s), tauv;
     if (K > 0) {  // tc[k][i] = tau_k(t_i) * dt_i
         tauv.assign(tau, tau + (size_t)K * n_pts);
         for (int kk = 0; kk < K; ++kk)
@@ -2351,95 +2426,6 @@ HalfCoef bdf2_half(double tau_i, double tau_im1) {
     return h;
 }
 
-int level_heat1d_2pts(mgrit_hip_engine *e, int lvl, int n_pts, const double *t_local, int n, int ld, double fac, double dtau,
-                      int order, int K, const double *s, const double *tau, const double *tau2) {
-    int rc = check_level(e, lvl, false);
-    if (rc) return rc;
-    if (n < 1 || n > MGRIT_HIP_MAX_N_WIDE)
-        return fail(MGRIT_HIP_EUNSUPPORTED, "n=%d DOFs per time point outside [1,%d] (two-point stepper)", n, MGRIT_HIP_MAX_N_WIDE);
-    if (ld != 2 * mgrit_hip_row_stride(n)) return fail(MGRIT_HIP_EINVAL, "ld=%d must equal 2*mgrit_hip_row_stride(n=%d)=%d", ld, n, 2 * mgrit_hip_row_stride(n));
-    if (order != 1 && order != 2) return fail(MGRIT_HIP_EINVAL, "BDF order must be 1 or 2");
-    if (n_pts < 0 || (n_pts > 0 && !t_local)) return fail(MGRIT_HIP_EINVAL, "bad local time grid");
-    if (K < 0 || K > 8 || (K > 0 && (!s || (n_pts > 0 && (!tau || !tau2))))) return fail(MGRIT_HIP_EINVAL, "bad forcing description (K=%d)", K);
-    if ((rc = register_lds_limits())) return rc;
-    Level &lv = e->L[lvl];
-    if (lv.set) return fail(MGRIT_HIP_EINVAL, "level %d already described", lvl);
-    const int G = (n + GROUP - 1) / GROUP, T = G * LANES;
-    lv.G = G;
-    lv.order = order;
-    if (n > MGRIT_HIP_MAX_N_2PTS) lv.wide = new WideHost();   // wider than a workgroup holds: every half-solve as three launches (mgrit_hip_wide.inc)
-    LevelDev &d = lv.dev;
-    d.n = n; d.ld = ld; d.T = T; d.n_pts = n_pts; d.K = K; d.kind = MGRIT_HIP_STEPPER_HEAT1D_2PTS;
-    d.stream_rows = 0;
-    const size_t np = n_pts > 0 ? n_pts : 0;
-    std::vector<double> uniq, hc(np * 4, 0.0), fs(np * 2, 0.0), dts(np, 0.0);
-    std::vector<int32_t> cidx2(np * 2, 0);
-    auto set_of = [&](double dt_eff) -> int {
-        for (size_t q = 0; q < uniq.size(); ++q)
-            if (std::memcmp(&uniq[q], &dt_eff, sizeof(double)) == 0) return (int)q;
-        uniq.push_back(dt_eff);
-        return (int)uniq.size() - 1;
-    };
-    for (int i = 1; i < n_pts; ++i) {
-        const double t_start = t_local[i - 1], t_stop = t_local[i];
-        dts[i] = t_stop - t_start;
-        const double tl0 = t_stop - t_start - dtau;
-        HalfCoef h[2];
-        if (order == 1) {
-            h[0].dt_eff = tl0; h[1].dt_eff = dtau;
-            for (int q = 0; q < 2; ++q) { h[q].a = 1.0; h[q].nb = 0.0; h[q].fs = h[q].dt_eff; }
-        } else {
-            h[0] = bdf2_half(tl0, dtau);
-            h[1] = bdf2_half(dtau, tl0);
-        }
-        for (int q = 0; q < 2; ++q) {
-            cidx2[2 * (size_t)i + q] = set_of(h[q].dt_eff);
-            hc[4 * (size_t)i + 2 * q] = h[q].a;
-            hc[4 * (size_t)i + 2 * q + 1] = h[q].nb;
-            fs[2 * (size_t)i + q] = h[q].fs;
-        }
-        if (uniq.size() > 4096) return fail(MGRIT_HIP_EUNSUPPORTED, "more than 4096 distinct time-step sizes on level %d", lvl);
-    }
-    lv.n_csets = (int)uniq.size();
-    std::vector<CSet> cs(uniq.size());
-    std::vector<double> tabT(uniq.size() * (size_t)E * T, 0.0), tab;
-    std::vector<double> ptT(uniq.size() * (size_t)2 * GROUP, 0.0), pt(GROUP);
-    for (size_t q = 0; q < uniq.size(); ++q) {
-        std::memset(&cs[q], 0, sizeof(CSet));
-        build_cset_heat1d(cs[q], tab, n, fac, uniq[q]);
-        build_pt(cs[q], GROUP, pt.data());
-        cs[q].pi_full = pt[0];
-        for (int j = 0; j < GROUP; ++j) ptT[q * (size_t)2 * GROUP + row_pos(j)] = pt[j];
-        build_pt(cs[q], n - ((n - 1) / GROUP) * GROUP, pt.data());
-        cs[q].pi_last = pt[0];
-        for (int j = 0; j < GROUP; ++j) ptT[q * (size_t)2 * GROUP + GROUP + row_pos(j)] = pt[j];
-        for (int j = 0; j < n; ++j) tabT[q * (size_t)E * T + row_pos(j)] = tab[j];
-    }
-    std::vector<double> sT((size_t)(K > 0 ? K : 0) * E * T, 0.0), tc((size_t)(K > 0 ? K : 0) * np * 2, 0.0);
-    for (int kk = 0; kk < K; ++kk) {
-        for (int j = 0; j < n; ++j) sT[(size_t)kk * E * T + row_pos(j)] = s[(size_t)kk * n + j];
-        for (int i = 1; i < n_pts; ++i) {   // tc[k][i][half] = tau_k(t_i [+ dtau]) * forcing scale of the half
-            tc[((size_t)kk * np + i) * 2] = tau[(size_t)kk * n_pts + i] * fs[2 * (size_t)i];
-            tc[((size_t)kk * np + i) * 2 + 1] = tau2[(size_t)kk * n_pts + i] * fs[2 * (size_t)i + 1];
-        }
-    }
-    int32_t *d_cidx2; double *d_dt, *d_tc, *d_sT, *d_tabT, *d_ptT, *d_hc; CSet *d_cs;
-    if ((rc = dev_upload(lv, e->stream, cidx2, &d_cidx2))) return rc;
-    if ((rc = dev_upload(lv, e->stream, dts, &d_dt))) return rc;
-    if ((rc = dev_upload(lv, e->stream, tc, &d_tc))) return rc;
-    if ((rc = dev_upload(lv, e->stream, sT, &d_sT))) return rc;
-    if ((rc = dev_upload(lv, e->stream, cs, &d_cs))) return rc;
-    if ((rc = dev_upload(lv, e->stream, tabT, &d_tabT))) return rc;
-    if ((rc = dev_upload(lv, e->stream, ptT, &d_ptT))) return rc;
-    if ((rc = dev_upload(lv, e->stream, hc, &d_hc))) return rc;
-    d.cidx = nullptr; d.cidx2 = d_cidx2; d.hc = d_hc; d.dt = d_dt; d.tc = d_tc; d.cs = d_cs;
-    d.ptP = reinterpret_cast<const double2 *>(d_ptT);
-    d.sP = reinterpret_cast<const double2 *>(d_sT);
-    d.tabP = reinterpret_cast<const double2 *>(d_tabT);
-    lv.set = true;
-    return 0;
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // Batch plans of the batched route (Heat2D, Allen-Cahn, wide 1-D); Heat2D host side: tables, the batched Phi pipeline
 // ---------------------------------------------------------------------------------------------------------------
@@ -2447,12 +2433,6 @@ constexpr int H2D_MAX_BATCH = 1024;  // items per GEMM batch (work buffers: 2 x 
 constexpr int WIDE_MAX_BATCH = 2048;   // wide 1-D levels: items per batch (work slab: 2048 rows of up to 512 KB)
 
 uint64_t dbl_bits(double v) { uint64_t b; std::memcpy(&b, &v, 8); return b; }
-
-template <typename T>
-int dev_upload_raw(Level &lv, hipStream_t st, const T *h, size_t n, T **out) {
-    std::vector<T> tmp(h, h + n);
-    return dev_upload(lv, st, tmp, out);
-}
 
 // One item of a batch: row `in` of the input slab takes step `step`; the sweep's arithmetic writes row `dst` from rows `a`, `b`.
 struct BatchItem { int32_t in, step, dst, a, b; };
@@ -2480,11 +2460,11 @@ int batch_make_plans(mgrit_hip_engine *e, Level &lv, const std::vector<BatchItem
             pl.count = (int)cnt;
             pl.dtbits = k;
             int rc;
-            if ((rc = dev_upload_raw(lv, e->stream, vin.data() + off, cnt, &pl.d_in))) return rc;
-            if ((rc = dev_upload_raw(lv, e->stream, vst.data() + off, cnt, &pl.d_step))) return rc;
-            if ((rc = dev_upload_raw(lv, e->stream, vds.data() + off, cnt, &pl.d_dst))) return rc;
-            if ((rc = dev_upload_raw(lv, e->stream, va.data() + off, cnt, &pl.d_a))) return rc;
-            if ((rc = dev_upload_raw(lv, e->stream, vb.data() + off, cnt, &pl.d_b))) return rc;
+            if ((rc = dev_upload(lv, e->stream, vin.data() + off, cnt, &pl.d_in))) return rc;
+            if ((rc = dev_upload(lv, e->stream, vst.data() + off, cnt, &pl.d_step))) return rc;
+            if ((rc = dev_upload(lv, e->stream, vds.data() + off, cnt, &pl.d_dst))) return rc;
+            if ((rc = dev_upload(lv, e->stream, va.data() + off, cnt, &pl.d_a))) return rc;
+            if ((rc = dev_upload(lv, e->stream, vb.data() + off, cnt, &pl.d_b))) return rc;
             out.push_back(pl);
         }
     }
@@ -2552,6 +2532,9 @@ BatchItems fas_coarse_items(const PairList &pl) {
     return {items};
 }
 
+// The work slabs of the batched Phi grow by free-and-allocate, unlike the slabs of slab_regrow: retired slabs would hold gigabytes at
+// the sizes of BASELINE config 4 (2 x 1024 items of Mi x Mj doubles each). They reach their full size (H2D_MAX_BATCH, or the largest
+// batch of the level) with the first sweeps of a solve, before a cycle is captured.
 int h2d_reserve(Level &lv, int count) {
     H2DHost &h = *lv.h2d;
     if ((size_t)count <= h.cap_items) return 0;
@@ -2567,6 +2550,19 @@ int h2d_reserve(Level &lv, int count) {
     return 0;
 }
 
+// The live modes of a Heat2D level in spectral slot order -- per axis the even modes in slots [0, ceil(m/2)), the odd ones in
+// [HP, HP + floor(m/2)) --: f(position of the mode in an [Mi][Mj] table, its eigenvalue lx + ly)
+template <typename Fn>
+void h2d_each_mode(const H2DHost &h, Fn f) {
+    const H2DDev &H = h.dev;
+    const int hxe = (H.mi + 1) / 2, hxo = H.mi / 2, hye = (H.mj + 1) / 2, hyo = H.mj / 2;
+    for (int a = 0; a < H.Mi; ++a) {
+        if (!((a < hxe) || (a >= h.HPx && a < h.HPx + hxo))) continue;
+        for (int b = 0; b < H.Mj; ++b)
+            if ((b < hye) || (b >= h.HPy && b < h.HPy + hyo)) f((size_t)a * H.Mj + b, h.lx[a] + h.ly[b]);
+    }
+}
+
 int h2d_dinv(mgrit_hip_engine *e, Level &lv, uint64_t dtbits, double **out) {
     H2DHost &h = *lv.h2d;
     auto it = h.dinv.find(dtbits);
@@ -2578,20 +2574,7 @@ int h2d_dinv(mgrit_hip_engine *e, Level &lv, uint64_t dtbits, double **out) {
     if (h.ac) {   // natural mode order, modes 0 .. nx - 1 on both axes
         for (int a = 0; a < h.dev.nx; ++a)
             for (int b = 0; b < h.dev.nx; ++b) tab[(size_t)a * h.dev.Mj + b] = 1.0 / (1.0 + dt * (h.lx[a] + h.ly[b]));
-        double *d = nullptr;
-        int rc = dev_upload(lv, e->stream, tab, &d);
-        if (rc) return rc;
-        h.dinv[dtbits] = d;
-        *out = d;
-        return 0;
-    }
-    const int hxe = (h.dev.mi + 1) / 2, hxo = h.dev.mi / 2, hye = (h.dev.mj + 1) / 2, hyo = h.dev.mj / 2;
-    for (int a = 0; a < h.dev.Mi; ++a) {
-        if (!((a < hxe) || (a >= h.HPx && a < h.HPx + hxo))) continue;
-        for (int b = 0; b < h.dev.Mj; ++b)
-            if ((b < hye) || (b >= h.HPy && b < h.HPy + hyo))
-                tab[(size_t)a * h.dev.Mj + b] = 1.0 / (1.0 + thdt * (h.lx[a] + h.ly[b]));
-    }
+    } else h2d_each_mode(h, [&](size_t q, double lam) { tab[q] = 1.0 / (1.0 + thdt * lam); });
     double *d = nullptr;
     int rc = dev_upload(lv, e->stream, tab, &d);
     if (rc) return rc;
@@ -2696,6 +2679,11 @@ int h2d_finish(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const double
     return 0;
 }
 
+// The carve-up of every time-parallel solve (Heat2D here, the 1-D forms below): block b of B over N steps = steps first .. last,
+// BLK_K each, the last block with the remainder
+struct BlkSteps { int first, last; };
+BlkSteps blk_steps(int b, int B, int N) { return {BLK_K * b + 1, b == B - 1 ? N : BLK_K * (b + 1)}; }
+
 // Time-parallel forward solve of a Heat2D level with backward Euler (the oracle's heat2d_block_solve_spec): the level's
 // steps in blocks of BLK_K. First pass: step s of EVERY block as one batch -- the error x_b a block has accumulated,
 // x_b = (g_i + Phi(u_{i-1} + x_b)) - u_i from x_b = 0; the errors at the block ends through the forward transforms, the recurrence
@@ -2718,50 +2706,47 @@ int h2d_block_build(mgrit_hip_engine *e, Level &lv) {
     const int K = MGRIT_HIP_BLOCK_K, N = lv.dev.n_pts - 1, B = N / K;
     const size_t per = (size_t)H.Mi * H.Mj;
     int rc;
-    auto first = [&](int b) { return K * b + 1; };
-    auto last = [&](int b) { return b == B - 1 ? N : K * (b + 1); };
+    std::vector<BlkSteps> blk;
     int maxlen = 0;
-    for (int b = 0; b < B; ++b) maxlen = std::max(maxlen, last(b) - first(b) + 1);
+    for (int b = 0; b < B; ++b) {
+        blk.push_back(blk_steps(b, B, N));
+        maxlen = std::max(maxlen, blk[b].last - blk[b].first + 1);
+    }
     k.p1.resize(maxlen); k.p3.resize(maxlen);
     for (int s = 0; s < maxlen; ++s) {
         std::vector<BatchItem> it1, it3;
         for (int b = 0; b < B; ++b) {
-            const int i = first(b) + s;
-            if (i > last(b)) continue;
+            const int i = blk[b].first + s;
+            if (i > blk[b].last) continue;
             // first pass: input row = u_{i-1} (s = 0) or Y[b] = u_{i-1} + x_b; output x_b = (g_i + Phi) - u_i into X[b]
             it1.push_back({s == 0 ? i - 1 : b, i, b, i, i});
-            if (i < last(b)) it3.push_back({i - 1, i, i, i, i});
+            if (i < blk[b].last) it3.push_back({i - 1, i, i, i, i});
         }
         if (!it1.empty() && (rc = batch_make_plans(e, lv, it1, k.p1[s]))) return rc;
         if (!it3.empty() && (rc = batch_make_plans(e, lv, it3, k.p3[s]))) return rc;
     }
     std::vector<int32_t> iota(B), end_all, end_tail, dsel(B, 0);
-    for (int b = 0; b < B; ++b) { iota[b] = b; end_all.push_back(last(b)); }
-    for (int b = 1; b < B; ++b) end_tail.push_back(last(b));
+    for (int b = 0; b < B; ++b) { iota[b] = b; end_all.push_back(blk[b].last); }
+    for (int b = 1; b < B; ++b) end_tail.push_back(blk[b].last);
     // propagator tables: the elementwise product of the steps' D tables in step order; one table per distinct sequence of step sizes
     std::map<std::vector<uint64_t>, int> seen;
     std::vector<double> tabs, dv(per);
-    const int hxe = (H.mi + 1) / 2, hxo = H.mi / 2, hye = (H.mj + 1) / 2, hyo = H.mj / 2;
     for (int b = 1; b < B; ++b) {
         std::vector<uint64_t> key;
-        for (int i = first(b); i <= last(b); ++i) key.push_back(dbl_bits(h.dts[i]));
+        for (int i = blk[b].first; i <= blk[b].last; ++i) key.push_back(dbl_bits(h.dts[i]));
         auto it = seen.find(key);
         if (it == seen.end()) {
             const size_t off = tabs.size();
             tabs.resize(off + per, 0.0);
-            for (int i = first(b); i <= last(b); ++i) {
+            for (int i = blk[b].first; i <= blk[b].last; ++i) {
                 const double thdt = H.theta * h.dts[i];
                 std::fill(dv.begin(), dv.end(), 0.0);
-                for (int a = 0; a < H.Mi; ++a) {
-                    if (!((a < hxe) || (a >= h.HPx && a < h.HPx + hxo))) continue;
-                    for (int c = 0; c < H.Mj; ++c)
-                        if ((c < hye) || (c >= h.HPy && c < h.HPy + hyo)) {
-                            const double lam = h.lx[a] + h.ly[c], inv = 1.0 / (1.0 + thdt * lam);
-                            // (theta < 1: the step's explicit half carries theta as well, heat_2d.py:309; oracle h2d_prop_table)
-                            dv[(size_t)a * H.Mj + c] = H.theta == 1.0 ? inv : (1.0 - thdt * lam) * inv;
-                        }
-                }
-                if (i == first(b)) std::copy(dv.begin(), dv.end(), tabs.begin() + (long)off);
+                h2d_each_mode(h, [&](size_t q, double lam) {
+                    const double inv = 1.0 / (1.0 + thdt * lam);
+                    // (theta < 1: the step's explicit half carries theta as well, heat_2d.py:309; oracle h2d_prop_table)
+                    dv[q] = H.theta == 1.0 ? inv : (1.0 - thdt * lam) * inv;
+                });
+                if (i == blk[b].first) std::copy(dv.begin(), dv.end(), tabs.begin() + (long)off);
                 else for (size_t q = 0; q < per; ++q) tabs[off + q] = tabs[off + q] * dv[q];
             }
             it = seen.emplace(key, (int)seen.size()).first;
@@ -2773,12 +2758,8 @@ int h2d_block_build(mgrit_hip_engine *e, Level &lv) {
     if ((rc = dev_upload(lv, e->stream, end_tail, &k.d_end_tail))) return rc;
     if ((rc = dev_upload(lv, e->stream, dsel, &k.d_dsel))) return rc;
     if ((rc = dev_upload(lv, e->stream, tabs, &k.Dtab))) return rc;
-    for (double **buf : {&k.spec, &k.X, &k.Y}) {
-        const size_t doubles = (buf == &k.spec ? per : (size_t)lv.dev.ld) * (size_t)B;
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(buf), sizeof(double) * doubles));
-        lv.allocs.push_back(*buf);
-        HIP_TRY(hipMemsetAsync(*buf, 0, sizeof(double) * doubles, e->stream));
-    }
+    for (double **buf : {&k.spec, &k.X, &k.Y})
+        if ((rc = level_zeros(e, lv, (buf == &k.spec ? per : (size_t)lv.dev.ld) * (size_t)B, buf))) return rc;
     if ((rc = h2d_reserve(lv, std::min(H2D_MAX_BATCH, B)))) return rc;
     if (H.theta != 1.0) {
         HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&k.rim_flag), 256, hipHostMallocMapped));
@@ -2855,18 +2836,12 @@ int h2d_points_sumsq(mgrit_hip_engine *e, int lvl, RunList *rl, const double *pr
     if ((rc = batch_plans_once(e, lv, rl->points, [&] { return point_items(lv, *rl); }))) return rc;
     for (const BatchPlan &pl : rl->points.plans) {
         if ((rc = h2d_reserve(lv, std::min(H2D_MAX_BATCH, pl.count)))) return rc;
-        if (!prev) {
-            if ((rc = h2d_phi_batch(e, lv, pl, lv.dev.u))) return rc;
-            if (lv.h2d->ac)
-                hipLaunchKernelGGL((h2d_rowsq_kernel<true>), dim3((H.nx + 63) / 64, pl.count), dim3(64), 0, e->stream, H, lv.h2d->W0, lv.dev.u,
-                                   pl.d_in, pl.d_step, lv.dev.u, pl.d_dst, H2D_OP_RESIDUAL, lv.h2d->rowsq);
-            else
-                hipLaunchKernelGGL((h2d_rowsq_kernel<false>), dim3((H.nx + 63) / 64, pl.count), dim3(64), 0, e->stream, H, lv.h2d->W0, lv.dev.u,
-                                   pl.d_in, pl.d_step, lv.dev.u, pl.d_dst, H2D_OP_RESIDUAL, lv.h2d->rowsq);
-        } else {
-            hipLaunchKernelGGL((h2d_rowsq_kernel<false>), dim3((H.nx + 63) / 64, pl.count), dim3(64), 0, e->stream, H, lv.h2d->W0, lv.dev.u,
-                               pl.d_dst, pl.d_step, prev, pl.d_dst, H2D_OP_JUMP, lv.h2d->rowsq);
-        }
+        if (!prev && (rc = h2d_phi_batch(e, lv, pl, lv.dev.u))) return rc;
+        // residual: Phi (in W0) of the row in front against the point's row, the Allen-Cahn instance where the level is one; jump: the
+        // point's row against prev's
+        const auto rowsq = !prev && lv.h2d->ac ? &h2d_rowsq_kernel<true> : &h2d_rowsq_kernel<false>;
+        hipLaunchKernelGGL(rowsq, dim3((H.nx + 63) / 64, pl.count), dim3(64), 0, e->stream, H, lv.h2d->W0, lv.dev.u, prev ? pl.d_dst : pl.d_in,
+                           pl.d_step, prev ? prev : lv.dev.u, pl.d_dst, prev ? H2D_OP_JUMP : H2D_OP_RESIDUAL, lv.h2d->rowsq);
         hipLaunchKernelGGL(h2d_rowsum_kernel, dim3((pl.count + 63) / 64), dim3(64), 0, e->stream, lv.h2d->rowsq, H.nx, pl.count,
                            out, pl.d_b);
         HIP_TRY(hipGetLastError());
@@ -2946,17 +2921,14 @@ int force_mode(const Level &lv) {
 int wide_reserve(Level &lv, int count) {
     WideHost &h = *lv.wide;
     if ((size_t)count <= h.cap) return 0;
-    for (double **p : {&h.W, &h.tot, &h.car, &h.z0, &h.red, &h.T0}) {
-        if (*p) lv.allocs.push_back(*p);   // kept until the engine goes: a captured cycle may still launch with the old addresses
-        *p = nullptr;
-    }
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.W), sizeof(double) * (size_t)count * lv.dev.ld));
-    if (lv.dev.kind == MGRIT_HIP_STEPPER_HEAT1D_2PTS)
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.T0), sizeof(double) * (size_t)count * (lv.dev.ld / 2)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.tot), sizeof(double) * (size_t)count * 2 * WIDE_MAX_G));
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.car), sizeof(double) * (size_t)count * 2 * WIDE_MAX_G));
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.z0), sizeof(double) * (size_t)count));
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.red), sizeof(double) * (size_t)count * 2 * WIDE_MAX_G));   // (two-point: both halves)
+    const size_t c = (size_t)count, per_group = c * 2 * WIDE_MAX_G;   // (red of a two-point level: both halves)
+    int rc;
+    h.cap = 0;   // (a growth that fails half way is tried again by the next call)
+    if ((rc = slab_regrow(lv, &h.W, c * lv.dev.ld))) return rc;
+    if (lv.dev.kind == MGRIT_HIP_STEPPER_HEAT1D_2PTS && (rc = slab_regrow(lv, &h.T0, c * (lv.dev.ld / 2)))) return rc;
+    if ((rc = slab_regrow(lv, &h.tot, per_group)) || (rc = slab_regrow(lv, &h.car, per_group)) || (rc = slab_regrow(lv, &h.z0, c)) ||
+        (rc = slab_regrow(lv, &h.red, per_group)))
+        return rc;
     h.cap = count;
     return 0;
 }
@@ -3096,23 +3068,25 @@ double blk_lam4(int n, int k) {
 }
 int blk_count(int nt) { const int N = nt - 1; return N >= 4 * BLK_K ? N / BLK_K : 0; }
 
-// D[b][k], k <= BLK_RMAX (row stride BLK_RMAX + 1), and the rank; 0: not eligible
-int blk_rank(int n, double fac, int nt, const double *t, std::vector<double> *D) {
+// Heat1D: what the steps of a block leave of sine mode k, D_b(k) = prod over the block's steps of 1 / (1 + dt_i fac 4 sin^2(theta_k / 2)),
+// the product in step order
+double blk_decay(int n, int k, double fac, const double *t, BlkSteps s) {
+    const double lam = blk_lam4(n, k);
+    double d = 1.0;
+    for (int i = s.first; i <= s.last; ++i) d = d * (1.0 / (1.0 + ((t[i] - t[i - 1]) * fac) * lam));
+    return d;
+}
+
+// the rank: the first mode every block but the first damps below BLK_THR; 0: not eligible
+int blk_rank(int n, double fac, int nt, const double *t) {
     const int B = blk_count(nt);
     int r = 0;
     if (B == 0 || n < 2) return 0;
     const int KM = BLK_RMAX + 1 < n ? BLK_RMAX + 1 : n;
-    if (D) D->assign((size_t)B * (BLK_RMAX + 1), 0.0);
     for (int b = 0; b < B; ++b) {
-        const int first = BLK_K * b + 1, last = b == B - 1 ? nt - 1 : BLK_K * (b + 1);
         int rb = -1;
-        for (int k = 0; k < KM; ++k) {
-            const double lam = blk_lam4(n, k);
-            double d = 1.0;
-            for (int i = first; i <= last; ++i) d = d * (1.0 / (1.0 + ((t[i] - t[i - 1]) * fac) * lam));
-            if (D) (*D)[(size_t)b * (BLK_RMAX + 1) + k] = d;
-            if (rb < 0 && d < BLK_THR) rb = k;
-        }
+        for (int k = 0; k < KM && rb < 0; ++k)
+            if (blk_decay(n, k, fac, t, blk_steps(b, B, nt - 1)) < BLK_THR) rb = k;
         if (b >= 1) {
             if (rb < 0 || rb > BLK_RMAX) return 0;
             if (rb > r) r = rb;
@@ -3231,9 +3205,8 @@ int blk_config(mgrit_hip_engine *e, int lvl, int r, int first_real, int has_succ
     if (r < 0 && !can) return 0;
     if (!can) return fail(MGRIT_HIP_EUNSUPPORTED, "time-parallel forward solve: a register-resident Heat1D / Advection1D level > 0");
     const int n = lv.dev.n, ld = lv.dev.ld, nt = lv.dev.n_pts;
-    std::vector<double> D;
     if (r < 0) {   // one rank: the rule on the local (= global) grid
-        r = heat ? blk_rank(n, lv.fac, nt, lv.t_host.data(), nullptr) : (blk_fourier_ok(n, nt) ? n : 0);
+        r = heat ? blk_rank(n, lv.fac, nt, lv.t_host.data()) : (blk_fourier_ok(n, nt) ? n : 0);
         if (r == 0) return 0;
     }
     const int B = (nt - 1) / BLK_K;   // whole blocks of the rank's share, the last one with the remainder (a rank of a sharded level may hold fewer than 4)
@@ -3244,17 +3217,9 @@ int blk_config(mgrit_hip_engine *e, int lvl, int r, int first_real, int has_succ
     BlkDev bk{};
     if (heat) {
         if (r > BLK_RMAX || r > n) return fail(MGRIT_HIP_EINVAL, "time-parallel forward solve: r = %d modes outside [1, %d]", r, std::min(BLK_RMAX, n));
-        // D_b(k) = prod over the block's steps of 1 / (1 + dt_i fac 4 sin^2(theta_k / 2)), products in step order
-        std::vector<double> Dt((size_t)B * BLK_RMAX, 0.0);
-        for (int b = 0; b < B; ++b) {
-            const int first = BLK_K * b + 1, last = b == B - 1 ? nt - 1 : BLK_K * (b + 1);
-            for (int k = 0; k < BLK_RMAX && k < n; ++k) {
-                const double lam = blk_lam4(n, k);
-                double d = 1.0;
-                for (int i = first; i <= last; ++i) d = d * (1.0 / (1.0 + ((lv.t_host[i] - lv.t_host[i - 1]) * lv.fac) * lam));
-                Dt[(size_t)b * BLK_RMAX + k] = d;
-            }
-        }
+        std::vector<double> Dt((size_t)B * BLK_RMAX, 0.0);   // D_b(k)
+        for (int b = 0; b < B; ++b)
+            for (int k = 0; k < BLK_RMAX && k < n; ++k) Dt[(size_t)b * BLK_RMAX + k] = blk_decay(n, k, lv.fac, lv.t_host.data(), blk_steps(b, B, nt - 1));
         // the sine modes in row storage order: a table of (r rounded up to 16) x ld doubles that depends on (n, ld, rows) only -- 8 MB and
         // 0.8 M calls of sin at config 3. A process that builds solver after solver on the same spatial grid (a service; the second
         // constructor of bench.py's time-to-solution) finds it in a small process-wide cache, device resident and immutable
@@ -3291,10 +3256,8 @@ int blk_config(mgrit_hip_engine *e, int lvl, int r, int first_real, int has_succ
         if ((rc = dev_upload(lv, e->stream, Dt, &dD))) return rc;
         // amplitudes, propagated amplitudes and the chunks' partial sums: one slab, zeroed on the device ([2 + G][B][BLK_RMAX]: 9 MB at
         // config 3 -- modes past r are never written and must read as zero)
-        const size_t per = (size_t)B * BLK_RMAX, slab = (size_t)(2 + lv.G) * per;
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&dW), sizeof(double) * slab));
-        lv.allocs.push_back(dW);
-        HIP_TRY(hipMemsetAsync(dW, 0, sizeof(double) * slab, e->stream));
+        const size_t per = (size_t)B * BLK_RMAX;
+        if ((rc = level_zeros(e, lv, (size_t)(2 + lv.G) * per, &dW))) return rc;
         bk.Q = dQ; bk.D = dD; bk.what = dW; bk.C = dW + per;
         lv.blk_part = dW + 2 * per;
     } else {
@@ -3310,11 +3273,11 @@ int blk_config(mgrit_hip_engine *e, int lvl, int r, int first_real, int has_succ
             W[2 * (size_t)t] = sep_cos(ang); W[2 * (size_t)t + 1] = -sep_sin(ang);
         }
         for (int b = 0; b < B; ++b) {
-            const int first = BLK_K * b + 1, last = b == B - 1 ? nt - 1 : BLK_K * (b + 1);
+            const BlkSteps sb = blk_steps(b, B, nt - 1);
             for (int k = 0; k < n; ++k) {
                 const double th = 2.0 * M_PI * (double)k / (double)n, cs = sep_cos(th), sn = sep_sin(th);
                 double pr = 1.0, pi = 0.0;
-                for (int i = first; i <= last; ++i) {
+                for (int i = sb.first; i <= sb.last; ++i) {
                     const double alpha = (lv.t_host[i] - lv.t_host[i - 1]) * lv.fac;
                     const double mr = (1.0 + alpha) - alpha * cs, mi = alpha * sn, den = mr * mr + mi * mi;
                     const double dr = mr / den, di = -mi / den;
@@ -3328,21 +3291,15 @@ int blk_config(mgrit_hip_engine *e, int lvl, int r, int first_real, int has_succ
         if ((rc = dev_upload(lv, e->stream, W, &dT))) return rc;
         if ((rc = dev_upload(lv, e->stream, Dt, &dD))) return rc;
         const size_t per = (size_t)B * n * 2;       // amplitudes and propagated amplitudes: zeroed on the device
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&dW), sizeof(double) * 2 * per));
-        lv.allocs.push_back(dW);
-        HIP_TRY(hipMemsetAsync(dW, 0, sizeof(double) * 2 * per, e->stream));
+        if ((rc = level_zeros(e, lv, 2 * per, &dW))) return rc;
         bk.tw = reinterpret_cast<const double2 *>(dT); bk.D = dD; bk.what = dW; bk.C = dW + per;
         bk.fourier = pow2 ? 1 : 2;                  // 1: radix-2 in LDS, 2: ordered sums on the matrix cores
         bk.lg_n = 0;
         while ((1 << bk.lg_n) < n) ++bk.lg_n;
     }
-    {
-        double *dWs = nullptr;   // (zeroed on the device: as a host vector of B rows it was 33 MB allocated, cleared and copied at config 3)
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&dWs), sizeof(double) * (size_t)B * ld));
-        lv.allocs.push_back(dWs);
-        HIP_TRY(hipMemsetAsync(dWs, 0, sizeof(double) * (size_t)B * ld, e->stream));
-        bk.Ws = dWs;
-    }
+    double *dWs = nullptr;   // (zeroed on the device: as a host vector of B rows it was 33 MB allocated, cleared and copied at config 3)
+    if ((rc = level_zeros(e, lv, (size_t)B * ld, &dWs))) return rc;
+    bk.Ws = dWs;
     lv.blk_qt = nullptr;
     if (heat && lv.G == 1 && lv.dev.T == LANES && ld == GROUP && r <= BLK_ONE_MAX_R && B <= BLK_ONE_MAX_B && first_real && !has_successor &&
         blk_one_launch_enabled()) {
@@ -3354,9 +3311,7 @@ int blk_config(mgrit_hip_engine *e, int lvl, int r, int first_real, int has_succ
                            reinterpret_cast<double2 *>(qt));
         HIP_TRY(hipGetLastError());
         if (!lv.blk_sync) {
-            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&lv.blk_sync), 256));
-            lv.allocs.push_back(lv.blk_sync);
-            HIP_TRY(hipMemsetAsync(lv.blk_sync, 0, 256, e->stream));
+            if ((rc = level_zeros(e, lv, 256 / sizeof(unsigned), &lv.blk_sync))) return rc;
             HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&lv.blk_err), 256, hipHostMallocMapped));
             *lv.blk_err = 0u;
         }
@@ -3412,23 +3367,11 @@ int mgrit_hip_destroy(mgrit_hip_engine *e) {
     (void)hipStreamSynchronize(e->stream);
     for (auto &lv : e->L) {
         if (lv.blk_err) (void)hipHostFree(lv.blk_err);
-        if (lv.h2d) {
-            if (lv.h2d->W0) (void)hipFree(lv.h2d->W0);
-            if (lv.h2d->W1) (void)hipFree(lv.h2d->W1);
-            if (lv.h2d->rowsq) (void)hipFree(lv.h2d->rowsq);
-            if (lv.h2d->Wc0) (void)hipFree(lv.h2d->Wc0);
-            if (lv.h2d->Wc1) (void)hipFree(lv.h2d->Wc1);
-            if (lv.h2d->blk.rim_flag) (void)hipHostFree(lv.h2d->blk.rim_flag);
-            if (lv.h2d->blk.rim_ev) (void)hipEventDestroy(lv.h2d->blk.rim_ev);
-            delete lv.h2d;
-        }
-        if (lv.wide) {
-            for (double *p : {lv.wide->W, lv.wide->tot, lv.wide->car, lv.wide->z0, lv.wide->red, lv.wide->T0})
-                if (p) (void)hipFree(p);
-            delete lv.wide;
-        }
+        if (lv.h2d) h2d_release(lv.h2d);
+        if (lv.wide) wide_release(lv.wide);
         for (void *p : lv.allocs) (void)hipFree(p);
         if (lv.scratch) (void)hipFree(lv.scratch);
+        if (lv.gen_rows) (void)hipFree(lv.gen_rows);
     }
     e->arena.release();
     if (e->chain_gran) (void)hipFree(e->chain_gran);
@@ -3467,10 +3410,82 @@ int mgrit_hip_level_heat1d(mgrit_hip_engine *e, int lvl, int n_pts_local, const 
     return level_common(e, lvl, MGRIT_HIP_STEPPER_HEAT1D, n_pts_local, t_local, n, ld, fac, K, s, tau);
 }
 
-int mgrit_hip_level_heat1d_2pts(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int n, int ld,
-                                double fac, double dtau, int order, int K, const double *s, const double *tau,
-                                const double *tau2) {
-    return level_heat1d_2pts(e, lvl, n_pts_local, t_local, n, ld, fac, dtau, order, K, s, tau, tau2);
+int mgrit_hip_level_heat1d_2pts(mgrit_hip_engine *e, int lvl, int n_pts, const double *t_local, int n, int ld, double fac, double dtau,
+                                int order, int K, const double *s, const double *tau, const double *tau2) {
+    int rc = check_level(e, lvl, false);
+    if (rc) return rc;
+    if (n < 1 || n > MGRIT_HIP_MAX_N_WIDE)
+        return fail(MGRIT_HIP_EUNSUPPORTED, "n=%d DOFs per time point outside [1,%d] (two-point stepper)", n, MGRIT_HIP_MAX_N_WIDE);
+    if (ld != 2 * mgrit_hip_row_stride(n)) return fail(MGRIT_HIP_EINVAL, "ld=%d must equal 2*mgrit_hip_row_stride(n=%d)=%d", ld, n, 2 * mgrit_hip_row_stride(n));
+    if (order != 1 && order != 2) return fail(MGRIT_HIP_EINVAL, "BDF order must be 1 or 2");
+    if (no_time_grid(n_pts, t_local)) return fail(MGRIT_HIP_EINVAL, "bad local time grid");
+    if ((rc = check_forcing(K, n_pts, s, tau && tau2))) return rc;
+    if ((rc = register_lds_limits())) return rc;
+    if ((rc = level_fresh(e, lvl))) return rc;
+    Level &lv = e->L[lvl];
+    const int G = (n + GROUP - 1) / GROUP, T = G * LANES;
+    lv.G = G;
+    lv.order = order;
+    if (n > MGRIT_HIP_MAX_N_2PTS) lv.wide = new WideHost();   // wider than a workgroup holds: every half-solve as three launches (mgrit_hip_wide.inc)
+    LevelDev &d = lv.dev;
+    d.n = n; d.ld = ld; d.T = T; d.n_pts = n_pts; d.K = K; d.kind = MGRIT_HIP_STEPPER_HEAT1D_2PTS;
+    d.stream_rows = 0;
+    const size_t np = n_pts > 0 ? n_pts : 0;
+    const std::vector<double> dts = step_sizes(n_pts, t_local);
+    std::vector<double> uniq, hc(np * 4, 0.0), fs(np * 2, 0.0);
+    std::vector<int32_t> cidx2(np * 2, 0);
+    auto set_of = [&](double dt_eff) -> int {
+        for (size_t q = 0; q < uniq.size(); ++q)
+            if (std::memcmp(&uniq[q], &dt_eff, sizeof(double)) == 0) return (int)q;
+        uniq.push_back(dt_eff);
+        return (int)uniq.size() - 1;
+    };
+    for (int i = 1; i < n_pts; ++i) {
+        const double tl0 = dts[i] - dtau;
+        HalfCoef h[2];
+        if (order == 1) {
+            h[0].dt_eff = tl0; h[1].dt_eff = dtau;
+            for (int q = 0; q < 2; ++q) { h[q].a = 1.0; h[q].nb = 0.0; h[q].fs = h[q].dt_eff; }
+        } else {
+            h[0] = bdf2_half(tl0, dtau);
+            h[1] = bdf2_half(dtau, tl0);
+        }
+        for (int q = 0; q < 2; ++q) {
+            cidx2[2 * (size_t)i + q] = set_of(h[q].dt_eff);
+            hc[4 * (size_t)i + 2 * q] = h[q].a;
+            hc[4 * (size_t)i + 2 * q + 1] = h[q].nb;
+            fs[2 * (size_t)i + q] = h[q].fs;
+        }
+        if (uniq.size() > 4096) return fail(MGRIT_HIP_EUNSUPPORTED, "more than 4096 distinct time-step sizes on level %d", lvl);
+    }
+    lv.n_csets = (int)uniq.size();
+    std::vector<CSet> cs(uniq.size());
+    std::vector<double> tabT(uniq.size() * (size_t)E * T, 0.0), tab;
+    std::vector<double> ptT(uniq.size() * (size_t)2 * GROUP, 0.0), pt(GROUP), pt_last(GROUP);
+    for (size_t q = 0; q < uniq.size(); ++q)
+        heat1d_cset_tables(cs[q], tabT.data() + q * (size_t)E * T, ptT.data() + q * (size_t)2 * GROUP, n, fac, uniq[q], tab, pt.data(),
+                           pt_last.data());
+    std::vector<double> sT = space_factors(K, n, T, s), tc((size_t)(K > 0 ? K : 0) * np * 2, 0.0);
+    for (int kk = 0; kk < K; ++kk)
+        for (int i = 1; i < n_pts; ++i) {   // tc[k][i][half] = tau_k(t_i [+ dtau]) * forcing scale of the half
+            tc[((size_t)kk * np + i) * 2] = tau[(size_t)kk * n_pts + i] * fs[2 * (size_t)i];
+            tc[((size_t)kk * np + i) * 2 + 1] = tau2[(size_t)kk * n_pts + i] * fs[2 * (size_t)i + 1];
+        }
+    int32_t *d_cidx2; double *d_dt, *d_tc, *d_sT, *d_tabT, *d_ptT, *d_hc; CSet *d_cs;
+    if ((rc = dev_upload(lv, e->stream, cidx2, &d_cidx2))) return rc;
+    if ((rc = dev_upload(lv, e->stream, dts, &d_dt))) return rc;
+    if ((rc = dev_upload(lv, e->stream, tc, &d_tc))) return rc;
+    if ((rc = dev_upload(lv, e->stream, sT, &d_sT))) return rc;
+    if ((rc = dev_upload(lv, e->stream, cs, &d_cs))) return rc;
+    if ((rc = dev_upload(lv, e->stream, tabT, &d_tabT))) return rc;
+    if ((rc = dev_upload(lv, e->stream, ptT, &d_ptT))) return rc;
+    if ((rc = dev_upload(lv, e->stream, hc, &d_hc))) return rc;
+    d.cidx = nullptr; d.cidx2 = d_cidx2; d.hc = d_hc; d.dt = d_dt; d.tc = d_tc; d.cs = d_cs;
+    d.ptP = reinterpret_cast<const double2 *>(d_ptT);
+    d.sP = reinterpret_cast<const double2 *>(d_sT);
+    d.tabP = reinterpret_cast<const double2 *>(d_tabT);
+    lv.set = true;
+    return 0;
 }
 
 int mgrit_hip_level_advection1d(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int n, int ld,
@@ -3485,10 +3500,10 @@ int mgrit_hip_level_heat2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const 
     if (nx < 3 || ny < 3 || nx > 2050 || ny > 2050) return fail(MGRIT_HIP_EUNSUPPORTED, "Heat2D grid %dx%d outside [3,2050]^2", nx, ny);
     if (ld < nx * ny || (ld % 16) != 0) return fail(MGRIT_HIP_EINVAL, "ld=%d must be a multiple of 16 and >= nx*ny=%d", ld, nx * ny);
     if (!(theta == 0.0 || theta == 0.5 || theta == 1.0)) return fail(MGRIT_HIP_EINVAL, "theta must be 0 (FE), 0.5 (CN) or 1 (BE)");
-    if (n_pts_local < 0 || (n_pts_local > 0 && !t_local) || !bc) return fail(MGRIT_HIP_EINVAL, "bad arguments");
-    if (K < 0 || K > 8 || (K > 0 && (!S || (n_pts_local > 0 && !tau)))) return fail(MGRIT_HIP_EINVAL, "bad forcing description (K=%d)", K);
+    if (no_time_grid(n_pts_local, t_local) || !bc) return fail(MGRIT_HIP_EINVAL, "bad arguments");
+    if ((rc = check_forcing(K, n_pts_local, S, tau != nullptr))) return rc;
+    if ((rc = level_fresh(e, lvl))) return rc;
     Level &lv = e->L[lvl];
-    if (lv.set) return fail(MGRIT_HIP_EINVAL, "level %d already described", lvl);
     H2DHost *h = new H2DHost();
     lv.h2d = h;
     H2DDev &H = h->dev;
@@ -3496,13 +3511,12 @@ int mgrit_hip_level_heat2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const 
     h->HPx = (((H.mi + 1) / 2 + 63) / 64) * 64; h->HPy = (((H.mj + 1) / 2 + 63) / 64) * 64;
     H.Mi = 2 * h->HPx; H.Mj = 2 * h->HPy;   // one padded length per axis for the natural and the spectral layout
     H.K = K; H.n_pts = n_pts_local; H.ld = ld; H.fx = fx; H.fy = fy; H.theta = theta;
-    h->dts.assign(n_pts_local > 0 ? n_pts_local : 0, 0.0);
-    for (int i = 1; i < n_pts_local; ++i) h->dts[i] = t_local[i] - t_local[i - 1];
+    h->dts = step_sizes(n_pts_local, t_local);
     // tables
     std::vector<double> fxe, fxo, fxet, fxot, fye, fyo, fyet, fyot;
     h2d_axis_tables(H.mi, h->HPx, fx, fxe, fxo, fxet, fxot, h->lx);
     h2d_axis_tables(H.mj, h->HPy, fy, fye, fyo, fyet, fyot, h->ly);
-    std::vector<double> W((size_t)H.Mi * H.Mj, 0.0), Sp((size_t)(K > 0 ? K : 0) * H.Mi * H.Mj, 0.0), bcv(bc, bc + (size_t)nx * ny);
+    std::vector<double> W((size_t)H.Mi * H.Mj, 0.0), Sp((size_t)(K > 0 ? K : 0) * H.Mi * H.Mj, 0.0);
     H.has_w = 0;
     for (int a = 0; a < H.mi; ++a)
         for (int b = 0; b < H.mj; ++b) {
@@ -3517,18 +3531,16 @@ int mgrit_hip_level_heat2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const 
     for (int k = 0; k < K; ++k)
         for (int a = 0; a < H.mi; ++a)
             for (int b = 0; b < H.mj; ++b) Sp[((size_t)k * H.Mi + a) * H.Mj + b] = S[((size_t)k * H.mi + a) * H.mj + b];
-    std::vector<double> tauv;
-    if (K > 0) tauv.assign(tau, tau + (size_t)K * n_pts_local);
     double *d_bc, *d_W, *d_S, *d_tau, *d_dt;
     if ((rc = dev_upload(lv, e->stream, fxe, &h->Fxe)) || (rc = dev_upload(lv, e->stream, fxo, &h->Fxo)) ||
         (rc = dev_upload(lv, e->stream, fxet, &h->FxeT)) || (rc = dev_upload(lv, e->stream, fxot, &h->FxoT)) ||
         (rc = dev_upload(lv, e->stream, fye, &h->Fye)) || (rc = dev_upload(lv, e->stream, fyo, &h->Fyo)) ||
         (rc = dev_upload(lv, e->stream, fyet, &h->FyeT)) || (rc = dev_upload(lv, e->stream, fyot, &h->FyoT)))
         return rc;
-    if ((rc = dev_upload(lv, e->stream, bcv, &d_bc))) return rc;
+    if ((rc = dev_upload(lv, e->stream, bc, (size_t)nx * ny, &d_bc))) return rc;
     if ((rc = dev_upload(lv, e->stream, W, &d_W))) return rc;
     if ((rc = dev_upload(lv, e->stream, Sp, &d_S))) return rc;
-    if ((rc = dev_upload(lv, e->stream, tauv, &d_tau))) return rc;
+    if ((rc = dev_upload(lv, e->stream, tau, K > 0 ? (size_t)K * n_pts_local : 0, &d_tau))) return rc;
     if ((rc = dev_upload(lv, e->stream, h->dts, &d_dt))) return rc;
     H.bc = d_bc; H.W = d_W; H.S = d_S; H.tstop = d_tau; H.dt = d_dt;
     lv.dev.kind = MGRIT_HIP_STEPPER_HEAT2D;
@@ -3545,9 +3557,9 @@ int mgrit_hip_level_allencahn2d(mgrit_hip_engine *e, int lvl, int n_pts_local, c
     if (nx < 4 || nx > 2048) return fail(MGRIT_HIP_EUNSUPPORTED, "Allen-Cahn grid %dx%d outside [4,2048]^2", nx, nx);
     if (ld < nx * nx || (ld % 16) != 0) return fail(MGRIT_HIP_EINVAL, "ld=%d must be a multiple of 16 and >= nx*nx=%d", ld, nx * nx);
     if (nu < 1 || nu > 64 || !(inv_dx2 > 0.0) || !(inv_eps2 > 0.0)) return fail(MGRIT_HIP_EINVAL, "bad Allen-Cahn parameters (nu=%d)", nu);
-    if (n_pts_local < 0 || (n_pts_local > 0 && !t_local)) return fail(MGRIT_HIP_EINVAL, "bad arguments");
+    if (no_time_grid(n_pts_local, t_local)) return fail(MGRIT_HIP_EINVAL, "bad arguments");
+    if ((rc = level_fresh(e, lvl))) return rc;
     Level &lv = e->L[lvl];
-    if (lv.set) return fail(MGRIT_HIP_EINVAL, "level %d already described", lvl);
     H2DHost *h = new H2DHost();
     lv.h2d = h;
     h->ac = true; h->ac_inv_eps2 = inv_eps2; h->ac_nu = nu;
@@ -3557,8 +3569,7 @@ int mgrit_hip_level_allencahn2d(mgrit_hip_engine *e, int lvl, int n_pts_local, c
     h->HPx = h->HPy = P / 2;
     h->ac_KP = ((nx + H2D_BK - 1) / H2D_BK) * H2D_BK;
     H.K = 0; H.n_pts = n_pts_local; H.ld = ld; H.fx = H.fy = 0.0; H.theta = 1.0; H.has_w = 0;
-    h->dts.assign(n_pts_local > 0 ? n_pts_local : 0, 0.0);
-    for (int i = 1; i < n_pts_local; ++i) h->dts[i] = t_local[i] - t_local[i - 1];
+    h->dts = step_sizes(n_pts_local, t_local);
     // Hartley table (the angle reduced exactly: (i k) mod nx) and the eigenvalues of the periodic 5-point Laplacian
     std::vector<double> tab((size_t)P * P, 0.0);
     const long double two_pi = 6.283185307179586476925286766559L, s = 1.0L / sqrtl((long double)nx);
@@ -3653,7 +3664,7 @@ int mgrit_hip_chain_resume(mgrit_hip_engine *e, int lvl, int on) {
 int mgrit_hip_block_solve_rank(int stepper, int n, double fac, int nt, const double *t, int *r_out) {
     if (!r_out || (nt > 0 && !t)) return fail(MGRIT_HIP_EINVAL, "null argument");
     *r_out = 0;
-    if (stepper == MGRIT_HIP_STEPPER_HEAT1D) *r_out = (n >= 2 && n <= MGRIT_HIP_MAX_N && nt >= 2) ? blk_rank(n, fac, nt, t, nullptr) : 0;
+    if (stepper == MGRIT_HIP_STEPPER_HEAT1D) *r_out = (n >= 2 && n <= MGRIT_HIP_MAX_N && nt >= 2) ? blk_rank(n, fac, nt, t) : 0;
     else if (stepper == MGRIT_HIP_STEPPER_ADVECTION1D) *r_out = blk_fourier_ok(n, nt) ? n : 0;
     return 0;
 }
@@ -3745,26 +3756,21 @@ int mgrit_hip_runs_create(mgrit_hip_engine *e, int lvl, int n_runs, const int32_
     rl.n = n_runs;
     rl.h_start.assign(start, start + n_runs);
     rl.h_len.assign(len, len + n_runs);
-    std::vector<int32_t> hs(start, start + n_runs), hl(len, len + n_runs);
-    if ((rc = dev_upload(lv, e->stream, hs, &rl.d_start))) return rc;
-    if ((rc = dev_upload(lv, e->stream, hl, &rl.d_len))) return rc;
+    if ((rc = dev_upload(lv, e->stream, start, (size_t)n_runs, &rl.d_start))) return rc;
+    if ((rc = dev_upload(lv, e->stream, len, (size_t)n_runs, &rl.d_len))) return rc;
     lv.runs.push_back(rl);
     *id_out = (int)lv.runs.size() - 1;
     return 0;
 }
 
-// rows of the level's scratch slab, grown here and nowhere else: a bigger need than any before gets a NEW slab, the old one stays
-// alive until the engine goes (lf.allocs) -- a captured cycle that ran a sweep on a block's shorter list still launches with its
-// address (found by the state fuzz: a whole-level fas_residual by hand between two replays of a two-block plan freed the slab
-// under the graph)
+// rows of the level's scratch slab, grown here and nowhere else (slab_regrow: a captured cycle that ran a sweep on a block's shorter
+// list still launches with the old address)
 static int scratch_reserve(Level &lf, size_t rows) {
     if (lf.scratch_rows >= rows) return 0;
-    if (lf.scratch) lf.allocs.push_back(lf.scratch);
-    lf.scratch = nullptr;
     lf.scratch_rows = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&lf.scratch), sizeof(double) * rows * lf.dev.ld));
-    lf.scratch_rows = rows;
-    return 0;
+    const int rc = slab_regrow(lf, &lf.scratch, rows * lf.dev.ld);
+    if (!rc) lf.scratch_rows = rows;
+    return rc;
 }
 
 int mgrit_hip_pairs_create(mgrit_hip_engine *e, int lvl, int n_pairs, const int32_t *fine_idx, const int32_t *coarse_idx,
@@ -3783,10 +3789,10 @@ int mgrit_hip_pairs_create(mgrit_hip_engine *e, int lvl, int n_pairs, const int3
     pl.n = n_pairs;
     pl.h_fine.assign(fine_idx, fine_idx + n_pairs);
     pl.h_coarse.assign(coarse_idx, coarse_idx + n_pairs);
-    std::vector<int32_t> hf(fine_idx, fine_idx + n_pairs), hc(coarse_idx, coarse_idx + n_pairs), iota(n_pairs);
+    std::vector<int32_t> iota(n_pairs);
     for (int p = 0; p < n_pairs; ++p) iota[p] = p;
-    if ((rc = dev_upload(lv, e->stream, hf, &pl.d_fine))) return rc;
-    if ((rc = dev_upload(lv, e->stream, hc, &pl.d_coarse))) return rc;
+    if ((rc = dev_upload(lv, e->stream, fine_idx, (size_t)n_pairs, &pl.d_fine))) return rc;
+    if ((rc = dev_upload(lv, e->stream, coarse_idx, (size_t)n_pairs, &pl.d_coarse))) return rc;
     if ((rc = dev_upload(lv, e->stream, iota, &pl.d_iota))) return rc;
     // a 2-D library transfer takes the fine half of the FAS right-hand side through scratch rows of the level (mgrit_hip_fas_rhs): the
     // slab is sized here, where lists are made, so that the sweep itself -- possibly part of a captured or replayed cycle -- never allocates
@@ -3932,6 +3938,17 @@ static T2DGeom t2d_geom(const Level &lf, const Level &lc) {
     return T2DGeom{lf.h2d->dev.nx, lf.h2d->dev.ny, lc.h2d->dev.nx, lc.h2d->dev.ny, lf.transfer == MGRIT_HIP_TRANSFER_PERIODIC2D ? 1 : 0};
 }
 
+// The 1-D row transfer: row d_idx[p] of dst (rows of level `to`) = R(row s_idx[p] of src (rows of level `from`)) for count rows; kind:
+// the levels' transfer, MGRIT_HIP_TRANSFER_COPY between rows of one level = a gather / scatter of rows
+static int restrict_rows_launch(mgrit_hip_engine *e, const Level &from, const double *src, const int32_t *s_idx, const Level &to, double *dst,
+                                const int32_t *d_idx, int count, int kind) {
+    const dim3 grid(count, (to.dev.ld + 255) / 256);
+    hipLaunchKernelGGL(restrict_rows_kernel, grid, dim3(256), 0, e->stream, src, from.dev.ld, from.dev.T, s_idx, dst, to.dev.ld, to.dev.T, d_idx,
+                       to.dev.n, kind);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 static int restrict2d_launch(mgrit_hip_engine *e, const Level &lf, const Level &lc, const double *src, const int32_t *s_idx, double *dst,
                              const PairList *pl) {
     const dim3 grid(pl->n, (lc.dev.ld + 255) / 256);
@@ -4007,11 +4024,7 @@ int mgrit_hip_restrict_u(mgrit_hip_engine *e, int lvl, int pairs_id) {
     if (pl->n == 0) return 0;
     Timed timed(e, MGRIT_HIP_T_RESTRICT, lvl);
     if (transfer_2d(lf)) return restrict2d_launch(e, lf, lc, lf.dev.u, pl->d_fine, lc.dev.u, pl);
-    dim3 grid(pl->n, (lc.dev.ld + 255) / 256);
-    hipLaunchKernelGGL(restrict_rows_kernel, grid, dim3(256), 0, e->stream, lf.dev.u, lf.dev.ld, lf.dev.T, pl->d_fine, lc.dev.u,
-                       lc.dev.ld, lc.dev.T, pl->d_coarse, lc.dev.n, lf.transfer);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return restrict_rows_launch(e, lf, lf.dev.u, pl->d_fine, lc, lc.dev.u, pl->d_coarse, pl->n, lf.transfer);
 }
 
 int mgrit_hip_copy_u_to_v(mgrit_hip_engine *e, int lvl_coarse) {
@@ -4083,14 +4096,9 @@ int mgrit_hip_fas_rhs(mgrit_hip_engine *e, int lvl, int pairs_id) {
         if ((rc = fas_fine_half(e, lvl, pl, lc.dev.g, lc.dev.ld, false))) return rc;
     } else {
         if ((rc = fas_fine_half(e, lvl, pl, lf.scratch, lf.dev.ld, true))) return rc;
-        if (transfer_2d(lf)) {
-            if ((rc = restrict2d_launch(e, lf, lc, lf.scratch, pl->d_iota, lc.dev.g, pl))) return rc;
-        } else {
-            dim3 grid(pl->n, (lc.dev.ld + 255) / 256);
-            hipLaunchKernelGGL(restrict_rows_kernel, grid, dim3(256), 0, e->stream, lf.scratch, lf.dev.ld, lf.dev.T, pl->d_iota,
-                               lc.dev.g, lc.dev.ld, lc.dev.T, pl->d_coarse, lc.dev.n, lf.transfer);
-            HIP_TRY(hipGetLastError());
-        }
+        rc = transfer_2d(lf) ? restrict2d_launch(e, lf, lc, lf.scratch, pl->d_iota, lc.dev.g, pl)
+                             : restrict_rows_launch(e, lf, lf.scratch, pl->d_iota, lc, lc.dev.g, pl->d_coarse, pl->n, lf.transfer);
+        if (rc) return rc;
     }
     return fas_coarse_half(e, lvl, pl);
 }
@@ -4239,11 +4247,7 @@ int mgrit_hip_copy_pairs_u_to_v(mgrit_hip_engine *e, int lvl, int pairs_id) {
     if ((rc = check_bound(lc, true))) return rc;
     if (pl->n == 0) return 0;
     Timed timed(e, MGRIT_HIP_T_COPY, lvl);
-    dim3 grid(pl->n, (lc.dev.ld + 255) / 256);
-    hipLaunchKernelGGL(restrict_rows_kernel, grid, dim3(256), 0, e->stream, lc.dev.u, lc.dev.ld, lc.dev.T, pl->d_coarse, lc.dev.v,
-                       lc.dev.ld, lc.dev.T, pl->d_coarse, lc.dev.n, MGRIT_HIP_TRANSFER_COPY);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return restrict_rows_launch(e, lc, lc.dev.u, pl->d_coarse, lc, lc.dev.v, pl->d_coarse, pl->n, MGRIT_HIP_TRANSFER_COPY);
 }
 
 static int interp_common(mgrit_hip_engine *e, int lvl, int pairs_id, int mode) {
@@ -4294,15 +4298,10 @@ static int at_batched(mgrit_hip_engine *e, int lvl, int k) {
     });
     if (rc) return rc;
     double *X = lv.scratch;
-    const dim3 grid(ap.count, (ld + 255) / 256);
-    hipLaunchKernelGGL(restrict_rows_kernel, grid, dim3(256), 0, e->stream, lv.dev.u, ld, lv.dev.T, ap.d_src, X, ld, lv.dev.T, ap.d_own,
-                       lv.dev.n, MGRIT_HIP_TRANSFER_COPY);
+    if ((rc = restrict_rows_launch(e, lv, lv.dev.u, ap.d_src, lv, X, ap.d_own, ap.count, MGRIT_HIP_TRANSFER_COPY))) return rc;
     for (const BatchPlan &pl : ap.steps.plans)
         if ((rc = batch_phi_op(e, lv, pl, X, X, ld, lv.dev.g, X, H2D_OP_F, 1, 1.0))) return rc;
-    hipLaunchKernelGGL(restrict_rows_kernel, grid, dim3(256), 0, e->stream, X, ld, lv.dev.T, ap.d_own, lv.dev.u, ld, lv.dev.T, ap.d_own,
-                       lv.dev.n, MGRIT_HIP_TRANSFER_COPY);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return restrict_rows_launch(e, lv, X, ap.d_own, lv, lv.dev.u, ap.d_own, ap.count, MGRIT_HIP_TRANSFER_COPY);
 }
 
 int mgrit_hip_at_solve(mgrit_hip_engine *e, int lvl, int k) {
@@ -4333,8 +4332,7 @@ int mgrit_hip_ec_runs_create(mgrit_hip_engine *e, int lvl, int n_runs, const int
     for (int r = 0; r < n_runs; ++r)
         if (coarse_idx[r] < -1 || coarse_idx[r] >= e->L[lvl + 1].dev.n_pts)
             return fail(MGRIT_HIP_EINVAL, "run %d: coarse slot %d outside [-1,%d)", r, coarse_idx[r], e->L[lvl + 1].dev.n_pts);
-    std::vector<int32_t> h(coarse_idx, coarse_idx + n_runs);
-    return dev_upload(lv, e->stream, h, &lv.runs[*id_out].d_ec);
+    return dev_upload(lv, e->stream, coarse_idx, (size_t)n_runs, &lv.runs[*id_out].d_ec);
 }
 
 int mgrit_hip_ec_relax(mgrit_hip_engine *e, int lvl, int ec_runs_id) {
@@ -4479,11 +4477,11 @@ int mgrit_hip_intervals_create(mgrit_hip_engine *e, int lvl, int n, const int32_
     for (size_t k = 0; k < cf.size(); ++k) kp[cf[k] + cl[k] - 1] |= 2;   // a chunk (of this or of the next list) starts from its end
     IntervalsDev d{};
     int32_t *p[8];
-    const std::vector<int32_t> hs[8] = {std::vector<int32_t>(cstart, cstart + n), std::vector<int32_t>(cend, cend + n),
-                                        std::vector<int32_t>(cend_coarse, cend_coarse + n), std::vector<int32_t>(res_pos, res_pos + n),
-                                        cf, cl, cc, kp};
-    for (int k = 0; k < 8; ++k)
-        if ((rc = dev_upload(lv, e->stream, hs[k], &p[k]))) return rc;
+    if ((rc = dev_upload(lv, e->stream, cstart, (size_t)n, &p[0])) || (rc = dev_upload(lv, e->stream, cend, (size_t)n, &p[1])) ||
+        (rc = dev_upload(lv, e->stream, cend_coarse, (size_t)n, &p[2])) || (rc = dev_upload(lv, e->stream, res_pos, (size_t)n, &p[3])) ||
+        (rc = dev_upload(lv, e->stream, cf, &p[4])) || (rc = dev_upload(lv, e->stream, cl, &p[5])) ||
+        (rc = dev_upload(lv, e->stream, cc, &p[6])) || (rc = dev_upload(lv, e->stream, kp, &p[7])))
+        return rc;
     d.cstart = p[0]; d.cend = p[1]; d.cend_coarse = p[2]; d.res_pos = p[3]; d.chunk_first = p[4]; d.chunk_len = p[5];
     d.chunk_start_coarse = p[6]; d.keep = p[7]; d.n_chunks = (int)cf.size();
     lv.ivals.push_back(d);
@@ -4573,12 +4571,9 @@ static int gen_reserve(mgrit_hip_engine *e, Level &lf, size_t res_len) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(e->stream, &cs);
     if (cs != hipStreamCaptureStatusNone) return fail(MGRIT_HIP_EINVAL, "first whole-level pass of a level inside a stream capture");
-    void *d = nullptr;
-    HIP_TRY(hipMalloc(&d, res_len * (size_t)lf.dev.ld * sizeof(double)));
-    lf.allocs.push_back(d);      // (an earlier, smaller slab stays in the list until the engine goes)
-    lf.gen_rows = static_cast<double *>(d);
-    lf.gen_len = res_len;
-    return 0;
+    const int rc = slab_regrow(lf, &lf.gen_rows, res_len * (size_t)lf.dev.ld);
+    if (!rc) lf.gen_len = res_len;
+    return rc;
 }
 
 int mgrit_hip_gen_down(mgrit_hip_engine *e, int lvl, int ivals_id) { return mgrit_hip_gen_down_part(e, lvl, ivals_id, 3); }
