@@ -51,13 +51,12 @@ def _lists(mg, lvl):
 
 
 def _set_states(dev, host, states):
-    """states[(name, lvl)] = [n_pts][nx*nx]"""
+    """states[(name, lvl)] = [n_pts][values of one state in row-major order] (nx x nx here, nx x ny for Heat2D)"""
     for (name, lvl), val in states.items():
         dev.backend.set_natural(name, lvl, val)
-        nx = host.problem[lvl].nx
         lst = dict(_lists(host, lvl))[name]
         for i in range(len(lst)):
-            lst[i].set_values(val[i].reshape(nx, nx).copy())
+            lst[i].set_values(val[i].reshape(np.shape(lst[i].get_values())).copy())
 
 
 def _random_states(host, seed, zero_g=False):

@@ -1,6 +1,13 @@
 """GPU parity for Heat2D (BASELINE config 4 family): the MFMA fast-diagonalisation stepper and every sweep on 2-D states
 against the oracle (same arithmetic: fma dot products in ascending k = v_mfma_f64_16x16x4 chains), bit for bit; solves
-against the oracle (1e-10 rel) and the reference fixtures (tests/golden/heat2d.*)."""
+against the oracle (1e-10 rel) and the reference fixtures (tests/golden/heat2d.*).
+
+What this comparison can see: any difference between the kernels and the oracle -- operand order, a race, a tile edge, a wrong index.
+What it cannot see: a mistake the two share. The oracle restates the device's algorithm (same fold, same table formula, same
+eigenvalues, same operand order), so a wrong table entry or eigenvalue, the centre row of an odd fold or a leaking pad would be equal
+bits on both sides. That the bits are the right answer is shown against a second implementation that shares none of this, the
+transform-free long-double solve of tests/heat2d_reference.py: the oracle and the host step in tests/test_heat2d_reference_cpu.py,
+the device sweep by sweep in tests/test_hip_heat2d_reference.py."""
 import numpy as np
 import pytest
 
