@@ -109,9 +109,22 @@ int mgrit_hip_level_heat2d_forcing_rows(mgrit_hip_engine *e, int lvl, const doub
  * batched products with the full nx x nx Hartley table on the FP64 matrix cores per step. Such a level runs through
  * the Heat2D entry points (copy transfer or the caller's); its Phi is non-linear, so the time-parallel forward solve is never
  * taken (mgrit_hip_block_solve_config with r < 0 leaves it step by step, r > 0 is MGRIT_HIP_EUNSUPPORTED). The methods 'IMPL'
- * and 'CN' (allen_cahn.py:206-228, Newton) have no device form. */
+ * and 'CN' (allen_cahn.py:206-228, Newton): mgrit_hip_level_allencahn2d_newton below. */
 int mgrit_hip_level_allencahn2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld,
                                 double inv_dx2, double inv_eps2, int nu);
+/* AllenCahn with method = 'IMPL' (theta = 1) or 'CN' (theta = 0.5) and linear_solver = 'pcg' (DESIGN.md 3.9): the level of
+ * mgrit_hip_level_allencahn2d, whose Phi is Newton's method on x - fac (L x + r(x) / eps^2) = rhs, fac = theta dt, with every
+ * correction by conjugate gradients preconditioned with (1 + fac nu / eps^2) I - fac L through the Hartley products. Per item: at most
+ * newton_maxiter Newton iterations, stopped before the solve once norm_inf(g) < newton_tol; at most lin_maxiter CG iterations each,
+ * stopped at norm_2(r) <= lin_tol norm_2(g). MGRIT_HIP_EINVAL (with a message that states the bound on the step size) unless nu is
+ * even, theta is 0.5 or 1 and theta * max(dt) * inv_eps2 < 1: only then is the Jacobian positive definite for every iterate.
+ * The host reads one word per Newton iteration and per few CG iterations, so such a level never runs inside a captured graph. */
+int mgrit_hip_level_allencahn2d_newton(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld,
+                                       double inv_dx2, double inv_eps2, int nu, double theta, double newton_tol, int newton_maxiter,
+                                       double lin_tol, int lin_maxiter);
+/* out = { Phi evaluated, Newton iterations, CG iterations, items that ended at newton_maxiter } of a Newton level since the last call
+ * (the call resets the counts; it waits for the engine's stream). */
+int mgrit_hip_newton_stats(mgrit_hip_engine *e, int lvl, int64_t out[4]);
 /* Device slabs u, v, g of Mgrit.create_u_v_g (mgrit.py:840-858); v and g may be NULL on level 0. */
 int mgrit_hip_level_bind(mgrit_hip_engine *e, int lvl, double *u, double *v, double *g);
 /* Hand-over state of forward_solve (mgrit.py:459-486) between the owners of a level (op 5, mgrit.py:468-485): a level whose

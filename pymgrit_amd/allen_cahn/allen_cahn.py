@@ -14,10 +14,21 @@ attributes and helpers. Three time integrators:
     runs on the MI355X: ``device_stepper()`` describes it (kind ``"allencahn2d"``) and the engine applies the four products on the
     FP64 matrix cores (csrc/mgrit_hip_allencahn.inc). ``step`` is the same formula in numpy (plugin path).
 ``method='IMPL'`` and ``method='CN'``
-    Newton's method with a sparse direct solve per iteration, on the host only: ``device_stepper()`` returns ``None`` and a
-    hierarchy that holds such a level runs through ``step`` on the plugin path like any host application. The Newton Jacobian
-    ``I - fac (L + diag((1 - (nu + 1) u^nu) / eps^2))`` changes with the iterate and is not diagonal in any fixed basis, so the
-    fast diagonalisation does not carry over.
+    Newton's method on ``x - fac (L x + r(x) / eps^2) = rhs``, ``fac = theta dt`` (theta = 1 / 0.5). The Newton Jacobian
+    ``J = I - fac (L + diag((1 - (nu + 1) x^nu) / eps^2))`` changes with the iterate and is not diagonal in any fixed basis, so
+    there is no table that inverts it. Two linear solvers:
+
+    ``linear_solver='direct'`` (default, the reference's behaviour)
+        a sparse direct solve (SuperLU) per Newton iteration, on the host only: ``device_stepper()`` returns ``None`` and a
+        hierarchy that holds such a level runs through ``step`` on the plugin path like any host application.
+    ``linear_solver='pcg'``
+        conjugate gradients on the symmetric J, preconditioned by ``P = (1 + fac nu / eps^2) I - fac L`` -- J away from the
+        interface, where ``|u| = 1`` --, which the Hartley tables invert exactly like the IMEX solve. ``lin_tol`` and
+        ``lin_maxiter`` bound the inner iteration. This form has a device description (``theta``, ``newton_tol``, ...) and runs on
+        the MI355X as batched Newton-PCG steps; ``step`` states the same algorithm in numpy. Offered only where
+        the implicit system is uniquely solvable and J positive definite for every iterate: even ``nu`` and
+        ``theta max(dt) / eps^2 < 1`` (L is negative semi-definite and ``1 - (nu + 1) x^nu <= 1``, so ``J >= (1 - fac / eps^2) I``);
+        anything else is refused at construction.
 """
 import numpy as np
 import scipy.sparse as sp
@@ -88,11 +99,12 @@ def periodic_laplacian_eigenvalues(n, dx):
 
 
 class AllenCahn(Application):
-    """Allen-Cahn in 2-D space with periodic boundary conditions (module docstring). ``method='IMEX'`` has a device form;
-    ``'IMPL'`` and ``'CN'`` are host-side Newton solves and send their hierarchy to the plugin path."""
+    """Allen-Cahn in 2-D space with periodic boundary conditions (module docstring). ``method='IMEX'`` has a device form, and so
+    have ``'IMPL'`` and ``'CN'`` with ``linear_solver='pcg'``; with ``'direct'`` they are host-side Newton solves and send their
+    hierarchy to the plugin path."""
 
     def __init__(self, nx=128, nu=2, eps=0.04, newton_maxiter=100, newton_tol=1e-12, lin_tol=1e-12, lin_maxiter=100,
-                 radius=0.25, method='IMPL', *args, **kwargs):
+                 radius=0.25, method='IMPL', linear_solver='direct', *args, **kwargs):
         super().__init__(*args, **kwargs)
         self.nu = nu
         self.eps = eps
@@ -106,6 +118,13 @@ class AllenCahn(Application):
         self.method = method
         if method not in ('IMPL', 'IMEX', 'CN'):
             raise Exception("Unknown method. Choose IMPL (implicit), IMEX (implicit-explicit) or CN (Crank-Nicolson")
+        if linear_solver not in ('direct', 'pcg'):
+            raise Exception("Unknown linear_solver. Choose direct (sparse LU per Newton iteration) or pcg (preconditioned "
+                            "conjugate gradients)")
+        self.linear_solver = linear_solver
+        self.theta = 0.5 if method == 'CN' else 1.0
+        if linear_solver == 'pcg':
+            self._check_pcg()
         self.dx = 1.0 / self.nx
         self.space_disc = self.compute_matrix()
         self.id = sp.eye(self.nx * self.ny)
@@ -158,19 +177,89 @@ class AllenCahn(Application):
             new = new - spsolve(sp.csc_matrix(jac), g)
         return new.reshape(self.nx, self.ny)
 
+    def _check_pcg(self):
+        """linear_solver='pcg' is offered where J is positive definite for every iterate (module docstring), refused elsewhere"""
+        if self.method == 'IMEX':
+            raise Exception("linear_solver='pcg' belongs to the Newton methods IMPL and CN; method='IMEX' has no Newton iteration")
+        if int(self.nu) != self.nu or int(self.nu) < 2 or int(self.nu) % 2 != 0:
+            raise Exception(f"linear_solver='pcg' requires an even nu (nu={self.nu}): for odd nu the Jacobian's diagonal term "
+                            "1 - (nu + 1) u^nu is unbounded above for negative u")
+        fac_max = self.theta * float(np.max(np.diff(self.t))) if len(self.t) > 1 else 0.0
+        if not fac_max / self.eps ** 2 < 1.0:
+            raise Exception(f"linear_solver='pcg' requires theta * dt / eps^2 < 1 on every step, i.e. dt < "
+                            f"{self.eps ** 2 / self.theta:.6g} for method={self.method!r}, eps={self.eps}; the largest step of this "
+                            f"time grid is {fac_max / self.theta:.6g}")
+
+    def _hartley_tables(self):
+        if self._hartley is None:
+            self._hartley = hartley_matrix(self.nx)
+            self._lam = periodic_laplacian_eigenvalues(self.nx, self.dx)
+        return self._hartley, self._lam
+
+    def _lap(self, v):
+        """periodic 5-point Laplacian of the nx x nx grid v, the device kernels' order"""
+        s = ((np.roll(v, 1, 0) + np.roll(v, -1, 0)) + (np.roll(v, 1, 1) + np.roll(v, -1, 1))) - 4.0 * v
+        return s * (1.0 / self.dx ** 2)
+
+    def _step_pcg(self, u, dt):
+        """Newton with preconditioned conjugate gradients (the specification the device step shares)"""
+        T, lam = self._hartley_tables()
+        inv_eps2 = 1.0 / self.eps ** 2
+        fac = self.theta * dt
+        nu = int(self.nu)
+        dinv = 1.0 / ((1.0 + fac * nu * inv_eps2) + fac * (lam[:, None] + lam[None, :]))
+        rhs = u + fac * (self._lap(u) + inv_eps2 * self._reaction(u)) if self.method == 'CN' else u
+        x = u.copy()
+        for _ in range(int(self.newton_maxiter)):
+            g = (x - fac * (self._lap(x) + inv_eps2 * self._reaction(x))) - rhs
+            if np.max(np.abs(g)) < self.newton_tol:
+                break
+            pw = x.copy()
+            for _q in range(1, nu):
+                pw = pw * x
+            d = (1.0 - (nu + 1) * pw) * inv_eps2
+            delta, r, p, rz = np.zeros_like(x), g.copy(), None, 0.0
+            stop = self.lin_tol * np.sqrt(np.sum(g * g))
+            for _k in range(int(self.lin_maxiter)):
+                z = T @ (((T @ r) @ T) * dinv) @ T
+                rz_new = float(np.sum(r * z))
+                p = z if p is None else z + (rz_new / rz) * p
+                rz = rz_new
+                jp = p - fac * (self._lap(p) + d * p)
+                pjp = float(np.sum(p * jp))
+                if not pjp > 0.0:
+                    break
+                alpha = rz / pjp
+                delta = delta + alpha * p
+                r = r - alpha * jp
+                rr = float(np.sum(r * r))
+                if rr == 0.0 or np.sqrt(rr) <= stop:
+                    break
+            x = x - delta
+        return x
+
     def step(self, u_start: VectorAllenCahn2D, t_start: float, t_stop: float) -> VectorAllenCahn2D:
         u = np.asarray(u_start.get_values(), dtype=np.float64)
         dt = t_stop - t_start
         ret = VectorAllenCahn2D(self.nx, self.ny)
-        ret.set_values(self._step_imex(u, dt) if self.method == 'IMEX' else self._step_newton(u, dt))
+        if self.method == 'IMEX':
+            out = self._step_imex(u, dt)
+        else:
+            out = self._step_pcg(u, dt) if self.linear_solver == 'pcg' else self._step_newton(u, dt)
+        ret.set_values(out)
         return ret
 
     def device_stepper(self):
-        """description of Phi for the HIP engine: ``method='IMEX'`` only (``None`` otherwise: plugin path)"""
-        if self.method != 'IMEX':
+        """description of Phi for the HIP engine: ``method='IMEX'``, and the Newton methods with ``linear_solver='pcg'`` (extended by
+        ``theta`` and the solver's parameters); ``None`` otherwise: plugin path"""
+        if self.method != 'IMEX' and self.linear_solver != 'pcg':
             return None
-        return {"kind": "allencahn2d", "n": self.nx * self.ny, "nx": self.nx, "inv_dx2": 1.0 / self.dx ** 2,
-                "inv_eps2": 1.0 / self.eps ** 2, "nu": int(self.nu)}
+        d = {"kind": "allencahn2d", "n": self.nx * self.ny, "nx": self.nx, "inv_dx2": 1.0 / self.dx ** 2,
+             "inv_eps2": 1.0 / self.eps ** 2, "nu": int(self.nu)}
+        if self.method != 'IMEX':
+            d.update(theta=self.theta, newton_tol=float(self.newton_tol), newton_maxiter=int(self.newton_maxiter),
+                     lin_tol=float(self.lin_tol), lin_maxiter=int(self.lin_maxiter))
+        return d
 
     def initial_guess(self):
         initial = VectorAllenCahn2D(nx=self.nx, ny=self.ny)

@@ -191,14 +191,14 @@ class HipBackend:
         """what the Allen-Cahn device path does not cover is refused by name, never run differently"""
         from pymgrit_amd.core.at_mgrit import AtMgrit
         if any(d["kind"] != "allencahn2d" for d in self.desc):
-            raise MgritHipError("Allen-Cahn (IMEX) levels on the HIP engine: every level of the hierarchy must be an AllenCahn "
-                                "application with method='IMEX'")
+            raise MgritHipError("Allen-Cahn levels on the HIP engine: every level of the hierarchy must be an AllenCahn "
+                                "application with method='IMEX', or 'IMPL' / 'CN' with linear_solver='pcg'")
         if mg.comm_time_size > 1:
-            raise MgritHipError("Allen-Cahn (IMEX) levels on the HIP engine: one time rank only")
+            raise MgritHipError("Allen-Cahn levels on the HIP engine: one time rank only")
         if isinstance(mg, AtMgrit):
-            raise MgritHipError("Allen-Cahn (IMEX) levels on the HIP engine: AT-MGRIT is not supported, use Mgrit")
+            raise MgritHipError("Allen-Cahn levels on the HIP engine: AT-MGRIT is not supported, use Mgrit")
         if not mg.global_conv_crit:
-            raise MgritHipError("Allen-Cahn (IMEX) levels on the HIP engine: the global convergence criteria only (conv_crit 0 or 1)")
+            raise MgritHipError("Allen-Cahn levels on the HIP engine: the global convergence criteria only (conv_crit 0 or 1)")
 
     # -- state (mgrit.py:840-858) -------------------------------------------------------------------
     @staticmethod
@@ -264,8 +264,16 @@ class HipBackend:
             check(self.lib.mgrit_hip_level_heat2d_forcing_rows(self.h, engine_lvl, C.c_void_p(rows.data_ptr())))
 
     def _describe_allencahn2d(self, engine_lvl, d, t_local, n, ld):
-        check(self.lib.mgrit_hip_level_allencahn2d(self.h, engine_lvl, t_local.size, _ptr(t_local), int(d["nx"]), ld,
-                                                   float(d["inv_dx2"]), float(d["inv_eps2"]), int(d["nu"])))
+        """IMEX, or -- a description that carries theta -- the Newton-PCG step of IMPL / CN"""
+        common = (self.h, engine_lvl, t_local.size, _ptr(t_local), int(d["nx"]), ld, float(d["inv_dx2"]), float(d["inv_eps2"]), int(d["nu"]))
+        if "theta" in d:      # (through hip_lib: the recorded call sequences of this file's own exports stay as they are)
+            hip_lib.level_allencahn2d_newton(*common, d)
+        else:
+            check(self.lib.mgrit_hip_level_allencahn2d(*common))
+
+    def newton_stats(self, lvl):
+        """counts of an Allen-Cahn Newton-PCG level since the last call (which resets them)"""
+        return hip_lib.newton_stats(self.h, lvl)
 
     _DESCRIBE = {"heat1d": _describe_heat1d, "heat1d_2pts": _describe_heat1d_2pts, "advection1d": _describe_advection1d,
                  "heat2d": _describe_heat2d, "allencahn2d": _describe_allencahn2d}

@@ -46,6 +46,9 @@ EXPORTS = {
     "mgrit_hip_level_heat2d_forcing_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "mgrit_hip_level_allencahn2d": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double,
                                               C.c_int]),
+    "mgrit_hip_level_allencahn2d_newton": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double,
+                                                     C.c_double, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_int]),
+    "mgrit_hip_newton_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "mgrit_hip_level_bind": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgrit_hip_chain_enable": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "mgrit_hip_chain_state_len": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
@@ -157,3 +160,17 @@ def row_permutation(n):
     for probe in (0, n // 2, n - 1):  # the formula must agree with the library
         assert perm[probe] == lib.mgrit_hip_row_position(int(n), int(probe))
     return perm
+
+
+def level_allencahn2d_newton(h, engine_lvl, n_pts, t_ptr, nx, ld, inv_dx2, inv_eps2, nu, d):
+    """describe an Allen-Cahn level whose Phi is the Newton-PCG step; d: the application's description"""
+    check(load().mgrit_hip_level_allencahn2d_newton(h, engine_lvl, n_pts, t_ptr, nx, ld, inv_dx2, inv_eps2, nu, float(d["theta"]),
+                                                    float(d["newton_tol"]), int(d["newton_maxiter"]), float(d["lin_tol"]),
+                                                    int(d["lin_maxiter"])))
+
+
+def newton_stats(h, lvl):
+    """{phi, newton_iterations, cg_iterations, at_newton_maxiter} of a Newton-PCG level since the last call (which resets them)"""
+    out = (C.c_int64 * 4)()
+    check(load().mgrit_hip_newton_stats(h, int(lvl), out))
+    return dict(zip(("phi", "newton_iterations", "cg_iterations", "at_newton_maxiter"), (int(v) for v in out)))

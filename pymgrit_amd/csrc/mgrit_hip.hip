@@ -1618,11 +1618,29 @@ struct H2DHost {
     // Allen-Cahn IMEX (mgrit_hip_allencahn.inc) runs through this route with its own transforms: the full Hartley table [P][P]
     // (P = Mi = Mj = nx padded to 64), lx = ly = the periodic Laplacian's eigenvalues in natural mode order, no rim, no fold
     bool ac = false;
-    double *acT = nullptr, ac_inv_eps2 = 0.0;
+    double *acT = nullptr, ac_inv_eps2 = 0.0, ac_inv_dx2 = 0.0;
     int ac_nu = 0, ac_KP = 0;
     double *Wc0 = nullptr, *Wc1 = nullptr;   // one item each: the work buffers of the coarsest-level chain, which in a planned
                                              // cycle steps on a second stream BESIDE sweeps that apply this level's Phi too (the
                                              // coarse half of the FAS right-hand side of another block of time points)
+    // Allen-Cahn IMPL / CN with Newton-PCG steps (mgrit_hip_level_allencahn2d_newton; acn_* in mgrit_hip_allencahn.inc): the solver's
+    // parameters, the shifted D tables 1/(1 + fac nu/eps^2 + fac (lam_i + lam_j)) per distinct dt (theta is the level's: one table per
+    // (dt, theta)), the work rows of the batched route and of the coarsest-level chain (batches of one), the word the host reads
+    struct Newton {
+        bool on = false;
+        double theta = 1.0, newton_tol = 0.0, lin_tol = 0.0;
+        int newton_maxiter = 0, lin_maxiter = 0;
+        std::map<uint64_t, double *> dinv;
+        struct Work {
+            double *rows = nullptr;   // [ACN_ROWS][cap] items of P x P doubles: x, rhs, r, z, p, Jp, delta and the products' W0, W1
+            int32_t *ints = nullptr;  // [5][cap]
+            double *dbls = nullptr;   // [4][cap] and the partials [cap][ACN_NB][2]
+            size_t cap = 0;
+        } main, chain;
+        unsigned *word = nullptr;            // pinned, device-mapped
+        hipEvent_t ev = nullptr;
+        unsigned long long *tot = nullptr;   // device: the four counts of mgrit_hip_newton_stats
+    } acn;
 };
 // What the two structs own outside the level's allocs and the upload arena (the engine's streams are idle)
 void h2d_blk_release(H2DHost::Blk &k) {
@@ -1633,6 +1651,14 @@ void h2d_release(H2DHost *h) {
     for (double *p : {h->W0, h->W1, h->rowsq, h->Wc0, h->Wc1})
         if (p) (void)hipFree(p);
     h2d_blk_release(h->blk);
+    for (H2DHost::Newton::Work *w : {&h->acn.main, &h->acn.chain}) {
+        if (w->rows) (void)hipFree(w->rows);
+        if (w->ints) (void)hipFree(w->ints);
+        if (w->dbls) (void)hipFree(w->dbls);
+    }
+    if (h->acn.tot) (void)hipFree(h->acn.tot);
+    if (h->acn.word) (void)hipHostFree(h->acn.word);
+    if (h->acn.ev) (void)hipEventDestroy(h->acn.ev);
     delete h;
 }
 
@@ -2543,8 +2569,10 @@ int h2d_reserve(Level &lv, int count) {
     if (h.rowsq) HIP_TRY(hipFree(h.rowsq));
     h.W0 = h.W1 = h.rowsq = nullptr;
     const size_t per = (size_t)h.dev.Mi * h.dev.Mj;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.W0), sizeof(double) * per * count));
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.W1), sizeof(double) * per * count));
+    if (!h.acn.on) {   // (a Newton-PCG level's products run on its own work rows: acn_reserve)
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.W0), sizeof(double) * per * count));
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.W1), sizeof(double) * per * count));
+    }
     HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.rowsq), sizeof(double) * (size_t)h.dev.nx * count));
     h.cap_items = count;
     return 0;
@@ -2583,6 +2611,137 @@ int h2d_dinv(mgrit_hip_engine *e, Level &lv, uint64_t dtbits, double **out) {
     return 0;
 }
 
+// ---- Allen-Cahn Newton-PCG steps --------------------------------------------------------------------------------
+constexpr int ACN_ROWS = 9;   // x, rhs, r, z, p, Jp, delta + the two operands of the preconditioner's products
+// items per Newton batch: the ACN_ROWS work rows of a batch stay within the 2 x H2D_MAX_BATCH items the level's IMEX form reserves
+constexpr int ACN_MAX_BATCH = 2 * H2D_MAX_BATCH / ACN_ROWS;
+static_assert(ACN_MAX_BATCH <= 256, "acn_reduce_kernel: one thread per item of a batch, one workgroup");
+constexpr int ACN_CHECK_EVERY = 4;   // CG iterations between two reads of the batch's "items running" word
+
+BatchPlan batch_slice(const BatchPlan &pl, int off, int count) {
+    BatchPlan s = pl;
+    s.count = count;
+    for (int32_t **p : {&s.d_in, &s.d_step, &s.d_dst, &s.d_a, &s.d_b})
+        if (*p) *p += off;
+    return s;
+}
+
+int acn_reserve(mgrit_hip_engine *e, H2DHost &h, H2DHost::Newton::Work &w, int count) {
+    if ((size_t)count <= w.cap) return 0;
+    HIP_TRY(hipStreamSynchronize(e->stream));   // (the rows about to be freed may still be read)
+    for (void *p : {(void *)w.rows, (void *)w.ints, (void *)w.dbls})
+        if (p) HIP_TRY(hipFree(p));
+    w.rows = nullptr; w.ints = nullptr; w.dbls = nullptr; w.cap = 0;
+    const size_t per = (size_t)h.dev.Mi * h.dev.Mj, n_dbl = (size_t)count * (4 + 2 * ACN_NB);
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&w.rows), sizeof(double) * per * ACN_ROWS * count));
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&w.ints), sizeof(int32_t) * 5 * count));
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&w.dbls), sizeof(double) * n_dbl));
+    // the pads of every work row are zero and stay zero: no kernel writes them, the products map zero pads to zero pads
+    HIP_TRY(hipMemsetAsync(w.rows, 0, sizeof(double) * per * ACN_ROWS * count, e->stream));
+    HIP_TRY(hipMemsetAsync(w.ints, 0, sizeof(int32_t) * 5 * count, e->stream));
+    HIP_TRY(hipMemsetAsync(w.dbls, 0, sizeof(double) * n_dbl, e->stream));
+    w.cap = count;
+    return 0;
+}
+
+int acn_dinv(mgrit_hip_engine *e, Level &lv, uint64_t dtbits, double **out) {
+    H2DHost &h = *lv.h2d;
+    auto it = h.acn.dinv.find(dtbits);
+    if (it != h.acn.dinv.end()) { *out = it->second; return 0; }
+    double dt;
+    std::memcpy(&dt, &dtbits, 8);
+    const double fac = h.acn.theta * dt, shift = 1.0 + fac * (double)h.ac_nu * h.ac_inv_eps2;
+    std::vector<double> tab((size_t)h.dev.Mi * h.dev.Mj, 0.0);
+    for (int a = 0; a < h.dev.nx; ++a)
+        for (int b = 0; b < h.dev.nx; ++b) tab[(size_t)a * h.dev.Mj + b] = 1.0 / (shift + fac * (h.lx[a] + h.ly[b]));
+    double *d = nullptr;
+    int rc = dev_upload(lv, e->stream, tab, &d);
+    if (rc) return rc;
+    h.acn.dinv[dtbits] = d;
+    *out = d;
+    return 0;
+}
+
+// The one word of a batch the host reads: the items still running, written by acn_reduce_kernel into pinned memory in front of the
+// event. A bounded wait (as mgrit_hip_sync_bounded), never an open spin. Allen-Cahn levels never enter planned or captured cycles
+// (HipBackend.plan_allowed / plan_single_block leave "allencahn2d" out), so a host read between two launches is always possible here.
+int acn_running(mgrit_hip_engine *e, H2DHost::Newton &N, unsigned *out) {
+    HIP_TRY(hipEventRecord(N.ev, e->stream));
+    const auto t0 = std::chrono::steady_clock::now();
+    for (;;) {
+        const hipError_t q = hipEventQuery(N.ev);
+        if (q == hipSuccess) break;
+        if (q != hipErrorNotReady) return fail(MGRIT_HIP_EHIP, "hipEventQuery: %s", hipGetErrorString(q));
+        if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 60.0)
+            return fail(MGRIT_HIP_EHIP, "Allen-Cahn Newton step: the batch's kernels did not finish within 60 s");
+        std::this_thread::sleep_for(std::chrono::microseconds(20));   // (as mgrit_hip_sync_bounded: the host core is not held)
+    }
+    *out = *static_cast<volatile unsigned *>(N.word);
+    return 0;
+}
+
+// Phi of one batch of at most ACN_MAX_BATCH items by Newton-PCG; the converged x through the sweep's arithmetic (fin) or left in the
+// work row x (no fin: h2d_points_sumsq reads it there). Launches per batch <= newton_maxiter * (11 lin_maxiter + 4) + 4 by construction.
+int acn_phi_batch(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const double *in_slab, bool chain, const H2DFin *fin) {
+    H2DHost &h = *lv.h2d;
+    H2DHost::Newton &N = h.acn;
+    const H2DDev &H = h.dev;
+    H2DHost::Newton::Work &w = chain ? N.chain : N.main;
+    int rc;
+    if (pl.count < 1) return 0;
+    if (pl.count > ACN_MAX_BATCH) return fail(MGRIT_HIP_EINVAL, "Newton batch of %d items", pl.count);
+    if ((rc = acn_reserve(e, h, w, pl.count))) return rc;
+    double *dinv = nullptr;
+    if ((rc = acn_dinv(e, lv, pl.dtbits, &dinv))) return rc;
+    double dt;
+    std::memcpy(&dt, &pl.dtbits, 8);
+    const int P = H.Mi, n = H.nx * H.nx, nb = std::min(ACN_NB, (n + 255) / 256);
+    const size_t per = (size_t)P * P, slab = per * w.cap;
+    double *const x = w.rows, *const rhs = x + slab, *const r = rhs + slab, *const z = r + slab, *const p = z + slab, *const jp = p + slab,
+                 *const delta = jp + slab, *const W0 = delta + slab, *const W1 = W0 + slab;
+    const size_t c = w.cap;
+    const ACNState S{w.ints, w.ints + c, w.ints + 2 * c, w.ints + 3 * c, w.ints + 4 * c, w.dbls, w.dbls + c, w.dbls + 2 * c, w.dbls + 3 * c,
+                     w.dbls + 4 * c};
+    const ACNPar A{H.nx, P, h.ac_nu, h.ac_inv_dx2, h.ac_inv_eps2, N.theta * dt};
+    const dim3 ge(nb, 1, pl.count), gg(P / 64, P / 64, pl.count), b256(256);
+    const ACPre pre{0.0, 0};
+    const H2DFin none{};
+    hipLaunchKernelGGL(acn_init_kernel, ge, b256, 0, e->stream, A, S, in_slab, pl.d_in, H.ld, x, N.theta == 1.0 ? rhs : nullptr, per);
+    if (N.theta != 1.0) hipLaunchKernelGGL((acn_residual_kernel<true>), ge, b256, 0, e->stream, A, S, x, nullptr, rhs, per);
+    for (int it = 0; it < N.newton_maxiter; ++it) {
+        hipLaunchKernelGGL((acn_residual_kernel<false>), ge, b256, 0, e->stream, A, S, x, rhs, r, per);
+        hipLaunchKernelGGL((acn_reduce_kernel<ACN_R_NEWTON>), dim3(1), b256, 0, e->stream, S, pl.count, nb, N.newton_tol, N.lin_tol,
+                           N.lin_maxiter, N.word);
+        HIP_TRY(hipGetLastError());
+        unsigned running = 0;
+        if ((rc = acn_running(e, N, &running))) return rc;
+        if (!running) break;
+        for (int k = 0; k < N.lin_maxiter; ++k) {
+            hipLaunchKernelGGL((ac_gemm_kernel<AC_WORK_PLAIN>), gg, b256, 0, e->stream, h.acT, P, h.ac_KP, H.nx, r, W1, nullptr, per, S.cg, 0, pre, H, none);
+            hipLaunchKernelGGL((ac_gemm_kernel<AC_WORK_SCALE>), gg, b256, 0, e->stream, h.acT, P, h.ac_KP, H.nx, W1, W0, dinv, per, S.cg, 0, pre, H, none);
+            hipLaunchKernelGGL((ac_gemm_kernel<AC_WORK_PLAIN>), gg, b256, 0, e->stream, h.acT, P, h.ac_KP, H.nx, W0, W1, nullptr, per, S.cg, 0, pre, H, none);
+            hipLaunchKernelGGL((ac_gemm_kernel<AC_WORK_PLAIN>), gg, b256, 0, e->stream, h.acT, P, h.ac_KP, H.nx, W1, z, nullptr, per, S.cg, 0, pre, H, none);
+            hipLaunchKernelGGL(acn_dot_kernel, ge, b256, 0, e->stream, A, S, r, z, per);
+            hipLaunchKernelGGL((acn_reduce_kernel<ACN_R_RZ>), dim3(1), b256, 0, e->stream, S, pl.count, nb, N.newton_tol, N.lin_tol, N.lin_maxiter, N.word);
+            hipLaunchKernelGGL(acn_dir_kernel, ge, b256, 0, e->stream, A, S, z, p, per);
+            hipLaunchKernelGGL(acn_jp_kernel, ge, b256, 0, e->stream, A, S, x, p, jp, per);
+            hipLaunchKernelGGL((acn_reduce_kernel<ACN_R_PJP>), dim3(1), b256, 0, e->stream, S, pl.count, nb, N.newton_tol, N.lin_tol, N.lin_maxiter, N.word);
+            hipLaunchKernelGGL(acn_update_kernel, ge, b256, 0, e->stream, A, S, p, jp, delta, r, per);
+            hipLaunchKernelGGL((acn_reduce_kernel<ACN_R_RR>), dim3(1), b256, 0, e->stream, S, pl.count, nb, N.newton_tol, N.lin_tol, N.lin_maxiter, N.word);
+            HIP_TRY(hipGetLastError());
+            if ((k + 1) % ACN_CHECK_EVERY == 0 && k + 1 < N.lin_maxiter) {   // (after lin_maxiter iterations no item is running)
+                if ((rc = acn_running(e, N, &running))) return rc;
+                if (!running) break;
+            }
+        }
+        hipLaunchKernelGGL(acn_step_kernel, ge, b256, 0, e->stream, A, S, x, delta, per);
+    }
+    if (fin) hipLaunchKernelGGL(acn_finish_kernel, ge, b256, 0, e->stream, A, x, per, H, *fin);
+    hipLaunchKernelGGL(acn_stats_kernel, dim3(1), b256, 0, e->stream, S, pl.count, N.tot);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // U (in W0) = interior of Phi applied to the rows in_slab[plan.d_in[b]] for the steps plan.d_step[b]  (theta > 0)
 // fin: the sweep's arithmetic is applied by the last transform itself (h2d_inv_kernel<true> + h2d_rim_kernel): no epilogue
 // launch, and the interior of U is neither written to nor read from the work slab
@@ -2594,6 +2753,20 @@ int h2d_phi_batch(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const dou
     int rc;
     const size_t per = (size_t)H.Mi * H.Mj;
     chain = chain && pl.count == 1;
+    if (h.acn.on) {   // Newton-PCG: the plan in batches of at most ACN_MAX_BATCH items (without fin the caller passes one such batch)
+        for (int off = 0; off < pl.count; off += ACN_MAX_BATCH) {
+            H2DFin part{};   // the sweep's index lists from the batch's first item on, like the plan's
+            if (fin) {
+                part = *fin;
+                part.dst_idx += off;
+                if (part.a_idx) part.a_idx += off;
+                if (part.b_idx) part.b_idx += off;
+            }
+            if ((rc = acn_phi_batch(e, lv, batch_slice(pl, off, std::min(ACN_MAX_BATCH, pl.count - off)), in_slab, chain, fin ? &part : nullptr)))
+                return rc;
+        }
+        return 0;
+    }
     if (chain && !h.Wc0) {
         HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.Wc0), sizeof(double) * per));
         HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.Wc1), sizeof(double) * per));
@@ -2836,12 +3009,18 @@ int h2d_points_sumsq(mgrit_hip_engine *e, int lvl, RunList *rl, const double *pr
     if ((rc = batch_plans_once(e, lv, rl->points, [&] { return point_items(lv, *rl); }))) return rc;
     for (const BatchPlan &pl : rl->points.plans) {
         if ((rc = h2d_reserve(lv, std::min(H2D_MAX_BATCH, pl.count)))) return rc;
-        if (!prev && (rc = h2d_phi_batch(e, lv, pl, lv.dev.u))) return rc;
         // residual: Phi (in W0) of the row in front against the point's row, the Allen-Cahn instance where the level is one; jump: the
-        // point's row against prev's
+        // point's row against prev's. A Newton-PCG level leaves Phi in its work row x, a batch of at most ACN_MAX_BATCH items at a time
         const auto rowsq = !prev && lv.h2d->ac ? &h2d_rowsq_kernel<true> : &h2d_rowsq_kernel<false>;
-        hipLaunchKernelGGL(rowsq, dim3((H.nx + 63) / 64, pl.count), dim3(64), 0, e->stream, H, lv.h2d->W0, lv.dev.u, prev ? pl.d_dst : pl.d_in,
-                           pl.d_step, prev ? prev : lv.dev.u, pl.d_dst, prev ? H2D_OP_JUMP : H2D_OP_RESIDUAL, lv.h2d->rowsq);
+        const bool newton = !prev && lv.h2d->acn.on;
+        const int part = newton ? ACN_MAX_BATCH : pl.count;
+        for (int off = 0; off < pl.count; off += part) {
+            const BatchPlan sub = batch_slice(pl, off, std::min(part, pl.count - off));
+            if (!prev && (rc = h2d_phi_batch(e, lv, sub, lv.dev.u))) return rc;
+            hipLaunchKernelGGL(rowsq, dim3((H.nx + 63) / 64, sub.count), dim3(64), 0, e->stream, H, newton ? lv.h2d->acn.main.rows : lv.h2d->W0,
+                               lv.dev.u, prev ? sub.d_dst : sub.d_in, sub.d_step, prev ? prev : lv.dev.u, sub.d_dst,
+                               prev ? H2D_OP_JUMP : H2D_OP_RESIDUAL, lv.h2d->rowsq + (size_t)off * H.nx);
+        }
         hipLaunchKernelGGL(h2d_rowsum_kernel, dim3((pl.count + 63) / 64), dim3(64), 0, e->stream, lv.h2d->rowsq, H.nx, pl.count,
                            out, pl.d_b);
         HIP_TRY(hipGetLastError());
@@ -3562,7 +3741,7 @@ int mgrit_hip_level_allencahn2d(mgrit_hip_engine *e, int lvl, int n_pts_local, c
     Level &lv = e->L[lvl];
     H2DHost *h = new H2DHost();
     lv.h2d = h;
-    h->ac = true; h->ac_inv_eps2 = inv_eps2; h->ac_nu = nu;
+    h->ac = true; h->ac_inv_eps2 = inv_eps2; h->ac_inv_dx2 = inv_dx2; h->ac_nu = nu;
     H2DDev &H = h->dev;
     const int P = ((nx + 63) / 64) * 64;
     H.nx = H.ny = H.mi = H.mj = nx; H.Mi = H.Mj = P;
@@ -3592,6 +3771,50 @@ int mgrit_hip_level_allencahn2d(mgrit_hip_engine *e, int lvl, int n_pts_local, c
     lv.dev.n = nx * nx; lv.dev.ld = ld; lv.dev.T = 0; lv.dev.n_pts = n_pts_local; lv.dev.K = 0; lv.dev.stream_rows = 0;
     lv.G = 0;
     lv.set = true;
+    return 0;
+}
+
+int mgrit_hip_level_allencahn2d_newton(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld, double inv_dx2,
+                                       double inv_eps2, int nu, double theta, double newton_tol, int newton_maxiter, double lin_tol,
+                                       int lin_maxiter) {
+    int rc = check_level(e, lvl, false);
+    if (rc) return rc;
+    if (!(theta == 0.5 || theta == 1.0)) return fail(MGRIT_HIP_EINVAL, "Allen-Cahn Newton step: theta must be 1 (IMPL) or 0.5 (CN)");
+    if (nu < 2 || nu % 2 != 0) return fail(MGRIT_HIP_EINVAL, "Allen-Cahn Newton step: nu=%d must be even (the Jacobian is positive definite for even nu only)", nu);
+    if (!(newton_tol >= 0.0) || !(lin_tol >= 0.0) || newton_maxiter < 0 || lin_maxiter < 0)
+        return fail(MGRIT_HIP_EINVAL, "bad Newton / CG parameters (newton_maxiter=%d, lin_maxiter=%d)", newton_maxiter, lin_maxiter);
+    if (no_time_grid(n_pts_local, t_local)) return fail(MGRIT_HIP_EINVAL, "bad arguments");
+    double dt_max = 0.0;
+    for (int i = 1; i < n_pts_local; ++i) dt_max = std::max(dt_max, t_local[i] - t_local[i - 1]);
+    if (!(theta * dt_max * inv_eps2 < 1.0))
+        return fail(MGRIT_HIP_EINVAL, "Allen-Cahn Newton step: theta * dt / eps^2 = %g on the largest step %g; the step needs theta * dt / eps^2 < 1, "
+                    "i.e. dt < %g", theta * dt_max * inv_eps2, dt_max, 1.0 / (theta * inv_eps2));
+    if ((rc = mgrit_hip_level_allencahn2d(e, lvl, n_pts_local, t_local, nx, ld, inv_dx2, inv_eps2, nu))) return rc;
+    // until the Newton state below is complete the level counts as not described: a failed allocation leaves an unusable level
+    // (whose pieces go with the engine), never one that steps as IMEX
+    e->L[lvl].set = false;
+    H2DHost::Newton &N = e->L[lvl].h2d->acn;
+    N.theta = theta; N.newton_tol = newton_tol; N.newton_maxiter = newton_maxiter; N.lin_tol = lin_tol; N.lin_maxiter = lin_maxiter;
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&N.word), sizeof(unsigned), hipHostMallocMapped));
+    *N.word = 0;
+    HIP_TRY(hipEventCreateWithFlags(&N.ev, hipEventDisableTiming));
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&N.tot), 4 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(N.tot, 0, 4 * sizeof(unsigned long long), e->stream));
+    N.on = true;
+    e->L[lvl].set = true;
+    return 0;
+}
+
+int mgrit_hip_newton_stats(mgrit_hip_engine *e, int lvl, int64_t out[4]) {
+    int rc = check_level(e, lvl);
+    if (rc) return rc;
+    if (!out || !e->L[lvl].h2d || !e->L[lvl].h2d->acn.on) return fail(MGRIT_HIP_EINVAL, "level %d is not an Allen-Cahn Newton level", lvl);
+    H2DHost::Newton &N = e->L[lvl].h2d->acn;
+    unsigned long long host[4];
+    HIP_TRY(hipMemcpyAsync(host, N.tot, sizeof(host), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemsetAsync(N.tot, 0, sizeof(host), e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (int k = 0; k < 4; ++k) out[k] = (int64_t)host[k];
     return 0;
 }
 
