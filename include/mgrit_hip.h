@@ -35,7 +35,7 @@ typedef struct mgrit_hip_engine mgrit_hip_engine;
 
 enum { MGRIT_HIP_OK = 0, MGRIT_HIP_EINVAL = -1, MGRIT_HIP_EHIP = -2, MGRIT_HIP_ENODEV = -3, MGRIT_HIP_EUNSUPPORTED = -4 };
 enum { MGRIT_HIP_STEPPER_HEAT1D = 1, MGRIT_HIP_STEPPER_ADVECTION1D = 2, MGRIT_HIP_STEPPER_HEAT2D = 3,
-       MGRIT_HIP_STEPPER_HEAT1D_2PTS = 4, MGRIT_HIP_STEPPER_ALLENCAHN2D = 5 };
+       MGRIT_HIP_STEPPER_HEAT1D_2PTS = 4, MGRIT_HIP_STEPPER_ALLENCAHN2D = 5, MGRIT_HIP_STEPPER_GRAYSCOTT2D = 6 };
 enum { MGRIT_HIP_TRANSFER_COPY = 0, MGRIT_HIP_TRANSFER_HEAT1D = 1, MGRIT_HIP_TRANSFER_PERIODIC1D = 2,
        /* the caller applies restriction / interpolation itself (a user's GridTransfer, reference core/grid_transfer.py:31-55:
           any Python code): mgrit_hip_restrict_u / _fas_rhs / _error_correction / _interpolate refuse the level pair, the FAS
@@ -112,6 +112,14 @@ int mgrit_hip_level_heat2d_forcing_rows(mgrit_hip_engine *e, int lvl, const doub
  * and 'CN' (allen_cahn.py:206-228, Newton): mgrit_hip_level_allencahn2d_newton below. */
 int mgrit_hip_level_allencahn2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld,
                                 double inv_dx2, double inv_eps2, int nu);
+/* GrayScott with method = 'IMEX' (gray_scott/gray_scott.py; reference petsc/gray_scott_2d_petsc.py:84-89, 198-216) on the periodic
+ * nx x nx grid, 4 <= nx <= 2048: a state row holds TWO planes [u | v], nx * nx values each in natural row-major order, n = 2 nx^2,
+ * ld >= 2 nx^2 a multiple of 16. b_u = u + dt (a (1 - u) - u v^2), b_v = v + dt (u v^2 - b v), then (I - dt d_c L) x_c = b_c per species
+ * through the Hartley tables of mgrit_hip_level_allencahn2d with one D table per species, both species in one set of four batched
+ * products. du, dv > 0; a, b finite. Everything said of an Allen-Cahn IMEX level holds: the Heat2D entry points,
+ * the copy transfer (the 2-D spatial transfers refuse such a level), no time-parallel forward solve. Norms run over all 2 nx^2 values. */
+int mgrit_hip_level_grayscott2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld,
+                                double inv_dx2, double du, double dv, double a, double b);
 /* AllenCahn with method = 'IMPL' (theta = 1) or 'CN' (theta = 0.5) and linear_solver = 'pcg' (DESIGN.md 3.9): the level of
  * mgrit_hip_level_allencahn2d, whose Phi is Newton's method on x - fac (L x + r(x) / eps^2) = rhs, fac = theta dt, with every
  * correction by conjugate gradients preconditioned with (1 + fac nu / eps^2) I - fac L through the Hartley products. Per item: at most

@@ -111,7 +111,8 @@ class SlabVectorList:
         return (self[k] for k in range(len(self)))
 
 
-GRID_2D = ("heat2d", "allencahn2d")   # states are whole 2-D grids in natural row-major order; the engine's Heat2D route
+GRID_2D = ("heat2d", "allencahn2d", "grayscott2d")   # states are whole 2-D grids in natural row-major order (Gray-Scott: two of them,
+                                                     # [u plane | v plane]); the engine's Heat2D route
 
 
 class HipBackend:
@@ -130,6 +131,8 @@ class HipBackend:
         self.desc = [p.device_stepper() for p in mg.problem]
         if any(d["kind"] == "allencahn2d" for d in self.desc):
             self._check_allencahn(mg)
+        if any(d["kind"] == "grayscott2d" for d in self.desc):
+            self._check_grayscott(mg)
         self.n = [int(d["n"]) for d in self.desc]
         # 1-D steppers: lane-blocked rows; Heat2D: the nx x ny grid in natural row-major order
         # two-point states: the row is [first | second], each half lane-blocked like a 1-D row of n values
@@ -199,6 +202,22 @@ class HipBackend:
             raise MgritHipError("Allen-Cahn levels on the HIP engine: AT-MGRIT is not supported, use Mgrit")
         if not mg.global_conv_crit:
             raise MgritHipError("Allen-Cahn levels on the HIP engine: the global convergence criteria only (conv_crit 0 or 1)")
+
+    def _check_grayscott(self, mg):
+        """what the Gray-Scott device path does not cover is refused by name, never run differently"""
+        from pymgrit_amd.core.at_mgrit import AtMgrit
+        from pymgrit_amd.core.grid_transfer_copy import GridTransferCopy
+        if any(d["kind"] != "grayscott2d" for d in self.desc) or len({d["nx"] for d in self.desc}) != 1:
+            raise MgritHipError("Gray-Scott levels on the HIP engine: every level of the hierarchy must be a GrayScott application "
+                                "with method='IMEX' on the same nx")
+        if any(type(tr) is not GridTransferCopy for tr in mg.transfer_objects):
+            raise MgritHipError("Gray-Scott levels on the HIP engine: GridTransferCopy only (no spatial coarsening)")
+        if mg.comm_time_size > 1:
+            raise MgritHipError("Gray-Scott levels on the HIP engine: one time rank only")
+        if isinstance(mg, AtMgrit):
+            raise MgritHipError("Gray-Scott levels on the HIP engine: AT-MGRIT is not supported, use Mgrit")
+        if not mg.global_conv_crit:
+            raise MgritHipError("Gray-Scott levels on the HIP engine: the global convergence criteria only (conv_crit 0 or 1)")
 
     # -- state (mgrit.py:840-858) -------------------------------------------------------------------
     @staticmethod
@@ -271,12 +290,16 @@ class HipBackend:
         else:
             check(self.lib.mgrit_hip_level_allencahn2d(*common))
 
+    def _describe_grayscott2d(self, engine_lvl, d, t_local, n, ld):
+        """IMEX, two planes per state (through hip_lib like the Newton form above)"""
+        hip_lib.level_grayscott2d(self.h, engine_lvl, t_local.size, _ptr(t_local), ld, d)
+
     def newton_stats(self, lvl):
         """counts of an Allen-Cahn Newton-PCG level since the last call (which resets them)"""
         return hip_lib.newton_stats(self.h, lvl)
 
     _DESCRIBE = {"heat1d": _describe_heat1d, "heat1d_2pts": _describe_heat1d_2pts, "advection1d": _describe_advection1d,
-                 "heat2d": _describe_heat2d, "allencahn2d": _describe_allencahn2d}
+                 "heat2d": _describe_heat2d, "allencahn2d": _describe_allencahn2d, "grayscott2d": _describe_grayscott2d}
 
     def _describe(self, engine_lvl, lvl, t_local):
         """tell the engine what level engine_lvl is: the stepper of level lvl on the time points t_local"""
@@ -351,7 +374,7 @@ class HipBackend:
         from pymgrit_amd.core.layout import compute_layout
         mg = self.mg
         r = C.c_int(0)
-        if d["kind"] == "allencahn2d":
+        if d["kind"] in ("allencahn2d", "grayscott2d"):
             # non-linear Phi: the time-parallel forward solve superposes block defects and holds for linear steppers only -- the
             # coarsest level is solved step by step whatever options.coarse_solve says
             check(self.lib.mgrit_hip_block_solve_config(self.h, lvl, 0, 1, 0, None, None))

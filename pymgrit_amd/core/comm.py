@@ -639,7 +639,10 @@ def run_loopback_ranks(size, target, timeout=600):
     for t in threads:
         t.join(max(0.0, deadline - time.time()))
     if any(e is not None for e in err):
-        raise [e for e in err if e is not None][0]
+        # a rank that fails aborts the barrier; a rank still waking up inside it then ends with BrokenBarrierError, whichever rank it
+        # is: that is the consequence, the failure itself is what the caller gets
+        raised = [e for e in err if e is not None]
+        raise ([e for e in raised if not isinstance(e, threading.BrokenBarrierError)] or raised)[0]
     if any(t.is_alive() for t in threads):
         raise RuntimeError(f"loopback ranks still running after {timeout} s")
     return world, out

@@ -1563,6 +1563,8 @@ __global__ void interp_rows_kernel(double *__restrict__ uf, int f_ld, int T_f, c
 
 #include "mgrit_hip_allencahn.inc"
 
+#include "mgrit_hip_grayscott.inc"
+
 #include "mgrit_hip_transfer2d.inc"
 
 #include "mgrit_hip_wide.inc"
@@ -1620,6 +1622,11 @@ struct H2DHost {
     bool ac = false;
     double *acT = nullptr, ac_inv_eps2 = 0.0, ac_inv_dx2 = 0.0;
     int ac_nu = 0, ac_KP = 0;
+    // Gray-Scott IMEX (mgrit_hip_grayscott.inc): an Allen-Cahn level in everything above (ac is set as well) whose state row holds two
+    // planes [u | v]: two work slab items per state, a D table per species, the right-hand side from both planes
+    bool gs = false;
+    double gs_du = 0.0, gs_dv = 0.0, gs_a = 0.0, gs_b = 0.0;
+    int comps() const { return gs ? 2 : 1; }   // planes of a state = work slab items of a state
     double *Wc0 = nullptr, *Wc1 = nullptr;   // one item each: the work buffers of the coarsest-level chain, which in a planned
                                              // cycle steps on a second stream BESIDE sweeps that apply this level's Phi too (the
                                              // coarse half of the FAS right-hand side of another block of time points)
@@ -2467,7 +2474,7 @@ using BatchItems = std::vector<std::vector<BatchItem>>;   // the item lists of a
 // Plans of one item list: grouped by key in first-seen key order -- Heat2D / Allen-Cahn: the time-step size of the item's step
 // (one D table per group); wide: one key, so item order is kept (wide_points_sumsq relies on it) --, each group in batches
 int batch_make_plans(mgrit_hip_engine *e, Level &lv, const std::vector<BatchItem> &items, std::vector<BatchPlan> &out) {
-    const size_t max_batch = lv.h2d ? H2D_MAX_BATCH : WIDE_MAX_BATCH;
+    const size_t max_batch = lv.h2d ? H2D_MAX_BATCH / lv.h2d->comps() : WIDE_MAX_BATCH;   // (H2D_MAX_BATCH work slab items a launch)
     std::vector<uint64_t> item_key, keys;
     for (const BatchItem &it : items) {
         item_key.push_back(lv.h2d ? dbl_bits(lv.h2d->dts[it.step]) : 0);
@@ -2568,12 +2575,12 @@ int h2d_reserve(Level &lv, int count) {
     if (h.W1) HIP_TRY(hipFree(h.W1));
     if (h.rowsq) HIP_TRY(hipFree(h.rowsq));
     h.W0 = h.W1 = h.rowsq = nullptr;
-    const size_t per = (size_t)h.dev.Mi * h.dev.Mj;
+    const size_t per = (size_t)h.dev.Mi * h.dev.Mj * h.comps();
     if (!h.acn.on) {   // (a Newton-PCG level's products run on its own work rows: acn_reserve)
         HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.W0), sizeof(double) * per * count));
         HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.W1), sizeof(double) * per * count));
     }
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.rowsq), sizeof(double) * (size_t)h.dev.nx * count));
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.rowsq), sizeof(double) * (size_t)h.dev.nx * h.comps() * count));
     h.cap_items = count;
     return 0;
 }
@@ -2598,8 +2605,15 @@ int h2d_dinv(mgrit_hip_engine *e, Level &lv, uint64_t dtbits, double **out) {
     double dt;
     std::memcpy(&dt, &dtbits, 8);
     const double thdt = h.dev.theta * dt;
-    std::vector<double> tab((size_t)h.dev.Mi * h.dev.Mj, 0.0);   // spectral slot order on both axes, 0 where no mode lives
-    if (h.ac) {   // natural mode order, modes 0 .. nx - 1 on both axes
+    std::vector<double> tab((size_t)h.dev.Mi * h.dev.Mj * h.comps(), 0.0);   // spectral slot order on both axes, 0 where no mode lives
+    if (h.gs) {   // [2][P][P], species u then v: 1 / (1 + (dt d_c) (lam_i + lam_j)), the operand order of GrayScott._dinv
+        for (int c = 0; c < 2; ++c) {
+            const double dtd = dt * (c ? h.gs_dv : h.gs_du);
+            for (int a = 0; a < h.dev.nx; ++a)
+                for (int b = 0; b < h.dev.nx; ++b)
+                    tab[((size_t)c * h.dev.Mi + a) * h.dev.Mj + b] = 1.0 / (1.0 + dtd * (h.lx[a] + h.ly[b]));
+        }
+    } else if (h.ac) {   // natural mode order, modes 0 .. nx - 1 on both axes
         for (int a = 0; a < h.dev.nx; ++a)
             for (int b = 0; b < h.dev.nx; ++b) tab[(size_t)a * h.dev.Mj + b] = 1.0 / (1.0 + dt * (h.lx[a] + h.ly[b]));
     } else h2d_each_mode(h, [&](size_t q, double lam) { tab[q] = 1.0 / (1.0 + thdt * lam); });
@@ -2753,6 +2767,7 @@ int h2d_phi_batch(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const dou
     int rc;
     const size_t per = (size_t)H.Mi * H.Mj;
     chain = chain && pl.count == 1;
+    if (h.gs && 2 * pl.count > H2D_MAX_BATCH) return fail(MGRIT_HIP_EINVAL, "Gray-Scott batch of %d states", pl.count);   // (blockIdx.z, the work slabs)
     if (h.acn.on) {   // Newton-PCG: the plan in batches of at most ACN_MAX_BATCH items (without fin the caller passes one such batch)
         for (int off = 0; off < pl.count; off += ACN_MAX_BATCH) {
             H2DFin part{};   // the sweep's index lists from the batch's first item on, like the plan's
@@ -2768,13 +2783,35 @@ int h2d_phi_batch(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const dou
         return 0;
     }
     if (chain && !h.Wc0) {
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.Wc0), sizeof(double) * per));
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.Wc1), sizeof(double) * per));
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.Wc0), sizeof(double) * per * h.comps()));
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.Wc1), sizeof(double) * per * h.comps()));
     }
     if (!chain && (rc = h2d_reserve(lv, std::min(H2D_MAX_BATCH, std::max(pl.count, 1))))) return rc;
     double *const W0 = chain ? h.Wc0 : h.W0, *const W1 = chain ? h.Wc1 : h.W1;
     double *dinv = nullptr;
     if ((rc = h2d_dinv(e, lv, pl.dtbits, &dinv))) return rc;
+    if (h.gs) {   // Gray-Scott IMEX: the four products once for both species, items 2 b (u) and 2 b + 1 (v) of state b
+        double dt;
+        std::memcpy(&dt, &pl.dtbits, 8);
+        const GSPre pre{dt, h.gs_a, h.gs_b, 0};
+        const int P = H.Mi;
+        const dim3 g(P / 64, P / 64, 2 * pl.count);
+        const H2DFin none{};
+        hipLaunchKernelGGL((gs_gemm_kernel<GS_FIRST>), g, dim3(256), 0, e->stream, h.acT, P, h.ac_KP, H.nx, in_slab, W1, nullptr, per,
+                           pl.d_in, H.ld, pre, H, none);
+        hipLaunchKernelGGL((gs_gemm_kernel<GS_SCALE>), g, dim3(256), 0, e->stream, h.acT, P, h.ac_KP, H.nx, W1, W0, dinv, per, nullptr, 0,
+                           pre, H, none);
+        hipLaunchKernelGGL((gs_gemm_kernel<GS_PLAIN>), g, dim3(256), 0, e->stream, h.acT, P, h.ac_KP, H.nx, W0, W1, nullptr, per, nullptr, 0,
+                           pre, H, none);
+        if (fin)
+            hipLaunchKernelGGL((gs_gemm_kernel<GS_FIN>), g, dim3(256), 0, e->stream, h.acT, P, h.ac_KP, H.nx, W1, W0, nullptr, per, nullptr,
+                               0, pre, H, *fin);
+        else
+            hipLaunchKernelGGL((gs_gemm_kernel<GS_PLAIN>), g, dim3(256), 0, e->stream, h.acT, P, h.ac_KP, H.nx, W1, W0, nullptr, per, nullptr,
+                               0, pre, H, none);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
     if (h.ac) {   // Allen-Cahn IMEX: four products with the full Hartley table, the non-linear right-hand side formed while staging the first
         double dt;
         std::memcpy(&dt, &pl.dtbits, 8);
@@ -3011,17 +3048,20 @@ int h2d_points_sumsq(mgrit_hip_engine *e, int lvl, RunList *rl, const double *pr
         if ((rc = h2d_reserve(lv, std::min(H2D_MAX_BATCH, pl.count)))) return rc;
         // residual: Phi (in W0) of the row in front against the point's row, the Allen-Cahn instance where the level is one; jump: the
         // point's row against prev's. A Newton-PCG level leaves Phi in its work row x, a batch of at most ACN_MAX_BATCH items at a time
-        const auto rowsq = !prev && lv.h2d->ac ? &h2d_rowsq_kernel<true> : &h2d_rowsq_kernel<false>;
+        // Gray-Scott: per (state, plane), a state's 2 nx row sums added u plane first
+        const int nc = lv.h2d->comps();
+        const auto rowsq = lv.h2d->gs ? (prev ? &h2d_rowsq_kernel<false, 2> : &h2d_rowsq_kernel<true, 2>)
+                                      : !prev && lv.h2d->ac ? &h2d_rowsq_kernel<true> : &h2d_rowsq_kernel<false>;
         const bool newton = !prev && lv.h2d->acn.on;
         const int part = newton ? ACN_MAX_BATCH : pl.count;
         for (int off = 0; off < pl.count; off += part) {
             const BatchPlan sub = batch_slice(pl, off, std::min(part, pl.count - off));
             if (!prev && (rc = h2d_phi_batch(e, lv, sub, lv.dev.u))) return rc;
-            hipLaunchKernelGGL(rowsq, dim3((H.nx + 63) / 64, sub.count), dim3(64), 0, e->stream, H, newton ? lv.h2d->acn.main.rows : lv.h2d->W0,
+            hipLaunchKernelGGL(rowsq, dim3((H.nx + 63) / 64, nc * sub.count), dim3(64), 0, e->stream, H, newton ? lv.h2d->acn.main.rows : lv.h2d->W0,
                                lv.dev.u, prev ? sub.d_dst : sub.d_in, sub.d_step, prev ? prev : lv.dev.u, sub.d_dst,
                                prev ? H2D_OP_JUMP : H2D_OP_RESIDUAL, lv.h2d->rowsq + (size_t)off * H.nx);
         }
-        hipLaunchKernelGGL(h2d_rowsum_kernel, dim3((pl.count + 63) / 64), dim3(64), 0, e->stream, lv.h2d->rowsq, H.nx, pl.count,
+        hipLaunchKernelGGL(h2d_rowsum_kernel, dim3((pl.count + 63) / 64), dim3(64), 0, e->stream, lv.h2d->rowsq, nc * H.nx, pl.count,
                            out, pl.d_b);
         HIP_TRY(hipGetLastError());
     }
@@ -3505,6 +3545,38 @@ int blk_config(mgrit_hip_engine *e, int lvl, int r, int first_real, int has_succ
     return 0;
 }
 
+// What the levels on the periodic nx x nx grid share (Allen-Cahn, Gray-Scott): the padded sizes, the step sizes, the full Hartley table
+// and the eigenvalues of the periodic 5-point Laplacian / dx^2 in natural mode order
+int periodic2d_tables(mgrit_hip_engine *e, Level &lv, H2DHost *h, int n_pts_local, const double *t_local, int nx, int ld, double inv_dx2) {
+    int rc;
+    H2DDev &H = h->dev;
+    const int P = ((nx + 63) / 64) * 64;
+    H.nx = H.ny = H.mi = H.mj = nx; H.Mi = H.Mj = P;
+    h->HPx = h->HPy = P / 2;
+    h->ac_KP = ((nx + H2D_BK - 1) / H2D_BK) * H2D_BK;
+    H.K = 0; H.n_pts = n_pts_local; H.ld = ld; H.fx = H.fy = 0.0; H.theta = 1.0; H.has_w = 0;
+    h->dts = step_sizes(n_pts_local, t_local);
+    // Hartley table (the angle reduced exactly: (i k) mod nx) and the eigenvalues of the periodic 5-point Laplacian
+    std::vector<double> tab((size_t)P * P, 0.0);
+    const long double two_pi = 6.283185307179586476925286766559L, s = 1.0L / sqrtl((long double)nx);
+    for (int i = 0; i < nx; ++i)
+        for (int k = 0; k < nx; ++k) {
+            const long double a = two_pi * (long double)(((long long)i * k) % nx) / (long double)nx;
+            tab[(size_t)i * P + k] = (double)((cosl(a) + sinl(a)) * s);
+        }
+    h->lx.assign(P, 0.0);
+    for (int k = 0; k < nx; ++k) {
+        const long double sn = sinl(two_pi * 0.5L * (long double)k / (long double)nx);
+        h->lx[k] = (double)(4.0L * (long double)inv_dx2 * sn * sn);
+    }
+    h->ly = h->lx;
+    double *d_dt;
+    if ((rc = dev_upload(lv, e->stream, tab, &h->acT))) return rc;
+    if ((rc = dev_upload(lv, e->stream, h->dts, &d_dt))) return rc;
+    H.dt = d_dt;
+    return 0;
+}
+
 }  // namespace
 
 // ===============================================================================================================
@@ -3742,33 +3814,33 @@ int mgrit_hip_level_allencahn2d(mgrit_hip_engine *e, int lvl, int n_pts_local, c
     H2DHost *h = new H2DHost();
     lv.h2d = h;
     h->ac = true; h->ac_inv_eps2 = inv_eps2; h->ac_inv_dx2 = inv_dx2; h->ac_nu = nu;
-    H2DDev &H = h->dev;
-    const int P = ((nx + 63) / 64) * 64;
-    H.nx = H.ny = H.mi = H.mj = nx; H.Mi = H.Mj = P;
-    h->HPx = h->HPy = P / 2;
-    h->ac_KP = ((nx + H2D_BK - 1) / H2D_BK) * H2D_BK;
-    H.K = 0; H.n_pts = n_pts_local; H.ld = ld; H.fx = H.fy = 0.0; H.theta = 1.0; H.has_w = 0;
-    h->dts = step_sizes(n_pts_local, t_local);
-    // Hartley table (the angle reduced exactly: (i k) mod nx) and the eigenvalues of the periodic 5-point Laplacian
-    std::vector<double> tab((size_t)P * P, 0.0);
-    const long double two_pi = 6.283185307179586476925286766559L, s = 1.0L / sqrtl((long double)nx);
-    for (int i = 0; i < nx; ++i)
-        for (int k = 0; k < nx; ++k) {
-            const long double a = two_pi * (long double)(((long long)i * k) % nx) / (long double)nx;
-            tab[(size_t)i * P + k] = (double)((cosl(a) + sinl(a)) * s);
-        }
-    h->lx.assign(P, 0.0);
-    for (int k = 0; k < nx; ++k) {
-        const long double sn = sinl(two_pi * 0.5L * (long double)k / (long double)nx);
-        h->lx[k] = (double)(4.0L * (long double)inv_dx2 * sn * sn);
-    }
-    h->ly = h->lx;
-    double *d_dt;
-    if ((rc = dev_upload(lv, e->stream, tab, &h->acT))) return rc;
-    if ((rc = dev_upload(lv, e->stream, h->dts, &d_dt))) return rc;
-    H.dt = d_dt;
+    if ((rc = periodic2d_tables(e, lv, h, n_pts_local, t_local, nx, ld, inv_dx2))) return rc;
     lv.dev.kind = MGRIT_HIP_STEPPER_ALLENCAHN2D;
     lv.dev.n = nx * nx; lv.dev.ld = ld; lv.dev.T = 0; lv.dev.n_pts = n_pts_local; lv.dev.K = 0; lv.dev.stream_rows = 0;
+    lv.G = 0;
+    lv.set = true;
+    return 0;
+}
+
+int mgrit_hip_level_grayscott2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld, double inv_dx2,
+                                double du, double dv, double a, double b) {
+    int rc = check_level(e, lvl, false);
+    if (rc) return rc;
+    if (nx < 4 || nx > 2048) return fail(MGRIT_HIP_EUNSUPPORTED, "Gray-Scott grid %dx%d outside [4,2048]^2", nx, nx);
+    if (ld < 2 * nx * nx || (ld % 16) != 0) return fail(MGRIT_HIP_EINVAL, "ld=%d must be a multiple of 16 and >= 2*nx*nx=%d", ld, 2 * nx * nx);
+    if (!(inv_dx2 > 0.0) || !(du > 0.0) || !(dv > 0.0) || !std::isfinite(inv_dx2) || !std::isfinite(du) || !std::isfinite(dv) ||
+        !std::isfinite(a) || !std::isfinite(b))
+        return fail(MGRIT_HIP_EINVAL, "bad Gray-Scott parameters (du=%g, dv=%g must be positive, a=%g, b=%g finite)", du, dv, a, b);
+    if (no_time_grid(n_pts_local, t_local)) return fail(MGRIT_HIP_EINVAL, "bad arguments");
+    if ((rc = level_fresh(e, lvl))) return rc;
+    Level &lv = e->L[lvl];
+    H2DHost *h = new H2DHost();
+    lv.h2d = h;
+    h->ac = true; h->ac_inv_dx2 = inv_dx2;
+    h->gs = true; h->gs_du = du; h->gs_dv = dv; h->gs_a = a; h->gs_b = b;
+    if ((rc = periodic2d_tables(e, lv, h, n_pts_local, t_local, nx, ld, inv_dx2))) return rc;
+    lv.dev.kind = MGRIT_HIP_STEPPER_GRAYSCOTT2D;
+    lv.dev.n = 2 * nx * nx; lv.dev.ld = ld; lv.dev.T = 0; lv.dev.n_pts = n_pts_local; lv.dev.K = 0; lv.dev.stream_rows = 0;
     lv.G = 0;
     lv.set = true;
     return 0;
@@ -3954,7 +4026,7 @@ int mgrit_hip_level_transfer(mgrit_hip_engine *e, int lvl, int kind) {
     } else if (kind == MGRIT_HIP_TRANSFER_HEAT2D || kind == MGRIT_HIP_TRANSFER_PERIODIC2D) {
         const H2DHost *hf = e->L[lvl].h2d, *hc = e->L[lvl + 1].h2d;
         const bool per = kind == MGRIT_HIP_TRANSFER_PERIODIC2D;
-        if (!hf || !hc || hf->ac != per || hc->ac != per)
+        if (!hf || !hc || hf->ac != per || hc->ac != per || hf->gs || hc->gs)
             return fail(MGRIT_HIP_EUNSUPPORTED, per ? "the periodic 2-D transfer joins two Allen-Cahn levels" : "the Heat2D transfer joins two Heat2D levels");
         const int off = per ? 0 : 1;
         if (2 * hc->dev.nx - off != hf->dev.nx || 2 * hc->dev.ny - off != hf->dev.ny)

@@ -53,20 +53,30 @@ constexpr int H2D_BK = 32, H2D_LDT = 80;
 // 2 x 8 B per point of HBM traffic falls away. The interior starts one point into a row, so these loads are 8-byte aligned only.
 typedef double d2u_t __attribute__((ext_vector_type(2), aligned(8)));
 // PRE (with GRID): a pointwise map applied to every value staged from the state row before it enters the product -- the identity for
-// Heat2D, the non-linear right-hand side of the Allen-Cahn IMEX step (mgrit_hip_allencahn.inc)
-struct H2DIdentity { __device__ __forceinline__ double operator()(double x) const { return x; } };
+// Heat2D, the non-linear right-hand side of the Allen-Cahn IMEX step (mgrit_hip_allencahn.inc). PRE::operands == 2: the map reads a
+// second value at the staged point, pre(x, y) with y from Bb2 -- the same point of another plane of the state row, loaded beside x
+// with the same clamps (Gray-Scott, mgrit_hip_grayscott.inc: the other species). For operands == 1 Bb2 is never read and the
+// instances compile to what they are without it (DESIGN.md 3.11).
+struct H2DIdentity {
+    static constexpr int operands = 1;
+    __device__ __forceinline__ double operator()(double x) const { return x; }
+};
 template <bool FOLD, bool GRID = false, class PRE = H2DIdentity>
 __device__ __forceinline__ void h2d_kloop(d4_t (&acc)[2][2], double *smem, const double *__restrict__ A, int lda, int m0,
                                           const double *__restrict__ Bb, int N, int n0, int KP, int m_real, int hO, double sign,
-                                          int tid, int lane, int w, int n_real = 0, PRE pre = PRE()) {
+                                          int tid, int lane, int w, int n_real = 0, PRE pre = PRE(),
+                                          const double *__restrict__ Bb2 = nullptr) {
+    constexpr bool TWO = PRE::operands == 2;
+    static_assert(!TWO || (GRID && !FOLD), "a two-operand map is applied to values staged from a state row");
     double(*As)[H2D_LDT] = reinterpret_cast<double(*)[H2D_LDT]>(smem);
     double(*Bs)[H2D_LDT] = reinterpret_cast<double(*)[H2D_LDT]>(smem + H2D_BK * H2D_LDT);
     const int wm = (w & 1) * 32, wn = (w >> 1) * 32;
     const int lr = lane & 15, lk = lane >> 4;
     const int sr = tid >> 5, sc = (tid & 31) * 2;
-    d2_t ra[H2D_BK / 8], rb[H2D_BK / 8], rc[H2D_BK / 8];
+    d2_t ra[H2D_BK / 8], rb[H2D_BK / 8], rc[H2D_BK / 8], rb2[H2D_BK / 8];
     const bool cv0 = !GRID || n0 + sc < n_real, cv1 = !GRID || n0 + sc + 1 < n_real;   // (a valid column's pair stays inside its row)
     const double *Ap = A + (size_t)sr * lda + m0 + sc, *Bp = Bb + (cv0 ? n0 + sc : 0);
+    const double *Bp2 = TWO ? Bb2 + (cv0 ? n0 + sc : 0) : nullptr;
     auto ldb = [&](const double *q) -> d2_t {
         if (GRID) return (d2_t)*reinterpret_cast<const d2u_t *>(q);
         return *reinterpret_cast<const d2_t *>(q);
@@ -77,6 +87,7 @@ __device__ __forceinline__ void h2d_kloop(d4_t (&acc)[2][2], double *smem, const
             const int k = k0 + sr + 8 * h;
             ra[h] = *reinterpret_cast<const d2_t *>(Ap + (size_t)(k0 + 8 * h) * lda);
             rb[h] = ldb(Bp + (size_t)(GRID && k >= m_real ? m_real - 1 : k) * N);
+            if constexpr (TWO) rb2[h] = ldb(Bp2 + (size_t)(k >= m_real ? m_real - 1 : k) * N);
             if (FOLD) {
                 const int km = m_real - 1 - k;
                 rc[h] = ldb(Bp + (size_t)(km > 0 ? km : 0) * N);
@@ -90,8 +101,13 @@ __device__ __forceinline__ void h2d_kloop(d4_t (&acc)[2][2], double *smem, const
             d2_t bv = rb[h];
             if (GRID) {
                 const bool rv = (k0 + sr + 8 * h) < m_real;
-                bv.x = rv && cv0 ? pre(bv.x) : 0.0;
-                bv.y = rv && cv1 ? pre(bv.y) : 0.0;
+                if constexpr (TWO) {
+                    bv.x = rv && cv0 ? pre(bv.x, rb2[h].x) : 0.0;
+                    bv.y = rv && cv1 ? pre(bv.y, rb2[h].y) : 0.0;
+                } else {
+                    bv.x = rv && cv0 ? pre(bv.x) : 0.0;
+                    bv.y = rv && cv1 ? pre(bv.y) : 0.0;
+                }
             }
             if (FOLD) {
                 const double mult = (k0 + sr + 8 * h) < hO ? sign : 0.0;
@@ -362,16 +378,20 @@ __global__ void h2d_rim_kernel(H2DDev H, H2DFin F) {
 // per row reading its row on its own, 64 rows 4 KB apart per load instruction, the residual check of config 4 took 18.4 us per
 // point against 10.5 for the Phi alone.)
 // FULL: U holds Phi on the whole grid, no rim (Allen-Cahn: periodic)
-template <bool FULL>
+// NC > 1 (Gray-Scott): a state row is NC planes of nx x ny values and blockIdx.y runs over (state, plane), the plane fastest -- the work
+// slab item of U and the rows of rowsq follow blockIdx.y, so h2d_rowsum_kernel over NC * nx rows adds a state's planes in order
+template <bool FULL, int NC = 1>
 __global__ void __launch_bounds__(64) h2d_rowsq_kernel(H2DDev H, const double *__restrict__ U, const double *__restrict__ in_slab,
                                                        const int32_t *__restrict__ in_idx, const int32_t *__restrict__ step_idx,
                                                        const double *__restrict__ cmp_slab, const int32_t *__restrict__ cmp_idx, int op,
                                                        double *__restrict__ rowsq) {
     __shared__ double tile[64][65];
     const int b = blockIdx.y, r0 = blockIdx.x * 64, lane = threadIdx.x;
-    const double *uin = in_slab + (size_t)in_idx[b] * H.ld;
-    const double *cmp = cmp_slab + (size_t)cmp_idx[b] * H.ld;
-    const int step = step_idx[b];
+    const int st = NC == 1 ? b : b / NC;                                         // the state of the batch
+    const size_t plane = NC == 1 ? 0 : (size_t)(b % NC) * H.nx * H.ny;
+    const double *uin = in_slab + (size_t)in_idx[st] * H.ld + plane;
+    const double *cmp = cmp_slab + (size_t)cmp_idx[st] * H.ld + plane;
+    const int step = step_idx[st];
     double acc = 0.0;
     for (int c0 = 0; c0 < H.ny; c0 += 64) {
         const int gj = c0 + lane;

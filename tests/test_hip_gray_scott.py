@@ -1,0 +1,389 @@
+"""GPU tests of the Gray-Scott IMEX device path (csrc/mgrit_hip_grayscott.inc): every sweep of the device hierarchy
+against the SAME hierarchy on the plugin path over ``ReferenceGrayScott`` (tests/gray_scott_reference.py), whose step is a
+transform-free solve of (I - dt d_c Lap) x_c = b_c refined in long double. It shares neither the Hartley table nor the eigenvalues nor
+the reaction term's code with the device or the host step. States are fresh random, u in [0, 1], v in [0, 0.5]: the planes differ and
+are not symmetric in (i, j), so swapped planes, swapped tables or a transposed product miss by orders of magnitude. What the cases are
+chosen for:
+
+  a. the size edges of the tile product: nx = 4 (smallest grid), 33 / 97 (just past a K step of 32), 96 (KP = 96 < P = 128), 129 (just
+     past a tile of 64); the default du = 100 dv, and one case with du = dv;
+  b. several step sizes on one level (nx = 20, 66): batch_make_plans groups a sweep's items by the bit pattern of dt, one pair of D
+     tables per group; coarsening 4 puts F-points of one interval into different groups;
+  c. a dt group of more than one batch: a launch holds at most H2D_MAX_BATCH = 1024 work slab items = 512 states, so 513 F-points of
+     one exact (dyadic) step are a batch of 512 and one of 1, blockIdx.z restarting and the index arrays offset per plan. The test
+     asserts the group size it relies on;
+  d. one Phi at nx = 256, 257 (P = 256, 320);
+  e. the fixed point (u, v) = (1, 0) and a constant state: mode 0, D = 1, Phi = b.
+
+Tolerances, nothing in them measured on the device (test_gray_scott_cpu.py states the per-species bound):
+  per Phi:     sqrt(tol_u^2 + tol_v^2),  tol_c = ((4 nx + 8) + 1) EPS bnorm_c  -- (4 nx + 8) EPS bnorm_c for the device's four products
+               and pointwise work, EPS bnorm_c for the rounding of the reference to float64; the species are independent solves, a
+               state's error is the two combined in quadrature. bnorm_c bounds norm_F(b_c) from the input rows with the level's largest
+               dt:  bnorm_u = norm_F(|u| + dt (|a| |1 - u| + |u| v^2)),  bnorm_v = norm_F(|v| + dt (|u| v^2 + |b| |v|)), the largest row;
+  + SLACK      8 EPS * 3 * the largest row norm involved, for the sweep's own arithmetic (a handful of additions per value);
+  fas_residual: the sum over the two levels;
+  chained steps (forward_solve, F-relaxation over 3 F-points): both sides apply Phi to their own previous result, so
+               e_k = Lip_k e_(k-1) + the step's per-Phi term + SLACK.  Phi = (solve) o (pointwise map); each solve is a contraction
+               (all eigenvalues of I - dt d_c Lap are >= 1), and the pointwise map (u, v) -> (b_u, b_v) has the Jacobian
+                   [[1 - dt (a + v^2), -2 dt u v], [dt v^2, 1 + dt (2 u v - b)]],
+               whose Frobenius norm bounds its 2-norm at every point. With R = max|state| of the step's input,
+                   Lip_k = norm_F([[1 + dt (|a| + R^2), 2 dt R^2], [dt R^2, 1 + dt (2 R^2 + |b|)]]).
+Every comparison covers all rows of a list. Each sweep prints its worst error / allowed ("RATIO" lines). Largest ratio of the first
+run on an MI355X: see DESIGN.md 3.11.
+"""
+import collections
+import ctypes as C
+import types
+
+import numpy as np
+import pytest
+
+import cases
+from gray_scott_reference import ReferenceGrayScott
+from test_hip_allen_cahn import _compare, _host_state, _lists, _row_norm, _set_states
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+EPS = cases.EPS
+ALL_SWEEPS = ("f_relax", "c_relax", "fas_residual", "forward_solve", "error_correction", "compute_residual")
+STORED_STATE_SWEEPS = ("f_relax", "c_relax", "fas_residual", "compute_residual")
+
+
+def _uniform(nts, t_stop):
+    return [dict(t_start=0, t_stop=t_stop, nt=nt) for nt in nts]
+
+
+def _intervals(ts):
+    return [dict(t_interval=np.asarray(t)) for t in ts]
+
+
+def _t_sweep(nx):
+    """[0, T] with 16 fine steps of r = dt du / dx^2 = 2 (du = 1, L = 2): r = 8 on the coarsest of the three levels; dt = 0.5 at nx = 4"""
+    return 16 * 2.0 * (2.0 / nx) ** 2
+
+
+def _pair(nx, grids, par=None, **opts):
+    """(device Mgrit, plugin Mgrit over ReferenceGrayScott) on the same hierarchy"""
+    from pymgrit_amd import GrayScott, Mgrit
+    opts.setdefault("nested_iteration", False)
+    par = par or {}
+    dev = Mgrit([GrayScott(nx=nx, method="IMEX", **par, **g) for g in grids], logging_lvl=30, **opts)
+    ref = Mgrit([ReferenceGrayScott(nx=nx, method="IMEX", **par, **g) for g in grids], logging_lvl=30, **opts)
+    assert type(dev.backend).__name__ == "HipBackend" and type(ref.backend).__name__ == "PluginBackend"
+    for a, b in zip(dev.t, ref.t):
+        assert np.array_equal(a, b)
+    return dev, ref
+
+
+def _random_states(ref, seed):
+    """per list and level [n_pts][2 nx^2]: u plane uniform in [0, 1], v plane uniform in [0, 0.5]"""
+    rng = np.random.default_rng(seed)
+    out = {}
+    for lvl in range(ref.lvl_max):
+        for name, lst in _lists(ref, lvl):
+            n = ref.problem[lvl].nx ** 2
+            out[(name, lvl)] = np.concatenate((rng.uniform(0.0, 1.0, size=(len(lst), n)), rng.uniform(0.0, 0.5, size=(len(lst), n))), axis=1)
+    return out
+
+
+def _phi_term(app, rows, dt):
+    """one device evaluation and the reference's rounding, the two species in quadrature (module docstring)"""
+    rows = np.abs(np.atleast_2d(rows))
+    n = app.nx ** 2
+    u, v = rows[:, :n], rows[:, n:]
+    bu = float(np.max(np.linalg.norm(u + dt * (abs(app.a) * np.abs(1.0 - u) + u * v * v), axis=1)))
+    bv = float(np.max(np.linalg.norm(v + dt * (u * v * v + abs(app.b) * v), axis=1)))
+    return ((4 * app.nx + 8) + 1) * EPS * float(np.hypot(bu, bv))
+
+
+def _tol(ref, lvl, rows):
+    return _phi_term(ref.problem[lvl], rows, float(np.max(np.diff(ref.t[lvl]))))
+
+
+def _lip(app, dt, rows):
+    R2 = float(np.abs(rows).max()) ** 2
+    return float(np.linalg.norm([[1 + dt * (abs(app.a) + R2), 2 * dt * R2], [dt * R2, 1 + dt * (2 * R2 + abs(app.b))]]))
+
+
+def _chain(app, t, inputs, slack):
+    """e_k = Lip_k e_(k-1) + per-Phi term + SLACK over the steps t[k-1] -> t[k], inputs[k-1] the reference's input of step k"""
+    e = 0.0
+    for k in range(1, len(t)):
+        dt = t[k] - t[k - 1]
+        e = _lip(app, dt, inputs[k - 1]) * e + _phi_term(app, inputs[k - 1], dt) + slack
+    return e
+
+
+def _ratio(record, what, err, allowed):
+    record[what] = max(record.get(what, 0.0), err / allowed if allowed > 0.0 else 0.0)
+
+
+def _run_sweeps(dev, ref, w, seed, sweeps, levels=None, record=None):
+    """the named sweeps on fresh random states, each against the reference hierarchy"""
+    record = {} if record is None else record
+    top = dev.lvl_max - 1
+    levels = list(range(top)) if levels is None else levels
+    seeds = iter(range(seed, seed + 1000))
+
+    def fresh():
+        st = _random_states(ref, next(seeds))
+        _set_states(dev, ref, st)
+        return st
+
+    for lvl in levels:
+        app = ref.problem[lvl]
+        if "f_relax" in sweeps:
+            st = fresh()
+            slack = 8 * EPS * 3 * _row_norm(*st.values())
+            dev.f_relax(lvl); ref.f_relax(lvl)
+            cpts = [int(i) for i in np.asarray(ref.cpts[lvl])]
+            if len(cpts) < 2 or max(np.diff(cpts)) <= 2:      # every Phi acts on a stored state
+                allowed = _tol(ref, lvl, st[("u", lvl)]) + slack
+            else:                                             # F-points of one interval are chained
+                after, t, allowed = _host_state(ref, "u", lvl), ref.t[lvl], 0.0
+                for a, z in zip(cpts[:-1], cpts[1:]):
+                    allowed = max(allowed, _chain(app, t[a:z], [st[("u", lvl)][a]] + [after[i] for i in range(a + 1, z - 1)], slack))
+            _ratio(record, "f_relax", _compare(dev, ref, lvl, allowed, "f_relax"), allowed)
+        if "c_relax" in sweeps:
+            st = fresh()
+            slack = 8 * EPS * 3 * _row_norm(*st.values())
+            dev.c_relax(lvl); ref.c_relax(lvl)
+            allowed = max(1.0, w) * _tol(ref, lvl, st[("u", lvl)]) + slack * (abs(w) + abs(1 - w))
+            _ratio(record, f"c_relax w={w}", _compare(dev, ref, lvl, allowed, f"c_relax w={w}"), allowed)
+        if "fas_residual" in sweeps:
+            st = fresh()
+            slack = 8 * EPS * 3 * _row_norm(*st.values())
+            dev.fas_residual(lvl); ref.fas_residual(lvl)
+            # g of the coarse level: one Phi of the fine level, one of the coarse level on restricted (= copied) rows of the fine u
+            allowed = _tol(ref, lvl, st[("u", lvl)]) + _tol(ref, lvl + 1, st[("u", lvl)]) + slack
+            _ratio(record, "fas_residual", _compare(dev, ref, lvl + 1, allowed, "fas_residual"), allowed)
+    if "forward_solve" in sweeps:
+        st = fresh()
+        dev.forward_solve(top); ref.forward_solve(top)
+        uh = _host_state(ref, "u", top)
+        allowed = _chain(ref.problem[top], ref.t[top], uh, 8 * EPS * 3 * _row_norm(uh, st[("g", top)]))
+        _ratio(record, "forward_solve", _compare(dev, ref, top, allowed, "forward_solve"), allowed)
+    if "error_correction" in sweeps:
+        for lvl in reversed(levels):
+            st = fresh()
+            dev.error_correction(lvl); ref.error_correction(lvl)
+            allowed = 8 * EPS * 3 * _row_norm(*st.values())
+            _ratio(record, "error_correction", _compare(dev, ref, lvl, allowed, "error_correction"), allowed)
+    if "compute_residual" in sweeps:
+        st = fresh()
+        n = ref.problem[0].nx ** 2
+        got, want = np.asarray(dev.compute_residual()), np.asarray(ref.compute_residual())
+        # the norm of one point: its values' errors, and (2 nx^2 + 2) EPS relative for the sum of 2 nx^2 squares and the root
+        allowed = _tol(ref, 0, st[("u", 0)]) + 8 * EPS * 3 * _row_norm(st[("u", 0)]) + (2 * n + 2) * EPS * want
+        assert got.shape == want.shape and got.size == len(ref.cpts[0]) - 1
+        assert np.all(np.abs(got - want) <= allowed), np.abs(got - want).max()
+        _ratio(record, "compute_residual", float(np.max(np.abs(got - want) / allowed)), 1.0)
+    return record
+
+
+def _report(test, record):
+    for what, r in record.items():
+        print(f"RATIO {test} {what}: worst error/allowed {r:.4f}")
+
+
+# ---- a. every sweep at the size edges of the tile product --------------------------------------------------------------------------
+@pytest.mark.parametrize("nx", [4, 33, 96, 97, 129])
+def test_every_sweep_at_the_size_edges(nx):
+    assert torch.cuda.is_available()
+    record = {}
+    for w, sweeps in ((1.0, ALL_SWEEPS), (1.3, ("c_relax",))):      # (the weight enters the C-relaxation only)
+        dev, ref = _pair(nx, _uniform((17, 9, 5), _t_sweep(nx)), weight_c=w)
+        assert dev.problem[0].du == 100 * dev.problem[0].dv
+        _run_sweeps(dev, ref, w, 100 * nx + (7 if w != 1.0 else 0), sweeps, record=record)
+    _report(f"size_edges[nx={nx}]", record)
+
+
+def test_every_sweep_with_equal_diffusion_coefficients():
+    """du = dv: with the default du = 100 dv beside it (above), a table taken for the wrong species shows in one of the two"""
+    assert torch.cuda.is_available()
+    nx, record = 33, {}
+    for w, sweeps in ((1.0, ALL_SWEEPS), (1.3, ("c_relax",))):
+        dev, ref = _pair(nx, _uniform((17, 9, 5), _t_sweep(nx)), par=dict(du=0.5, dv=0.5, a=0.04, b=0.1), weight_c=w)
+        _run_sweeps(dev, ref, w, 4242 + (7 if w != 1.0 else 0), sweeps, record=record)
+    _report("equal_diffusion[nx=33]", record)
+
+
+# ---- b. several step sizes per level -----------------------------------------------------------------------------------------------
+RAGGED = np.concatenate(([0.0], np.cumsum(np.array([1, 1, 1.5, .5, 2, 1, 1, .75, 1, 1, 1, 1.25, 3, 1, 1, 1]))))
+
+
+def _ragged(nx, grid):
+    t = RAGGED * 0.5 * (2.0 / nx) ** 2      # unit step: r = dt du / dx^2 = 0.5; at most 6.25 units per coarse step
+    return {"by2_3lvl": [t, t[::2], t[::4]], "by4_2lvl": [t, t[::4]]}[grid]
+
+
+def _distinct_steps(t):
+    return len(set(np.diff(np.asarray(t, dtype=np.float64)).view(np.int64).tolist()))
+
+
+@pytest.mark.parametrize("nx", [20, 66])
+@pytest.mark.parametrize("grid", ["by2_3lvl", "by4_2lvl"])
+def test_every_sweep_with_several_step_sizes_per_level(grid, nx):
+    assert torch.cuda.is_available()
+    record = {}
+    for w, sweeps in ((1.0, ALL_SWEEPS), (1.3, ("c_relax",))):
+        dev, ref = _pair(nx, _intervals(_ragged(nx, grid)), weight_c=w)
+        for t in dev.t:
+            assert _distinct_steps(t) >= 3, np.diff(t)
+        if grid == "by4_2lvl":      # the three F-points of one interval do not share one pair of D tables
+            assert sum(_distinct_steps(dev.t[0][a:a + 4]) >= 2 for a in range(0, 16, 4)) >= 2
+        _run_sweeps(dev, ref, w, 500 * nx + (3 if w != 1.0 else 0), sweeps, record=record)
+    _report(f"step_sizes[{grid},nx={nx}]", record)
+
+
+# ---- c. a dt group larger than one batch -------------------------------------------------------------------------------------------
+def test_sweeps_of_more_than_one_batch():
+    """1027 points with the exact step 2^-7 (every t_k = k 2^-7 and every difference is exact: one bit pattern of dt): 513 F-points and
+    513 relaxed C-points, each one dt group = a batch of 512 states (1024 work slab items) and a batch of 1"""
+    assert torch.cuda.is_available()
+    nx, w, h = 4, 1.3, 2.0 ** -7
+    t = h * np.arange(1027.0)
+    dev, ref = _pair(nx, _intervals([t, t[::2]]), weight_c=w)
+    t = np.asarray(dev.t[0])
+    assert len(t) == 1027 and len(dev.t[1]) == 514
+    for pts in (np.arange(1, len(t), 2), np.arange(2, len(t), 2)):      # F-points, relaxed C-points
+        groups = sorted(collections.Counter((t[pts] - t[pts - 1]).view(np.int64).tolist()).values())
+        assert groups == [513] and 513 > 1024 // 2, groups
+    record = _run_sweeps(dev, ref, w, 77, STORED_STATE_SWEEPS, levels=[0])
+    _report("batches[dyadic_1027]", record)
+
+
+# ---- d. one Phi at larger grids ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("nx", [256, 257])
+def test_one_phi_at_larger_grids(nx):
+    assert torch.cuda.is_available()
+    dev, ref = _pair(nx, _uniform((5, 3), 2.0 ** -9))      # (steps of 2^-11, exact: one factorisation per species; r = 8)
+    st = _random_states(ref, nx)
+    _set_states(dev, ref, st)
+    dev.f_relax(0); ref.f_relax(0)
+    allowed = _tol(ref, 0, st[("u", 0)]) + 8 * EPS * 3 * _row_norm(*st.values())
+    worst = _compare(dev, ref, 0, allowed, "f_relax")
+    print(f"RATIO larger_grids[nx={nx}] f_relax: worst error/allowed {worst / allowed:.4f}")
+
+
+# ---- e. the fixed point and a constant state ---------------------------------------------------------------------------------------
+def test_fixed_point_and_constant_rows():
+    """(u, v) = (1, 0) is a fixed point of the system: b = (1, 0) and mode 0 has D = 1. A constant state (0.5, 0.25): b is constant per
+    plane, so Phi = b = (0.5 + dt (a / 2 - 1 / 32), 0.25 + dt (1 / 32 - b / 4))."""
+    assert torch.cuda.is_available()
+    nx = 33
+    dev, ref = _pair(nx, _uniform((17, 9, 5), _t_sweep(nx)))
+    app, n, dt = ref.problem[0], nx * nx, float(ref.t[0][1] - ref.t[0][0])
+    st = _random_states(ref, 5)
+    fixed = np.concatenate((np.ones(n), np.zeros(n)))
+    const = np.concatenate((np.full(n, 0.5), np.full(n, 0.25)))
+    st[("u", 0)][0::4], st[("u", 0)][2::4] = fixed, const      # C-points 0, 4, .. the fixed point, 2, 6, .. the constant state
+    _set_states(dev, ref, st)
+    dev.f_relax(0); ref.f_relax(0)
+    allowed = _tol(ref, 0, st[("u", 0)][0::2]) + 8 * EPS * 3 * _row_norm(*st.values())
+    worst = _compare(dev, ref, 0, allowed, "f_relax, fixed point and constant rows")
+    got = dev.backend.natural("u", 0)
+    want_const = np.concatenate((np.full(n, 0.5 + dt * (app.a * 0.5 - 0.5 * 0.0625)), np.full(n, 0.25 + dt * (0.5 * 0.0625 - app.b * 0.25))))
+    err = max(float(np.max(np.linalg.norm(got[1::4] - fixed, axis=1))), float(np.max(np.linalg.norm(got[3::4] - want_const, axis=1))))
+    print(f"RATIO constants f_relax: worst error/allowed {max(worst, err) / allowed:.4f}")
+    assert err <= allowed, (err, allowed)
+    assert np.array_equal(got[1::4][:, n:], np.zeros_like(got[1::4][:, n:]))      # v = 0 stays 0 exactly
+
+
+# ---- Mgrit.solve() -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("cycle", ["V", "F"])
+def test_solve_matches_the_reference_hierarchy(cycle):
+    """from the initial guess on (nx = 20, [0, 6], nt 65 / 17 / 5): residual histories by the rule of tests/cases.py"""
+    assert torch.cuda.is_available()
+    dev, ref = _pair(20, _uniform((65, 17, 5), 6.0), cycle_type=cycle, max_iter=6, tol=1e-9, nested_iteration=True)
+    conv, rconv = np.asarray(dev.solve()["conv"]), np.asarray(ref.solve()["conv"])
+    u = dev.backend.natural("u", 0)
+    norm_u = cases.spacetime_norm(u)
+    assert len(conv) == len(rconv) >= 2, (conv, rconv)
+    dev_ref = np.abs(conv - rconv)
+    print(f"RATIO solve[{cycle}] conv ({len(conv)} iterations): largest deviation {np.max(dev_ref) / (EPS * norm_u):.2f} units of "
+          f"eps*norm(u) (allowed {cases.BLK_K} beyond 1e-10 relative)")
+    assert np.all(dev_ref <= 1e-10 * rconv + cases.BLK_K * EPS * norm_u), (conv, rconv)
+    last = _host_state(ref, "u", 0)[-1]
+    print(f"RATIO solve[{cycle}] last state: relative deviation {np.abs(u[-1] - last).max() / np.abs(last).max():.3e}")
+
+
+def test_jump_criterion_matches_the_reference_hierarchy():
+    """conv_crit = 1: the norms of u_i - previous u_i over both planes (h2d_rowsq_kernel<false, 2>), three iterations from the
+    initial guess; the same rule as for the residual histories"""
+    assert torch.cuda.is_available()
+    dev, ref = _pair(20, _uniform((33, 17, 9), 4.0), conv_crit=1, max_iter=3, tol=0.0)
+    conv, rconv = np.asarray(dev.solve()["conv"]), np.asarray(ref.solve()["conv"])
+    norm_u = cases.spacetime_norm(dev.backend.natural("u", 0))
+    assert len(conv) == len(rconv) == 3 and np.all(rconv > 0.0), (conv, rconv)
+    print(f"RATIO solve[jump] conv: largest deviation {np.max(np.abs(conv - rconv)) / (EPS * norm_u):.2f} units of eps*norm(u)")
+    assert np.all(np.abs(conv - rconv) <= 1e-10 * rconv + cases.BLK_K * EPS * norm_u), (conv, rconv)
+
+
+# ---- what is refused ---------------------------------------------------------------------------------------------------------------
+def test_what_is_not_covered_is_refused():
+    from pymgrit_amd import AtMgrit, GrayScott, GridTransfer, GridTransferCopy, Mgrit
+    from pymgrit_amd.core.backend_hip import HipBackend
+    from pymgrit_amd.core.hip_lib import MgritHipError
+
+    def prob(nxs=(12, 12)):
+        return [GrayScott(nx=nx, method="IMEX", t_start=0, t_stop=0.5, nt=nt) for nx, nt in zip(nxs, (9, 3))]
+
+    class GridTransferGrayScott(GridTransfer):      # a spatial coarsening of the user's
+        def restriction(self, u):
+            return u
+
+        def interpolation(self, u):
+            return u
+    with pytest.raises(MgritHipError, match="same nx"):
+        Mgrit(prob((12, 6)), transfer=[GridTransferGrayScott()], logging_lvl=30)
+    with pytest.raises(MgritHipError, match="GridTransferCopy only"):
+        Mgrit(prob(), transfer=[GridTransferGrayScott()], logging_lvl=30)
+    with pytest.raises(MgritHipError, match="AT-MGRIT is not supported"):
+        AtMgrit(k=2, problem=prob(), logging_lvl=30)
+    with pytest.raises(MgritHipError, match="global convergence criteria only"):
+        Mgrit(prob(), conv_crit=2, logging_lvl=30)
+    stub = types.SimpleNamespace(desc=[p.device_stepper() for p in prob()])
+    with pytest.raises(MgritHipError, match="one time rank only"):
+        HipBackend._check_grayscott(stub, types.SimpleNamespace(comm_time_size=2, global_conv_crit=True, transfer_objects=[GridTransferCopy()]))
+    with pytest.raises(MgritHipError, match="outside"):
+        Mgrit([GrayScott(nx=3, method="IMEX", t_start=0, t_stop=0.5, nt=nt) for nt in (9, 3)], logging_lvl=30)
+    # the host steppers have no device form: such a hierarchy runs on the plugin path
+    for method in ("EXPL", "IMPL"):
+        mg = Mgrit([GrayScott(nx=8, method=method, t_start=0, t_stop=0.01, nt=nt) for nt in (9, 3)], logging_lvl=30, max_iter=1)
+        assert type(mg.backend).__name__ == "PluginBackend"
+
+
+def test_level_entry_point_refuses_bad_arguments():
+    """mgrit_hip_level_grayscott2d through raw ctypes: negative codes with a message, and what follows from the level's kind"""
+    assert torch.cuda.is_available()
+    from pymgrit_amd.core import hip_lib
+    lib = hip_lib.load()
+    EINVAL, EUNSUPPORTED = -1, -4
+    gs, cfg, msg = lib.mgrit_hip_level_grayscott2d, lib.mgrit_hip_block_solve_config, lib.mgrit_hip_last_error
+    eng = C.c_void_p()
+    assert lib.mgrit_hip_create(C.byref(eng), 3, C.c_void_p(torch.cuda.current_stream().cuda_stream)) == 0
+    try:
+        t9 = np.ascontiguousarray(np.linspace(0.0, 1.0, 9))
+        tp, null = C.c_void_p(t9.ctypes.data), C.c_void_p(0)
+        ok = (20, 800, 100.0, 1.0, 0.01, 0.09, 0.086)
+        assert gs(None, 0, 9, tp, *ok) < 0 and gs(eng, 5, 9, tp, *ok) < 0 and gs(eng, -1, 9, tp, *ok) < 0
+        assert gs(eng, 0, 9, tp, 3, 32, 100.0, 1.0, 0.01, 0.09, 0.086) == EUNSUPPORTED and b"Gray-Scott grid" in msg()
+        assert gs(eng, 0, 9, tp, 2049, 2 * 2049 * 2049 + 14, 100.0, 1.0, 0.01, 0.09, 0.086) == EUNSUPPORTED
+        assert gs(eng, 0, 9, tp, 20, 400, 100.0, 1.0, 0.01, 0.09, 0.086) == EINVAL and b"2*nx*nx" in msg()      # one plane's worth
+        assert gs(eng, 0, 9, tp, 20, 808, 100.0, 1.0, 0.01, 0.09, 0.086) == EINVAL                                # not a multiple of 16
+        for bad in ((20, 800, 0.0, 1.0, 0.01, 0.09, 0.086), (20, 800, 100.0, 0.0, 0.01, 0.09, 0.086), (20, 800, 100.0, 1.0, -0.01, 0.09, 0.086),
+                    (20, 800, 100.0, 1.0, 0.01, float("nan"), 0.086), (20, 800, 100.0, 1.0, 0.01, 0.09, float("inf"))):
+            assert gs(eng, 0, 9, tp, *bad) == EINVAL and b"Gray-Scott parameters" in msg(), bad
+        assert gs(eng, 0, 9, null, *ok) == EINVAL and gs(eng, 0, -1, tp, *ok) == EINVAL
+        assert gs(eng, 0, 9, tp, *ok) == 0 and gs(eng, 1, 9, tp, *ok) == 0
+        assert gs(eng, 0, 9, tp, *ok) < 0 and b"already" in msg()                # already described
+        # non-linear Phi: no time-parallel forward solve (r > 0 refused, the rule r < 0 leaves it step by step)
+        assert cfg(eng, 1, 4, 1, 0, null, null) == EUNSUPPORTED
+        assert cfg(eng, 1, -1, 1, 0, null, null) == 0
+        # no spatial transfer joins two such levels; the copy does
+        assert lib.mgrit_hip_level_transfer(eng, 0, hip_lib.TRANSFER_PERIODIC2D) == EUNSUPPORTED
+        assert lib.mgrit_hip_level_transfer(eng, 0, hip_lib.TRANSFER_COPY) == 0
+    finally:
+        assert lib.mgrit_hip_destroy(eng) == 0
