@@ -315,6 +315,23 @@ int mgrit_hip_intervals_create(mgrit_hip_engine *e, int lvl, int n, const int32_
                                int chunk, const int32_t *keep, int *id_out);
 int mgrit_hip_cf_fas(mgrit_hip_engine *e, int lvl, int intervals_id, int pre_relaxed);
 int mgrit_hip_ec_relax_res(mgrit_hip_engine *e, int lvl, int intervals_id, int store_all_f);
+/* Rows that are not stored because their bits already sit in a sibling row. mgrit_hip_cf_fas(..., pre_relaxed = 1) finds the
+ * relaxed C-point of every interval in row cend-1 and never writes that row, so it leaves row cend of level lvl unwritten and
+ * the engine notes the list as pending on the level; mgrit_hip_ec_relax_res with the same list and store_all_f = 2 -- the next
+ * sweep of a cycle to read the level -- takes the C-point from row cend-1, rewrites both rows as always and clears the note.
+ * Every other entry point that names the level first copies row cend-1 to row cend for the pending list (one small launch) and
+ * then runs as always, so no caller ever sees the difference in a result; a caller that reads or overwrites the slab WITHOUT the
+ * engine in between the two passes calls any entry point of the level first (mgrit_hip_relax mode F is what HipBackend uses).
+ * The engine defers on every level size, and only on an engine without exchange links (a rank of a sharded run hands rows to
+ * its neighbours in between), outside a stream capture, and while the switch is on. Inside a capture nothing is deferred and
+ * nothing is settled: an entry point that finds a pending list there returns MGRIT_HIP_EINVAL.
+ *   mgrit_hip_deferred:  the pending interval list of the level, -1 if none, MGRIT_HIP_DEFERRED_BAD for a null engine or a level
+ *                        out of range. Touches nothing.
+ *   mgrit_hip_set_defer: on = 0 every row is stored as before, 1 (default; MGRIT_HIP_DEFER=0 in the environment of
+ *                        mgrit_hip_create makes it 0) as described. A list that is pending stays pending. */
+#define MGRIT_HIP_DEFERRED_BAD (-2)
+int mgrit_hip_deferred(mgrit_hip_engine *e, int lvl);
+int mgrit_hip_set_defer(mgrit_hip_engine *e, int on);
 /* the same pass with the per-point sums of squares written to sumsq_out[res_pos] (device-accessible memory of the caller, e.g.
  * pinned host memory) instead of the engine's buffer: a rank of a sharded run fills the values of its complete intervals this
  * way and the first local C-point's through mgrit_hip_residual */

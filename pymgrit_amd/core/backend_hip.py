@@ -155,6 +155,8 @@ class HipBackend:
         self._f_stale = 0         # level-0 F-points: 0 all in place; 1 all but the last of every interval await materialise();
                                   # 2 as 1, and the last one's row holds Phi of it (the next C-relaxation's value, cf_fas pre)
         self._cycle_pre = False   # the state at the start of the running cycle was 2 (begin_cycle)
+        self._down_pending = False   # cf_fas has run with pre-relaxed C-points and the level-0 way up has not: the engine may hold
+                                     # the closing C-points one row back (include/mgrit_hip.h, mgrit_hip_deferred) until then
         self.f_relax_follows = False   # set by Mgrit.iteration around its own C-relaxations (_before_c_write)
         self._residual_cache = None    # the level-0 points whose residual sums the engine's pinned buffer holds (residual_ready)
         self._write_gen = 0            # write_generation()
@@ -573,11 +575,18 @@ class HipBackend:
         output_fcn, mgrit.u[0][i], natural(), the U slabs -- gets the others rebuilt here by one F-relaxation from the
         C-points: the same Phi on the same values, so bit for bit what an every-point store would have left."""
         self._cycle_pre = False     # whatever the cycle's down pass was promised (begin_cycle), the rows are plain again
-        if self._f_stale:
-            self._f_stale = 0
+        if self._f_stale or self._down_pending:   # (pending: the F-relaxation is an engine call on level 0, which puts the rows in place)
+            self._f_stale, self._down_pending = 0, False
             cache = self._residual_cache          # an F-relaxation that rewrites identical values leaves the residual valid
             self.relax(0, self.mg._f_runs(0), 'F')
             self._residual_cache = cache
+
+    def _rows_in_place(self):
+        """in front of a torch read or write of level-0 rows that no engine call stands before: between cf_fas with pre-relaxed
+        C-points and the way up the engine may hold the closing C-points one row back, and only an engine call on the level
+        puts them in place (materialise()'s F-relaxation is one). Outside that window nothing happens."""
+        if self._down_pending:
+            self.materialise()
 
     def _settle(self, lvl):
         """before any sweep other than the two whole-level passes reads level 0: state 2 (the last F-point's row holds Phi of
@@ -602,6 +611,7 @@ class HipBackend:
         """upload a [n_local_points][n] host array given in natural x order"""
         self._invalidate(outside=True)
         if which == "u" and lvl == 0:
+            self._rows_in_place()
             self._f_stale = 0      # every row replaced: nothing of the last cycle's C-point storage is left to rebuild
         slab = {"u": self._U, "v": self.V, "g": self.G}[which][lvl]
         slab.zero_()
@@ -1025,6 +1035,7 @@ class HipBackend:
 
     # -- C-point snapshots of level 0 (pipelined solve, Mgrit._solve_pipelined): rows copied inside HBM ------------
     def _snap_slot(self, slot, points):
+        self._rows_in_place()
         if self._snap_idx is None:
             self._snap_idx = torch.as_tensor(np.asarray(points, dtype=np.int64), device=self.device)
         if slot not in self._snap:
@@ -1059,6 +1070,7 @@ class HipBackend:
             torch.index_select(self._U[0], 0, self._snap_idx, out=self._snap[slot])
 
     def restore_cpoints(self, slot, points):
+        self._rows_in_place()
         self._invalidate()
         if len(points):
             self._U[0].index_copy_(0, self._snap_idx, self._snap[slot])
@@ -1253,13 +1265,17 @@ class HipBackend:
         keep): keep = which rows of lvl+1 the closing C-point needs (bit 0: u, bit 1: v; include/mgrit_hip.h)"""
         if intervals:
             self._enter(lvl, settle=False, clear="every")
-            check(self.lib.mgrit_hip_cf_fas(self.h, lvl, self._intervals_id(lvl, intervals), 1 if (lvl == 0 and self._cycle_pre) else 0))
+            pre = lvl == 0 and self._cycle_pre
+            check(self.lib.mgrit_hip_cf_fas(self.h, lvl, self._intervals_id(lvl, intervals), 1 if pre else 0))
+            self._down_pending = self._down_pending or pre
 
     def ec_relax_res_to(self, lvl, intervals, buf):
         """several ranks: error_correction + f_relax + the residual sums of the rank's complete intervals (every F-point stored:
         neighbours and the generic sweeps read them), sums into the reserved slot `buf` (residual_reserve)"""
         if intervals:
             check(self.lib.mgrit_hip_ec_relax_res_to(self.h, lvl, self._intervals_id(lvl, intervals), 1, C.c_void_p(buf.data_ptr())))
+            if lvl == 0:
+                self._down_pending = False
 
     def ec_relax_res(self, lvl, intervals, base=0):
         """error_correction + f_relax + compute_residual; the per-point sums of squares stay in pinned host memory until
@@ -1271,6 +1287,8 @@ class HipBackend:
             # IS the next reader of the level (cf_iter = 1: no plain C-relaxation in front of it)
             mode = 1 if not lazy else (2 if (self.mg.cf_iter[0] == 1 and not options.no_pre_relax) else 0)
             check(self.lib.mgrit_hip_ec_relax_res(self.h, lvl, self._intervals_id(lvl, intervals), mode))
+            if lvl == 0:
+                self._down_pending = False
             if lvl == 0 and self._mirror_on:
                 self._mirror_hit = True
             if lazy:

@@ -1126,6 +1126,9 @@ __device__ __forceinline__ void stage_other_level(const Smem &sm, const LevelDev
 //          reads it) nor anywhere on a coarsest level that is solved by forward_solve;
 //   bit 1: v^{l+1} -- its only reader is the error correction, which may take the same bits from the fine C-point (identity
 //          transfer); needed where a chunk of the way up starts (that row is being overwritten by the chunk in front of it).
+// A list may be PENDING on its level (Level::held, round 7): mgrit_hip_cf_fas with pre-relaxed C-points has not stored row cend of
+// its intervals -- row cend-1 holds those bits -- and mgrit_hip_ec_relax_res with the same list reads them there; anybody else gets
+// the rows put in place first (check_level, settle_held_kernel).
 struct IntervalsDev {
     const int32_t *cstart, *cend, *cend_coarse, *res_pos, *chunk_first, *chunk_len, *chunk_start_coarse, *keep;
     int n_chunks;
@@ -1148,10 +1151,15 @@ struct IntervalsDev {
 // experiment build of its own: profiles/r04_cfas_timeline.txt. Per interval of config 3: five Phi at ~2.1 us of solve each plus
 // ~1.7 us each for streaming the forcing factor from L2 -- LDS, where ecfr_kernel keeps it, holds q here --, 4.4 us of row
 // traffic that the wave waits for, 2 us until the stores of the interval before have drained.)
+// pre: bit 0 = the pre-relaxed rows described above; bit 1 (CFAS_HELD, with bit 0 only) = C'_{j+1} is NOT stored to the fine row ce:
+// row ce-1 holds those very bits and the kernel does not write it, so the next reader of row ce -- ecfr_kernel with ECFR_HELD, or
+// settle_held_kernel in front of anybody else -- takes them from there (Level::held). One row less written per interval.
+enum { CFAS_PRE = 1, CFAS_HELD = 2, ECFR_HELD = 4 };
 template <int FORCE, int TB = 1024>
-__global__ void __launch_bounds__(TB) cfas_kernel(LevelDev L, LevelDev Lc, IntervalsDev I, int pre) {
+__global__ void __launch_bounds__(TB) cfas_kernel(LevelDev L, LevelDev Lc, IntervalsDev I, int flags) {
     constexpr int KIND = MGRIT_HIP_STEPPER_HEAT1D;
     WG_PROLOGUE_TB(TB);
+    const int pre = flags & CFAS_PRE, held = flags & CFAS_HELD;   // (wave-uniform launch arguments)
     constexpr bool ONE = TB == LANES;   // one wave per state: Phi without the cross-group exchange (heat_solve)
     stage_other_level(sm, Lc, t);
     for (wq.begin(L.sched, L.xcc0_limit, wgq_slot, t); wq.cur < I.n_chunks; wq.advance(t)) {
@@ -1196,7 +1204,7 @@ __global__ void __launch_bounds__(TB) cfas_kernel(LevelDev L, LevelDev Lc, Inter
             // them -- a load issued behind stores retires behind them (vmcnt counts in order), and the Phi would wait for their
             // round trip to HBM --, its solve (LDS and registers only) behind them
             phi_apply<KIND, FORCE, true, 1, false, ONE>(x, ctx, L, ce, sm, t, lane, wave, G);
-            store_row_nt(L.u + (size_t)ce * L.ld, sl, b, L.stream_rows);
+            if (!held) store_row_nt(L.u + (size_t)ce * L.ld, sl, b, L.stream_rows);
             const int keep = __builtin_amdgcn_readfirstlane(I.keep[it]);
             if (keep & 1) store_row_nt(Lc.u + (size_t)jc * Lc.ld, sl, b, Lc.stream_rows);
             if (keep & 2) store_row_nt(Lc.v + (size_t)jc * Lc.ld, sl, b, Lc.stream_rows);
@@ -1239,8 +1247,11 @@ __global__ void __launch_bounds__(TB) cfas_kernel(LevelDev L, LevelDev Lc, Inter
 //   out[res_pos] = || Phi_l(F''_last) - C''_{j+1} ||^2
 // 2 rows read + m written per interval instead of 2 + m (correction + F-relaxation) and 2 more for the residual.
 template <int FORCE, bool USE_G, bool RES, int TB = 1024>
-__global__ void __launch_bounds__(TB) ecfr_kernel(LevelDev L, LevelDev Lc, IntervalsDev I, double *__restrict__ out, int store_f,
+__global__ void __launch_bounds__(TB) ecfr_kernel(LevelDev L, LevelDev Lc, IntervalsDev I, double *__restrict__ out, int store_flags,
                                                     double *const *__restrict__ mirror, int mirror_row0) {
+    // store_flags = store_f | ECFR_HELD: with ECFR_HELD (store_f = 2 only) the uncorrected closing C-point is read from row ce-1, where
+    // cfas_kernel (CFAS_HELD) found it and left it; this kernel overwrites that row only behind the read, by the same lane
+    const int store_f = store_flags & 3, held = store_flags >> 2;   // (wave-uniform launch arguments; held = 0 / 1 rows back)
     constexpr int KIND = MGRIT_HIP_STEPPER_HEAT1D;
     constexpr bool CF = FORCE == 4;   // forcing factor in LDS, so every Phi in closed form
     WG_PROLOGUE_TB(TB);
@@ -1281,7 +1292,7 @@ __global__ void __launch_bounds__(TB) ecfr_kernel(LevelDev L, LevelDev Lc, Inter
             double b[E];
             {   // v^{l+1}_{j+1} from the fine row itself (the same bits; only this chunk writes that row), see IntervalsDev::keep
                 double w[E];
-                load_row_nt(L.u + (size_t)ce * L.ld, sl, b, L.stream_rows);
+                load_row_nt(L.u + (size_t)(ce - held) * L.ld, sl, b, L.stream_rows);
                 load_row_nt(Lc.u + (size_t)jc * Lc.ld, sl, w, Lc.stream_rows);
 #pragma unroll
                 for (int e = 0; e < E; ++e) b[e] = b[e] + (w[e] - b[e]);
@@ -1764,6 +1775,9 @@ struct Level {
     double *blk_qt = nullptr;        // blk_one_kernel (small levels, one launch): the modes transposed; null: the six-launch form
     unsigned *blk_sync = nullptr;    //   its barrier counters (device) ...
     unsigned *blk_err = nullptr;     //   ... and the word a barrier that gave up sets (pinned, host-visible)
+    int held = -1;                   // interval list whose closing C-points mgrit_hip_cf_fas has NOT stored: row cend-1 holds the bits of
+                                     // row cend (cfas_kernel CFAS_HELD). mgrit_hip_ec_relax_res with the same list reads them there
+                                     // and clears this; every other entry point of the level puts the rows in place first (check_level)
 };
 
 // ghost exchange (mgrit_hip_comm.inc): one direction of one pair of ranks
@@ -1791,6 +1805,7 @@ struct mgrit_hip_engine {
     std::vector<TimeRec> trecs;              // one per timed entry-point call since the last drain
     std::vector<hipEvent_t> ev_pool;         // events of drained records, reused
     hipEvent_t last0 = nullptr, last1 = nullptr;   // events of the most recent timed call (mgrit_hip_last_kernel_ms)
+    bool defer = true;            // mgrit_hip_set_defer / MGRIT_HIP_DEFER: rows whose bits sit in a sibling row are not stored (Level::held)
     int fas_chunk = 0;            // mgrit_hip_set_fas_chunk: -1 fas_fused1_kernel, 0 chunks by the library's rule, n > 0 chunks of n
     int reserve = 0;              // mgrit_hip_set_reserve: CUs of XCD 0 the sweeps leave to the chain workers (0: program order)
     int *sched = nullptr;         // device counter block (1 KB, allocated with the first chain / planned launch): [0..2] {next, xcc0,
@@ -2307,10 +2322,45 @@ int register_lds_limits() {
     return err.empty() ? 0 : fail(MGRIT_HIP_EHIP, "%s", err.c_str());
 }
 
-int check_level(mgrit_hip_engine *e, int lvl, bool need_set = true) {
+// Level::held: the rows a deferring mgrit_hip_cf_fas has left out are put in place -- row cend-1 copied to row cend for every
+// interval of the list -- and the record is cleared. Never launched into a stream capture: a captured copy would be replayed
+// in cycles that have nothing pending.
+__global__ void __launch_bounds__(256) settle_held_kernel(double *__restrict__ u, int ld, const int32_t *__restrict__ cend, int n) {
+    for (int it = blockIdx.x; it < n; it += gridDim.x) {
+        const int ce = cend[it];   // 2 <= ce < n_pts (mgrit_hip_intervals_create)
+        const double2 *src = reinterpret_cast<const double2 *>(u + (size_t)(ce - 1) * ld);
+        double2 *dst = reinterpret_cast<double2 *>(u + (size_t)ce * ld);
+        for (int k = threadIdx.x; k < ld / 2; k += blockDim.x) dst[k] = src[k];
+    }
+}
+
+bool capturing(const mgrit_hip_engine *e) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(e->stream, &cs);
+    return cs != hipStreamCaptureStatusNone;
+}
+
+bool has_links(const mgrit_hip_engine *e) {
+    for (const Link &l : e->links)
+        if (l.kind != LINK_NONE) return true;
+    return false;
+}
+
+int settle_held(mgrit_hip_engine *e, int lvl) {
+    Level &lv = e->L[lvl];
+    if (capturing(e)) return fail(MGRIT_HIP_EINVAL, "level %d has unstored C-points pending (interval list %d) inside a stream capture", lvl, lv.held);
+    const int n = lv.ivals_cnt[lv.held];
+    const int rc = launch(&settle_held_kernel, dim3(std::min(n, 4096)), dim3(256), 0, e->stream, lv.dev.u, lv.dev.ld, lv.ivals[lv.held].cend, n);
+    if (!rc) lv.held = -1;
+    return rc;
+}
+
+// partner: the interval list whose pending rows (Level::held) the caller reads where they are; any other pending list is settled
+int check_level(mgrit_hip_engine *e, int lvl, bool need_set = true, int partner = -1) {
     if (!e) return fail(MGRIT_HIP_EINVAL, "null engine");
     if (lvl < 0 || lvl >= e->n_levels) return fail(MGRIT_HIP_EINVAL, "level %d out of range [0,%d)", lvl, e->n_levels);
     if (need_set && !e->L[lvl].set) return fail(MGRIT_HIP_EINVAL, "level %d has no stepper", lvl);
+    if (e->L[lvl].held >= 0 && e->L[lvl].held != partner) return settle_held(e, lvl);
     return 0;
 }
 
@@ -3606,6 +3656,10 @@ int mgrit_hip_create(mgrit_hip_engine **out, int n_levels, void *stream) {
     mgrit_hip_engine *e = new mgrit_hip_engine();
     e->n_levels = n_levels;
     e->fas_chunk = ffas_env();
+    {
+        const char *s = std::getenv("MGRIT_HIP_DEFER");   // "0": every row stored (mgrit_hip_set_defer)
+        e->defer = !(s && std::strcmp(s, "0") == 0);
+    }
     e->stream = static_cast<hipStream_t>(stream);
     e->L.resize(n_levels);
     for (auto &lv : e->L) lv.arena = &e->arena;
@@ -4786,8 +4840,8 @@ int mgrit_hip_intervals_create(mgrit_hip_engine *e, int lvl, int n, const int32_
     return 0;
 }
 
-static int fused_level_check(mgrit_hip_engine *e, int lvl, int ivals_id, const char *what, bool level0_only) {
-    int rc = check_level(e, lvl);
+static int fused_level_check(mgrit_hip_engine *e, int lvl, int ivals_id, const char *what, bool level0_only, int partner = -1) {
+    int rc = check_level(e, lvl, true, partner);
     if (rc) return rc;
     if (lvl != 0 && level0_only) return fail(MGRIT_HIP_EUNSUPPORTED, "%s: level 0 only", what);
     if (lvl + 1 >= e->n_levels || !e->L[lvl + 1].set) return fail(MGRIT_HIP_EINVAL, "level %d has no coarser level", lvl);
@@ -4807,9 +4861,16 @@ int mgrit_hip_cf_fas(mgrit_hip_engine *e, int lvl, int ivals_id, int pre_relaxed
     Level &lf = e->L[lvl], &lc = e->L[lvl + 1];
     const IntervalsDev &I = lf.ivals[ivals_id];
     if (I.n_chunks == 0) return 0;
+    // The closing C-points stay unstored (Level::held) when their bits already sit in the row in front of them (pre_relaxed), on one
+    // rank -- a rank with exchange links hands rows to its neighbours and would pay a settle per cycle --, outside a capture (a
+    // graph would bake the decision into cycles it does not hold for), on every level size (the row saved is HBM traffic on the
+    // levels that stream and a store of 8 KB-128 KB less on those that do not).
+    const bool defer = pre_relaxed && e->defer && !has_links(e) && !capturing(e);
     Timed timed(e, MGRIT_HIP_T_CF_FAS, lvl);
-    return launch(cfas_fn(force_mode(lf), lf.dev.T), dim3(persistent_grid(lf, I.n_chunks)), dim3(lf.dev.T), smem_bytes(lf.G, lf.dev.kind),
-                  e->stream, sched_dev(e, lf), lc.dev, I, pre_relaxed ? 1 : 0);
+    rc = launch(cfas_fn(force_mode(lf), lf.dev.T), dim3(persistent_grid(lf, I.n_chunks)), dim3(lf.dev.T), smem_bytes(lf.G, lf.dev.kind),
+                e->stream, sched_dev(e, lf), lc.dev, I, !pre_relaxed ? 0 : defer ? (CFAS_PRE | CFAS_HELD) : CFAS_PRE);
+    if (!rc && defer) lf.held = ivals_id;
+    return rc;
 }
 
 static int ec_relax_res_impl(mgrit_hip_engine *e, int lvl, int ivals_id, int store_all_f, double *out_caller);
@@ -4824,7 +4885,10 @@ int mgrit_hip_ec_relax_res_to(mgrit_hip_engine *e, int lvl, int ivals_id, int st
 }
 
 static int ec_relax_res_impl(mgrit_hip_engine *e, int lvl, int ivals_id, int store_all_f, double *out_caller) {
-    int rc = fused_level_check(e, lvl, ivals_id, "fused correction + F-relaxation + residual", false);
+    // the partner of a deferring mgrit_hip_cf_fas: the same list on level 0 with store_all_f = 2, outside a capture, reads the
+    // pending rows where they are; anything else finds them put in place by check_level
+    const bool partner = e && lvl == 0 && store_all_f == 2 && ivals_id >= 0 && e->n_levels > 0 && e->L[0].held == ivals_id && !capturing(e);
+    int rc = fused_level_check(e, lvl, ivals_id, "fused correction + F-relaxation + residual", false, partner ? ivals_id : -1);
     if (rc) return rc;
     Level &lf = e->L[lvl], &lc = e->L[lvl + 1];
     const IntervalsDev &I = lf.ivals[ivals_id];
@@ -4840,8 +4904,11 @@ static int ec_relax_res_impl(mgrit_hip_engine *e, int lvl, int ivals_id, int sto
     double *out = out_caller ? out_caller : e->pinned;
     Timed timed(e, MGRIT_HIP_T_EC_RELAX_RES, lvl);
     double *const *mirror = e->mirror_cur;   // null until mgrit_hip_cpoint_mirror has been called
-    return launch(ecfr_fn(force_mode(lf), false, lf.dev.T), grid, block, smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, I,
-                  out, store_all_f, mirror, e->mirror_row0);
+    const bool held = lf.held == ivals_id;   // (only as the partner: check_level has settled every other pending list)
+    rc = launch(ecfr_fn(force_mode(lf), false, lf.dev.T), grid, block, smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, I,
+                out, held ? (store_all_f | ECFR_HELD) : store_all_f, mirror, e->mirror_row0);
+    if (!rc && held) lf.held = -1;   // the pass has rewritten row cend and row cend-1 of every interval
+    return rc;
 }
 
 static int gen_check(mgrit_hip_engine *e, int lvl, int ivals_id, const char *what) {
@@ -4939,6 +5006,19 @@ int mgrit_hip_chain_clock(mgrit_hip_engine *e, double *mhz, double *us_per_step)
     if (w[2] == 0 || w[3] == 0) return 0;
     *mhz = 100.0 * (double)w[1] / (double)w[2];
     *us_per_step = (double)w[2] / 100.0 / (double)w[3];
+    return 0;
+}
+
+int mgrit_hip_deferred(mgrit_hip_engine *e, int lvl) {
+    if (!e) return fail(MGRIT_HIP_DEFERRED_BAD, "null engine");
+    if (lvl < 0 || lvl >= e->n_levels) return fail(MGRIT_HIP_DEFERRED_BAD, "level %d out of range [0,%d)", lvl, e->n_levels);
+    return e->L[lvl].held;
+}
+
+int mgrit_hip_set_defer(mgrit_hip_engine *e, int on) {
+    if (!e) return fail(MGRIT_HIP_EINVAL, "null engine");
+    if (on != 0 && on != 1) return fail(MGRIT_HIP_EINVAL, "defer %d: 0 = every row stored, 1 = rows held in a sibling row left out", on);
+    e->defer = on != 0;   // (a record that is pending stays: its partner or the next entry point of the level deals with it)
     return 0;
 }
 
