@@ -1572,6 +1572,8 @@ __global__ void interp_rows_kernel(double *__restrict__ uf, int f_ld, int T_f, c
 
 #include "mgrit_hip_heat2d.inc"
 
+#include "mgrit_hip_periodic2d.inc"
+
 #include "mgrit_hip_allencahn.inc"
 
 #include "mgrit_hip_grayscott.inc"
@@ -1608,6 +1610,7 @@ struct PairList {
     BatchPlans fine_to_coarse, fine_to_rows, coarse;   // fine half into g^{l+1} (dst: the coarse slot) or into rows (dst: the pair's position)
 };
 
+enum class H2DKind { HEAT2D, ALLENCAHN_IMEX, ALLENCAHN_NEWTON, GRAYSCOTT_IMEX };   // what a level of the batched 2-D route steps with
 struct H2DHost {
     H2DDev dev{};
     std::vector<double> lx, ly, dts;
@@ -1628,16 +1631,19 @@ struct H2DHost {
         unsigned *rim_flag = nullptr;   // pinned, device-mapped (theta < 1): set when an error at a block end has a non-zero rim
         hipEvent_t rim_ev = nullptr;
     } blk;
-    // Allen-Cahn IMEX (mgrit_hip_allencahn.inc) runs through this route with its own transforms: the full Hartley table [P][P]
-    // (P = Mi = Mj = nx padded to 64), lx = ly = the periodic Laplacian's eigenvalues in natural mode order, no rim, no fold
-    bool ac = false;
-    double *acT = nullptr, ac_inv_eps2 = 0.0, ac_inv_dx2 = 0.0;
-    int ac_nu = 0, ac_KP = 0;
-    // Gray-Scott IMEX (mgrit_hip_grayscott.inc): an Allen-Cahn level in everything above (ac is set as well) whose state row holds two
-    // planes [u | v]: two work slab items per state, a D table per species, the right-hand side from both planes
-    bool gs = false;
-    double gs_du = 0.0, gs_dv = 0.0, gs_a = 0.0, gs_b = 0.0;
-    int comps() const { return gs ? 2 : 1; }   // planes of a state = work slab items of a state
+    // The levels on the periodic nx x nx grid (mgrit_hip_periodic2d.inc) run through this route with their own transforms: the full
+    // Hartley table [P][P] (P = Mi = Mj = nx padded to 64), lx = ly = the periodic Laplacian's eigenvalues in natural mode order, no
+    // rim, no fold. A Gray-Scott state row holds two planes [u | v]: two work slab items per state, a D table per species, the
+    // right-hand side from both planes. ALLENCAHN_NEWTON: an Allen-Cahn level whose Phi is the Newton-PCG step (acn below).
+    H2DKind kind = H2DKind::HEAT2D;
+    bool periodic() const { return kind != H2DKind::HEAT2D; }
+    bool allencahn() const { return kind == H2DKind::ALLENCAHN_IMEX || kind == H2DKind::ALLENCAHN_NEWTON; }
+    bool newton() const { return kind == H2DKind::ALLENCAHN_NEWTON; }
+    int comps() const { return kind == H2DKind::GRAYSCOTT_IMEX ? 2 : 1; }   // planes of a state = work slab items of a state
+    double *T = nullptr;   // the Hartley table
+    int KP = 0;            // nx rounded up to the K step of the tile product
+    struct { double inv_dx2 = 0.0, inv_eps2 = 0.0; int nu = 0; } ac;
+    struct { double du = 0.0, dv = 0.0, a = 0.0, b = 0.0; } gs;
     double *Wc0 = nullptr, *Wc1 = nullptr;   // one item each: the work buffers of the coarsest-level chain, which in a planned
                                              // cycle steps on a second stream BESIDE sweeps that apply this level's Phi too (the
                                              // coarse half of the FAS right-hand side of another block of time points)
@@ -1645,7 +1651,6 @@ struct H2DHost {
     // parameters, the shifted D tables 1/(1 + fac nu/eps^2 + fac (lam_i + lam_j)) per distinct dt (theta is the level's: one table per
     // (dt, theta)), the work rows of the batched route and of the coarsest-level chain (batches of one), the word the host reads
     struct Newton {
-        bool on = false;
         double theta = 1.0, newton_tol = 0.0, lin_tol = 0.0;
         int newton_maxiter = 0, lin_maxiter = 0;
         std::map<uint64_t, double *> dinv;
@@ -2626,7 +2631,7 @@ int h2d_reserve(Level &lv, int count) {
     if (h.rowsq) HIP_TRY(hipFree(h.rowsq));
     h.W0 = h.W1 = h.rowsq = nullptr;
     const size_t per = (size_t)h.dev.Mi * h.dev.Mj * h.comps();
-    if (!h.acn.on) {   // (a Newton-PCG level's products run on its own work rows: acn_reserve)
+    if (!h.newton()) {   // (a Newton-PCG level's products run on its own work rows: acn_reserve)
         HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.W0), sizeof(double) * per * count));
         HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.W1), sizeof(double) * per * count));
     }
@@ -2648,30 +2653,71 @@ void h2d_each_mode(const H2DHost &h, Fn f) {
     }
 }
 
-int h2d_dinv(mgrit_hip_engine *e, Level &lv, uint64_t dtbits, double **out) {
-    H2DHost &h = *lv.h2d;
-    auto it = h.dinv.find(dtbits);
-    if (it != h.dinv.end()) { *out = it->second; return 0; }
+// The one "made on first use" rule of a level's tables per distinct dt: found in the cache, or fill(dt, table of n zeros), uploaded
+// and kept
+template <typename Fill>
+int h2d_table_once(mgrit_hip_engine *e, Level &lv, std::map<uint64_t, double *> &cache, uint64_t dtbits, size_t n, Fill fill, double **out) {
+    auto it = cache.find(dtbits);
+    if (it != cache.end()) { *out = it->second; return 0; }
     double dt;
     std::memcpy(&dt, &dtbits, 8);
-    const double thdt = h.dev.theta * dt;
-    std::vector<double> tab((size_t)h.dev.Mi * h.dev.Mj * h.comps(), 0.0);   // spectral slot order on both axes, 0 where no mode lives
-    if (h.gs) {   // [2][P][P], species u then v: 1 / (1 + (dt d_c) (lam_i + lam_j)), the operand order of GrayScott._dinv
-        for (int c = 0; c < 2; ++c) {
-            const double dtd = dt * (c ? h.gs_dv : h.gs_du);
-            for (int a = 0; a < h.dev.nx; ++a)
-                for (int b = 0; b < h.dev.nx; ++b)
-                    tab[((size_t)c * h.dev.Mi + a) * h.dev.Mj + b] = 1.0 / (1.0 + dtd * (h.lx[a] + h.ly[b]));
-        }
-    } else if (h.ac) {   // natural mode order, modes 0 .. nx - 1 on both axes
-        for (int a = 0; a < h.dev.nx; ++a)
-            for (int b = 0; b < h.dev.nx; ++b) tab[(size_t)a * h.dev.Mj + b] = 1.0 / (1.0 + dt * (h.lx[a] + h.ly[b]));
-    } else h2d_each_mode(h, [&](size_t q, double lam) { tab[q] = 1.0 / (1.0 + thdt * lam); });
+    std::vector<double> tab(n, 0.0);
+    fill(dt, tab.data());
     double *d = nullptr;
     int rc = dev_upload(lv, e->stream, tab, &d);
     if (rc) return rc;
-    h.dinv[dtbits] = d;
+    cache[dtbits] = d;
     *out = d;
+    return 0;
+}
+
+// one [P][P] table of a periodic level, natural mode order, modes 0 .. nx - 1 on both axes: 1 / (shift + coef (lam_a + lam_b))
+void p2d_fill_dinv(const H2DHost &h, double *tab, double shift, double coef) {
+    for (int a = 0; a < h.dev.nx; ++a)
+        for (int b = 0; b < h.dev.nx; ++b) tab[(size_t)a * h.dev.Mj + b] = 1.0 / (shift + coef * (h.lx[a] + h.ly[b]));
+}
+
+// D of the level's implicit solve: Heat2D 1 / (1 + theta dt (lx + ly)) in spectral slot order on both axes, 0 where no mode lives;
+// Allen-Cahn IMEX 1 / (1 + dt (lam_a + lam_b)); Gray-Scott [2][P][P], species u then v, 1 / (1 + (dt d_c) (lam_a + lam_b)), the operand
+// order of GrayScott._dinv
+int h2d_dinv(mgrit_hip_engine *e, Level &lv, uint64_t dtbits, double **out) {
+    H2DHost &h = *lv.h2d;
+    const size_t per = (size_t)h.dev.Mi * h.dev.Mj;
+    return h2d_table_once(e, lv, h.dinv, dtbits, per * h.comps(), [&](double dt, double *tab) {
+        if (h.kind == H2DKind::GRAYSCOTT_IMEX) {
+            p2d_fill_dinv(h, tab, 1.0, dt * h.gs.du);
+            p2d_fill_dinv(h, tab + per, 1.0, dt * h.gs.dv);
+        } else if (h.periodic()) p2d_fill_dinv(h, tab, 1.0, dt);
+        else {
+            const double thdt = h.dev.theta * dt;
+            h2d_each_mode(h, [&](size_t q, double lam) { tab[q] = 1.0 / (1.0 + thdt * lam); });
+        }
+    }, out);
+}
+
+// The four Hartley products of one batch on a periodic level (mgrit_hip_periodic2d.inc), PRE::operands work slab items per state:
+// the first from src, through W1, W0 (o dinv) and W1 again, the last through the sweep's arithmetic (fin) or into out.
+// FLAGS = false: src is the state slab, the operand of state b its row idx[b], mapped by pre while it is staged.
+// FLAGS = true (the preconditioner of the Newton-PCG steps): src is a work row, idx[b] the item's "CG running" flag -- the products of
+// an item whose flag is 0 return at once --, pre is not applied.
+template <class PRE, bool FLAGS = false>
+int p2d_products(mgrit_hip_engine *e, const H2DHost &h, int count, const PRE &pre, const double *src, const int32_t *idx, const double *dinv,
+                 double *W0, double *W1, double *out, const H2DFin *fin) {
+    constexpr int FIRST = FLAGS ? P2D_WORK_PLAIN : P2D_FIRST, SCALE = FLAGS ? P2D_WORK_SCALE : P2D_SCALE, PLAIN = FLAGS ? P2D_WORK_PLAIN : P2D_PLAIN;
+    const H2DDev &H = h.dev;
+    const int P = H.Mi;
+    const size_t per = (size_t)P * P;
+    const dim3 g(P / 64, P / 64, PRE::operands * count);
+    const H2DFin none{};
+    auto launch = [&](auto kernel, const double *B, double *o, const double *d, const H2DFin &F) {
+        hipLaunchKernelGGL(kernel, g, dim3(256), 0, e->stream, h.T, P, h.KP, H.nx, B, o, d, per, idx, H.ld, pre, H, F);
+    };
+    launch(&p2d_gemm_kernel<FIRST, PRE>, src, W1, nullptr, none);
+    launch(&p2d_gemm_kernel<SCALE, PRE>, W1, W0, dinv, none);
+    launch(&p2d_gemm_kernel<PLAIN, PRE>, W0, W1, nullptr, none);
+    if (fin) launch(&p2d_gemm_kernel<P2D_FIN, PRE>, W1, out, nullptr, *fin);
+    else launch(&p2d_gemm_kernel<PLAIN, PRE>, W1, out, nullptr, none);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -2708,22 +2754,13 @@ int acn_reserve(mgrit_hip_engine *e, H2DHost &h, H2DHost::Newton::Work &w, int c
     return 0;
 }
 
+// D of the preconditioner P = (1 + fac nu / eps^2) I - fac L, fac = theta dt
 int acn_dinv(mgrit_hip_engine *e, Level &lv, uint64_t dtbits, double **out) {
     H2DHost &h = *lv.h2d;
-    auto it = h.acn.dinv.find(dtbits);
-    if (it != h.acn.dinv.end()) { *out = it->second; return 0; }
-    double dt;
-    std::memcpy(&dt, &dtbits, 8);
-    const double fac = h.acn.theta * dt, shift = 1.0 + fac * (double)h.ac_nu * h.ac_inv_eps2;
-    std::vector<double> tab((size_t)h.dev.Mi * h.dev.Mj, 0.0);
-    for (int a = 0; a < h.dev.nx; ++a)
-        for (int b = 0; b < h.dev.nx; ++b) tab[(size_t)a * h.dev.Mj + b] = 1.0 / (shift + fac * (h.lx[a] + h.ly[b]));
-    double *d = nullptr;
-    int rc = dev_upload(lv, e->stream, tab, &d);
-    if (rc) return rc;
-    h.acn.dinv[dtbits] = d;
-    *out = d;
-    return 0;
+    return h2d_table_once(e, lv, h.acn.dinv, dtbits, (size_t)h.dev.Mi * h.dev.Mj, [&](double dt, double *tab) {
+        const double fac = h.acn.theta * dt;
+        p2d_fill_dinv(h, tab, 1.0 + fac * (double)h.ac.nu * h.ac.inv_eps2, fac);
+    }, out);
 }
 
 // The one word of a batch the host reads: the items still running, written by acn_reduce_kernel into pinned memory in front of the
@@ -2766,10 +2803,8 @@ int acn_phi_batch(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const dou
     const size_t c = w.cap;
     const ACNState S{w.ints, w.ints + c, w.ints + 2 * c, w.ints + 3 * c, w.ints + 4 * c, w.dbls, w.dbls + c, w.dbls + 2 * c, w.dbls + 3 * c,
                      w.dbls + 4 * c};
-    const ACNPar A{H.nx, P, h.ac_nu, h.ac_inv_dx2, h.ac_inv_eps2, N.theta * dt};
-    const dim3 ge(nb, 1, pl.count), gg(P / 64, P / 64, pl.count), b256(256);
-    const ACPre pre{0.0, 0};
-    const H2DFin none{};
+    const ACNPar A{H.nx, P, h.ac.nu, h.ac.inv_dx2, h.ac.inv_eps2, N.theta * dt};
+    const dim3 ge(nb, 1, pl.count), b256(256);
     hipLaunchKernelGGL(acn_init_kernel, ge, b256, 0, e->stream, A, S, in_slab, pl.d_in, H.ld, x, N.theta == 1.0 ? rhs : nullptr, per);
     if (N.theta != 1.0) hipLaunchKernelGGL((acn_residual_kernel<true>), ge, b256, 0, e->stream, A, S, x, nullptr, rhs, per);
     for (int it = 0; it < N.newton_maxiter; ++it) {
@@ -2781,10 +2816,7 @@ int acn_phi_batch(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const dou
         if ((rc = acn_running(e, N, &running))) return rc;
         if (!running) break;
         for (int k = 0; k < N.lin_maxiter; ++k) {
-            hipLaunchKernelGGL((ac_gemm_kernel<AC_WORK_PLAIN>), gg, b256, 0, e->stream, h.acT, P, h.ac_KP, H.nx, r, W1, nullptr, per, S.cg, 0, pre, H, none);
-            hipLaunchKernelGGL((ac_gemm_kernel<AC_WORK_SCALE>), gg, b256, 0, e->stream, h.acT, P, h.ac_KP, H.nx, W1, W0, dinv, per, S.cg, 0, pre, H, none);
-            hipLaunchKernelGGL((ac_gemm_kernel<AC_WORK_PLAIN>), gg, b256, 0, e->stream, h.acT, P, h.ac_KP, H.nx, W0, W1, nullptr, per, S.cg, 0, pre, H, none);
-            hipLaunchKernelGGL((ac_gemm_kernel<AC_WORK_PLAIN>), gg, b256, 0, e->stream, h.acT, P, h.ac_KP, H.nx, W1, z, nullptr, per, S.cg, 0, pre, H, none);
+            if ((rc = (p2d_products<ACPre, true>(e, h, pl.count, ACPre{0.0, 0}, r, S.cg, dinv, W0, W1, z, nullptr)))) return rc;
             hipLaunchKernelGGL(acn_dot_kernel, ge, b256, 0, e->stream, A, S, r, z, per);
             hipLaunchKernelGGL((acn_reduce_kernel<ACN_R_RZ>), dim3(1), b256, 0, e->stream, S, pl.count, nb, N.newton_tol, N.lin_tol, N.lin_maxiter, N.word);
             hipLaunchKernelGGL(acn_dir_kernel, ge, b256, 0, e->stream, A, S, z, p, per);
@@ -2817,8 +2849,8 @@ int h2d_phi_batch(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const dou
     int rc;
     const size_t per = (size_t)H.Mi * H.Mj;
     chain = chain && pl.count == 1;
-    if (h.gs && 2 * pl.count > H2D_MAX_BATCH) return fail(MGRIT_HIP_EINVAL, "Gray-Scott batch of %d states", pl.count);   // (blockIdx.z, the work slabs)
-    if (h.acn.on) {   // Newton-PCG: the plan in batches of at most ACN_MAX_BATCH items (without fin the caller passes one such batch)
+    if (h.kind == H2DKind::GRAYSCOTT_IMEX && 2 * pl.count > H2D_MAX_BATCH) return fail(MGRIT_HIP_EINVAL, "Gray-Scott batch of %d states", pl.count);   // (blockIdx.z, the work slabs)
+    if (h.newton()) {   // Newton-PCG: the plan in batches of at most ACN_MAX_BATCH items (without fin the caller passes one such batch)
         for (int off = 0; off < pl.count; off += ACN_MAX_BATCH) {
             H2DFin part{};   // the sweep's index lists from the batch's first item on, like the plan's
             if (fin) {
@@ -2840,49 +2872,12 @@ int h2d_phi_batch(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const dou
     double *const W0 = chain ? h.Wc0 : h.W0, *const W1 = chain ? h.Wc1 : h.W1;
     double *dinv = nullptr;
     if ((rc = h2d_dinv(e, lv, pl.dtbits, &dinv))) return rc;
-    if (h.gs) {   // Gray-Scott IMEX: the four products once for both species, items 2 b (u) and 2 b + 1 (v) of state b
+    if (h.periodic()) {   // IMEX on the periodic grid: four products with the full Hartley table, the non-linear right-hand side formed
+                          // while the first is staged; Gray-Scott once for both species, items 2 b (u) and 2 b + 1 (v) of state b
         double dt;
         std::memcpy(&dt, &pl.dtbits, 8);
-        const GSPre pre{dt, h.gs_a, h.gs_b, 0};
-        const int P = H.Mi;
-        const dim3 g(P / 64, P / 64, 2 * pl.count);
-        const H2DFin none{};
-        hipLaunchKernelGGL((gs_gemm_kernel<GS_FIRST>), g, dim3(256), 0, e->stream, h.acT, P, h.ac_KP, H.nx, in_slab, W1, nullptr, per,
-                           pl.d_in, H.ld, pre, H, none);
-        hipLaunchKernelGGL((gs_gemm_kernel<GS_SCALE>), g, dim3(256), 0, e->stream, h.acT, P, h.ac_KP, H.nx, W1, W0, dinv, per, nullptr, 0,
-                           pre, H, none);
-        hipLaunchKernelGGL((gs_gemm_kernel<GS_PLAIN>), g, dim3(256), 0, e->stream, h.acT, P, h.ac_KP, H.nx, W0, W1, nullptr, per, nullptr, 0,
-                           pre, H, none);
-        if (fin)
-            hipLaunchKernelGGL((gs_gemm_kernel<GS_FIN>), g, dim3(256), 0, e->stream, h.acT, P, h.ac_KP, H.nx, W1, W0, nullptr, per, nullptr,
-                               0, pre, H, *fin);
-        else
-            hipLaunchKernelGGL((gs_gemm_kernel<GS_PLAIN>), g, dim3(256), 0, e->stream, h.acT, P, h.ac_KP, H.nx, W1, W0, nullptr, per, nullptr,
-                               0, pre, H, none);
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
-    if (h.ac) {   // Allen-Cahn IMEX: four products with the full Hartley table, the non-linear right-hand side formed while staging the first
-        double dt;
-        std::memcpy(&dt, &pl.dtbits, 8);
-        const ACPre pre{dt * h.ac_inv_eps2, h.ac_nu};
-        const int P = H.Mi;
-        const dim3 g(P / 64, P / 64, pl.count);
-        const H2DFin none{};
-        hipLaunchKernelGGL((ac_gemm_kernel<AC_FIRST>), g, dim3(256), 0, e->stream, h.acT, P, h.ac_KP, H.nx, in_slab, W1, nullptr, per,
-                           pl.d_in, H.ld, pre, H, none);
-        hipLaunchKernelGGL((ac_gemm_kernel<AC_SCALE>), g, dim3(256), 0, e->stream, h.acT, P, h.ac_KP, H.nx, W1, W0, dinv, per, nullptr, 0,
-                           pre, H, none);
-        hipLaunchKernelGGL((ac_gemm_kernel<AC_PLAIN>), g, dim3(256), 0, e->stream, h.acT, P, h.ac_KP, H.nx, W0, W1, nullptr, per, nullptr, 0,
-                           pre, H, none);
-        if (fin)
-            hipLaunchKernelGGL((ac_gemm_kernel<AC_FIN>), g, dim3(256), 0, e->stream, h.acT, P, h.ac_KP, H.nx, W1, W0, nullptr, per, nullptr,
-                               0, pre, H, *fin);
-        else
-            hipLaunchKernelGGL((ac_gemm_kernel<AC_PLAIN>), g, dim3(256), 0, e->stream, h.acT, P, h.ac_KP, H.nx, W1, W0, nullptr, per, nullptr,
-                               0, pre, H, none);
-        HIP_TRY(hipGetLastError());
-        return 0;
+        if (h.kind == H2DKind::GRAYSCOTT_IMEX) return p2d_products(e, h, pl.count, GSPre{dt, h.gs.a, h.gs.b, 0}, in_slab, pl.d_in, dinv, W0, W1, W0, fin);
+        return p2d_products(e, h, pl.count, ACPre{dt * h.ac.inv_eps2, h.ac.nu}, in_slab, pl.d_in, dinv, W0, W1, W0, fin);
     }
     // W1[j][i'] = x to spectral slots ; W0[i'][j'] = y to spectral slots, o D ; W1[j'][i] = x back ; W0[i][j] = y back = U
     const dim3 fx(H.Mj / 64, H.Mi / 64, pl.count), fy(H.Mi / 64, H.Mj / 64, pl.count);        // (n tiles, slot tiles, items)
@@ -2921,7 +2916,7 @@ int h2d_phi_op(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const double
     int rc;
     // (the sequential coarsest-level solve keeps the epilogue kernel: fused, one step of one state took 107 instead of 92 us --
     // the last transform's 64 tiles then also carry the sweep's loads and the rim is a launch of its own)
-    if (lv.h2d->dev.theta != 0.0 && (!chain || lv.h2d->ac)) {   // (Allen-Cahn has no epilogue kernel: always fused)
+    if (lv.h2d->dev.theta != 0.0 && (!chain || lv.h2d->periodic())) {   // (the periodic levels have no epilogue kernel: always fused)
         const H2DFin fin{dst_slab, dst_ld, pl.d_dst, a_slab, pl.d_a, b_slab, pl.d_b, op, use_g, w, 1.0 - w};
         return h2d_phi_batch(e, lv, pl, in_slab, chain, &fin);
     }
@@ -2954,7 +2949,7 @@ bool h2d_block_ok(const Level &lv, int lvl) {
     // backward Euler, and (round 5) Crank-Nicolson: the explicit half of a step is diagonal in the same sine basis for an error
     // whose rim is zero -- every state of the level carries the boundary values there --, which h2d_block_solve checks per solve
     // Never for Allen-Cahn: the block solve superposes block defects, which holds for a linear Phi only.
-    if (!lv.h2d || lv.h2d->ac || lvl == 0 || !(lv.h2d->dev.theta == 1.0 || lv.h2d->dev.theta == 0.5)) return false;
+    if (!lv.h2d || lv.h2d->periodic() || lvl == 0 || !(lv.h2d->dev.theta == 1.0 || lv.h2d->dev.theta == 0.5)) return false;
     const int N = lv.dev.n_pts - 1;
     return N >= 4 * MGRIT_HIP_BLOCK_K && N / MGRIT_HIP_BLOCK_K <= H2D_MAX_BATCH;
 }
@@ -3088,6 +3083,14 @@ int h2d_block_solve(mgrit_hip_engine *e, int lvl, bool *stepped) {
     return 0;
 }
 
+// the h2d_rowsq_kernel instance of a level: FULL where the residual reads Phi on the whole grid (the periodic levels: no rim), one
+// block row per plane of a state
+auto h2d_rowsq_instance(const H2DHost &h, bool residual) {
+    const bool full = residual && h.periodic();
+    if (h.comps() == 2) return full ? &h2d_rowsq_kernel<true, 2> : &h2d_rowsq_kernel<false, 2>;
+    return full ? &h2d_rowsq_kernel<true> : &h2d_rowsq_kernel<false>;
+}
+
 // per-point sums of squares: Phi(u_{i-1}) - u_i (residual) or u_i - prev_i (jump)
 int h2d_points_sumsq(mgrit_hip_engine *e, int lvl, RunList *rl, const double *prev, double *out) {
     Level &lv = e->L[lvl];
@@ -3100,9 +3103,8 @@ int h2d_points_sumsq(mgrit_hip_engine *e, int lvl, RunList *rl, const double *pr
         // point's row against prev's. A Newton-PCG level leaves Phi in its work row x, a batch of at most ACN_MAX_BATCH items at a time
         // Gray-Scott: per (state, plane), a state's 2 nx row sums added u plane first
         const int nc = lv.h2d->comps();
-        const auto rowsq = lv.h2d->gs ? (prev ? &h2d_rowsq_kernel<false, 2> : &h2d_rowsq_kernel<true, 2>)
-                                      : !prev && lv.h2d->ac ? &h2d_rowsq_kernel<true> : &h2d_rowsq_kernel<false>;
-        const bool newton = !prev && lv.h2d->acn.on;
+        const auto rowsq = h2d_rowsq_instance(*lv.h2d, !prev);
+        const bool newton = !prev && lv.h2d->newton();
         const int part = newton ? ACN_MAX_BATCH : pl.count;
         for (int off = 0; off < pl.count; off += part) {
             const BatchPlan sub = batch_slice(pl, off, std::min(part, pl.count - off));
@@ -3603,7 +3605,7 @@ int periodic2d_tables(mgrit_hip_engine *e, Level &lv, H2DHost *h, int n_pts_loca
     const int P = ((nx + 63) / 64) * 64;
     H.nx = H.ny = H.mi = H.mj = nx; H.Mi = H.Mj = P;
     h->HPx = h->HPy = P / 2;
-    h->ac_KP = ((nx + H2D_BK - 1) / H2D_BK) * H2D_BK;
+    h->KP = ((nx + H2D_BK - 1) / H2D_BK) * H2D_BK;
     H.K = 0; H.n_pts = n_pts_local; H.ld = ld; H.fx = H.fy = 0.0; H.theta = 1.0; H.has_w = 0;
     h->dts = step_sizes(n_pts_local, t_local);
     // Hartley table (the angle reduced exactly: (i k) mod nx) and the eigenvalues of the periodic 5-point Laplacian
@@ -3621,9 +3623,31 @@ int periodic2d_tables(mgrit_hip_engine *e, Level &lv, H2DHost *h, int n_pts_loca
     }
     h->ly = h->lx;
     double *d_dt;
-    if ((rc = dev_upload(lv, e->stream, tab, &h->acT))) return rc;
+    if ((rc = dev_upload(lv, e->stream, tab, &h->T))) return rc;
     if ((rc = dev_upload(lv, e->stream, h->dts, &d_dt))) return rc;
     H.dt = d_dt;
+    return 0;
+}
+
+// What the 2-D level entry points share around their own checks and tables. The rule of the row stride (what = the state's size as
+// the message spells it):
+int check_ld_2d(int ld, int n, const char *what) {
+    if (ld < n || (ld % 16) != 0) return fail(MGRIT_HIP_EINVAL, "ld=%d must be a multiple of 16 and >= %s=%d", ld, what, n);
+    return 0;
+}
+// A fresh level with its H2DHost, tables(lv, h) for the application's own parameters and tables, then the level's description
+template <typename Tables>
+int level_2d(mgrit_hip_engine *e, int lvl, int stepper, H2DKind kind, int n, int ld, int n_pts_local, int K, Tables tables) {
+    int rc;
+    if ((rc = level_fresh(e, lvl))) return rc;
+    Level &lv = e->L[lvl];
+    H2DHost *h = lv.h2d = new H2DHost();
+    h->kind = kind;
+    if ((rc = tables(lv, h))) return rc;
+    lv.dev.kind = stepper;
+    lv.dev.n = n; lv.dev.ld = ld; lv.dev.T = 0; lv.dev.n_pts = n_pts_local; lv.dev.K = K; lv.dev.stream_rows = 0;
+    lv.G = 0;
+    lv.set = true;
     return 0;
 }
 
@@ -3803,56 +3827,50 @@ int mgrit_hip_level_heat2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const 
     int rc = check_level(e, lvl, false);
     if (rc) return rc;
     if (nx < 3 || ny < 3 || nx > 2050 || ny > 2050) return fail(MGRIT_HIP_EUNSUPPORTED, "Heat2D grid %dx%d outside [3,2050]^2", nx, ny);
-    if (ld < nx * ny || (ld % 16) != 0) return fail(MGRIT_HIP_EINVAL, "ld=%d must be a multiple of 16 and >= nx*ny=%d", ld, nx * ny);
+    if ((rc = check_ld_2d(ld, nx * ny, "nx*ny"))) return rc;
     if (!(theta == 0.0 || theta == 0.5 || theta == 1.0)) return fail(MGRIT_HIP_EINVAL, "theta must be 0 (FE), 0.5 (CN) or 1 (BE)");
     if (no_time_grid(n_pts_local, t_local) || !bc) return fail(MGRIT_HIP_EINVAL, "bad arguments");
     if ((rc = check_forcing(K, n_pts_local, S, tau != nullptr))) return rc;
-    if ((rc = level_fresh(e, lvl))) return rc;
-    Level &lv = e->L[lvl];
-    H2DHost *h = new H2DHost();
-    lv.h2d = h;
-    H2DDev &H = h->dev;
-    H.nx = nx; H.ny = ny; H.mi = nx - 2; H.mj = ny - 2;
-    h->HPx = (((H.mi + 1) / 2 + 63) / 64) * 64; h->HPy = (((H.mj + 1) / 2 + 63) / 64) * 64;
-    H.Mi = 2 * h->HPx; H.Mj = 2 * h->HPy;   // one padded length per axis for the natural and the spectral layout
-    H.K = K; H.n_pts = n_pts_local; H.ld = ld; H.fx = fx; H.fy = fy; H.theta = theta;
-    h->dts = step_sizes(n_pts_local, t_local);
-    // tables
-    std::vector<double> fxe, fxo, fxet, fxot, fye, fyo, fyet, fyot;
-    h2d_axis_tables(H.mi, h->HPx, fx, fxe, fxo, fxet, fxot, h->lx);
-    h2d_axis_tables(H.mj, h->HPy, fy, fye, fyo, fyet, fyot, h->ly);
-    std::vector<double> W((size_t)H.Mi * H.Mj, 0.0), Sp((size_t)(K > 0 ? K : 0) * H.Mi * H.Mj, 0.0);
-    H.has_w = 0;
-    for (int a = 0; a < H.mi; ++a)
-        for (int b = 0; b < H.mj; ++b) {
-            double w = 0.0;
-            if (a == 0) w += fx * bc[(size_t)0 * ny + b + 1];
-            if (a == H.mi - 1) w += fx * bc[(size_t)(nx - 1) * ny + b + 1];
-            if (b == 0) w += fy * bc[(size_t)(a + 1) * ny + 0];
-            if (b == H.mj - 1) w += fy * bc[(size_t)(a + 1) * ny + ny - 1];
-            W[(size_t)a * H.Mj + b] = w;
-            if (w != 0.0) H.has_w = 1;
-        }
-    for (int k = 0; k < K; ++k)
+    return level_2d(e, lvl, MGRIT_HIP_STEPPER_HEAT2D, H2DKind::HEAT2D, nx * ny, ld, n_pts_local, K, [&](Level &lv, H2DHost *h) {
+        H2DDev &H = h->dev;
+        H.nx = nx; H.ny = ny; H.mi = nx - 2; H.mj = ny - 2;
+        h->HPx = (((H.mi + 1) / 2 + 63) / 64) * 64; h->HPy = (((H.mj + 1) / 2 + 63) / 64) * 64;
+        H.Mi = 2 * h->HPx; H.Mj = 2 * h->HPy;   // one padded length per axis for the natural and the spectral layout
+        H.K = K; H.n_pts = n_pts_local; H.ld = ld; H.fx = fx; H.fy = fy; H.theta = theta;
+        h->dts = step_sizes(n_pts_local, t_local);
+        // tables
+        std::vector<double> fxe, fxo, fxet, fxot, fye, fyo, fyet, fyot;
+        h2d_axis_tables(H.mi, h->HPx, fx, fxe, fxo, fxet, fxot, h->lx);
+        h2d_axis_tables(H.mj, h->HPy, fy, fye, fyo, fyet, fyot, h->ly);
+        std::vector<double> W((size_t)H.Mi * H.Mj, 0.0), Sp((size_t)(K > 0 ? K : 0) * H.Mi * H.Mj, 0.0);
+        H.has_w = 0;
         for (int a = 0; a < H.mi; ++a)
-            for (int b = 0; b < H.mj; ++b) Sp[((size_t)k * H.Mi + a) * H.Mj + b] = S[((size_t)k * H.mi + a) * H.mj + b];
-    double *d_bc, *d_W, *d_S, *d_tau, *d_dt;
-    if ((rc = dev_upload(lv, e->stream, fxe, &h->Fxe)) || (rc = dev_upload(lv, e->stream, fxo, &h->Fxo)) ||
-        (rc = dev_upload(lv, e->stream, fxet, &h->FxeT)) || (rc = dev_upload(lv, e->stream, fxot, &h->FxoT)) ||
-        (rc = dev_upload(lv, e->stream, fye, &h->Fye)) || (rc = dev_upload(lv, e->stream, fyo, &h->Fyo)) ||
-        (rc = dev_upload(lv, e->stream, fyet, &h->FyeT)) || (rc = dev_upload(lv, e->stream, fyot, &h->FyoT)))
-        return rc;
-    if ((rc = dev_upload(lv, e->stream, bc, (size_t)nx * ny, &d_bc))) return rc;
-    if ((rc = dev_upload(lv, e->stream, W, &d_W))) return rc;
-    if ((rc = dev_upload(lv, e->stream, Sp, &d_S))) return rc;
-    if ((rc = dev_upload(lv, e->stream, tau, K > 0 ? (size_t)K * n_pts_local : 0, &d_tau))) return rc;
-    if ((rc = dev_upload(lv, e->stream, h->dts, &d_dt))) return rc;
-    H.bc = d_bc; H.W = d_W; H.S = d_S; H.tstop = d_tau; H.dt = d_dt;
-    lv.dev.kind = MGRIT_HIP_STEPPER_HEAT2D;
-    lv.dev.n = nx * ny; lv.dev.ld = ld; lv.dev.T = 0; lv.dev.n_pts = n_pts_local; lv.dev.K = K; lv.dev.stream_rows = 0;
-    lv.G = 0;
-    lv.set = true;
-    return 0;
+            for (int b = 0; b < H.mj; ++b) {
+                double w = 0.0;
+                if (a == 0) w += fx * bc[(size_t)0 * ny + b + 1];
+                if (a == H.mi - 1) w += fx * bc[(size_t)(nx - 1) * ny + b + 1];
+                if (b == 0) w += fy * bc[(size_t)(a + 1) * ny + 0];
+                if (b == H.mj - 1) w += fy * bc[(size_t)(a + 1) * ny + ny - 1];
+                W[(size_t)a * H.Mj + b] = w;
+                if (w != 0.0) H.has_w = 1;
+            }
+        for (int k = 0; k < K; ++k)
+            for (int a = 0; a < H.mi; ++a)
+                for (int b = 0; b < H.mj; ++b) Sp[((size_t)k * H.Mi + a) * H.Mj + b] = S[((size_t)k * H.mi + a) * H.mj + b];
+        double *d_bc, *d_W, *d_S, *d_tau, *d_dt;
+        if ((rc = dev_upload(lv, e->stream, fxe, &h->Fxe)) || (rc = dev_upload(lv, e->stream, fxo, &h->Fxo)) ||
+            (rc = dev_upload(lv, e->stream, fxet, &h->FxeT)) || (rc = dev_upload(lv, e->stream, fxot, &h->FxoT)) ||
+            (rc = dev_upload(lv, e->stream, fye, &h->Fye)) || (rc = dev_upload(lv, e->stream, fyo, &h->Fyo)) ||
+            (rc = dev_upload(lv, e->stream, fyet, &h->FyeT)) || (rc = dev_upload(lv, e->stream, fyot, &h->FyoT)))
+            return rc;
+        if ((rc = dev_upload(lv, e->stream, bc, (size_t)nx * ny, &d_bc))) return rc;
+        if ((rc = dev_upload(lv, e->stream, W, &d_W))) return rc;
+        if ((rc = dev_upload(lv, e->stream, Sp, &d_S))) return rc;
+        if ((rc = dev_upload(lv, e->stream, tau, K > 0 ? (size_t)K * n_pts_local : 0, &d_tau))) return rc;
+        if ((rc = dev_upload(lv, e->stream, h->dts, &d_dt))) return rc;
+        H.bc = d_bc; H.W = d_W; H.S = d_S; H.tstop = d_tau; H.dt = d_dt;
+        return 0;
+    });
 }
 
 int mgrit_hip_level_allencahn2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld, double inv_dx2,
@@ -3860,20 +3878,13 @@ int mgrit_hip_level_allencahn2d(mgrit_hip_engine *e, int lvl, int n_pts_local, c
     int rc = check_level(e, lvl, false);
     if (rc) return rc;
     if (nx < 4 || nx > 2048) return fail(MGRIT_HIP_EUNSUPPORTED, "Allen-Cahn grid %dx%d outside [4,2048]^2", nx, nx);
-    if (ld < nx * nx || (ld % 16) != 0) return fail(MGRIT_HIP_EINVAL, "ld=%d must be a multiple of 16 and >= nx*nx=%d", ld, nx * nx);
+    if ((rc = check_ld_2d(ld, nx * nx, "nx*nx"))) return rc;
     if (nu < 1 || nu > 64 || !(inv_dx2 > 0.0) || !(inv_eps2 > 0.0)) return fail(MGRIT_HIP_EINVAL, "bad Allen-Cahn parameters (nu=%d)", nu);
     if (no_time_grid(n_pts_local, t_local)) return fail(MGRIT_HIP_EINVAL, "bad arguments");
-    if ((rc = level_fresh(e, lvl))) return rc;
-    Level &lv = e->L[lvl];
-    H2DHost *h = new H2DHost();
-    lv.h2d = h;
-    h->ac = true; h->ac_inv_eps2 = inv_eps2; h->ac_inv_dx2 = inv_dx2; h->ac_nu = nu;
-    if ((rc = periodic2d_tables(e, lv, h, n_pts_local, t_local, nx, ld, inv_dx2))) return rc;
-    lv.dev.kind = MGRIT_HIP_STEPPER_ALLENCAHN2D;
-    lv.dev.n = nx * nx; lv.dev.ld = ld; lv.dev.T = 0; lv.dev.n_pts = n_pts_local; lv.dev.K = 0; lv.dev.stream_rows = 0;
-    lv.G = 0;
-    lv.set = true;
-    return 0;
+    return level_2d(e, lvl, MGRIT_HIP_STEPPER_ALLENCAHN2D, H2DKind::ALLENCAHN_IMEX, nx * nx, ld, n_pts_local, 0, [&](Level &lv, H2DHost *h) {
+        h->ac = {inv_dx2, inv_eps2, nu};
+        return periodic2d_tables(e, lv, h, n_pts_local, t_local, nx, ld, inv_dx2);
+    });
 }
 
 int mgrit_hip_level_grayscott2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld, double inv_dx2,
@@ -3881,23 +3892,15 @@ int mgrit_hip_level_grayscott2d(mgrit_hip_engine *e, int lvl, int n_pts_local, c
     int rc = check_level(e, lvl, false);
     if (rc) return rc;
     if (nx < 4 || nx > 2048) return fail(MGRIT_HIP_EUNSUPPORTED, "Gray-Scott grid %dx%d outside [4,2048]^2", nx, nx);
-    if (ld < 2 * nx * nx || (ld % 16) != 0) return fail(MGRIT_HIP_EINVAL, "ld=%d must be a multiple of 16 and >= 2*nx*nx=%d", ld, 2 * nx * nx);
+    if ((rc = check_ld_2d(ld, 2 * nx * nx, "2*nx*nx"))) return rc;
     if (!(inv_dx2 > 0.0) || !(du > 0.0) || !(dv > 0.0) || !std::isfinite(inv_dx2) || !std::isfinite(du) || !std::isfinite(dv) ||
         !std::isfinite(a) || !std::isfinite(b))
         return fail(MGRIT_HIP_EINVAL, "bad Gray-Scott parameters (du=%g, dv=%g must be positive, a=%g, b=%g finite)", du, dv, a, b);
     if (no_time_grid(n_pts_local, t_local)) return fail(MGRIT_HIP_EINVAL, "bad arguments");
-    if ((rc = level_fresh(e, lvl))) return rc;
-    Level &lv = e->L[lvl];
-    H2DHost *h = new H2DHost();
-    lv.h2d = h;
-    h->ac = true; h->ac_inv_dx2 = inv_dx2;
-    h->gs = true; h->gs_du = du; h->gs_dv = dv; h->gs_a = a; h->gs_b = b;
-    if ((rc = periodic2d_tables(e, lv, h, n_pts_local, t_local, nx, ld, inv_dx2))) return rc;
-    lv.dev.kind = MGRIT_HIP_STEPPER_GRAYSCOTT2D;
-    lv.dev.n = 2 * nx * nx; lv.dev.ld = ld; lv.dev.T = 0; lv.dev.n_pts = n_pts_local; lv.dev.K = 0; lv.dev.stream_rows = 0;
-    lv.G = 0;
-    lv.set = true;
-    return 0;
+    return level_2d(e, lvl, MGRIT_HIP_STEPPER_GRAYSCOTT2D, H2DKind::GRAYSCOTT_IMEX, 2 * nx * nx, ld, n_pts_local, 0, [&](Level &lv, H2DHost *h) {
+        h->gs = {du, dv, a, b};
+        return periodic2d_tables(e, lv, h, n_pts_local, t_local, nx, ld, inv_dx2);
+    });
 }
 
 int mgrit_hip_level_allencahn2d_newton(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld, double inv_dx2,
@@ -3926,7 +3929,7 @@ int mgrit_hip_level_allencahn2d_newton(mgrit_hip_engine *e, int lvl, int n_pts_l
     HIP_TRY(hipEventCreateWithFlags(&N.ev, hipEventDisableTiming));
     HIP_TRY(hipMalloc(reinterpret_cast<void **>(&N.tot), 4 * sizeof(unsigned long long)));
     HIP_TRY(hipMemsetAsync(N.tot, 0, 4 * sizeof(unsigned long long), e->stream));
-    N.on = true;
+    e->L[lvl].h2d->kind = H2DKind::ALLENCAHN_NEWTON;
     e->L[lvl].set = true;
     return 0;
 }
@@ -3934,7 +3937,7 @@ int mgrit_hip_level_allencahn2d_newton(mgrit_hip_engine *e, int lvl, int n_pts_l
 int mgrit_hip_newton_stats(mgrit_hip_engine *e, int lvl, int64_t out[4]) {
     int rc = check_level(e, lvl);
     if (rc) return rc;
-    if (!out || !e->L[lvl].h2d || !e->L[lvl].h2d->acn.on) return fail(MGRIT_HIP_EINVAL, "level %d is not an Allen-Cahn Newton level", lvl);
+    if (!out || !e->L[lvl].h2d || !e->L[lvl].h2d->newton()) return fail(MGRIT_HIP_EINVAL, "level %d is not an Allen-Cahn Newton level", lvl);
     H2DHost::Newton &N = e->L[lvl].h2d->acn;
     unsigned long long host[4];
     HIP_TRY(hipMemcpyAsync(host, N.tot, sizeof(host), hipMemcpyDeviceToHost, e->stream));
@@ -3974,7 +3977,7 @@ int mgrit_hip_level_heat2d_forcing_rows(mgrit_hip_engine *e, int lvl, const doub
     int rc = check_level(e, lvl);
     if (rc) return rc;
     Level &lv = e->L[lvl];
-    if (!lv.h2d || lv.h2d->ac) return fail(MGRIT_HIP_EUNSUPPORTED, "level %d is not a Heat2D level", lvl);
+    if (!lv.h2d || lv.h2d->periodic()) return fail(MGRIT_HIP_EUNSUPPORTED, "level %d is not a Heat2D level", lvl);
     if (rows && lv.h2d->dev.K != 0) return fail(MGRIT_HIP_EINVAL, "level %d already has %d separable forcing terms", lvl, lv.h2d->dev.K);
     lv.h2d->dev.fb = rows;
     return 0;
@@ -4080,7 +4083,7 @@ int mgrit_hip_level_transfer(mgrit_hip_engine *e, int lvl, int kind) {
     } else if (kind == MGRIT_HIP_TRANSFER_HEAT2D || kind == MGRIT_HIP_TRANSFER_PERIODIC2D) {
         const H2DHost *hf = e->L[lvl].h2d, *hc = e->L[lvl + 1].h2d;
         const bool per = kind == MGRIT_HIP_TRANSFER_PERIODIC2D;
-        if (!hf || !hc || hf->ac != per || hc->ac != per || hf->gs || hc->gs)
+        if (!hf || !hc || (per ? !hf->allencahn() || !hc->allencahn() : hf->periodic() || hc->periodic()))
             return fail(MGRIT_HIP_EUNSUPPORTED, per ? "the periodic 2-D transfer joins two Allen-Cahn levels" : "the Heat2D transfer joins two Heat2D levels");
         const int off = per ? 0 : 1;
         if (2 * hc->dev.nx - off != hf->dev.nx || 2 * hc->dev.ny - off != hf->dev.ny)

@@ -20,7 +20,7 @@ def main():
     names = subprocess.run(["c++filt"] + [r[0] for r in rows], capture_output=True, text=True).stdout.split("\n")
     print(f"{'kernel':70s} VGPR AGPR sgprSpill vgprSpill scratchB occ LDS")
     for r, nm in zip(rows, names):
-        nm = re.sub(r"^void \(anonymous namespace\)::", "", nm)
+        nm = re.sub(r"^void ", "", nm.replace("(anonymous namespace)::", ""))
         nm = re.sub(r"\(.*$", "", nm)
         if want and not any(w in nm for w in want):
             continue
