@@ -130,8 +130,22 @@ int mgrit_hip_level_grayscott2d(mgrit_hip_engine *e, int lvl, int n_pts_local, c
 int mgrit_hip_level_allencahn2d_newton(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld,
                                        double inv_dx2, double inv_eps2, int nu, double theta, double newton_tol, int newton_maxiter,
                                        double lin_tol, int lin_maxiter);
-/* out = { Phi evaluated, Newton iterations, CG iterations, items that ended at newton_maxiter } of a Newton level since the last call
- * (the call resets the counts; it waits for the engine's stream). */
+/* GrayScott with method = 'IMPL' and linear_solver = 'bicgstab' ("The Newton-BiCGStab step"): the level of
+ * mgrit_hip_level_grayscott2d -- the same argument checks with the same codes and texts --, whose Phi is Newton's method on
+ * F(x) = x - dt rate(x) - w from x = w, with every correction J(x) delta = g by right-preconditioned BiCGStab (shadow residual g,
+ * matrix-free Jacobian), preconditioned with blockdiag((1 + dt a) I - dt du L, (1 + dt b) I - dt dv L) through the Hartley products of
+ * both species. Per item: at most newton_maxiter Newton iterations, stopped before the solve once norm_inf(g) < newton_tol; at most
+ * lin_maxiter BiCGStab iterations each, stopped at norm_2(s) or norm_2(r) <= lin_tol norm_2(g) or on a breakdown, the delta accumulated
+ * so far being used. MGRIT_HIP_EINVAL for negative or NaN tolerances or caps. No step size is refused: where dt mu < 1 on the box of the
+ * data the step has one solution; beyond it the root found may differ from the one a direct solver finds. The host
+ * reads one word per Newton iteration and per few inner iterations, so such a level never runs inside a captured graph. */
+int mgrit_hip_level_grayscott2d_newton(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld,
+                                       double inv_dx2, double du, double dv, double a, double b, double newton_tol, int newton_maxiter,
+                                       double lin_tol, int lin_maxiter);
+/* out = { Phi evaluated, Newton iterations, inner (CG / BiCGStab) iterations, items that ended at newton_maxiter } of a Newton level
+ * (Allen-Cahn or Gray-Scott) since the last call (the call resets the counts; it waits for the engine's stream). The last count is of
+ * items that took all newton_maxiter corrections: no test follows the last one (as in the numpy steps), so such an item may well have
+ * converged with it -- the count says "the cap was reached", not "not converged". */
 int mgrit_hip_newton_stats(mgrit_hip_engine *e, int lvl, int64_t out[4]);
 /* Device slabs u, v, g of Mgrit.create_u_v_g (mgrit.py:840-858); v and g may be NULL on level 0. */
 int mgrit_hip_level_bind(mgrit_hip_engine *e, int lvl, double *u, double *v, double *g);

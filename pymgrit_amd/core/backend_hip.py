@@ -211,7 +211,7 @@ class HipBackend:
         from pymgrit_amd.core.grid_transfer_copy import GridTransferCopy
         if any(d["kind"] != "grayscott2d" for d in self.desc) or len({d["nx"] for d in self.desc}) != 1:
             raise MgritHipError("Gray-Scott levels on the HIP engine: every level of the hierarchy must be a GrayScott application "
-                                "with method='IMEX' on the same nx")
+                                "with method='IMEX', or 'IMPL' with linear_solver='bicgstab', on the same nx")
         if any(type(tr) is not GridTransferCopy for tr in mg.transfer_objects):
             raise MgritHipError("Gray-Scott levels on the HIP engine: GridTransferCopy only (no spatial coarsening)")
         if mg.comm_time_size > 1:
@@ -293,11 +293,13 @@ class HipBackend:
             check(self.lib.mgrit_hip_level_allencahn2d(*common))
 
     def _describe_grayscott2d(self, engine_lvl, d, t_local, n, ld):
-        """IMEX, two planes per state (through hip_lib like the Newton form above)"""
-        hip_lib.level_grayscott2d(self.h, engine_lvl, t_local.size, _ptr(t_local), ld, d)
+        """IMEX, two planes per state, or -- a description that carries theta -- the Newton-BiCGStab step of IMPL (DESIGN.md 3.11;
+        through hip_lib like the Allen-Cahn Newton form above)"""
+        describe = hip_lib.level_grayscott2d_newton if "theta" in d else hip_lib.level_grayscott2d
+        describe(self.h, engine_lvl, t_local.size, _ptr(t_local), ld, d)
 
     def newton_stats(self, lvl):
-        """counts of an Allen-Cahn Newton-PCG level since the last call (which resets them)"""
+        """counts of a Newton level (Allen-Cahn PCG, Gray-Scott BiCGStab) since the last call (which resets them)"""
         return hip_lib.newton_stats(self.h, lvl)
 
     _DESCRIBE = {"heat1d": _describe_heat1d, "heat1d_2pts": _describe_heat1d_2pts, "advection1d": _describe_advection1d,

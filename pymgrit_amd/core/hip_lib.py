@@ -51,6 +51,8 @@ EXPORTS = {
                                                      C.c_double, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_int]),
     "mgrit_hip_level_grayscott2d": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double,
                                               C.c_double, C.c_double, C.c_double]),
+    "mgrit_hip_level_grayscott2d_newton": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double,
+                                                     C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, C.c_int]),
     "mgrit_hip_newton_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "mgrit_hip_level_bind": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgrit_hip_chain_enable": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -180,8 +182,16 @@ def level_grayscott2d(h, engine_lvl, n_pts, t_ptr, ld, d):
                                              float(d["dv"]), float(d["a"]), float(d["b"])))
 
 
+def level_grayscott2d_newton(h, engine_lvl, n_pts, t_ptr, ld, d):
+    """describe a Gray-Scott level whose Phi is the Newton-BiCGStab step; d: the application's description"""
+    check(load().mgrit_hip_level_grayscott2d_newton(h, engine_lvl, n_pts, t_ptr, int(d["nx"]), ld, float(d["inv_dx2"]), float(d["du"]),
+                                                    float(d["dv"]), float(d["a"]), float(d["b"]), float(d["newton_tol"]),
+                                                    int(d["newton_maxiter"]), float(d["lin_tol"]), int(d["lin_maxiter"])))
+
+
 def newton_stats(h, lvl):
-    """{phi, newton_iterations, cg_iterations, at_newton_maxiter} of a Newton-PCG level since the last call (which resets them)"""
+    """{phi, newton_iterations, cg_iterations, at_newton_maxiter} of a Newton level since the last call (which resets them);
+    cg_iterations counts the inner iterations: CG (Allen-Cahn) or BiCGStab (Gray-Scott)"""
     out = (C.c_int64 * 4)()
     check(load().mgrit_hip_newton_stats(h, int(lvl), out))
     return dict(zip(("phi", "newton_iterations", "cg_iterations", "at_newton_maxiter"), (int(v) for v in out)))

@@ -17,8 +17,9 @@
 //   3. W1[z][j'][i]  = sum_i' T[i'][i]  W0[z][i'][j']                                                                      P2D_PLAIN
 //   4. x_c[i][j]     = sum_j' T[j'][j]  W1[z][j'][i]   through the sweep's arithmetic at offset c nx^2 + i nx + j of the
 //                                                      destination row (P2D_FIN), or into the work slab (P2D_PLAIN: norms)
-// P2D_WORK_PLAIN / P2D_WORK_SCALE: the products of the Newton-PCG preconditioner -- as P2D_PLAIN / P2D_SCALE, but in_idx[item] is the
-// item's "CG running" flag and a workgroup of an item whose flag is 0 returns at once.
+// P2D_WORK_PLAIN / P2D_WORK_SCALE: the products of the Newton steps' preconditioners (Allen-Cahn PCG, Gray-Scott BiCGStab) -- as
+// P2D_PLAIN / P2D_SCALE, but in_idx[state] is the "inner iteration running" flag of the item's state z / NC and a workgroup of an
+// item whose state's flag is 0 returns at once.
 // ===============================================================================================================
 enum { P2D_FIRST = 0, P2D_SCALE = 1, P2D_PLAIN = 2, P2D_FIN = 3, P2D_WORK_PLAIN = 4, P2D_WORK_SCALE = 5 };
 
@@ -37,7 +38,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const unsigned z = blockIdx.z, st = z / NC, comp = z % NC;   // item, its state, its plane
     const size_t plane = (size_t)nx * nx;
-    if (MODE >= P2D_WORK_PLAIN && !in_idx[z]) return;
+    if (MODE >= P2D_WORK_PLAIN && !in_idx[st]) return;
     h2d_stagger();
     const int n0 = blockIdx.x * 64, m0 = blockIdx.y * 64;
     d4_t acc[2][2];
