@@ -35,7 +35,8 @@ typedef struct mgrit_hip_engine mgrit_hip_engine;
 
 enum { MGRIT_HIP_OK = 0, MGRIT_HIP_EINVAL = -1, MGRIT_HIP_EHIP = -2, MGRIT_HIP_ENODEV = -3, MGRIT_HIP_EUNSUPPORTED = -4 };
 enum { MGRIT_HIP_STEPPER_HEAT1D = 1, MGRIT_HIP_STEPPER_ADVECTION1D = 2, MGRIT_HIP_STEPPER_HEAT2D = 3,
-       MGRIT_HIP_STEPPER_HEAT1D_2PTS = 4, MGRIT_HIP_STEPPER_ALLENCAHN2D = 5, MGRIT_HIP_STEPPER_GRAYSCOTT2D = 6 };
+       MGRIT_HIP_STEPPER_HEAT1D_2PTS = 4, MGRIT_HIP_STEPPER_ALLENCAHN2D = 5, MGRIT_HIP_STEPPER_GRAYSCOTT2D = 6,
+       MGRIT_HIP_STEPPER_CAHNHILLIARD2D = 7 };
 enum { MGRIT_HIP_TRANSFER_COPY = 0, MGRIT_HIP_TRANSFER_HEAT1D = 1, MGRIT_HIP_TRANSFER_PERIODIC1D = 2,
        /* the caller applies restriction / interpolation itself (a user's GridTransfer, reference core/grid_transfer.py:31-55:
           any Python code): mgrit_hip_restrict_u / _fas_rhs / _error_correction / _interpolate refuse the level pair, the FAS
@@ -44,7 +45,7 @@ enum { MGRIT_HIP_TRANSFER_COPY = 0, MGRIT_HIP_TRANSFER_HEAT1D = 1, MGRIT_HIP_TRA
        /* 2-D grids halved per axis (no reference class; arithmetic: DESIGN.md 3.10, csrc/mgrit_hip_transfer2d.inc): between two Heat2D
           levels, grids with their rim, fine nx = 2*coarse nx - 1 and fine ny = 2*coarse ny - 1 (rim injected, interior 9-point full
           weighting, bilinear interpolation); between two Allen-Cahn levels, periodic, fine nx = 2*coarse nx (the same stencils with
-          wrap-around). The sizes are those of the level descriptions; any other pairing is MGRIT_HIP_EUNSUPPORTED. */
+          wrap-around), and likewise between two Cahn-Hilliard levels (never one of each). The sizes are those of the level descriptions; any other pairing is MGRIT_HIP_EUNSUPPORTED. */
        MGRIT_HIP_TRANSFER_HEAT2D = 4, MGRIT_HIP_TRANSFER_PERIODIC2D = 5 };
 enum { MGRIT_HIP_RELAX_F = 0, MGRIT_HIP_RELAX_C = 1, MGRIT_HIP_RELAX_CHAIN = 2,
        /* f_relax + c_relax (mgrit.py:270-275) of a level > 0 in one pass, valid right after the finer level's FAS sweep has
@@ -120,6 +121,16 @@ int mgrit_hip_level_allencahn2d(mgrit_hip_engine *e, int lvl, int n_pts_local, c
  * the copy transfer (the 2-D spatial transfers refuse such a level), no time-parallel forward solve. Norms run over all 2 nx^2 values. */
 int mgrit_hip_level_grayscott2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld,
                                 double inv_dx2, double du, double dv, double a, double b);
+/* CahnHilliard with method = 'IMEX' (cahn_hilliard/cahn_hilliard.py; no reference class) on the periodic nx x nx grid,
+ * 4 <= nx <= 2048: rows as for an Allen-Cahn level, n = nx^2, ld >= nx^2 a multiple of 16. The linearly stabilised step
+ * (I + dt (eps2 L^2 - stab L)) x = u + dt L w, w = u^3 - (1 + stab) u, L the periodic 5-point Laplacian / dx^2, through the Hartley
+ * tables of mgrit_hip_level_allencahn2d: x = T ((T u T) o D1 + (T w T) o D2) T, D1 = 1 / (1 + dt (eps2 mu^2 + stab mu)),
+ * D2 = -(dt mu) D1, mu = lam_i + lam_j -- two forward transforms per state joined mode by mode, one inverse transform, six batched
+ * item-products on the FP64 matrix cores per step. eps2 > 0, stab >= 0, all parameters finite (MGRIT_HIP_EINVAL "bad Cahn-Hilliard
+ * parameters" otherwise). Everything said of an Allen-Cahn IMEX level holds: the Heat2D entry points, the copy transfer, the caller's,
+ * or MGRIT_HIP_TRANSFER_PERIODIC2D between two such levels; no time-parallel forward solve. */
+int mgrit_hip_level_cahnhilliard2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld,
+                                   double inv_dx2, double eps2, double stab);
 /* AllenCahn with method = 'IMPL' (theta = 1) or 'CN' (theta = 0.5) and linear_solver = 'pcg' (DESIGN.md 3.9): the level of
  * mgrit_hip_level_allencahn2d, whose Phi is Newton's method on x - fac (L x + r(x) / eps^2) = rhs, fac = theta dt, with every
  * correction by conjugate gradients preconditioned with (1 + fac nu / eps^2) I - fac L through the Hartley products. Per item: at most

@@ -3,8 +3,8 @@
 Same public names as the reference package for everything on the hot path (``Mgrit``, ``AtMgrit``, ``Application``, ``Vector``,
 ``GridTransfer``, ``GridTransferCopy``, ``simple_setup_problem``, ``Dahlquist``, ``Heat1D``, ``Heat1DBDF1``, ``Heat1DBDF2``,
 ``Heat2D``, ``Advection1D``, ``AllenCahn``), the Gray-Scott system of the reference's PETSc examples in numpy with its IMEX step on the
-device (``GrayScott``), plus the spatial-coarsening transfers that run as HIP kernels (``GridTransferHeat``,
-``GridTransferAdvection``, ``GridTransferHeat2D``, ``GridTransferAllenCahn``).
+device (``GrayScott``), the Cahn-Hilliard equation with its stabilised IMEX step on the device (``CahnHilliard``), plus the spatial-coarsening transfers that run as HIP kernels (``GridTransferHeat``,
+``GridTransferAdvection``, ``GridTransferHeat2D``, ``GridTransferAllenCahn``, ``GridTransferCahnHilliard``).
 """
 from pymgrit_amd.core.application import Application
 from pymgrit_amd.core.vector import Vector
@@ -25,6 +25,8 @@ from pymgrit_amd.heat.grid_transfer_heat_2d import GridTransferHeat2D
 from pymgrit_amd.allen_cahn.allen_cahn import AllenCahn, VectorAllenCahn2D
 from pymgrit_amd.allen_cahn.grid_transfer_allen_cahn import GridTransferAllenCahn
 from pymgrit_amd.gray_scott.gray_scott import GrayScott, VectorGrayScott2D
+from pymgrit_amd.cahn_hilliard.cahn_hilliard import CahnHilliard, VectorCahnHilliard2D
+from pymgrit_amd.cahn_hilliard.grid_transfer_cahn_hilliard import GridTransferCahnHilliard
 from pymgrit_amd.advection.advection_1d import Advection1D
 from pymgrit_amd.advection.grid_transfer_advection import GridTransferAdvection
 
@@ -40,4 +42,5 @@ def elementwise(f):
 
 __all__ = ["elementwise", "Application", "Vector", "GridTransfer", "GridTransferCopy", "simple_setup_problem", "Mgrit", "AtMgrit", "Dahlquist",
            "Heat1D", "Heat1DBDF1", "Heat1DBDF2", "Heat2D", "GridTransferHeat", "Advection1D", "GridTransferAdvection", "AllenCahn", "VectorAllenCahn2D", "VectorHeat1D2Pts",
-           "GridTransferHeat2D", "GridTransferAllenCahn", "GrayScott", "VectorGrayScott2D"]
+           "GridTransferHeat2D", "GridTransferAllenCahn", "GrayScott", "VectorGrayScott2D",
+           "CahnHilliard", "VectorCahnHilliard2D", "GridTransferCahnHilliard"]

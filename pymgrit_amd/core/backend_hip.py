@@ -111,7 +111,7 @@ class SlabVectorList:
         return (self[k] for k in range(len(self)))
 
 
-GRID_2D = ("heat2d", "allencahn2d", "grayscott2d")   # states are whole 2-D grids in natural row-major order (Gray-Scott: two of them,
+GRID_2D = ("heat2d", "allencahn2d", "grayscott2d", "cahnhilliard2d")   # states are whole 2-D grids in natural row-major order (Gray-Scott: two of them,
                                                      # [u plane | v plane]); the engine's Heat2D route
 
 
@@ -133,6 +133,8 @@ class HipBackend:
             self._check_allencahn(mg)
         if any(d["kind"] == "grayscott2d" for d in self.desc):
             self._check_grayscott(mg)
+        if any(d["kind"] == "cahnhilliard2d" for d in self.desc):
+            self._check_cahnhilliard(mg)
         self.n = [int(d["n"]) for d in self.desc]
         # 1-D steppers: lane-blocked rows; Heat2D: the nx x ny grid in natural row-major order
         # two-point states: the row is [first | second], each half lane-blocked like a 1-D row of n values
@@ -221,6 +223,20 @@ class HipBackend:
         if not mg.global_conv_crit:
             raise MgritHipError("Gray-Scott levels on the HIP engine: the global convergence criteria only (conv_crit 0 or 1)")
 
+    def _check_cahnhilliard(self, mg):
+        """what the Cahn-Hilliard device path does not cover is refused by name, never run differently (transfers: as for Allen-Cahn
+        levels -- GridTransferCopy, GridTransferCahnHilliard, or a user's GridTransfer through its Python methods)"""
+        from pymgrit_amd.core.at_mgrit import AtMgrit
+        if any(d["kind"] != "cahnhilliard2d" for d in self.desc):
+            raise MgritHipError("Cahn-Hilliard levels on the HIP engine: every level of the hierarchy must be a CahnHilliard "
+                                "application (method='IMEX')")
+        if mg.comm_time_size > 1:
+            raise MgritHipError("Cahn-Hilliard levels on the HIP engine: one time rank only")
+        if isinstance(mg, AtMgrit):
+            raise MgritHipError("Cahn-Hilliard levels on the HIP engine: AT-MGRIT is not supported, use Mgrit")
+        if not mg.global_conv_crit:
+            raise MgritHipError("Cahn-Hilliard levels on the HIP engine: the global convergence criteria only (conv_crit 0 or 1)")
+
     # -- state (mgrit.py:840-858) -------------------------------------------------------------------
     @staticmethod
     def _forcing_tables(space, time_fns, width, *grids):
@@ -298,12 +314,17 @@ class HipBackend:
         describe = hip_lib.level_grayscott2d_newton if "theta" in d else hip_lib.level_grayscott2d
         describe(self.h, engine_lvl, t_local.size, _ptr(t_local), ld, d)
 
+    def _describe_cahnhilliard2d(self, engine_lvl, d, t_local, n, ld):
+        """the stabilised IMEX step, one plane per state (through hip_lib like the Gray-Scott forms above)"""
+        hip_lib.level_cahnhilliard2d(self.h, engine_lvl, t_local.size, _ptr(t_local), ld, d)
+
     def newton_stats(self, lvl):
         """counts of a Newton level (Allen-Cahn PCG, Gray-Scott BiCGStab) since the last call (which resets them)"""
         return hip_lib.newton_stats(self.h, lvl)
 
     _DESCRIBE = {"heat1d": _describe_heat1d, "heat1d_2pts": _describe_heat1d_2pts, "advection1d": _describe_advection1d,
-                 "heat2d": _describe_heat2d, "allencahn2d": _describe_allencahn2d, "grayscott2d": _describe_grayscott2d}
+                 "heat2d": _describe_heat2d, "allencahn2d": _describe_allencahn2d, "grayscott2d": _describe_grayscott2d,
+                 "cahnhilliard2d": _describe_cahnhilliard2d}
 
     def _describe(self, engine_lvl, lvl, t_local):
         """tell the engine what level engine_lvl is: the stepper of level lvl on the time points t_local"""
@@ -378,7 +399,7 @@ class HipBackend:
         from pymgrit_amd.core.layout import compute_layout
         mg = self.mg
         r = C.c_int(0)
-        if d["kind"] in ("allencahn2d", "grayscott2d"):
+        if d["kind"] in ("allencahn2d", "grayscott2d", "cahnhilliard2d"):
             # non-linear Phi: the time-parallel forward solve superposes block defects and holds for linear steppers only -- the
             # coarsest level is solved step by step whatever options.coarse_solve says
             check(self.lib.mgrit_hip_block_solve_config(self.h, lvl, 0, 1, 0, None, None))

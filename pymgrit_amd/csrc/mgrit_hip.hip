@@ -1578,6 +1578,8 @@ __global__ void interp_rows_kernel(double *__restrict__ uf, int f_ld, int T_f, c
 
 #include "mgrit_hip_grayscott.inc"
 
+#include "mgrit_hip_cahnhilliard.inc"
+
 #include "mgrit_hip_transfer2d.inc"
 
 #include "mgrit_hip_wide.inc"
@@ -1610,7 +1612,7 @@ struct PairList {
     BatchPlans fine_to_coarse, fine_to_rows, coarse;   // fine half into g^{l+1} (dst: the coarse slot) or into rows (dst: the pair's position)
 };
 
-enum class H2DKind { HEAT2D, ALLENCAHN_IMEX, ALLENCAHN_NEWTON, GRAYSCOTT_IMEX, GRAYSCOTT_NEWTON };   // what a level of the batched 2-D route steps with
+enum class H2DKind { HEAT2D, ALLENCAHN_IMEX, ALLENCAHN_NEWTON, GRAYSCOTT_IMEX, GRAYSCOTT_NEWTON, CAHNHILLIARD_IMEX };   // what a level of the batched 2-D route steps with
 struct H2DHost {
     H2DDev dev{};
     std::vector<double> lx, ly, dts;
@@ -1636,16 +1638,21 @@ struct H2DHost {
     // rim, no fold. A Gray-Scott state row holds two planes [u | v]: two work slab items per state, a D table per species, the
     // right-hand side from both planes. ALLENCAHN_NEWTON: an Allen-Cahn level whose Phi is the Newton-PCG step (newton_state below);
     // GRAYSCOTT_NEWTON: a Gray-Scott level whose Phi is the Newton-BiCGStab step, with the same struct for its parameters and work rows.
+    // CAHNHILLIARD_IMEX: one plane per state like Allen-Cahn, two work slab items per state like Gray-Scott, a [2][P][P] table (D1, D2).
     H2DKind kind = H2DKind::HEAT2D;
     bool periodic() const { return kind != H2DKind::HEAT2D; }
     bool allencahn() const { return kind == H2DKind::ALLENCAHN_IMEX || kind == H2DKind::ALLENCAHN_NEWTON; }
     bool grayscott() const { return kind == H2DKind::GRAYSCOTT_IMEX || kind == H2DKind::GRAYSCOTT_NEWTON; }
     bool newton() const { return kind == H2DKind::ALLENCAHN_NEWTON || kind == H2DKind::GRAYSCOTT_NEWTON; }
-    int comps() const { return grayscott() ? 2 : 1; }   // planes of a state = work slab items of a state
+    bool cahnhilliard() const { return kind == H2DKind::CAHNHILLIARD_IMEX; }
+    int comps() const { return grayscott() ? 2 : 1; }                      // planes of a state row
+    int items() const { return grayscott() || cahnhilliard() ? 2 : 1; }   // work slab items of a state in the first two products (Cahn-
+                                                                           // Hilliard: u and w(u) from its one plane, joined by the second)
     double *T = nullptr;   // the Hartley table
     int KP = 0;            // nx rounded up to the K step of the tile product
     struct { double inv_dx2 = 0.0, inv_eps2 = 0.0; int nu = 0; } ac;
     struct { double du = 0.0, dv = 0.0, a = 0.0, b = 0.0, inv_dx2 = 0.0; } gs;   // inv_dx2: the stencil of the Newton kernels
+    struct { double eps2 = 0.0, stab = 0.0; } ch;
     double *Wc0 = nullptr, *Wc1 = nullptr;   // one item each: the work buffers of the coarsest-level chain, which in a planned
                                              // cycle steps on a second stream BESIDE sweeps that apply this level's Phi too (the
                                              // coarse half of the FAS right-hand side of another block of time points)
@@ -2534,7 +2541,7 @@ using BatchItems = std::vector<std::vector<BatchItem>>;   // the item lists of a
 // Plans of one item list: grouped by key in first-seen key order -- Heat2D / Allen-Cahn: the time-step size of the item's step
 // (one D table per group); wide: one key, so item order is kept (wide_points_sumsq relies on it) --, each group in batches
 int batch_make_plans(mgrit_hip_engine *e, Level &lv, const std::vector<BatchItem> &items, std::vector<BatchPlan> &out) {
-    const size_t max_batch = lv.h2d ? H2D_MAX_BATCH / lv.h2d->comps() : WIDE_MAX_BATCH;   // (H2D_MAX_BATCH work slab items a launch)
+    const size_t max_batch = lv.h2d ? H2D_MAX_BATCH / lv.h2d->items() : WIDE_MAX_BATCH;   // (H2D_MAX_BATCH work slab items a launch)
     std::vector<uint64_t> item_key, keys;
     for (const BatchItem &it : items) {
         item_key.push_back(lv.h2d ? dbl_bits(lv.h2d->dts[it.step]) : 0);
@@ -2635,7 +2642,7 @@ int h2d_reserve(Level &lv, int count) {
     if (h.W1) HIP_TRY(hipFree(h.W1));
     if (h.rowsq) HIP_TRY(hipFree(h.rowsq));
     h.W0 = h.W1 = h.rowsq = nullptr;
-    const size_t per = (size_t)h.dev.Mi * h.dev.Mj * h.comps();
+    const size_t per = (size_t)h.dev.Mi * h.dev.Mj * h.items();
     if (!h.newton()) {   // (a Newton-PCG level's products run on its own work rows: acn_reserve)
         HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.W0), sizeof(double) * per * count));
         HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.W1), sizeof(double) * per * count));
@@ -2684,14 +2691,23 @@ void p2d_fill_dinv(const H2DHost &h, double *tab, double shift, double coef) {
 
 // D of the level's implicit solve: Heat2D 1 / (1 + theta dt (lx + ly)) in spectral slot order on both axes, 0 where no mode lives;
 // Allen-Cahn IMEX 1 / (1 + dt (lam_a + lam_b)); Gray-Scott [2][P][P], species u then v, 1 / (1 + (dt d_c) (lam_a + lam_b)), the operand
-// order of GrayScott._dinv
+// order of GrayScott._dinv; Cahn-Hilliard [2][P][P], D1 = 1 / (1 + dt (eps^2 mu^2 + s mu)) then D2 = -(dt mu) D1, mu = lam_a + lam_b, the
+// operand order of CahnHilliard._tables
 int h2d_dinv(mgrit_hip_engine *e, Level &lv, uint64_t dtbits, double **out) {
     H2DHost &h = *lv.h2d;
     const size_t per = (size_t)h.dev.Mi * h.dev.Mj;
-    return h2d_table_once(e, lv, h.dinv, dtbits, per * h.comps(), [&](double dt, double *tab) {
+    return h2d_table_once(e, lv, h.dinv, dtbits, per * h.items(), [&](double dt, double *tab) {
         if (h.kind == H2DKind::GRAYSCOTT_IMEX) {
             p2d_fill_dinv(h, tab, 1.0, dt * h.gs.du);
             p2d_fill_dinv(h, tab + per, 1.0, dt * h.gs.dv);
+        } else if (h.cahnhilliard()) {
+            for (int a = 0; a < h.dev.nx; ++a)
+                for (int b = 0; b < h.dev.nx; ++b) {
+                    const double mu = h.lx[a] + h.ly[b];
+                    const double d1 = 1.0 / (1.0 + dt * (h.ch.eps2 * mu * mu + h.ch.stab * mu));
+                    tab[(size_t)a * h.dev.Mj + b] = d1;
+                    tab[per + (size_t)a * h.dev.Mj + b] = -(dt * mu) * d1;
+                }
         } else if (h.periodic()) p2d_fill_dinv(h, tab, 1.0, dt);
         else {
             const double thdt = h.dev.theta * dt;
@@ -2722,6 +2738,26 @@ int p2d_products(mgrit_hip_engine *e, const H2DHost &h, int count, const PRE &pr
     launch(&p2d_gemm_kernel<PLAIN, PRE>, W0, W1, nullptr, none);
     if (fin) launch(&p2d_gemm_kernel<P2D_FIN, PRE>, W1, out, nullptr, *fin);
     else launch(&p2d_gemm_kernel<PLAIN, PRE>, W1, out, nullptr, none);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// The products of one Cahn-Hilliard batch, six item-products per state: the first over 2 * count items (u and w(u) of
+// state b staged from row idx[b] into W1 items 2 b, 2 b + 1), the combine product over count states (W1 -> W0 item b, o D1 / D2), then the
+// one-plane products of p2d_gemm_kernel over count items -- W0 -> W1, and W1 through the sweep's arithmetic (fin) or into W0.
+int ch_products(mgrit_hip_engine *e, const H2DHost &h, int count, const CHPre &pre, const double *src, const int32_t *idx, const double *dinv,
+                double *W0, double *W1, const H2DFin *fin) {
+    const H2DDev &H = h.dev;
+    const int P = H.Mi;
+    const size_t per = (size_t)P * P;
+    const dim3 g2(P / 64, P / 64, 2 * count), g1(P / 64, P / 64, count);
+    const H2DFin none{};
+    const ACPre one{0.0, 0};   // (the one-plane instances of the last two products: they stage nothing, pre is not applied)
+    hipLaunchKernelGGL((p2d_gemm_kernel<P2D_FIRST, CHPre>), g2, dim3(256), 0, e->stream, h.T, P, h.KP, H.nx, src, W1, nullptr, per, idx, H.ld, pre, H, none);
+    hipLaunchKernelGGL(p2d_combine_kernel, g1, dim3(256), 0, e->stream, h.T, P, h.KP, W1, W0, dinv, per);
+    hipLaunchKernelGGL((p2d_gemm_kernel<P2D_PLAIN, ACPre>), g1, dim3(256), 0, e->stream, h.T, P, h.KP, H.nx, W0, W1, nullptr, per, idx, H.ld, one, H, none);
+    if (fin) hipLaunchKernelGGL((p2d_gemm_kernel<P2D_FIN, ACPre>), g1, dim3(256), 0, e->stream, h.T, P, h.KP, H.nx, W1, W0, nullptr, per, idx, H.ld, one, H, *fin);
+    else hipLaunchKernelGGL((p2d_gemm_kernel<P2D_PLAIN, ACPre>), g1, dim3(256), 0, e->stream, h.T, P, h.KP, H.nx, W1, W0, nullptr, per, idx, H.ld, one, H, none);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -2945,6 +2981,7 @@ int h2d_phi_batch(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const dou
     const size_t per = (size_t)H.Mi * H.Mj;
     chain = chain && pl.count == 1;
     if (h.grayscott() && 2 * pl.count > H2D_MAX_BATCH) return fail(MGRIT_HIP_EINVAL, "Gray-Scott batch of %d states", pl.count);   // (blockIdx.z, the work slabs)
+    if (h.cahnhilliard() && 2 * pl.count > H2D_MAX_BATCH) return fail(MGRIT_HIP_EINVAL, "Cahn-Hilliard batch of %d states", pl.count);
     if (h.newton()) {   // Newton-PCG / Newton-BiCGStab: the plan in batches of at most the kind's cap (without fin the caller passes one such batch)
         const int cap = newton_max_batch(h);
         for (int off = 0; off < pl.count; off += cap) {
@@ -2961,8 +2998,8 @@ int h2d_phi_batch(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const dou
         return 0;
     }
     if (chain && !h.Wc0) {
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.Wc0), sizeof(double) * per * h.comps()));
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.Wc1), sizeof(double) * per * h.comps()));
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.Wc0), sizeof(double) * per * h.items()));
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.Wc1), sizeof(double) * per * h.items()));
     }
     if (!chain && (rc = h2d_reserve(lv, std::min(H2D_MAX_BATCH, std::max(pl.count, 1))))) return rc;
     double *const W0 = chain ? h.Wc0 : h.W0, *const W1 = chain ? h.Wc1 : h.W1;
@@ -2973,6 +3010,7 @@ int h2d_phi_batch(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const dou
         double dt;
         std::memcpy(&dt, &pl.dtbits, 8);
         if (h.kind == H2DKind::GRAYSCOTT_IMEX) return p2d_products(e, h, pl.count, GSPre{dt, h.gs.a, h.gs.b, 0}, in_slab, pl.d_in, dinv, W0, W1, W0, fin);
+        if (h.cahnhilliard()) return ch_products(e, h, pl.count, CHPre{1.0 + h.ch.stab, 0}, in_slab, pl.d_in, dinv, W0, W1, fin);
         return p2d_products(e, h, pl.count, ACPre{dt * h.ac.inv_eps2, h.ac.nu}, in_slab, pl.d_in, dinv, W0, W1, W0, fin);
     }
     // W1[j][i'] = x to spectral slots ; W0[i'][j'] = y to spectral slots, o D ; W1[j'][i] = x back ; W0[i][j] = y back = U
@@ -3999,6 +4037,21 @@ int mgrit_hip_level_grayscott2d(mgrit_hip_engine *e, int lvl, int n_pts_local, c
     });
 }
 
+int mgrit_hip_level_cahnhilliard2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld, double inv_dx2,
+                                   double eps2, double stab) {
+    int rc = check_level(e, lvl, false);
+    if (rc) return rc;
+    if (nx < 4 || nx > 2048) return fail(MGRIT_HIP_EUNSUPPORTED, "Cahn-Hilliard grid %dx%d outside [4,2048]^2", nx, nx);
+    if ((rc = check_ld_2d(ld, nx * nx, "nx*nx"))) return rc;
+    if (!(inv_dx2 > 0.0) || !(eps2 > 0.0) || !(stab >= 0.0) || !std::isfinite(inv_dx2) || !std::isfinite(eps2) || !std::isfinite(stab))
+        return fail(MGRIT_HIP_EINVAL, "bad Cahn-Hilliard parameters (eps2=%g must be positive, stab=%g not negative)", eps2, stab);
+    if (no_time_grid(n_pts_local, t_local)) return fail(MGRIT_HIP_EINVAL, "bad arguments");
+    return level_2d(e, lvl, MGRIT_HIP_STEPPER_CAHNHILLIARD2D, H2DKind::CAHNHILLIARD_IMEX, nx * nx, ld, n_pts_local, 0, [&](Level &lv, H2DHost *h) {
+        h->ch = {eps2, stab};
+        return periodic2d_tables(e, lv, h, n_pts_local, t_local, nx, ld, inv_dx2);
+    });
+}
+
 int mgrit_hip_level_allencahn2d_newton(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld, double inv_dx2,
                                        double inv_eps2, int nu, double theta, double newton_tol, int newton_maxiter, double lin_tol,
                                        int lin_maxiter) {
@@ -4203,7 +4256,9 @@ int mgrit_hip_level_transfer(mgrit_hip_engine *e, int lvl, int kind) {
     } else if (kind == MGRIT_HIP_TRANSFER_HEAT2D || kind == MGRIT_HIP_TRANSFER_PERIODIC2D) {
         const H2DHost *hf = e->L[lvl].h2d, *hc = e->L[lvl + 1].h2d;
         const bool per = kind == MGRIT_HIP_TRANSFER_PERIODIC2D;
-        if (!hf || !hc || (per ? !hf->allencahn() || !hc->allencahn() : hf->periodic() || hc->periodic()))
+        // (periodic: two Allen-Cahn levels or two Cahn-Hilliard levels -- one plane per state both --, never one of each)
+        const bool per_ok = hf && hc && ((hf->allencahn() && hc->allencahn()) || (hf->cahnhilliard() && hc->cahnhilliard()));
+        if (!hf || !hc || (per ? !per_ok : hf->periodic() || hc->periodic()))
             return fail(MGRIT_HIP_EUNSUPPORTED, per ? "the periodic 2-D transfer joins two Allen-Cahn levels" : "the Heat2D transfer joins two Heat2D levels");
         const int off = per ? 0 : 1;
         if (2 * hc->dev.nx - off != hf->dev.nx || 2 * hc->dev.ny - off != hf->dev.ny)

@@ -9,7 +9,7 @@
 
 // b = fma(c, u * (1 - p), u), c = dt * (1 / eps^2) (formed once on the host), p = u^nu by nu - 1 multiplications p = p * u
 struct ACPre {
-    static constexpr int operands = 1;
+    static constexpr int operands = 1, items = 1;
     double c; int nu;
     __device__ __forceinline__ double operator()(double u) const {
         double p = u;

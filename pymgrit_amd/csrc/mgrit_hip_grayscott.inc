@@ -16,7 +16,7 @@
 // own = the staged value of the workgroup's species, other = the other species at the same point. The operand order is the one
 // GrayScott._rhs_imex states in numpy:  uv2 = u * (v * v);  b_u = fma(dt, a * (1 - u) - uv2, u);  b_v = fma(dt, uv2 - b * v, v)
 struct GSPre {
-    static constexpr int operands = 2;
+    static constexpr int operands = 2, items = 2;
     double dt, a, b; int comp;
     __device__ __forceinline__ double operator()(double own, double other) const {
         const double u = comp ? other : own, v = comp ? own : other;

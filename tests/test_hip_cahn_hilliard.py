@@ -1,0 +1,498 @@
+"""GPU tests of the Cahn-Hilliard IMEX stepper (csrc/mgrit_hip_cahnhilliard.inc, p2d_combine_kernel): every sweep of the device path
+against the SAME hierarchy on the plugin path over the host ``step`` -- the same formula in numpy, so a mistake common to both does not
+show here; tests/test_hip_cahn_hilliard_reference.py holds the device path against the transform-free long-double solve of
+tests/cahn_hilliard_reference.py with the machinery of this file. Then solves, the jump criterion, a spatially coarsened hierarchy,
+the mass, and everything that is refused.
+
+Tolerances, none measured on the device (test_cahn_hilliard_cpu.py derives C(nx) = 4 nx + 36 and bnorm):
+  per Phi, one evaluation:          norm_F(error) <= C(nx) EPS bnorm,   bnorm = norm_F(u) + d2max norm_F(|u|^3 + (1 + s) |u|) of the
+                                    input rows, d2max = max over the modes of dt mu / (1 + dt (eps^2 mu^2 + s mu)) at the level's LARGEST
+                                    dt (D2 grows with dt)
+  host and device, two evaluations: twice that;   device and reference: C(nx) EPS bnorm + EPS bnorm (the reference's asserted error)
+  SLACK:                            8 EPS * 3 * the largest row norm involved, for the sweep's own arithmetic (done on both sides)
+  chained steps (forward_solve, F-relaxation over several F-points): e_k <= Lip_k e_(k-1) + the step's per-Phi term + SLACK,
+                                    Lip_k <= 1 + d2max_k max|3 u^2 - (1 + s)| over |u| <= R, R the largest |value| of the step's input
+                                    (the u path is a contraction, |D1| <= 1; the w path has the Lipschitz constant of w times d2max)
+Every comparison covers all rows of a list. Each sweep prints its worst error / allowed ("RATIO" lines).
+
+Parameters. Random states in [-1, 1]. The grid spacing is held at dx = 1 / 16 (L = nx / 16) with eps = 0.1 and stab = 2, so that
+absrow(A) = 1 + dt (64 eps^2 / dx^4 + 8 s / dx^2) = 1 + 4.6e4 dt stays near 25 at the coarsest step 5e-4 for every nx: inside the
+range in which the reference certifies its own error (cahn_hilliard_reference.py), while D2 reaches 0.09 -- the w path carries a tenth
+of the result, six orders above the tolerances.
+"""
+import collections
+import ctypes as C
+import types
+
+import numpy as np
+import pytest
+
+import cases
+from test_cahn_hilliard_cpu import EPS, b_norm, c_of, d2max
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+T_SWEEP = 0.002     # sweeps: nt = 17 / 9 / 5 on [0, T_SWEEP], coarsening factor 2 -- every Phi of a relaxation acts on a stored state
+ALL_SWEEPS = ("f_relax", "c_relax", "fas_residual", "forward_solve", "error_correction", "compute_residual")
+STORED_STATE_SWEEPS = ("f_relax", "c_relax", "fas_residual", "compute_residual")
+RAGGED = np.concatenate(([0.0], np.cumsum(1e-4 * np.array([1, 1, 1.5, .5, 2, 1, 1, .75, 1, 1, 1, 1.25, 3, 1, 1, 1]))))   # the grid of
+RAGGED_GRIDS = {"by2_3lvl": [RAGGED, RAGGED[::2], RAGGED[::4]], "by4_2lvl": [RAGGED, RAGGED[::4]]}                       # the Allen-Cahn reference test
+H = 2.0 ** -17      # every t_k = k H and every difference is exact: one bit pattern of dt
+
+
+def _host_class():
+    from pymgrit_amd import CahnHilliard
+
+    class HostCahnHilliard(CahnHilliard):     # overriding step sends the hierarchy to the plugin path
+        def step(self, u_start, t_start, t_stop):
+            return super().step(u_start, t_start, t_stop)
+    return HostCahnHilliard
+
+
+def _reference_class():
+    from cahn_hilliard_reference import ReferenceCahnHilliard
+    return ReferenceCahnHilliard
+
+
+# the other side of a comparison: its class, and the per-Phi allowance in units of EPS bnorm beyond the device's own C(nx)
+SIDES = {"host": (_host_class, lambda nx: c_of(nx)), "reference": (_reference_class, lambda nx: 1)}
+
+
+def _uniform(nts, t_stop):
+    return [dict(t_start=0, t_stop=t_stop, nt=nt) for nt in nts]
+
+
+def _intervals(ts):
+    return [dict(t_interval=np.asarray(t)) for t in ts]
+
+
+def _app_args(nx, **over):
+    args = dict(nx=nx, L=nx / 16.0, eps=0.1, stab=2.0)
+    args.update(over)
+    return args
+
+
+def _pair(side, nxs, grids, transfer=None, app=None, **opts):
+    """(device Mgrit, plugin Mgrit over the side's class) on the same hierarchy; nxs: one nx, or one per level (on one square: L is the
+    finest level's nx / 16); app: eps, stab, mean, amplitude other than this file's"""
+    from pymgrit_amd import CahnHilliard, Mgrit
+    opts.setdefault("nested_iteration", False)
+    nxs = [nxs] * len(grids) if np.isscalar(nxs) else list(nxs)
+    if transfer is not None:
+        opts["transfer"] = transfer
+    app = dict(app or {}, L=nxs[0] / 16.0)
+    dev = Mgrit([CahnHilliard(**_app_args(nx, **app), **g) for nx, g in zip(nxs, grids)], logging_lvl=30, **opts)
+    other = Mgrit([SIDES[side][0]()(**_app_args(nx, **app), **g) for nx, g in zip(nxs, grids)], logging_lvl=30, **opts)
+    assert type(dev.backend).__name__ == "HipBackend" and type(other.backend).__name__ == "PluginBackend"
+    for a, b in zip(dev.t, other.t):
+        assert np.array_equal(a, b)
+    other.side = side
+    return dev, other
+
+
+def _lists(mg, lvl):
+    return [(name, lst[lvl]) for name, lst in (("u", mg.u), ("v", mg.v), ("g", mg.g)) if lst[lvl] is not None]
+
+
+def _set_states(dev, host, states):
+    """states[(name, lvl)] = [n_pts][nx * nx values of one state in row-major order]"""
+    for (name, lvl), val in states.items():
+        dev.backend.set_natural(name, lvl, val)
+        lst = dict(_lists(host, lvl))[name]
+        for i in range(len(lst)):
+            lst[i].set_values(val[i].reshape(np.shape(lst[i].get_values())).copy())
+
+
+def _random_states(host, seed):
+    rng = np.random.default_rng(seed)
+    return {(name, lvl): rng.uniform(-1.0, 1.0, size=(len(lst), host.problem[lvl].nx ** 2))
+            for lvl in range(host.lvl_max) for name, lst in _lists(host, lvl)}
+
+
+def _host_state(host, name, lvl):
+    return np.array([np.asarray(v.get_values()).ravel() for v in dict(_lists(host, lvl))[name]])
+
+
+def _row_norm(*arrays):
+    return max(float(np.max(np.linalg.norm(np.atleast_2d(a), axis=1))) for a in arrays)
+
+
+def _phi_term(host, app, rows, dt):
+    """the device's evaluation and the other side's: (C(nx) + the side's units) EPS bnorm"""
+    return (c_of(app.nx) + SIDES[host.side][1](app.nx)) * EPS * b_norm(app, rows, dt)
+
+
+def _tol(host, lvl, rows):
+    return _phi_term(host, host.problem[lvl], rows, float(np.max(np.diff(host.t[lvl]))))
+
+
+def _lip(app, dt, rows):
+    R = float(np.abs(rows).max())
+    return 1.0 + d2max(app, dt) * max(1.0 + app.stab, abs(3.0 * R * R - (1.0 + app.stab)))
+
+
+def _chain(host, app, t, inputs, slack):
+    """e_k = Lip_k e_(k-1) + per-Phi term + SLACK over the steps t[k-1] -> t[k], inputs[k-1] the other side's input of step k"""
+    e = 0.0
+    for k in range(1, len(t)):
+        dt = float(t[k] - t[k - 1])
+        e = _lip(app, dt, inputs[k - 1]) * e + _phi_term(host, app, inputs[k - 1], dt) + slack
+    return e
+
+
+def _compare(dev, host, lvl, allowed, what):
+    worst = 0.0
+    for name, _ in _lists(host, lvl):
+        got, ref = dev.backend.natural(name, lvl), _host_state(host, name, lvl)
+        err = float(np.max(np.linalg.norm(got - ref, axis=1)))
+        worst = max(worst, err)
+        assert err <= allowed, (what, name, lvl, err, allowed)
+    print(f"{what} level {lvl}: worst row error {worst:.3e}, allowed {allowed:.3e}")
+    return worst
+
+
+def _ratio(record, what, err, allowed):
+    record[what] = max(record.get(what, 0.0), err / allowed if allowed > 0.0 else 0.0)
+
+
+def _report(test, record):
+    for what, r in record.items():
+        print(f"RATIO {test} {what}: worst error/allowed {r:.4f}")
+
+
+def _run_sweeps(dev, host, w, seed, sweeps, levels=None, record=None):
+    """the sweeps on fresh random states in [-1, 1], each against the plugin hierarchy. Transfers: copy, or any the two sides share"""
+    record = {} if record is None else record
+    top = dev.lvl_max - 1
+    levels = list(range(top)) if levels is None else levels
+    seeds = iter(range(seed, seed + 1000))
+
+    def fresh():
+        st = _random_states(host, next(seeds))
+        _set_states(dev, host, st)
+        return st
+
+    for lvl in levels:
+        app = host.problem[lvl]
+        if "f_relax" in sweeps:
+            st = fresh()
+            slack = 8 * EPS * 3 * _row_norm(*st.values())
+            dev.f_relax(lvl); host.f_relax(lvl)
+            cpts = [int(i) for i in np.asarray(host.cpts[lvl])]
+            if (max(np.diff(cpts)) if len(cpts) > 1 else 1) <= 2:      # every Phi acts on a stored state
+                allowed = _tol(host, lvl, st[("u", lvl)]) + slack
+            else:                                                      # F-points of one interval are chained
+                after, t, allowed = _host_state(host, "u", lvl), host.t[lvl], 0.0
+                for a, z in zip(cpts[:-1], cpts[1:]):
+                    allowed = max(allowed, _chain(host, app, t[a:z], [st[("u", lvl)][a]] + [after[i] for i in range(a + 1, z - 1)], slack))
+            _ratio(record, "f_relax", _compare(dev, host, lvl, allowed, "f_relax"), allowed)
+        if "c_relax" in sweeps:
+            st = fresh()
+            slack = 8 * EPS * 3 * _row_norm(*st.values())
+            dev.c_relax(lvl); host.c_relax(lvl)
+            allowed = max(1.0, w) * _tol(host, lvl, st[("u", lvl)]) + slack * (abs(w) + abs(1 - w))
+            _ratio(record, "c_relax", _compare(dev, host, lvl, allowed, f"c_relax w={w}"), allowed)
+        if "fas_residual" in sweeps:
+            st = fresh()
+            slack = 8 * EPS * 3 * _row_norm(*st.values())
+            dev.fas_residual(lvl); host.fas_residual(lvl)
+            # g of the coarse level: one Phi of the fine level, one of the coarse level on the restricted rows of the fine u (full
+            # weighting has non-negative weights that sum to 1: values stay in [-1, 1], a row norm does not grow beyond the fine row's)
+            restricted = _host_state(host, "v", lvl + 1)
+            allowed = _tol(host, lvl, st[("u", lvl)]) + _tol(host, lvl + 1, restricted) + slack
+            _ratio(record, "fas_residual", _compare(dev, host, lvl + 1, allowed, "fas_residual"), allowed)
+    if "forward_solve" in sweeps:
+        st = fresh()
+        dev.forward_solve(top); host.forward_solve(top)
+        uh = _host_state(host, "u", top)
+        allowed = _chain(host, host.problem[top], host.t[top], uh, 8 * EPS * 3 * _row_norm(uh, st[("g", top)]))
+        _ratio(record, "forward_solve", _compare(dev, host, top, allowed, "forward_solve"), allowed)
+    if "error_correction" in sweeps:
+        for lvl in reversed(levels):
+            st = fresh()
+            dev.error_correction(lvl); host.error_correction(lvl)
+            allowed = 8 * EPS * 3 * _row_norm(*st.values())
+            _ratio(record, "error_correction", _compare(dev, host, lvl, allowed, "error_correction"), allowed)
+    if "compute_residual" in sweeps:
+        st = fresh()
+        nx = host.problem[0].nx
+        got, want = np.asarray(dev.compute_residual()), np.asarray(host.compute_residual())
+        allowed = _tol(host, 0, st[("u", 0)]) + 8 * EPS * 3 * _row_norm(st[("u", 0)]) + (nx * nx + 2) * EPS * want
+        assert got.shape == want.shape and got.size == len(host.cpts[0]) - 1
+        print(f"residual norms: worst deviation {np.abs(got - want).max():.3e}, allowed {allowed.min():.3e}")
+        assert np.all(np.abs(got - want) <= allowed), np.abs(got - want).max()
+        _ratio(record, "compute_residual", float(np.max(np.abs(got - want) / allowed)), 1.0)
+    return record
+
+
+# ---- the cases, shared with test_hip_cahn_hilliard_reference.py ---------------------------------------------------------------------
+def check_size_edges(side, nx):
+    """every sweep with weight_c = 1; C-relaxation, the one sweep the weight enters, with 1.3 as well"""
+    record = {}
+    dev, host = _pair(side, nx, _uniform((17, 9, 5), T_SWEEP), weight_c=1.0)
+    _run_sweeps(dev, host, 1.0, 100 * nx, ALL_SWEEPS, record=record)
+    dev, host = _pair(side, nx, _uniform((17, 9, 5), T_SWEEP), weight_c=1.3)
+    _run_sweeps(dev, host, 1.3, 100 * nx + 50, ("c_relax",), record=record)
+    _report(f"size_edges[{side},nx={nx}]", record)
+
+
+def _distinct_steps(t):
+    return len(set(np.diff(np.asarray(t, dtype=np.float64)).view(np.int64).tolist()))
+
+
+def check_several_step_sizes(side, grid, nx):
+    record = {}
+    for w in (1.0, 1.3):
+        dev, host = _pair(side, nx, _intervals(RAGGED_GRIDS[grid]), weight_c=w)
+        for t in dev.t:
+            assert _distinct_steps(t) >= 3 and len(set(np.round(np.diff(t) / 1e-4, 6))) >= 3, np.diff(t)
+        if grid == "by4_2lvl":      # the three F-points of one interval do not share one pair of D tables
+            assert sum(len(set(np.round(np.diff(dev.t[0][a:a + 4]) / 1e-4, 6))) >= 2 for a in range(0, 16, 4)) >= 2
+        _run_sweeps(dev, host, w, 500 * nx + (3 if w != 1.0 else 0), ALL_SWEEPS if w == 1.0 else ("c_relax",), record=record)
+    _report(f"step_sizes[{side},{grid},nx={nx}]", record)
+
+
+def check_split_at_the_batch_cap(side):
+    """2051 points with the exact step 2^-17: 1025 F-points and 1025 relaxed C-points, each ONE dt group -- a state owns two work slab
+    items through the first two products, so a launch holds 512 states: batches of 512, 512 and 1"""
+    nx, w = 8, 1.3
+    t = H * np.arange(2051.0)
+    dev, host = _pair(side, nx, _intervals([t, t[::2]]), weight_c=w)
+    t = np.asarray(dev.t[0])
+    assert len(t) == 2051 and len(dev.t[1]) == 1026
+    for pts in (np.arange(1, len(t), 2), np.arange(2, len(t), 2)):      # F-points, relaxed C-points
+        groups = sorted(collections.Counter((t[pts] - t[pts - 1]).view(np.int64).tolist()).values())
+        assert groups == [1025] and 1025 > 2 * 512, groups
+    record = _run_sweeps(dev, host, w, 77, STORED_STATE_SWEEPS, levels=[0])
+    _report(f"batches[{side},dyadic_2051]", record)
+
+
+def check_one_phi_at_larger_grids(side, nx):
+    dev, host = _pair(side, nx, _uniform((5, 3), 2.0 ** -9))      # (steps of 2^-11, exact)
+    st = _random_states(host, nx)
+    _set_states(dev, host, st)
+    dev.f_relax(0); host.f_relax(0)
+    allowed = _tol(host, 0, st[("u", 0)]) + 8 * EPS * 3 * _row_norm(*st.values())
+    worst = _compare(dev, host, 0, allowed, "f_relax")
+    print(f"RATIO larger_grids[{side},nx={nx}] f_relax: worst error/allowed {worst / allowed:.4f}")
+
+
+def check_constant_rows(side):
+    """u = 0, +0.5, -0.5: w is constant, only mode (0, 0) is non-zero, D1 = 1 and D2 = 0 there: Phi(u) = u. Zeros bit for bit"""
+    nx = 33
+    dev, host = _pair(side, nx, _uniform((17, 9, 5), T_SWEEP))
+    st = _random_states(host, 5)
+    const = np.array([0.0, 0.5, -0.5])[(np.arange(17) // 2) % 3]          # the C-point 2 k and the F-point behind it: the same constant
+    st[("u", 0)] = np.repeat(const[:, None], nx * nx, axis=1)
+    st[("u", 0)][1::2] = 0.25                                              # (what F-relaxation has to overwrite)
+    _set_states(dev, host, st)
+    dev.f_relax(0); host.f_relax(0)
+    allowed = _tol(host, 0, st[("u", 0)][0::2]) + 8 * EPS * 3 * _row_norm(*st.values())
+    worst = _compare(dev, host, 0, allowed, "f_relax, constant rows")
+    got = dev.backend.natural("u", 0)
+    err = float(np.max(np.linalg.norm(got - const[:, None], axis=1)))
+    print(f"RATIO constants[{side}] f_relax: worst error/allowed {max(worst, err) / allowed:.4f}")
+    assert err <= allowed, (err, allowed)
+    for i in np.flatnonzero(const == 0.0):
+        assert np.array_equal(got[i], np.zeros(nx * nx)), i
+
+
+def check_history(dev, host, what, iterations):
+    conv, hconv = np.asarray(dev.solve()["conv"]), np.asarray(host.solve()["conv"])
+    u = dev.backend.natural("u", 0)
+    norm_u = cases.spacetime_norm(u)
+    assert len(conv) == len(hconv) == iterations, (conv, hconv)
+    dev_host = np.abs(conv - hconv)
+    print(f"RATIO {what} conv: largest deviation {np.max(dev_host) / (EPS * norm_u):.2f} units of eps*norm(u) "
+          f"(allowed {cases.BLK_K} beyond 1e-10 relative)")
+    assert np.all(dev_host <= 1e-10 * hconv + cases.BLK_K * EPS * norm_u), (conv, hconv)
+    last = _host_state(host, "u", 0)[-1]
+    print(f"RATIO {what} last state: relative deviation {np.abs(u[-1] - last).max() / np.abs(last).max():.3e}")
+    assert np.abs(u[-1] - last).max() <= 1e-9 * np.abs(last).max()
+    return u
+
+
+# ---- against the host step ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("nx", [4, 33, 96, 97, 129])
+def test_every_sweep_at_the_size_edges(nx):
+    """nx = 4 (smallest grid), 33 / 97 (just past a K step of 32), 96 (KP = 96 < P = 128), 129 (just past a tile of 64)"""
+    assert torch.cuda.is_available()
+    check_size_edges("host", nx)
+
+
+@pytest.mark.parametrize("nx", [20, 66])
+@pytest.mark.parametrize("grid", sorted(RAGGED_GRIDS))
+def test_every_sweep_with_several_step_sizes_per_level(grid, nx):
+    assert torch.cuda.is_available()
+    check_several_step_sizes("host", grid, nx)
+
+
+def test_sweeps_split_at_the_batch_cap():
+    assert torch.cuda.is_available()
+    check_split_at_the_batch_cap("host")
+
+
+@pytest.mark.parametrize("nx", [256, 257])
+def test_one_phi_at_larger_grids(nx):
+    assert torch.cuda.is_available()
+    check_one_phi_at_larger_grids("host", nx)
+
+
+def test_constant_rows_are_returned():
+    assert torch.cuda.is_available()
+    check_constant_rows("host")
+
+
+@pytest.mark.parametrize("nx", [20, 97])
+def test_a_sweep_run_twice_gives_the_same_bits(nx):
+    """a race in the staging of the two items or in the combine product's two passes through LDS would show here"""
+    assert torch.cuda.is_available()
+    dev, host = _pair("host", nx, _uniform((17, 9, 5), T_SWEEP), weight_c=1.3)
+    st = _random_states(host, nx)
+    top = dev.lvl_max - 1
+    sweeps = [("f_relax", lambda l=l: dev.f_relax(l)) for l in range(top)] + [("c_relax", lambda l=l: dev.c_relax(l)) for l in range(top)] + \
+             [("fas_residual", lambda l=l: dev.fas_residual(l)) for l in range(top)] + [("forward_solve", lambda: dev.forward_solve(top))]
+    for name, run in sweeps:
+        out = []
+        for rep in range(2):
+            for (which, lvl), val in st.items():
+                dev.backend.set_natural(which, lvl, val)
+            run()
+            out.append({key: dev.backend.natural(*key) for key in st})
+        for key in st:
+            assert np.array_equal(out[0][key], out[1][key]), (name, key)
+
+
+@pytest.mark.parametrize("cycle", ["V", "F"])
+def test_solves_match_the_plugin_path(cycle):
+    """three iterations from the initial state, copy transfer, nt = 17 / 9 / 5, on the default square (L = 1, nx = 16, eps = 0.05)"""
+    assert torch.cuda.is_available()
+    dev, host = _pair("host", 16, _uniform((17, 9, 5), 0.01), app=dict(eps=0.05), cycle_type=cycle, max_iter=3, tol=0.0)
+    check_history(dev, host, f"solve[{cycle}]", 3)
+
+
+def test_jump_criterion_matches_the_plugin_path():
+    """conv_crit = 1: the norms of u_i - previous u_i (h2d_rowsq_kernel<false>), three iterations; the same rule"""
+    assert torch.cuda.is_available()
+    dev, host = _pair("host", 16, _uniform((17, 9, 5), 0.01), app=dict(eps=0.05), conv_crit=1, max_iter=3, tol=0.0)
+    check_history(dev, host, "solve[jump]", 3)
+
+
+def test_spatially_coarsened_hierarchy():
+    """nx = 16 -> 8 with GridTransferCahnHilliard (the periodic 2-D transfer kernels between two Cahn-Hilliard levels): the sweeps, and
+    three iterations by the rule of the residual histories. Such a hierarchy converges slowly (eps is fixed while dx doubles)."""
+    from pymgrit_amd import GridTransferCahnHilliard
+    assert torch.cuda.is_available()
+    record = {}
+    for w in (1.0, 1.3):
+        dev, host = _pair("host", (16, 8), _uniform((17, 9), T_SWEEP), transfer=[GridTransferCahnHilliard()], weight_c=w)
+        assert dev.backend._device_transfer(0) and dev.problem[1].dx == 2 * dev.problem[0].dx
+        _run_sweeps(dev, host, w, 900 + (3 if w != 1.0 else 0), ALL_SWEEPS, record=record)
+    _report("coarsened[16->8]", record)
+    dev, host = _pair("host", (16, 8), _uniform((17, 9), 0.01), transfer=[GridTransferCahnHilliard()], app=dict(eps=0.05), max_iter=3, tol=0.0)
+    check_history(dev, host, "solve[16->8]", 3)
+
+
+def test_a_users_transfer_runs_through_its_python_methods():
+    """a user's GridTransfer between two Cahn-Hilliard levels: the caller route, exactly as for Allen-Cahn levels"""
+    from pymgrit_amd import GridTransfer, GridTransferCahnHilliard
+    assert torch.cuda.is_available()
+
+    class Mine(GridTransfer):
+        def __init__(self):
+            super().__init__()
+            self.inner = GridTransferCahnHilliard()
+
+        def restriction(self, u):
+            return self.inner.restriction(u)
+
+        def interpolation(self, u):
+            return self.inner.interpolation(u)
+    t = 2.0 ** -11 * np.arange(17.0)      # (exact steps: the caller route takes one time-step size per level, as for Allen-Cahn)
+    dev, host = _pair("host", (16, 8), _intervals([t, t[::2]]), transfer=[Mine()], app=dict(eps=0.05), max_iter=2, tol=0.0)
+    assert not dev.backend._device_transfer(0)
+    check_history(dev, host, "solve[user transfer]", 2)
+
+
+def test_mass_after_a_device_solve():
+    """|mean(u_i) - mean(u_0)| <= i * (per-Phi bound) / nx: every state of the solution is at most i Phis from u_0 (the C-points through
+    the coarse levels' steps, whose bound at their larger dt is the one used), and norm_F / nx bounds the mean of a grid"""
+    assert torch.cuda.is_available()
+    nx = 16
+    dev, host = _pair("host", nx, _uniform((17, 9, 5), 0.01), app=dict(eps=0.05, mean=0.2), max_iter=3, tol=0.0)
+    dev.solve()
+    u = dev.backend.natural("u", 0)
+    per_phi = max(c_of(nx) * EPS * b_norm(host.problem[lvl], u, float(np.max(np.diff(host.t[lvl])))) for lvl in range(3)) + 8 * EPS * 3 * _row_norm(u)
+    drift = np.abs(u.mean(axis=1) - u[0].mean())
+    print(f"RATIO mass: largest drift {drift.max():.3e}, allowed at the last point {16 * per_phi / nx:.3e}")
+    assert abs(u[0].mean() - 0.2) <= 4 * EPS
+    assert np.all(drift <= np.arange(17) * per_phi / nx), drift
+
+
+# ---- what is refused ---------------------------------------------------------------------------------------------------------------
+def test_what_is_not_covered_is_refused():
+    from pymgrit_amd import AllenCahn, AtMgrit, CahnHilliard, GridTransferAllenCahn, GridTransferCahnHilliard, Mgrit
+    from pymgrit_amd.core.backend_hip import HipBackend
+    from pymgrit_amd.core.hip_lib import MgritHipError
+
+    def prob(nxs=(12, 12)):
+        return [CahnHilliard(nx=nx, t_start=0, t_stop=0.002, nt=nt) for nx, nt in zip(nxs, (9, 3))]
+    with pytest.raises(MgritHipError, match="AT-MGRIT is not supported"):
+        AtMgrit(k=2, problem=prob(), logging_lvl=30)
+    with pytest.raises(MgritHipError, match="Cahn-Hilliard levels on the HIP engine: the global convergence criteria only"):
+        Mgrit(prob(), conv_crit=2, logging_lvl=30)
+    stub = types.SimpleNamespace(desc=[p.device_stepper() for p in prob()])
+    with pytest.raises(MgritHipError, match="Cahn-Hilliard levels on the HIP engine: one time rank only"):
+        HipBackend._check_cahnhilliard(stub, types.SimpleNamespace(comm_time_size=2, global_conv_crit=True))
+    with pytest.raises(Exception, match="nx=3"):
+        CahnHilliard(nx=3, t_start=0, t_stop=0.002, nt=9)
+    # a hierarchy that mixes Cahn-Hilliard and Allen-Cahn levels: by name, in either order
+    mixed = [prob()[0], AllenCahn(nx=12, method="IMEX", t_start=0, t_stop=0.002, nt=3)]
+    for levels in (mixed, [AllenCahn(nx=12, method="IMEX", t_start=0, t_stop=0.002, nt=9), prob()[1]]):
+        with pytest.raises(MgritHipError, match="every level of the hierarchy must be"):
+            Mgrit(levels, logging_lvl=30)
+    assert GridTransferAllenCahn().device_transfer() == GridTransferCahnHilliard().device_transfer()
+
+
+def test_level_entry_point_refuses_bad_arguments():
+    """mgrit_hip_level_cahnhilliard2d through raw ctypes: negative codes with a message, and what follows from the level's kind"""
+    assert torch.cuda.is_available()
+    from pymgrit_amd.core import hip_lib
+    lib = hip_lib.load()
+    EINVAL, EUNSUPPORTED = -1, -4
+    ch, ac, cfg, msg = lib.mgrit_hip_level_cahnhilliard2d, lib.mgrit_hip_level_allencahn2d, lib.mgrit_hip_block_solve_config, lib.mgrit_hip_last_error
+    eng = C.c_void_p()
+    assert lib.mgrit_hip_create(C.byref(eng), 5, C.c_void_p(torch.cuda.current_stream().cuda_stream)) == 0
+    try:
+        t9 = np.ascontiguousarray(np.linspace(0.0, 1e-3, 9))
+        tp, null = C.c_void_p(t9.ctypes.data), C.c_void_p(0)
+        ok = (20, 400, 400.0, 0.0025, 2.0)
+        assert ch(None, 0, 9, tp, *ok) < 0 and ch(eng, 6, 9, tp, *ok) < 0 and ch(eng, -1, 9, tp, *ok) < 0
+        assert ch(eng, 0, 9, tp, 3, 16, 9.0, 0.0025, 2.0) == EUNSUPPORTED and b"Cahn-Hilliard grid" in msg()
+        assert ch(eng, 0, 9, tp, 2049, 2049 * 2049 + 15, 400.0, 0.0025, 2.0) == EUNSUPPORTED
+        assert ch(eng, 0, 9, tp, 20, 384, 400.0, 0.0025, 2.0) == EINVAL and b"nx*nx" in msg()      # shorter than a state
+        assert ch(eng, 0, 9, tp, 20, 408, 400.0, 0.0025, 2.0) == EINVAL                            # not a multiple of 16
+        for bad in ((20, 400, 0.0, 0.0025, 2.0), (20, 400, 400.0, 0.0, 2.0), (20, 400, 400.0, -1.0, 2.0), (20, 400, 400.0, 0.0025, -0.5),
+                    (20, 400, float("inf"), 0.0025, 2.0), (20, 400, 400.0, float("nan"), 2.0), (20, 400, 400.0, float("inf"), 2.0),
+                    (20, 400, 400.0, 0.0025, float("nan")), (20, 400, 400.0, 0.0025, float("inf"))):
+            assert ch(eng, 0, 9, tp, *bad) == EINVAL and b"bad Cahn-Hilliard parameters" in msg(), bad
+        assert ch(eng, 0, 9, null, *ok) == EINVAL and ch(eng, 0, -1, tp, *ok) == EINVAL
+        assert ch(eng, 0, 9, tp, *ok) == 0 and ch(eng, 1, 9, tp, 10, 112, 100.0, 0.0025, 0.0) == 0      # (stab = 0 is allowed)
+        assert ch(eng, 0, 9, tp, *ok) < 0 and b"already" in msg()                # already described
+        # non-linear Phi: no time-parallel forward solve (r > 0 refused, the rule r < 0 leaves it step by step)
+        assert cfg(eng, 1, 4, 1, 0, null, null) == EUNSUPPORTED
+        assert cfg(eng, 1, -1, 1, 0, null, null) == 0
+        # the periodic transfer joins two Cahn-Hilliard levels with n_fine = 2 n_coarse, and the copy joins equal ones
+        assert lib.mgrit_hip_level_transfer(eng, 0, hip_lib.TRANSFER_PERIODIC2D) == 0
+        assert lib.mgrit_hip_level_transfer(eng, 0, hip_lib.TRANSFER_COPY) == EINVAL and b"equal DOFs" in msg()
+        assert ch(eng, 2, 9, tp, 12, 144, 144.0, 0.0025, 2.0) == 0
+        assert lib.mgrit_hip_level_transfer(eng, 1, hip_lib.TRANSFER_PERIODIC2D) == EINVAL and b"n_fine = 2*n_coarse" in msg()
+        # never a Cahn-Hilliard level with an Allen-Cahn level, in either order: the refusal of the other pairings, verbatim
+        assert ac(eng, 3, 9, tp, 8, 64, 64.0, 625.0, 2) == 0 and ch(eng, 4, 9, tp, 4, 16, 16.0, 0.0025, 2.0) == 0
+        for lvl in (2, 3):      # Cahn-Hilliard 12 over Allen-Cahn 8 (the kind is looked at first), Allen-Cahn 8 over Cahn-Hilliard 4
+            assert lib.mgrit_hip_level_transfer(eng, lvl, hip_lib.TRANSFER_PERIODIC2D) == EUNSUPPORTED
+            assert b"the periodic 2-D transfer joins two Allen-Cahn levels" in msg()
+        assert lib.mgrit_hip_level_transfer(eng, 2, hip_lib.TRANSFER_HEAT2D) == EUNSUPPORTED
+    finally:
+        assert lib.mgrit_hip_destroy(eng) == 0
