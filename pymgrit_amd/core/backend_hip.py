@@ -111,8 +111,15 @@ class SlabVectorList:
         return (self[k] for k in range(len(self)))
 
 
-GRID_2D = ("heat2d", "allencahn2d", "grayscott2d", "cahnhilliard2d")   # states are whole 2-D grids in natural row-major order (Gray-Scott: two of them,
-                                                     # [u plane | v plane]); the engine's Heat2D route
+# The applications on the periodic nx x nx grid, kind -> (name in the refusals, what every level of the hierarchy must be, whether the
+# levels share one nx joined by GridTransferCopy -- no spatial coarsening). Checked in this order (HipBackend._check_periodic).
+PERIODIC_2D = {
+    "allencahn2d": ("Allen-Cahn", "an AllenCahn application with method='IMEX', or 'IMPL' / 'CN' with linear_solver='pcg'", False),
+    "grayscott2d": ("Gray-Scott", "a GrayScott application with method='IMEX', or 'IMPL' with linear_solver='bicgstab', on the same nx", True),
+    "cahnhilliard2d": ("Cahn-Hilliard", "a CahnHilliard application (method='IMEX')", False),
+}
+GRID_2D = ("heat2d",) + tuple(PERIODIC_2D)   # states are whole 2-D grids in natural row-major order (Gray-Scott: two of them,
+                                             # [u plane | v plane]); the engine's Heat2D route
 
 
 class HipBackend:
@@ -129,12 +136,9 @@ class HipBackend:
         # one spare level index: the work level of AT-MGRIT on several ranks (at_forward_solve), described on first use
         check(self.lib.mgrit_hip_create(C.byref(self.h), mg.lvl_max + 1, C.c_void_p(self.stream.cuda_stream)))
         self.desc = [p.device_stepper() for p in mg.problem]
-        if any(d["kind"] == "allencahn2d" for d in self.desc):
-            self._check_allencahn(mg)
-        if any(d["kind"] == "grayscott2d" for d in self.desc):
-            self._check_grayscott(mg)
-        if any(d["kind"] == "cahnhilliard2d" for d in self.desc):
-            self._check_cahnhilliard(mg)
+        for kind in PERIODIC_2D:
+            if any(d["kind"] == kind for d in self.desc):
+                self._check_periodic(mg, kind)
         self.n = [int(d["n"]) for d in self.desc]
         # 1-D steppers: lane-blocked rows; Heat2D: the nx x ny grid in natural row-major order
         # two-point states: the row is [first | second], each half lane-blocked like a 1-D row of n values
@@ -194,48 +198,23 @@ class HipBackend:
         except Exception:
             pass
 
-    def _check_allencahn(self, mg):
-        """what the Allen-Cahn device path does not cover is refused by name, never run differently"""
-        from pymgrit_amd.core.at_mgrit import AtMgrit
-        if any(d["kind"] != "allencahn2d" for d in self.desc):
-            raise MgritHipError("Allen-Cahn levels on the HIP engine: every level of the hierarchy must be an AllenCahn "
-                                "application with method='IMEX', or 'IMPL' / 'CN' with linear_solver='pcg'")
-        if mg.comm_time_size > 1:
-            raise MgritHipError("Allen-Cahn levels on the HIP engine: one time rank only")
-        if isinstance(mg, AtMgrit):
-            raise MgritHipError("Allen-Cahn levels on the HIP engine: AT-MGRIT is not supported, use Mgrit")
-        if not mg.global_conv_crit:
-            raise MgritHipError("Allen-Cahn levels on the HIP engine: the global convergence criteria only (conv_crit 0 or 1)")
-
-    def _check_grayscott(self, mg):
-        """what the Gray-Scott device path does not cover is refused by name, never run differently"""
+    def _check_periodic(self, mg, kind):
+        """what the device path of a periodic 2-D application does not cover is refused by name, never run differently (transfers
+        of the kinds with spatial coarsening: GridTransferCopy, the application's own GridTransfer, or a user's through its Python
+        methods)"""
         from pymgrit_amd.core.at_mgrit import AtMgrit
         from pymgrit_amd.core.grid_transfer_copy import GridTransferCopy
-        if any(d["kind"] != "grayscott2d" for d in self.desc) or len({d["nx"] for d in self.desc}) != 1:
-            raise MgritHipError("Gray-Scott levels on the HIP engine: every level of the hierarchy must be a GrayScott application "
-                                "with method='IMEX', or 'IMPL' with linear_solver='bicgstab', on the same nx")
-        if any(type(tr) is not GridTransferCopy for tr in mg.transfer_objects):
-            raise MgritHipError("Gray-Scott levels on the HIP engine: GridTransferCopy only (no spatial coarsening)")
+        name, every_level, copy_only = PERIODIC_2D[kind]
+        if any(d["kind"] != kind for d in self.desc) or (copy_only and len({d["nx"] for d in self.desc}) != 1):
+            raise MgritHipError(f"{name} levels on the HIP engine: every level of the hierarchy must be {every_level}")
+        if copy_only and any(type(tr) is not GridTransferCopy for tr in mg.transfer_objects):
+            raise MgritHipError(f"{name} levels on the HIP engine: GridTransferCopy only (no spatial coarsening)")
         if mg.comm_time_size > 1:
-            raise MgritHipError("Gray-Scott levels on the HIP engine: one time rank only")
+            raise MgritHipError(f"{name} levels on the HIP engine: one time rank only")
         if isinstance(mg, AtMgrit):
-            raise MgritHipError("Gray-Scott levels on the HIP engine: AT-MGRIT is not supported, use Mgrit")
+            raise MgritHipError(f"{name} levels on the HIP engine: AT-MGRIT is not supported, use Mgrit")
         if not mg.global_conv_crit:
-            raise MgritHipError("Gray-Scott levels on the HIP engine: the global convergence criteria only (conv_crit 0 or 1)")
-
-    def _check_cahnhilliard(self, mg):
-        """what the Cahn-Hilliard device path does not cover is refused by name, never run differently (transfers: as for Allen-Cahn
-        levels -- GridTransferCopy, GridTransferCahnHilliard, or a user's GridTransfer through its Python methods)"""
-        from pymgrit_amd.core.at_mgrit import AtMgrit
-        if any(d["kind"] != "cahnhilliard2d" for d in self.desc):
-            raise MgritHipError("Cahn-Hilliard levels on the HIP engine: every level of the hierarchy must be a CahnHilliard "
-                                "application (method='IMEX')")
-        if mg.comm_time_size > 1:
-            raise MgritHipError("Cahn-Hilliard levels on the HIP engine: one time rank only")
-        if isinstance(mg, AtMgrit):
-            raise MgritHipError("Cahn-Hilliard levels on the HIP engine: AT-MGRIT is not supported, use Mgrit")
-        if not mg.global_conv_crit:
-            raise MgritHipError("Cahn-Hilliard levels on the HIP engine: the global convergence criteria only (conv_crit 0 or 1)")
+            raise MgritHipError(f"{name} levels on the HIP engine: the global convergence criteria only (conv_crit 0 or 1)")
 
     # -- state (mgrit.py:840-858) -------------------------------------------------------------------
     @staticmethod
@@ -399,7 +378,7 @@ class HipBackend:
         from pymgrit_amd.core.layout import compute_layout
         mg = self.mg
         r = C.c_int(0)
-        if d["kind"] in ("allencahn2d", "grayscott2d", "cahnhilliard2d"):
+        if d["kind"] in PERIODIC_2D:
             # non-linear Phi: the time-parallel forward solve superposes block defects and holds for linear steppers only -- the
             # coarsest level is solved step by step whatever options.coarse_solve says
             check(self.lib.mgrit_hip_block_solve_config(self.h, lvl, 0, 1, 0, None, None))

@@ -1612,7 +1612,36 @@ struct PairList {
     BatchPlans fine_to_coarse, fine_to_rows, coarse;   // fine half into g^{l+1} (dst: the coarse slot) or into rows (dst: the pair's position)
 };
 
+constexpr int H2D_MAX_BATCH = 1024;  // items per GEMM batch (work buffers: 2 x 1024 x Mi x Mj doubles; 2048 measured no faster)
 enum class H2DKind { HEAT2D, ALLENCAHN_IMEX, ALLENCAHN_NEWTON, GRAYSCOTT_IMEX, GRAYSCOTT_NEWTON, CAHNHILLIARD_IMEX };   // what a level of the batched 2-D route steps with
+// What is a constant of a kind, one row per kind in the enum's order. The Newton columns (0 for the other kinds): the work rows of an
+// item, comps planes each -- Allen-Cahn PCG x, rhs, r, z, p, Jp, delta + the two operands of the preconditioner's
+// products; Gray-Scott BiCGStab (3.11) x, w, r, r^, p, v, s, y, delta + the same two, which between two sets of products carry
+// z = P^-1 s and t = J z --, the int32 and double columns of its solver state (ACNState / GSNState), the partial pairs behind them,
+// the items of a batch and the inner iterations between two reads of the batch's "items running" word (Allen-Cahn: DESIGN.md 3.9;
+// Gray-Scott: 3 .. 5 BiCGStab iterations per Newton step measured on the host).
+struct H2DKindRow {
+    const char *name;   // the application, as the messages spell it: two kinds with one name are forms of one application
+    bool periodic;      // on the periodic nx x nx grid (mgrit_hip_periodic2d.inc)
+    int comps;          // planes of a state row
+    int items;          // work slab items of a state in the first two products (Cahn-Hilliard: u and w(u) from its one plane,
+                        // joined by the second)
+    bool transfer2d;    // the device 2-D transfer joins two levels of it
+    int n_rows, n_int, n_dbl, nb, max_batch, check_every;
+};
+// items per Newton batch: the work rows of a batch stay within the 2 x H2D_MAX_BATCH items the level's IMEX form reserves
+constexpr int newton_cap(int comps, int n_rows) { return 2 * H2D_MAX_BATCH / (comps * n_rows); }
+constexpr H2DKindRow H2D_KINDS[] = {
+    {"Heat2D", false, 1, 1, true, 0, 0, 0, 0, 0, 0},
+    {"Allen-Cahn", true, 1, 1, true, 0, 0, 0, 0, 0, 0},
+    {"Allen-Cahn", true, 1, 1, true, 9, 5, 4, ACN_NB, newton_cap(1, 9), 4},
+    {"Gray-Scott", true, 2, 2, false, 0, 0, 0, 0, 0, 0},
+    {"Gray-Scott", true, 2, 2, false, 11, 6, 5, GSN_NB, newton_cap(2, 11), 2},
+    {"Cahn-Hilliard", true, 1, 2, true, 0, 0, 0, 0, 0, 0},
+};
+constexpr const H2DKindRow &kind_row(H2DKind k) { return H2D_KINDS[(int)k]; }
+static_assert(kind_row(H2DKind::ALLENCAHN_NEWTON).max_batch <= 256, "acn_reduce_kernel: one thread per item of a batch, one workgroup");
+static_assert(kind_row(H2DKind::GRAYSCOTT_NEWTON).max_batch <= 256, "gsn_reduce_kernel: one thread per item of a batch, one workgroup");
 struct H2DHost {
     H2DDev dev{};
     std::vector<double> lx, ly, dts;
@@ -1635,19 +1664,14 @@ struct H2DHost {
     } blk;
     // The levels on the periodic nx x nx grid (mgrit_hip_periodic2d.inc) run through this route with their own transforms: the full
     // Hartley table [P][P] (P = Mi = Mj = nx padded to 64), lx = ly = the periodic Laplacian's eigenvalues in natural mode order, no
-    // rim, no fold. A Gray-Scott state row holds two planes [u | v]: two work slab items per state, a D table per species, the
-    // right-hand side from both planes. ALLENCAHN_NEWTON: an Allen-Cahn level whose Phi is the Newton-PCG step (newton_state below);
-    // GRAYSCOTT_NEWTON: a Gray-Scott level whose Phi is the Newton-BiCGStab step, with the same struct for its parameters and work rows.
-    // CAHNHILLIARD_IMEX: one plane per state like Allen-Cahn, two work slab items per state like Gray-Scott, a [2][P][P] table (D1, D2).
+    // rim, no fold. A Gray-Scott state row holds two planes [u | v], a D table per species, the right-hand side from both planes;
+    // Cahn-Hilliard a [2][P][P] table (D1, D2). The Newton kinds: the level's Phi is the Newton step over newton_state below.
     H2DKind kind = H2DKind::HEAT2D;
-    bool periodic() const { return kind != H2DKind::HEAT2D; }
-    bool allencahn() const { return kind == H2DKind::ALLENCAHN_IMEX || kind == H2DKind::ALLENCAHN_NEWTON; }
-    bool grayscott() const { return kind == H2DKind::GRAYSCOTT_IMEX || kind == H2DKind::GRAYSCOTT_NEWTON; }
-    bool newton() const { return kind == H2DKind::ALLENCAHN_NEWTON || kind == H2DKind::GRAYSCOTT_NEWTON; }
-    bool cahnhilliard() const { return kind == H2DKind::CAHNHILLIARD_IMEX; }
-    int comps() const { return grayscott() ? 2 : 1; }                      // planes of a state row
-    int items() const { return grayscott() || cahnhilliard() ? 2 : 1; }   // work slab items of a state in the first two products (Cahn-
-                                                                           // Hilliard: u and w(u) from its one plane, joined by the second)
+    const H2DKindRow &row() const { return kind_row(kind); }
+    bool periodic() const { return row().periodic; }
+    bool newton() const { return row().max_batch > 0; }
+    int comps() const { return row().comps; }
+    int items() const { return row().items; }
     double *T = nullptr;   // the Hartley table
     int KP = 0;            // nx rounded up to the K step of the tile product
     struct { double inv_dx2 = 0.0, inv_eps2 = 0.0; int nu = 0; } ac;
@@ -1656,26 +1680,23 @@ struct H2DHost {
     double *Wc0 = nullptr, *Wc1 = nullptr;   // one item each: the work buffers of the coarsest-level chain, which in a planned
                                              // cycle steps on a second stream BESIDE sweeps that apply this level's Phi too (the
                                              // coarse half of the FAS right-hand side of another block of time points)
-    // Allen-Cahn IMPL / CN with Newton-PCG steps (mgrit_hip_level_allencahn2d_newton; acn_* in mgrit_hip_allencahn.inc): the solver's
-    // parameters, the shifted D tables 1/(1 + fac nu/eps^2 + fac (lam_i + lam_j)) per distinct dt (theta is the level's: one table per
-    // (dt, theta)), the work rows of the batched route and of the coarsest-level chain (batches of one), the word the host reads.
-    // Gray-Scott IMPL with Newton-BiCGStab steps (mgrit_hip_level_grayscott2d_newton; gsn_* in mgrit_hip_grayscott.inc) keeps the same
-    // things here: theta = 1, dinv the [2][P][P] tables of its block preconditioner, rows / ints / dbls sized for GSN_ROWS and GSNState.
+    // A Newton kind (newton_attach; Allen-Cahn IMPL / CN by PCG, acn_* in mgrit_hip_allencahn.inc; Gray-Scott IMPL by BiCGStab, gsn_* in
+    // mgrit_hip_grayscott.inc): the solver's parameters (theta is the level's; Gray-Scott 1), the preconditioner's D tables per distinct
+    // dt (newton_dinv), the work rows of the batched route and of the coarsest-level chain (batches of one), the word the host reads
     struct Newton {
         double theta = 1.0, newton_tol = 0.0, lin_tol = 0.0;
         int newton_maxiter = 0, lin_maxiter = 0;
         std::map<uint64_t, double *> dinv;
         struct Work {
-            double *rows = nullptr;   // [ACN_ROWS][cap] items of P x P doubles: x, rhs, r, z, p, Jp, delta and the products' W0, W1
-                                      // (Gray-Scott: [GSN_ROWS][cap] items of two such planes)
-            int32_t *ints = nullptr;  // [5][cap]  (Gray-Scott: [6][cap])
-            double *dbls = nullptr;   // [4][cap] and the partials [cap][ACN_NB][2]  (Gray-Scott: [5][cap] and [cap][GSN_NB][2])
+            double *rows = nullptr;   // (the counts: the kind's row of H2D_KINDS) [n_rows][cap] items of comps planes of P x P doubles, the products' W0 and W1 the last two
+            int32_t *ints = nullptr;  // [n_int][cap]
+            double *dbls = nullptr;   // [n_dbl][cap] and the partials [cap][nb][2]
             size_t cap = 0;
         } main, chain;
         unsigned *word = nullptr;            // pinned, device-mapped
         hipEvent_t ev = nullptr;
         unsigned long long *tot = nullptr;   // device: the four counts of mgrit_hip_newton_stats
-    } newton_state;   // (the two Newton kinds share it: Allen-Cahn PCG, Gray-Scott BiCGStab)
+    } newton_state;
 };
 // What the two structs own outside the level's allocs and the upload arena (the engine's streams are idle)
 void h2d_blk_release(H2DHost::Blk &k) {
@@ -2529,7 +2550,6 @@ HalfCoef bdf2_half(double tau_i, double tau_im1) {
 // ---------------------------------------------------------------------------------------------------------------
 // Batch plans of the batched route (Heat2D, Allen-Cahn, wide 1-D); Heat2D host side: tables, the batched Phi pipeline
 // ---------------------------------------------------------------------------------------------------------------
-constexpr int H2D_MAX_BATCH = 1024;  // items per GEMM batch (work buffers: 2 x 1024 x Mi x Mj doubles; 2048 measured no faster)
 constexpr int WIDE_MAX_BATCH = 2048;   // wide 1-D levels: items per batch (work slab: 2048 rows of up to 512 KB)
 
 uint64_t dbl_bits(double v) { uint64_t b; std::memcpy(&b, &v, 8); return b; }
@@ -2643,7 +2663,7 @@ int h2d_reserve(Level &lv, int count) {
     if (h.rowsq) HIP_TRY(hipFree(h.rowsq));
     h.W0 = h.W1 = h.rowsq = nullptr;
     const size_t per = (size_t)h.dev.Mi * h.dev.Mj * h.items();
-    if (!h.newton()) {   // (a Newton-PCG level's products run on its own work rows: acn_reserve)
+    if (!h.newton()) {   // (a Newton level's products run on its own work rows: newton_reserve)
         HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.W0), sizeof(double) * per * count));
         HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h.W1), sizeof(double) * per * count));
     }
@@ -2697,10 +2717,17 @@ int h2d_dinv(mgrit_hip_engine *e, Level &lv, uint64_t dtbits, double **out) {
     H2DHost &h = *lv.h2d;
     const size_t per = (size_t)h.dev.Mi * h.dev.Mj;
     return h2d_table_once(e, lv, h.dinv, dtbits, per * h.items(), [&](double dt, double *tab) {
-        if (h.kind == H2DKind::GRAYSCOTT_IMEX) {
+        switch (h.kind) {
+        case H2DKind::HEAT2D: {
+            const double thdt = h.dev.theta * dt;
+            h2d_each_mode(h, [&](size_t q, double lam) { tab[q] = 1.0 / (1.0 + thdt * lam); });
+            break;
+        }
+        case H2DKind::GRAYSCOTT_IMEX:
             p2d_fill_dinv(h, tab, 1.0, dt * h.gs.du);
             p2d_fill_dinv(h, tab + per, 1.0, dt * h.gs.dv);
-        } else if (h.cahnhilliard()) {
+            break;
+        case H2DKind::CAHNHILLIARD_IMEX:
             for (int a = 0; a < h.dev.nx; ++a)
                 for (int b = 0; b < h.dev.nx; ++b) {
                     const double mu = h.lx[a] + h.ly[b];
@@ -2708,10 +2735,8 @@ int h2d_dinv(mgrit_hip_engine *e, Level &lv, uint64_t dtbits, double **out) {
                     tab[(size_t)a * h.dev.Mj + b] = d1;
                     tab[per + (size_t)a * h.dev.Mj + b] = -(dt * mu) * d1;
                 }
-        } else if (h.periodic()) p2d_fill_dinv(h, tab, 1.0, dt);
-        else {
-            const double thdt = h.dev.theta * dt;
-            h2d_each_mode(h, [&](size_t q, double lam) { tab[q] = 1.0 / (1.0 + thdt * lam); });
+            break;
+        default: p2d_fill_dinv(h, tab, 1.0, dt);   // Allen-Cahn (the Newton kinds have their own tables: newton_dinv)
         }
     }, out);
 }
@@ -2762,13 +2787,7 @@ int ch_products(mgrit_hip_engine *e, const H2DHost &h, int count, const CHPre &p
     return 0;
 }
 
-// ---- Allen-Cahn Newton-PCG steps --------------------------------------------------------------------------------
-constexpr int ACN_ROWS = 9;   // x, rhs, r, z, p, Jp, delta + the two operands of the preconditioner's products
-// items per Newton batch: the ACN_ROWS work rows of a batch stay within the 2 x H2D_MAX_BATCH items the level's IMEX form reserves
-constexpr int ACN_MAX_BATCH = 2 * H2D_MAX_BATCH / ACN_ROWS;
-static_assert(ACN_MAX_BATCH <= 256, "acn_reduce_kernel: one thread per item of a batch, one workgroup");
-constexpr int ACN_CHECK_EVERY = 4;   // CG iterations between two reads of the batch's "items running" word
-
+// ---- Newton steps of the periodic levels: Allen-Cahn Newton-PCG, Gray-Scott Newton-BiCGStab (3.11) -----------------
 BatchPlan batch_slice(const BatchPlan &pl, int off, int count) {
     BatchPlan s = pl;
     s.count = count;
@@ -2777,40 +2796,54 @@ BatchPlan batch_slice(const BatchPlan &pl, int off, int count) {
     return s;
 }
 
-// the work of a Newton batch of count items: n_rows rows of comps() planes each, n_int int32 and n_dbl doubles per item beside nb partial pairs
-int newton_reserve(mgrit_hip_engine *e, H2DHost &h, H2DHost::Newton::Work &w, int count, int n_rows, int n_int, int n_dbl_item, int nb) {
+// the work of a Newton batch of count items, the counts of the level's kind: n_rows rows of comps() planes each, n_int int32 and n_dbl
+// doubles per item beside nb partial pairs
+int newton_reserve(mgrit_hip_engine *e, H2DHost &h, H2DHost::Newton::Work &w, int count) {
     if ((size_t)count <= w.cap) return 0;
+    const H2DKindRow &K = h.row();
     HIP_TRY(hipStreamSynchronize(e->stream));   // (the rows about to be freed may still be read)
     for (void *p : {(void *)w.rows, (void *)w.ints, (void *)w.dbls})
         if (p) HIP_TRY(hipFree(p));
     w.rows = nullptr; w.ints = nullptr; w.dbls = nullptr; w.cap = 0;
-    const size_t per = (size_t)h.dev.Mi * h.dev.Mj * h.comps(), n_dbl = (size_t)count * (n_dbl_item + 2 * nb);
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&w.rows), sizeof(double) * per * n_rows * count));
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&w.ints), sizeof(int32_t) * n_int * count));
+    const size_t per = (size_t)h.dev.Mi * h.dev.Mj * h.comps(), n_dbl = (size_t)count * (K.n_dbl + 2 * K.nb);
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&w.rows), sizeof(double) * per * K.n_rows * count));
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&w.ints), sizeof(int32_t) * K.n_int * count));
     HIP_TRY(hipMalloc(reinterpret_cast<void **>(&w.dbls), sizeof(double) * n_dbl));
     // the pads of every work row are zero and stay zero: no kernel writes them, the products map zero pads to zero pads
-    HIP_TRY(hipMemsetAsync(w.rows, 0, sizeof(double) * per * n_rows * count, e->stream));
-    HIP_TRY(hipMemsetAsync(w.ints, 0, sizeof(int32_t) * n_int * count, e->stream));
+    HIP_TRY(hipMemsetAsync(w.rows, 0, sizeof(double) * per * K.n_rows * count, e->stream));
+    HIP_TRY(hipMemsetAsync(w.ints, 0, sizeof(int32_t) * K.n_int * count, e->stream));
     HIP_TRY(hipMemsetAsync(w.dbls, 0, sizeof(double) * n_dbl, e->stream));
     w.cap = count;
     return 0;
 }
-int acn_reserve(mgrit_hip_engine *e, H2DHost &h, H2DHost::Newton::Work &w, int count) { return newton_reserve(e, h, w, count, ACN_ROWS, 5, 4, ACN_NB); }
 
-// D of the preconditioner P = (1 + fac nu / eps^2) I - fac L, fac = theta dt
-int acn_dinv(mgrit_hip_engine *e, Level &lv, uint64_t dtbits, double **out) {
+// D of a Newton level's preconditioner, comps() tables [P][P]. Allen-Cahn: P = (1 + fac nu / eps^2) I - fac L, fac = theta dt;
+// Gray-Scott: P = blockdiag((1 + dt a) I - dt du L, (1 + dt b) I - dt dv L), species u then v
+int newton_dinv(mgrit_hip_engine *e, Level &lv, uint64_t dtbits, double **out) {
     H2DHost &h = *lv.h2d;
-    return h2d_table_once(e, lv, h.newton_state.dinv, dtbits, (size_t)h.dev.Mi * h.dev.Mj, [&](double dt, double *tab) {
-        const double fac = h.newton_state.theta * dt;
-        p2d_fill_dinv(h, tab, 1.0 + fac * (double)h.ac.nu * h.ac.inv_eps2, fac);
+    const size_t per = (size_t)h.dev.Mi * h.dev.Mj;
+    return h2d_table_once(e, lv, h.newton_state.dinv, dtbits, per * h.comps(), [&](double dt, double *tab) {
+        switch (h.kind) {
+        case H2DKind::ALLENCAHN_NEWTON: {
+            const double fac = h.newton_state.theta * dt;
+            p2d_fill_dinv(h, tab, 1.0 + fac * (double)h.ac.nu * h.ac.inv_eps2, fac);
+            break;
+        }
+        case H2DKind::GRAYSCOTT_NEWTON:
+            p2d_fill_dinv(h, tab, 1.0 + dt * h.gs.a, dt * h.gs.du);
+            p2d_fill_dinv(h, tab + per, 1.0 + dt * h.gs.b, dt * h.gs.dv);
+            break;
+        default: break;   // (no other kind has a Newton form)
+        }
     }, out);
 }
 
-// The one word of a batch the host reads: the items still running, written by acn_reduce_kernel into pinned memory in front of the
-// event. A bounded wait (as mgrit_hip_sync_bounded), never an open spin. Allen-Cahn levels never enter planned or captured cycles
-// (HipBackend.plan_allowed / plan_single_block leave "allencahn2d" and "grayscott2d" out), so a host read between two launches is
-// always possible here. The Gray-Scott Newton-BiCGStab loop (gsn_phi_batch) reads its word the same way.
-int acn_running(mgrit_hip_engine *e, H2DHost::Newton &N, unsigned *out, const char *app = "Allen-Cahn") {
+// The one word of a batch the host reads: the items still running, written by the kind's reduce kernel into pinned memory in front of
+// the event. A bounded wait (as mgrit_hip_sync_bounded), never an open spin. The periodic levels never enter planned or captured cycles
+// (HipBackend.plan_allowed / plan_single_block list the kinds they allow, and no periodic kind is among them), so a host read between
+// two launches is always possible here.
+int newton_running(mgrit_hip_engine *e, const H2DHost &h, unsigned *out) {
+    const H2DHost::Newton &N = h.newton_state;
     HIP_TRY(hipEventRecord(N.ev, e->stream));
     const auto t0 = std::chrono::steady_clock::now();
     for (;;) {
@@ -2818,153 +2851,163 @@ int acn_running(mgrit_hip_engine *e, H2DHost::Newton &N, unsigned *out, const ch
         if (q == hipSuccess) break;
         if (q != hipErrorNotReady) return fail(MGRIT_HIP_EHIP, "hipEventQuery: %s", hipGetErrorString(q));
         if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 60.0)
-            return fail(MGRIT_HIP_EHIP, "%s Newton step: the batch's kernels did not finish within 60 s", app);
+            return fail(MGRIT_HIP_EHIP, "%s Newton step: the batch's kernels did not finish within 60 s", h.row().name);
         std::this_thread::sleep_for(std::chrono::microseconds(20));   // (as mgrit_hip_sync_bounded: the host core is not held)
     }
     *out = *static_cast<volatile unsigned *>(N.word);
     return 0;
 }
 
-// Phi of one batch of at most ACN_MAX_BATCH items by Newton-PCG; the converged x through the sweep's arithmetic (fin) or left in the
-// work row x (no fin: h2d_points_sumsq reads it there). Launches per batch <= newton_maxiter * (11 lin_maxiter + 4) + 4 by construction.
-int acn_phi_batch(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const double *in_slab, bool chain, const H2DFin *fin) {
-    H2DHost &h = *lv.h2d;
-    H2DHost::Newton &N = h.newton_state;
-    const H2DDev &H = h.dev;
-    H2DHost::Newton::Work &w = chain ? N.chain : N.main;
-    int rc;
-    if (pl.count < 1) return 0;
-    if (pl.count > ACN_MAX_BATCH) return fail(MGRIT_HIP_EINVAL, "Newton batch of %d items", pl.count);
-    if ((rc = acn_reserve(e, h, w, pl.count))) return rc;
-    double *dinv = nullptr;
-    if ((rc = acn_dinv(e, lv, pl.dtbits, &dinv))) return rc;
-    double dt;
-    std::memcpy(&dt, &pl.dtbits, 8);
-    const int P = H.Mi, n = H.nx * H.nx, nb = std::min(ACN_NB, (n + 255) / 256);
-    const size_t per = (size_t)P * P, slab = per * w.cap;
-    double *const x = w.rows, *const rhs = x + slab, *const r = rhs + slab, *const z = r + slab, *const p = z + slab, *const jp = p + slab,
-                 *const delta = jp + slab, *const W0 = delta + slab, *const W1 = W0 + slab;
-    const size_t c = w.cap;
-    const ACNState S{w.ints, w.ints + c, w.ints + 2 * c, w.ints + 3 * c, w.ints + 4 * c, w.dbls, w.dbls + c, w.dbls + 2 * c, w.dbls + 3 * c,
-                     w.dbls + 4 * c};
-    const ACNPar A{H.nx, P, h.ac.nu, h.ac.inv_dx2, h.ac.inv_eps2, N.theta * dt};
-    const dim3 ge(nb, 1, pl.count), b256(256);
-    hipLaunchKernelGGL(acn_init_kernel, ge, b256, 0, e->stream, A, S, in_slab, pl.d_in, H.ld, x, N.theta == 1.0 ? rhs : nullptr, per);
-    if (N.theta != 1.0) hipLaunchKernelGGL((acn_residual_kernel<true>), ge, b256, 0, e->stream, A, S, x, nullptr, rhs, per);
-    for (int it = 0; it < N.newton_maxiter; ++it) {
-        hipLaunchKernelGGL((acn_residual_kernel<false>), ge, b256, 0, e->stream, A, S, x, rhs, r, per);
-        hipLaunchKernelGGL((acn_reduce_kernel<ACN_R_NEWTON>), dim3(1), b256, 0, e->stream, S, pl.count, nb, N.newton_tol, N.lin_tol,
-                           N.lin_maxiter, N.word);
-        HIP_TRY(hipGetLastError());
-        unsigned running = 0;
-        if ((rc = acn_running(e, N, &running))) return rc;
-        if (!running) break;
-        for (int k = 0; k < N.lin_maxiter; ++k) {
-            if ((rc = (p2d_products<ACPre, true>(e, h, pl.count, ACPre{0.0, 0}, r, S.cg, dinv, W0, W1, z, nullptr)))) return rc;
-            hipLaunchKernelGGL(acn_dot_kernel, ge, b256, 0, e->stream, A, S, r, z, per);
-            hipLaunchKernelGGL((acn_reduce_kernel<ACN_R_RZ>), dim3(1), b256, 0, e->stream, S, pl.count, nb, N.newton_tol, N.lin_tol, N.lin_maxiter, N.word);
-            hipLaunchKernelGGL(acn_dir_kernel, ge, b256, 0, e->stream, A, S, z, p, per);
-            hipLaunchKernelGGL(acn_jp_kernel, ge, b256, 0, e->stream, A, S, x, p, jp, per);
-            hipLaunchKernelGGL((acn_reduce_kernel<ACN_R_PJP>), dim3(1), b256, 0, e->stream, S, pl.count, nb, N.newton_tol, N.lin_tol, N.lin_maxiter, N.word);
-            hipLaunchKernelGGL(acn_update_kernel, ge, b256, 0, e->stream, A, S, p, jp, delta, r, per);
-            hipLaunchKernelGGL((acn_reduce_kernel<ACN_R_RR>), dim3(1), b256, 0, e->stream, S, pl.count, nb, N.newton_tol, N.lin_tol, N.lin_maxiter, N.word);
-            HIP_TRY(hipGetLastError());
-            if ((k + 1) % ACN_CHECK_EVERY == 0 && k + 1 < N.lin_maxiter) {   // (after lin_maxiter iterations no item is running)
-                if ((rc = acn_running(e, N, &running))) return rc;
-                if (!running) break;
-            }
-        }
-        hipLaunchKernelGGL(acn_step_kernel, ge, b256, 0, e->stream, A, S, x, delta, per);
+// What the launches of one Newton batch work on (made by newton_phi_batch): per = P * P, one plane; rows[i] the batch's i-th work row,
+// cap items of comps() planes; nb workgroups per item of the elementwise kernels
+constexpr int NEWTON_MAX_ROWS = 11;
+struct NewtonBatch {
+    mgrit_hip_engine *e;
+    const H2DHost &h;
+    const H2DHost::Newton::Work &w;
+    const BatchPlan &pl;
+    const double *in_slab;
+    double dt = 0.0, *dinv = nullptr, *rows[NEWTON_MAX_ROWS] = {};
+    int nb = 0;
+    size_t per = 0;
+    dim3 ge{}, b256{256}, one{1};
+};
+
+// The launches of an Allen-Cahn Newton-PCG batch, in newton_phi_batch's order. Launches per batch <= newton_maxiter * (11 lin_maxiter
+// + 4) + 4 by construction.
+struct ACNBatch {
+    const NewtonBatch &B;
+    const H2DHost::Newton &N;
+    hipStream_t st;
+    const size_t per, c;
+    double *const x, *const rhs, *const r, *const z, *const p, *const jp, *const delta, *const W0, *const W1;
+    const ACNState S;
+    const ACNPar A;
+    explicit ACNBatch(const NewtonBatch &b)
+        : B(b), N(b.h.newton_state), st(b.e->stream), per(b.per), c(b.w.cap), x(b.rows[0]), rhs(b.rows[1]), r(b.rows[2]), z(b.rows[3]),
+          p(b.rows[4]), jp(b.rows[5]), delta(b.rows[6]), W0(b.rows[7]), W1(b.rows[8]),
+          S{b.w.ints, b.w.ints + c, b.w.ints + 2 * c, b.w.ints + 3 * c, b.w.ints + 4 * c, b.w.dbls, b.w.dbls + c, b.w.dbls + 2 * c,
+            b.w.dbls + 3 * c, b.w.dbls + 4 * c},
+          A{b.h.dev.nx, b.h.dev.Mi, b.h.ac.nu, b.h.ac.inv_dx2, b.h.ac.inv_eps2, N.theta * b.dt} {}
+    template <int WHAT>
+    void reduce() const {
+        hipLaunchKernelGGL((acn_reduce_kernel<WHAT>), B.one, B.b256, 0, st, S, B.pl.count, B.nb, N.newton_tol, N.lin_tol, N.lin_maxiter, N.word);
     }
-    if (fin) hipLaunchKernelGGL(acn_finish_kernel, ge, b256, 0, e->stream, A, x, per, H, *fin);
-    hipLaunchKernelGGL(acn_stats_kernel, dim3(1), b256, 0, e->stream, S, pl.count, N.tot);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
+    void init() const {
+        hipLaunchKernelGGL(acn_init_kernel, B.ge, B.b256, 0, st, A, S, B.in_slab, B.pl.d_in, B.h.dev.ld, x, N.theta == 1.0 ? rhs : nullptr, per);
+        if (N.theta != 1.0) hipLaunchKernelGGL((acn_residual_kernel<true>), B.ge, B.b256, 0, st, A, S, x, nullptr, rhs, per);
+    }
+    void residual() const {   // and the Newton reduce
+        hipLaunchKernelGGL((acn_residual_kernel<false>), B.ge, B.b256, 0, st, A, S, x, rhs, r, per);
+        reduce<ACN_R_NEWTON>();
+    }
+    int inner() const {   // one CG iteration
+        int rc;
+        if ((rc = (p2d_products<ACPre, true>(B.e, B.h, B.pl.count, ACPre{0.0, 0}, r, S.cg, B.dinv, W0, W1, z, nullptr)))) return rc;
+        hipLaunchKernelGGL(acn_dot_kernel, B.ge, B.b256, 0, st, A, S, r, z, per);
+        reduce<ACN_R_RZ>();
+        hipLaunchKernelGGL(acn_dir_kernel, B.ge, B.b256, 0, st, A, S, z, p, per);
+        hipLaunchKernelGGL(acn_jp_kernel, B.ge, B.b256, 0, st, A, S, x, p, jp, per);
+        reduce<ACN_R_PJP>();
+        hipLaunchKernelGGL(acn_update_kernel, B.ge, B.b256, 0, st, A, S, p, jp, delta, r, per);
+        reduce<ACN_R_RR>();
+        return 0;
+    }
+    void step() const { hipLaunchKernelGGL(acn_step_kernel, B.ge, B.b256, 0, st, A, S, x, delta, per); }
+    void finish(const H2DFin &fin) const { hipLaunchKernelGGL(acn_finish_kernel, B.ge, B.b256, 0, st, A, x, per, B.h.dev, fin); }
+    void stats() const { hipLaunchKernelGGL(acn_stats_kernel, B.one, B.b256, 0, st, S, B.pl.count, N.tot); }
+};
 
-// ---- Gray-Scott Newton-BiCGStab steps --------------------------------------------------------------------------
-// work rows of an item, two planes each: x, w, r, r^, p, v, s, y, delta + the two operands of the preconditioner's products, which
-// between two sets of products carry z = P^-1 s (W0, the last product's output) and t = J z (W1): 11 rows, 22 work slab items a state
-constexpr int GSN_ROWS = 11;
-// items per Newton batch: the GSN_ROWS work rows of a batch stay within the 2 x H2D_MAX_BATCH items the level's IMEX form reserves
-constexpr int GSN_MAX_BATCH = 2 * H2D_MAX_BATCH / (2 * GSN_ROWS);
-static_assert(GSN_MAX_BATCH <= 256, "gsn_reduce_kernel: one thread per item of a batch, one workgroup");
-constexpr int GSN_CHECK_EVERY = 2;   // BiCGStab iterations between two reads of the batch's "items running" word (3 .. 5 per Newton step measured on the host)
+// The launches of a Gray-Scott Newton-BiCGStab batch, in newton_phi_batch's order. Launches per batch <= newton_maxiter * (17
+// lin_maxiter + 3) + 3 by construction: per inner iteration 2 x 4 products, 5 elementwise / stencil kernels and 4 reduce kernels; per
+// Newton iteration the residual, its reduce and the step; init, finish, stats.
+struct GSNBatch {
+    const NewtonBatch &B;
+    const H2DHost::Newton &N;
+    hipStream_t st;
+    const size_t per, c;
+    double *const x, *const wr, *const r, *const rhat, *const p, *const v, *const s, *const y, *const delta, *const W0, *const W1;
+    double *const z, *const t;   // (between the products of z and those of the next y)
+    const GSNState S;
+    const GSNPar A;
+    const GSPre none{0.0, 0.0, 0.0, 0};   // (the work modes of the products apply no map; its two operands make them two-plane)
+    explicit GSNBatch(const NewtonBatch &b)
+        : B(b), N(b.h.newton_state), st(b.e->stream), per(b.per), c(b.w.cap), x(b.rows[0]), wr(b.rows[1]), r(b.rows[2]), rhat(b.rows[3]),
+          p(b.rows[4]), v(b.rows[5]), s(b.rows[6]), y(b.rows[7]), delta(b.rows[8]), W0(b.rows[9]), W1(b.rows[10]), z(W0), t(W1),
+          S{b.w.ints, b.w.ints + c, b.w.ints + 2 * c, b.w.ints + 3 * c, b.w.ints + 4 * c, b.w.ints + 5 * c,
+            b.w.dbls, b.w.dbls + c, b.w.dbls + 2 * c, b.w.dbls + 3 * c, b.w.dbls + 4 * c, b.w.dbls + 5 * c},
+          A{ACNPar{b.h.dev.nx, b.h.dev.Mi, 0, b.h.gs.inv_dx2, 0.0, 0.0}, b.h.gs.du, b.h.gs.dv, b.h.gs.a, b.h.gs.b, b.dt} {}
+    template <int WHAT>
+    void reduce() const {
+        hipLaunchKernelGGL((gsn_reduce_kernel<WHAT>), B.one, B.b256, 0, st, S, B.pl.count, B.nb, N.newton_tol, N.lin_tol, N.lin_maxiter, N.word);
+    }
+    void init() const { hipLaunchKernelGGL(gsn_init_kernel, B.ge, B.b256, 0, st, A, S, B.in_slab, B.pl.d_in, B.h.dev.ld, x, wr, per); }
+    void residual() const {   // and the Newton reduce
+        hipLaunchKernelGGL(gsn_residual_kernel, B.ge, B.b256, 0, st, A, S, x, wr, r, rhat, per);
+        reduce<GSN_R_NEWTON>();
+    }
+    int inner() const {   // one BiCGStab iteration
+        int rc;
+        hipLaunchKernelGGL(gsn_dir_kernel, B.ge, B.b256, 0, st, A, S, r, v, p, per);
+        if ((rc = (p2d_products<GSPre, true>(B.e, B.h, B.pl.count, none, p, S.lin, B.dinv, W0, W1, y, nullptr)))) return rc;
+        hipLaunchKernelGGL((gsn_jy_kernel<false>), B.ge, B.b256, 0, st, A, S, x, y, rhat, v, per);
+        reduce<GSN_R_SIGMA>();
+        hipLaunchKernelGGL(gsn_s_kernel, B.ge, B.b256, 0, st, A, S, r, v, s, per);
+        reduce<GSN_R_HALF>();
+        if ((rc = (p2d_products<GSPre, true>(B.e, B.h, B.pl.count, none, s, S.lin, B.dinv, W0, W1, z, nullptr)))) return rc;
+        hipLaunchKernelGGL((gsn_jy_kernel<true>), B.ge, B.b256, 0, st, A, S, x, z, s, t, per);
+        reduce<GSN_R_OMEGA>();
+        hipLaunchKernelGGL(gsn_update_kernel, B.ge, B.b256, 0, st, A, S, y, z, s, t, rhat, delta, r, per);
+        reduce<GSN_R_FULL>();
+        return 0;
+    }
+    void step() const { hipLaunchKernelGGL(gsn_step_kernel, B.ge, B.b256, 0, st, A, S, x, delta, per); }
+    void finish(const H2DFin &fin) const { hipLaunchKernelGGL(gsn_finish_kernel, B.ge, B.b256, 0, st, A, x, per, B.h.dev, fin); }
+    void stats() const { hipLaunchKernelGGL(gsn_stats_kernel, B.one, B.b256, 0, st, S, B.pl.count, N.tot); }
+};
 
-// the Newton batch cap of a level's kind
-int newton_max_batch(const H2DHost &h) { return h.grayscott() ? GSN_MAX_BATCH : ACN_MAX_BATCH; }
-
-// D of the block preconditioner P = blockdiag((1 + dt a) I - dt du L, (1 + dt b) I - dt dv L): [2][P][P], species u then v
-int gsn_dinv(mgrit_hip_engine *e, Level &lv, uint64_t dtbits, double **out) {
-    H2DHost &h = *lv.h2d;
-    const size_t per = (size_t)h.dev.Mi * h.dev.Mj;
-    return h2d_table_once(e, lv, h.newton_state.dinv, dtbits, 2 * per, [&](double dt, double *tab) {
-        p2d_fill_dinv(h, tab, 1.0 + dt * h.gs.a, dt * h.gs.du);
-        p2d_fill_dinv(h, tab + per, 1.0 + dt * h.gs.b, dt * h.gs.dv);
-    }, out);
-}
-
-// Phi of one batch of at most GSN_MAX_BATCH items by Newton-BiCGStab; the converged x through the sweep's arithmetic (fin) or left in
-// the work row x (no fin: h2d_points_sumsq reads it there). Launches per batch <= newton_maxiter * (17 lin_maxiter + 3) + 3 by
-// construction: per inner iteration 2 x 4 products, 5 elementwise / stencil kernels and 4 reduce kernels; per Newton iteration the
-// residual, its reduce and the step; init, finish, stats.
-int gsn_phi_batch(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const double *in_slab, bool chain, const H2DFin *fin) {
+// Phi of one batch of at most the kind's cap of items by Newton steps with an inner Krylov loop, LAUNCHES the kind's kernels (ACNBatch,
+// GSNBatch); the converged x through the sweep's arithmetic (fin) or left in the work row x (no fin: h2d_points_sumsq reads it there).
+// The host reads one word (the items still running) after every Newton reduce and after every check_every-th inner iteration.
+template <class LAUNCHES>
+int newton_phi_batch(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const double *in_slab, bool chain, const H2DFin *fin) {
     H2DHost &h = *lv.h2d;
     H2DHost::Newton &N = h.newton_state;
-    const H2DDev &H = h.dev;
+    const H2DKindRow &K = h.row();
+    static_assert(NEWTON_MAX_ROWS >= kind_row(H2DKind::ALLENCAHN_NEWTON).n_rows && NEWTON_MAX_ROWS >= kind_row(H2DKind::GRAYSCOTT_NEWTON).n_rows,
+                  "NewtonBatch::rows holds the work rows of every Newton kind");
     H2DHost::Newton::Work &w = chain ? N.chain : N.main;
     int rc;
     if (pl.count < 1) return 0;
-    if (pl.count > GSN_MAX_BATCH) return fail(MGRIT_HIP_EINVAL, "Newton batch of %d items", pl.count);
-    if ((rc = newton_reserve(e, h, w, pl.count, GSN_ROWS, 6, 5, GSN_NB))) return rc;
-    double *dinv = nullptr;
-    if ((rc = gsn_dinv(e, lv, pl.dtbits, &dinv))) return rc;
-    double dt;
-    std::memcpy(&dt, &pl.dtbits, 8);
-    const int P = H.Mi, n = H.nx * H.nx, nb = std::min(GSN_NB, (n + 255) / 256);
-    const size_t per = (size_t)P * P, slab = 2 * per * w.cap;
-    double *const x = w.rows, *const wr = x + slab, *const r = wr + slab, *const rhat = r + slab, *const p = rhat + slab, *const v = p + slab,
-                 *const s = v + slab, *const y = s + slab, *const delta = y + slab, *const W0 = delta + slab, *const W1 = W0 + slab;
-    double *const z = W0, *const t = W1;   // (between the products of z and those of the next y)
-    const size_t c = w.cap;
-    const GSNState S{w.ints, w.ints + c, w.ints + 2 * c, w.ints + 3 * c, w.ints + 4 * c, w.ints + 5 * c,
-                     w.dbls, w.dbls + c, w.dbls + 2 * c, w.dbls + 3 * c, w.dbls + 4 * c, w.dbls + 5 * c};
-    const GSNPar A{ACNPar{H.nx, P, 0, h.gs.inv_dx2, 0.0, 0.0}, h.gs.du, h.gs.dv, h.gs.a, h.gs.b, dt};
-    const GSPre none{0.0, 0.0, 0.0, 0};   // (the work modes of the products apply no map; its two operands make them two-plane)
-    const dim3 ge(nb, 1, pl.count), b256(256), one(1);
-    auto reduce = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, one, b256, 0, e->stream, S, pl.count, nb, N.newton_tol, N.lin_tol, N.lin_maxiter, N.word);
-    };
-    hipLaunchKernelGGL(gsn_init_kernel, ge, b256, 0, e->stream, A, S, in_slab, pl.d_in, H.ld, x, wr, per);
+    if (pl.count > K.max_batch) return fail(MGRIT_HIP_EINVAL, "Newton batch of %d items", pl.count);
+    if ((rc = newton_reserve(e, h, w, pl.count))) return rc;
+    NewtonBatch B{e, h, w, pl, in_slab};
+    if ((rc = newton_dinv(e, lv, pl.dtbits, &B.dinv))) return rc;
+    std::memcpy(&B.dt, &pl.dtbits, 8);
+    B.nb = std::min(K.nb, (h.dev.nx * h.dev.nx + 255) / 256);
+    B.per = (size_t)h.dev.Mi * h.dev.Mi;
+    for (int i = 0; i < K.n_rows; ++i) B.rows[i] = w.rows + i * (B.per * h.comps() * w.cap);
+    B.ge = dim3(B.nb, 1, pl.count);
+    const LAUNCHES L(B);
+    L.init();
     for (int it = 0; it < N.newton_maxiter; ++it) {
-        hipLaunchKernelGGL(gsn_residual_kernel, ge, b256, 0, e->stream, A, S, x, wr, r, rhat, per);
-        reduce(&gsn_reduce_kernel<GSN_R_NEWTON>);
+        L.residual();
         HIP_TRY(hipGetLastError());
         unsigned running = 0;
-        if ((rc = acn_running(e, N, &running, "Gray-Scott"))) return rc;
+        if ((rc = newton_running(e, h, &running))) return rc;
         if (!running) break;   // every item frozen, or none with an inner iteration to run: nothing changes any more
         for (int k = 0; k < N.lin_maxiter; ++k) {
-            hipLaunchKernelGGL(gsn_dir_kernel, ge, b256, 0, e->stream, A, S, r, v, p, per);
-            if ((rc = (p2d_products<GSPre, true>(e, h, pl.count, none, p, S.lin, dinv, W0, W1, y, nullptr)))) return rc;
-            hipLaunchKernelGGL((gsn_jy_kernel<false>), ge, b256, 0, e->stream, A, S, x, y, rhat, v, per);
-            reduce(&gsn_reduce_kernel<GSN_R_SIGMA>);
-            hipLaunchKernelGGL(gsn_s_kernel, ge, b256, 0, e->stream, A, S, r, v, s, per);
-            reduce(&gsn_reduce_kernel<GSN_R_HALF>);
-            if ((rc = (p2d_products<GSPre, true>(e, h, pl.count, none, s, S.lin, dinv, W0, W1, z, nullptr)))) return rc;
-            hipLaunchKernelGGL((gsn_jy_kernel<true>), ge, b256, 0, e->stream, A, S, x, z, s, t, per);
-            reduce(&gsn_reduce_kernel<GSN_R_OMEGA>);
-            hipLaunchKernelGGL(gsn_update_kernel, ge, b256, 0, e->stream, A, S, y, z, s, t, rhat, delta, r, per);
-            reduce(&gsn_reduce_kernel<GSN_R_FULL>);
+            if ((rc = L.inner())) return rc;
             HIP_TRY(hipGetLastError());
-            if ((k + 1) % GSN_CHECK_EVERY == 0 && k + 1 < N.lin_maxiter) {   // (after lin_maxiter iterations no item is running)
-                if ((rc = acn_running(e, N, &running, "Gray-Scott"))) return rc;
+            if ((k + 1) % K.check_every == 0 && k + 1 < N.lin_maxiter) {   // (after lin_maxiter iterations no item is running)
+                if ((rc = newton_running(e, h, &running))) return rc;
                 if (!running) break;
             }
         }
-        hipLaunchKernelGGL(gsn_step_kernel, ge, b256, 0, e->stream, A, S, x, delta, per);
+        L.step();
     }
-    if (fin) hipLaunchKernelGGL(gsn_finish_kernel, ge, b256, 0, e->stream, A, x, per, H, *fin);
-    hipLaunchKernelGGL(gsn_stats_kernel, one, b256, 0, e->stream, S, pl.count, N.tot);
+    if (fin) L.finish(*fin);
+    L.stats();
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -2980,10 +3023,10 @@ int h2d_phi_batch(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const dou
     int rc;
     const size_t per = (size_t)H.Mi * H.Mj;
     chain = chain && pl.count == 1;
-    if (h.grayscott() && 2 * pl.count > H2D_MAX_BATCH) return fail(MGRIT_HIP_EINVAL, "Gray-Scott batch of %d states", pl.count);   // (blockIdx.z, the work slabs)
-    if (h.cahnhilliard() && 2 * pl.count > H2D_MAX_BATCH) return fail(MGRIT_HIP_EINVAL, "Cahn-Hilliard batch of %d states", pl.count);
+    if (h.items() > 1 && h.items() * pl.count > H2D_MAX_BATCH)   // (blockIdx.z, the work slabs)
+        return fail(MGRIT_HIP_EINVAL, "%s batch of %d states", h.row().name, pl.count);
     if (h.newton()) {   // Newton-PCG / Newton-BiCGStab: the plan in batches of at most the kind's cap (without fin the caller passes one such batch)
-        const int cap = newton_max_batch(h);
+        const int cap = h.row().max_batch;
         for (int off = 0; off < pl.count; off += cap) {
             H2DFin part{};   // the sweep's index lists from the batch's first item on, like the plan's
             if (fin) {
@@ -2993,7 +3036,8 @@ int h2d_phi_batch(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const dou
                 if (part.b_idx) part.b_idx += off;
             }
             const BatchPlan sub = batch_slice(pl, off, std::min(cap, pl.count - off));
-            if ((rc = (h.grayscott() ? gsn_phi_batch : acn_phi_batch)(e, lv, sub, in_slab, chain, fin ? &part : nullptr))) return rc;
+            const auto batch = h.kind == H2DKind::GRAYSCOTT_NEWTON ? &newton_phi_batch<GSNBatch> : &newton_phi_batch<ACNBatch>;
+            if ((rc = batch(e, lv, sub, in_slab, chain, fin ? &part : nullptr))) return rc;
         }
         return 0;
     }
@@ -3009,9 +3053,11 @@ int h2d_phi_batch(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const dou
                           // while the first is staged; Gray-Scott once for both species, items 2 b (u) and 2 b + 1 (v) of state b
         double dt;
         std::memcpy(&dt, &pl.dtbits, 8);
-        if (h.kind == H2DKind::GRAYSCOTT_IMEX) return p2d_products(e, h, pl.count, GSPre{dt, h.gs.a, h.gs.b, 0}, in_slab, pl.d_in, dinv, W0, W1, W0, fin);
-        if (h.cahnhilliard()) return ch_products(e, h, pl.count, CHPre{1.0 + h.ch.stab, 0}, in_slab, pl.d_in, dinv, W0, W1, fin);
-        return p2d_products(e, h, pl.count, ACPre{dt * h.ac.inv_eps2, h.ac.nu}, in_slab, pl.d_in, dinv, W0, W1, W0, fin);
+        switch (h.kind) {
+        case H2DKind::GRAYSCOTT_IMEX: return p2d_products(e, h, pl.count, GSPre{dt, h.gs.a, h.gs.b, 0}, in_slab, pl.d_in, dinv, W0, W1, W0, fin);
+        case H2DKind::CAHNHILLIARD_IMEX: return ch_products(e, h, pl.count, CHPre{1.0 + h.ch.stab, 0}, in_slab, pl.d_in, dinv, W0, W1, fin);
+        default: return p2d_products(e, h, pl.count, ACPre{dt * h.ac.inv_eps2, h.ac.nu}, in_slab, pl.d_in, dinv, W0, W1, W0, fin);
+        }
     }
     // W1[j][i'] = x to spectral slots ; W0[i'][j'] = y to spectral slots, o D ; W1[j'][i] = x back ; W0[i][j] = y back = U
     const dim3 fx(H.Mj / 64, H.Mi / 64, pl.count), fy(H.Mi / 64, H.Mj / 64, pl.count);        // (n tiles, slot tiles, items)
@@ -3234,12 +3280,12 @@ int h2d_points_sumsq(mgrit_hip_engine *e, int lvl, RunList *rl, const double *pr
     for (const BatchPlan &pl : rl->points.plans) {
         if ((rc = h2d_reserve(lv, std::min(H2D_MAX_BATCH, pl.count)))) return rc;
         // residual: Phi (in W0) of the row in front against the point's row, the Allen-Cahn instance where the level is one; jump: the
-        // point's row against prev's. A Newton level leaves Phi in its work row x, a batch of at most newton_max_batch items at a time
+        // point's row against prev's. A Newton level leaves Phi in its work row x, a batch of at most its kind's max_batch items at a time
         // Gray-Scott: per (state, plane), a state's 2 nx row sums added u plane first
         const int nc = lv.h2d->comps();
         const auto rowsq = h2d_rowsq_instance(*lv.h2d, !prev);
         const bool newton = !prev && lv.h2d->newton();
-        const int part = newton ? newton_max_batch(*lv.h2d) : pl.count;
+        const int part = newton ? lv.h2d->row().max_batch : pl.count;
         for (int off = 0; off < pl.count; off += part) {
             const BatchPlan sub = batch_slice(pl, off, std::min(part, pl.count - off));
             if (!prev && (rc = h2d_phi_batch(e, lv, sub, lv.dev.u))) return rc;
@@ -3784,6 +3830,40 @@ int level_2d(mgrit_hip_engine *e, int lvl, int stepper, H2DKind kind, int n, int
     lv.set = true;
     return 0;
 }
+// The IMEX level of a periodic application. The checks in the order callers rely on: level, nx range, row stride (size: the state's
+// size as the message spells it), check() for the application's own parameters, time grid; then store(h) keeps those parameters
+template <typename Check, typename Store>
+int level_periodic2d(mgrit_hip_engine *e, int lvl, int stepper, H2DKind kind, int n_pts_local, const double *t_local, int nx, int ld,
+                     double inv_dx2, const char *size, Check check, Store store) {
+    const H2DKindRow &K = kind_row(kind);
+    int rc = check_level(e, lvl, false);
+    if (rc) return rc;
+    if (nx < 4 || nx > 2048) return fail(MGRIT_HIP_EUNSUPPORTED, "%s grid %dx%d outside [4,2048]^2", K.name, nx, nx);
+    if ((rc = check_ld_2d(ld, K.comps * nx * nx, size))) return rc;
+    if ((rc = check())) return rc;
+    if (no_time_grid(n_pts_local, t_local)) return fail(MGRIT_HIP_EINVAL, "bad arguments");
+    return level_2d(e, lvl, stepper, kind, K.comps * nx * nx, ld, n_pts_local, 0, [&](Level &lv, H2DHost *h) {
+        store(h);
+        return periodic2d_tables(e, lv, h, n_pts_local, t_local, nx, ld, inv_dx2);
+    });
+}
+// The Newton form of a level its IMEX entry point has just described: the solver's parameters, the word the host reads, the counts
+int newton_attach(mgrit_hip_engine *e, int lvl, H2DKind kind, double theta, double newton_tol, int newton_maxiter, double lin_tol,
+                  int lin_maxiter) {
+    // until the Newton state below is complete the level counts as not described: a failed allocation leaves an unusable level
+    // (whose pieces go with the engine), never one that steps as IMEX
+    e->L[lvl].set = false;
+    H2DHost::Newton &N = e->L[lvl].h2d->newton_state;
+    N.theta = theta; N.newton_tol = newton_tol; N.newton_maxiter = newton_maxiter; N.lin_tol = lin_tol; N.lin_maxiter = lin_maxiter;
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&N.word), sizeof(unsigned), hipHostMallocMapped));
+    *N.word = 0;
+    HIP_TRY(hipEventCreateWithFlags(&N.ev, hipEventDisableTiming));
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&N.tot), 4 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(N.tot, 0, 4 * sizeof(unsigned long long), e->stream));
+    e->L[lvl].h2d->kind = kind;
+    e->L[lvl].set = true;
+    return 0;
+}
 
 }  // namespace
 
@@ -4009,47 +4089,29 @@ int mgrit_hip_level_heat2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const 
 
 int mgrit_hip_level_allencahn2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld, double inv_dx2,
                                 double inv_eps2, int nu) {
-    int rc = check_level(e, lvl, false);
-    if (rc) return rc;
-    if (nx < 4 || nx > 2048) return fail(MGRIT_HIP_EUNSUPPORTED, "Allen-Cahn grid %dx%d outside [4,2048]^2", nx, nx);
-    if ((rc = check_ld_2d(ld, nx * nx, "nx*nx"))) return rc;
-    if (nu < 1 || nu > 64 || !(inv_dx2 > 0.0) || !(inv_eps2 > 0.0)) return fail(MGRIT_HIP_EINVAL, "bad Allen-Cahn parameters (nu=%d)", nu);
-    if (no_time_grid(n_pts_local, t_local)) return fail(MGRIT_HIP_EINVAL, "bad arguments");
-    return level_2d(e, lvl, MGRIT_HIP_STEPPER_ALLENCAHN2D, H2DKind::ALLENCAHN_IMEX, nx * nx, ld, n_pts_local, 0, [&](Level &lv, H2DHost *h) {
-        h->ac = {inv_dx2, inv_eps2, nu};
-        return periodic2d_tables(e, lv, h, n_pts_local, t_local, nx, ld, inv_dx2);
-    });
+    return level_periodic2d(e, lvl, MGRIT_HIP_STEPPER_ALLENCAHN2D, H2DKind::ALLENCAHN_IMEX, n_pts_local, t_local, nx, ld, inv_dx2, "nx*nx", [&] {
+        if (nu < 1 || nu > 64 || !(inv_dx2 > 0.0) || !(inv_eps2 > 0.0)) return fail(MGRIT_HIP_EINVAL, "bad Allen-Cahn parameters (nu=%d)", nu);
+        return 0;
+    }, [&](H2DHost *h) { h->ac = {inv_dx2, inv_eps2, nu}; });
 }
 
 int mgrit_hip_level_grayscott2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld, double inv_dx2,
                                 double du, double dv, double a, double b) {
-    int rc = check_level(e, lvl, false);
-    if (rc) return rc;
-    if (nx < 4 || nx > 2048) return fail(MGRIT_HIP_EUNSUPPORTED, "Gray-Scott grid %dx%d outside [4,2048]^2", nx, nx);
-    if ((rc = check_ld_2d(ld, 2 * nx * nx, "2*nx*nx"))) return rc;
-    if (!(inv_dx2 > 0.0) || !(du > 0.0) || !(dv > 0.0) || !std::isfinite(inv_dx2) || !std::isfinite(du) || !std::isfinite(dv) ||
-        !std::isfinite(a) || !std::isfinite(b))
-        return fail(MGRIT_HIP_EINVAL, "bad Gray-Scott parameters (du=%g, dv=%g must be positive, a=%g, b=%g finite)", du, dv, a, b);
-    if (no_time_grid(n_pts_local, t_local)) return fail(MGRIT_HIP_EINVAL, "bad arguments");
-    return level_2d(e, lvl, MGRIT_HIP_STEPPER_GRAYSCOTT2D, H2DKind::GRAYSCOTT_IMEX, 2 * nx * nx, ld, n_pts_local, 0, [&](Level &lv, H2DHost *h) {
-        h->gs = {du, dv, a, b, inv_dx2};
-        return periodic2d_tables(e, lv, h, n_pts_local, t_local, nx, ld, inv_dx2);
-    });
+    return level_periodic2d(e, lvl, MGRIT_HIP_STEPPER_GRAYSCOTT2D, H2DKind::GRAYSCOTT_IMEX, n_pts_local, t_local, nx, ld, inv_dx2, "2*nx*nx", [&] {
+        if (!(inv_dx2 > 0.0) || !(du > 0.0) || !(dv > 0.0) || !std::isfinite(inv_dx2) || !std::isfinite(du) || !std::isfinite(dv) ||
+            !std::isfinite(a) || !std::isfinite(b))
+            return fail(MGRIT_HIP_EINVAL, "bad Gray-Scott parameters (du=%g, dv=%g must be positive, a=%g, b=%g finite)", du, dv, a, b);
+        return 0;
+    }, [&](H2DHost *h) { h->gs = {du, dv, a, b, inv_dx2}; });
 }
 
 int mgrit_hip_level_cahnhilliard2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld, double inv_dx2,
                                    double eps2, double stab) {
-    int rc = check_level(e, lvl, false);
-    if (rc) return rc;
-    if (nx < 4 || nx > 2048) return fail(MGRIT_HIP_EUNSUPPORTED, "Cahn-Hilliard grid %dx%d outside [4,2048]^2", nx, nx);
-    if ((rc = check_ld_2d(ld, nx * nx, "nx*nx"))) return rc;
-    if (!(inv_dx2 > 0.0) || !(eps2 > 0.0) || !(stab >= 0.0) || !std::isfinite(inv_dx2) || !std::isfinite(eps2) || !std::isfinite(stab))
-        return fail(MGRIT_HIP_EINVAL, "bad Cahn-Hilliard parameters (eps2=%g must be positive, stab=%g not negative)", eps2, stab);
-    if (no_time_grid(n_pts_local, t_local)) return fail(MGRIT_HIP_EINVAL, "bad arguments");
-    return level_2d(e, lvl, MGRIT_HIP_STEPPER_CAHNHILLIARD2D, H2DKind::CAHNHILLIARD_IMEX, nx * nx, ld, n_pts_local, 0, [&](Level &lv, H2DHost *h) {
-        h->ch = {eps2, stab};
-        return periodic2d_tables(e, lv, h, n_pts_local, t_local, nx, ld, inv_dx2);
-    });
+    return level_periodic2d(e, lvl, MGRIT_HIP_STEPPER_CAHNHILLIARD2D, H2DKind::CAHNHILLIARD_IMEX, n_pts_local, t_local, nx, ld, inv_dx2, "nx*nx", [&] {
+        if (!(inv_dx2 > 0.0) || !(eps2 > 0.0) || !(stab >= 0.0) || !std::isfinite(inv_dx2) || !std::isfinite(eps2) || !std::isfinite(stab))
+            return fail(MGRIT_HIP_EINVAL, "bad Cahn-Hilliard parameters (eps2=%g must be positive, stab=%g not negative)", eps2, stab);
+        return 0;
+    }, [&](H2DHost *h) { h->ch = {eps2, stab}; });
 }
 
 int mgrit_hip_level_allencahn2d_newton(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld, double inv_dx2,
@@ -4068,19 +4130,7 @@ int mgrit_hip_level_allencahn2d_newton(mgrit_hip_engine *e, int lvl, int n_pts_l
         return fail(MGRIT_HIP_EINVAL, "Allen-Cahn Newton step: theta * dt / eps^2 = %g on the largest step %g; the step needs theta * dt / eps^2 < 1, "
                     "i.e. dt < %g", theta * dt_max * inv_eps2, dt_max, 1.0 / (theta * inv_eps2));
     if ((rc = mgrit_hip_level_allencahn2d(e, lvl, n_pts_local, t_local, nx, ld, inv_dx2, inv_eps2, nu))) return rc;
-    // until the Newton state below is complete the level counts as not described: a failed allocation leaves an unusable level
-    // (whose pieces go with the engine), never one that steps as IMEX
-    e->L[lvl].set = false;
-    H2DHost::Newton &N = e->L[lvl].h2d->newton_state;
-    N.theta = theta; N.newton_tol = newton_tol; N.newton_maxiter = newton_maxiter; N.lin_tol = lin_tol; N.lin_maxiter = lin_maxiter;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&N.word), sizeof(unsigned), hipHostMallocMapped));
-    *N.word = 0;
-    HIP_TRY(hipEventCreateWithFlags(&N.ev, hipEventDisableTiming));
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&N.tot), 4 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(N.tot, 0, 4 * sizeof(unsigned long long), e->stream));
-    e->L[lvl].h2d->kind = H2DKind::ALLENCAHN_NEWTON;
-    e->L[lvl].set = true;
-    return 0;
+    return newton_attach(e, lvl, H2DKind::ALLENCAHN_NEWTON, theta, newton_tol, newton_maxiter, lin_tol, lin_maxiter);
 }
 
 int mgrit_hip_level_grayscott2d_newton(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld, double inv_dx2,
@@ -4091,25 +4141,13 @@ int mgrit_hip_level_grayscott2d_newton(mgrit_hip_engine *e, int lvl, int n_pts_l
     if (!(newton_tol >= 0.0) || !(lin_tol >= 0.0) || newton_maxiter < 0 || lin_maxiter < 0)
         return fail(MGRIT_HIP_EINVAL, "bad Newton / BiCGStab parameters (newton_maxiter=%d, lin_maxiter=%d)", newton_maxiter, lin_maxiter);
     if ((rc = mgrit_hip_level_grayscott2d(e, lvl, n_pts_local, t_local, nx, ld, inv_dx2, du, dv, a, b))) return rc;
-    // until the Newton state below is complete the level counts as not described (as mgrit_hip_level_allencahn2d_newton)
-    e->L[lvl].set = false;
-    H2DHost *h = e->L[lvl].h2d;
-    H2DHost::Newton &N = h->newton_state;
-    N.theta = 1.0; N.newton_tol = newton_tol; N.newton_maxiter = newton_maxiter; N.lin_tol = lin_tol; N.lin_maxiter = lin_maxiter;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&N.word), sizeof(unsigned), hipHostMallocMapped));
-    *N.word = 0;
-    HIP_TRY(hipEventCreateWithFlags(&N.ev, hipEventDisableTiming));
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&N.tot), 4 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(N.tot, 0, 4 * sizeof(unsigned long long), e->stream));
-    h->kind = H2DKind::GRAYSCOTT_NEWTON;
-    e->L[lvl].set = true;
-    return 0;
+    return newton_attach(e, lvl, H2DKind::GRAYSCOTT_NEWTON, 1.0, newton_tol, newton_maxiter, lin_tol, lin_maxiter);
 }
 
 int mgrit_hip_newton_stats(mgrit_hip_engine *e, int lvl, int64_t out[4]) {
     int rc = check_level(e, lvl);
     if (rc) return rc;
-    // (the text predates the Gray-Scott Newton levels, which are accepted too; tests pin it, so "Allen-Cahn" stays in it for now)
+    // (every Newton kind is accepted; tests pin the text, so "Allen-Cahn" stays in it)
     if (!out || !e->L[lvl].h2d || !e->L[lvl].h2d->newton()) return fail(MGRIT_HIP_EINVAL, "level %d is not an Allen-Cahn Newton level", lvl);
     H2DHost::Newton &N = e->L[lvl].h2d->newton_state;
     unsigned long long host[4];
@@ -4256,9 +4294,9 @@ int mgrit_hip_level_transfer(mgrit_hip_engine *e, int lvl, int kind) {
     } else if (kind == MGRIT_HIP_TRANSFER_HEAT2D || kind == MGRIT_HIP_TRANSFER_PERIODIC2D) {
         const H2DHost *hf = e->L[lvl].h2d, *hc = e->L[lvl + 1].h2d;
         const bool per = kind == MGRIT_HIP_TRANSFER_PERIODIC2D;
-        // (periodic: two Allen-Cahn levels or two Cahn-Hilliard levels -- one plane per state both --, never one of each)
-        const bool per_ok = hf && hc && ((hf->allencahn() && hc->allencahn()) || (hf->cahnhilliard() && hc->cahnhilliard()));
-        if (!hf || !hc || (per ? !per_ok : hf->periodic() || hc->periodic()))
+        // (the same application on both levels, one that has the transfer -- the periodic kinds of one plane per state --, the periodic
+        // transfer for the periodic grid and the Heat2D transfer for Heat2D)
+        if (!hf || !hc || std::strcmp(hf->row().name, hc->row().name) != 0 || !hf->row().transfer2d || hf->periodic() != per)
             return fail(MGRIT_HIP_EUNSUPPORTED, per ? "the periodic 2-D transfer joins two Allen-Cahn levels" : "the Heat2D transfer joins two Heat2D levels");
         const int off = per ? 0 : 1;
         if (2 * hc->dev.nx - off != hf->dev.nx || 2 * hc->dev.ny - off != hf->dev.ny)

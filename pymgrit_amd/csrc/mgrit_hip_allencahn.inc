@@ -22,7 +22,7 @@ struct ACPre {
 // AllenCahn, methods 'IMPL' and 'CN' with linear_solver = 'pcg' (DESIGN.md 3.9): per item Newton's method on
 //   x - fac (L x + r(x) / eps^2) = rhs,   fac = theta dt,  r(v) = v (1 - v^nu),  rhs = u (IMPL) or u + fac (L u + r(u) / eps^2) (CN),
 // each correction J delta = g by conjugate gradients preconditioned with P = (1 + fac nu / eps^2) I - fac L through the four Hartley
-// products above (no ACPre, the shifted D table). A batch's Phi is a host-driven loop over the kernels below (acn_phi_batch in
+// products above (no ACPre, the shifted D table). A batch's Phi is a host-driven loop over the kernels below (ACNBatch under newton_phi_batch in
 // mgrit_hip.hip); blockIdx.z (or the thread of acn_reduce_kernel) is the item. Work rows are P x P slab items like the products'
 // operands, pads zero and never written. Per-item state lives in ACNState: an item whose Newton test has passed is FROZEN (act = 0) --
 // every kernel returns at once for it and its x is never written again --; cg = 1 while its inner iteration runs.

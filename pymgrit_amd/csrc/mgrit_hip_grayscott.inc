@@ -31,7 +31,7 @@ struct GSPre {
 // right-preconditioned BiCGStab with the shadow residual r^ = g, matrix-free, preconditioned with
 // P = blockdiag((1 + dt a) I - dt du L, (1 + dt b) I - dt dv L) through the four Hartley products per species (p2d_gemm_kernel in its
 // work modes with two planes, the shifted [2][P][P] table). The structure is that of acn_* (mgrit_hip_allencahn.inc): a batch's Phi is
-// a host-driven loop over the kernels below (gsn_phi_batch in mgrit_hip.hip); blockIdx.z (or the thread of gsn_reduce_kernel) is the
+// a host-driven loop over the kernels below (GSNBatch under newton_phi_batch in mgrit_hip.hip); blockIdx.z (or the thread of gsn_reduce_kernel) is the
 // item. A work row of an item is two P x P planes [u | v], pads zero and never written. Per-item state lives in GSNState: an item whose
 // Newton test has passed is FROZEN (act = 0) -- every kernel returns at once for it and its x is never written again --; lin = 1 while
 // its inner iteration runs, half = 1 between the decision that the iteration ends with delta += alpha y only and that update.

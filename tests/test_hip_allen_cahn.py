@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 import cases
+from periodic2d_sweeps import compare as _compare, host_state as _host_state, lists as _lists, row_norm as _row_norm, set_states as _set_states
 from test_allen_cahn_cpu import ARR, EPS, META, check_history, ours_bound, reference_bound, step_input
 
 pytestmark = pytest.mark.gpu
@@ -46,19 +47,6 @@ def _pair(nx, nts, t_stop, nu=2, **opts):
     return dev, host
 
 
-def _lists(mg, lvl):
-    return [(name, lst[lvl]) for name, lst in (("u", mg.u), ("v", mg.v), ("g", mg.g)) if lst[lvl] is not None]
-
-
-def _set_states(dev, host, states):
-    """states[(name, lvl)] = [n_pts][values of one state in row-major order] (nx x nx here, nx x ny for Heat2D)"""
-    for (name, lvl), val in states.items():
-        dev.backend.set_natural(name, lvl, val)
-        lst = dict(_lists(host, lvl))[name]
-        for i in range(len(lst)):
-            lst[i].set_values(val[i].reshape(np.shape(lst[i].get_values())).copy())
-
-
 def _random_states(host, seed, zero_g=False):
     rng = np.random.default_rng(seed)
     out = {}
@@ -67,10 +55,6 @@ def _random_states(host, seed, zero_g=False):
             n = host.problem[lvl].nx ** 2
             out[(name, lvl)] = np.zeros((len(lst), n)) if (zero_g and name == "g") else rng.uniform(-1.0, 1.0, size=(len(lst), n))
     return out
-
-
-def _host_state(host, name, lvl):
-    return np.array([np.asarray(v.get_values()).ravel() for v in dict(_lists(host, lvl))[name]])
 
 
 def _b_norm(app, rows, c):
@@ -83,21 +67,6 @@ def _tol(host, lvl, rows):
     app = host.problem[lvl]
     c = float(np.max(np.diff(host.t[lvl]))) / app.eps ** 2
     return 2 * (4 * app.nx + 8) * EPS * _b_norm(app, rows, c)
-
-
-def _row_norm(*arrays):
-    return max(float(np.max(np.linalg.norm(np.atleast_2d(a), axis=1))) for a in arrays)
-
-
-def _compare(dev, host, lvl, allowed, what):
-    worst = 0.0
-    for name, _ in _lists(host, lvl):
-        got, ref = dev.backend.natural(name, lvl), _host_state(host, name, lvl)
-        err = float(np.max(np.linalg.norm(got - ref, axis=1)))
-        worst = max(worst, err)
-        assert err <= allowed, (what, name, lvl, err, allowed)
-    print(f"{what} level {lvl}: worst row error {worst:.3e}, allowed {allowed:.3e}")
-    return worst
 
 
 SIZES = [9, 20, 63, 64, 66, 130, 200]
@@ -296,6 +265,6 @@ def test_what_is_not_covered_is_refused():
         Mgrit(prob(), conv_crit=2, logging_lvl=30)
     stub = types.SimpleNamespace(desc=[p.device_stepper() for p in prob()])
     with pytest.raises(MgritHipError, match="one time rank only"):
-        HipBackend._check_allencahn(stub, types.SimpleNamespace(comm_time_size=2, global_conv_crit=True))
+        HipBackend._check_periodic(stub, types.SimpleNamespace(comm_time_size=2, global_conv_crit=True), "allencahn2d")
     with pytest.raises(Exception, match="outside"):
         Mgrit([AllenCahn(nx=3, method="IMEX", t_start=0, t_stop=0.002, nt=nt) for nt in (9, 3)], logging_lvl=30)

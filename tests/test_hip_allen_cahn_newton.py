@@ -36,25 +36,17 @@ import pytest
 import cases
 import test_allen_cahn_cpu
 from allen_cahn_newton_reference import ReferenceAllenCahnNewton, reference_phi, residual
+from periodic2d_sweeps import (ALL_SWEEPS, compare as _compare, intervals as _intervals, report as _report, row_norm as _row_norm, run_sweeps,
+                               set_states as _set_states, tol, uniform as _uniform)
 from test_allen_cahn_cpu import EPS, apply_step, check_history
-from test_hip_allen_cahn import T_SWEEP, _compare, _host_state, _random_states, _row_norm, _set_states
+from test_hip_allen_cahn import T_SWEEP, _random_states
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 META = cases.load_json("allen_cahn_newton.json")
 ARR = np.load(cases.GOLDEN + "/allen_cahn_newton.npz")
-ALL_SWEEPS = ("f_relax", "c_relax", "fas_residual", "forward_solve", "error_correction", "compute_residual")
-STORED_STATE_SWEEPS = ("f_relax", "c_relax", "fas_residual", "compute_residual")
 THETA = {"IMPL": 1.0, "CN": 0.5}
-
-
-def _uniform(nts, t_stop):
-    return [dict(t_start=0, t_stop=t_stop, nt=nt) for nt in nts]
-
-
-def _intervals(ts):
-    return [dict(t_interval=np.asarray(t)) for t in ts]
 
 
 def _pair(nx, grids, method, nu=2, app=None, **opts):
@@ -89,95 +81,24 @@ def _tau(app, dt, rows):
     return (app.nx * app.newton_tol + (1 if app.method == "IMPL" else 2) * e_g) / m + EPS * x_norm
 
 
-def _tol(ref, lvl, rows):
-    return _tau(ref.problem[lvl], float(np.max(np.diff(ref.t[lvl]))), rows)
-
-
 def _lip(app, dt):
     theta = THETA[app.method]
     c = theta * dt / app.eps ** 2
     return (1.0 + (1.0 - theta) / theta * c) / (1.0 - c)
 
 
-def _chain(app, t, inputs, slack):
-    e = 0.0
-    for k in range(1, len(t)):
-        dt = float(t[k] - t[k - 1])
-        e = _lip(app, dt) * e + _tau(app, dt, inputs[k - 1]) + slack
-    return e
-
-
-def _ratio(record, what, err, allowed):
-    record[what] = max(record.get(what, 0.0), err / allowed if allowed > 0.0 else 0.0)
-
-
-def _report(test, record):
-    for what, r in record.items():
-        print(f"RATIO {test} {what}: worst error/allowed {r:.4f}")
-
-
-def _run_sweeps(dev, ref, w, seed, sweeps, levels=None, record=None):
-    """the sweeps on fresh random states in [-1, 1], each against the reference hierarchy"""
-    record = {} if record is None else record
-    top = dev.lvl_max - 1
-    levels = list(range(top)) if levels is None else levels
-    seeds = iter(range(seed, seed + 1000))
-
-    def fresh():
-        st = _random_states(ref, next(seeds))
-        _set_states(dev, ref, st)
-        return st
-
-    for lvl in levels:
-        app = ref.problem[lvl]
-        if "f_relax" in sweeps:
-            st = fresh()
-            slack = 8 * EPS * 3 * _row_norm(*st.values())
-            dev.f_relax(lvl); ref.f_relax(lvl)
-            cpts = [int(i) for i in np.asarray(ref.cpts[lvl])]
-            if (max(np.diff(cpts)) if len(cpts) > 1 else 1) <= 2:      # every Phi acts on a stored state
-                allowed = _tol(ref, lvl, st[("u", lvl)]) + slack
-            else:                                                       # F-points of one interval are chained
-                after, t, allowed = _host_state(ref, "u", lvl), ref.t[lvl], 0.0
-                for a, z in zip(cpts[:-1], cpts[1:]):
-                    allowed = max(allowed, _chain(app, t[a:z], [st[("u", lvl)][a]] + [after[i] for i in range(a + 1, z - 1)], slack))
-            _ratio(record, "f_relax", _compare(dev, ref, lvl, allowed, "f_relax"), allowed)
-        if "c_relax" in sweeps:
-            st = fresh()
-            slack = 8 * EPS * 3 * _row_norm(*st.values())
-            dev.c_relax(lvl); ref.c_relax(lvl)
-            allowed = max(1.0, w) * _tol(ref, lvl, st[("u", lvl)]) + slack * (abs(w) + abs(1 - w))
-            _ratio(record, "c_relax", _compare(dev, ref, lvl, allowed, f"c_relax w={w}"), allowed)
-        if "fas_residual" in sweeps:
-            st = fresh()
-            slack = 8 * EPS * 3 * _row_norm(*st.values())
-            dev.fas_residual(lvl); ref.fas_residual(lvl)
-            allowed = _tol(ref, lvl, st[("u", lvl)]) + _tol(ref, lvl + 1, st[("u", lvl)]) + slack
-            _ratio(record, "fas_residual", _compare(dev, ref, lvl + 1, allowed, "fas_residual"), allowed)
-    if "forward_solve" in sweeps:
-        st = fresh()
-        dev.forward_solve(top); ref.forward_solve(top)
-        uh = _host_state(ref, "u", top)
-        allowed = _chain(ref.problem[top], ref.t[top], uh, 8 * EPS * 3 * _row_norm(uh, st[("g", top)]))
-        _ratio(record, "forward_solve", _compare(dev, ref, top, allowed, "forward_solve"), allowed)
-    if "error_correction" in sweeps:
-        for lvl in reversed(levels):
-            st = fresh()
-            dev.error_correction(lvl); ref.error_correction(lvl)
-            allowed = 8 * EPS * 3 * _row_norm(*st.values())
-            _ratio(record, "error_correction", _compare(dev, ref, lvl, allowed, "error_correction"), allowed)
-    if "compute_residual" in sweeps:
-        st = fresh()
-        nx = ref.problem[0].nx
-        got, want = np.asarray(dev.compute_residual()), np.asarray(ref.compute_residual())
-        allowed = _tol(ref, 0, st[("u", 0)]) + 8 * EPS * 3 * _row_norm(st[("u", 0)]) + (nx * nx + 2) * EPS * want
-        assert got.shape == want.shape and got.size == len(ref.cpts[0]) - 1
-        print(f"residual norms: worst deviation {np.abs(got - want).max():.3e}, allowed {allowed.min():.3e}")
-        assert np.all(np.abs(got - want) <= allowed), np.abs(got - want).max()
-        _ratio(record, "compute_residual", float(np.max(np.abs(got - want) / allowed)), 1.0)
+def _no_item_at_newton_maxiter(dev):
     for lvl in range(dev.lvl_max):
         assert dev.backend.newton_stats(lvl)["at_newton_maxiter"] == 0
-    return record
+
+
+BOUNDS = types.SimpleNamespace(random_states=_random_states, phi_term=lambda ref, app, rows, dt: _tau(app, dt, rows),
+                               lip=lambda app, dt, rows: _lip(app, dt), values_per_state=lambda app: app.nx * app.nx,
+                               coarse_rows=lambda ref, st, lvl: st[("u", lvl)], weight_in_key=False, after=_no_item_at_newton_maxiter)
+
+
+def _tol(ref, lvl, rows):
+    return tol(BOUNDS, ref, lvl, rows)
 
 
 # ---- every sweep at the edge sizes of the new kernels ------------------------------------------------------------------------------
@@ -191,7 +112,7 @@ def test_every_sweep_at_the_size_edges(nx, nu, method):
         dev, ref = _pair(nx, _uniform((17, 9, 5), T_SWEEP), method, nu=nu, weight_c=w)
         d = dev.problem[0].device_stepper()
         assert d["theta"] == THETA[method] and d["nu"] == nu
-        _run_sweeps(dev, ref, w, 100 * nx + (7 if w != 1.0 else 0), ALL_SWEEPS, record=record)
+        run_sweeps(dev, ref, BOUNDS, w, 100 * nx + (7 if w != 1.0 else 0), ALL_SWEEPS, record=record)
     _report(f"size_edges[nx={nx},nu={nu},{method}]", record)
 
 
@@ -288,7 +209,7 @@ def test_every_sweep_with_several_step_sizes_per_level(grid, method):
         for t in dev.t:
             assert len(set(np.diff(np.asarray(t, dtype=np.float64)).view(np.int64).tolist())) >= 3
             assert THETA[method] * np.max(np.diff(t)) / 0.04 ** 2 < 1.0
-        _run_sweeps(dev, ref, w, 500 * nx + (3 if w != 1.0 else 0), ALL_SWEEPS, record=record)
+        run_sweeps(dev, ref, BOUNDS, w, 500 * nx + (3 if w != 1.0 else 0), ALL_SWEEPS, record=record)
     _report(f"step_sizes[{grid},{method}]", record)
 
 
@@ -309,9 +230,9 @@ def test_sweeps_of_more_than_one_batch():
         groups = sorted(collections.Counter((t[pts] - t[pts - 1]).view(np.int64).tolist()).values())
         assert len(pts) >= 1025 and groups == [1, 1025], groups
     dev.backend.newton_stats(0)
-    record = _run_sweeps(dev, ref, w, 77, ("f_relax",), levels=[0])
-    assert dev.backend.newton_stats(0)["phi"] == 0      # (_run_sweeps has read the counts: the call resets them)
-    _run_sweeps(dev, ref, w, 78, ("c_relax", "fas_residual", "compute_residual"), levels=[0], record=record)
+    record = run_sweeps(dev, ref, BOUNDS, w, 77, ("f_relax",), levels=[0])
+    assert dev.backend.newton_stats(0)["phi"] == 0      # (run_sweeps has read the counts: the call resets them)
+    run_sweeps(dev, ref, BOUNDS, w, 78, ("c_relax", "fas_residual", "compute_residual"), levels=[0], record=record)
     _report("batches[dyadic_2053_two_sizes]", record)
 
 
@@ -457,7 +378,7 @@ def test_what_is_not_covered_is_refused():
         Mgrit(prob(), conv_crit=2, logging_lvl=30)
     stub = types.SimpleNamespace(desc=[p.device_stepper() for p in prob()])
     with pytest.raises(MgritHipError, match="one time rank only"):
-        HipBackend._check_allencahn(stub, types.SimpleNamespace(comm_time_size=2, global_conv_crit=True))
+        HipBackend._check_periodic(stub, types.SimpleNamespace(comm_time_size=2, global_conv_crit=True), "allencahn2d")
     # the raw ABI: a step with theta dt / eps^2 >= 1, an odd nu, another theta
     lib = hip_lib.load()
     eng = C.c_void_p()

@@ -26,28 +26,21 @@ Tolerances: those of test_hip_allen_cahn.py with ONE device evaluation instead o
 Every comparison covers all rows of a list. Each sweep prints its worst error / allowed ("RATIO" lines).
 """
 import collections
+import types
 
 import numpy as np
 import pytest
 
 import cases
 from allen_cahn_reference import ReferenceAllenCahn
+from periodic2d_sweeps import (ALL_SWEEPS, STORED_STATE_SWEEPS, compare as _compare, distinct_steps as _distinct_steps, host_state as _host_state,
+                               intervals as _intervals, ratio as _ratio, report as _report, row_norm as _row_norm, run_sweeps,
+                               set_states as _set_states, tol, uniform as _uniform)      # (_ratio: for test_hip_heat2d_reference.py)
 from test_allen_cahn_cpu import EPS
-from test_hip_allen_cahn import T_SWEEP, _b_norm, _compare, _host_state, _random_states, _row_norm, _set_states
+from test_hip_allen_cahn import T_SWEEP, _b_norm, _random_states
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
-
-ALL_SWEEPS = ("f_relax", "c_relax", "fas_residual", "forward_solve", "error_correction", "compute_residual")
-STORED_STATE_SWEEPS = ("f_relax", "c_relax", "fas_residual", "compute_residual")
-
-
-def _uniform(nts, t_stop):
-    return [dict(t_start=0, t_stop=t_stop, nt=nt) for nt in nts]
-
-
-def _intervals(ts):
-    return [dict(t_interval=np.asarray(t)) for t in ts]
 
 
 def _pair(nx, grids, nu=2, **opts):
@@ -67,97 +60,19 @@ def _phi_term(app, rows, c):
     return ((4 * app.nx + 8) + 1) * EPS * _b_norm(app, rows, c)
 
 
-def _tol(ref, lvl, rows):
-    app = ref.problem[lvl]
-    return _phi_term(app, rows, float(np.max(np.diff(ref.t[lvl]))) / app.eps ** 2)
-
-
 def _lip(app, c, rows):
     R = float(np.abs(rows).max())
     return max(abs(1 + c), abs(1 + c * (1 - (app.nu + 1) * R ** app.nu)))
 
 
-def _chain(app, t, inputs, slack):
-    """e_k = Lip_k e_(k-1) + per-Phi term + SLACK over the steps t[k-1] -> t[k], inputs[k-1] the reference's input of step k"""
-    e = 0.0
-    for k in range(1, len(t)):
-        c = (t[k] - t[k - 1]) / app.eps ** 2
-        e = _lip(app, c, inputs[k - 1]) * e + _phi_term(app, inputs[k - 1], c) + slack
-    return e
+# the formulas above take c = dt / eps^2
+BOUNDS = types.SimpleNamespace(random_states=_random_states, phi_term=lambda ref, app, rows, dt: _phi_term(app, rows, dt / app.eps ** 2),
+                               lip=lambda app, dt, rows: _lip(app, dt / app.eps ** 2, rows), values_per_state=lambda app: app.nx * app.nx,
+                               coarse_rows=lambda ref, st, lvl: st[("u", lvl)], weight_in_key=False)
 
 
-def _ratio(record, what, err, allowed):
-    r = err / allowed if allowed > 0.0 else 0.0
-    record[what] = max(record.get(what, 0.0), r)
-
-
-def _run_sweeps(dev, ref, w, seed, sweeps, levels=None, record=None):
-    """the sweeps of test_every_sweep_matches_the_plugin_path on fresh random states in [-1, 1], each against the reference hierarchy"""
-    record = {} if record is None else record
-    top = dev.lvl_max - 1
-    levels = list(range(top)) if levels is None else levels
-    seeds = iter(range(seed, seed + 1000))
-
-    def fresh():
-        st = _random_states(ref, next(seeds))
-        _set_states(dev, ref, st)
-        return st
-
-    for lvl in levels:
-        app = ref.problem[lvl]
-        if "f_relax" in sweeps:
-            st = fresh()
-            slack = 8 * EPS * 3 * _row_norm(*st.values())
-            dev.f_relax(lvl); ref.f_relax(lvl)
-            cpts = [int(i) for i in np.asarray(ref.cpts[lvl])]
-            m = max(np.diff(cpts)) if len(cpts) > 1 else 1
-            if m <= 2:      # every Phi acts on a stored state
-                allowed = _tol(ref, lvl, st[("u", lvl)]) + slack
-            else:           # F-points of one interval are chained
-                after, t, allowed = _host_state(ref, "u", lvl), ref.t[lvl], 0.0
-                for a, z in zip(cpts[:-1], cpts[1:]):
-                    allowed = max(allowed, _chain(app, t[a:z], [st[("u", lvl)][a]] + [after[i] for i in range(a + 1, z - 1)], slack))
-            _ratio(record, "f_relax", _compare(dev, ref, lvl, allowed, "f_relax"), allowed)
-        if "c_relax" in sweeps:
-            st = fresh()
-            slack = 8 * EPS * 3 * _row_norm(*st.values())
-            dev.c_relax(lvl); ref.c_relax(lvl)
-            allowed = max(1.0, w) * _tol(ref, lvl, st[("u", lvl)]) + slack * (abs(w) + abs(1 - w))
-            _ratio(record, "c_relax", _compare(dev, ref, lvl, allowed, f"c_relax w={w}"), allowed)
-        if "fas_residual" in sweeps:
-            st = fresh()
-            slack = 8 * EPS * 3 * _row_norm(*st.values())
-            dev.fas_residual(lvl); ref.fas_residual(lvl)
-            # g of the coarse level: one Phi of the fine level, one of the coarse level on restricted (= copied) rows of the fine u
-            allowed = _tol(ref, lvl, st[("u", lvl)]) + _tol(ref, lvl + 1, st[("u", lvl)]) + slack
-            _ratio(record, "fas_residual", _compare(dev, ref, lvl + 1, allowed, "fas_residual"), allowed)
-    if "forward_solve" in sweeps:
-        st = fresh()
-        dev.forward_solve(top); ref.forward_solve(top)
-        uh = _host_state(ref, "u", top)
-        allowed = _chain(ref.problem[top], ref.t[top], uh, 8 * EPS * 3 * _row_norm(uh, st[("g", top)]))
-        _ratio(record, "forward_solve", _compare(dev, ref, top, allowed, "forward_solve"), allowed)
-    if "error_correction" in sweeps:
-        for lvl in reversed(levels):
-            st = fresh()
-            dev.error_correction(lvl); ref.error_correction(lvl)
-            allowed = 8 * EPS * 3 * _row_norm(*st.values())
-            _ratio(record, "error_correction", _compare(dev, ref, lvl, allowed, "error_correction"), allowed)
-    if "compute_residual" in sweeps:
-        st = fresh()
-        nx = ref.problem[0].nx
-        got, want = np.asarray(dev.compute_residual()), np.asarray(ref.compute_residual())
-        allowed = _tol(ref, 0, st[("u", 0)]) + 8 * EPS * 3 * _row_norm(st[("u", 0)]) + (nx * nx + 2) * EPS * want
-        assert got.shape == want.shape and got.size == len(ref.cpts[0]) - 1
-        print(f"residual norms: worst deviation {np.abs(got - want).max():.3e}, allowed {allowed.min():.3e}")
-        assert np.all(np.abs(got - want) <= allowed), np.abs(got - want).max()
-        _ratio(record, "compute_residual", float(np.max(np.abs(got - want) / allowed)), 1.0)
-    return record
-
-
-def _report(test, record):
-    for what, r in record.items():
-        print(f"RATIO {test} {what}: worst error/allowed {r:.4f}")
+def _tol(ref, lvl, rows):
+    return tol(BOUNDS, ref, lvl, rows)
 
 
 # ---- a. every sweep at the size edges of the tile product --------------------------------------------------------------------------
@@ -167,7 +82,7 @@ def test_every_sweep_at_the_size_edges(nx):
     record = {}
     for w in (1.0, 1.3):
         dev, ref = _pair(nx, _uniform((17, 9, 5), T_SWEEP), weight_c=w)
-        _run_sweeps(dev, ref, w, 100 * nx + (7 if w != 1.0 else 0), ALL_SWEEPS, record=record)
+        run_sweeps(dev, ref, BOUNDS, w, 100 * nx + (7 if w != 1.0 else 0), ALL_SWEEPS, record=record)
     _report(f"size_edges[nx={nx}]", record)
 
 
@@ -180,17 +95,13 @@ def test_every_sweep_for_other_exponents(nx, nu):
     for w in (1.0, 1.3):
         dev, ref = _pair(nx, _uniform((17, 9, 5), T_SWEEP), nu=nu, weight_c=w)
         assert dev.problem[0].device_stepper()["nu"] == nu
-        _run_sweeps(dev, ref, w, 1000 * nx + 10 * nu + (5 if w != 1.0 else 0), ALL_SWEEPS if nu % 2 == 0 else STORED_STATE_SWEEPS, record=record)
+        run_sweeps(dev, ref, BOUNDS, w, 1000 * nx + 10 * nu + (5 if w != 1.0 else 0), ALL_SWEEPS if nu % 2 == 0 else STORED_STATE_SWEEPS, record=record)
     _report(f"exponents[nx={nx},nu={nu}]", record)
 
 
 # ---- c. several step sizes per level -----------------------------------------------------------------------------------------------
 RAGGED = np.concatenate(([0.0], np.cumsum(1e-4 * np.array([1, 1, 1.5, .5, 2, 1, 1, .75, 1, 1, 1, 1.25, 3, 1, 1, 1]))))
 RAGGED_GRIDS = {"by2_3lvl": [RAGGED, RAGGED[::2], RAGGED[::4]], "by4_2lvl": [RAGGED, RAGGED[::4]]}
-
-
-def _distinct_steps(t):
-    return len(set(np.diff(np.asarray(t, dtype=np.float64)).view(np.int64).tolist()))
 
 
 @pytest.mark.parametrize("nu", [2, 4])
@@ -205,7 +116,7 @@ def test_every_sweep_with_several_step_sizes_per_level(grid, nx, nu):
             assert _distinct_steps(t) >= 3 and len(set(np.round(np.diff(t) / 1e-4, 6))) >= 3, np.diff(t)
         if grid == "by4_2lvl":      # the three F-points of one interval do not share one D table (steps 1, 1, 1.5 and 2, 1, 1 of 1e-4)
             assert sum(len(set(np.round(np.diff(dev.t[0][a:a + 4]) / 1e-4, 6))) >= 2 for a in range(0, 16, 4)) >= 2
-        _run_sweeps(dev, ref, w, 500 * nx + 10 * nu + (3 if w != 1.0 else 0), ALL_SWEEPS, record=record)
+        run_sweeps(dev, ref, BOUNDS, w, 500 * nx + 10 * nu + (3 if w != 1.0 else 0), ALL_SWEEPS, record=record)
     _report(f"step_sizes[{grid},nx={nx},nu={nu}]", record)
 
 
@@ -261,7 +172,7 @@ def test_sweeps_of_more_than_one_batch(grid):
         assert len(pts) >= 1025
         if grid in BATCH_GROUPS:
             assert groups == BATCH_GROUPS[grid], groups
-    record = _run_sweeps(dev, ref, w, 77, STORED_STATE_SWEEPS, levels=[0])
+    record = run_sweeps(dev, ref, BOUNDS, w, 77, STORED_STATE_SWEEPS, levels=[0])
     _report(f"batches[{grid}]", record)
 
 

@@ -28,14 +28,15 @@ import numpy as np
 import pytest
 
 import cases
+from periodic2d_sweeps import (ALL_SWEEPS, STORED_STATE_SWEEPS, compare as _compare, distinct_steps as _distinct_steps, host_state as _host_state,
+                               intervals as _intervals, lists as _lists, report as _report, row_norm as _row_norm, run_sweeps,
+                               set_states as _set_states, tol, uniform as _uniform)
 from test_cahn_hilliard_cpu import EPS, b_norm, c_of, d2max
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 T_SWEEP = 0.002     # sweeps: nt = 17 / 9 / 5 on [0, T_SWEEP], coarsening factor 2 -- every Phi of a relaxation acts on a stored state
-ALL_SWEEPS = ("f_relax", "c_relax", "fas_residual", "forward_solve", "error_correction", "compute_residual")
-STORED_STATE_SWEEPS = ("f_relax", "c_relax", "fas_residual", "compute_residual")
 RAGGED = np.concatenate(([0.0], np.cumsum(1e-4 * np.array([1, 1, 1.5, .5, 2, 1, 1, .75, 1, 1, 1, 1.25, 3, 1, 1, 1]))))   # the grid of
 RAGGED_GRIDS = {"by2_3lvl": [RAGGED, RAGGED[::2], RAGGED[::4]], "by4_2lvl": [RAGGED, RAGGED[::4]]}                       # the Allen-Cahn reference test
 H = 2.0 ** -17      # every t_k = k H and every difference is exact: one bit pattern of dt
@@ -57,14 +58,6 @@ def _reference_class():
 
 # the other side of a comparison: its class, and the per-Phi allowance in units of EPS bnorm beyond the device's own C(nx)
 SIDES = {"host": (_host_class, lambda nx: c_of(nx)), "reference": (_reference_class, lambda nx: 1)}
-
-
-def _uniform(nts, t_stop):
-    return [dict(t_start=0, t_stop=t_stop, nt=nt) for nt in nts]
-
-
-def _intervals(ts):
-    return [dict(t_interval=np.asarray(t)) for t in ts]
 
 
 def _app_args(nx, **over):
@@ -91,31 +84,10 @@ def _pair(side, nxs, grids, transfer=None, app=None, **opts):
     return dev, other
 
 
-def _lists(mg, lvl):
-    return [(name, lst[lvl]) for name, lst in (("u", mg.u), ("v", mg.v), ("g", mg.g)) if lst[lvl] is not None]
-
-
-def _set_states(dev, host, states):
-    """states[(name, lvl)] = [n_pts][nx * nx values of one state in row-major order]"""
-    for (name, lvl), val in states.items():
-        dev.backend.set_natural(name, lvl, val)
-        lst = dict(_lists(host, lvl))[name]
-        for i in range(len(lst)):
-            lst[i].set_values(val[i].reshape(np.shape(lst[i].get_values())).copy())
-
-
 def _random_states(host, seed):
     rng = np.random.default_rng(seed)
     return {(name, lvl): rng.uniform(-1.0, 1.0, size=(len(lst), host.problem[lvl].nx ** 2))
             for lvl in range(host.lvl_max) for name, lst in _lists(host, lvl)}
-
-
-def _host_state(host, name, lvl):
-    return np.array([np.asarray(v.get_values()).ravel() for v in dict(_lists(host, lvl))[name]])
-
-
-def _row_norm(*arrays):
-    return max(float(np.max(np.linalg.norm(np.atleast_2d(a), axis=1))) for a in arrays)
 
 
 def _phi_term(host, app, rows, dt):
@@ -123,107 +95,19 @@ def _phi_term(host, app, rows, dt):
     return (c_of(app.nx) + SIDES[host.side][1](app.nx)) * EPS * b_norm(app, rows, dt)
 
 
-def _tol(host, lvl, rows):
-    return _phi_term(host, host.problem[lvl], rows, float(np.max(np.diff(host.t[lvl]))))
-
-
 def _lip(app, dt, rows):
     R = float(np.abs(rows).max())
     return 1.0 + d2max(app, dt) * max(1.0 + app.stab, abs(3.0 * R * R - (1.0 + app.stab)))
 
 
-def _chain(host, app, t, inputs, slack):
-    """e_k = Lip_k e_(k-1) + per-Phi term + SLACK over the steps t[k-1] -> t[k], inputs[k-1] the other side's input of step k"""
-    e = 0.0
-    for k in range(1, len(t)):
-        dt = float(t[k] - t[k - 1])
-        e = _lip(app, dt, inputs[k - 1]) * e + _phi_term(host, app, inputs[k - 1], dt) + slack
-    return e
+# fas_residual: the coarse level's Phi acts on the restricted rows of the fine u (full weighting has non-negative weights that sum to 1:
+# values stay in [-1, 1], a row norm does not grow beyond the fine row's)
+BOUNDS = types.SimpleNamespace(random_states=_random_states, phi_term=_phi_term, lip=_lip, values_per_state=lambda app: app.nx * app.nx,
+                               coarse_rows=lambda host, st, lvl: _host_state(host, "v", lvl + 1), weight_in_key=False)
 
 
-def _compare(dev, host, lvl, allowed, what):
-    worst = 0.0
-    for name, _ in _lists(host, lvl):
-        got, ref = dev.backend.natural(name, lvl), _host_state(host, name, lvl)
-        err = float(np.max(np.linalg.norm(got - ref, axis=1)))
-        worst = max(worst, err)
-        assert err <= allowed, (what, name, lvl, err, allowed)
-    print(f"{what} level {lvl}: worst row error {worst:.3e}, allowed {allowed:.3e}")
-    return worst
-
-
-def _ratio(record, what, err, allowed):
-    record[what] = max(record.get(what, 0.0), err / allowed if allowed > 0.0 else 0.0)
-
-
-def _report(test, record):
-    for what, r in record.items():
-        print(f"RATIO {test} {what}: worst error/allowed {r:.4f}")
-
-
-def _run_sweeps(dev, host, w, seed, sweeps, levels=None, record=None):
-    """the sweeps on fresh random states in [-1, 1], each against the plugin hierarchy. Transfers: copy, or any the two sides share"""
-    record = {} if record is None else record
-    top = dev.lvl_max - 1
-    levels = list(range(top)) if levels is None else levels
-    seeds = iter(range(seed, seed + 1000))
-
-    def fresh():
-        st = _random_states(host, next(seeds))
-        _set_states(dev, host, st)
-        return st
-
-    for lvl in levels:
-        app = host.problem[lvl]
-        if "f_relax" in sweeps:
-            st = fresh()
-            slack = 8 * EPS * 3 * _row_norm(*st.values())
-            dev.f_relax(lvl); host.f_relax(lvl)
-            cpts = [int(i) for i in np.asarray(host.cpts[lvl])]
-            if (max(np.diff(cpts)) if len(cpts) > 1 else 1) <= 2:      # every Phi acts on a stored state
-                allowed = _tol(host, lvl, st[("u", lvl)]) + slack
-            else:                                                      # F-points of one interval are chained
-                after, t, allowed = _host_state(host, "u", lvl), host.t[lvl], 0.0
-                for a, z in zip(cpts[:-1], cpts[1:]):
-                    allowed = max(allowed, _chain(host, app, t[a:z], [st[("u", lvl)][a]] + [after[i] for i in range(a + 1, z - 1)], slack))
-            _ratio(record, "f_relax", _compare(dev, host, lvl, allowed, "f_relax"), allowed)
-        if "c_relax" in sweeps:
-            st = fresh()
-            slack = 8 * EPS * 3 * _row_norm(*st.values())
-            dev.c_relax(lvl); host.c_relax(lvl)
-            allowed = max(1.0, w) * _tol(host, lvl, st[("u", lvl)]) + slack * (abs(w) + abs(1 - w))
-            _ratio(record, "c_relax", _compare(dev, host, lvl, allowed, f"c_relax w={w}"), allowed)
-        if "fas_residual" in sweeps:
-            st = fresh()
-            slack = 8 * EPS * 3 * _row_norm(*st.values())
-            dev.fas_residual(lvl); host.fas_residual(lvl)
-            # g of the coarse level: one Phi of the fine level, one of the coarse level on the restricted rows of the fine u (full
-            # weighting has non-negative weights that sum to 1: values stay in [-1, 1], a row norm does not grow beyond the fine row's)
-            restricted = _host_state(host, "v", lvl + 1)
-            allowed = _tol(host, lvl, st[("u", lvl)]) + _tol(host, lvl + 1, restricted) + slack
-            _ratio(record, "fas_residual", _compare(dev, host, lvl + 1, allowed, "fas_residual"), allowed)
-    if "forward_solve" in sweeps:
-        st = fresh()
-        dev.forward_solve(top); host.forward_solve(top)
-        uh = _host_state(host, "u", top)
-        allowed = _chain(host, host.problem[top], host.t[top], uh, 8 * EPS * 3 * _row_norm(uh, st[("g", top)]))
-        _ratio(record, "forward_solve", _compare(dev, host, top, allowed, "forward_solve"), allowed)
-    if "error_correction" in sweeps:
-        for lvl in reversed(levels):
-            st = fresh()
-            dev.error_correction(lvl); host.error_correction(lvl)
-            allowed = 8 * EPS * 3 * _row_norm(*st.values())
-            _ratio(record, "error_correction", _compare(dev, host, lvl, allowed, "error_correction"), allowed)
-    if "compute_residual" in sweeps:
-        st = fresh()
-        nx = host.problem[0].nx
-        got, want = np.asarray(dev.compute_residual()), np.asarray(host.compute_residual())
-        allowed = _tol(host, 0, st[("u", 0)]) + 8 * EPS * 3 * _row_norm(st[("u", 0)]) + (nx * nx + 2) * EPS * want
-        assert got.shape == want.shape and got.size == len(host.cpts[0]) - 1
-        print(f"residual norms: worst deviation {np.abs(got - want).max():.3e}, allowed {allowed.min():.3e}")
-        assert np.all(np.abs(got - want) <= allowed), np.abs(got - want).max()
-        _ratio(record, "compute_residual", float(np.max(np.abs(got - want) / allowed)), 1.0)
-    return record
+def _tol(host, lvl, rows):
+    return tol(BOUNDS, host, lvl, rows)
 
 
 # ---- the cases, shared with test_hip_cahn_hilliard_reference.py ---------------------------------------------------------------------
@@ -231,14 +115,10 @@ def check_size_edges(side, nx):
     """every sweep with weight_c = 1; C-relaxation, the one sweep the weight enters, with 1.3 as well"""
     record = {}
     dev, host = _pair(side, nx, _uniform((17, 9, 5), T_SWEEP), weight_c=1.0)
-    _run_sweeps(dev, host, 1.0, 100 * nx, ALL_SWEEPS, record=record)
+    run_sweeps(dev, host, BOUNDS, 1.0, 100 * nx, ALL_SWEEPS, record=record)
     dev, host = _pair(side, nx, _uniform((17, 9, 5), T_SWEEP), weight_c=1.3)
-    _run_sweeps(dev, host, 1.3, 100 * nx + 50, ("c_relax",), record=record)
+    run_sweeps(dev, host, BOUNDS, 1.3, 100 * nx + 50, ("c_relax",), record=record)
     _report(f"size_edges[{side},nx={nx}]", record)
-
-
-def _distinct_steps(t):
-    return len(set(np.diff(np.asarray(t, dtype=np.float64)).view(np.int64).tolist()))
 
 
 def check_several_step_sizes(side, grid, nx):
@@ -249,7 +129,7 @@ def check_several_step_sizes(side, grid, nx):
             assert _distinct_steps(t) >= 3 and len(set(np.round(np.diff(t) / 1e-4, 6))) >= 3, np.diff(t)
         if grid == "by4_2lvl":      # the three F-points of one interval do not share one pair of D tables
             assert sum(len(set(np.round(np.diff(dev.t[0][a:a + 4]) / 1e-4, 6))) >= 2 for a in range(0, 16, 4)) >= 2
-        _run_sweeps(dev, host, w, 500 * nx + (3 if w != 1.0 else 0), ALL_SWEEPS if w == 1.0 else ("c_relax",), record=record)
+        run_sweeps(dev, host, BOUNDS, w, 500 * nx + (3 if w != 1.0 else 0), ALL_SWEEPS if w == 1.0 else ("c_relax",), record=record)
     _report(f"step_sizes[{side},{grid},nx={nx}]", record)
 
 
@@ -264,7 +144,7 @@ def check_split_at_the_batch_cap(side):
     for pts in (np.arange(1, len(t), 2), np.arange(2, len(t), 2)):      # F-points, relaxed C-points
         groups = sorted(collections.Counter((t[pts] - t[pts - 1]).view(np.int64).tolist()).values())
         assert groups == [1025] and 1025 > 2 * 512, groups
-    record = _run_sweeps(dev, host, w, 77, STORED_STATE_SWEEPS, levels=[0])
+    record = run_sweeps(dev, host, BOUNDS, w, 77, STORED_STATE_SWEEPS, levels=[0])
     _report(f"batches[{side},dyadic_2051]", record)
 
 
@@ -388,7 +268,7 @@ def test_spatially_coarsened_hierarchy():
     for w in (1.0, 1.3):
         dev, host = _pair("host", (16, 8), _uniform((17, 9), T_SWEEP), transfer=[GridTransferCahnHilliard()], weight_c=w)
         assert dev.backend._device_transfer(0) and dev.problem[1].dx == 2 * dev.problem[0].dx
-        _run_sweeps(dev, host, w, 900 + (3 if w != 1.0 else 0), ALL_SWEEPS, record=record)
+        run_sweeps(dev, host, BOUNDS, w, 900 + (3 if w != 1.0 else 0), ALL_SWEEPS, record=record)
     _report("coarsened[16->8]", record)
     dev, host = _pair("host", (16, 8), _uniform((17, 9), 0.01), transfer=[GridTransferCahnHilliard()], app=dict(eps=0.05), max_iter=3, tol=0.0)
     check_history(dev, host, "solve[16->8]", 3)
@@ -444,7 +324,7 @@ def test_what_is_not_covered_is_refused():
         Mgrit(prob(), conv_crit=2, logging_lvl=30)
     stub = types.SimpleNamespace(desc=[p.device_stepper() for p in prob()])
     with pytest.raises(MgritHipError, match="Cahn-Hilliard levels on the HIP engine: one time rank only"):
-        HipBackend._check_cahnhilliard(stub, types.SimpleNamespace(comm_time_size=2, global_conv_crit=True))
+        HipBackend._check_periodic(stub, types.SimpleNamespace(comm_time_size=2, global_conv_crit=True), "cahnhilliard2d")
     with pytest.raises(Exception, match="nx=3"):
         CahnHilliard(nx=3, t_start=0, t_stop=0.002, nt=9)
     # a hierarchy that mixes Cahn-Hilliard and Allen-Cahn levels: by name, in either order

@@ -40,22 +40,14 @@ import pytest
 
 import cases
 from gray_scott_reference import ReferenceGrayScott
-from test_hip_allen_cahn import _compare, _host_state, _lists, _row_norm, _set_states
+from periodic2d_sweeps import (ALL_SWEEPS, STORED_STATE_SWEEPS, compare as _compare, distinct_steps as _distinct_steps, host_state as _host_state,
+                               intervals as _intervals, lists as _lists, report as _report, row_norm as _row_norm, run_sweeps,
+                               set_states as _set_states, tol, uniform as _uniform)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 EPS = cases.EPS
-ALL_SWEEPS = ("f_relax", "c_relax", "fas_residual", "forward_solve", "error_correction", "compute_residual")
-STORED_STATE_SWEEPS = ("f_relax", "c_relax", "fas_residual", "compute_residual")
-
-
-def _uniform(nts, t_stop):
-    return [dict(t_start=0, t_stop=t_stop, nt=nt) for nt in nts]
-
-
-def _intervals(ts):
-    return [dict(t_interval=np.asarray(t)) for t in ts]
 
 
 def _t_sweep(nx):
@@ -97,94 +89,17 @@ def _phi_term(app, rows, dt):
     return ((4 * app.nx + 8) + 1) * EPS * float(np.hypot(bu, bv))
 
 
-def _tol(ref, lvl, rows):
-    return _phi_term(ref.problem[lvl], rows, float(np.max(np.diff(ref.t[lvl]))))
-
-
 def _lip(app, dt, rows):
     R2 = float(np.abs(rows).max()) ** 2
     return float(np.linalg.norm([[1 + dt * (abs(app.a) + R2), 2 * dt * R2], [dt * R2, 1 + dt * (2 * R2 + abs(app.b))]]))
 
 
-def _chain(app, t, inputs, slack):
-    """e_k = Lip_k e_(k-1) + per-Phi term + SLACK over the steps t[k-1] -> t[k], inputs[k-1] the reference's input of step k"""
-    e = 0.0
-    for k in range(1, len(t)):
-        dt = t[k] - t[k - 1]
-        e = _lip(app, dt, inputs[k - 1]) * e + _phi_term(app, inputs[k - 1], dt) + slack
-    return e
+BOUNDS = types.SimpleNamespace(random_states=_random_states, phi_term=lambda ref, app, rows, dt: _phi_term(app, rows, dt), lip=_lip,
+                               values_per_state=lambda app: 2 * app.nx ** 2, coarse_rows=lambda ref, st, lvl: st[("u", lvl)], weight_in_key=True)
 
 
-def _ratio(record, what, err, allowed):
-    record[what] = max(record.get(what, 0.0), err / allowed if allowed > 0.0 else 0.0)
-
-
-def _run_sweeps(dev, ref, w, seed, sweeps, levels=None, record=None):
-    """the named sweeps on fresh random states, each against the reference hierarchy"""
-    record = {} if record is None else record
-    top = dev.lvl_max - 1
-    levels = list(range(top)) if levels is None else levels
-    seeds = iter(range(seed, seed + 1000))
-
-    def fresh():
-        st = _random_states(ref, next(seeds))
-        _set_states(dev, ref, st)
-        return st
-
-    for lvl in levels:
-        app = ref.problem[lvl]
-        if "f_relax" in sweeps:
-            st = fresh()
-            slack = 8 * EPS * 3 * _row_norm(*st.values())
-            dev.f_relax(lvl); ref.f_relax(lvl)
-            cpts = [int(i) for i in np.asarray(ref.cpts[lvl])]
-            if len(cpts) < 2 or max(np.diff(cpts)) <= 2:      # every Phi acts on a stored state
-                allowed = _tol(ref, lvl, st[("u", lvl)]) + slack
-            else:                                             # F-points of one interval are chained
-                after, t, allowed = _host_state(ref, "u", lvl), ref.t[lvl], 0.0
-                for a, z in zip(cpts[:-1], cpts[1:]):
-                    allowed = max(allowed, _chain(app, t[a:z], [st[("u", lvl)][a]] + [after[i] for i in range(a + 1, z - 1)], slack))
-            _ratio(record, "f_relax", _compare(dev, ref, lvl, allowed, "f_relax"), allowed)
-        if "c_relax" in sweeps:
-            st = fresh()
-            slack = 8 * EPS * 3 * _row_norm(*st.values())
-            dev.c_relax(lvl); ref.c_relax(lvl)
-            allowed = max(1.0, w) * _tol(ref, lvl, st[("u", lvl)]) + slack * (abs(w) + abs(1 - w))
-            _ratio(record, f"c_relax w={w}", _compare(dev, ref, lvl, allowed, f"c_relax w={w}"), allowed)
-        if "fas_residual" in sweeps:
-            st = fresh()
-            slack = 8 * EPS * 3 * _row_norm(*st.values())
-            dev.fas_residual(lvl); ref.fas_residual(lvl)
-            # g of the coarse level: one Phi of the fine level, one of the coarse level on restricted (= copied) rows of the fine u
-            allowed = _tol(ref, lvl, st[("u", lvl)]) + _tol(ref, lvl + 1, st[("u", lvl)]) + slack
-            _ratio(record, "fas_residual", _compare(dev, ref, lvl + 1, allowed, "fas_residual"), allowed)
-    if "forward_solve" in sweeps:
-        st = fresh()
-        dev.forward_solve(top); ref.forward_solve(top)
-        uh = _host_state(ref, "u", top)
-        allowed = _chain(ref.problem[top], ref.t[top], uh, 8 * EPS * 3 * _row_norm(uh, st[("g", top)]))
-        _ratio(record, "forward_solve", _compare(dev, ref, top, allowed, "forward_solve"), allowed)
-    if "error_correction" in sweeps:
-        for lvl in reversed(levels):
-            st = fresh()
-            dev.error_correction(lvl); ref.error_correction(lvl)
-            allowed = 8 * EPS * 3 * _row_norm(*st.values())
-            _ratio(record, "error_correction", _compare(dev, ref, lvl, allowed, "error_correction"), allowed)
-    if "compute_residual" in sweeps:
-        st = fresh()
-        n = ref.problem[0].nx ** 2
-        got, want = np.asarray(dev.compute_residual()), np.asarray(ref.compute_residual())
-        # the norm of one point: its values' errors, and (2 nx^2 + 2) EPS relative for the sum of 2 nx^2 squares and the root
-        allowed = _tol(ref, 0, st[("u", 0)]) + 8 * EPS * 3 * _row_norm(st[("u", 0)]) + (2 * n + 2) * EPS * want
-        assert got.shape == want.shape and got.size == len(ref.cpts[0]) - 1
-        assert np.all(np.abs(got - want) <= allowed), np.abs(got - want).max()
-        _ratio(record, "compute_residual", float(np.max(np.abs(got - want) / allowed)), 1.0)
-    return record
-
-
-def _report(test, record):
-    for what, r in record.items():
-        print(f"RATIO {test} {what}: worst error/allowed {r:.4f}")
+def _tol(ref, lvl, rows):
+    return tol(BOUNDS, ref, lvl, rows)
 
 
 # ---- a. every sweep at the size edges of the tile product --------------------------------------------------------------------------
@@ -195,7 +110,7 @@ def test_every_sweep_at_the_size_edges(nx):
     for w, sweeps in ((1.0, ALL_SWEEPS), (1.3, ("c_relax",))):      # (the weight enters the C-relaxation only)
         dev, ref = _pair(nx, _uniform((17, 9, 5), _t_sweep(nx)), weight_c=w)
         assert dev.problem[0].du == 100 * dev.problem[0].dv
-        _run_sweeps(dev, ref, w, 100 * nx + (7 if w != 1.0 else 0), sweeps, record=record)
+        run_sweeps(dev, ref, BOUNDS, w, 100 * nx + (7 if w != 1.0 else 0), sweeps, record=record)
     _report(f"size_edges[nx={nx}]", record)
 
 
@@ -205,7 +120,7 @@ def test_every_sweep_with_equal_diffusion_coefficients():
     nx, record = 33, {}
     for w, sweeps in ((1.0, ALL_SWEEPS), (1.3, ("c_relax",))):
         dev, ref = _pair(nx, _uniform((17, 9, 5), _t_sweep(nx)), par=dict(du=0.5, dv=0.5, a=0.04, b=0.1), weight_c=w)
-        _run_sweeps(dev, ref, w, 4242 + (7 if w != 1.0 else 0), sweeps, record=record)
+        run_sweeps(dev, ref, BOUNDS, w, 4242 + (7 if w != 1.0 else 0), sweeps, record=record)
     _report("equal_diffusion[nx=33]", record)
 
 
@@ -216,10 +131,6 @@ RAGGED = np.concatenate(([0.0], np.cumsum(np.array([1, 1, 1.5, .5, 2, 1, 1, .75,
 def _ragged(nx, grid):
     t = RAGGED * 0.5 * (2.0 / nx) ** 2      # unit step: r = dt du / dx^2 = 0.5; at most 6.25 units per coarse step
     return {"by2_3lvl": [t, t[::2], t[::4]], "by4_2lvl": [t, t[::4]]}[grid]
-
-
-def _distinct_steps(t):
-    return len(set(np.diff(np.asarray(t, dtype=np.float64)).view(np.int64).tolist()))
 
 
 @pytest.mark.parametrize("nx", [20, 66])
@@ -233,7 +144,7 @@ def test_every_sweep_with_several_step_sizes_per_level(grid, nx):
             assert _distinct_steps(t) >= 3, np.diff(t)
         if grid == "by4_2lvl":      # the three F-points of one interval do not share one pair of D tables
             assert sum(_distinct_steps(dev.t[0][a:a + 4]) >= 2 for a in range(0, 16, 4)) >= 2
-        _run_sweeps(dev, ref, w, 500 * nx + (3 if w != 1.0 else 0), sweeps, record=record)
+        run_sweeps(dev, ref, BOUNDS, w, 500 * nx + (3 if w != 1.0 else 0), sweeps, record=record)
     _report(f"step_sizes[{grid},nx={nx}]", record)
 
 
@@ -250,7 +161,7 @@ def test_sweeps_of_more_than_one_batch():
     for pts in (np.arange(1, len(t), 2), np.arange(2, len(t), 2)):      # F-points, relaxed C-points
         groups = sorted(collections.Counter((t[pts] - t[pts - 1]).view(np.int64).tolist()).values())
         assert groups == [513] and 513 > 1024 // 2, groups
-    record = _run_sweeps(dev, ref, w, 77, STORED_STATE_SWEEPS, levels=[0])
+    record = run_sweeps(dev, ref, BOUNDS, w, 77, STORED_STATE_SWEEPS, levels=[0])
     _report("batches[dyadic_1027]", record)
 
 
@@ -346,7 +257,7 @@ def test_what_is_not_covered_is_refused():
         Mgrit(prob(), conv_crit=2, logging_lvl=30)
     stub = types.SimpleNamespace(desc=[p.device_stepper() for p in prob()])
     with pytest.raises(MgritHipError, match="one time rank only"):
-        HipBackend._check_grayscott(stub, types.SimpleNamespace(comm_time_size=2, global_conv_crit=True, transfer_objects=[GridTransferCopy()]))
+        HipBackend._check_periodic(stub, types.SimpleNamespace(comm_time_size=2, global_conv_crit=True, transfer_objects=[GridTransferCopy()]), "grayscott2d")
     with pytest.raises(MgritHipError, match="outside"):
         Mgrit([GrayScott(nx=3, method="IMEX", t_start=0, t_stop=0.5, nt=nt) for nt in (9, 3)], logging_lvl=30)
     # the host steppers have no device form: such a hierarchy runs on the plugin path

@@ -38,26 +38,21 @@ import pytest
 
 import cases
 from gray_scott_newton_reference import LD, ReferenceGrayScottNewton, mu, residual
+from periodic2d_sweeps import (ALL_SWEEPS, STORED_STATE_SWEEPS, compare as _compare, host_state as _host_state, intervals as _intervals,
+                               lists as _lists, ratio as _ratio, report as _report, row_norm as _row_norm, set_states as _set_states)
 from test_gray_scott_newton_cpu import (C_G_DEVICE, PARS, e_g, exit_criterion, history_allowance, margin, norm2, par_of, tau,
                                         tau_phi_a_priori)
-from test_hip_allen_cahn import _compare, _host_state, _lists, _row_norm, _set_states
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 EPS = cases.EPS
-ALL_SWEEPS = ("f_relax", "c_relax", "fas_residual", "forward_solve", "error_correction", "compute_residual")
-STORED_STATE_SWEEPS = ("f_relax", "c_relax", "fas_residual", "compute_residual")
 GSN_MAX_BATCH = 2 * 1024 // (2 * 11)      # csrc/mgrit_hip.hip: 11 two-plane work rows within 2 x H2D_MAX_BATCH work slab items
 
 
 def _uniform(nts, t_stop=1.0):
     """coarsest step 0.25 for nts = (17, 9, 5)"""
     return [dict(t_start=0, t_stop=t_stop, nt=nt) for nt in nts]
-
-
-def _intervals(ts):
-    return [dict(t_interval=np.asarray(t)) for t in ts]
 
 
 def _pair(nx, grids, par=None, app=None, **opts):
@@ -142,15 +137,6 @@ def _check_chains(dev, ref, lvl, st, chains, slack, record, what, w=1.0):
             _ratio(record, what + " max|F(x_dev)|", r_g, 1.0)
             worst_allowed = max(worst_allowed, e)
     _compare(dev, ref, lvl, worst_allowed, what)      # (all rows of all lists, the untouched ones included)
-
-
-def _ratio(record, what, err, allowed):
-    record[what] = max(record.get(what, 0.0), err / allowed if allowed > 0.0 else 0.0)
-
-
-def _report(test, record):
-    for what, r in record.items():
-        print(f"RATIO {test} {what}: worst error/allowed {r:.4f}")
 
 
 def _run_sweeps(dev, ref, w, seed, sweeps, levels=None, record=None):
