@@ -36,7 +36,7 @@ typedef struct mgrit_hip_engine mgrit_hip_engine;
 enum { MGRIT_HIP_OK = 0, MGRIT_HIP_EINVAL = -1, MGRIT_HIP_EHIP = -2, MGRIT_HIP_ENODEV = -3, MGRIT_HIP_EUNSUPPORTED = -4 };
 enum { MGRIT_HIP_STEPPER_HEAT1D = 1, MGRIT_HIP_STEPPER_ADVECTION1D = 2, MGRIT_HIP_STEPPER_HEAT2D = 3,
        MGRIT_HIP_STEPPER_HEAT1D_2PTS = 4, MGRIT_HIP_STEPPER_ALLENCAHN2D = 5, MGRIT_HIP_STEPPER_GRAYSCOTT2D = 6,
-       MGRIT_HIP_STEPPER_CAHNHILLIARD2D = 7 };
+       MGRIT_HIP_STEPPER_CAHNHILLIARD2D = 7, MGRIT_HIP_STEPPER_BURGERS2D = 8 };
 enum { MGRIT_HIP_TRANSFER_COPY = 0, MGRIT_HIP_TRANSFER_HEAT1D = 1, MGRIT_HIP_TRANSFER_PERIODIC1D = 2,
        /* the caller applies restriction / interpolation itself (a user's GridTransfer, reference core/grid_transfer.py:31-55:
           any Python code): mgrit_hip_restrict_u / _fas_rhs / _error_correction / _interpolate refuse the level pair, the FAS
@@ -131,6 +131,16 @@ int mgrit_hip_level_grayscott2d(mgrit_hip_engine *e, int lvl, int n_pts_local, c
  * or MGRIT_HIP_TRANSFER_PERIODIC2D between two such levels; no time-parallel forward solve. */
 int mgrit_hip_level_cahnhilliard2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld,
                                    double inv_dx2, double eps2, double stab);
+/* Burgers2D with method = 'IMEX' (burgers/burgers.py; reference firedrake/burgers_firedrake.py:78-133 restated on a grid; DESIGN.md
+ * 3.13) on the periodic nx x nx grid, 4 <= nx <= 2048: a state row holds TWO planes [u | v] like a Gray-Scott row, n = 2 nx^2,
+ * ld >= 2 nx^2 a multiple of 16. Per plane c: b_c = c - dt (u ax_c + v ay_c) with the central differences
+ * ax_c = (c[i+1][j] - c[i-1][j]) inv_2dx, ay_c = (c[i][j+1] - c[i][j-1]) inv_2dx (indices mod nx, inv_2dx = 1 / (2 dx)), then
+ * (I - dt nu L) x_c = b_c through the Hartley tables of mgrit_hip_level_allencahn2d with one D table for both planes. The right-hand
+ * side reads a point's neighbours, so it is a launch of its own in front of the four two-plane products (five launches per Phi).
+ * nu, inv_dx2, inv_2dx positive and finite (MGRIT_HIP_EINVAL "bad Burgers parameters" otherwise). Everything said of a Gray-Scott IMEX
+ * level holds: the Heat2D entry points, the copy transfer only, no time-parallel forward solve, norms over all 2 nx^2 values. */
+int mgrit_hip_level_burgers2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld,
+                              double inv_dx2, double inv_2dx, double nu);
 /* AllenCahn with method = 'IMPL' (theta = 1) or 'CN' (theta = 0.5) and linear_solver = 'pcg' (DESIGN.md 3.9): the level of
  * mgrit_hip_level_allencahn2d, whose Phi is Newton's method on x - fac (L x + r(x) / eps^2) = rhs, fac = theta dt, with every
  * correction by conjugate gradients preconditioned with (1 + fac nu / eps^2) I - fac L through the Hartley products. Per item: at most

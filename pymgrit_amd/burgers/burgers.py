@@ -1,0 +1,151 @@
+"""2-D viscous Burgers equation with periodic boundary conditions: state vector and application.
+
+    u_t + u u_x + v u_y = nu Lap u
+    v_t + u v_x + v v_y = nu Lap v          on [0, L)^2 x (t_start, t_end],  periodic,
+
+the vector-valued non-linear PDE the reference ships (reference src/pymgrit/firedrake/burgers_firedrake.py:78-133, there P2 finite
+elements on a Firedrake mesh with a fully implicit step, nu = 1e-2). This module restates the problem in numpy on the ``nx x nx`` grid
+``x_i = i dx``, ``dx = L / nx``, axis 0 = x, axis 1 = y, as gray_scott.py restates the PETSc example. What has no counterpart here: the
+arguments ``mesh`` and ``comm_space`` (the grid is on one process) and the finite-element space. One time integrator:
+
+``method='IMEX'``
+    the transport explicit with central differences, the diffusion implicit. Per plane c = u, v (indices mod nx)::
+
+        ax_c[i][j] = (c[i+1][j] - c[i-1][j]) * inv_2dx,     ay_c[i][j] = (c[i][j+1] - c[i][j-1]) * inv_2dx,     inv_2dx = 1 / (2 dx)
+        b_c = c - dt (u ax_c + v ay_c)
+        (I - dt nu Lh) x_c = b_c
+
+    Lh the periodic 5-point Laplacian / dx^2. The solve is the eigen-decomposition of Lh in the discrete Hartley basis ``T``
+    (allen_cahn.hartley_matrix), exact up to rounding: ``x_c = T ((T b_c T) o D) T``, ``D[i][j] = 1 / (1 + (dt nu) (lam_i + lam_j))``, one
+    table for both planes. ``device_stepper()`` describes the step (kind ``"burgers2d"``) and the engine applies it as a stencil pass
+    that forms both right-hand sides from one staged tile of the state, followed by the four two-plane Hartley products on the FP64
+    matrix cores (csrc/mgrit_hip_burgers.inc). ``step`` is the same formula in numpy, in the operand order the kernel
+    shares (``_rhs_imex``, ``_dinv``): the plugin path and the specification of the device step.
+
+Unlike the right-hand sides of Allen-Cahn, Gray-Scott and Cahn-Hilliard, b_c is not a map of the values at one grid point: it reads the
+point's four neighbours in its own plane.
+"""
+import numpy as np
+
+from pymgrit_amd.allen_cahn.allen_cahn import hartley_matrix, periodic_laplacian_eigenvalues
+from pymgrit_amd.core.application import Application
+from pymgrit_amd.core.vector import Vector
+
+
+class VectorBurgers2D(Vector):
+    """The two velocity components of one time point: ``values[0]`` is u, ``values[1]`` is v, each an nx x nx grid; the norm is the
+    2-norm over all 2 nx^2 values. A device state row is ``[u plane | v plane]``, which is ``values.ravel()``."""
+
+    def __init__(self, nx):
+        super().__init__()
+        self.nx = nx
+        self.values = np.zeros((2, nx, nx))
+
+    def _like(self, values):
+        out = VectorBurgers2D(self.nx)
+        out.set_values(values)
+        return out
+
+    def __add__(self, other):
+        return self._like(self.get_values() + other.get_values())
+
+    def __sub__(self, other):
+        return self._like(self.get_values() - other.get_values())
+
+    def __mul__(self, other):
+        return self._like(self.get_values() * other)
+
+    def norm(self):
+        return np.linalg.norm(self.values)
+
+    def clone(self):
+        return self._like(self.get_values().copy())
+
+    def clone_zero(self):
+        return VectorBurgers2D(self.nx)
+
+    def clone_rand(self):
+        return self._like(np.random.rand(2, self.nx, self.nx))
+
+    def set_values(self, values):
+        self.values = values
+
+    def get_values(self):
+        return self.values
+
+    def pack(self):
+        return self.values
+
+    def unpack(self, values):
+        self.values = values
+
+
+class Burgers2D(Application):
+    """Viscous Burgers in 2-D space with periodic boundary conditions, IMEX step (module docstring)"""
+
+    def __init__(self, nx=32, nu=1e-2, L=1.0, method='IMEX', *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        if method != 'IMEX':
+            raise Exception(f"Unknown method {method!r}. Burgers2D offers IMEX (transport explicit, diffusion implicit)")
+        try:
+            finite = all(np.isfinite(float(v)) for v in (nu, L))
+        except (TypeError, ValueError):
+            finite = False
+        if not finite or not nu > 0 or not L > 0:
+            raise Exception(f"Burgers2D: nu and L must be positive and finite (nu={nu}, L={L})")
+        if int(nx) != nx or nx < 4:
+            raise Exception(f"Burgers2D: nx={nx!r} must be an integer >= 4")
+        self.nx = int(nx)
+        self.nu, self.L = float(nu), float(L)
+        self.method = method
+        self.dx = self.L / self.nx
+        self.inv_2dx = 1.0 / (2.0 * self.dx)
+        self.x = self.dx * np.arange(self.nx)
+        self._hartley = None
+        self._lam = None
+        self.vector_template = VectorBurgers2D(self.nx)
+        self.vector_t_start = self.initial_guess()
+
+    def _rhs_imex(self, u, v, dt):
+        """(b_u, b_v). The operand order is fixed and is the device kernel's (bg_rhs_kernel, csrc/mgrit_hip_burgers.inc), which fuses
+        two multiply-adds numpy rounds separately: per plane c,  ax = (c[i+1][j] - c[i-1][j]) * inv_2dx;
+        ay = (c[i][j+1] - c[i][j-1]) * inv_2dx;  adv = fma(v, ay, u * ax);  b_c = fma(-dt, adv, c)"""
+        out = []
+        for c in (u, v):
+            ax = (np.roll(c, -1, 0) - np.roll(c, 1, 0)) * self.inv_2dx
+            ay = (np.roll(c, -1, 1) - np.roll(c, 1, 1)) * self.inv_2dx
+            out.append(-dt * (v * ay + u * ax) + c)
+        return out
+
+    def _dinv(self, dt):
+        """D = 1 / (1 + (dt nu) (lam_i + lam_j)), the engine's table for one bit pattern of dt (h2d_dinv; the operand order of
+        GrayScott._dinv)"""
+        return 1.0 / (1.0 + (dt * self.nu) * (self._lam[:, None] + self._lam[None, :]))
+
+    def _step_imex(self, w, dt):
+        if self._hartley is None:
+            self._hartley = hartley_matrix(self.nx)
+            self._lam = periodic_laplacian_eigenvalues(self.nx, self.dx)
+        T, D = self._hartley, self._dinv(dt)
+        out = np.empty((2, self.nx, self.nx))
+        for c, b in enumerate(self._rhs_imex(w[0], w[1], dt)):
+            out[c] = T @ (((T @ b) @ T) * D) @ T
+        return out
+
+    def step(self, u_start: VectorBurgers2D, t_start: float, t_stop: float) -> VectorBurgers2D:
+        w = np.asarray(u_start.get_values(), dtype=np.float64)
+        ret = VectorBurgers2D(self.nx)
+        ret.set_values(self._step_imex(w, t_stop - t_start))
+        return ret
+
+    def device_stepper(self):
+        """description of Phi for the HIP engine (mgrit_hip_level_burgers2d)"""
+        return {"kind": "burgers2d", "n": 2 * self.nx ** 2, "nx": self.nx, "inv_dx2": 1.0 / self.dx ** 2, "inv_2dx": self.inv_2dx,
+                "nu": self.nu}
+
+    def initial_guess(self):
+        """u = sin(2 pi x / L), v = 0.5 sin(2 pi (x + y) / L): both planes and both derivatives are non-trivial from the first step"""
+        initial = VectorBurgers2D(self.nx)
+        x, y = self.x[:, None], self.x[None, :]
+        initial.set_values(np.stack((np.sin(2 * np.pi * x / self.L) + 0.0 * y, 0.5 * np.sin(2 * np.pi * (x + y) / self.L))))
+        return initial

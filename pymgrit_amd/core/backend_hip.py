@@ -117,6 +117,7 @@ PERIODIC_2D = {
     "allencahn2d": ("Allen-Cahn", "an AllenCahn application with method='IMEX', or 'IMPL' / 'CN' with linear_solver='pcg'", False),
     "grayscott2d": ("Gray-Scott", "a GrayScott application with method='IMEX', or 'IMPL' with linear_solver='bicgstab', on the same nx", True),
     "cahnhilliard2d": ("Cahn-Hilliard", "a CahnHilliard application (method='IMEX')", False),
+    "burgers2d": ("Burgers", "a Burgers2D application (method='IMEX') on the same nx", True),
 }
 GRID_2D = ("heat2d",) + tuple(PERIODIC_2D)   # states are whole 2-D grids in natural row-major order (Gray-Scott: two of them,
                                              # [u plane | v plane]); the engine's Heat2D route
@@ -297,13 +298,17 @@ class HipBackend:
         """the stabilised IMEX step, one plane per state (through hip_lib like the Gray-Scott forms above)"""
         hip_lib.level_cahnhilliard2d(self.h, engine_lvl, t_local.size, _ptr(t_local), ld, d)
 
+    def _describe_burgers2d(self, engine_lvl, d, t_local, n, ld):
+        """the IMEX step, two planes per state, a stencil pass in front of the products"""
+        hip_lib.level_burgers2d(self.h, engine_lvl, t_local.size, _ptr(t_local), ld, d)
+
     def newton_stats(self, lvl):
         """counts of a Newton level (Allen-Cahn PCG, Gray-Scott BiCGStab) since the last call (which resets them)"""
         return hip_lib.newton_stats(self.h, lvl)
 
     _DESCRIBE = {"heat1d": _describe_heat1d, "heat1d_2pts": _describe_heat1d_2pts, "advection1d": _describe_advection1d,
                  "heat2d": _describe_heat2d, "allencahn2d": _describe_allencahn2d, "grayscott2d": _describe_grayscott2d,
-                 "cahnhilliard2d": _describe_cahnhilliard2d}
+                 "cahnhilliard2d": _describe_cahnhilliard2d, "burgers2d": _describe_burgers2d}
 
     def _describe(self, engine_lvl, lvl, t_local):
         """tell the engine what level engine_lvl is: the stepper of level lvl on the time points t_local"""

@@ -16,6 +16,7 @@ STEPPER_HEAT1D, STEPPER_ADVECTION1D = 1, 2
 STEPPER_ALLENCAHN2D = 5
 STEPPER_GRAYSCOTT2D = 6
 STEPPER_CAHNHILLIARD2D = 7
+STEPPER_BURGERS2D = 8
 TRANSFER_COPY, TRANSFER_HEAT1D, TRANSFER_CALLER = 0, 1, 3
 TRANSFER_HEAT2D, TRANSFER_PERIODIC2D = 4, 5
 MAX_N = 16384
@@ -56,6 +57,8 @@ EXPORTS = {
                                                      C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, C.c_int]),
     "mgrit_hip_level_cahnhilliard2d": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double,
                                                  C.c_double]),
+    "mgrit_hip_level_burgers2d": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double,
+                                            C.c_double]),
     "mgrit_hip_newton_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "mgrit_hip_level_bind": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgrit_hip_chain_enable": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -190,6 +193,12 @@ def level_grayscott2d_newton(h, engine_lvl, n_pts, t_ptr, ld, d):
     check(load().mgrit_hip_level_grayscott2d_newton(h, engine_lvl, n_pts, t_ptr, int(d["nx"]), ld, float(d["inv_dx2"]), float(d["du"]),
                                                     float(d["dv"]), float(d["a"]), float(d["b"]), float(d["newton_tol"]),
                                                     int(d["newton_maxiter"]), float(d["lin_tol"]), int(d["lin_maxiter"])))
+
+
+def level_burgers2d(h, engine_lvl, n_pts, t_ptr, ld, d):
+    """describe a Burgers IMEX level; d: the application's description"""
+    check(load().mgrit_hip_level_burgers2d(h, engine_lvl, n_pts, t_ptr, int(d["nx"]), ld, float(d["inv_dx2"]), float(d["inv_2dx"]),
+                                           float(d["nu"])))
 
 
 def level_cahnhilliard2d(h, engine_lvl, n_pts, t_ptr, ld, d):
