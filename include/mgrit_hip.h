@@ -367,6 +367,18 @@ int mgrit_hip_ec_relax_res(mgrit_hip_engine *e, int lvl, int intervals_id, int s
 #define MGRIT_HIP_DEFERRED_BAD (-2)
 int mgrit_hip_deferred(mgrit_hip_engine *e, int lvl);
 int mgrit_hip_set_defer(mgrit_hip_engine *e, int on);
+/* The two forms of mgrit_hip_cf_fas. With pre_relaxed = 1 and ONE separable forcing term the pass keeps the level's forcing space
+ * factor in LDS and q = Phi_{l+1}(C'_j) in registers (cfasq_kernel) instead of streaming the factor from L2 in every Phi with q
+ * parked in LDS (cfas_kernel). Both store the same rows with the same bits, so only the query tells which one ran.
+ *   mgrit_hip_set_cfas_form: 0 = cfas_kernel always, 1 (default; MGRIT_HIP_CFAS_FORM=0 in the environment of mgrit_hip_create
+ *                            makes it 0) = the new form where it applies. Anything else, or a null engine: MGRIT_HIP_EINVAL.
+ *   mgrit_hip_cfas_form:     the form of the level's last mgrit_hip_cf_fas launch: 0 cfas_kernel, 1 cfasq_kernel, 2 cfasq_kernel
+ *                            with the coarse level's factor read from LDS as well (the two levels' factors as described are
+ *                            equal byte for byte; compared once per engine), -1 none yet;
+ *                            MGRIT_HIP_CFAS_FORM_BAD for a null engine or a level out of range. Touches nothing. */
+#define MGRIT_HIP_CFAS_FORM_BAD (-2)
+int mgrit_hip_set_cfas_form(mgrit_hip_engine *e, int form);
+int mgrit_hip_cfas_form(mgrit_hip_engine *e, int lvl);
 /* the same pass with the per-point sums of squares written to sumsq_out[res_pos] (device-accessible memory of the caller, e.g.
  * pinned host memory) instead of the engine's buffer: a rank of a sharded run fills the values of its complete intervals this
  * way and the first local C-point's through mgrit_hip_residual */

@@ -104,6 +104,8 @@ EXPORTS = {
     "mgrit_hip_ec_relax_res": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "mgrit_hip_deferred": (C.c_int, [C.c_void_p, C.c_int]),
     "mgrit_hip_set_defer": (C.c_int, [C.c_void_p, C.c_int]),
+    "mgrit_hip_set_cfas_form": (C.c_int, [C.c_void_p, C.c_int]),
+    "mgrit_hip_cfas_form": (C.c_int, [C.c_void_p, C.c_int]),
     "mgrit_hip_ec_relax_res_to": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mgrit_hip_gen_down": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "mgrit_hip_gen_down_part": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),

@@ -1074,7 +1074,9 @@ __global__ void __launch_bounds__(TB) fas_fused_kernel(LevelDev L, LevelDev Lc, 
 // correction table, Pt and the forcing factors of Lc are read straight from global memory -- 144 KB per level that every
 // workgroup reads, so they stay in L2 and cost no HBM traffic -- and its scalar coefficients live only for this call (the
 // caller reloads its own set afterwards: both at once do not fit the SGPR file). Arithmetic identical to phi_apply on Lc.
-template <int FORCE, bool LDSBAR = false, bool ONE = false>
+// SLDS: Lc's (one) forcing space factor is the vector the caller has staged in sm.tab (stage_forcing<4> of its own level, and the
+// host has found the two levels' factors equal byte for byte): the same operand from LDS, and this Phi issues no vector load for it
+template <int FORCE, bool LDSBAR = false, bool ONE = false, bool SLDS = false>
 __device__ __forceinline__ void phi_other_level(double (&w)[E], StepCtx &ctx, const LevelDev &Lc, int j, const Smem &sm, unsigned sl,
                                                 int t, int lane, int wave, int G) {
     const int cj = Lc.one_cset ? 0 : ld_uniform(Lc.cidx + j);
@@ -1085,7 +1087,15 @@ __device__ __forceinline__ void phi_other_level(double (&w)[E], StepCtx &ctx, co
     smc.wf = Lc.one_cset ? sm.wf2 : const_cast<double *>(gc->pg);
     smc.lp = Lc.one_cset ? sm.lp2 : const_cast<double *>(gc->lp);
     smc.pt = const_cast<double2 *>(Lc.ptP) + (size_t)cj * 1024;
-    if (FORCE != 0) {
+    if (SLDS) {
+        const double ck = ld_uniform(Lc.tc + j);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const double2 sv = sm.tab[sl + q * 64];
+            w[2 * q] = fma(sv.x, ck, w[2 * q]);
+            w[2 * q + 1] = fma(sv.y, ck, w[2 * q + 1]);
+        }
+    } else if (FORCE != 0) {
         for (int kk = 0; kk < Lc.K; ++kk) {
             const double ck = ld_uniform(Lc.tc + (size_t)kk * Lc.n_pts + j);
 #pragma unroll
@@ -1222,6 +1232,94 @@ __global__ void __launch_bounds__(TB) cfas_kernel(LevelDev L, LevelDev Lc, Inter
                 x[2 * q + 1] = x[2 * q + 1] - w.y;
             }
             store_row_nt(Lc.g + (size_t)jc * Lc.ld, sl, x, Lc.stream_rows);
+#pragma unroll
+            for (int e = 0; e < E; ++e) x[e] = b[e];
+            /*STAMP 5*/
+        }
+    }
+    wq.end(t);
+    /*STAMP 7*/
+}
+
+// cfas_kernel<2> with CFAS_PRE for ONE separable forcing term, q in registers (round 11). LDS then holds the level's forcing space
+// factor as in ecfr_kernel (stage_forcing<4>) instead of q, and none of the interval's four own-level Phi streams those 128 KB per
+// workgroup from L2. What makes room for q beside x is the order: b, the closing C-point, is wanted only behind the last Phi
+// (with CFAS_PRE row ce-1 holds it as it is), so per interval
+//   q = Phi_{l+1}(x);  x = Phi_l^m(x), ONE call site;  b = row ce-1;  g^{l+1} = ((x - b) + b) - q;  the stores;  x = b
+// and two vectors are live beside every Phi, as in cfas_kernel. Values, operation order and the rows stored are cfas_kernel's, bit
+// for bit (add_forcing<4> and <2> with K = 1 are the same fma on the same operands). The register allocator needs the help
+// ffas_kernel's needs, and more of it -- spilled VGPRs of the 1024-thread instance in a reduced copy of this file as the pieces went
+// in: 117 (two call sites of the fine Phi), 77 (one), 48 (thread index opaque per item), 14 (q pinned behind the coarse Phi and behind
+// the loop), 5 (index opaque again in front of the loop), 6 with the `touch` read. In this file: 8 with the read and 5-6 without it,
+// cfas_kernel<2, 1024> has 10; none at 512 and 64 threads. The read stays: 6.03-6.07 against 6.10-6.14 ms per cycle without it.
+// Measured: with the own-level factor in LDS alone the pass is no faster than cfas_kernel; with CLDS
+// as well -- no Phi of the interval issues a forcing load -- 1.57 -> 1.34 ms per launch at 16384 x 65537.
+// CLDS: the coarse level's forcing factor is the same vector (mgrit_hip_cf_fas has compared the two), so the coarse Phi reads the LDS
+// copy as well and the interval issues no forcing load at all.
+template <int TB = 1024, bool CLDS = false>
+__global__ void __launch_bounds__(TB) cfasq_kernel(LevelDev L, LevelDev Lc, IntervalsDev I, int flags) {
+    constexpr int KIND = MGRIT_HIP_STEPPER_HEAT1D, FORCE = 4;
+    WG_PROLOGUE_TB(TB);
+    (void)lane;
+    const int held = flags & CFAS_HELD;   // (wave-uniform launch argument; CFAS_PRE is what the host picks this kernel for)
+    constexpr bool ONE = TB == LANES;   // one wave per state: Phi without the cross-group exchange (heat_solve)
+    stage_forcing<FORCE>(sm, L, sl);
+    stage_other_level(sm, Lc, t);
+    for (wq.begin(L.sched, L.xcc0_limit, wgq_slot, t); wq.cur < I.n_chunks; wq.advance(t)) {
+        const int k = wq.cur;
+        wq.prefetch(t);
+        const int i0 = I.chunk_first[k], cnt = I.chunk_len[k];
+        double x[E];
+        {   // C'_j of the chunk's first C-point: what the row in front of it holds (pre-relaxed), or the first point of the grid
+            const int cs = I.cstart[i0];
+            load_row_nt(L.u + (size_t)(I.chunk_start_coarse[k] >= 0 ? cs - 1 : cs) * L.ld, sl, x, L.stream_rows);
+        }
+        /*STAMP 6*/
+        for (int it = i0; it < i0 + cnt; ++it) {
+            const int cs = I.cstart[it], ce = I.cend[it], jc = I.cend_coarse[it];
+            /*DRAIN*/ /*STAMP 8*/
+            int ti = t;   // the thread index of this item, opaque to the compiler (ffas_kernel)
+            asm volatile("" : "+v"(ti));
+            double q[E];
+            {   // q = Phi_{l+1}(v_j), v_j = C'_j
+#pragma unroll
+                for (int e = 0; e < E; ++e) q[e] = x[e];
+                phi_other_level<FORCE, false, ONE, CLDS>(q, ctx, Lc, jc, sm, slot0(ti), ti, ti & 63, wave, G);
+            }
+            // q is final here and is read again only behind the loop: pinned at both ends, so that the compiler neither carries parts of
+            // the coarse Phi's finishing pass into the loop nor keeps q anywhere but in its sixteen register pairs
+#pragma unroll
+            for (int e = 0; e < E; ++e) asm volatile("" : "+v"(q[e]));
+            /*STAMP 0*/
+            load_coef(ctx.c, L.cs + (ctx.cur >= 0 ? ctx.cur : 0));   // back to this level's set (ctx.cur < 0: any set, phi_apply loads the right one)
+            /*STAMP 9*/
+            asm volatile("" : "+v"(ti));   // (again: what the coarse Phi derived from the index is dead here)
+            const int li = ti & 63;
+            const unsigned si = slot0(ti);
+            int touch = 0;
+            for (int i = cs + 1; i <= ce; ++i) {   // the F-steps and the residual Phi
+                // b is wanted right behind the last Phi and not before it: ffas_kernel's one-word read of every line of the row
+                /*STAMP 1*/
+                if (i == ce) touch = reinterpret_cast<const int *>(L.u + (size_t)(ce - 1) * L.ld)[(wave << 11) + (li << 5)];
+                phi_apply<KIND, FORCE, true, 0, false, ONE>(x, ctx, L, i, sm, ti, li, wave, G);
+            }
+            asm volatile("" : : "v"(touch));   // (keeps the load above)
+#pragma unroll
+            for (int e = 0; e < E; ++e) asm volatile("" : "+v"(q[e]));
+            /*STAMP 4*/
+            double b[E];
+            load_row_nt(L.u + (size_t)(ce - 1) * L.ld, si, b, L.stream_rows);
+#pragma unroll
+            for (int e = 0; e < E; ++e) x[e] = x[e] - b[e];
+#pragma unroll
+            for (int e = 0; e < E; ++e) x[e] = x[e] + b[e];
+#pragma unroll
+            for (int e = 0; e < E; ++e) x[e] = x[e] - q[e];
+            store_row_nt(Lc.g + (size_t)jc * Lc.ld, si, x, Lc.stream_rows);
+            if (!held) store_row_nt(L.u + (size_t)ce * L.ld, si, b, L.stream_rows);
+            const int keep = __builtin_amdgcn_readfirstlane(I.keep[it]);
+            if (keep & 1) store_row_nt(Lc.u + (size_t)jc * Lc.ld, si, b, Lc.stream_rows);
+            if (keep & 2) store_row_nt(Lc.v + (size_t)jc * Lc.ld, si, b, Lc.stream_rows);
 #pragma unroll
             for (int e = 0; e < E; ++e) x[e] = b[e];
             /*STAMP 5*/
@@ -1849,6 +1947,8 @@ struct mgrit_hip_engine {
     std::vector<hipEvent_t> ev_pool;         // events of drained records, reused
     hipEvent_t last0 = nullptr, last1 = nullptr;   // events of the most recent timed call (mgrit_hip_last_kernel_ms)
     bool defer = true;            // mgrit_hip_set_defer / MGRIT_HIP_DEFER: rows whose bits sit in a sibling row are not stored (Level::held)
+    int cfas_form = 1;            // mgrit_hip_set_cfas_form / MGRIT_HIP_CFAS_FORM: 0 always cfas_kernel, 1 cfasq_kernel where it applies
+    int cfas_last = -1;           // mgrit_hip_cfas_form: the form level 0's last mgrit_hip_cf_fas launched (-1: none yet)
     int fas_chunk = 0;            // mgrit_hip_set_fas_chunk: -1 fas_fused1_kernel, 0 chunks by the library's rule, n > 0 chunks of n
     int reserve = 0;              // mgrit_hip_set_reserve: CUs of XCD 0 the sweeps leave to the chain workers (0: program order)
     int *sched = nullptr;         // device counter block (1 KB, allocated with the first chain / planned launch): [0..2] {next, xcc0,
@@ -2220,6 +2320,11 @@ auto cfas_fn(int fm, int T) {
     return pick<0, 2>(streamed_force(fm), [&](auto F) {
         return pick<LANES, 512, 1024>(instance_tb(T, true), [&](auto TB) { return &cfas_kernel<F, TB>; });
     });
+}
+
+// the same pass for one term and pre-relaxed C-points: forcing factor in LDS, q in registers (mgrit_hip_set_cfas_form)
+auto cfasq_fn(int T, bool coarse_lds) {
+    return pick<LANES, 512, 1024>(instance_tb(T, true), [&](auto TB) { return coarse_lds ? &cfasq_kernel<TB, true> : &cfasq_kernel<TB, false>; });
 }
 
 auto ffas_fn(int fm, int T) {
@@ -3400,6 +3505,17 @@ int force_mode(const Level &lv) {
     return lv.dev.K == 0 ? 0 : lv.dev.K == 1 ? 1 : 2;
 }
 
+// The next coarser level carries the same ONE forcing space factor: the arrays as uploaded (row storage order, padding included)
+// are equal byte for byte -- memcmp, not ==: a -0.0 against a 0.0 is another operand of the fma --, so a kernel that has the fine
+// level's factor in LDS may read it for the coarse Phi as well. 131 KB compared once per pair: a level is described once in an
+// engine's life (level_fresh), so the answer kept in Level::same_factor_below never goes stale.
+bool same_factor_below(Level &lf, const Level &lc) {
+    if (lf.same_factor_below < 0)
+        lf.same_factor_below = force_mode(lf) == 1 && force_mode(lc) == 1 && lf.dev.T == lc.dev.T && lf.s_host.size() == lc.s_host.size() &&
+                               std::memcmp(lf.s_host.data(), lc.s_host.data(), lf.s_host.size() * sizeof(double)) == 0 ? 1 : 0;
+    return lf.same_factor_below == 1;
+}
+
 
 // ---------------------------------------------------------------------------------------------------------------
 // Wide Heat1D states (mgrit_hip_wide.inc): the three-launch Phi on a batch and its work slabs
@@ -3932,6 +4048,8 @@ int mgrit_hip_create(mgrit_hip_engine **out, int n_levels, void *stream) {
     {
         const char *s = std::getenv("MGRIT_HIP_DEFER");   // "0": every row stored (mgrit_hip_set_defer)
         e->defer = !(s && std::strcmp(s, "0") == 0);
+        s = std::getenv("MGRIT_HIP_CFAS_FORM");      // "0": cfas_kernel everywhere (mgrit_hip_set_cfas_form)
+        e->cfas_form = !(s && std::strcmp(s, "0") == 0);
     }
     e->stream = static_cast<hipStream_t>(stream);
     e->L.resize(n_levels);
@@ -4838,8 +4956,7 @@ int mgrit_hip_fas_fused_opts(mgrit_hip_engine *e, int lvl, int triples_id, int o
             return launch(ffas_fn(fm, lf.dev.T), dim3(persistent_grid(lf, pl->chunks.n_chunks)), dim3(lf.dev.T), smem_bytes(lf.G, lf.dev.kind),
                           e->stream, sched_dev(e, lf), lc.dev, pl->chunks, opts & MGRIT_HIP_FAS_SKIP_COARSE_U);
         }
-        if (lf.same_factor_below < 0) lf.same_factor_below = (fm == 1 && lf.s_host == lc.s_host) ? 1 : 0;   // (131 KB compared once)
-        const int kopts = opts | (lf.same_factor_below ? 4 : 0);
+        const int kopts = opts | (same_factor_below(lf, lc) ? 4 : 0);
         return launch(fas_fused1_fn(fm, (opts & MGRIT_HIP_FAS_WITH_F_RELAX) != 0, lf.dev.T), dim3(persistent_grid(lf, pl->n)), dim3(lf.dev.T),
                       smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, pl->d_fine, pl->d_prev, pl->d_coarse, pl->n, use_g, kopts);
     }
@@ -5126,9 +5243,16 @@ int mgrit_hip_cf_fas(mgrit_hip_engine *e, int lvl, int ivals_id, int pre_relaxed
     // graph would bake the decision into cycles it does not hold for), on every level size (the row saved is HBM traffic on the
     // levels that stream and a store of 8 KB-128 KB less on those that do not).
     const bool defer = pre_relaxed && e->defer && !has_links(e) && !capturing(e);
+    // One separable term and pre-relaxed C-points (every cycle but the first): the form that keeps the forcing factor in LDS and q
+    // in registers (cfasq_kernel; same bits, same rows). Everything else -- no forcing, several terms, the first cycle -- cfas_kernel.
+    // Where the coarse level's factor is the same vector, its Phi reads the LDS copy too (form 2).
+    const bool q_regs = pre_relaxed && e->cfas_form == 1 && force_mode(lf) == 1;
+    const bool coarse_lds = q_regs && same_factor_below(lf, lc);
     Timed timed(e, MGRIT_HIP_T_CF_FAS, lvl);
-    rc = launch(cfas_fn(force_mode(lf), lf.dev.T), dim3(persistent_grid(lf, I.n_chunks)), dim3(lf.dev.T), smem_bytes(lf.G, lf.dev.kind),
-                e->stream, sched_dev(e, lf), lc.dev, I, !pre_relaxed ? 0 : defer ? (CFAS_PRE | CFAS_HELD) : CFAS_PRE);
+    rc = launch(q_regs ? cfasq_fn(lf.dev.T, coarse_lds) : cfas_fn(force_mode(lf), lf.dev.T), dim3(persistent_grid(lf, I.n_chunks)),
+                dim3(lf.dev.T), smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, I,
+                !pre_relaxed ? 0 : defer ? (CFAS_PRE | CFAS_HELD) : CFAS_PRE);
+    if (!rc) e->cfas_last = !q_regs ? 0 : coarse_lds ? 2 : 1;
     if (!rc && defer) lf.held = ivals_id;
     return rc;
 }
@@ -5280,6 +5404,19 @@ int mgrit_hip_set_defer(mgrit_hip_engine *e, int on) {
     if (on != 0 && on != 1) return fail(MGRIT_HIP_EINVAL, "defer %d: 0 = every row stored, 1 = rows held in a sibling row left out", on);
     e->defer = on != 0;   // (a record that is pending stays: its partner or the next entry point of the level deals with it)
     return 0;
+}
+
+int mgrit_hip_set_cfas_form(mgrit_hip_engine *e, int form) {
+    if (!e) return fail(MGRIT_HIP_EINVAL, "null engine");
+    if (form != 0 && form != 1) return fail(MGRIT_HIP_EINVAL, "cfas form %d: 0 = cfas_kernel always, 1 = cfasq_kernel where it applies", form);
+    e->cfas_form = form;
+    return 0;
+}
+
+int mgrit_hip_cfas_form(mgrit_hip_engine *e, int lvl) {
+    if (!e) return fail(MGRIT_HIP_CFAS_FORM_BAD, "null engine");
+    if (lvl < 0 || lvl >= e->n_levels) return fail(MGRIT_HIP_CFAS_FORM_BAD, "level %d out of range [0,%d)", lvl, e->n_levels);
+    return lvl == 0 ? e->cfas_last : -1;   // (mgrit_hip_cf_fas is level 0's)
 }
 
 int mgrit_hip_set_stream(mgrit_hip_engine *e, void *stream) {
