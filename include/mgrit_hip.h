@@ -367,6 +367,28 @@ int mgrit_hip_ec_relax_res(mgrit_hip_engine *e, int lvl, int intervals_id, int s
 #define MGRIT_HIP_DEFERRED_BAD (-2)
 int mgrit_hip_deferred(mgrit_hip_engine *e, int lvl);
 int mgrit_hip_set_defer(mgrit_hip_engine *e, int on);
+/* Rows of u of a COARSE level that are not stored because the same bits go to the row of v in the same slot. Two passes write a
+ * C-point to u and to v of the next level: the level-0 way down (cf_fas), whose successor on the coarse level -- the F-C-relaxation
+ * -- starts from v and rewrites u without reading it, and the chunked FAS pass with its F-relaxation (fas_fused_opts) onto a
+ * coarsest level whose time-parallel solve, in its six-launch Heat1D form on one rank, can read the level's current values from v
+ * as well. The engine then leaves the rows of u out and notes a record as pending on the coarse level; the partner pass clears
+ * it. Every other entry point that names the coarse level, or the level above it, first copies v to u for the record's slots (one
+ * small launch) and runs as always; a record that was ever settled that way is not deferred again on the engine. List
+ * constructors, and a copy_pairs_u_to_v of rows that are none of the record's, leave it pending. The conditions are
+ * those of the rows above: no exchange links, outside a stream capture (where a pending record makes an entry point return
+ * MGRIT_HIP_EINVAL), the switch on. Binding a level's slabs again drops its record.
+ *   set_twin: mask bit 0 = the way down of level 0, bit 1 = the FAS pass onto the coarsest level may defer (default 2: the way
+ *             down alone showed no gain beyond run-to-run noise when measured, so it waits behind its bit;
+ *             MGRIT_HIP_TWIN=0..3 in the environment of the engine's creation sets it). Other bits, a null engine: MGRIT_HIP_EINVAL.
+ *   twin:     the pending record of the level (an id >= 0), -1 if none, MGRIT_HIP_DEFERRED_BAD for a null engine or a level out
+ *             of range. Touches nothing.
+ *   settle:   puts every pending row of the level and of the next coarser level in place -- for a caller that reads or writes a
+ *             slab without the engine in between a producer and its partner. That holds for v of the level as much as for u:
+ *             while a record is pending the rows of v ARE the level's u, so a caller that writes v there without settling first
+ *             changes the bits a later settle copies into u. */
+int mgrit_hip_set_twin(mgrit_hip_engine *e, int mask);
+int mgrit_hip_twin(mgrit_hip_engine *e, int lvl);
+int mgrit_hip_settle(mgrit_hip_engine *e, int lvl);
 /* The two forms of mgrit_hip_cf_fas. With pre_relaxed = 1 and ONE separable forcing term the pass keeps the level's forcing space
  * factor in LDS and q = Phi_{l+1}(C'_j) in registers (cfasq_kernel) instead of streaming the factor from L2 in every Phi with q
  * parked in LDS (cfas_kernel). Both store the same rows with the same bits, so only the query tells which one ran.

@@ -164,6 +164,8 @@ class HipBackend:
         self._cycle_pre = False   # the state at the start of the running cycle was 2 (begin_cycle)
         self._down_pending = False   # cf_fas has run with pre-relaxed C-points and the level-0 way up has not: the engine may hold
                                      # the closing C-points one row back (include/mgrit_hip.h, mgrit_hip_deferred) until then
+        self._twin_open = set()      # coarse levels whose rows of u the engine may hold back in v (include/mgrit_hip.h, mgrit_hip_twin):
+                                     # entered behind cf_fas / fas_fused, left behind the level's relax FC / forward solve and a settle
         self.f_relax_follows = False   # set by Mgrit.iteration around its own C-relaxations (_before_c_write)
         self._residual_cache = None    # the level-0 points whose residual sums the engine's pinned buffer holds (residual_ready)
         self._write_gen = 0            # write_generation()
@@ -367,9 +369,12 @@ class HipBackend:
         self._config_chain(lvl, d, n, gt)
         self._config_block_solve(lvl, d, n, gt)
         tmpl = mg.problem[lvl].vector_template
-        mg.u.append(SlabVectorList(u, n, tmpl, self.perm[lvl], on_write=self._before_write if lvl == 0 else self._outside_write,
-                                   on_read=self.materialise if lvl == 0 else None))
-        mg.v.append(SlabVectorList(v, n, tmpl, self.perm[lvl]) if v is not None else None)
+        mg.u.append(SlabVectorList(u, n, tmpl, self.perm[lvl],
+                                   on_write=self._before_write if lvl == 0 else lambda lvl=lvl: self._coarse_write(lvl),
+                                   on_read=self.materialise if lvl == 0 else lambda lvl=lvl: self._coarse_rows_in_place(lvl)))
+        # (a write to v of a coarse level: a pending row of u takes its bits from v, so the rows are put in place first)
+        mg.v.append(SlabVectorList(v, n, tmpl, self.perm[lvl], on_write=None if lvl == 0 else lambda lvl=lvl: self._coarse_rows_in_place(lvl))
+                    if v is not None else None)
         mg.g.append(SlabVectorList(g, n, tmpl, self.perm[lvl]) if g is not None else None)
         if mg.comm_time_rank == 0 and t_local.size:
             mg.u[lvl][0] = mg.problem[lvl].vector_t_start
@@ -442,6 +447,7 @@ class HipBackend:
         2 = recurrence over the blocks (+ the corrected last point when a successor waits for it), 4 = corrections + second pass"""
         self._enter(lvl, clear=None)
         check(self.lib.mgrit_hip_block_solve(self.h, lvl, int(phases)))
+        self._twin_open.discard(lvl)
 
     def block_solve_form(self, lvl):
         """how the level's forward solve runs (mgrit_hip_block_solve_form): 0 step by step, 1 a launch or more per phase of the
@@ -559,6 +565,18 @@ class HipBackend:
     def _outside_write(self):
         self._invalidate(outside=True)
 
+    def _coarse_rows_in_place(self, lvl):
+        """in front of a torch read or write of u of a level >= 1 that no engine call stands before: between the pass that fills
+        the level and the level's own first pass the engine may hold rows of u back in v (mgrit_hip_twin); outside that window
+        nothing happens, and no engine call is made"""
+        if lvl in self._twin_open:
+            hip_lib.settle(self.h, lvl)
+            self._twin_open.discard(lvl)
+
+    def _coarse_write(self, lvl):
+        self._coarse_rows_in_place(lvl)
+        self._outside_write()
+
     def _cached(self, points):
         """the residual cache holds exactly these points (compared by identity first: Mgrit hands over the same cached list
         every time)"""
@@ -574,6 +592,8 @@ class HipBackend:
     def U(self):
         """the state slabs, level 0 with every F-point in place (tests, post-processing)"""
         self.materialise()
+        for lvl in sorted(self._twin_open):
+            self._coarse_rows_in_place(lvl)
         return self._U
 
     def materialise(self):
@@ -611,6 +631,8 @@ class HipBackend:
         """host copy of a whole slab in natural x order, shape [n_local_points][n] (tests / post-processing)"""
         if which == "u" and lvl == 0:
             self.materialise()
+        if which == "u" and lvl > 0:
+            self._coarse_rows_in_place(lvl)
         slab = {"u": self._U, "v": self.V, "g": self.G}[which][lvl]
         return slab[:, self.perm[lvl]].cpu().numpy()
 
@@ -620,6 +642,8 @@ class HipBackend:
         if which == "u" and lvl == 0:
             self._rows_in_place()
             self._f_stale = 0      # every row replaced: nothing of the last cycle's C-point storage is left to rebuild
+        if which in ("u", "v") and lvl > 0:     # (v too: a pending row of u takes its bits from v)
+            self._coarse_rows_in_place(lvl)
         slab = {"u": self._U, "v": self.V, "g": self.G}[which][lvl]
         slab.zero_()
         slab[:, self.perm[lvl]] = torch.from_numpy(np.ascontiguousarray(values, dtype=np.float64)).to(slab.device)
@@ -628,6 +652,8 @@ class HipBackend:
     def payload(self, lvl, idx, op=None):
         if lvl == 0:
             self.materialise()
+        else:
+            self._coarse_rows_in_place(lvl)
         if op == 5 and self.block_sharded.get(lvl):    # time-parallel solve: the point and the mode amplitudes behind it
             return torch.cat((self._U[lvl][idx], self.block_uh[lvl][1]))
         if op == 5 and self.chain_handover.get(lvl):   # forward-solve hand-over: the point and the chain's running state
@@ -724,6 +750,8 @@ class HipBackend:
             return
         code = {'F': hip_lib.RELAX_F, 'C': hip_lib.RELAX_C, 'CHAIN': hip_lib.RELAX_CHAIN, 'FC': hip_lib.RELAX_FC}[mode]
         check(self.lib.mgrit_hip_relax(self.h, lvl, self._list_id("runs", lvl, runs), code, float(self.mg.weight_c)))
+        if mode in ('FC', 'CHAIN'):
+            self._twin_open.discard(lvl)
 
     def relax_chain_part(self, lvl, runs, resume):
         """one block of the coarsest-level solve (cycle_plan.py); resume: it continues the chain of the block before it from
@@ -1150,6 +1178,7 @@ class HipBackend:
             return
         opts = (hip_lib.FAS_WITH_F_RELAX if with_f_relax else 0) | (hip_lib.FAS_SKIP_COARSE_U if skip_coarse_u else 0)
         check(self.lib.mgrit_hip_fas_fused_opts(self.h, lvl, self._list_id("triples", lvl, triples), opts))
+        self._twin_open.add(lvl + 1)
 
     def fas_chunks(self, lvl, triples):
         """mgrit_hip_fas_chunks: the chunks fas_fused(with_f_relax=True) launches over for this list, 0 = item by item"""
@@ -1274,6 +1303,7 @@ class HipBackend:
             self._enter(lvl, settle=False, clear="every")
             pre = lvl == 0 and self._cycle_pre
             check(self.lib.mgrit_hip_cf_fas(self.h, lvl, self._intervals_id(lvl, intervals), 1 if pre else 0))
+            self._twin_open.add(lvl + 1)
             self._down_pending = self._down_pending or pre
 
     def ec_relax_res_to(self, lvl, intervals, buf):

@@ -104,6 +104,9 @@ EXPORTS = {
     "mgrit_hip_ec_relax_res": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "mgrit_hip_deferred": (C.c_int, [C.c_void_p, C.c_int]),
     "mgrit_hip_set_defer": (C.c_int, [C.c_void_p, C.c_int]),
+    "mgrit_hip_set_twin": (C.c_int, [C.c_void_p, C.c_int]),
+    "mgrit_hip_twin": (C.c_int, [C.c_void_p, C.c_int]),
+    "mgrit_hip_settle": (C.c_int, [C.c_void_p, C.c_int]),
     "mgrit_hip_set_cfas_form": (C.c_int, [C.c_void_p, C.c_int]),
     "mgrit_hip_cfas_form": (C.c_int, [C.c_void_p, C.c_int]),
     "mgrit_hip_ec_relax_res_to": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
@@ -207,6 +210,12 @@ def level_cahnhilliard2d(h, engine_lvl, n_pts, t_ptr, ld, d):
     """describe a Cahn-Hilliard IMEX level; d: the application's description"""
     check(load().mgrit_hip_level_cahnhilliard2d(h, engine_lvl, n_pts, t_ptr, int(d["nx"]), ld, float(d["inv_dx2"]), float(d["eps2"]),
                                                 float(d["stab"])))
+
+
+def settle(h, lvl):
+    """rows of u the engine has left unstored on the level or the next coarser one (include/mgrit_hip.h, mgrit_hip_twin) are put
+    in place: for a reader or writer of a coarse slab that goes past the engine"""
+    check(load().mgrit_hip_settle(h, int(lvl)))
 
 
 def newton_stats(h, lvl):

@@ -1164,6 +1164,10 @@ struct IntervalsDev {
 // pre: bit 0 = the pre-relaxed rows described above; bit 1 (CFAS_HELD, with bit 0 only) = C'_{j+1} is NOT stored to the fine row ce:
 // row ce-1 holds those very bits and the kernel does not write it, so the next reader of row ce -- ecfr_kernel with ECFR_HELD, or
 // settle_held_kernel in front of anybody else -- takes them from there (Level::held). One row less written per interval.
+// Level::twin of the coarse level (round 12): where the closing C-point goes to BOTH u^{l+1} and v^{l+1} the host may hand these
+// kernels a keep array with bit 0 cleared at those intervals -- the coarse level's first pass, relax_kernel ROLE_FC, starts its runs
+// from v and rewrites that row of u without reading it. (As a launch flag tested beside `keep` the same choice cost
+// cfasq_kernel<1024, true> two more spilled VGPRs, 8 -> 10, with the flags kept as one scalar or as two: the array costs none.)
 enum { CFAS_PRE = 1, CFAS_HELD = 2, ECFR_HELD = 4 };
 template <int FORCE, int TB = 1024>
 __global__ void __launch_bounds__(TB) cfas_kernel(LevelDev L, LevelDev Lc, IntervalsDev I, int flags) {
@@ -1919,7 +1923,24 @@ struct Level {
     int held = -1;                   // interval list whose closing C-points mgrit_hip_cf_fas has NOT stored: row cend-1 holds the bits of
                                      // row cend (cfas_kernel CFAS_HELD). mgrit_hip_ec_relax_res with the same list reads them there
                                      // and clears this; every other entry point of the level puts the rows in place first (check_level)
+    // Level::twin (round 12), kept on the COARSE level of a pair: u of the record's slots was not stored by the finer level's pass,
+    // the row of v in the same slot holds its bits. The partner pass -- one that reads no u there and rewrites every such row --
+    // clears it; every other entry point that reaches this level or the level above it gets the rows copied first (check_level,
+    // settle_twin_kernel), and a record that ever had to be settled that way is not deferred again (missed).
+    struct TwinRec {
+        int kind, list;                 // TWIN_CFAS: interval list `list` of the finer level; TWIN_FFAS: its triples list `list`
+        const int32_t *d_slots;         // the slots on the device (the finer level's arrays)
+        std::vector<int32_t> slots;     // ... and on the host, ascending
+        bool missed = false;
+        std::map<int, bool> covered;    // TWIN_CFAS: run list id of this level -> its runs' closing points contain every slot
+        std::map<int, bool> apart;      // pair list id of the finer level -> none of its coarse points is a slot (mgrit_hip_copy_pairs_u_to_v)
+    };
+    std::vector<TwinRec> twin_recs;
+    int twin = -1;                      // pending record (index into twin_recs), -1: none
+    struct BothSlots { std::vector<int32_t> slots; const int32_t *d_slots = nullptr, *d_keep = nullptr; };   // d_keep: the list's keep with bit 0 cleared there
+    std::vector<BothSlots> ivals_both;  // per interval list of THIS level: coarse slots whose closing C-point goes to u AND v (keep == 3)
 };
+enum { TWIN_CFAS = 0, TWIN_FFAS = 1 };
 
 // ghost exchange (mgrit_hip_comm.inc): one direction of one pair of ranks
 enum { LINK_NONE = 0, LINK_RCCL = 1, LINK_MAILBOX = 2 };
@@ -1947,6 +1968,9 @@ struct mgrit_hip_engine {
     std::vector<hipEvent_t> ev_pool;         // events of drained records, reused
     hipEvent_t last0 = nullptr, last1 = nullptr;   // events of the most recent timed call (mgrit_hip_last_kernel_ms)
     bool defer = true;            // mgrit_hip_set_defer / MGRIT_HIP_DEFER: rows whose bits sit in a sibling row are not stored (Level::held)
+    int twin_mask = 2;            // mgrit_hip_set_twin / MGRIT_HIP_TWIN: bit 0 = mgrit_hip_cf_fas, bit 1 = mgrit_hip_fas_fused_opts may leave out
+                                  // rows of u^{l+1} whose bits sit in v^{l+1} (Level::twin). Bit 0 is off by default: alone it did not
+                                  // show a gain beyond run-to-run noise on the flagship shape
     int cfas_form = 1;            // mgrit_hip_set_cfas_form / MGRIT_HIP_CFAS_FORM: 0 always cfas_kernel, 1 cfasq_kernel where it applies
     int cfas_last = -1;           // mgrit_hip_cfas_form: the form level 0's last mgrit_hip_cf_fas launched (-1: none yet)
     int fas_chunk = 0;            // mgrit_hip_set_fas_chunk: -1 fas_fused1_kernel, 0 chunks by the library's rule, n > 0 chunks of n
@@ -2381,8 +2405,9 @@ auto chain2_fn(int fm, bool use_g) {
 }
 
 // the two passes of the six-launch form: the blocks' local solves, and (finish) the second pass from the corrected block ends
-auto blk_pass_fn(int kind, int fm, bool finish) {
-    auto pass = [&](auto K, auto F) { return finish ? &blk_finish_kernel<K, F> : &blk_local_kernel<K, F>; };
+// twin (first pass of a Heat1D level only): the instance that reads the level's current values through BlkDev::cur (Level::twin)
+auto blk_pass_fn(int kind, int fm, bool finish, bool twin = false) {
+    auto pass = [&](auto K, auto F) { return finish ? &blk_finish_kernel<K, F> : twin ? &blk_local_kernel<K, F, true> : &blk_local_kernel<K, F>; };
     if (kind == MGRIT_HIP_STEPPER_ADVECTION1D) return pick<0>(fm, [&](auto F) { return pass(IntC<MGRIT_HIP_STEPPER_ADVECTION1D>{}, F); });
     return pick<0, 2, 3, 4>(kind == MGRIT_HIP_STEPPER_HEAT1D ? blk_force(fm) : -1, [&](auto F) { return pass(IntC<MGRIT_HIP_STEPPER_HEAT1D>{}, F); });
 }
@@ -2451,6 +2476,7 @@ int register_lds_limits() {
                 allow(fas_coarse_fn(kind, fm), big);
                 allow(at_fn(kind, fm), big);
                 allow(blk_pass_fn(kind, fm, false), blk_smem_bytes(MAX_G));
+                allow(blk_pass_fn(kind, fm, false, true), blk_smem_bytes(MAX_G));
                 allow(blk_pass_fn(kind, fm, true), blk_smem_bytes(MAX_G));
             }
         for (int order : {1, 2})
@@ -2503,11 +2529,55 @@ int settle_held(mgrit_hip_engine *e, int lvl) {
     return rc;
 }
 
-// partner: the interval list whose pending rows (Level::held) the caller reads where they are; any other pending list is settled
-int check_level(mgrit_hip_engine *e, int lvl, bool need_set = true, int partner = -1) {
+// Level::twin: row v of every slot of the pending record copied to row u, the record cleared and marked (it is not deferred again).
+// Never launched into a stream capture, as settle_held_kernel.
+__global__ void __launch_bounds__(256) settle_twin_kernel(double *__restrict__ u, const double *__restrict__ v, int ld,
+                                                          const int32_t *__restrict__ slots, int n) {
+    for (int it = blockIdx.x; it < n; it += gridDim.x) {
+        const int j = slots[it];   // 0 <= j < n_pts (mgrit_hip_intervals_create / mgrit_hip_pairs_create)
+        const double2 *src = reinterpret_cast<const double2 *>(v + (size_t)j * ld);
+        double2 *dst = reinterpret_cast<double2 *>(u + (size_t)j * ld);
+        for (int k = threadIdx.x; k < ld / 2; k += blockDim.x) dst[k] = src[k];
+    }
+}
+
+int settle_twin(mgrit_hip_engine *e, int lvl) {
+    Level &lv = e->L[lvl];
+    if (lv.twin < 0) return 0;
+    Level::TwinRec &rec = lv.twin_recs[lv.twin];
+    if (capturing(e)) return fail(MGRIT_HIP_EINVAL, "level %d has unstored rows of u pending (record %d) inside a stream capture", lvl, lv.twin);
+    const int n = (int)rec.slots.size();
+    const int rc = launch(&settle_twin_kernel, dim3(std::min(n, 4096)), dim3(256), 0, e->stream, lv.dev.u, (const double *)lv.dev.v, lv.dev.ld,
+                          rec.d_slots, n);
+    if (!rc) { rec.missed = true; lv.twin = -1; }
+    return rc;
+}
+
+// the record of (kind, list) on the coarse level lc: found, or made from the slots (ascending on the host)
+int twin_record(Level &lc, int kind, int list, const std::vector<int32_t> &slots, const int32_t *d_slots) {
+    for (size_t i = 0; i < lc.twin_recs.size(); ++i)
+        if (lc.twin_recs[i].kind == kind && lc.twin_recs[i].list == list) return (int)i;
+    Level::TwinRec rec;
+    rec.kind = kind; rec.list = list; rec.d_slots = d_slots; rec.slots = slots;
+    std::sort(rec.slots.begin(), rec.slots.end());
+    lc.twin_recs.push_back(rec);
+    return (int)lc.twin_recs.size() - 1;
+}
+
+// TWIN_KEEP_OWN / TWIN_KEEP_BELOW: the caller leaves the pending record of the level itself / of the next coarser level alone -- it is
+// the record's partner, its producer's own bookkeeping, or it touches no row of either level (list constructors).
+enum { TWIN_KEEP_OWN = 1, TWIN_KEEP_BELOW = 2 };
+
+// partner: the interval list whose pending rows (Level::held) the caller reads where they are; any other pending list is settled.
+// Level::twin: an entry point of level lvl may read u of lvl and of lvl + 1, so both levels' records are settled unless twin_keep says
+// otherwise.
+int check_level(mgrit_hip_engine *e, int lvl, bool need_set = true, int partner = -1, int twin_keep = 0) {
     if (!e) return fail(MGRIT_HIP_EINVAL, "null engine");
     if (lvl < 0 || lvl >= e->n_levels) return fail(MGRIT_HIP_EINVAL, "level %d out of range [0,%d)", lvl, e->n_levels);
     if (need_set && !e->L[lvl].set) return fail(MGRIT_HIP_EINVAL, "level %d has no stepper", lvl);
+    int rc;
+    if (!(twin_keep & TWIN_KEEP_OWN) && e->L[lvl].twin >= 0 && (rc = settle_twin(e, lvl))) return rc;
+    if (!(twin_keep & TWIN_KEEP_BELOW) && lvl + 1 < e->n_levels && e->L[lvl + 1].twin >= 0 && (rc = settle_twin(e, lvl + 1))) return rc;
     if (e->L[lvl].held >= 0 && e->L[lvl].held != partner) return settle_held(e, lvl);
     return 0;
 }
@@ -3464,16 +3534,16 @@ void h2d_axis_tables(int m, int HP, double f, std::vector<double> &Fe, std::vect
     for (int o = 0; o < hO; ++o) { const double hs = std::sin(M_PI * (double)(2 * o + 2) / (2.0 * (m + 1))); lam[HP + o] = 4.0 * f * hs * hs; }
 }
 
-int get_runs(mgrit_hip_engine *e, int lvl, int id, RunList **out) {
-    int rc = check_level(e, lvl);
+int get_runs(mgrit_hip_engine *e, int lvl, int id, RunList **out, int twin_keep = 0) {
+    int rc = check_level(e, lvl, true, -1, twin_keep);
     if (rc) return rc;
     if (id < 0 || id >= (int)e->L[lvl].runs.size()) return fail(MGRIT_HIP_EINVAL, "bad run-list id %d on level %d", id, lvl);
     *out = &e->L[lvl].runs[id];
     return 0;
 }
 
-int get_pairs(mgrit_hip_engine *e, int lvl, int id, PairList **out) {
-    int rc = check_level(e, lvl);
+int get_pairs(mgrit_hip_engine *e, int lvl, int id, PairList **out, int twin_keep = 0) {
+    int rc = check_level(e, lvl, true, -1, twin_keep);
     if (rc) return rc;
     if (lvl + 1 >= e->n_levels || !e->L[lvl + 1].set) return fail(MGRIT_HIP_EINVAL, "level %d has no coarser level", lvl);
     if (id < 0 || id >= (int)e->L[lvl].pairs.size()) return fail(MGRIT_HIP_EINVAL, "bad pair-list id %d on level %d", id, lvl);
@@ -3717,8 +3787,11 @@ bool blk_one_launch_enabled() {
     return !(s && std::atoi(s) == 0);
 }
 
-int blk_launch(mgrit_hip_engine *e, Level &lv, int phases) {
-    BlkDev &bk = lv.blk;
+// twin: the caller is the partner of the level's pending record (Level::twin) -- the first pass and the correction of the block ends
+// read the level's current values from v, and every row the record speaks of is written before the call is over
+int blk_launch(mgrit_hip_engine *e, Level &lv, int phases, bool twin = false) {
+    BlkDev bk = lv.blk;
+    bk.cur = twin ? lv.dev.v : lv.dev.u;
     const int fm = force_mode(lv);
     int rc;
     const size_t lds = blk_smem_bytes(lv.G);
@@ -3736,7 +3809,7 @@ int blk_launch(mgrit_hip_engine *e, Level &lv, int phases) {
     const size_t dft_lds = (size_t)n * sizeof(double2);                          // the table of all n roots of unity
     const unsigned dft_gy = (unsigned)(((n + 15) / 16 + DFT_WAVES - 1) / DFT_WAVES);   // DFT_WAVES tiles of 16 per workgroup
     if (phases & 1) {
-        if ((rc = launch(blk_pass_fn(lv.dev.kind, fm, false), dim3(std::min(bk.B, cap)), block, lds, e->stream, lv.dev, bk))) return rc;
+        if ((rc = launch(blk_pass_fn(lv.dev.kind, fm, false, twin), dim3(std::min(bk.B, cap)), block, lds, e->stream, lv.dev, bk))) return rc;
         const int cnt = bk.B - 1 + (bk.project_last ? 1 : 0);     // blocks whose amplitudes the recurrence reads
         if (adv) {   // what_b = FFT(W_b)
             if (cnt > 0 && dft) hipLaunchKernelGGL(adv_dft_fwd_kernel, dim3((cnt + 15) / 16, dft_gy), dim3(64 * DFT_WAVES), dft_lds, e->stream, lv.dev, bk, 0, cnt);
@@ -3768,6 +3841,7 @@ int blk_launch(mgrit_hip_engine *e, Level &lv, int phases) {
         if ((rc = launch(blk_pass_fn(lv.dev.kind, fm, true), dim3(std::min(bk.B, cap)), block, lds, e->stream, lv.dev, b2))) return rc;
     }
     HIP_TRY(hipGetLastError());
+    if (twin) lv.twin = -1;   // blk_correct_kernel has written every block end (b_end = B on one rank), blk_finish_kernel every interior point
     return 0;
 }
 
@@ -4050,6 +4124,8 @@ int mgrit_hip_create(mgrit_hip_engine **out, int n_levels, void *stream) {
         e->defer = !(s && std::strcmp(s, "0") == 0);
         s = std::getenv("MGRIT_HIP_CFAS_FORM");      // "0": cfas_kernel everywhere (mgrit_hip_set_cfas_form)
         e->cfas_form = !(s && std::strcmp(s, "0") == 0);
+        s = std::getenv("MGRIT_HIP_TWIN");           // "0" .. "3": mgrit_hip_set_twin
+        if (s && s[0] >= '0' && s[0] <= '3' && !s[1]) e->twin_mask = s[0] - '0';
     }
     e->stream = static_cast<hipStream_t>(stream);
     e->L.resize(n_levels);
@@ -4321,6 +4397,7 @@ int mgrit_hip_newton_stats(mgrit_hip_engine *e, int lvl, int64_t out[4]) {
 }
 
 int mgrit_hip_level_bind(mgrit_hip_engine *e, int lvl, double *u, double *v, double *g) {
+    if (e && lvl >= 0 && lvl < e->n_levels) e->L[lvl].twin = -1;   // the slabs the record spoke of are no longer the level's
     int rc = check_level(e, lvl);
     if (rc) return rc;
     if (!u && e->L[lvl].dev.n_pts > 0) return fail(MGRIT_HIP_EINVAL, "u slab is null");
@@ -4425,15 +4502,52 @@ int mgrit_hip_block_solve_form(mgrit_hip_engine *e, int lvl, int *form_out) {
     return 0;
 }
 
+// Level::twin, the partners of a pending record of level lvl (outside a capture; everybody else has check_level settle it):
+// - of mgrit_hip_cf_fas: the F-C-relaxation of the level whose runs close on every slot of the record -- relax_kernel ROLE_FC starts
+//   its runs from v, reads no u and stores u at every closing point (worked out once per record and run list);
+// - of mgrit_hip_fas_fused_opts: the whole time-parallel solve in its six-launch Heat1D form on one rank, when the record is exactly
+//   the slots the solve steps over (1 .. n_steps): it reads the level's current values from v (BlkDev::cur) and writes every one.
+static bool twin_blk_form(const Level &lv) {
+    return !lv.h2d && lv.blk_state >= 0 && lv.blk.r > 0 && !lv.blk.fourier && !lv.blk_qt && lv.blk.first_real && !lv.blk.project_last;
+}
+// the whole-level chain: one run over every step of a level > 0
+static bool is_whole_chain(const Level &lv, int lvl, int mode, const RunList &rl) {
+    return mode == MGRIT_HIP_RELAX_CHAIN && lvl > 0 && rl.n == 1 && rl.h_start[0] == 1 && rl.h_len[0] == lv.dev.n_pts - 1;
+}
+static bool twin_partner_fc(mgrit_hip_engine *e, int lvl, int runs_id) {
+    if (!e || lvl < 0 || lvl >= e->n_levels || e->L[lvl].twin < 0 || capturing(e)) return false;
+    Level &lv = e->L[lvl];
+    Level::TwinRec &rec = lv.twin_recs[lv.twin];
+    if (rec.kind != TWIN_CFAS || runs_id < 0 || runs_id >= (int)lv.runs.size()) return false;
+    const auto seen = rec.covered.find(runs_id);
+    if (seen != rec.covered.end()) return seen->second;
+    const RunList &rl = lv.runs[runs_id];
+    std::vector<int32_t> ends(rl.n);
+    for (int r = 0; r < rl.n; ++r) ends[r] = rl.h_start[r] + rl.h_len[r] - 1;
+    std::sort(ends.begin(), ends.end());
+    const bool all = std::includes(ends.begin(), ends.end(), rec.slots.begin(), rec.slots.end());
+    rec.covered[runs_id] = all;
+    return all;
+}
+static bool twin_partner_blk(mgrit_hip_engine *e, int lvl, int phases) {
+    if (!e || lvl < 0 || lvl >= e->n_levels || e->L[lvl].twin < 0 || capturing(e)) return false;
+    const Level &lv = e->L[lvl];
+    const Level::TwinRec &rec = lv.twin_recs[lv.twin];
+    const int n = (int)rec.slots.size();
+    return rec.kind == TWIN_FFAS && phases == 7 && twin_blk_form(lv) && n == lv.blk.n_steps && rec.slots.front() == 1 && rec.slots.back() == n &&
+           std::adjacent_find(rec.slots.begin(), rec.slots.end()) == rec.slots.end();
+}
+
 int mgrit_hip_block_solve(mgrit_hip_engine *e, int lvl, int phases) {
-    int rc = check_level(e, lvl);
+    const bool twin = twin_partner_blk(e, lvl, phases);   // (any other phase mask finds the pending rows put in place)
+    int rc = check_level(e, lvl, true, -1, twin ? TWIN_KEEP_OWN : 0);
     if (rc) return rc;
     Level &lv = e->L[lvl];
     if (lv.blk_state < 0 || lv.blk.r == 0) return fail(MGRIT_HIP_EINVAL, "level %d has no time-parallel forward solve configured", lvl);
     if (phases < 1 || phases > 7) return fail(MGRIT_HIP_EINVAL, "bad phase mask %d", phases);
     if ((rc = check_bound(lv, true))) return rc;
     Timed timed(e, MGRIT_HIP_T_CHAIN, lvl);
-    return blk_launch(e, lv, phases);
+    return blk_launch(e, lv, phases, twin);
 }
 
 int mgrit_hip_level_transfer(mgrit_hip_engine *e, int lvl, int kind) {
@@ -4471,7 +4585,7 @@ int mgrit_hip_level_transfer(mgrit_hip_engine *e, int lvl, int kind) {
 }
 
 int mgrit_hip_runs_create(mgrit_hip_engine *e, int lvl, int n_runs, const int32_t *start, const int32_t *len, int *id_out) {
-    int rc = check_level(e, lvl);
+    int rc = check_level(e, lvl, true, -1, TWIN_KEEP_OWN | TWIN_KEEP_BELOW);   // (a list constructor touches no row)
     if (rc) return rc;
     if (n_runs < 0 || !id_out || (n_runs > 0 && (!start || !len))) return fail(MGRIT_HIP_EINVAL, "bad run list");
     Level &lv = e->L[lvl];
@@ -4502,7 +4616,7 @@ static int scratch_reserve(Level &lf, size_t rows) {
 
 int mgrit_hip_pairs_create(mgrit_hip_engine *e, int lvl, int n_pairs, const int32_t *fine_idx, const int32_t *coarse_idx,
                            int *id_out) {
-    int rc = check_level(e, lvl);
+    int rc = check_level(e, lvl, true, -1, TWIN_KEEP_OWN | TWIN_KEEP_BELOW);   // (a list constructor touches no row)
     if (rc) return rc;
     if (lvl + 1 >= e->n_levels || !e->L[lvl + 1].set) return fail(MGRIT_HIP_EINVAL, "level %d has no described coarser level", lvl);
     if (n_pairs < 0 || !id_out || (n_pairs > 0 && (!fine_idx || !coarse_idx))) return fail(MGRIT_HIP_EINVAL, "bad pair list");
@@ -4532,7 +4646,13 @@ int mgrit_hip_pairs_create(mgrit_hip_engine *e, int lvl, int n_pairs, const int3
 
 int mgrit_hip_relax(mgrit_hip_engine *e, int lvl, int runs_id, int mode, double weight_c) {
     RunList *rl;
-    int rc = get_runs(e, lvl, runs_id, &rl);
+    // (the whole-level chain of a level with the time-parallel solve is mgrit_hip_block_solve with every phase)
+    // (the partner of a pending record is decided in front of get_runs, whose check_level settles it for everybody else)
+    const bool ids_ok = e && lvl >= 0 && lvl < e->n_levels && runs_id >= 0 && runs_id < (int)e->L[lvl].runs.size();
+    const bool chain_all = ids_ok && is_whole_chain(e->L[lvl], lvl, mode, e->L[lvl].runs[runs_id]) && !batched(e->L[lvl]) && !is_2pts(e->L[lvl]);
+    const bool twin_fc = mode == MGRIT_HIP_RELAX_FC && weight_c == 1.0 && twin_partner_fc(e, lvl, runs_id) && !batched(e->L[lvl]) && !is_2pts(e->L[lvl]);
+    const bool twin_blk = chain_all && twin_partner_blk(e, lvl, 7);
+    int rc = get_runs(e, lvl, runs_id, &rl, (twin_fc || twin_blk) ? TWIN_KEEP_OWN : 0);
     if (rc) return rc;
     Level &lv = e->L[lvl];
     if (mode != MGRIT_HIP_RELAX_F && mode != MGRIT_HIP_RELAX_C && mode != MGRIT_HIP_RELAX_CHAIN && mode != MGRIT_HIP_RELAX_FC)
@@ -4543,7 +4663,7 @@ int mgrit_hip_relax(mgrit_hip_engine *e, int lvl, int runs_id, int mode, double 
     if (rl->n == 0) return 0;
     Timed timed(e, mode == MGRIT_HIP_RELAX_F ? MGRIT_HIP_T_RELAX_F : mode == MGRIT_HIP_RELAX_CHAIN ? MGRIT_HIP_T_CHAIN :
                    mode == MGRIT_HIP_RELAX_FC ? MGRIT_HIP_T_RELAX_FC : MGRIT_HIP_T_RELAX_C, lvl);
-    const bool whole_chain = mode == MGRIT_HIP_RELAX_CHAIN && lvl > 0 && rl->n == 1 && rl->h_start[0] == 1 && rl->h_len[0] == lv.dev.n_pts - 1;
+    const bool whole_chain = is_whole_chain(lv, lvl, mode, *rl);
     // the whole level: the time-parallel form where the level qualifies (not configured yet: the engine's own rule)
     if (whole_chain && lv.blk_state < 0 && (rc = mgrit_hip_block_solve_config(e, lvl, -1, 1, 0, nullptr, nullptr))) return rc;
     if (lv.h2d && whole_chain && lv.blk_state > 0) {
@@ -4562,7 +4682,7 @@ int mgrit_hip_relax(mgrit_hip_engine *e, int lvl, int runs_id, int mode, double 
         if (lv.blk.r > 0) {
             if (!lv.blk.first_real || lv.blk.project_last)
                 return fail(MGRIT_HIP_EINVAL, "level %d is one rank's part of a sharded solve: call mgrit_hip_block_solve by phases", lvl);
-            return blk_launch(e, lv, 7);
+            return blk_launch(e, lv, 7, twin_blk);
         }
     }
     if (mode == MGRIT_HIP_RELAX_CHAIN) {
@@ -4614,8 +4734,10 @@ int mgrit_hip_relax(mgrit_hip_engine *e, int lvl, int runs_id, int mode, double 
         const int role = mode == MGRIT_HIP_RELAX_F ? ROLE_F : mode == MGRIT_HIP_RELAX_FC ? ROLE_FC : (weight_c != 1.0) ? ROLE_C_WEIGHTED : ROLE_C;
         const double w = weight_c, w1 = 1.0 - weight_c;
         // persistent grid: as many workgroups as stay resident (LDS- and thread-limited), at most one per run
-        return launch(relax_fn(lv.dev.kind, force_mode(lv), use_g, role, lv.dev.T), dim3(persistent_grid(lv, rl->n)), dim3(lv.dev.T),
-                      smem_bytes(lv.G, lv.dev.kind), e->stream, sched_dev(e, lv), rl->d_start, rl->d_len, rl->n, w, w1);
+        rc = launch(relax_fn(lv.dev.kind, force_mode(lv), use_g, role, lv.dev.T), dim3(persistent_grid(lv, rl->n)), dim3(lv.dev.T),
+                    smem_bytes(lv.G, lv.dev.kind), e->stream, sched_dev(e, lv), rl->d_start, rl->d_len, rl->n, w, w1);
+        if (!rc && twin_fc) lv.twin = -1;   // the pass has rewritten u of every pending slot from v
+        return rc;
     }
 }
 
@@ -4953,8 +5075,23 @@ int mgrit_hip_fas_fused_opts(mgrit_hip_engine *e, int lvl, int triples_id, int o
         // the timing kind is the same for both
         if ((opts & MGRIT_HIP_FAS_WITH_F_RELAX) && e->fas_chunk >= 0 && pl->chunks_of >= 0) {
             if (pl->chunks_of == 0) return fail(MGRIT_HIP_EINVAL, "list %d has no chunk view", triples_id);
-            return launch(ffas_fn(fm, lf.dev.T), dim3(persistent_grid(lf, pl->chunks.n_chunks)), dim3(lf.dev.T), smem_bytes(lf.G, lf.dev.kind),
-                          e->stream, sched_dev(e, lf), lc.dev, pl->chunks, opts & MGRIT_HIP_FAS_SKIP_COARSE_U);
+            // u^{l+1} stays unstored (Level::twin) where the caller has not said so already and the coarse level is the coarsest one
+            // with the time-parallel solve in its six-launch form on one rank, which then reads the same bits from v: one rank, outside
+            // a capture, a list that is exactly the solve's points and that no other pass ever had to put in place
+            int twin = -1;
+            if (!(opts & MGRIT_HIP_FAS_SKIP_COARSE_U) && (e->twin_mask & 2) && (lvl + 2 >= e->n_levels || !e->L[lvl + 2].set) && twin_blk_form(lc) && !has_links(e) &&
+                !capturing(e)) {
+                twin = twin_record(lc, TWIN_FFAS, triples_id, pl->h_coarse, pl->d_coarse);
+                const Level::TwinRec &rec = lc.twin_recs[twin];
+                const int n = (int)rec.slots.size();
+                const bool whole = n == lc.blk.n_steps && rec.slots.front() == 1 && rec.slots.back() == n &&
+                                   std::adjacent_find(rec.slots.begin(), rec.slots.end()) == rec.slots.end();
+                if (rec.missed || !whole) twin = -1;
+            }
+            rc = launch(ffas_fn(fm, lf.dev.T), dim3(persistent_grid(lf, pl->chunks.n_chunks)), dim3(lf.dev.T), smem_bytes(lf.G, lf.dev.kind),
+                        e->stream, sched_dev(e, lf), lc.dev, pl->chunks, (opts & MGRIT_HIP_FAS_SKIP_COARSE_U) | (twin >= 0 ? MGRIT_HIP_FAS_SKIP_COARSE_U : 0));
+            if (!rc && twin >= 0) lc.twin = twin;
+            return rc;
         }
         const int kopts = opts | (same_factor_below(lf, lc) ? 4 : 0);
         return launch(fas_fused1_fn(fm, (opts & MGRIT_HIP_FAS_WITH_F_RELAX) != 0, lf.dev.T), dim3(persistent_grid(lf, pl->n)), dim3(lf.dev.T),
@@ -4967,7 +5104,21 @@ int mgrit_hip_fas_fused_opts(mgrit_hip_engine *e, int lvl, int triples_id, int o
 
 int mgrit_hip_copy_pairs_u_to_v(mgrit_hip_engine *e, int lvl, int pairs_id) {
     PairList *pl;
-    int rc = get_pairs(e, lvl, pairs_id, &pl);
+    // (Level::twin: a copy of rows that are none of the pending record's slots -- the first point of the level, a ghost -- reads and
+    // writes nothing the record speaks of, and leaves it pending for its partner; worked out once per record and pair list)
+    int keep = 0;
+    if (e && lvl >= 0 && lvl + 1 < e->n_levels && e->L[lvl + 1].twin >= 0 && pairs_id >= 0 && pairs_id < (int)e->L[lvl].pairs.size()) {
+        Level::TwinRec &rec = e->L[lvl + 1].twin_recs[e->L[lvl + 1].twin];
+        auto seen = rec.apart.find(pairs_id);
+        if (seen == rec.apart.end()) {
+            bool apart = true;
+            for (int32_t j : e->L[lvl].pairs[pairs_id].h_coarse)
+                if (std::binary_search(rec.slots.begin(), rec.slots.end(), j)) { apart = false; break; }
+            seen = rec.apart.emplace(pairs_id, apart).first;
+        }
+        keep = seen->second ? TWIN_KEEP_BELOW : 0;
+    }
+    int rc = get_pairs(e, lvl, pairs_id, &pl, keep);
     if (rc) return rc;
     Level &lc = e->L[lvl + 1];
     if ((rc = check_bound(lc, true))) return rc;
@@ -5159,7 +5310,7 @@ int mgrit_hip_timing_drain(mgrit_hip_engine *e, int max_records, int *kind, int 
 int mgrit_hip_intervals_create(mgrit_hip_engine *e, int lvl, int n, const int32_t *cstart, const int32_t *cend,
                                const int32_t *cstart_coarse, const int32_t *cend_coarse, const int32_t *res_pos, int res_len,
                                int chunk, const int32_t *keep, int *id_out) {
-    int rc = check_level(e, lvl);
+    int rc = check_level(e, lvl, true, -1, TWIN_KEEP_OWN | TWIN_KEEP_BELOW);   // (a list constructor touches no row)
     if (rc) return rc;
     if (lvl + 1 >= e->n_levels || !e->L[lvl + 1].set) return fail(MGRIT_HIP_EINVAL, "level %d has no described coarser level", lvl);
     if (n < 0 || chunk < MGRIT_HIP_CHUNK_LONG || res_len < n || !id_out || (n > 0 && (!cstart || !cend || !cstart_coarse || !cend_coarse || !res_pos)))
@@ -5210,6 +5361,19 @@ int mgrit_hip_intervals_create(mgrit_hip_engine *e, int lvl, int n, const int32_
         return rc;
     d.cstart = p[0]; d.cend = p[1]; d.cend_coarse = p[2]; d.res_pos = p[3]; d.chunk_first = p[4]; d.chunk_len = p[5];
     d.chunk_start_coarse = p[6]; d.keep = p[7]; d.n_chunks = (int)cf.size();
+    // Level::twin: the coarse slots that take the closing C-point in u AND in v -- what a deferring mgrit_hip_cf_fas leaves out of u
+    Level::BothSlots both;
+    for (int i = 0; i < n; ++i)
+        if (kp[i] == 3) both.slots.push_back(cend_coarse[i]);
+    if (!both.slots.empty()) {
+        std::vector<int32_t> kt(kp);
+        for (int32_t &k : kt)
+            if (k == 3) k = 2;
+        int32_t *ds = nullptr, *dk = nullptr;
+        if ((rc = dev_upload(lv, e->stream, both.slots, &ds)) || (rc = dev_upload(lv, e->stream, kt, &dk))) return rc;
+        both.d_slots = ds; both.d_keep = dk;
+    }
+    lv.ivals_both.push_back(both);
     lv.ivals.push_back(d);
     lv.ivals_n.push_back(res_len);
     lv.ivals_cnt.push_back(n);
@@ -5248,12 +5412,24 @@ int mgrit_hip_cf_fas(mgrit_hip_engine *e, int lvl, int ivals_id, int pre_relaxed
     // Where the coarse level's factor is the same vector, its Phi reads the LDS copy too (form 2).
     const bool q_regs = pre_relaxed && e->cfas_form == 1 && force_mode(lf) == 1;
     const bool coarse_lds = q_regs && same_factor_below(lf, lc);
+    // Rows of u^{l+1} stay unstored (Level::twin of the coarse level) where the same bits go to v^{l+1}: under the same conditions as
+    // above but for pre_relaxed, where the list has such slots at all (none on a coarsest level: its v bit comes from the chunk ends)
+    // and no other pass ever had to put them in place
+    int twin = -1;
+    if ((e->twin_mask & 1) && !has_links(e) && !capturing(e) && !lf.ivals_both[ivals_id].slots.empty()) {
+        const Level::BothSlots &both = lf.ivals_both[ivals_id];
+        twin = twin_record(lc, TWIN_CFAS, ivals_id, both.slots, both.d_slots);
+        if (lc.twin_recs[twin].missed) twin = -1;
+    }
+    IntervalsDev It = I;
+    if (twin >= 0) It.keep = lf.ivals_both[ivals_id].d_keep;   // bit 0 cleared where both bits were set
     Timed timed(e, MGRIT_HIP_T_CF_FAS, lvl);
     rc = launch(q_regs ? cfasq_fn(lf.dev.T, coarse_lds) : cfas_fn(force_mode(lf), lf.dev.T), dim3(persistent_grid(lf, I.n_chunks)),
-                dim3(lf.dev.T), smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, I,
+                dim3(lf.dev.T), smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, It,
                 !pre_relaxed ? 0 : defer ? (CFAS_PRE | CFAS_HELD) : CFAS_PRE);
     if (!rc) e->cfas_last = !q_regs ? 0 : coarse_lds ? 2 : 1;
     if (!rc && defer) lf.held = ivals_id;
+    if (!rc && twin >= 0) lc.twin = twin;
     return rc;
 }
 
@@ -5405,6 +5581,21 @@ int mgrit_hip_set_defer(mgrit_hip_engine *e, int on) {
     e->defer = on != 0;   // (a record that is pending stays: its partner or the next entry point of the level deals with it)
     return 0;
 }
+
+int mgrit_hip_twin(mgrit_hip_engine *e, int lvl) {
+    if (!e) return fail(MGRIT_HIP_DEFERRED_BAD, "null engine");
+    if (lvl < 0 || lvl >= e->n_levels) return fail(MGRIT_HIP_DEFERRED_BAD, "level %d out of range [0,%d)", lvl, e->n_levels);
+    return e->L[lvl].twin;
+}
+
+int mgrit_hip_set_twin(mgrit_hip_engine *e, int mask) {
+    if (!e) return fail(MGRIT_HIP_EINVAL, "null engine");
+    if (mask & ~3) return fail(MGRIT_HIP_EINVAL, "twin mask %d: bit 0 = mgrit_hip_cf_fas, bit 1 = mgrit_hip_fas_fused_opts may leave rows of u out", mask);
+    e->twin_mask = mask;   // (a record that is pending stays: its partner or the next entry point of the level deals with it)
+    return 0;
+}
+
+int mgrit_hip_settle(mgrit_hip_engine *e, int lvl) { return check_level(e, lvl, false); }
 
 int mgrit_hip_set_cfas_form(mgrit_hip_engine *e, int form) {
     if (!e) return fail(MGRIT_HIP_EINVAL, "null engine");

@@ -53,6 +53,8 @@ struct BlkDev {
     int project_last;    // the amplitudes of the last block's end are wanted too (a rank with a successor)
     int skip_last_row;   // blk_finish_kernel: the last point has been corrected already (blk_last_kernel, sent to the next rank)
     double *Ws;          // [B][ld] the blocks' propagated defects W_b (row storage order)
+    const double *cur;   // the level's current values at the points 1 .. n_steps as blk_correct_kernel and blk_local_kernel<.., TWIN> read
+                         // them (set per launch, blk_launch): the level's u, or its v while u of those rows was left unstored (Level::twin)
     // Advection1D (periodic; all n Fourier modes, n a power of two): what / C / D / uh_in / uh_out hold complex values
     // [B][n] (re, im interleaved), r = n; tw = the n/2 twiddles (cos, -sin)(2 pi t / n)
     const double2 *tw;
@@ -62,7 +64,9 @@ struct BlkDev {
 __device__ __forceinline__ int blk_first(int b) { return BLK_K * b + 1; }
 __device__ __forceinline__ int blk_last(const BlkDev &Bk, int b) { return b == Bk.B - 1 ? Bk.n_steps : BLK_K * (b + 1); }
 
-template <int KIND, int FORCE>
+// TWIN: the level's current values come from Bk.cur (all but the point in front of the first block, which is no row of the record).
+// An instance of its own: with the pointer beside L.u in the one kernel every instance spilled two more VGPRs (round 12).
+template <int KIND, int FORCE, bool TWIN = false>
 __global__ void __launch_bounds__(1024) blk_local_kernel(LevelDev L, BlkDev Bk) {
     constexpr bool HEAT = KIND == MGRIT_HIP_STEPPER_HEAT1D;   // closed-form Phi (the forcing factor may live where the table would)
     WG_PROLOGUE;
@@ -71,14 +75,14 @@ __global__ void __launch_bounds__(1024) blk_local_kernel(LevelDev L, BlkDev Bk) 
     for (int b = blockIdx.x; b < Bk.B; b += gridDim.x) {
         const int first = blk_first(b), last = blk_last(Bk, b);
         double x[E], gi[E];
-        load_row(L.u + (size_t)(first - 1) * L.ld, sl, x);   // the first step's input: u_{i-1} itself (zero error)
+        load_row(((TWIN && b > 0) ? Bk.cur : L.u) + (size_t)(first - 1) * L.ld, sl, x);   // the first step's input: u_{i-1} itself (zero error)
         /*BSTAMP 4*/
         for (int i = first; i <= last; ++i) {
             load_row(L.g + (size_t)i * L.ld, sl, gi);   // in flight while Phi runs (the step's barrier is LDS-only: it does not wait for it)
             phi_apply<KIND, FORCE, HEAT, 0, HEAT>(x, ctx, L, i, sm, t, lane, wave, G);
             /*BSTAMP 5*/
             double cur[E];
-            load_row(L.u + (size_t)i * L.ld, sl, cur);  // (after Phi: one live vector less while it runs)
+            load_row((TWIN ? Bk.cur : L.u) + (size_t)i * L.ld, sl, cur);  // (after Phi: one live vector less while it runs)
 #pragma unroll
             for (int e = 0; e < E; ++e) x[e] = (gi[e] + x[e]) - cur[e];   // the error the block has accumulated at point i
             if (i < last) {
@@ -151,8 +155,9 @@ __global__ void __launch_bounds__(64) blk_correct_kernel(LevelDev L, BlkDev Bk, 
         const int b = b0 + lk + 4 * r;
         if (b >= b_end) continue;
         double *row = L.u + (size_t)blk_last(Bk, b) * ld + p0 + lr;
+        const double *was = Bk.cur + (size_t)blk_last(Bk, b) * ld + p0 + lr;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) row[16 * j] = row[16 * j] + acc[j][r];
+        for (int j = 0; j < 4; ++j) row[16 * j] = was[16 * j] + acc[j][r];
     }
 }
 
