@@ -389,6 +389,46 @@ int mgrit_hip_set_defer(mgrit_hip_engine *e, int on);
 int mgrit_hip_set_twin(mgrit_hip_engine *e, int mask);
 int mgrit_hip_twin(mgrit_hip_engine *e, int lvl);
 int mgrit_hip_settle(mgrit_hip_engine *e, int lvl);
+/* Lagged C-points: corrected level-0 C-points that are not stored because nobody reads them before they are overwritten. In the
+ * steady state of a solve the row cend that mgrit_hip_ec_relax_res(store_all_f = 2) writes -- C'' = A + (u^1_jc - A), A the uncorrected
+ * closing C-point the pass has read -- has no reader: the next mgrit_hip_cf_fas(pre_relaxed = 1) takes P = Phi(F''_last) from row cend-1,
+ * the next mgrit_hip_ec_relax_res takes its uncorrected C-point from where that pass found it, and both rows are rewritten. A way up
+ * that LAGS leaves the store of row cend out. P must not overwrite A, and the next cycle's A is this cycle's P, so the row of P
+ * alternates: with A read from row cend-b (b = 0 or 1 rows back) the pass stores P to row cend-(1-b) and leaves, for its list,
+ *   row cend-k = P,  row cend-(1-k) = A (the bits of v^1_jc),  u^1_jc intact,  k = 1-b,
+ * noted on level 0 as pending. mgrit_hip_cf_fas with the same list, pre_relaxed = 1 and deferring (above) is its partner: it reads
+ * the closing C-points from row cend-k (a chunk's first one from row cstart-k), stores nothing on level 0 and drops the record --
+ * nobody asked for the corrected points, and they are gone for good; mgrit_hip_deferred then names the list as always, and the next
+ * way up reads its A from row cend-k. Every other entry point that names level 0, or level 1 (it may write u^1), first puts the rows in
+ * place for the pending list -- row cend := A + (u^1_jc - A) in exactly that operation order, row cend-1 := P, one small launch -- and
+ * then runs as always: bit for bit what a pass that does not lag leaves. List constructors, mgrit_hip_copy_pairs_u_to_v, a
+ * mgrit_hip_restrict_u whose pairs name none of the record's rows (worked out once per record list and pair list), and the calls
+ * that name no level (mgrit_hip_residual_fetch, sync, timing, queries) leave the record pending. Binding the slabs of level 0 or 1
+ * again drops it. Unlike the records above this one outlives its cycle, so mgrit_hip_set_stream to ANOTHER stream first puts the rows
+ * in place on the stream it leaves: a cycle captured on the new stream finds nothing pending. A captured graph that is REPLAYED goes
+ * past the engine -- its way down reads the rows a pass that does not lag leaves --, so a caller that replays one behind a way up
+ * launched outside it calls mgrit_hip_lag_settle first (HipBackend does).
+ * Conditions: those of the rows above -- no exchange links, outside a stream capture (where a pending record makes an entry point
+ * return MGRIT_HIP_EINVAL), store_all_f = 2, level 0 --, a list in which every C-point that a chunk starts from and that takes part
+ * in the sweep (cstart_coarse >= 0) is the closing C-point of an interval of the same list (the partner reads it where the record
+ * keeps it; a list of some of the level's intervals that begins at another list's closing C-point never lags), and the mode:
+ *   mgrit_hip_set_lag:    0 = never; 1 (default) = by the waiting rule; 2 = every way up that meets the conditions (tests,
+ *                         per-sweep profiles). MGRIT_HIP_LAG=0..2 in the environment of mgrit_hip_create sets it. Anything else, a
+ *                         null engine: MGRIT_HIP_EINVAL. A record that is pending stays pending.
+ *                         The waiting rule: putting the rows in place costs 3-5 rows per interval and a lagged cycle saves one, so
+ *                         lagging must survive several cycles to pay. Per list the engine counts consecutive way ups that ran as the
+ *                         partner of a deferring way down with nothing put in place in between, and lags once that count has reached
+ *                         `wait`, initially 2 -- a solve of three iterations never lags. Each time a lagged list has to be put in
+ *                         place, wait = min(2 * wait, 64) and the count restarts: a caller that looks at the solution every cycle
+ *                         stops paying after a few misses.
+ *   mgrit_hip_lagged:     the pending list of the level, -1 if none, MGRIT_HIP_DEFERRED_BAD for a null engine or a level out of
+ *                         range. Touches nothing.
+ *   mgrit_hip_lag_settle: puts the rows of a pending lagged list of the level in place and nothing else -- no other pending record,
+ *                         no F-point is touched. For a caller that reads the slab of level 0, or writes u of level 1, without the
+ *                         engine behind a way up. */
+int mgrit_hip_set_lag(mgrit_hip_engine *e, int mode);
+int mgrit_hip_lagged(mgrit_hip_engine *e, int lvl);
+int mgrit_hip_lag_settle(mgrit_hip_engine *e, int lvl);
 /* The two forms of mgrit_hip_cf_fas. With pre_relaxed = 1 and ONE separable forcing term the pass keeps the level's forcing space
  * factor in LDS and q = Phi_{l+1}(C'_j) in registers (cfasq_kernel) instead of streaming the factor from L2 in every Phi with q
  * parked in LDS (cfas_kernel). Both store the same rows with the same bits, so only the query tells which one ran.

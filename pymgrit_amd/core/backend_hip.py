@@ -158,12 +158,14 @@ class HipBackend:
                     perm = hip_lib.row_permutation(n)
                 made[key] = torch.from_numpy(np.asarray(perm, dtype=np.int64)).to(self.device)
             self.perm.append(made[key])
-        self._U, self.V, self.G, self.FB = [], [], [], {}     # the slabs per level; FB: the rows of a general forcing
+        self._Us, self.V, self.G, self.FB = [], [], [], {}     # the slabs per level; FB: the rows of a general forcing
         self._f_stale = 0         # level-0 F-points: 0 all in place; 1 all but the last of every interval await materialise();
                                   # 2 as 1, and the last one's row holds Phi of it (the next C-relaxation's value, cf_fas pre)
         self._cycle_pre = False   # the state at the start of the running cycle was 2 (begin_cycle)
         self._down_pending = False   # cf_fas has run with pre-relaxed C-points and the level-0 way up has not: the engine may hold
                                      # the closing C-points one row back (include/mgrit_hip.h, mgrit_hip_deferred) until then
+        self._lag_open = False       # the level-0 way up has run in the form that may leave the corrected C-points unstored
+                                     # (include/mgrit_hip.h, mgrit_hip_lagged) and neither cf_fas nor a settle has followed
         self._twin_open = set()      # coarse levels whose rows of u the engine may hold back in v (include/mgrit_hip.h, mgrit_hip_twin):
                                      # entered behind cf_fas / fas_fused, left behind the level's relax FC / forward solve and a settle
         self.f_relax_follows = False   # set by Mgrit.iteration around its own C-relaxations (_before_c_write)
@@ -334,7 +336,7 @@ class HipBackend:
         if lvl > 0:
             v = torch.zeros_like(u)
             g = torch.zeros_like(u)
-        self._U.append(u), self.V.append(v), self.G.append(g)
+        self._Us.append(u), self.V.append(v), self.G.append(g)
         check(self.lib.mgrit_hip_level_bind(self.h, lvl, C.c_void_p(u.data_ptr()),
                                             C.c_void_p(v.data_ptr() if v is not None else 0),
                                             C.c_void_p(g.data_ptr() if g is not None else 0)))
@@ -533,7 +535,7 @@ class HipBackend:
         if recv_idx is not None:
             (rl, rs), fin = self._xlink(src, 'recv', CH_SWEEP, ordinals[1])
             self._invalidate()
-            check(self.lib.mgrit_hip_recv(self.h, rl, rs, C.c_void_p(self._U[lvl][int(recv_idx)].data_ptr()), ld))
+            check(self.lib.mgrit_hip_recv(self.h, rl, rs, C.c_void_p(self._Us[lvl][int(recv_idx)].data_ptr()), ld))
             if fin is not None:
                 fin()
 
@@ -573,7 +575,26 @@ class HipBackend:
             hip_lib.settle(self.h, lvl)
             self._twin_open.discard(lvl)
 
+    def _lag_in_place(self):
+        """in front of a torch read of level-0 C-points, a torch write of u of level 1, or a graph replay, that no engine call stands
+        before: behind the level-0 way up the engine may hold the corrected C-points back as two rows of level 0 and one of u of
+        level 1 (mgrit_hip_lagged). Puts those rows in place and nothing else. _lag_open is an upper bound -- set behind every way
+        up that MAY have lagged, not cleared by a settle the engine made on its own --, so the call may find nothing to do; with the
+        flag clear (behind cf_fas, materialise(), a capture, this call) none is made"""
+        if self._lag_open:
+            self._lag_open = False
+            hip_lib.lag_settle(self.h, 0)
+
+    @property
+    def _U(self):
+        """the state slabs as they are -- level 0 possibly without its F-points (materialise()) -- with every stored C-point in
+        place; the backend's own code reads self._Us behind the guards of its entry points"""
+        self._lag_in_place()
+        return self._Us
+
     def _coarse_write(self, lvl):
+        if lvl == 1:
+            self._lag_in_place()     # (a pending level-0 record takes u of level 1 as it is now)
         self._coarse_rows_in_place(lvl)
         self._outside_write()
 
@@ -592,9 +613,10 @@ class HipBackend:
     def U(self):
         """the state slabs, level 0 with every F-point in place (tests, post-processing)"""
         self.materialise()
+        self._lag_in_place()
         for lvl in sorted(self._twin_open):
             self._coarse_rows_in_place(lvl)
-        return self._U
+        return self._Us
 
     def materialise(self):
         """C-point storage (include/mgrit_hip.h, mgrit_hip_ec_relax_res): in the steady state of a solve the way up stores, of
@@ -602,8 +624,9 @@ class HipBackend:
         output_fcn, mgrit.u[0][i], natural(), the U slabs -- gets the others rebuilt here by one F-relaxation from the
         C-points: the same Phi on the same values, so bit for bit what an every-point store would have left."""
         self._cycle_pre = False     # whatever the cycle's down pass was promised (begin_cycle), the rows are plain again
-        if self._f_stale or self._down_pending:   # (pending: the F-relaxation is an engine call on level 0, which puts the rows in place)
-            self._f_stale, self._down_pending = 0, False
+        if self._f_stale or self._down_pending:   # (pending: the F-relaxation is an engine call on level 0, which puts the rows in place;
+            self._f_stale, self._down_pending = 0, False   # so it does for _lag_open, which is only ever set in state 2)
+            self._lag_open = False
             cache = self._residual_cache          # an F-relaxation that rewrites identical values leaves the residual valid
             self.relax(0, self.mg._f_runs(0), 'F')
             self._residual_cache = cache
@@ -612,7 +635,7 @@ class HipBackend:
         """in front of a torch read or write of level-0 rows that no engine call stands before: between cf_fas with pre-relaxed
         C-points and the way up the engine may hold the closing C-points one row back, and only an engine call on the level
         puts them in place (materialise()'s F-relaxation is one). Outside that window nothing happens."""
-        if self._down_pending:
+        if self._down_pending or self._lag_open:
             self.materialise()
 
     def _settle(self, lvl):
@@ -633,7 +656,7 @@ class HipBackend:
             self.materialise()
         if which == "u" and lvl > 0:
             self._coarse_rows_in_place(lvl)
-        slab = {"u": self._U, "v": self.V, "g": self.G}[which][lvl]
+        slab = {"u": self._Us, "v": self.V, "g": self.G}[which][lvl]
         return slab[:, self.perm[lvl]].cpu().numpy()
 
     def set_natural(self, which, lvl, values):
@@ -644,7 +667,9 @@ class HipBackend:
             self._f_stale = 0      # every row replaced: nothing of the last cycle's C-point storage is left to rebuild
         if which in ("u", "v") and lvl > 0:     # (v too: a pending row of u takes its bits from v)
             self._coarse_rows_in_place(lvl)
-        slab = {"u": self._U, "v": self.V, "g": self.G}[which][lvl]
+        if which == "u" and lvl == 1:
+            self._lag_in_place()
+        slab = {"u": self._Us, "v": self.V, "g": self.G}[which][lvl]
         slab.zero_()
         slab[:, self.perm[lvl]] = torch.from_numpy(np.ascontiguousarray(values, dtype=np.float64)).to(slab.device)
 
@@ -655,31 +680,31 @@ class HipBackend:
         else:
             self._coarse_rows_in_place(lvl)
         if op == 5 and self.block_sharded.get(lvl):    # time-parallel solve: the point and the mode amplitudes behind it
-            return torch.cat((self._U[lvl][idx], self.block_uh[lvl][1]))
+            return torch.cat((self._Us[lvl][idx], self.block_uh[lvl][1]))
         if op == 5 and self.chain_handover.get(lvl):   # forward-solve hand-over: the point and the chain's running state
             state = self.chain_state[lvl]
             if state is None:   # this rank has no step of its own on the level (it owns the first point only): a fresh start
-                state = torch.cat((self._U[lvl][idx], torch.zeros(64, dtype=torch.float64, device=self.device)))
-            return torch.cat((self._U[lvl][idx], state))
-        return self._U[lvl][idx]
+                state = torch.cat((self._Us[lvl][idx], torch.zeros(64, dtype=torch.float64, device=self.device)))
+            return torch.cat((self._Us[lvl][idx], state))
+        return self._Us[lvl][idx]
 
     def recv_buffer(self, lvl, idx, op=None):
         if op == 5 and self.chain_handover.get(lvl):
             if lvl not in self._handover:
-                self._handover[lvl] = torch.empty(self._U[lvl].shape[1] + self.chain_handover[lvl], dtype=torch.float64,
+                self._handover[lvl] = torch.empty(self._Us[lvl].shape[1] + self.chain_handover[lvl], dtype=torch.float64,
                                                   device=self.device)
             return self._handover[lvl]
-        return self._U[lvl][idx]
+        return self._Us[lvl][idx]
 
     def commit(self, lvl, idx, got, op=None):
         self._invalidate()
         if op == 5 and self.block_sharded.get(lvl):
-            ld = self._U[lvl].shape[1]
-            self._U[lvl][idx].copy_(got[:ld])
+            ld = self._Us[lvl].shape[1]
+            self._Us[lvl][idx].copy_(got[:ld])
             self.block_uh[lvl][0].copy_(got[ld:])
         elif op == 5 and self.chain_handover.get(lvl):
-            ld = self._U[lvl].shape[1]
-            self._U[lvl][idx].copy_(got[:ld])
+            ld = self._Us[lvl].shape[1]
+            self._Us[lvl][idx].copy_(got[:ld])
             if self.chain_state[lvl] is not None:
                 self.chain_state[lvl].copy_(got[ld:])
                 check(self.lib.mgrit_hip_chain_resume(self.h, lvl, 1))   # the next forward solve continues the sender's chain
@@ -864,7 +889,8 @@ class HipBackend:
                     self._f_stale = was
                     if gc_was_on:
                         gc.enable()
-                state["graph"] = graph
+                self._lag_open = False      # (nothing lags inside a capture, and the engine has put a record of the cycle before
+                state["graph"] = graph      # in place when it was moved to the capture stream: mgrit_hip_set_stream)
                 self._replay(state)
                 return
             except Exception as exc:   # noqa: BLE001 - capture is an optimisation: any refusal falls back to plain launches
@@ -888,6 +914,9 @@ class HipBackend:
             self._f_stale = max(self._f_stale, was)   # (also when a launch failed: rows that awaited materialise() still do)
 
     def _replay(self, state):
+        # a replayed graph goes past the engine: its way down reads the rows a cycle that does not lag leaves, so a record that a
+        # launch-by-launch cycle has left since the capture (timed sweeps, another plan of the same solver) is put in place first
+        self._lag_in_place()
         with torch.cuda.stream(self.stream):      # (the engine's stream, whatever the caller has made current since)
             state["graph"].replay()
         self._f_stale = max(self._f_stale, state.get("f_stale", 0))   # what the replayed launches did to the F-points
@@ -1064,7 +1093,7 @@ class HipBackend:
 
     def save_last(self):
         self.materialise()
-        self.prev = self._U[0].clone()
+        self.prev = self._Us[0].clone()
         self.mg.save_values_last_iter = SlabVectorList(self.prev, self.n[0], self.mg.problem[0].vector_template,
                                                        self.perm[0])
 
@@ -1076,7 +1105,7 @@ class HipBackend:
         if slot not in self._snap:
             self._snap[slot] = torch.empty((len(points), self.ld[0]), dtype=torch.float64, device=self.device)
             if len(points):   # every row valid from the start: the mirror never writes a point nobody corrects (the first time point)
-                torch.index_select(self._U[0], 0, self._snap_idx, out=self._snap[slot])
+                torch.index_select(self._Us[0], 0, self._snap_idx, out=self._snap[slot])
         return self._snap[slot]
 
     def mirror_cpoints(self, slot, points):
@@ -1102,13 +1131,13 @@ class HipBackend:
             return     # the cycle's own pass has written them there
         self._snap_slot(slot, points)
         if len(points):
-            torch.index_select(self._U[0], 0, self._snap_idx, out=self._snap[slot])
+            torch.index_select(self._Us[0], 0, self._snap_idx, out=self._snap[slot])
 
     def restore_cpoints(self, slot, points):
         self._rows_in_place()
         self._invalidate()
         if len(points):
-            self._U[0].index_copy_(0, self._snap_idx, self._snap[slot])
+            self._Us[0].index_copy_(0, self._snap_idx, self._snap[slot])
 
     def jump_norms(self, points):
         self.materialise()
@@ -1118,7 +1147,7 @@ class HipBackend:
             check(self.lib.mgrit_hip_jump_host(self.h, 0, self._point_run_id(0, points),
                                                C.c_void_p(self.prev.data_ptr()), _ptr(host)))
             out = np.sqrt(host)
-        self.prev.copy_(self._U[0])
+        self.prev.copy_(self._Us[0])
         return out
 
     def restrict_u(self, lvl, pairs):
@@ -1237,7 +1266,7 @@ class HipBackend:
         if not at["n_own"]:
             return
         own = slice(int(mg.index_local[lvl][0]), int(mg.index_local[lvl][-1]) + 1)   # rows of the owned points in the slab
-        U, G = self._U[lvl], self.G[lvl]
+        U, G = self._Us[lvl], self.G[lvl]
         for slab, work in ((U, at["u"]), (G, at["g"])):        # old u, then g: last rows to the next holder, halo from the previous
             send = (slab[own][at["n_own"] - at["give"]:], at["next"]) if at["give"] else None
             recv = (work[:at["halo"]], at["prev"]) if at["halo"] else None
@@ -1305,6 +1334,8 @@ class HipBackend:
             check(self.lib.mgrit_hip_cf_fas(self.h, lvl, self._intervals_id(lvl, intervals), 1 if pre else 0))
             self._twin_open.add(lvl + 1)
             self._down_pending = self._down_pending or pre
+            if lvl == 0:
+                self._lag_open = False      # (its partner has dropped the record, anything else has had the rows put in place)
 
     def ec_relax_res_to(self, lvl, intervals, buf):
         """several ranks: error_correction + f_relax + the residual sums of the rank's complete intervals (every F-point stored:
@@ -1330,6 +1361,8 @@ class HipBackend:
                 self._mirror_hit = True
             if lazy:
                 self._f_stale = max(self._f_stale, 2 if mode == 2 else 1)
+            if lvl == 0 and mode == 2 and not self.device_links:
+                self._lag_open = True
 
     # -- the same two passes for any 1-D stepper pair and any of the library's transfers (mgrit_hip_gen_down / mgrit_hip_gen_up) --
     def can_gen_level(self, lvl):

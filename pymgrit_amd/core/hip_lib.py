@@ -107,6 +107,9 @@ EXPORTS = {
     "mgrit_hip_set_twin": (C.c_int, [C.c_void_p, C.c_int]),
     "mgrit_hip_twin": (C.c_int, [C.c_void_p, C.c_int]),
     "mgrit_hip_settle": (C.c_int, [C.c_void_p, C.c_int]),
+    "mgrit_hip_set_lag": (C.c_int, [C.c_void_p, C.c_int]),
+    "mgrit_hip_lagged": (C.c_int, [C.c_void_p, C.c_int]),
+    "mgrit_hip_lag_settle": (C.c_int, [C.c_void_p, C.c_int]),
     "mgrit_hip_set_cfas_form": (C.c_int, [C.c_void_p, C.c_int]),
     "mgrit_hip_cfas_form": (C.c_int, [C.c_void_p, C.c_int]),
     "mgrit_hip_ec_relax_res_to": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
@@ -216,6 +219,12 @@ def settle(h, lvl):
     """rows of u the engine has left unstored on the level or the next coarser one (include/mgrit_hip.h, mgrit_hip_twin) are put
     in place: for a reader or writer of a coarse slab that goes past the engine"""
     check(load().mgrit_hip_settle(h, int(lvl)))
+
+
+def lag_settle(h, lvl):
+    """corrected C-points the level's way up has left unstored (include/mgrit_hip.h, mgrit_hip_lagged) are put in place, and
+    nothing else: for a reader of the level-0 slab, or a writer of u of level 1, that goes past the engine"""
+    check(load().mgrit_hip_lag_settle(h, int(lvl)))
 
 
 def newton_stats(h, lvl):

@@ -1168,7 +1168,14 @@ struct IntervalsDev {
 // kernels a keep array with bit 0 cleared at those intervals -- the coarse level's first pass, relax_kernel ROLE_FC, starts its runs
 // from v and rewrites that row of u without reading it. (As a launch flag tested beside `keep` the same choice cost
 // cfasq_kernel<1024, true> two more spilled VGPRs, 8 -> 10, with the flags kept as one scalar or as two: the array costs none.)
-enum { CFAS_PRE = 1, CFAS_HELD = 2, ECFR_HELD = 4 };
+// Lagged C-points (round 13, Level::lag): a level-0 way up that lags (ECFR_LAG) does not store the corrected C-point at all and leaves
+// P = Phi_l(F''_last) in the row the uncorrected C-point A was NOT read from -- row ce-1 and row ce in turn. Where it sits in row ce
+// the way down needs no word of it in these kernels: with CFAS_PRE | CFAS_HELD they read level-0 rows ce-1 and cs-1 (cs itself for a
+// first point that is not relaxed) and store none, so the host hands them L.u one row further on and a chunk_start_coarse without
+// negative entries (mgrit_hip_cf_fas) -- every read lands one row later, the first point's on row cs. (As a launch flag the same
+// choice cost cfasq_kernel<1024, true> two more spilled VGPRs, 8 -> 10, as a row offset beside each read and as a base pointer
+// computed once per launch and pinned in SGPRs alike.)
+enum { CFAS_PRE = 1, CFAS_HELD = 2, ECFR_HELD = 4, ECFR_LAG = 8 };
 template <int FORCE, int TB = 1024>
 __global__ void __launch_bounds__(TB) cfas_kernel(LevelDev L, LevelDev Lc, IntervalsDev I, int flags) {
     constexpr int KIND = MGRIT_HIP_STEPPER_HEAT1D;
@@ -1353,7 +1360,12 @@ __global__ void __launch_bounds__(TB) ecfr_kernel(LevelDev L, LevelDev Lc, Inter
                                                     double *const *__restrict__ mirror, int mirror_row0) {
     // store_flags = store_f | ECFR_HELD: with ECFR_HELD (store_f = 2 only) the uncorrected closing C-point is read from row ce-1, where
     // cfas_kernel (CFAS_HELD) found it and left it; this kernel overwrites that row only behind the read, by the same lane
-    const int store_f = store_flags & 3, held = store_flags >> 2;   // (wave-uniform launch arguments; held = 0 / 1 rows back)
+    // ECFR_LAG (RES, store_f = 2 only; Level::lag): the corrected C-point is NOT stored -- it is A + (u^{l+1}_jc - A) of two rows that
+    // stay as they are, for whoever asks (settle_lag_kernel) -- and P goes to the row A was not read from: row ce when A sits one row
+    // back, row ce-1 when it sits in row ce, so the next way down finds P and the next way up finds its A in turn
+    const int store_f = store_flags & 3, held = (store_flags >> 2) & 1;   // (wave-uniform launch arguments; held = 0 / 1 rows back)
+    const bool lag = RES && (store_flags & ECFR_LAG);
+    const int p_back = lag ? 1 - held : 1;                                // rows back from ce where P goes
     constexpr int KIND = MGRIT_HIP_STEPPER_HEAT1D;
     constexpr bool CF = FORCE == 4;   // forcing factor in LDS, so every Phi in closed form
     WG_PROLOGUE_TB(TB);
@@ -1399,11 +1411,11 @@ __global__ void __launch_bounds__(TB) ecfr_kernel(LevelDev L, LevelDev Lc, Inter
 #pragma unroll
                 for (int e = 0; e < E; ++e) b[e] = b[e] + (w[e] - b[e]);
             }
-            store_row_nt(L.u + (size_t)ce * L.ld, sl, b, L.stream_rows);
+            if (!lag) store_row_nt(L.u + (size_t)ce * L.ld, sl, b, L.stream_rows);
             if (RES && mir) store_row_nt(mir + (size_t)(mirror_row0 + I.res_pos[it]) * L.ld, sl, b, 1);
             if (RES) {
                 phi_apply<KIND, FORCE, CF, 0, false, ONE>(x, ctx, L, ce, sm, t, lane, wave, G);
-                if (store_f == 2) store_row_nt(L.u + (size_t)(ce - 1) * L.ld, sl, x, L.stream_rows);   // Phi(last F-point): the next C-relaxation's value
+                if (store_f == 2) store_row_nt(L.u + (size_t)(ce - p_back) * L.ld, sl, x, L.stream_rows);   // Phi(last F-point): the next C-relaxation's value
 #pragma unroll
                 for (int e = 0; e < E; ++e) x[e] = x[e] - b[e];
                 const double tot = block_sumsq(x, sm, L.n, t, lane, wave, G);
@@ -1923,6 +1935,19 @@ struct Level {
     int held = -1;                   // interval list whose closing C-points mgrit_hip_cf_fas has NOT stored: row cend-1 holds the bits of
                                      // row cend (cfas_kernel CFAS_HELD). mgrit_hip_ec_relax_res with the same list reads them there
                                      // and clears this; every other entry point of the level puts the rows in place first (check_level)
+    int held_back = 1;               // ... and how many rows back from cend those bits sit: 1, or 0 behind a lagged way up (row cend itself)
+    // Level::lag (round 13), level 0 only: interval list whose corrected closing C-points the last mgrit_hip_ec_relax_res has NOT stored.
+    // P = Phi(F''_last) sits in row cend-lag_k, the uncorrected C-point A in the other row of the two, u^{l+1} at cend_coarse is intact, and
+    // the corrected value is A + (u^{l+1} - A) (settle_lag_kernel). mgrit_hip_cf_fas with the same list reads P where it is and drops the
+    // record; every other entry point that names this level or the next one gets the rows put in place first (check_level).
+    int lag = -1, lag_k = 0;
+    // the waiting rule of mode 1: a settle of a lagged list costs 3-5 rows per interval and a lagged cycle saves one, so a list lags only
+    // after lag_wait consecutive way ups as the partner of a deferring way down, and every such settle doubles lag_wait (up to 64)
+    int lag_wait = 2;
+    std::map<int, int> lag_streak;                    // interval list -> consecutive partner way ups with no settle in between
+    std::map<std::pair<int, int>, bool> lag_apart;    // (interval list, pair list) -> the pairs name none of the record's rows
+    std::vector<std::vector<int32_t>> ivals_rows, ivals_cslots;   // per interval list, ascending: fine rows cend-1 / cend, coarse slots cend_coarse
+    std::vector<char> ivals_lag_ok;                   // per interval list: every relaxed C-point a chunk starts from closes an interval of the SAME list
     // Level::twin (round 12), kept on the COARSE level of a pair: u of the record's slots was not stored by the finer level's pass,
     // the row of v in the same slot holds its bits. The partner pass -- one that reads no u there and rewrites every such row --
     // clears it; every other entry point that reaches this level or the level above it gets the rows copied first (check_level,
@@ -1971,6 +1996,7 @@ struct mgrit_hip_engine {
     int twin_mask = 2;            // mgrit_hip_set_twin / MGRIT_HIP_TWIN: bit 0 = mgrit_hip_cf_fas, bit 1 = mgrit_hip_fas_fused_opts may leave out
                                   // rows of u^{l+1} whose bits sit in v^{l+1} (Level::twin). Bit 0 is off by default: alone it did not
                                   // show a gain beyond run-to-run noise on the flagship shape
+    int lag_mode = 1;             // mgrit_hip_set_lag / MGRIT_HIP_LAG: 0 never, 1 by the waiting rule, 2 every way up that may (Level::lag)
     int cfas_form = 1;            // mgrit_hip_set_cfas_form / MGRIT_HIP_CFAS_FORM: 0 always cfas_kernel, 1 cfasq_kernel where it applies
     int cfas_last = -1;           // mgrit_hip_cfas_form: the form level 0's last mgrit_hip_cf_fas launched (-1: none yet)
     int fas_chunk = 0;            // mgrit_hip_set_fas_chunk: -1 fas_fused1_kernel, 0 chunks by the library's rule, n > 0 chunks of n
@@ -2499,12 +2525,35 @@ int register_lds_limits() {
 // Level::held: the rows a deferring mgrit_hip_cf_fas has left out are put in place -- row cend-1 copied to row cend for every
 // interval of the list -- and the record is cleared. Never launched into a stream capture: a captured copy would be replayed
 // in cycles that have nothing pending.
-__global__ void __launch_bounds__(256) settle_held_kernel(double *__restrict__ u, int ld, const int32_t *__restrict__ cend, int n) {
+// back = Level::held_back: 1 = the bits sit in row cend-1 (copied to row cend); 0 = behind a lagged way up they sit in row cend itself,
+// and row cend-1 receives them, so that both rows hold what they hold behind every other settle.
+__global__ void __launch_bounds__(256) settle_held_kernel(double *__restrict__ u, int ld, const int32_t *__restrict__ cend, int n, int back) {
     for (int it = blockIdx.x; it < n; it += gridDim.x) {
         const int ce = cend[it];   // 2 <= ce < n_pts (mgrit_hip_intervals_create)
-        const double2 *src = reinterpret_cast<const double2 *>(u + (size_t)(ce - 1) * ld);
-        double2 *dst = reinterpret_cast<double2 *>(u + (size_t)ce * ld);
+        const double2 *src = reinterpret_cast<const double2 *>(u + (size_t)(ce - back) * ld);
+        double2 *dst = reinterpret_cast<double2 *>(u + (size_t)(ce - 1 + back) * ld);
         for (int k = threadIdx.x; k < ld / 2; k += blockDim.x) dst[k] = src[k];
+    }
+}
+
+// Level::lag: the rows a lagging mgrit_hip_ec_relax_res has left out are put in place and the record is cleared. With A the uncorrected
+// closing C-point and P = Phi(F''_last) in rows cend-1 / cend (k = 1: A in row cend, P in row cend-1; k = 0: the other way round), row
+// cend := A + (uc - A) with uc = row cend_coarse of u^{l+1} -- ecfr_kernel's expression on ecfr_kernel's operands, element by element,
+// pad columns included -- and row cend-1 := P: bit for bit what a pass that does not lag leaves. Every lane reads its operands before
+// it writes, so the rows are rewritten in place. Never launched into a stream capture, as settle_held_kernel.
+__global__ void __launch_bounds__(256) settle_lag_kernel(double *__restrict__ u, const double *__restrict__ uc, int ld, int ldc,
+                                                         const int32_t *__restrict__ cend, const int32_t *__restrict__ cend_coarse, int n,
+                                                         int k_lag) {
+    for (int it = blockIdx.x; it < n; it += gridDim.x) {
+        const int ce = cend[it], jc = cend_coarse[it];   // 2 <= ce < n_pts, 0 <= jc < n_pts of the coarse level (mgrit_hip_intervals_create)
+        double2 *r1 = reinterpret_cast<double2 *>(u + (size_t)ce * ld);
+        double2 *r0 = reinterpret_cast<double2 *>(u + (size_t)(ce - 1) * ld);
+        const double2 *rc = reinterpret_cast<const double2 *>(uc + (size_t)jc * ldc);
+        for (int k = threadIdx.x; k < ld / 2; k += blockDim.x) {
+            const double2 a = k_lag ? r1[k] : r0[k], w = rc[k];
+            if (!k_lag) r0[k] = r1[k];
+            r1[k] = make_double2(a.x + (w.x - a.x), a.y + (w.y - a.y));
+        }
     }
 }
 
@@ -2524,8 +2573,31 @@ int settle_held(mgrit_hip_engine *e, int lvl) {
     Level &lv = e->L[lvl];
     if (capturing(e)) return fail(MGRIT_HIP_EINVAL, "level %d has unstored C-points pending (interval list %d) inside a stream capture", lvl, lv.held);
     const int n = lv.ivals_cnt[lv.held];
-    const int rc = launch(&settle_held_kernel, dim3(std::min(n, 4096)), dim3(256), 0, e->stream, lv.dev.u, lv.dev.ld, lv.ivals[lv.held].cend, n);
-    if (!rc) lv.held = -1;
+    const int rc = launch(&settle_held_kernel, dim3(std::min(n, 4096)), dim3(256), 0, e->stream, lv.dev.u, lv.dev.ld, lv.ivals[lv.held].cend, n,
+                          lv.held_back);
+    if (!rc) {
+        lv.lag_streak[lv.held] = 0;   // (the waiting rule counts way ups with no settle in between)
+        lv.held = -1;
+        lv.held_back = 1;
+    }
+    return rc;
+}
+
+// Level::lag of level 0 (the only level that lags): see settle_lag_kernel. A settle is a miss of the waiting rule.
+int settle_lag(mgrit_hip_engine *e) {
+    Level &lv = e->L[0];
+    if (lv.lag < 0) return 0;
+    if (capturing(e)) return fail(MGRIT_HIP_EINVAL, "level 0 has unstored corrected C-points pending (interval list %d) inside a stream capture", lv.lag);
+    const Level &lc = e->L[1];
+    const int n = lv.ivals_cnt[lv.lag];
+    const IntervalsDev &I = lv.ivals[lv.lag];
+    const int rc = launch(&settle_lag_kernel, dim3(std::min(n, 4096)), dim3(256), 0, e->stream, lv.dev.u, (const double *)lc.dev.u, lv.dev.ld,
+                          lc.dev.ld, I.cend, I.cend_coarse, n, lv.lag_k);
+    if (!rc) {
+        lv.lag_streak[lv.lag] = 0;
+        lv.lag_wait = std::min(2 * lv.lag_wait, 64);
+        lv.lag = -1;
+    }
     return rc;
 }
 
@@ -2566,11 +2638,13 @@ int twin_record(Level &lc, int kind, int list, const std::vector<int32_t> &slots
 
 // TWIN_KEEP_OWN / TWIN_KEEP_BELOW: the caller leaves the pending record of the level itself / of the next coarser level alone -- it is
 // the record's partner, its producer's own bookkeeping, or it touches no row of either level (list constructors).
-enum { TWIN_KEEP_OWN = 1, TWIN_KEEP_BELOW = 2 };
+// LAG_KEEP: likewise for Level::lag of level 0 -- mgrit_hip_cf_fas as its partner, list constructors, a pair-list copy of other rows.
+enum { TWIN_KEEP_OWN = 1, TWIN_KEEP_BELOW = 2, LAG_KEEP = 4, KEEP_ALL = 7 };
 
 // partner: the interval list whose pending rows (Level::held) the caller reads where they are; any other pending list is settled.
 // Level::twin: an entry point of level lvl may read u of lvl and of lvl + 1, so both levels' records are settled unless twin_keep says
-// otherwise.
+// otherwise. Level::lag: the record of level 0 speaks of rows of level 0 and of u of level 1, which an entry point of either may read
+// or write, so both settle it unless twin_keep says otherwise.
 int check_level(mgrit_hip_engine *e, int lvl, bool need_set = true, int partner = -1, int twin_keep = 0) {
     if (!e) return fail(MGRIT_HIP_EINVAL, "null engine");
     if (lvl < 0 || lvl >= e->n_levels) return fail(MGRIT_HIP_EINVAL, "level %d out of range [0,%d)", lvl, e->n_levels);
@@ -2578,6 +2652,7 @@ int check_level(mgrit_hip_engine *e, int lvl, bool need_set = true, int partner 
     int rc;
     if (!(twin_keep & TWIN_KEEP_OWN) && e->L[lvl].twin >= 0 && (rc = settle_twin(e, lvl))) return rc;
     if (!(twin_keep & TWIN_KEEP_BELOW) && lvl + 1 < e->n_levels && e->L[lvl + 1].twin >= 0 && (rc = settle_twin(e, lvl + 1))) return rc;
+    if (!(twin_keep & LAG_KEEP) && lvl <= 1 && e->L[0].lag >= 0 && (rc = settle_lag(e))) return rc;
     if (e->L[lvl].held >= 0 && e->L[lvl].held != partner) return settle_held(e, lvl);
     return 0;
 }
@@ -4126,6 +4201,8 @@ int mgrit_hip_create(mgrit_hip_engine **out, int n_levels, void *stream) {
         e->cfas_form = !(s && std::strcmp(s, "0") == 0);
         s = std::getenv("MGRIT_HIP_TWIN");           // "0" .. "3": mgrit_hip_set_twin
         if (s && s[0] >= '0' && s[0] <= '3' && !s[1]) e->twin_mask = s[0] - '0';
+        s = std::getenv("MGRIT_HIP_LAG");            // "0" .. "2": mgrit_hip_set_lag
+        if (s && s[0] >= '0' && s[0] <= '2' && !s[1]) e->lag_mode = s[0] - '0';
     }
     e->stream = static_cast<hipStream_t>(stream);
     e->L.resize(n_levels);
@@ -4398,6 +4475,7 @@ int mgrit_hip_newton_stats(mgrit_hip_engine *e, int lvl, int64_t out[4]) {
 
 int mgrit_hip_level_bind(mgrit_hip_engine *e, int lvl, double *u, double *v, double *g) {
     if (e && lvl >= 0 && lvl < e->n_levels) e->L[lvl].twin = -1;   // the slabs the record spoke of are no longer the level's
+    if (e && lvl >= 0 && lvl <= 1 && lvl < e->n_levels) e->L[0].lag = -1;   // (Level::lag speaks of u of level 0 and of level 1)
     int rc = check_level(e, lvl);
     if (rc) return rc;
     if (!u && e->L[lvl].dev.n_pts > 0) return fail(MGRIT_HIP_EINVAL, "u slab is null");
@@ -4585,7 +4663,7 @@ int mgrit_hip_level_transfer(mgrit_hip_engine *e, int lvl, int kind) {
 }
 
 int mgrit_hip_runs_create(mgrit_hip_engine *e, int lvl, int n_runs, const int32_t *start, const int32_t *len, int *id_out) {
-    int rc = check_level(e, lvl, true, -1, TWIN_KEEP_OWN | TWIN_KEEP_BELOW);   // (a list constructor touches no row)
+    int rc = check_level(e, lvl, true, -1, KEEP_ALL);   // (a list constructor touches no row)
     if (rc) return rc;
     if (n_runs < 0 || !id_out || (n_runs > 0 && (!start || !len))) return fail(MGRIT_HIP_EINVAL, "bad run list");
     Level &lv = e->L[lvl];
@@ -4616,7 +4694,7 @@ static int scratch_reserve(Level &lf, size_t rows) {
 
 int mgrit_hip_pairs_create(mgrit_hip_engine *e, int lvl, int n_pairs, const int32_t *fine_idx, const int32_t *coarse_idx,
                            int *id_out) {
-    int rc = check_level(e, lvl, true, -1, TWIN_KEEP_OWN | TWIN_KEEP_BELOW);   // (a list constructor touches no row)
+    int rc = check_level(e, lvl, true, -1, KEEP_ALL);   // (a list constructor touches no row)
     if (rc) return rc;
     if (lvl + 1 >= e->n_levels || !e->L[lvl + 1].set) return fail(MGRIT_HIP_EINVAL, "level %d has no described coarser level", lvl);
     if (n_pairs < 0 || !id_out || (n_pairs > 0 && (!fine_idx || !coarse_idx))) return fail(MGRIT_HIP_EINVAL, "bad pair list");
@@ -4863,9 +4941,30 @@ static int fas_coarse_half(mgrit_hip_engine *e, int lvl, PairList *pl) {
                   pl->d_coarse, 0);
 }
 
+// Level::lag: a pair list leaves the pending record of level 0 alone when it names none of its rows -- on level 0 neither a fine row
+// cend-1 / cend nor a coarse slot cend_coarse (the injection of the first time point); on level 1 always: rows of u^1 are read
+// there and none written. Worked out once per record list and pair list.
+static int lag_keep_pairs(mgrit_hip_engine *e, int lvl, int pairs_id) {
+    if (!e || lvl < 0 || lvl > 1 || lvl >= e->n_levels || e->L[0].lag < 0) return 0;
+    if (lvl == 1) return LAG_KEEP;
+    Level &lf = e->L[0];
+    if (pairs_id < 0 || pairs_id >= (int)lf.pairs.size()) return 0;
+    const auto key = std::make_pair(lf.lag, pairs_id);
+    auto seen = lf.lag_apart.find(key);
+    if (seen == lf.lag_apart.end()) {
+        const PairList &pl = lf.pairs[pairs_id];
+        const std::vector<int32_t> &rows = lf.ivals_rows[lf.lag], &slots = lf.ivals_cslots[lf.lag];
+        bool apart = true;
+        for (int p = 0; p < pl.n && apart; ++p)
+            apart = !std::binary_search(rows.begin(), rows.end(), pl.h_fine[p]) && !std::binary_search(slots.begin(), slots.end(), pl.h_coarse[p]);
+        seen = lf.lag_apart.emplace(key, apart).first;
+    }
+    return seen->second ? LAG_KEEP : 0;
+}
+
 int mgrit_hip_restrict_u(mgrit_hip_engine *e, int lvl, int pairs_id) {
     PairList *pl;
-    int rc = get_pairs(e, lvl, pairs_id, &pl);
+    int rc = get_pairs(e, lvl, pairs_id, &pl, lag_keep_pairs(e, lvl, pairs_id));
     if (rc) return rc;
     Level &lf = e->L[lvl], &lc = e->L[lvl + 1];
     if ((rc = caller_transfer(lf, lvl))) return rc;
@@ -5118,6 +5217,8 @@ int mgrit_hip_copy_pairs_u_to_v(mgrit_hip_engine *e, int lvl, int pairs_id) {
         }
         keep = seen->second ? TWIN_KEEP_BELOW : 0;
     }
+    // (Level::lag: the copy reads u and writes v of level lvl + 1, so of the record's rows it can only read u^1 -- which is intact)
+    if (e && lvl <= 1 && e->n_levels > 0 && e->L[0].lag >= 0) keep |= LAG_KEEP;
     int rc = get_pairs(e, lvl, pairs_id, &pl, keep);
     if (rc) return rc;
     Level &lc = e->L[lvl + 1];
@@ -5310,7 +5411,7 @@ int mgrit_hip_timing_drain(mgrit_hip_engine *e, int max_records, int *kind, int 
 int mgrit_hip_intervals_create(mgrit_hip_engine *e, int lvl, int n, const int32_t *cstart, const int32_t *cend,
                                const int32_t *cstart_coarse, const int32_t *cend_coarse, const int32_t *res_pos, int res_len,
                                int chunk, const int32_t *keep, int *id_out) {
-    int rc = check_level(e, lvl, true, -1, TWIN_KEEP_OWN | TWIN_KEEP_BELOW);   // (a list constructor touches no row)
+    int rc = check_level(e, lvl, true, -1, KEEP_ALL);   // (a list constructor touches no row)
     if (rc) return rc;
     if (lvl + 1 >= e->n_levels || !e->L[lvl + 1].set) return fail(MGRIT_HIP_EINVAL, "level %d has no described coarser level", lvl);
     if (n < 0 || chunk < MGRIT_HIP_CHUNK_LONG || res_len < n || !id_out || (n > 0 && (!cstart || !cend || !cstart_coarse || !cend_coarse || !res_pos)))
@@ -5374,6 +5475,22 @@ int mgrit_hip_intervals_create(mgrit_hip_engine *e, int lvl, int n, const int32_
         both.d_slots = ds; both.d_keep = dk;
     }
     lv.ivals_both.push_back(both);
+    // Level::lag: the rows a record of this list speaks of (what a pair-list copy must stay clear of to leave it pending)
+    std::vector<int32_t> rows, cslots(cend_coarse, cend_coarse + n);
+    for (int i = 0; i < n; ++i) { rows.push_back(cend[i] - 1); rows.push_back(cend[i]); }
+    std::sort(rows.begin(), rows.end());
+    std::sort(cslots.begin(), cslots.end());
+    lv.ivals_rows.push_back(rows);
+    lv.ivals_cslots.push_back(cslots);
+    // ... and whether the list may lag at all: as the record's partner the way down reads a chunk's first C-point where the RECORD
+    // keeps it, so that point must close an interval of this list (a block's list of a planned cycle starts at another list's
+    // closing C-point, a list with gaps likewise: those never lag)
+    std::vector<int32_t> ends(cend, cend + n);
+    std::sort(ends.begin(), ends.end());
+    bool lag_ok = true;
+    for (size_t k = 0; k < cf.size() && lag_ok; ++k)
+        lag_ok = cc[k] < 0 || std::binary_search(ends.begin(), ends.end(), cstart[cf[k]]);
+    lv.ivals_lag_ok.push_back(lag_ok);
     lv.ivals.push_back(d);
     lv.ivals_n.push_back(res_len);
     lv.ivals_cnt.push_back(n);
@@ -5381,8 +5498,8 @@ int mgrit_hip_intervals_create(mgrit_hip_engine *e, int lvl, int n, const int32_
     return 0;
 }
 
-static int fused_level_check(mgrit_hip_engine *e, int lvl, int ivals_id, const char *what, bool level0_only, int partner = -1) {
-    int rc = check_level(e, lvl, true, partner);
+static int fused_level_check(mgrit_hip_engine *e, int lvl, int ivals_id, const char *what, bool level0_only, int partner = -1, int keep = 0) {
+    int rc = check_level(e, lvl, true, partner, keep);
     if (rc) return rc;
     if (lvl != 0 && level0_only) return fail(MGRIT_HIP_EUNSUPPORTED, "%s: level 0 only", what);
     if (lvl + 1 >= e->n_levels || !e->L[lvl + 1].set) return fail(MGRIT_HIP_EINVAL, "level %d has no coarser level", lvl);
@@ -5397,7 +5514,12 @@ static int fused_level_check(mgrit_hip_engine *e, int lvl, int ivals_id, const c
 }
 
 int mgrit_hip_cf_fas(mgrit_hip_engine *e, int lvl, int ivals_id, int pre_relaxed) {
-    int rc = fused_level_check(e, lvl, ivals_id, "fused C-F-relaxation + FAS residual", true);
+    // the partner of a lagging mgrit_hip_ec_relax_res (Level::lag): the same list with pre-relaxed C-points, deferring as below, reads
+    // them in the row the way up left them in and drops the record -- nobody asked for the corrected C-points, and they are gone for good.
+    // Anything else finds the rows put in place by check_level.
+    const bool lag_partner = e && lvl == 0 && pre_relaxed && ivals_id >= 0 && e->n_levels > 0 && e->L[0].lag == ivals_id && e->defer &&
+                             !has_links(e) && !capturing(e);
+    int rc = fused_level_check(e, lvl, ivals_id, "fused C-F-relaxation + FAS residual", true, -1, lag_partner ? LAG_KEEP : 0);
     if (rc) return rc;
     Level &lf = e->L[lvl], &lc = e->L[lvl + 1];
     const IntervalsDev &I = lf.ivals[ivals_id];
@@ -5421,14 +5543,22 @@ int mgrit_hip_cf_fas(mgrit_hip_engine *e, int lvl, int ivals_id, int pre_relaxed
         twin = twin_record(lc, TWIN_CFAS, ivals_id, both.slots, both.d_slots);
         if (lc.twin_recs[twin].missed) twin = -1;
     }
+    // Level::lag, P in row cend itself (lagged(0)): the kernels read one row further on (see the enum above). They store no level-0
+    // row (lag_partner implies defer) and use chunk_start_coarse for its sign alone; chunk_first has no negative entry. Rows read:
+    // cend and cstart of the list's intervals, inside the slab; every relaxed cstart a chunk begins with is a cend of the list
+    // (ivals_lag_ok: no other list ever lags), so the record holds P in that row too.
+    const bool row_ce = lag_partner && lf.lag_k == 0;
     IntervalsDev It = I;
+    LevelDev Lf = sched_dev(e, lf);
+    if (row_ce) { Lf.u += Lf.ld; It.chunk_start_coarse = I.chunk_first; }
     if (twin >= 0) It.keep = lf.ivals_both[ivals_id].d_keep;   // bit 0 cleared where both bits were set
     Timed timed(e, MGRIT_HIP_T_CF_FAS, lvl);
     rc = launch(q_regs ? cfasq_fn(lf.dev.T, coarse_lds) : cfas_fn(force_mode(lf), lf.dev.T), dim3(persistent_grid(lf, I.n_chunks)),
-                dim3(lf.dev.T), smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, It,
+                dim3(lf.dev.T), smem_bytes(lf.G, lf.dev.kind), e->stream, Lf, lc.dev, It,
                 !pre_relaxed ? 0 : defer ? (CFAS_PRE | CFAS_HELD) : CFAS_PRE);
     if (!rc) e->cfas_last = !q_regs ? 0 : coarse_lds ? 2 : 1;
-    if (!rc && defer) lf.held = ivals_id;
+    if (!rc && defer) { lf.held = ivals_id; lf.held_back = row_ce ? 0 : 1; }
+    if (!rc && lag_partner) lf.lag = -1;
     if (!rc && twin >= 0) lc.twin = twin;
     return rc;
 }
@@ -5465,9 +5595,17 @@ static int ec_relax_res_impl(mgrit_hip_engine *e, int lvl, int ivals_id, int sto
     Timed timed(e, MGRIT_HIP_T_EC_RELAX_RES, lvl);
     double *const *mirror = e->mirror_cur;   // null until mgrit_hip_cpoint_mirror has been called
     const bool held = lf.held == ivals_id;   // (only as the partner: check_level has settled every other pending list)
+    const int back = held ? lf.held_back : 0;   // rows back from cend where the uncorrected C-point sits
+    // Level::lag: under the conditions of Level::held -- one rank, outside a capture, store_all_f = 2 --, for a list whose chunks start
+    // from its own closing C-points (ivals_lag_ok, mgrit_hip_intervals_create), and by the engine's mode: always
+    // (2), or once the list has been the partner of a deferring way down lag_wait times in a row with no settle in between (1)
+    int &streak = lf.lag_streak[ivals_id];
+    const bool lag = store_all_f == 2 && lf.ivals_lag_ok[ivals_id] && !has_links(e) && !capturing(e) && (e->lag_mode == 2 || (e->lag_mode == 1 && held && streak >= lf.lag_wait));
+    streak = held ? streak + 1 : 0;
     rc = launch(ecfr_fn(force_mode(lf), false, lf.dev.T), grid, block, smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, I,
-                out, held ? (store_all_f | ECFR_HELD) : store_all_f, mirror, e->mirror_row0);
-    if (!rc && held) lf.held = -1;   // the pass has rewritten row cend and row cend-1 of every interval
+                out, store_all_f | (back ? ECFR_HELD : 0) | (lag ? ECFR_LAG : 0), mirror, e->mirror_row0);
+    if (!rc && held) { lf.held = -1; lf.held_back = 1; }   // the pass has read the pending rows and, unless it lags, rewritten row cend and row cend-1 of every interval
+    if (!rc && lag) { lf.lag = ivals_id; lf.lag_k = 1 - back; }
     return rc;
 }
 
@@ -5597,6 +5735,25 @@ int mgrit_hip_set_twin(mgrit_hip_engine *e, int mask) {
 
 int mgrit_hip_settle(mgrit_hip_engine *e, int lvl) { return check_level(e, lvl, false); }
 
+int mgrit_hip_lagged(mgrit_hip_engine *e, int lvl) {
+    if (!e) return fail(MGRIT_HIP_DEFERRED_BAD, "null engine");
+    if (lvl < 0 || lvl >= e->n_levels) return fail(MGRIT_HIP_DEFERRED_BAD, "level %d out of range [0,%d)", lvl, e->n_levels);
+    return e->L[lvl].lag;
+}
+
+int mgrit_hip_set_lag(mgrit_hip_engine *e, int mode) {
+    if (!e) return fail(MGRIT_HIP_EINVAL, "null engine");
+    if (mode < 0 || mode > 2) return fail(MGRIT_HIP_EINVAL, "lag mode %d: 0 = never, 1 = by the waiting rule, 2 = every way up that may", mode);
+    e->lag_mode = mode;   // (a record that is pending stays: its partner or the next entry point of the level deals with it)
+    return 0;
+}
+
+int mgrit_hip_lag_settle(mgrit_hip_engine *e, int lvl) {
+    if (!e) return fail(MGRIT_HIP_EINVAL, "null engine");
+    if (lvl < 0 || lvl >= e->n_levels) return fail(MGRIT_HIP_EINVAL, "level %d out of range [0,%d)", lvl, e->n_levels);
+    return lvl == 0 ? settle_lag(e) : 0;
+}
+
 int mgrit_hip_set_cfas_form(mgrit_hip_engine *e, int form) {
     if (!e) return fail(MGRIT_HIP_EINVAL, "null engine");
     if (form != 0 && form != 1) return fail(MGRIT_HIP_EINVAL, "cfas form %d: 0 = cfas_kernel always, 1 = cfasq_kernel where it applies", form);
@@ -5612,7 +5769,14 @@ int mgrit_hip_cfas_form(mgrit_hip_engine *e, int lvl) {
 
 int mgrit_hip_set_stream(mgrit_hip_engine *e, void *stream) {
     if (!e) return fail(MGRIT_HIP_EINVAL, "null engine");
-    e->stream = static_cast<hipStream_t>(stream);
+    // Level::lag outlives the cycle that left it, so a caller that moves the engine to another stream -- to capture the next cycle
+    // there, where nothing can be put in place -- gets the rows put in place on the stream the record's pass ran on, behind it
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (s != e->stream && e->n_levels > 1 && e->L[0].lag >= 0) {
+        const int rc = settle_lag(e);
+        if (rc) return rc;
+    }
+    e->stream = s;
     return 0;
 }
 
