@@ -36,7 +36,7 @@ typedef struct mgrit_hip_engine mgrit_hip_engine;
 enum { MGRIT_HIP_OK = 0, MGRIT_HIP_EINVAL = -1, MGRIT_HIP_EHIP = -2, MGRIT_HIP_ENODEV = -3, MGRIT_HIP_EUNSUPPORTED = -4 };
 enum { MGRIT_HIP_STEPPER_HEAT1D = 1, MGRIT_HIP_STEPPER_ADVECTION1D = 2, MGRIT_HIP_STEPPER_HEAT2D = 3,
        MGRIT_HIP_STEPPER_HEAT1D_2PTS = 4, MGRIT_HIP_STEPPER_ALLENCAHN2D = 5, MGRIT_HIP_STEPPER_GRAYSCOTT2D = 6,
-       MGRIT_HIP_STEPPER_CAHNHILLIARD2D = 7, MGRIT_HIP_STEPPER_BURGERS2D = 8 };
+       MGRIT_HIP_STEPPER_CAHNHILLIARD2D = 7, MGRIT_HIP_STEPPER_BURGERS2D = 8, MGRIT_HIP_STEPPER_NAVIERSTOKES2D = 9 };
 enum { MGRIT_HIP_TRANSFER_COPY = 0, MGRIT_HIP_TRANSFER_HEAT1D = 1, MGRIT_HIP_TRANSFER_PERIODIC1D = 2,
        /* the caller applies restriction / interpolation itself (a user's GridTransfer, reference core/grid_transfer.py:31-55:
           any Python code): mgrit_hip_restrict_u / _fas_rhs / _error_correction / _interpolate refuse the level pair, the FAS
@@ -141,6 +141,17 @@ int mgrit_hip_level_cahnhilliard2d(mgrit_hip_engine *e, int lvl, int n_pts_local
  * level holds: the Heat2D entry points, the copy transfer only, no time-parallel forward solve, norms over all 2 nx^2 values. */
 int mgrit_hip_level_burgers2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld,
                               double inv_dx2, double inv_2dx, double nu);
+/* NavierStokes2D with method = 'IMEX' (navier_stokes/navier_stokes.py; no reference class): incompressible flow in
+ * vorticity form on the periodic nx x nx grid, 4 <= nx <= 2048. A state row holds ONE plane, the vorticity w, n = nx^2, ld >= nx^2 a
+ * multiple of 16. Per step: psi = T ((T w T) o S) T with S = 1 / (lam_i + lam_j), S[0][0] = 0 (the stream function, L psi = -(w - mean w));
+ * b = w - dt (psi_y w_x - psi_x w_y) [+ dt f] with central differences times inv_2dx = 1 / (2 dx), indices mod nx; then
+ * (I - dt nu L) x = b through the Hartley tables of mgrit_hip_level_allencahn2d. Nine launches per Phi: four products, a stencil pass,
+ * four products. forcing: nx * nx doubles in natural order (f[i * nx + j], axis 0 = x), independent of time, copied before the call
+ * returns, or NULL. nu, inv_dx2, inv_2dx positive and finite, the forcing finite (MGRIT_HIP_EINVAL "bad Navier-Stokes parameters"
+ * otherwise). Everything said of an Allen-Cahn IMEX level holds: the Heat2D entry points, MGRIT_HIP_TRANSFER_COPY or
+ * MGRIT_HIP_TRANSFER_PERIODIC2D between two such levels, no time-parallel forward solve. */
+int mgrit_hip_level_navierstokes2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld,
+                                   double inv_dx2, double inv_2dx, double nu, const double *forcing);
 /* AllenCahn with method = 'IMPL' (theta = 1) or 'CN' (theta = 0.5) and linear_solver = 'pcg' (DESIGN.md 3.9): the level of
  * mgrit_hip_level_allencahn2d, whose Phi is Newton's method on x - fac (L x + r(x) / eps^2) = rhs, fac = theta dt, with every
  * correction by conjugate gradients preconditioned with (1 + fac nu / eps^2) I - fac L through the Hartley products. Per item: at most

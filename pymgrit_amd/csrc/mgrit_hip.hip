@@ -1694,6 +1694,8 @@ __global__ void interp_rows_kernel(double *__restrict__ uf, int f_ld, int T_f, c
 
 #include "mgrit_hip_burgers.inc"
 
+#include "mgrit_hip_navierstokes.inc"
+
 #include "mgrit_hip_cahnhilliard.inc"
 
 #include "mgrit_hip_transfer2d.inc"
@@ -1729,7 +1731,7 @@ struct PairList {
 };
 
 constexpr int H2D_MAX_BATCH = 1024;  // items per GEMM batch (work buffers: 2 x 1024 x Mi x Mj doubles; 2048 measured no faster)
-enum class H2DKind { HEAT2D, ALLENCAHN_IMEX, ALLENCAHN_NEWTON, GRAYSCOTT_IMEX, GRAYSCOTT_NEWTON, CAHNHILLIARD_IMEX, BURGERS_IMEX };   // what a level of the batched 2-D route steps with
+enum class H2DKind { HEAT2D, ALLENCAHN_IMEX, ALLENCAHN_NEWTON, GRAYSCOTT_IMEX, GRAYSCOTT_NEWTON, CAHNHILLIARD_IMEX, BURGERS_IMEX, NAVIERSTOKES_IMEX };   // what a level of the batched 2-D route steps with
 // What is a constant of a kind, one row per kind in the enum's order. The Newton columns (0 for the other kinds): the work rows of an
 // item, comps planes each -- Allen-Cahn PCG x, rhs, r, z, p, Jp, delta + the two operands of the preconditioner's
 // products; Gray-Scott BiCGStab (3.11) x, w, r, r^, p, v, s, y, delta + the same two, which between two sets of products carry
@@ -1755,6 +1757,7 @@ constexpr H2DKindRow H2D_KINDS[] = {
     {"Gray-Scott", true, 2, 2, false, 11, 6, 5, GSN_NB, newton_cap(2, 11), 2},
     {"Cahn-Hilliard", true, 1, 2, true, 0, 0, 0, 0, 0, 0},
     {"Burgers", true, 2, 2, false, 0, 0, 0, 0, 0, 0},
+    {"Navier-Stokes", true, 1, 1, true, 0, 0, 0, 0, 0, 0},
 };
 constexpr const H2DKindRow &kind_row(H2DKind k) { return H2D_KINDS[(int)k]; }
 static_assert(kind_row(H2DKind::ALLENCAHN_NEWTON).max_batch <= 256, "acn_reduce_kernel: one thread per item of a batch, one workgroup");
@@ -1783,7 +1786,9 @@ struct H2DHost {
     // Hartley table [P][P] (P = Mi = Mj = nx padded to 64), lx = ly = the periodic Laplacian's eigenvalues in natural mode order, no
     // rim, no fold. A Gray-Scott state row holds two planes [u | v], a D table per species, the right-hand side from both planes;
     // Cahn-Hilliard a [2][P][P] table (D1, D2); a Burgers row is two planes as well, one D table stored twice, the right-hand side
-    // from a stencil pass in front of the products (mgrit_hip_burgers.inc). The Newton kinds: the level's Phi is the Newton step over newton_state below.
+    // from a stencil pass in front of the products (mgrit_hip_burgers.inc); a Navier-Stokes row is one plane, the vorticity, with a
+    // second table S for the stream-function solve and a stencil pass between the two sets of products (mgrit_hip_navierstokes.inc).
+    // The Newton kinds: the level's Phi is the Newton step over newton_state below.
     H2DKind kind = H2DKind::HEAT2D;
     const H2DKindRow &row() const { return kind_row(kind); }
     bool periodic() const { return row().periodic; }
@@ -1796,6 +1801,8 @@ struct H2DHost {
     struct { double du = 0.0, dv = 0.0, a = 0.0, b = 0.0, inv_dx2 = 0.0; } gs;   // inv_dx2: the stencil of the Newton kernels
     struct { double eps2 = 0.0, stab = 0.0; } ch;
     struct { double nu = 0.0, inv_2dx = 0.0; } bg;
+    struct { double nu = 0.0, inv_2dx = 0.0; double *S = nullptr, *f = nullptr; } ns;   // S: the table of the stream-function solve
+                                                                                       // (ns_sinv), f: the forcing plane or null
     double *Wc0 = nullptr, *Wc1 = nullptr;   // one item each: the work buffers of the coarsest-level chain, which in a planned
                                              // cycle steps on a second stream BESIDE sweeps that apply this level's Phi too (the
                                              // coarse half of the FAS right-hand side of another block of time points)
@@ -2968,7 +2975,7 @@ void p2d_fill_dinv(const H2DHost &h, double *tab, double shift, double coef) {
 // Allen-Cahn IMEX 1 / (1 + dt (lam_a + lam_b)); Gray-Scott [2][P][P], species u then v, 1 / (1 + (dt d_c) (lam_a + lam_b)), the operand
 // order of GrayScott._dinv; Cahn-Hilliard [2][P][P], D1 = 1 / (1 + dt (eps^2 mu^2 + s mu)) then D2 = -(dt mu) D1, mu = lam_a + lam_b, the
 // operand order of CahnHilliard._tables; Burgers [2][P][P], the same D = 1 / (1 + (dt nu) (lam_a + lam_b)) twice (one per plane's item),
-// the operand order of Burgers2D._dinv
+// the operand order of Burgers2D._dinv; Navier-Stokes that D once, the operand order of NavierStokes2D._dinv
 int h2d_dinv(mgrit_hip_engine *e, Level &lv, uint64_t dtbits, double **out) {
     H2DHost &h = *lv.h2d;
     const size_t per = (size_t)h.dev.Mi * h.dev.Mj;
@@ -2996,9 +3003,27 @@ int h2d_dinv(mgrit_hip_engine *e, Level &lv, uint64_t dtbits, double **out) {
             p2d_fill_dinv(h, tab, 1.0, dt * h.bg.nu);
             p2d_fill_dinv(h, tab + per, 1.0, dt * h.bg.nu);
             break;
+        case H2DKind::NAVIERSTOKES_IMEX: p2d_fill_dinv(h, tab, 1.0, dt * h.ns.nu); break;
         default: p2d_fill_dinv(h, tab, 1.0, dt);   // Allen-Cahn (the Newton kinds have their own tables: newton_dinv)
         }
     }, out);
+}
+
+// S of a Navier-Stokes level's stream-function solve, [P][P], natural mode order: 1 / (lam_a + lam_b), 0 at mode (0, 0) -- the mean of
+// the vorticity never reaches psi -- and in the pads. It depends on the level only: made on first use, kept with the level
+// (the operand order of NavierStokes2D._sinv)
+int ns_sinv(mgrit_hip_engine *e, Level &lv, double **out) {
+    H2DHost &h = *lv.h2d;
+    if (!h.ns.S) {
+        std::vector<double> tab((size_t)h.dev.Mi * h.dev.Mj, 0.0);
+        for (int a = 0; a < h.dev.nx; ++a)
+            for (int b = 0; b < h.dev.nx; ++b)
+                if (a || b) tab[(size_t)a * h.dev.Mj + b] = 1.0 / (h.lx[a] + h.ly[b]);
+        int rc = dev_upload(lv, e->stream, tab, &h.ns.S);
+        if (rc) return rc;
+    }
+    *out = h.ns.S;
+    return 0;
 }
 
 // The four Hartley products of one batch on a periodic level (mgrit_hip_periodic2d.inc), PRE::operands work slab items per state:
@@ -3067,6 +3092,36 @@ int bg_products(mgrit_hip_engine *e, const H2DHost &h, int count, double dt, con
     launch(&p2d_gemm_kernel<P2D_PLAIN, GSPre>, W0, W1, nullptr, nofin);
     if (fin) launch(&p2d_gemm_kernel<P2D_FIN, GSPre>, W1, W0, nullptr, *fin);
     else launch(&p2d_gemm_kernel<P2D_PLAIN, GSPre>, W1, W0, nullptr, nofin);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// The nine launches of one Navier-Stokes batch, one work slab item per state. The stream-function solve: w of state b
+// staged from row idx[b] (NSPre, the identity) -> W0, W0 -> W1 (o sinv), W1 -> W0, W0 -> W1 = psi. The stencil pass forms b from the psi
+// items and the state rows into W0 (ns_rhs_kernel, whole items, pads zero). Then the products of p2d_products with nothing left to map:
+// W0 -> W1, W1 -> W0 (o dinv), W0 -> W1, and W1 through the sweep's arithmetic (fin) or into W0. The state rows are read by the first
+// and the fifth launch and written by the ninth only.
+int ns_products(mgrit_hip_engine *e, const H2DHost &h, int count, double dt, const double *src, const int32_t *idx, const double *sinv,
+                const double *dinv, double *W0, double *W1, const H2DFin *fin) {
+    const H2DDev &H = h.dev;
+    const int P = H.Mi;
+    const size_t per = (size_t)P * P;
+    const dim3 g(P / 64, P / 64, count);
+    const H2DFin nofin{};
+    const ACPre one{0.0, 0};   // (the one-plane instances of the work-slab modes: they stage nothing, pre is not applied)
+    auto launch = [&](auto kernel, const double *B, double *o, const double *d, const H2DFin &F) {
+        hipLaunchKernelGGL(kernel, g, dim3(256), 0, e->stream, h.T, P, h.KP, H.nx, B, o, d, per, idx, H.ld, one, H, F);
+    };
+    hipLaunchKernelGGL((p2d_gemm_kernel<P2D_FIRST, NSPre>), g, dim3(256), 0, e->stream, h.T, P, h.KP, H.nx, src, W0, nullptr, per, idx, H.ld, NSPre{}, H, nofin);
+    launch(&p2d_gemm_kernel<P2D_SCALE, ACPre>, W0, W1, sinv, nofin);
+    launch(&p2d_gemm_kernel<P2D_PLAIN, ACPre>, W1, W0, nullptr, nofin);
+    launch(&p2d_gemm_kernel<P2D_PLAIN, ACPre>, W0, W1, nullptr, nofin);
+    hipLaunchKernelGGL(ns_rhs_kernel, dim3(P / BG_TJ, P / BG_TI, count), dim3(256), 0, e->stream, H.nx, P, W1, src, idx, H.ld, h.ns.f, dt, h.ns.inv_2dx, W0, per);
+    launch(&p2d_gemm_kernel<P2D_PLAIN, ACPre>, W0, W1, nullptr, nofin);
+    launch(&p2d_gemm_kernel<P2D_SCALE, ACPre>, W1, W0, dinv, nofin);
+    launch(&p2d_gemm_kernel<P2D_PLAIN, ACPre>, W0, W1, nullptr, nofin);
+    if (fin) launch(&p2d_gemm_kernel<P2D_FIN, ACPre>, W1, W0, nullptr, *fin);
+    else launch(&p2d_gemm_kernel<P2D_PLAIN, ACPre>, W1, W0, nullptr, nofin);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -3340,6 +3395,11 @@ int h2d_phi_batch(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const dou
         switch (h.kind) {
         case H2DKind::GRAYSCOTT_IMEX: return p2d_products(e, h, pl.count, GSPre{dt, h.gs.a, h.gs.b, 0}, in_slab, pl.d_in, dinv, W0, W1, W0, fin);
         case H2DKind::BURGERS_IMEX: return bg_products(e, h, pl.count, dt, in_slab, pl.d_in, dinv, W0, W1, fin);
+        case H2DKind::NAVIERSTOKES_IMEX: {
+            double *sinv = nullptr;
+            if ((rc = ns_sinv(e, lv, &sinv))) return rc;
+            return ns_products(e, h, pl.count, dt, in_slab, pl.d_in, sinv, dinv, W0, W1, fin);
+        }
         case H2DKind::CAHNHILLIARD_IMEX: return ch_products(e, h, pl.count, CHPre{1.0 + h.ch.stab, 0}, in_slab, pl.d_in, dinv, W0, W1, fin);
         default: return p2d_products(e, h, pl.count, ACPre{dt * h.ac.inv_eps2, h.ac.nu}, in_slab, pl.d_in, dinv, W0, W1, W0, fin);
         }
@@ -4427,6 +4487,26 @@ int mgrit_hip_level_burgers2d(mgrit_hip_engine *e, int lvl, int n_pts_local, con
             return fail(MGRIT_HIP_EINVAL, "bad Burgers parameters (nu=%g, inv_dx2=%g, inv_2dx=%g must be positive and finite)", nu, inv_dx2, inv_2dx);
         return 0;
     }, [&](H2DHost *h) { h->bg = {nu, inv_2dx}; });
+}
+
+int mgrit_hip_level_navierstokes2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld, double inv_dx2,
+                                   double inv_2dx, double nu, const double *forcing) {
+    int rc = level_periodic2d(e, lvl, MGRIT_HIP_STEPPER_NAVIERSTOKES2D, H2DKind::NAVIERSTOKES_IMEX, n_pts_local, t_local, nx, ld, inv_dx2, "nx*nx", [&] {
+        if (!(inv_dx2 > 0.0) || !(inv_2dx > 0.0) || !(nu > 0.0) || !std::isfinite(inv_dx2) || !std::isfinite(inv_2dx) || !std::isfinite(nu))
+            return fail(MGRIT_HIP_EINVAL, "bad Navier-Stokes parameters (nu=%g, inv_dx2=%g, inv_2dx=%g must be positive and finite)", nu, inv_dx2, inv_2dx);
+        if (forcing)
+            for (size_t q = 0; q < (size_t)nx * nx; ++q)
+                if (!std::isfinite(forcing[q])) return fail(MGRIT_HIP_EINVAL, "bad Navier-Stokes parameters (the forcing is not finite at value %zu)", q);
+        return 0;
+    }, [&](H2DHost *h) { h->ns.nu = nu; h->ns.inv_2dx = inv_2dx; });
+    if (rc || !forcing) return rc;
+    // until the forcing is on the device the level counts as not described: a failed upload leaves an unusable level (whose pieces go
+    // with the engine), never one that steps without its forcing
+    Level &lv = e->L[lvl];
+    lv.set = false;
+    if ((rc = dev_upload(lv, e->stream, forcing, (size_t)nx * nx, &lv.h2d->ns.f))) return rc;
+    lv.set = true;
+    return 0;
 }
 
 int mgrit_hip_level_allencahn2d_newton(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld, double inv_dx2,
