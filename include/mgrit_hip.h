@@ -440,6 +440,33 @@ int mgrit_hip_settle(mgrit_hip_engine *e, int lvl);
 int mgrit_hip_set_lag(mgrit_hip_engine *e, int mode);
 int mgrit_hip_lagged(mgrit_hip_engine *e, int lvl);
 int mgrit_hip_lag_settle(mgrit_hip_engine *e, int lvl);
+/* The way up of levels 1 and 0 in one pass. When mgrit_hip_ec_relax(e, 1, runs) is followed by a level-0 way up that is known to lag
+ * (above), the call launches nothing and only notes the run list; mgrit_hip_ec_relax_res(e, 0, list, 2) then runs one kernel that
+ * computes u of level 1 where it needs it and stores no row of level 1. Until the next way down drops the record unread, u of level 1
+ * is NOT brought up: every other entry point that names level 0, 1 or 2 -- the record needs u of level 2, g of level 1 and the
+ * uncorrected rows of u of level 1 as the deferred call found them -- first gets the deferred pass launched as mgrit_hip_ec_relax
+ * would have launched it: bit for bit the rows of level 1 that the two passes leave, in front of whatever the entry point does to the
+ * lagged rows of level 0 (which stay pending for an entry point of level 2). So do mgrit_hip_settle of those levels,
+ * mgrit_hip_lag_settle(e, 0), mgrit_hip_up2_settle and mgrit_hip_set_stream to another stream. List constructors and calls that name
+ * no level leave the record pending; binding the slabs of levels 0 to 2 again drops it (and, behind the one-pass launch, the lagged
+ * list of level 0 with it). A caller that reads or writes u or g of level 1 or u of level 2 past the engine calls
+ * mgrit_hip_up2_settle first.
+ * Conditions: those of the lagging way up for the list the pending way down of level 0 has deferred, Heat1D with at most one separable
+ * forcing term on levels 0 and 1, the copy transfer and equal sizes on levels 0 to 2, no C-point mirror (mgrit_hip_cpoint_mirror: a
+ * mirrored row carries its padding, which the one-pass form fills with other values), and a run list and an interval list that pair:
+ * every F-point of a run closes exactly one interval whose predecessor in the same chunk closes on the point before it, no chunk
+ * starts on an F-point of a run, every corrected run start closes an interval or starts a chunk.
+ *   mgrit_hip_set_up2:     0 = never; 1 (default) = whenever the conditions hold. MGRIT_HIP_UP2=0|1 in the environment of
+ *                          mgrit_hip_create sets it. Anything else, a null engine: MGRIT_HIP_EINVAL. A pending record stays pending.
+ *   mgrit_hip_up2_pending: 0 = nothing pending, 1 = the level-1 way up is noted and nothing has run, 2 = the one-pass way up has run
+ *                          and u of level 1 is not brought up; MGRIT_HIP_DEFERRED_BAD for a null engine. Touches nothing.
+ *   mgrit_hip_up2_settle:  brings level 1 up from a pending record and nothing else: the lagged rows of level 0 stay as they are.
+ * Waiting rule (lag mode 1): bringing level 1 up behind a one-pass launch costs the deferred pass on top of it, so every such miss
+ * doubles a count (1, 2, 4, ... 64) of following ways up of level 1 that are not deferred. The count never shrinks in an engine's
+ * life, as the wait of the lagged list does not. Lag mode 2 defers whenever it may. */
+int mgrit_hip_set_up2(mgrit_hip_engine *e, int mode);
+int mgrit_hip_up2_settle(mgrit_hip_engine *e);
+int mgrit_hip_up2_pending(mgrit_hip_engine *e);
 /* The two forms of mgrit_hip_cf_fas. With pre_relaxed = 1 and ONE separable forcing term the pass keeps the level's forcing space
  * factor in LDS and q = Phi_{l+1}(C'_j) in registers (cfasq_kernel) instead of streaming the factor from L2 in every Phi with q
  * parked in LDS (cfas_kernel). Both store the same rows with the same bits, so only the query tells which one ran.

@@ -165,6 +165,7 @@ class HipBackend:
         self._cycle_pre = False   # the state at the start of the running cycle was 2 (begin_cycle)
         self._down_pending = False   # cf_fas has run with pre-relaxed C-points and the level-0 way up has not: the engine may hold
                                      # the closing C-points one row back (include/mgrit_hip.h, mgrit_hip_deferred) until then
+        self._up_open = False        # the way up of level 1 has run and may have been left to the level-0 way up (_up_in_place)
         self._lag_open = False       # the level-0 way up has run in the form that may leave the corrected C-points unstored
                                      # (include/mgrit_hip.h, mgrit_hip_lagged) and neither cf_fas nor a settle has followed
         self._twin_open = set()      # coarse levels whose rows of u the engine may hold back in v (include/mgrit_hip.h, mgrit_hip_twin):
@@ -388,7 +389,9 @@ class HipBackend:
         # (a write to v of a coarse level: a pending row of u takes its bits from v, so the rows are put in place first)
         mg.v.append(SlabVectorList(v, n, tmpl, self.perm[lvl], on_write=None if lvl == 0 else lambda lvl=lvl: self._coarse_rows_in_place(lvl))
                     if v is not None else None)
-        mg.g.append(SlabVectorList(g, n, tmpl, self.perm[lvl]) if g is not None else None)
+        # (g of level 1: the deferred way up of that level reads it, _coarse_g)
+        g_hook = (lambda lvl=lvl: self._coarse_g(lvl)) if lvl == 1 else None
+        mg.g.append(SlabVectorList(g, n, tmpl, self.perm[lvl], on_write=g_hook, on_read=g_hook) if g is not None else None)
         if mg.comm_time_rank == 0 and t_local.size:
             mg.u[lvl][0] = mg.problem[lvl].vector_t_start
 
@@ -582,16 +585,36 @@ class HipBackend:
         """in front of a torch read or write of u of a level >= 1 that no engine call stands before: between the pass that fills
         the level and the level's own first pass the engine may hold rows of u back in v (mgrit_hip_twin); outside that window
         nothing happens, and no engine call is made"""
+        if lvl in (1, 2):
+            self._up_in_place()     # (the way up of levels 1 and 0 in one pass, mgrit_hip_up2_pending: it has not brought u of level
+                                    # 1 up, and the pass that does so late reads u of level 2 as the cycle left it)
         if lvl in self._twin_open:
             hip_lib.settle(self.h, lvl)
             self._twin_open.discard(lvl)
+
+    def _coarse_g(self, lvl):
+        """in front of a torch read or write of g of level 1 that no engine call stands before: the deferred way up of level 1
+        (mgrit_hip_up2_pending) reads those rows"""
+        if lvl == 1:
+            self._up_in_place()
+
+    def _up_in_place(self):
+        """in front of a torch read of u or g of level 1 or of u of level 2, a write of g of level 1 or u of level 2, or a graph
+        replay, that no engine call stands before: where the ways up of levels 1 and 0 run as one pass the engine has not brought u
+        of level 1 up (mgrit_hip_up2_pending). Brings it up and nothing else -- corrected level-0 C-points that lag stay as they
+        are. _up_open is an upper bound, set behind every way up of level 1 and cleared behind cf_fas of level 0 (the record's
+        partner has dropped it, anything else has had level 1 brought up), a capture and this call"""
+        if self._up_open:
+            self._up_open = False
+            hip_lib.up2_settle(self.h)
 
     def _lag_in_place(self):
         """in front of a torch read of level-0 C-points, a torch write of u of level 1, or a graph replay, that no engine call stands
         before: behind the level-0 way up the engine may hold the corrected C-points back as two rows of level 0 and one of u of
         level 1 (mgrit_hip_lagged). Puts those rows in place and nothing else. _lag_open is an upper bound -- set behind every way
         up that MAY have lagged, not cleared by a settle the engine made on its own --, so the call may find nothing to do; with the
-        flag clear (behind cf_fas, materialise(), a capture, this call) none is made"""
+        flag clear (behind cf_fas, materialise(), a capture, this call) none is made.
+        (The engine's call also brings u of level 1 up first where the ways up of levels 1 and 0 ran as one pass: the record reads it.)"""
         if self._lag_open:
             self._lag_open = False
             hip_lib.lag_settle(self.h, 0)
@@ -601,6 +624,7 @@ class HipBackend:
         """the state slabs as they are -- level 0 possibly without its F-points (materialise()) -- with every stored C-point in
         place; the backend's own code reads self._Us behind the guards of its entry points"""
         self._lag_in_place()
+        self._up_in_place()
         return self._Us
 
     def _coarse_write(self, lvl):
@@ -625,6 +649,7 @@ class HipBackend:
         """the state slabs, level 0 with every F-point in place (tests, post-processing)"""
         self.materialise()
         self._lag_in_place()
+        self._up_in_place()
         for lvl in sorted(self._twin_open):
             self._coarse_rows_in_place(lvl)
         return self._Us
@@ -667,6 +692,8 @@ class HipBackend:
             self.materialise()
         if which == "u" and lvl > 0:
             self._coarse_rows_in_place(lvl)
+        if which == "g":
+            self._coarse_g(lvl)
         slab = {"u": self._Us, "v": self.V, "g": self.G}[which][lvl]
         return slab[:, self.perm[lvl]].cpu().numpy()
 
@@ -680,6 +707,8 @@ class HipBackend:
             self._coarse_rows_in_place(lvl)
         if which == "u" and lvl == 1:
             self._lag_in_place()
+        if which == "g":
+            self._coarse_g(lvl)
         slab = {"u": self._Us, "v": self.V, "g": self.G}[which][lvl]
         slab.zero_()
         slab[:, self.perm[lvl]] = torch.from_numpy(np.ascontiguousarray(values, dtype=np.float64)).to(slab.device)
@@ -900,6 +929,7 @@ class HipBackend:
                     self._f_stale = was
                     if gc_was_on:
                         gc.enable()
+                self._up_open = False
                 self._lag_open = False      # (nothing lags inside a capture, and the engine has put a record of the cycle before
                 state["graph"] = graph      # in place when it was moved to the capture stream: mgrit_hip_set_stream)
                 self._replay(state)
@@ -928,6 +958,7 @@ class HipBackend:
         # a replayed graph goes past the engine: its way down reads the rows a cycle that does not lag leaves, so a record that a
         # launch-by-launch cycle has left since the capture (timed sweeps, another plan of the same solver) is put in place first
         self._lag_in_place()
+        self._up_in_place()     # (likewise: the graph's way down would leave a record of level 1 pending over rows it rewrites)
         with torch.cuda.stream(self.stream):      # (the engine's stream, whatever the caller has made current since)
             state["graph"].replay()
         self._f_stale = max(self._f_stale, state.get("f_stale", 0))   # what the replayed launches did to the F-points
@@ -1296,6 +1327,8 @@ class HipBackend:
         if not triples:
             return
         check(self.lib.mgrit_hip_ec_relax(self.h, lvl, self._list_id("ecruns", lvl, triples)))
+        if lvl == 1 and not self.device_links:
+            self._up_open = True        # (the engine may have launched nothing and wait for the level-0 way up: mgrit_hip_up2_pending)
 
     # -- whole-level sweeps in one pass (include/mgrit_hip.h: mgrit_hip_cf_fas / mgrit_hip_ec_relax_res) -------------------
     def can_fuse_level(self, lvl):
@@ -1347,6 +1380,7 @@ class HipBackend:
             self._down_pending = self._down_pending or pre
             if lvl == 0:
                 self._lag_open = False      # (its partner has dropped the record, anything else has had the rows put in place)
+                self._up_open = False
 
     def ec_relax_res_to(self, lvl, intervals, buf):
         """several ranks: error_correction + f_relax + the residual sums of the rank's complete intervals (every F-point stored:

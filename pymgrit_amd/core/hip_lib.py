@@ -113,6 +113,9 @@ EXPORTS = {
     "mgrit_hip_set_lag": (C.c_int, [C.c_void_p, C.c_int]),
     "mgrit_hip_lagged": (C.c_int, [C.c_void_p, C.c_int]),
     "mgrit_hip_lag_settle": (C.c_int, [C.c_void_p, C.c_int]),
+    "mgrit_hip_set_up2": (C.c_int, [C.c_void_p, C.c_int]),
+    "mgrit_hip_up2_pending": (C.c_int, [C.c_void_p]),
+    "mgrit_hip_up2_settle": (C.c_int, [C.c_void_p]),
     "mgrit_hip_set_cfas_form": (C.c_int, [C.c_void_p, C.c_int]),
     "mgrit_hip_cfas_form": (C.c_int, [C.c_void_p, C.c_int]),
     "mgrit_hip_ec_relax_res_to": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
@@ -235,6 +238,24 @@ def lag_settle(h, lvl):
     """corrected C-points the level's way up has left unstored (include/mgrit_hip.h, mgrit_hip_lagged) are put in place, and
     nothing else: for a reader of the level-0 slab, or a writer of u of level 1, that goes past the engine"""
     check(load().mgrit_hip_lag_settle(h, int(lvl)))
+
+
+def set_up2(h, mode):
+    """0: the ways up of levels 1 and 0 as two passes; 1: as one pass whenever the level-0 way up lags (include/mgrit_hip.h,
+    mgrit_hip_set_up2)"""
+    check(load().mgrit_hip_set_up2(h, int(mode)))
+
+
+def up2_settle(h):
+    """u of level 1 is brought up where the ways up of levels 1 and 0 ran as one pass, and nothing else: for a reader of u or g of
+    level 1 or of u of level 2, or a writer of g of level 1 or u of level 2, that goes past the engine"""
+    check(load().mgrit_hip_up2_settle(h))
+
+
+def up2_pending(h):
+    """0: nothing pending; 1: the level-1 way up is noted and nothing has run; 2: the one-pass way up has run and u of level 1 is
+    not brought up (include/mgrit_hip.h, mgrit_hip_up2_pending)"""
+    return int(load().mgrit_hip_up2_pending(h))
 
 
 def newton_stats(h, lvl):

@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "mgrit_hip.h"
+#include "up2_table.h"
 
 namespace {
 
@@ -1428,6 +1429,126 @@ __global__ void __launch_bounds__(TB) ecfr_kernel(LevelDev L, LevelDev Lc, Inter
     wq.end(t);
 }
 
+// The way up of levels 1 and 0 in ONE pass (round 15, Level::up): ecfr_kernel<FORCE, false, true> with store_f = 2 and ECFR_LAG,
+// except that u^1 at the interval's closing point jc is not read from a row the level-1 way up (ecf_kernel) has stored but COMPUTED
+// here, in a second vector z that travels through the chunk beside x. code[it] (up2_table.h) says how:
+//   -2      jc is an F-point of the deferred level-1 run list: z = g^1_jc + Phi_1(z) from the z of the interval before (ecf_kernel's
+//           x = gi + x, same operand order; Phi_1 through phi_other_level, the bits of phi_apply on level 1, as in cfasq_kernel)
+//   j >= 0  jc is the C-point a deferred run starts from: z = c + (u^2_j - c), c = row jc of u^1 (ecf_kernel's expression)
+//   -1      anything else: row jc of u^1 as it stands
+// and zslot[k] / ccode[k] name the level-1 point z starts chunk k from -- the chunk's first C-point, or the point in front of the
+// first interval's F-point for the chunk that starts at the first point of the time grid -- and its code (never -2).
+// Per interval, in cfasq_kernel's order: the coarse Phi first, with x live beside it and the row of g^1 NOT in flight across it
+// (the one-word `touch` read in front, the row behind); then the m-1 F-steps and the residual Phi of level 0 at ONE call site
+// with z pinned as q is there; then P stored, A read, b = A + (z - A), the residual, x = b -- ecfr_kernel's rows (A from row
+// ce - held, P p_back rows back, the chunk start's A from v^1) and ecfr_kernel's bits. Two vectors live beside every Phi, never
+// three. Nothing is written on level 1 or 2: whoever wants to see u^1 gets ecf_kernel's pass run late (settle_up). 3.25 rows per
+// interval against 5.4 of the two passes.
+// No C-point mirror: a mirrored row carries its padding, and the padding of b here is not the two passes' (the closed-form coarse
+// Phi leaves other values there than ecf_kernel's table form; no reader of a slab sees them, a reader of raw mirror rows would),
+// so an engine with a mirror keeps the two passes.
+template <int FORCE, int TB = 1024, bool CLDS = false>
+__global__ void __launch_bounds__(TB) up2_kernel(LevelDev L, LevelDev Lc, const double *__restrict__ u2, int ld2, int stream2, IntervalsDev I,
+                                                   const int32_t *__restrict__ code, const int32_t *__restrict__ zslot,
+                                                   const int32_t *__restrict__ ccode, double *__restrict__ out, int held) {
+    constexpr int KIND = MGRIT_HIP_STEPPER_HEAT1D;
+    constexpr bool CF = FORCE == 4;   // forcing factor in LDS, so every Phi in closed form
+    WG_PROLOGUE_TB(TB);
+    (void)lane;
+    constexpr bool ONE = TB == LANES;   // one wave per state: Phi without the cross-group exchange (heat_solve)
+    const int p_back = 1 - held;        // rows back from ce where P goes (ECFR_LAG)
+    stage_forcing<FORCE>(sm, L, sl);
+    stage_other_level(sm, Lc, t);
+    for (wq.begin(L.sched, L.xcc0_limit, wgq_slot, t); wq.cur < I.n_chunks; wq.advance(t)) {
+        const int k = wq.cur;
+        wq.prefetch(t);
+        const int i0 = I.chunk_first[k], cnt = I.chunk_len[k];
+        double x[E], z[E];
+        {
+            const int cs = I.cstart[i0], js = I.chunk_start_coarse[k];
+            const int zs = __builtin_amdgcn_readfirstlane(zslot[k]), cj = __builtin_amdgcn_readfirstlane(ccode[k]);
+            if (zs >= 0) {   // u^1 at the point z starts from, as its code says
+                load_row_nt(Lc.u + (size_t)zs * Lc.ld, sl, z, Lc.stream_rows);
+                if (cj >= 0) {
+                    double w[E];
+                    load_row_nt(u2 + (size_t)cj * ld2, sl, w, stream2);
+#pragma unroll
+                    for (int e = 0; e < E; ++e) z[e] = z[e] + (w[e] - z[e]);
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < E; ++e) z[e] = 0.0;   // (no interval of the chunk steps from it: up2_table.h)
+            }
+            if (js >= 0) {   // the corrected value of the chunk's first C-point (zs == js), ecfr_kernel's expression
+                load_row_nt(Lc.v + (size_t)js * Lc.ld, sl, x, Lc.stream_rows);
+#pragma unroll
+                for (int e = 0; e < E; ++e) x[e] = x[e] + (z[e] - x[e]);
+            } else {
+                load_row_nt(L.u + (size_t)cs * L.ld, sl, x, L.stream_rows);
+            }
+        }
+        for (int it = i0; it < i0 + cnt; ++it) {
+            const int cs = I.cstart[it], ce = I.cend[it], jc = I.cend_coarse[it];
+            const int cd = __builtin_amdgcn_readfirstlane(code[it]);
+            int ti = t;   // the thread index of this item, opaque to the compiler (ffas_kernel)
+            asm volatile("" : "+v"(ti));
+            {   // u^1 at jc. ONE load of a level-1 row behind the only coarse Phi, for every code -- g^1_jc where the point is stepped to, the
+                // row of u^1 where it is not -- and a select: with the codes in two branches of their own the 1024-thread instance spilled
+                // 73 VGPRs, as it stands 11 (cfasq_kernel<1024, true>: 8)
+                const unsigned sj = slot0(ti);
+                const bool step = cd == -2;   // (wave-uniform)
+                const double *row = (step ? Lc.g : Lc.u) + (size_t)jc * Lc.ld;
+                int gtouch = 0;
+                if (step) {   // z = Phi_1(z); the row of g^1 is not in flight across it (the one-word read of every line: ffas_kernel)
+                    gtouch = reinterpret_cast<const int *>(row)[(wave << 11) + ((ti & 63) << 5)];
+                    phi_other_level<FORCE, false, ONE, CLDS>(z, ctx, Lc, jc, sm, sj, ti, ti & 63, wave, G);
+                }
+                asm volatile("" : : "v"(gtouch));   // (keeps the load above)
+#pragma unroll
+                for (int e = 0; e < E; ++e) asm volatile("" : "+v"(z[e]));
+                double r[E];
+                load_row_nt(row, sj, r, Lc.stream_rows);
+#pragma unroll
+                for (int e = 0; e < E; ++e) z[e] = step ? r[e] + z[e] : r[e];   // g^1_jc + Phi_1(z), ecf_kernel's operand order | the row
+                if (cd >= 0) {   // ecf_kernel's correction of the C-point its run starts from
+                    load_row_nt(u2 + (size_t)cd * ld2, sj, r, stream2);
+#pragma unroll
+                    for (int e = 0; e < E; ++e) z[e] = z[e] + (r[e] - z[e]);
+                }
+            }
+            // z is final here and is read again only behind the loop: pinned at both ends (cfasq_kernel's q)
+#pragma unroll
+            for (int e = 0; e < E; ++e) asm volatile("" : "+v"(z[e]));
+            load_coef(ctx.c, L.cs + (ctx.cur >= 0 ? ctx.cur : 0));   // back to this level's set (ctx.cur < 0: any set, phi_apply loads the right one)
+            asm volatile("" : "+v"(ti));   // (again: what the coarse Phi derived from the index is dead here)
+            const int li = ti & 63;
+            const unsigned si = slot0(ti);
+            int touch = 0;
+            for (int i = cs + 1; i <= ce; ++i) {   // the F-steps and the residual Phi
+                // A is wanted right behind the last Phi and not before it: ffas_kernel's one-word read of every line of the row
+                if (i == ce) touch = reinterpret_cast<const int *>(L.u + (size_t)(ce - held) * L.ld)[(wave << 11) + (li << 5)];
+                phi_apply<KIND, FORCE, CF, 0, false, ONE>(x, ctx, L, i, sm, ti, li, wave, G);
+            }
+            asm volatile("" : : "v"(touch));   // (keeps the load above)
+#pragma unroll
+            for (int e = 0; e < E; ++e) asm volatile("" : "+v"(z[e]));
+            store_row_nt(L.u + (size_t)(ce - p_back) * L.ld, si, x, L.stream_rows);   // P = Phi(last F-point): the next C-relaxation's value
+            double b[E];
+            load_row_nt(L.u + (size_t)(ce - held) * L.ld, si, b, L.stream_rows);
+#pragma unroll
+            for (int e = 0; e < E; ++e) b[e] = b[e] + (z[e] - b[e]);
+            const int rp = I.res_pos[it];
+#pragma unroll
+            for (int e = 0; e < E; ++e) x[e] = x[e] - b[e];
+            const double tot = block_sumsq(x, sm, L.n, ti, li, wave, G);
+            if (ti == 0) out[rp] = tot;
+#pragma unroll
+            for (int e = 0; e < E; ++e) x[e] = b[e];
+        }
+    }
+    wq.end(t);
+}
+
 // The same sweep in ONE pass per C-point for Heat1D (both levels of the pair): fine Phi with the fine level's tables in LDS
 // as everywhere else, then the coarse Phi with the coarse level's correction table, Pt and forcing factors read straight
 // from global memory -- 144 KB per level that every workgroup reads, so they stay in L2 and cost no HBM traffic -- and the
@@ -1716,7 +1837,7 @@ struct BatchPlans { std::vector<BatchPlan> plans; bool built = false; };
 struct RunList {
     int n = 0;
     int32_t *d_start = nullptr, *d_len = nullptr, *d_ec = nullptr;  // d_ec: mgrit_hip_ec_runs_create only
-    std::vector<int32_t> h_start, h_len;
+    std::vector<int32_t> h_start, h_len, h_ec;   // h_ec: mgrit_hip_ec_runs_create only
     BatchPlans relax, points;
 };
 struct PairList {
@@ -1948,6 +2069,20 @@ struct Level {
     // the corrected value is A + (u^{l+1} - A) (settle_lag_kernel). mgrit_hip_cf_fas with the same list reads P where it is and drops the
     // record; every other entry point that names this level or the next one gets the rows put in place first (check_level).
     int lag = -1, lag_k = 0;
+    // Level::up (round 15), kept on level 1: mgrit_hip_ec_relax of run list `up` has launched nothing, because the level-0 way up
+    // of interval list up_ivals that follows it lags and computes u^1 where it needs it (up2_kernel). up_done: that pass has run and
+    // Level::lag of level 0 is pending with u^1 NOT brought up -- it stays at most as long as the lag record. Everybody but the
+    // partner gets ecf_kernel's pass launched late (settle_up, check_level of levels 0 to 2), in front of a settle of the lag record.
+    int up = -1, up_ivals = -1;
+    bool up_done = false;
+    // its waiting rule (lag mode 1): bringing level 1 up behind a fused launch costs the whole deferred pass on top of the fused one,
+    // so every such miss doubles up_wait (up to 64) and the next up_wait ways up of level 1 are not deferred. Like lag_wait it
+    // never shrinks: a caller that has looked keeps paying less often, not more
+    int up_wait = 1, up_skip = 0;
+    struct Up2Dev { bool pairs = false; const int32_t *d_code = nullptr, *d_zslot = nullptr, *d_ccode = nullptr; };
+    struct IvalsHost { std::vector<int32_t> cend_coarse, chunk_first, chunk_len, chunk_start_coarse; };
+    std::vector<IvalsHost> ivals_host;                 // per interval list: what the pairing table is worked out from
+    std::map<std::pair<int, int>, Up2Dev> up_tables;  // (run list of level 1, interval list of level 0) -> the pairing table (up2_table.h)
     // the waiting rule of mode 1: a settle of a lagged list costs 3-5 rows per interval and a lagged cycle saves one, so a list lags only
     // after lag_wait consecutive way ups as the partner of a deferring way down, and every such settle doubles lag_wait (up to 64)
     int lag_wait = 2;
@@ -2004,6 +2139,7 @@ struct mgrit_hip_engine {
                                   // rows of u^{l+1} whose bits sit in v^{l+1} (Level::twin). Bit 0 is off by default: alone it did not
                                   // show a gain beyond run-to-run noise on the flagship shape
     int lag_mode = 1;             // mgrit_hip_set_lag / MGRIT_HIP_LAG: 0 never, 1 by the waiting rule, 2 every way up that may (Level::lag)
+    int up2_mode = 1;             // mgrit_hip_set_up2 / MGRIT_HIP_UP2: 0 never, 1 the way up of levels 1 and 0 in one pass whenever it lags (Level::up)
     int cfas_form = 1;            // mgrit_hip_set_cfas_form / MGRIT_HIP_CFAS_FORM: 0 always cfas_kernel, 1 cfasq_kernel where it applies
     int cfas_last = -1;           // mgrit_hip_cfas_form: the form level 0's last mgrit_hip_cf_fas launched (-1: none yet)
     int fas_chunk = 0;            // mgrit_hip_set_fas_chunk: -1 fas_fused1_kernel, 0 chunks by the library's rule, n > 0 chunks of n
@@ -2399,6 +2535,15 @@ auto ecfr_fn(int fm, bool use_g, int T) {
     });
 }
 
+// the way up of levels 1 and 0 in one pass: no forcing, or one term with the factor in LDS (coarse_lds: level 1 reads that copy too)
+using Up2Fn = decltype(&up2_kernel<0>);
+Up2Fn up2_fn(int fm, int T, bool coarse_lds) {
+    return pick<LANES, 512, 1024>(instance_tb(T, true), [&](auto TB) -> Up2Fn {
+        if (fm == 0) return &up2_kernel<0, TB, false>;
+        return coarse_lds ? &up2_kernel<4, TB, true> : &up2_kernel<4, TB, false>;
+    });
+}
+
 auto gen_down_fn(int kind, int fm, bool use_g, int T) {
     return by_stepper(kind, fm, [&](auto K, auto F) {
         return pick<512, 1024>(instance_tb(T, false), [&](auto TB) {
@@ -2646,7 +2791,11 @@ int twin_record(Level &lc, int kind, int list, const std::vector<int32_t> &slots
 // TWIN_KEEP_OWN / TWIN_KEEP_BELOW: the caller leaves the pending record of the level itself / of the next coarser level alone -- it is
 // the record's partner, its producer's own bookkeeping, or it touches no row of either level (list constructors).
 // LAG_KEEP: likewise for Level::lag of level 0 -- mgrit_hip_cf_fas as its partner, list constructors, a pair-list copy of other rows.
-enum { TWIN_KEEP_OWN = 1, TWIN_KEEP_BELOW = 2, LAG_KEEP = 4, KEEP_ALL = 7 };
+// UP_KEEP: likewise for Level::up of level 1 -- the lagging level-0 way up it waits for, the way down that drops it unread, list
+// constructors. Nobody else: the record needs u^2, g^1 and the uncorrected rows of u^1 as the deferred pass would have found them.
+enum { TWIN_KEEP_OWN = 1, TWIN_KEEP_BELOW = 2, LAG_KEEP = 4, UP_KEEP = 8, KEEP_ALL = 15 };
+
+int settle_up(mgrit_hip_engine *e);   // (behind the launch helpers it needs)
 
 // partner: the interval list whose pending rows (Level::held) the caller reads where they are; any other pending list is settled.
 // Level::twin: an entry point of level lvl may read u of lvl and of lvl + 1, so both levels' records are settled unless twin_keep says
@@ -2659,6 +2808,7 @@ int check_level(mgrit_hip_engine *e, int lvl, bool need_set = true, int partner 
     int rc;
     if (!(twin_keep & TWIN_KEEP_OWN) && e->L[lvl].twin >= 0 && (rc = settle_twin(e, lvl))) return rc;
     if (!(twin_keep & TWIN_KEEP_BELOW) && lvl + 1 < e->n_levels && e->L[lvl + 1].twin >= 0 && (rc = settle_twin(e, lvl + 1))) return rc;
+    if (!(twin_keep & UP_KEEP) && lvl <= 2 && (rc = settle_up(e))) return rc;
     if (!(twin_keep & LAG_KEEP) && lvl <= 1 && e->L[0].lag >= 0 && (rc = settle_lag(e))) return rc;
     if (e->L[lvl].held >= 0 && e->L[lvl].held != partner) return settle_held(e, lvl);
     return 0;
@@ -3863,6 +4013,70 @@ LevelDev sched_dev(const mgrit_hip_engine *e, const Level &lv) {
     return d;
 }
 
+// mgrit_hip_ec_relax's launch (the arguments checked by the caller), recorded as ec_relax of the level
+int ec_relax_launch(mgrit_hip_engine *e, int lvl, const RunList &rl) {
+    Level &lf = e->L[lvl], &lc = e->L[lvl + 1];
+    Timed timed(e, MGRIT_HIP_T_EC_RELAX, lvl);
+    return launch(ecf_fn(lf.dev.kind, force_mode(lf), lvl > 0, lf.dev.T), dim3(persistent_grid(lf, rl.n)), dim3(lf.dev.T),
+                  smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, rl.d_start, rl.d_len, rl.d_ec, rl.n);
+}
+
+// Level::up of level 1: the deferred ecf_kernel pass is launched exactly as mgrit_hip_ec_relax would have launched it -- u^2, g^1 and
+// the uncorrected rows of u^1 are as that call found them, every entry point that could change one comes through here first. The
+// rows of level 1 are then bit for bit what the two passes leave, and behind a fused launch (up_done) Level::lag of level 0 finds the
+// row of u^1 it speaks of in place: it stays pending for its own partner or settle (check_level settles this record first).
+int settle_up(mgrit_hip_engine *e) {
+    if (e->n_levels < 3 || e->L[1].up < 0) return 0;
+    Level &l1 = e->L[1];
+    if (capturing(e)) return fail(MGRIT_HIP_EINVAL, "level 1 has its way up pending (run list %d) inside a stream capture", l1.up);
+    const int rc = ec_relax_launch(e, 1, l1.runs[l1.up]);
+    if (rc) return rc;
+    if (l1.up_done) {   // a miss: somebody looked at level 1 behind the one-pass way up
+        l1.up_wait = std::min(2 * l1.up_wait, 64);
+        l1.up_skip = l1.up_wait;
+    }
+    l1.up = l1.up_ivals = -1;
+    l1.up_done = false;
+    return 0;
+}
+
+// What ec_relax_res_impl will decide for mgrit_hip_ec_relax_res(e, 0, ivals_id, 2) as the partner of the pending way down: it lags
+bool will_lag(mgrit_hip_engine *e, int ivals_id) {
+    Level &lf = e->L[0];
+    if (ivals_id < 0 || ivals_id >= (int)lf.ivals.size() || lf.held != ivals_id) return false;
+    const auto streak = lf.lag_streak.find(ivals_id);
+    return lf.ivals_lag_ok[ivals_id] && !has_links(e) && !capturing(e) &&
+           (e->lag_mode == 2 || (e->lag_mode == 1 && streak != lf.lag_streak.end() && streak->second >= lf.lag_wait));
+}
+
+// the pairing table of (run list of level 1, interval list of level 0), worked out and uploaded once (up2_table.h)
+int up2_table(mgrit_hip_engine *e, int runs_id, int ivals_id, const Level::Up2Dev **out) {
+    Level &l0 = e->L[0], &l1 = e->L[1];
+    const auto key = std::make_pair(runs_id, ivals_id);
+    auto seen = l1.up_tables.find(key);
+    if (seen == l1.up_tables.end()) {
+        const RunList &rl = l1.runs[runs_id];
+        const Level::IvalsHost &ih = l0.ivals_host[ivals_id];
+        const up2::Table tab = up2::build_table(l1.dev.n_pts, rl.n, rl.h_start.data(), rl.h_len.data(), rl.h_ec.data(), (int)ih.cend_coarse.size(),
+                                                ih.cend_coarse.data(), (int)ih.chunk_first.size(), ih.chunk_first.data(), ih.chunk_len.data(),
+                                                ih.chunk_start_coarse.data());
+        Level::Up2Dev d;
+        d.pairs = tab.pairs;
+        if (tab.pairs) {
+            // (every code >= 0 is an ec_coarse of the run list, inside u^2: mgrit_hip_ec_runs_create)
+            int32_t *pc = nullptr, *pz = nullptr, *pk = nullptr;
+            int rc;
+            if ((rc = dev_upload(l1, e->stream, tab.code, &pc)) || (rc = dev_upload(l1, e->stream, tab.chunk_slot, &pz)) ||
+                (rc = dev_upload(l1, e->stream, tab.chunk_code, &pk)))
+                return rc;
+            d.d_code = pc; d.d_zslot = pz; d.d_ccode = pk;
+        }
+        seen = l1.up_tables.emplace(key, d).first;
+    }
+    *out = &seen->second;
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Time-parallel forward solve (mgrit_hip_blk.inc): the rule and the tables. The oracle's
 // orc_block_solve_rank / heat1d_block_solve_spec state the same arithmetic independently.
@@ -4263,6 +4477,8 @@ int mgrit_hip_create(mgrit_hip_engine **out, int n_levels, void *stream) {
         if (s && s[0] >= '0' && s[0] <= '3' && !s[1]) e->twin_mask = s[0] - '0';
         s = std::getenv("MGRIT_HIP_LAG");            // "0" .. "2": mgrit_hip_set_lag
         if (s && s[0] >= '0' && s[0] <= '2' && !s[1]) e->lag_mode = s[0] - '0';
+        s = std::getenv("MGRIT_HIP_UP2");            // "0" / "1": mgrit_hip_set_up2
+        if (s && (s[0] == '0' || s[0] == '1') && !s[1]) e->up2_mode = s[0] - '0';
     }
     e->stream = static_cast<hipStream_t>(stream);
     e->L.resize(n_levels);
@@ -4556,6 +4772,11 @@ int mgrit_hip_newton_stats(mgrit_hip_engine *e, int lvl, int64_t out[4]) {
 int mgrit_hip_level_bind(mgrit_hip_engine *e, int lvl, double *u, double *v, double *g) {
     if (e && lvl >= 0 && lvl < e->n_levels) e->L[lvl].twin = -1;   // the slabs the record spoke of are no longer the level's
     if (e && lvl >= 0 && lvl <= 1 && lvl < e->n_levels) e->L[0].lag = -1;   // (Level::lag speaks of u of level 0 and of level 1)
+    if (e && lvl >= 0 && lvl <= 2 && lvl < e->n_levels && e->n_levels >= 3 && e->L[1].up >= 0) {   // (Level::up speaks of slabs of levels 0 to 2)
+        if (e->L[1].up_done) e->L[0].lag = -1;   // ... and the lag record behind it of a u^1 that is not there
+        e->L[1].up = e->L[1].up_ivals = -1;
+        e->L[1].up_done = false;
+    }
     int rc = check_level(e, lvl);
     if (rc) return rc;
     if (!u && e->L[lvl].dev.n_pts > 0) return fail(MGRIT_HIP_EINVAL, "u slab is null");
@@ -5390,7 +5611,44 @@ int mgrit_hip_ec_runs_create(mgrit_hip_engine *e, int lvl, int n_runs, const int
     for (int r = 0; r < n_runs; ++r)
         if (coarse_idx[r] < -1 || coarse_idx[r] >= e->L[lvl + 1].dev.n_pts)
             return fail(MGRIT_HIP_EINVAL, "run %d: coarse slot %d outside [-1,%d)", r, coarse_idx[r], e->L[lvl + 1].dev.n_pts);
+    lv.runs[*id_out].h_ec.assign(coarse_idx, coarse_idx + n_runs);
     return dev_upload(lv, e->stream, coarse_idx, (size_t)n_runs, &lv.runs[*id_out].d_ec);
+}
+
+// Level::up: the way up of level 1 waits for the level-0 way up that follows it when that one is known to lag (see the record)
+static bool up2_defers(mgrit_hip_engine *e, int lvl, int ec_runs_id) {
+    if (lvl != 1 || e->up2_mode != 1 || e->n_levels < 3 || !e->defer || has_links(e) || capturing(e) || e->mirror_cur) return false;
+    Level &l0 = e->L[0], &l1 = e->L[1], &l2 = e->L[2];
+    const int I = l0.held;
+    if (I < 0 || !will_lag(e, I) || l0.lag >= 0 || l0.ivals[I].n_chunks == 0) return false;
+    const int fm = force_mode(l0);
+    if (l0.dev.kind != MGRIT_HIP_STEPPER_HEAT1D || l1.dev.kind != MGRIT_HIP_STEPPER_HEAT1D || l0.transfer != MGRIT_HIP_TRANSFER_COPY ||
+        l1.transfer != MGRIT_HIP_TRANSFER_COPY || l0.dev.n != l1.dev.n || l1.dev.n != l2.dev.n || l0.dev.T != l1.dev.T || l0.dev.ld != l1.dev.ld ||
+        l0.dev.ld != l2.dev.ld || fm != force_mode(l1) || fm > 1 || batched(l0) || batched(l1) || !l0.dev.u || !l1.dev.u || !l1.dev.v ||
+        !l1.dev.g || !l2.dev.u)
+        return false;
+    const Level::Up2Dev *tab = nullptr;
+    if (up2_table(e, ec_runs_id, I, &tab) || !tab->pairs) return false;
+    if (e->lag_mode == 1 && l1.up_skip > 0) { --l1.up_skip; return false; }   // (the waiting rule of Level::up)
+    return true;
+}
+
+int mgrit_hip_up2_pending(mgrit_hip_engine *e) {
+    if (!e) return fail(MGRIT_HIP_DEFERRED_BAD, "null engine");
+    if (e->n_levels < 3 || e->L[1].up < 0) return 0;
+    return e->L[1].up_done ? 2 : 1;
+}
+
+int mgrit_hip_up2_settle(mgrit_hip_engine *e) {
+    if (!e) return fail(MGRIT_HIP_EINVAL, "null engine");
+    return settle_up(e);
+}
+
+int mgrit_hip_set_up2(mgrit_hip_engine *e, int mode) {
+    if (!e) return fail(MGRIT_HIP_EINVAL, "null engine");
+    if (mode != 0 && mode != 1) return fail(MGRIT_HIP_EINVAL, "up2 mode %d: 0 = never, 1 = levels 1 and 0 in one pass whenever the way up lags", mode);
+    e->up2_mode = mode;   // (a record that is pending stays: its partner or the next entry point of levels 0 to 2 deals with it)
+    return 0;
 }
 
 int mgrit_hip_ec_relax(mgrit_hip_engine *e, int lvl, int ec_runs_id) {
@@ -5404,9 +5662,13 @@ int mgrit_hip_ec_relax(mgrit_hip_engine *e, int lvl, int ec_runs_id) {
         return fail(MGRIT_HIP_EUNSUPPORTED, "fused correction + F-relaxation needs 1-D steppers and the copy transfer");
     if ((rc = no_wide(lf, &lc, "fused correction + F-relaxation"))) return rc;
     if (rl->n == 0) return 0;
-    Timed timed(e, MGRIT_HIP_T_EC_RELAX, lvl);
-    return launch(ecf_fn(lf.dev.kind, force_mode(lf), lvl > 0, lf.dev.T), dim3(persistent_grid(lf, rl->n)), dim3(lf.dev.T),
-                  smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, rl->d_start, rl->d_len, rl->d_ec, rl->n);
+    if (up2_defers(e, lvl, ec_runs_id)) {   // nothing launched, nothing recorded: the level-0 way up takes this pass along
+        lf.up = ec_runs_id;
+        lf.up_ivals = e->L[0].held;
+        lf.up_done = false;
+        return 0;
+    }
+    return ec_relax_launch(e, lvl, *rl);
 }
 
 // Host read-back of per-run scalars without any copy command: the kernels store straight into pinned, device-mapped
@@ -5571,6 +5833,7 @@ int mgrit_hip_intervals_create(mgrit_hip_engine *e, int lvl, int n, const int32_
     for (size_t k = 0; k < cf.size() && lag_ok; ++k)
         lag_ok = cc[k] < 0 || std::binary_search(ends.begin(), ends.end(), cstart[cf[k]]);
     lv.ivals_lag_ok.push_back(lag_ok);
+    lv.ivals_host.push_back(Level::IvalsHost{std::vector<int32_t>(cend_coarse, cend_coarse + n), cf, cl, cc});
     lv.ivals.push_back(d);
     lv.ivals_n.push_back(res_len);
     lv.ivals_cnt.push_back(n);
@@ -5599,7 +5862,9 @@ int mgrit_hip_cf_fas(mgrit_hip_engine *e, int lvl, int ivals_id, int pre_relaxed
     // Anything else finds the rows put in place by check_level.
     const bool lag_partner = e && lvl == 0 && pre_relaxed && ivals_id >= 0 && e->n_levels > 0 && e->L[0].lag == ivals_id && e->defer &&
                              !has_links(e) && !capturing(e);
-    int rc = fused_level_check(e, lvl, ivals_id, "fused C-F-relaxation + FAS residual", true, -1, lag_partner ? LAG_KEEP : 0);
+    // (Level::up behind a fused way up goes with it: u^1 is not brought up, this pass and the level-1 way down overwrite what they need of it)
+    const bool up_drop = lag_partner && e->n_levels >= 3 && e->L[1].up >= 0 && e->L[1].up_done;
+    int rc = fused_level_check(e, lvl, ivals_id, "fused C-F-relaxation + FAS residual", true, -1, lag_partner ? (up_drop ? LAG_KEEP | UP_KEEP : LAG_KEEP) : 0);
     if (rc) return rc;
     Level &lf = e->L[lvl], &lc = e->L[lvl + 1];
     const IntervalsDev &I = lf.ivals[ivals_id];
@@ -5639,6 +5904,7 @@ int mgrit_hip_cf_fas(mgrit_hip_engine *e, int lvl, int ivals_id, int pre_relaxed
     if (!rc) e->cfas_last = !q_regs ? 0 : coarse_lds ? 2 : 1;
     if (!rc && defer) { lf.held = ivals_id; lf.held_back = row_ce ? 0 : 1; }
     if (!rc && lag_partner) lf.lag = -1;
+    if (!rc && up_drop) { lc.up = lc.up_ivals = -1; lc.up_done = false; }
     if (!rc && twin >= 0) lc.twin = twin;
     return rc;
 }
@@ -5658,7 +5924,9 @@ static int ec_relax_res_impl(mgrit_hip_engine *e, int lvl, int ivals_id, int sto
     // the partner of a deferring mgrit_hip_cf_fas: the same list on level 0 with store_all_f = 2, outside a capture, reads the
     // pending rows where they are; anything else finds them put in place by check_level
     const bool partner = e && lvl == 0 && store_all_f == 2 && ivals_id >= 0 && e->n_levels > 0 && e->L[0].held == ivals_id && !capturing(e);
-    int rc = fused_level_check(e, lvl, ivals_id, "fused correction + F-relaxation + residual", false, partner ? ivals_id : -1);
+    // ... and the partner of a deferred level-1 way up (Level::up) that was noted for this very list, when the pass still lags
+    const bool up_partner = partner && e->n_levels >= 3 && e->L[1].up >= 0 && !e->L[1].up_done && e->L[1].up_ivals == ivals_id && !e->mirror_cur && will_lag(e, ivals_id);
+    int rc = fused_level_check(e, lvl, ivals_id, "fused correction + F-relaxation + residual", false, partner ? ivals_id : -1, up_partner ? UP_KEEP : 0);
     if (rc) return rc;
     Level &lf = e->L[lvl], &lc = e->L[lvl + 1];
     const IntervalsDev &I = lf.ivals[ivals_id];
@@ -5682,8 +5950,19 @@ static int ec_relax_res_impl(mgrit_hip_engine *e, int lvl, int ivals_id, int sto
     int &streak = lf.lag_streak[ivals_id];
     const bool lag = store_all_f == 2 && lf.ivals_lag_ok[ivals_id] && !has_links(e) && !capturing(e) && (e->lag_mode == 2 || (e->lag_mode == 1 && held && streak >= lf.lag_wait));
     streak = held ? streak + 1 : 0;
-    rc = launch(ecfr_fn(force_mode(lf), false, lf.dev.T), grid, block, smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, I,
-                out, store_all_f | (back ? ECFR_HELD : 0) | (lag ? ECFR_LAG : 0), mirror, e->mirror_row0);
+    const Level::Up2Dev *up_tab = nullptr;
+    if (up_partner) {   // (it lags: will_lag is the very predicate of `lag` above)
+        if ((rc = up2_table(e, lc.up, ivals_id, &up_tab))) return rc;
+    }
+    if (up_tab) {   // Level::up: both levels' ways up in one pass, u^1 computed where the pass needs it and stored nowhere
+        const Level &l2 = e->L[2];
+        rc = launch(up2_fn(force_mode(lf), lf.dev.T, force_mode(lf) == 1 && same_factor_below(lf, lc)), grid, block, smem_bytes(lf.G, lf.dev.kind),
+                    e->stream, sched_dev(e, lf), lc.dev, (const double *)l2.dev.u, l2.dev.ld, l2.dev.stream_rows, I, up_tab->d_code, up_tab->d_zslot, up_tab->d_ccode,
+                    out, back);
+        if (!rc) lc.up_done = true;
+    } else
+        rc = launch(ecfr_fn(force_mode(lf), false, lf.dev.T), grid, block, smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, I,
+                    out, store_all_f | (back ? ECFR_HELD : 0) | (lag ? ECFR_LAG : 0), mirror, e->mirror_row0);
     if (!rc && held) { lf.held = -1; lf.held_back = 1; }   // the pass has read the pending rows and, unless it lags, rewritten row cend and row cend-1 of every interval
     if (!rc && lag) { lf.lag = ivals_id; lf.lag_k = 1 - back; }
     return rc;
@@ -5831,7 +6110,9 @@ int mgrit_hip_set_lag(mgrit_hip_engine *e, int mode) {
 int mgrit_hip_lag_settle(mgrit_hip_engine *e, int lvl) {
     if (!e) return fail(MGRIT_HIP_EINVAL, "null engine");
     if (lvl < 0 || lvl >= e->n_levels) return fail(MGRIT_HIP_EINVAL, "level %d out of range [0,%d)", lvl, e->n_levels);
-    return lvl == 0 ? settle_lag(e) : 0;
+    if (lvl != 0) return 0;
+    const int rc = settle_up(e);   // (Level::up: u^1 first, the lag record reads it)
+    return rc ? rc : settle_lag(e);
 }
 
 int mgrit_hip_set_cfas_form(mgrit_hip_engine *e, int form) {
@@ -5852,6 +6133,10 @@ int mgrit_hip_set_stream(mgrit_hip_engine *e, void *stream) {
     // Level::lag outlives the cycle that left it, so a caller that moves the engine to another stream -- to capture the next cycle
     // there, where nothing can be put in place -- gets the rows put in place on the stream the record's pass ran on, behind it
     hipStream_t s = static_cast<hipStream_t>(stream);
+    if (s != e->stream) {
+        const int rc = settle_up(e);   // (Level::up likewise, in front of the lag record that reads u^1)
+        if (rc) return rc;
+    }
     if (s != e->stream && e->n_levels > 1 && e->L[0].lag >= 0) {
         const int rc = settle_lag(e);
         if (rc) return rc;
