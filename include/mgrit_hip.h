@@ -118,7 +118,8 @@ int mgrit_hip_level_allencahn2d(mgrit_hip_engine *e, int lvl, int n_pts_local, c
  * ld >= 2 nx^2 a multiple of 16. b_u = u + dt (a (1 - u) - u v^2), b_v = v + dt (u v^2 - b v), then (I - dt d_c L) x_c = b_c per species
  * through the Hartley tables of mgrit_hip_level_allencahn2d with one D table per species, both species in one set of four batched
  * products. du, dv > 0; a, b finite. Everything said of an Allen-Cahn IMEX level holds: the Heat2D entry points,
- * the copy transfer (the 2-D spatial transfers refuse such a level), no time-parallel forward solve. Norms run over all 2 nx^2 values. */
+ * the copy transfer, the caller's, or MGRIT_HIP_TRANSFER_PERIODIC2D between two Gray-Scott levels of either form (each plane of a row
+ * transferred on its own, sizes checked per axis on nx), no time-parallel forward solve. Norms run over all 2 nx^2 values. */
 int mgrit_hip_level_grayscott2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld,
                                 double inv_dx2, double du, double dv, double a, double b);
 /* CahnHilliard with method = 'IMEX' (cahn_hilliard/cahn_hilliard.py; no reference class) on the periodic nx x nx grid,
@@ -138,7 +139,8 @@ int mgrit_hip_level_cahnhilliard2d(mgrit_hip_engine *e, int lvl, int n_pts_local
  * (I - dt nu L) x_c = b_c through the Hartley tables of mgrit_hip_level_allencahn2d with one D table for both planes. The right-hand
  * side reads a point's neighbours, so it is a launch of its own in front of the four two-plane products (five launches per Phi).
  * nu, inv_dx2, inv_2dx positive and finite (MGRIT_HIP_EINVAL "bad Burgers parameters" otherwise). Everything said of a Gray-Scott IMEX
- * level holds: the Heat2D entry points, the copy transfer only, no time-parallel forward solve, norms over all 2 nx^2 values. */
+ * level holds: the Heat2D entry points, the copy transfer, the caller's, or MGRIT_HIP_TRANSFER_PERIODIC2D between two Burgers levels
+ * (plane by plane), no time-parallel forward solve, norms over all 2 nx^2 values. */
 int mgrit_hip_level_burgers2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld,
                               double inv_dx2, double inv_2dx, double nu);
 /* NavierStokes2D with method = 'IMEX' (navier_stokes/navier_stokes.py; no reference class): incompressible flow in
@@ -238,7 +240,10 @@ int mgrit_hip_block_solve_form(mgrit_hip_engine *e, int lvl, int *form_out);
 /* Spatial transfer between lvl and lvl+1: GridTransferCopy (core/grid_transfer_copy.py:23-47) or the full-weighting
  * / linear-interpolation pair of examples/example_spatial_coarsening.py:33-82 (fine n = 2*coarse n + 1), or its periodic
  * analogue for Advection1D grids (fine n = 2*coarse n; no reference class exists, BASELINE config 5), or one of the 2-D pairs
- * MGRIT_HIP_TRANSFER_HEAT2D / _PERIODIC2D between two Heat2D / two Allen-Cahn levels. */
+ * MGRIT_HIP_TRANSFER_HEAT2D / _PERIODIC2D between two Heat2D levels / two levels of one periodic 2-D application (Allen-Cahn,
+ * Cahn-Hilliard, Navier-Stokes; Gray-Scott and Burgers, whose rows of two planes [u | v] are transferred plane by plane: fine
+ * nx = 2 * coarse nx per axis, MGRIT_HIP_EINVAL with both sizes otherwise; two different applications, or two levels of one nx of
+ * these two-plane kinds, which the copy transfer joins: MGRIT_HIP_EUNSUPPORTED). */
 int mgrit_hip_level_transfer(mgrit_hip_engine *e, int lvl, int kind);
 
 /*

@@ -4,7 +4,7 @@ Same public names as the reference package for everything on the hot path (``Mgr
 ``GridTransfer``, ``GridTransferCopy``, ``simple_setup_problem``, ``Dahlquist``, ``Heat1D``, ``Heat1DBDF1``, ``Heat1DBDF2``,
 ``Heat2D``, ``Advection1D``, ``AllenCahn``), the Gray-Scott system of the reference's PETSc examples in numpy with its IMEX step on the
 device (``GrayScott``), the 2-D Burgers equation of its Firedrake examples in numpy with its IMEX step on the device (``Burgers2D``), the Cahn-Hilliard equation with its stabilised IMEX step on the device (``CahnHilliard``), the incompressible Navier-Stokes equations in vorticity form with their IMEX step on the device (``NavierStokes2D``), plus the spatial-coarsening transfers that run as HIP kernels (``GridTransferHeat``,
-``GridTransferAdvection``, ``GridTransferHeat2D``, ``GridTransferAllenCahn``, ``GridTransferCahnHilliard``, ``GridTransferNavierStokes``).
+``GridTransferAdvection``, ``GridTransferHeat2D``, ``GridTransferAllenCahn``, ``GridTransferCahnHilliard``, ``GridTransferNavierStokes``, and for the states of two planes ``GridTransferGrayScott``, ``GridTransferBurgers``).
 """
 from pymgrit_amd.core.application import Application
 from pymgrit_amd.core.vector import Vector
@@ -25,9 +25,11 @@ from pymgrit_amd.heat.grid_transfer_heat_2d import GridTransferHeat2D
 from pymgrit_amd.allen_cahn.allen_cahn import AllenCahn, VectorAllenCahn2D
 from pymgrit_amd.allen_cahn.grid_transfer_allen_cahn import GridTransferAllenCahn
 from pymgrit_amd.gray_scott.gray_scott import GrayScott, VectorGrayScott2D
+from pymgrit_amd.gray_scott.grid_transfer_gray_scott import GridTransferGrayScott
 from pymgrit_amd.cahn_hilliard.cahn_hilliard import CahnHilliard, VectorCahnHilliard2D
 from pymgrit_amd.cahn_hilliard.grid_transfer_cahn_hilliard import GridTransferCahnHilliard
 from pymgrit_amd.burgers.burgers import Burgers2D, VectorBurgers2D
+from pymgrit_amd.burgers.grid_transfer_burgers import GridTransferBurgers
 from pymgrit_amd.navier_stokes.navier_stokes import NavierStokes2D, VectorNavierStokes2D
 from pymgrit_amd.navier_stokes.grid_transfer_navier_stokes import GridTransferNavierStokes
 from pymgrit_amd.advection.advection_1d import Advection1D
@@ -47,4 +49,4 @@ __all__ = ["elementwise", "Application", "Vector", "GridTransfer", "GridTransfer
            "Heat1D", "Heat1DBDF1", "Heat1DBDF2", "Heat2D", "GridTransferHeat", "Advection1D", "GridTransferAdvection", "AllenCahn", "VectorAllenCahn2D", "VectorHeat1D2Pts",
            "GridTransferHeat2D", "GridTransferAllenCahn", "GrayScott", "VectorGrayScott2D",
            "CahnHilliard", "VectorCahnHilliard2D", "GridTransferCahnHilliard", "VectorBurgers2D", "Burgers2D",
-           "NavierStokes2D", "VectorNavierStokes2D", "GridTransferNavierStokes"]
+           "NavierStokes2D", "VectorNavierStokes2D", "GridTransferNavierStokes", "GridTransferGrayScott", "GridTransferBurgers"]

@@ -112,13 +112,18 @@ class SlabVectorList:
 
 
 # The applications on the periodic nx x nx grid, kind -> (name in the refusals, what every level of the hierarchy must be, whether the
-# levels share one nx joined by GridTransferCopy -- no spatial coarsening). Checked in this order (HipBackend._check_periodic).
+# kind takes no transfer of a user's -- the kinds whose state is two planes: GridTransferCopy between levels of one nx, the library
+# class named next or a subclass of it between levels with nx halved, nothing else; a kind of one plane takes GridTransferCopy, its
+# own GridTransfer or a user's through its Python methods --, that library class as (module, name), looked up when a hierarchy is
+# checked). Checked in this order (HipBackend._check_periodic).
 PERIODIC_2D = {
-    "allencahn2d": ("Allen-Cahn", "an AllenCahn application with method='IMEX', or 'IMPL' / 'CN' with linear_solver='pcg'", False),
-    "grayscott2d": ("Gray-Scott", "a GrayScott application with method='IMEX', or 'IMPL' with linear_solver='bicgstab', on the same nx", True),
-    "cahnhilliard2d": ("Cahn-Hilliard", "a CahnHilliard application (method='IMEX')", False),
-    "burgers2d": ("Burgers", "a Burgers2D application (method='IMEX') on the same nx", True),
-    "navierstokes2d": ("Navier-Stokes", "a NavierStokes2D application (method='IMEX')", False),
+    "allencahn2d": ("Allen-Cahn", "an AllenCahn application with method='IMEX', or 'IMPL' / 'CN' with linear_solver='pcg'", False, None),
+    "grayscott2d": ("Gray-Scott", "a GrayScott application with method='IMEX', or 'IMPL' with linear_solver='bicgstab'", True,
+                    ("pymgrit_amd.gray_scott.grid_transfer_gray_scott", "GridTransferGrayScott")),
+    "cahnhilliard2d": ("Cahn-Hilliard", "a CahnHilliard application (method='IMEX')", False, None),
+    "burgers2d": ("Burgers", "a Burgers2D application (method='IMEX')", True,
+                  ("pymgrit_amd.burgers.grid_transfer_burgers", "GridTransferBurgers")),
+    "navierstokes2d": ("Navier-Stokes", "a NavierStokes2D application (method='IMEX')", False, None),
 }
 GRID_2D = ("heat2d",) + tuple(PERIODIC_2D)   # states are whole 2-D grids in natural row-major order (Gray-Scott: two of them,
                                              # [u plane | v plane]); the engine's Heat2D route
@@ -207,21 +212,45 @@ class HipBackend:
 
     def _check_periodic(self, mg, kind):
         """what the device path of a periodic 2-D application does not cover is refused by name, never run differently (transfers
-        of the kinds with spatial coarsening: GridTransferCopy, the application's own GridTransfer, or a user's through its Python
-        methods)"""
+        of the kinds of one plane: GridTransferCopy, the application's own GridTransfer, or a user's through its Python methods; of
+        the kinds of two planes: _check_two_plane_transfers)"""
         from pymgrit_amd.core.at_mgrit import AtMgrit
-        from pymgrit_amd.core.grid_transfer_copy import GridTransferCopy
-        name, every_level, copy_only = PERIODIC_2D[kind]
-        if any(d["kind"] != kind for d in self.desc) or (copy_only and len({d["nx"] for d in self.desc}) != 1):
+        name, every_level, library_only, own = PERIODIC_2D[kind]
+        if any(d["kind"] != kind for d in self.desc):
             raise MgritHipError(f"{name} levels on the HIP engine: every level of the hierarchy must be {every_level}")
-        if copy_only and any(type(tr) is not GridTransferCopy for tr in mg.transfer_objects):
-            raise MgritHipError(f"{name} levels on the HIP engine: GridTransferCopy only (no spatial coarsening)")
+        if library_only:
+            HipBackend._check_two_plane_transfers(name, own, [int(d["nx"]) for d in self.desc], mg.transfer_objects)
         if mg.comm_time_size > 1:
             raise MgritHipError(f"{name} levels on the HIP engine: one time rank only")
         if isinstance(mg, AtMgrit):
             raise MgritHipError(f"{name} levels on the HIP engine: AT-MGRIT is not supported, use Mgrit")
         if not mg.global_conv_crit:
             raise MgritHipError(f"{name} levels on the HIP engine: the global convergence criteria only (conv_crit 0 or 1)")
+
+    @staticmethod
+    def _check_two_plane_transfers(name, own, nxs, transfers):
+        """Gray-Scott and Burgers hierarchies: levels of one nx joined by GridTransferCopy, a level of half the nx by the kind's
+        library class or a subclass of it (which goes through its Python methods where it overrides them, _device_transfer). Any
+        other class -- a user's GridTransfer, another application's -- is refused with its name and the two sizes"""
+        import importlib
+        from pymgrit_amd.core.grid_transfer_copy import GridTransferCopy
+        own = getattr(importlib.import_module(own[0]), own[1])
+        head = f"{name} levels on the HIP engine: "
+        for tr, nf, nc in zip(transfers, nxs, nxs[1:]):
+            cls = type(tr).__name__
+            if type(tr) is GridTransferCopy:
+                if nf != nc:
+                    raise MgritHipError(head + f"GridTransferCopy joins levels of the same nx, not nx {nf} and {nc} "
+                                               f"(spatial coarsening: {own.__name__}, nx halved)")
+            elif isinstance(tr, own):
+                if nf != 2 * nc:
+                    raise MgritHipError(head + f"{own.__name__} ({cls}) joins levels with nx_fine = 2 * nx_coarse, not nx {nf} and {nc}")
+            elif nf != nc:
+                raise MgritHipError(head + f"{cls} between levels of nx {nf} and {nc} is not this application's transfer: levels of "
+                                           f"the same nx are joined by GridTransferCopy, a level of half the nx by {own.__name__}")
+            else:
+                raise MgritHipError(head + f"GridTransferCopy only between levels of the same nx ({nf}), not {cls} "
+                                           f"(spatial coarsening: {own.__name__}, nx halved)")
 
     # -- state (mgrit.py:840-858) -------------------------------------------------------------------
     @staticmethod

@@ -1865,7 +1865,7 @@ struct H2DKindRow {
     int comps;          // planes of a state row
     int items;          // work slab items of a state in the first two products (Cahn-Hilliard: u and w(u) from its one plane,
                         // joined by the second)
-    bool transfer2d;    // the device 2-D transfer joins two levels of it
+    bool transfer2d;    // the device 2-D transfer joins two levels of it (plane by plane where a row holds two)
     int n_rows, n_int, n_dbl, nb, max_batch, check_every;
 };
 // items per Newton batch: the work rows of a batch stay within the 2 x H2D_MAX_BATCH items the level's IMEX form reserves
@@ -1874,10 +1874,10 @@ constexpr H2DKindRow H2D_KINDS[] = {
     {"Heat2D", false, 1, 1, true, 0, 0, 0, 0, 0, 0},
     {"Allen-Cahn", true, 1, 1, true, 0, 0, 0, 0, 0, 0},
     {"Allen-Cahn", true, 1, 1, true, 9, 5, 4, ACN_NB, newton_cap(1, 9), 4},
-    {"Gray-Scott", true, 2, 2, false, 0, 0, 0, 0, 0, 0},
-    {"Gray-Scott", true, 2, 2, false, 11, 6, 5, GSN_NB, newton_cap(2, 11), 2},
+    {"Gray-Scott", true, 2, 2, true, 0, 0, 0, 0, 0, 0},
+    {"Gray-Scott", true, 2, 2, true, 11, 6, 5, GSN_NB, newton_cap(2, 11), 2},
     {"Cahn-Hilliard", true, 1, 2, true, 0, 0, 0, 0, 0, 0},
-    {"Burgers", true, 2, 2, false, 0, 0, 0, 0, 0, 0},
+    {"Burgers", true, 2, 2, true, 0, 0, 0, 0, 0, 0},
     {"Navier-Stokes", true, 1, 1, true, 0, 0, 0, 0, 0, 0},
 };
 constexpr const H2DKindRow &kind_row(H2DKind k) { return H2D_KINDS[(int)k]; }
@@ -4949,10 +4949,15 @@ int mgrit_hip_level_transfer(mgrit_hip_engine *e, int lvl, int kind) {
     } else if (kind == MGRIT_HIP_TRANSFER_HEAT2D || kind == MGRIT_HIP_TRANSFER_PERIODIC2D) {
         const H2DHost *hf = e->L[lvl].h2d, *hc = e->L[lvl + 1].h2d;
         const bool per = kind == MGRIT_HIP_TRANSFER_PERIODIC2D;
-        // (the same application on both levels, one that has the transfer -- the periodic kinds of one plane per state --, the periodic
-        // transfer for the periodic grid and the Heat2D transfer for Heat2D)
+        // (the same application on both levels -- two forms of one application share its name and its planes --, one that has the
+        // transfer, the periodic transfer for the periodic grid and the Heat2D transfer for Heat2D; the sizes per axis, whatever the
+        // planes of a row)
         if (!hf || !hc || std::strcmp(hf->row().name, hc->row().name) != 0 || !hf->row().transfer2d || hf->periodic() != per)
             return fail(MGRIT_HIP_EUNSUPPORTED, per ? "the periodic 2-D transfer joins two Allen-Cahn levels" : "the Heat2D transfer joins two Heat2D levels");
+        // (two levels of one nx of a kind of two planes keep the answer they always had: the copy transfer is theirs)
+        if (hf->comps() > 1 && hf->dev.nx == hc->dev.nx)
+            return fail(MGRIT_HIP_EUNSUPPORTED, "%s levels of one nx (%d) are joined by the copy transfer, the periodic 2-D transfer joins nx = 2*n_coarse",
+                        hf->row().name, hf->dev.nx);
         const int off = per ? 0 : 1;
         if (2 * hc->dev.nx - off != hf->dev.nx || 2 * hc->dev.ny - off != hf->dev.ny)
             return fail(MGRIT_HIP_EINVAL, per ? "periodic 2-D transfer needs n_fine = 2*n_coarse per axis (%dx%d vs %dx%d)"
@@ -5163,7 +5168,8 @@ static bool transfer_2d(const Level &lf) {
 }
 
 static T2DGeom t2d_geom(const Level &lf, const Level &lc) {
-    return T2DGeom{lf.h2d->dev.nx, lf.h2d->dev.ny, lc.h2d->dev.nx, lc.h2d->dev.ny, lf.transfer == MGRIT_HIP_TRANSFER_PERIODIC2D ? 1 : 0};
+    return T2DGeom{lf.h2d->dev.nx, lf.h2d->dev.ny, lc.h2d->dev.nx, lc.h2d->dev.ny, lf.transfer == MGRIT_HIP_TRANSFER_PERIODIC2D ? 1 : 0,
+                   lf.h2d->comps()};
 }
 
 // The 1-D row transfer: row d_idx[p] of dst (rows of level `to`) = R(row s_idx[p] of src (rows of level `from`)) for count rows; kind:

@@ -1,17 +1,19 @@
 #!/usr/bin/env python3
 """The 2-D library transfers on the device against the same arithmetic through the caller's path, and the two kernels alone.
 
-Hierarchies: Heat2D 513 x 513 -> 257 x 257 (backward Euler) and AllenCahn 512 x 512 -> 256 x 256 (IMEX), two levels, nt = 257, m = 4,
-steps equal bit for bit (the caller's path takes one step size per level). Legs, each a child process under its own time limit:
+Hierarchies: Heat2D 513 x 513 -> 257 x 257 (backward Euler), AllenCahn 512 x 512 -> 256 x 256 (IMEX) and, rows of two planes,
+GrayScott (IMEX) and Burgers2D 512 x 512 -> 256 x 256; two levels, nt = 257, m = 4, steps equal bit for bit (the caller's path takes one
+step size per level). Legs, each a child process under its own time limit:
 
-  *_cycle_library   one V-cycle with GridTransferHeat2D / GridTransferAllenCahn (kernels restrict2d_rows_kernel / interp2d_rows_kernel)
+  *_cycle_library   one V-cycle with GridTransferHeat2D / GridTransferAllenCahn / GridTransferGrayScott / GridTransferBurgers (kernels
+                    restrict2d_rows_kernel / interp2d_rows_kernel)
   *_cycle_caller    the same with a subclass that overrides both methods by super() calls: the Python methods row by row on the host
                     between the kernels (MGRIT_HIP_TRANSFER_CALLER)
   *_kernels         mgrit_hip_restrict_u and mgrit_hip_interpolate over the level's 64 C-points alone, device events; bytes moved =
-                    8 * (n_fine + n_coarse) per pair (every value of the source row read once, every value of the destination
-                    written once), as a fraction of the 8 TB/s HBM peak
+                    8 * planes * (n_fine + n_coarse) per pair (every value of the source row read once, every value of the
+                    destination written once; planes = 2 for grayscott_* and burgers_*), as a fraction of the 8 TB/s HBM peak
 
-The first failure ends the run. One JSON line per leg.  Usage:  python tools/transfer2d_bench.py [nt]"""
+The first failure ends the run. One JSON line per leg.  Usage:  python tools/transfer2d_bench.py [nt [leg ...]]  (no leg named: all)"""
 import json
 import os
 import subprocess
@@ -19,7 +21,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HBM_PEAK = 8.0e12
-LEGS = tuple((f"{app}_{what}", 420) for app in ("heat2d", "allencahn") for what in ("kernels", "cycle_library", "cycle_caller"))
+LEGS = tuple((f"{app}_{what}", 420) for app in ("heat2d", "allencahn", "grayscott", "burgers") for what in ("kernels", "cycle_library", "cycle_caller"))
 
 
 def leg(name, nt):
@@ -27,9 +29,13 @@ def leg(name, nt):
     import time
     import numpy as np
     import torch
-    from pymgrit_amd import AllenCahn, GridTransferAllenCahn, GridTransferHeat2D, Heat2D, Mgrit
-    heat = name.startswith("heat2d")
-    base = GridTransferHeat2D if heat else GridTransferAllenCahn
+    from pymgrit_amd import (AllenCahn, Burgers2D, GrayScott, GridTransferAllenCahn, GridTransferBurgers, GridTransferGrayScott,
+                             GridTransferHeat2D, Heat2D, Mgrit)
+    app = name.split("_")[0]
+    heat = app == "heat2d"
+    base = {"heat2d": GridTransferHeat2D, "allencahn": GridTransferAllenCahn, "grayscott": GridTransferGrayScott,
+            "burgers": GridTransferBurgers}[app]
+    planes = 2 if app in ("grayscott", "burgers") else 1
 
     class ViaPython(base):
         def restriction(self, u):
@@ -44,15 +50,17 @@ def leg(name, nt):
         prob = [Heat2D(x_start=0, x_end=1, y_start=0, y_end=1, nx=n, ny=n, a=1.0, method="BE", t_interval=g) for n, g in zip(sizes, grids)]
     else:
         sizes = (512, 256)
-        prob = [AllenCahn(nx=n, method="IMEX", t_interval=g) for n, g in zip(sizes, grids)]
+        make = {"allencahn": lambda **kw: AllenCahn(method="IMEX", **kw), "grayscott": lambda **kw: GrayScott(method="IMEX", **kw),
+                "burgers": Burgers2D}[app]
+        prob = [make(nx=n, t_interval=g) for n, g in zip(sizes, grids)]
     tr = ViaPython() if name.endswith("caller") else base()
     mg = Mgrit(prob, transfer=[tr], cf_iter=1, nested_iteration=False, max_iter=3, tol=0.0, logging_lvl=30)
     be = mg.backend
     assert type(be).__name__ == "HipBackend" and be._device_transfer(0) == (not name.endswith("caller"))
-    out = {"leg": name, "nt": nt, "fine": sizes[0], "coarse": sizes[1]}
+    out = {"leg": name, "nt": nt, "fine": sizes[0], "coarse": sizes[1], "planes": planes}
     if name.endswith("kernels"):
         pairs = [(4 * j, j) for j in range(1, len(grids[1]))]
-        moved = 8.0 * (sizes[0] ** 2 + sizes[1] ** 2) * len(pairs)
+        moved = 8.0 * planes * (sizes[0] ** 2 + sizes[1] ** 2) * len(pairs)
         for sweep, kind in ((be.restrict_u, "restrict"), (be.interpolate, "interpolate")):
             for _ in range(2):
                 sweep(0, pairs)
@@ -84,7 +92,12 @@ def main():
         leg(sys.argv[2], int(sys.argv[3]))
         return
     nt = int(sys.argv[1]) if len(sys.argv) > 1 else 257
+    unknown = set(sys.argv[2:]) - {name for name, _ in LEGS}
+    if unknown:
+        sys.exit(f"unknown legs {sorted(unknown)}: one of {[name for name, _ in LEGS]}")
     for name, limit in LEGS:
+        if sys.argv[2:] and name not in sys.argv[2:]:
+            continue
         rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", name, str(nt)], timeout=limit).returncode
         if rc != 0:
             sys.exit(f"leg {name} failed with exit status {rc}: stopping")
