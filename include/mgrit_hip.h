@@ -36,7 +36,8 @@ typedef struct mgrit_hip_engine mgrit_hip_engine;
 enum { MGRIT_HIP_OK = 0, MGRIT_HIP_EINVAL = -1, MGRIT_HIP_EHIP = -2, MGRIT_HIP_ENODEV = -3, MGRIT_HIP_EUNSUPPORTED = -4 };
 enum { MGRIT_HIP_STEPPER_HEAT1D = 1, MGRIT_HIP_STEPPER_ADVECTION1D = 2, MGRIT_HIP_STEPPER_HEAT2D = 3,
        MGRIT_HIP_STEPPER_HEAT1D_2PTS = 4, MGRIT_HIP_STEPPER_ALLENCAHN2D = 5, MGRIT_HIP_STEPPER_GRAYSCOTT2D = 6,
-       MGRIT_HIP_STEPPER_CAHNHILLIARD2D = 7, MGRIT_HIP_STEPPER_BURGERS2D = 8, MGRIT_HIP_STEPPER_NAVIERSTOKES2D = 9 };
+       MGRIT_HIP_STEPPER_CAHNHILLIARD2D = 7, MGRIT_HIP_STEPPER_BURGERS2D = 8, MGRIT_HIP_STEPPER_NAVIERSTOKES2D = 9,
+       MGRIT_HIP_STEPPER_GINZBURGLANDAU2D = 10 };
 enum { MGRIT_HIP_TRANSFER_COPY = 0, MGRIT_HIP_TRANSFER_HEAT1D = 1, MGRIT_HIP_TRANSFER_PERIODIC1D = 2,
        /* the caller applies restriction / interpolation itself (a user's GridTransfer, reference core/grid_transfer.py:31-55:
           any Python code): mgrit_hip_restrict_u / _fas_rhs / _error_correction / _interpolate refuse the level pair, the FAS
@@ -154,6 +155,18 @@ int mgrit_hip_level_burgers2d(mgrit_hip_engine *e, int lvl, int n_pts_local, con
  * MGRIT_HIP_TRANSFER_PERIODIC2D between two such levels, no time-parallel forward solve. */
 int mgrit_hip_level_navierstokes2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld,
                                    double inv_dx2, double inv_2dx, double nu, const double *forcing);
+/* GinzburgLandau2D with method = 'IMEX' (ginzburg_landau/ginzburg_landau.py; no reference class): the complex
+ * Ginzburg-Landau equation A_t = A + (1 + i b) Lap A - (1 + i c) |A|^2 A on the periodic nx x nx grid, 4 <= nx <= 2048. A state row holds
+ * TWO planes [Re A | Im A] like a Gray-Scott row, n = 2 nx^2, ld >= 2 nx^2 a multiple of 16. With A = x + i y, q = x^2 + y^2:
+ * r = x + dt (x - q (x - c y)), s = y + dt (y - q (c x + y)), then the implicit operator, a 2 x 2 block per mode that couples the planes:
+ * x_new = T ((T r T) o Da + (T s T) o Db) T, y_new = T ((T s T) o Da - (T r T) o Db) T with Da = a / det, Db = beta / det, a = 1 + dt mu,
+ * beta = (b dt) mu, det = a^2 + beta^2, mu = lam_i + lam_j, through the Hartley tables of mgrit_hip_level_allencahn2d: four launches per
+ * Phi over two work items per state, the second product reading both spectra of a state and writing both items. inv_dx2 positive, all
+ * parameters finite (MGRIT_HIP_EINVAL "bad Ginzburg-Landau parameters" otherwise). Everything said of a Gray-Scott IMEX level holds: the
+ * Heat2D entry points, the copy transfer, the caller's, or MGRIT_HIP_TRANSFER_PERIODIC2D between two Ginzburg-Landau levels (plane by
+ * plane), no time-parallel forward solve, norms over all 2 nx^2 values. */
+int mgrit_hip_level_ginzburglandau2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld,
+                                     double inv_dx2, double b, double c);
 /* AllenCahn with method = 'IMPL' (theta = 1) or 'CN' (theta = 0.5) and linear_solver = 'pcg' (DESIGN.md 3.9): the level of
  * mgrit_hip_level_allencahn2d, whose Phi is Newton's method on x - fac (L x + r(x) / eps^2) = rhs, fac = theta dt, with every
  * correction by conjugate gradients preconditioned with (1 + fac nu / eps^2) I - fac L through the Hartley products. Per item: at most
@@ -241,7 +254,7 @@ int mgrit_hip_block_solve_form(mgrit_hip_engine *e, int lvl, int *form_out);
  * / linear-interpolation pair of examples/example_spatial_coarsening.py:33-82 (fine n = 2*coarse n + 1), or its periodic
  * analogue for Advection1D grids (fine n = 2*coarse n; no reference class exists, BASELINE config 5), or one of the 2-D pairs
  * MGRIT_HIP_TRANSFER_HEAT2D / _PERIODIC2D between two Heat2D levels / two levels of one periodic 2-D application (Allen-Cahn,
- * Cahn-Hilliard, Navier-Stokes; Gray-Scott and Burgers, whose rows of two planes [u | v] are transferred plane by plane: fine
+ * Cahn-Hilliard, Navier-Stokes; Gray-Scott, Burgers and Ginzburg-Landau, whose rows of two planes [u | v] are transferred plane by plane: fine
  * nx = 2 * coarse nx per axis, MGRIT_HIP_EINVAL with both sizes otherwise; two different applications, or two levels of one nx of
  * these two-plane kinds, which the copy transfer joins: MGRIT_HIP_EUNSUPPORTED). */
 int mgrit_hip_level_transfer(mgrit_hip_engine *e, int lvl, int kind);

@@ -3,8 +3,8 @@
 Same public names as the reference package for everything on the hot path (``Mgrit``, ``AtMgrit``, ``Application``, ``Vector``,
 ``GridTransfer``, ``GridTransferCopy``, ``simple_setup_problem``, ``Dahlquist``, ``Heat1D``, ``Heat1DBDF1``, ``Heat1DBDF2``,
 ``Heat2D``, ``Advection1D``, ``AllenCahn``), the Gray-Scott system of the reference's PETSc examples in numpy with its IMEX step on the
-device (``GrayScott``), the 2-D Burgers equation of its Firedrake examples in numpy with its IMEX step on the device (``Burgers2D``), the Cahn-Hilliard equation with its stabilised IMEX step on the device (``CahnHilliard``), the incompressible Navier-Stokes equations in vorticity form with their IMEX step on the device (``NavierStokes2D``), plus the spatial-coarsening transfers that run as HIP kernels (``GridTransferHeat``,
-``GridTransferAdvection``, ``GridTransferHeat2D``, ``GridTransferAllenCahn``, ``GridTransferCahnHilliard``, ``GridTransferNavierStokes``, and for the states of two planes ``GridTransferGrayScott``, ``GridTransferBurgers``).
+device (``GrayScott``), the 2-D Burgers equation of its Firedrake examples in numpy with its IMEX step on the device (``Burgers2D``), the Cahn-Hilliard equation with its stabilised IMEX step on the device (``CahnHilliard``), the incompressible Navier-Stokes equations in vorticity form with their IMEX step on the device (``NavierStokes2D``), the complex Ginzburg-Landau equation with its coupled-plane IMEX step on the device (``GinzburgLandau2D``), plus the spatial-coarsening transfers that run as HIP kernels (``GridTransferHeat``,
+``GridTransferAdvection``, ``GridTransferHeat2D``, ``GridTransferAllenCahn``, ``GridTransferCahnHilliard``, ``GridTransferNavierStokes``, and for the states of two planes ``GridTransferGrayScott``, ``GridTransferBurgers``, ``GridTransferGinzburgLandau``).
 """
 from pymgrit_amd.core.application import Application
 from pymgrit_amd.core.vector import Vector
@@ -32,6 +32,8 @@ from pymgrit_amd.burgers.burgers import Burgers2D, VectorBurgers2D
 from pymgrit_amd.burgers.grid_transfer_burgers import GridTransferBurgers
 from pymgrit_amd.navier_stokes.navier_stokes import NavierStokes2D, VectorNavierStokes2D
 from pymgrit_amd.navier_stokes.grid_transfer_navier_stokes import GridTransferNavierStokes
+from pymgrit_amd.ginzburg_landau.ginzburg_landau import GinzburgLandau2D, VectorGinzburgLandau2D
+from pymgrit_amd.ginzburg_landau.grid_transfer_ginzburg_landau import GridTransferGinzburgLandau
 from pymgrit_amd.advection.advection_1d import Advection1D
 from pymgrit_amd.advection.grid_transfer_advection import GridTransferAdvection
 
@@ -49,4 +51,5 @@ __all__ = ["elementwise", "Application", "Vector", "GridTransfer", "GridTransfer
            "Heat1D", "Heat1DBDF1", "Heat1DBDF2", "Heat2D", "GridTransferHeat", "Advection1D", "GridTransferAdvection", "AllenCahn", "VectorAllenCahn2D", "VectorHeat1D2Pts",
            "GridTransferHeat2D", "GridTransferAllenCahn", "GrayScott", "VectorGrayScott2D",
            "CahnHilliard", "VectorCahnHilliard2D", "GridTransferCahnHilliard", "VectorBurgers2D", "Burgers2D",
-           "NavierStokes2D", "VectorNavierStokes2D", "GridTransferNavierStokes", "GridTransferGrayScott", "GridTransferBurgers"]
+           "NavierStokes2D", "VectorNavierStokes2D", "GridTransferNavierStokes", "GridTransferGrayScott", "GridTransferBurgers",
+           "GinzburgLandau2D", "VectorGinzburgLandau2D", "GridTransferGinzburgLandau"]

@@ -124,6 +124,8 @@ PERIODIC_2D = {
     "burgers2d": ("Burgers", "a Burgers2D application (method='IMEX')", True,
                   ("pymgrit_amd.burgers.grid_transfer_burgers", "GridTransferBurgers")),
     "navierstokes2d": ("Navier-Stokes", "a NavierStokes2D application (method='IMEX')", False, None),
+    "ginzburglandau2d": ("Ginzburg-Landau", "a GinzburgLandau2D application (method='IMEX')", True,
+                         ("pymgrit_amd.ginzburg_landau.grid_transfer_ginzburg_landau", "GridTransferGinzburgLandau")),
 }
 GRID_2D = ("heat2d",) + tuple(PERIODIC_2D)   # states are whole 2-D grids in natural row-major order (Gray-Scott: two of them,
                                              # [u plane | v plane]); the engine's Heat2D route
@@ -229,7 +231,7 @@ class HipBackend:
 
     @staticmethod
     def _check_two_plane_transfers(name, own, nxs, transfers):
-        """Gray-Scott and Burgers hierarchies: levels of one nx joined by GridTransferCopy, a level of half the nx by the kind's
+        """Gray-Scott, Burgers and Ginzburg-Landau hierarchies: levels of one nx joined by GridTransferCopy, a level of half the nx by the kind's
         library class or a subclass of it (which goes through its Python methods where it overrides them, _device_transfer). Any
         other class -- a user's GridTransfer, another application's -- is refused with its name and the two sizes"""
         import importlib
@@ -346,6 +348,10 @@ class HipBackend:
                 raise MgritHipError(f"Navier-Stokes levels on the HIP engine: forcing of shape {f.shape}, not ({d['nx']}, {d['nx']})")
         hip_lib.level_navierstokes2d(self.h, engine_lvl, t_local.size, _ptr(t_local), ld, d, _ptr(f) if f is not None else C.c_void_p(0))
 
+    def _describe_ginzburglandau2d(self, engine_lvl, d, t_local, n, ld):
+        """the IMEX step, two planes per state that the implicit operator couples mode by mode"""
+        hip_lib.level_ginzburglandau2d(self.h, engine_lvl, t_local.size, _ptr(t_local), ld, d)
+
     def newton_stats(self, lvl):
         """counts of a Newton level (Allen-Cahn PCG, Gray-Scott BiCGStab) since the last call (which resets them)"""
         return hip_lib.newton_stats(self.h, lvl)
@@ -353,7 +359,7 @@ class HipBackend:
     _DESCRIBE = {"heat1d": _describe_heat1d, "heat1d_2pts": _describe_heat1d_2pts, "advection1d": _describe_advection1d,
                  "heat2d": _describe_heat2d, "allencahn2d": _describe_allencahn2d, "grayscott2d": _describe_grayscott2d,
                  "cahnhilliard2d": _describe_cahnhilliard2d, "burgers2d": _describe_burgers2d,
-                 "navierstokes2d": _describe_navierstokes2d}
+                 "navierstokes2d": _describe_navierstokes2d, "ginzburglandau2d": _describe_ginzburglandau2d}
 
     def _describe(self, engine_lvl, lvl, t_local):
         """tell the engine what level engine_lvl is: the stepper of level lvl on the time points t_local"""

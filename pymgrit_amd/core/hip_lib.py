@@ -18,6 +18,7 @@ STEPPER_GRAYSCOTT2D = 6
 STEPPER_CAHNHILLIARD2D = 7
 STEPPER_BURGERS2D = 8
 STEPPER_NAVIERSTOKES2D = 9
+STEPPER_GINZBURGLANDAU2D = 10
 TRANSFER_COPY, TRANSFER_HEAT1D, TRANSFER_CALLER = 0, 1, 3
 TRANSFER_HEAT2D, TRANSFER_PERIODIC2D = 4, 5
 MAX_N = 16384
@@ -62,6 +63,8 @@ EXPORTS = {
                                             C.c_double]),
     "mgrit_hip_level_navierstokes2d": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double,
                                                  C.c_double, C.c_void_p]),
+    "mgrit_hip_level_ginzburglandau2d": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double,
+                                                   C.c_double]),
     "mgrit_hip_newton_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "mgrit_hip_level_bind": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgrit_hip_chain_enable": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -220,6 +223,12 @@ def level_navierstokes2d(h, engine_lvl, n_pts, t_ptr, ld, d, forcing_ptr):
     order, which the library copies, or NULL"""
     check(load().mgrit_hip_level_navierstokes2d(h, engine_lvl, n_pts, t_ptr, int(d["nx"]), ld, float(d["inv_dx2"]), float(d["inv_2dx"]),
                                                 float(d["nu"]), forcing_ptr))
+
+
+def level_ginzburglandau2d(h, engine_lvl, n_pts, t_ptr, ld, d):
+    """describe a Ginzburg-Landau IMEX level; d: the application's description"""
+    check(load().mgrit_hip_level_ginzburglandau2d(h, engine_lvl, n_pts, t_ptr, int(d["nx"]), ld, float(d["inv_dx2"]), float(d["b"]),
+                                                  float(d["c"])))
 
 
 def level_cahnhilliard2d(h, engine_lvl, n_pts, t_ptr, ld, d):

@@ -1819,6 +1819,8 @@ __global__ void interp_rows_kernel(double *__restrict__ uf, int f_ld, int T_f, c
 
 #include "mgrit_hip_cahnhilliard.inc"
 
+#include "mgrit_hip_ginzburglandau.inc"
+
 #include "mgrit_hip_transfer2d.inc"
 
 #include "mgrit_hip_wide.inc"
@@ -1852,7 +1854,7 @@ struct PairList {
 };
 
 constexpr int H2D_MAX_BATCH = 1024;  // items per GEMM batch (work buffers: 2 x 1024 x Mi x Mj doubles; 2048 measured no faster)
-enum class H2DKind { HEAT2D, ALLENCAHN_IMEX, ALLENCAHN_NEWTON, GRAYSCOTT_IMEX, GRAYSCOTT_NEWTON, CAHNHILLIARD_IMEX, BURGERS_IMEX, NAVIERSTOKES_IMEX };   // what a level of the batched 2-D route steps with
+enum class H2DKind { HEAT2D, ALLENCAHN_IMEX, ALLENCAHN_NEWTON, GRAYSCOTT_IMEX, GRAYSCOTT_NEWTON, CAHNHILLIARD_IMEX, BURGERS_IMEX, NAVIERSTOKES_IMEX, GINZBURGLANDAU_IMEX };   // what a level of the batched 2-D route steps with
 // What is a constant of a kind, one row per kind in the enum's order. The Newton columns (0 for the other kinds): the work rows of an
 // item, comps planes each -- Allen-Cahn PCG x, rhs, r, z, p, Jp, delta + the two operands of the preconditioner's
 // products; Gray-Scott BiCGStab (3.11) x, w, r, r^, p, v, s, y, delta + the same two, which between two sets of products carry
@@ -1879,6 +1881,7 @@ constexpr H2DKindRow H2D_KINDS[] = {
     {"Cahn-Hilliard", true, 1, 2, true, 0, 0, 0, 0, 0, 0},
     {"Burgers", true, 2, 2, true, 0, 0, 0, 0, 0, 0},
     {"Navier-Stokes", true, 1, 1, true, 0, 0, 0, 0, 0, 0},
+    {"Ginzburg-Landau", true, 2, 2, true, 0, 0, 0, 0, 0, 0},
 };
 constexpr const H2DKindRow &kind_row(H2DKind k) { return H2D_KINDS[(int)k]; }
 static_assert(kind_row(H2DKind::ALLENCAHN_NEWTON).max_batch <= 256, "acn_reduce_kernel: one thread per item of a batch, one workgroup");
@@ -1908,7 +1911,9 @@ struct H2DHost {
     // rim, no fold. A Gray-Scott state row holds two planes [u | v], a D table per species, the right-hand side from both planes;
     // Cahn-Hilliard a [2][P][P] table (D1, D2); a Burgers row is two planes as well, one D table stored twice, the right-hand side
     // from a stencil pass in front of the products (mgrit_hip_burgers.inc); a Navier-Stokes row is one plane, the vorticity, with a
-    // second table S for the stream-function solve and a stencil pass between the two sets of products (mgrit_hip_navierstokes.inc).
+    // second table S for the stream-function solve and a stencil pass between the two sets of products (mgrit_hip_navierstokes.inc);
+    // a Ginzburg-Landau row is two planes [Re A | Im A], its [2][P][P] table (Da, Db) the 2 x 2 block of each mode, which the second
+    // product applies to both spectra of a state at once (mgrit_hip_ginzburglandau.inc).
     // The Newton kinds: the level's Phi is the Newton step over newton_state below.
     H2DKind kind = H2DKind::HEAT2D;
     const H2DKindRow &row() const { return kind_row(kind); }
@@ -1922,6 +1927,7 @@ struct H2DHost {
     struct { double du = 0.0, dv = 0.0, a = 0.0, b = 0.0, inv_dx2 = 0.0; } gs;   // inv_dx2: the stencil of the Newton kernels
     struct { double eps2 = 0.0, stab = 0.0; } ch;
     struct { double nu = 0.0, inv_2dx = 0.0; } bg;
+    struct { double b = 0.0, c = 0.0; } gl;
     struct { double nu = 0.0, inv_2dx = 0.0; double *S = nullptr, *f = nullptr; } ns;   // S: the table of the stream-function solve
                                                                                        // (ns_sinv), f: the forcing plane or null
     double *Wc0 = nullptr, *Wc1 = nullptr;   // one item each: the work buffers of the coarsest-level chain, which in a planned
@@ -3125,7 +3131,8 @@ void p2d_fill_dinv(const H2DHost &h, double *tab, double shift, double coef) {
 // Allen-Cahn IMEX 1 / (1 + dt (lam_a + lam_b)); Gray-Scott [2][P][P], species u then v, 1 / (1 + (dt d_c) (lam_a + lam_b)), the operand
 // order of GrayScott._dinv; Cahn-Hilliard [2][P][P], D1 = 1 / (1 + dt (eps^2 mu^2 + s mu)) then D2 = -(dt mu) D1, mu = lam_a + lam_b, the
 // operand order of CahnHilliard._tables; Burgers [2][P][P], the same D = 1 / (1 + (dt nu) (lam_a + lam_b)) twice (one per plane's item),
-// the operand order of Burgers2D._dinv; Navier-Stokes that D once, the operand order of NavierStokes2D._dinv
+// the operand order of Burgers2D._dinv; Navier-Stokes that D once, the operand order of NavierStokes2D._dinv; Ginzburg-Landau [2][P][P],
+// Da = a / det then Db = beta / det with a = 1 + dt mu, beta = (b dt) mu, det = a a + beta beta, the operand order of GinzburgLandau2D._dinv
 int h2d_dinv(mgrit_hip_engine *e, Level &lv, uint64_t dtbits, double **out) {
     H2DHost &h = *lv.h2d;
     const size_t per = (size_t)h.dev.Mi * h.dev.Mj;
@@ -3154,6 +3161,18 @@ int h2d_dinv(mgrit_hip_engine *e, Level &lv, uint64_t dtbits, double **out) {
             p2d_fill_dinv(h, tab + per, 1.0, dt * h.bg.nu);
             break;
         case H2DKind::NAVIERSTOKES_IMEX: p2d_fill_dinv(h, tab, 1.0, dt * h.ns.nu); break;
+        case H2DKind::GINZBURGLANDAU_IMEX: {
+            const double bdt = h.gl.b * dt;
+            for (int a = 0; a < h.dev.nx; ++a)
+                for (int b = 0; b < h.dev.nx; ++b) {
+                    const double mu = h.lx[a] + h.ly[b];
+                    const double re = 1.0 + dt * mu, im = bdt * mu;
+                    const double det = re * re + im * im;
+                    tab[(size_t)a * h.dev.Mj + b] = re / det;
+                    tab[per + (size_t)a * h.dev.Mj + b] = im / det;
+                }
+            break;
+        }
         default: p2d_fill_dinv(h, tab, 1.0, dt);   // Allen-Cahn (the Newton kinds have their own tables: newton_dinv)
         }
     }, out);
@@ -3218,6 +3237,27 @@ int ch_products(mgrit_hip_engine *e, const H2DHost &h, int count, const CHPre &p
     hipLaunchKernelGGL((p2d_gemm_kernel<P2D_PLAIN, ACPre>), g1, dim3(256), 0, e->stream, h.T, P, h.KP, H.nx, W0, W1, nullptr, per, idx, H.ld, one, H, none);
     if (fin) hipLaunchKernelGGL((p2d_gemm_kernel<P2D_FIN, ACPre>), g1, dim3(256), 0, e->stream, h.T, P, h.KP, H.nx, W1, W0, nullptr, per, idx, H.ld, one, H, *fin);
     else hipLaunchKernelGGL((p2d_gemm_kernel<P2D_PLAIN, ACPre>), g1, dim3(256), 0, e->stream, h.T, P, h.KP, H.nx, W1, W0, nullptr, per, idx, H.ld, one, H, none);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// The products of one Ginzburg-Landau batch, four launches over two work slab items per state: the first over
+// 2 * count items (r and s of state b staged from both planes of row idx[b] into W1 items 2 b, 2 b + 1, GLPre), the cross product over
+// count states (W1 -> W0, both items of a state read and both written, o Da / Db), then the two-plane products of p2d_gemm_kernel over
+// 2 * count items with nothing left to map -- W0 -> W1, and W1 through the sweep's arithmetic (fin) or into W0.
+int gl_products(mgrit_hip_engine *e, const H2DHost &h, int count, const GLPre &pre, const double *src, const int32_t *idx, const double *dinv,
+                double *W0, double *W1, const H2DFin *fin) {
+    const H2DDev &H = h.dev;
+    const int P = H.Mi;
+    const size_t per = (size_t)P * P;
+    const dim3 g2(P / 64, P / 64, 2 * count), g1(P / 64, P / 64, count);
+    const H2DFin none{};
+    const GSPre two{0.0, 0.0, 0.0, 0};   // (the two-plane instances of the last two products, Gray-Scott's: they stage nothing, pre is not applied)
+    hipLaunchKernelGGL((p2d_gemm_kernel<P2D_FIRST, GLPre>), g2, dim3(256), 0, e->stream, h.T, P, h.KP, H.nx, src, W1, nullptr, per, idx, H.ld, pre, H, none);
+    hipLaunchKernelGGL(p2d_cross_kernel, g1, dim3(256), 0, e->stream, h.T, P, h.KP, W1, W0, dinv, per);
+    hipLaunchKernelGGL((p2d_gemm_kernel<P2D_PLAIN, GSPre>), g2, dim3(256), 0, e->stream, h.T, P, h.KP, H.nx, W0, W1, nullptr, per, idx, H.ld, two, H, none);
+    if (fin) hipLaunchKernelGGL((p2d_gemm_kernel<P2D_FIN, GSPre>), g2, dim3(256), 0, e->stream, h.T, P, h.KP, H.nx, W1, W0, nullptr, per, idx, H.ld, two, H, *fin);
+    else hipLaunchKernelGGL((p2d_gemm_kernel<P2D_PLAIN, GSPre>), g2, dim3(256), 0, e->stream, h.T, P, h.KP, H.nx, W1, W0, nullptr, per, idx, H.ld, two, H, none);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -3550,6 +3590,7 @@ int h2d_phi_batch(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const dou
             if ((rc = ns_sinv(e, lv, &sinv))) return rc;
             return ns_products(e, h, pl.count, dt, in_slab, pl.d_in, sinv, dinv, W0, W1, fin);
         }
+        case H2DKind::GINZBURGLANDAU_IMEX: return gl_products(e, h, pl.count, GLPre{dt, h.gl.c, 0}, in_slab, pl.d_in, dinv, W0, W1, fin);
         case H2DKind::CAHNHILLIARD_IMEX: return ch_products(e, h, pl.count, CHPre{1.0 + h.ch.stab, 0}, in_slab, pl.d_in, dinv, W0, W1, fin);
         default: return p2d_products(e, h, pl.count, ACPre{dt * h.ac.inv_eps2, h.ac.nu}, in_slab, pl.d_in, dinv, W0, W1, W0, fin);
         }
@@ -4723,6 +4764,15 @@ int mgrit_hip_level_navierstokes2d(mgrit_hip_engine *e, int lvl, int n_pts_local
     if ((rc = dev_upload(lv, e->stream, forcing, (size_t)nx * nx, &lv.h2d->ns.f))) return rc;
     lv.set = true;
     return 0;
+}
+
+int mgrit_hip_level_ginzburglandau2d(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld, double inv_dx2,
+                                     double b, double c) {
+    return level_periodic2d(e, lvl, MGRIT_HIP_STEPPER_GINZBURGLANDAU2D, H2DKind::GINZBURGLANDAU_IMEX, n_pts_local, t_local, nx, ld, inv_dx2, "2*nx*nx", [&] {
+        if (!(inv_dx2 > 0.0) || !std::isfinite(inv_dx2) || !std::isfinite(b) || !std::isfinite(c))
+            return fail(MGRIT_HIP_EINVAL, "bad Ginzburg-Landau parameters (inv_dx2=%g must be positive, b=%g, c=%g finite)", inv_dx2, b, c);
+        return 0;
+    }, [&](H2DHost *h) { h->gl = {b, c}; });
 }
 
 int mgrit_hip_level_allencahn2d_newton(mgrit_hip_engine *e, int lvl, int n_pts_local, const double *t_local, int nx, int ld, double inv_dx2,

@@ -1,6 +1,6 @@
 // mgrit_hip_transfer2d.inc -- spatial transfers between two Heat2D levels (MGRIT_HIP_TRANSFER_HEAT2D: grids with their rim,
 // fine size 2 n_c - 1 per axis) and between two levels of one periodic application (MGRIT_HIP_TRANSFER_PERIODIC2D: Allen-Cahn,
-// Cahn-Hilliard, Navier-Stokes, Gray-Scott, Burgers; fine size 2 n_c per axis).
+// Cahn-Hilliard, Navier-Stokes, Gray-Scott, Burgers, Ginzburg-Landau; fine size 2 n_c per axis).
 //
 // The arithmetic is DESIGN.md 3.10, which is GridTransferHeat2D / GridTransferAllenCahn (pymgrit_amd/heat/grid_transfer_heat_2d.py,
 // pymgrit_amd/allen_cahn/grid_transfer_allen_cahn.py) operand by operand: every sum left to right, no FMA (the file is built with
