@@ -35,55 +35,11 @@ import scipy.sparse as sp
 from scipy.sparse.linalg import spsolve
 
 from pymgrit_amd.core.application import Application
-from pymgrit_amd.core.vector import Vector
+from pymgrit_amd.core.plane_vector import OnePlaneVector
 
 
-class VectorAllenCahn2D(Vector):
+class VectorAllenCahn2D(OnePlaneVector):
     """nx x ny grid values of one time point; the norm is the 2-norm over all of them"""
-
-    def __init__(self, nx, ny):
-        super().__init__()
-        self.nx = nx
-        self.ny = ny
-        self.values = np.zeros((nx, ny))
-
-    def _like(self, values):
-        out = VectorAllenCahn2D(self.nx, self.ny)
-        out.set_values(values)
-        return out
-
-    def __add__(self, other):
-        return self._like(self.get_values() + other.get_values())
-
-    def __sub__(self, other):
-        return self._like(self.get_values() - other.get_values())
-
-    def __mul__(self, other):
-        return self._like(self.get_values() * other)
-
-    def norm(self):
-        return np.linalg.norm(self.values)
-
-    def clone(self):
-        return self._like(self.get_values())
-
-    def clone_zero(self):
-        return VectorAllenCahn2D(self.nx, self.ny)
-
-    def clone_rand(self):
-        return self._like(np.random.rand(self.nx, self.ny))
-
-    def set_values(self, values):
-        self.values = values
-
-    def get_values(self):
-        return self.values
-
-    def pack(self):
-        return self.values
-
-    def unpack(self, values):
-        self.values = values
 
 
 def hartley_matrix(n):

@@ -3,44 +3,9 @@ weighting at every coarse point and bilinear interpolation, both with periodic w
 class (its interface, core/grid_transfer.py:31-55, is open); the arithmetic, operand by operand, is DESIGN.md 3.10 -- the
 expressions of GridTransferHeat2D with the indices taken modulo the grid size. HIP kernels via ``device_transfer()``
 (MGRIT_HIP_TRANSFER_PERIODIC2D)."""
-import numpy as np
-
 from pymgrit_amd.allen_cahn.allen_cahn import VectorAllenCahn2D
-from pymgrit_amd.core.grid_transfer import GridTransfer
-
-TRANSFER_PERIODIC2D = 5  # MGRIT_HIP_TRANSFER_PERIODIC2D
+from pymgrit_amd.core.grid_transfer_periodic2d import TRANSFER_PERIODIC2D, GridTransferPeriodic2D  # noqa: F401  (the constant: re-exported)
 
 
-class GridTransferAllenCahn(GridTransfer):
-    def __init__(self):
-        super().__init__()
-
-    def restriction(self, u: VectorAllenCahn2D) -> VectorAllenCahn2D:
-        f = np.asarray(u.get_values())
-        if f.ndim != 2 or f.shape[0] % 2 or f.shape[1] % 2 or min(f.shape) < 2:
-            raise Exception(f"GridTransferAllenCahn restricts even periodic fine grids (2*nc per axis), not {f.shape}")
-        up, left = np.roll(f, 1, axis=0), np.roll(f, 1, axis=1)       # up[i][j] = f[i-1][j], left[i][j] = f[i][j-1]
-        upleft = np.roll(up, 1, axis=1)
-        # the nine terms in the order of GridTransferHeat2D, i = 2I, j = 2J, indices modulo the fine size
-        c = (4 * f[::2, ::2] + 2 * (up[::2, ::2] + f[1::2, ::2] + left[::2, ::2] + f[::2, 1::2]) +
-             upleft[::2, ::2] + up[::2, 1::2] + left[1::2, ::2] + f[1::2, 1::2]) / 16
-        out = VectorAllenCahn2D(*c.shape)
-        out.set_values(c)
-        return out
-
-    def interpolation(self, u: VectorAllenCahn2D) -> VectorAllenCahn2D:
-        c = np.asarray(u.get_values())
-        if c.ndim != 2 or min(c.shape) < 1:
-            raise Exception(f"GridTransferAllenCahn interpolates 2-D periodic coarse grids, not {c.shape}")
-        dn, rt = np.roll(c, -1, axis=0), np.roll(c, -1, axis=1)       # dn[I][J] = c[I+1][J], rt[I][J] = c[I][J+1]
-        f = np.zeros((2 * c.shape[0], 2 * c.shape[1]))
-        f[::2, ::2] = c
-        f[1::2, ::2] = (c + dn) / 2
-        f[::2, 1::2] = (c + rt) / 2
-        f[1::2, 1::2] = (c + dn + rt + np.roll(dn, -1, axis=1)) / 4
-        out = VectorAllenCahn2D(*f.shape)
-        out.set_values(f)
-        return out
-
-    def device_transfer(self) -> int:
-        return TRANSFER_PERIODIC2D
+class GridTransferAllenCahn(GridTransferPeriodic2D):
+    VECTOR, PLANES = VectorAllenCahn2D, 1

@@ -3,22 +3,9 @@ GridTransferAllenCahn, operand by operand (9-point full weighting, bilinear inte
 applied to each of the two velocity planes of a state on its own, returning VectorBurgers2D. HIP kernels via ``device_transfer()``
 (MGRIT_HIP_TRANSFER_PERIODIC2D, which joins two Burgers levels as it joins two Allen-Cahn levels; the kernels take the planes of a
 row). L and nu are properties of the problem and stay fixed while dx doubles."""
-from pymgrit_amd.allen_cahn.grid_transfer_allen_cahn import TRANSFER_PERIODIC2D, GridTransferAllenCahn
 from pymgrit_amd.burgers.burgers import VectorBurgers2D
-from pymgrit_amd.core.grid_transfer import GridTransfer
-from pymgrit_amd.gray_scott.grid_transfer_gray_scott import per_plane
+from pymgrit_amd.core.grid_transfer_periodic2d import GridTransferPeriodic2D
 
 
-class GridTransferBurgers(GridTransfer):
-    def __init__(self):
-        super().__init__()
-        self._periodic = GridTransferAllenCahn()
-
-    def restriction(self, u: VectorBurgers2D) -> VectorBurgers2D:
-        return per_plane(self._periodic.restriction, u, "GridTransferBurgers restricts", VectorBurgers2D, even=True)
-
-    def interpolation(self, u: VectorBurgers2D) -> VectorBurgers2D:
-        return per_plane(self._periodic.interpolation, u, "GridTransferBurgers interpolates", VectorBurgers2D)
-
-    def device_transfer(self) -> int:
-        return TRANSFER_PERIODIC2D
+class GridTransferBurgers(GridTransferPeriodic2D):
+    VECTOR, PLANES = VectorBurgers2D, 2

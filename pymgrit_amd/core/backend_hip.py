@@ -317,49 +317,26 @@ class HipBackend:
             self.FB[engine_lvl] = rows
             check(self.lib.mgrit_hip_level_heat2d_forcing_rows(self.h, engine_lvl, C.c_void_p(rows.data_ptr())))
 
-    def _describe_allencahn2d(self, engine_lvl, d, t_local, n, ld):
-        """IMEX, or -- a description that carries theta -- the Newton-PCG step of IMPL / CN"""
-        common = (self.h, engine_lvl, t_local.size, _ptr(t_local), int(d["nx"]), ld, float(d["inv_dx2"]), float(d["inv_eps2"]), int(d["nu"]))
-        if "theta" in d:      # (through hip_lib: the recorded call sequences of this file's own exports stay as they are)
-            hip_lib.level_allencahn2d_newton(*common, d)
-        else:
-            check(self.lib.mgrit_hip_level_allencahn2d(*common))
-
-    def _describe_grayscott2d(self, engine_lvl, d, t_local, n, ld):
-        """IMEX, two planes per state, or -- a description that carries theta -- the Newton-BiCGStab step of IMPL (DESIGN.md 3.11;
-        through hip_lib like the Allen-Cahn Newton form above)"""
-        describe = hip_lib.level_grayscott2d_newton if "theta" in d else hip_lib.level_grayscott2d
-        describe(self.h, engine_lvl, t_local.size, _ptr(t_local), ld, d)
-
-    def _describe_cahnhilliard2d(self, engine_lvl, d, t_local, n, ld):
-        """the stabilised IMEX step, one plane per state (through hip_lib like the Gray-Scott forms above)"""
-        hip_lib.level_cahnhilliard2d(self.h, engine_lvl, t_local.size, _ptr(t_local), ld, d)
-
-    def _describe_burgers2d(self, engine_lvl, d, t_local, n, ld):
-        """the IMEX step, two planes per state, a stencil pass in front of the products"""
-        hip_lib.level_burgers2d(self.h, engine_lvl, t_local.size, _ptr(t_local), ld, d)
-
-    def _describe_navierstokes2d(self, engine_lvl, d, t_local, n, ld):
-        """the vorticity IMEX step, one plane per state, a stencil pass between two sets of four products"""
-        f = d.get("forcing")
-        if f is not None:
-            f = np.ascontiguousarray(f, dtype=np.float64)
-            if f.shape != (int(d["nx"]), int(d["nx"])):
-                raise MgritHipError(f"Navier-Stokes levels on the HIP engine: forcing of shape {f.shape}, not ({d['nx']}, {d['nx']})")
-        hip_lib.level_navierstokes2d(self.h, engine_lvl, t_local.size, _ptr(t_local), ld, d, _ptr(f) if f is not None else C.c_void_p(0))
-
-    def _describe_ginzburglandau2d(self, engine_lvl, d, t_local, n, ld):
-        """the IMEX step, two planes per state that the implicit operator couples mode by mode"""
-        hip_lib.level_ginzburglandau2d(self.h, engine_lvl, t_local.size, _ptr(t_local), ld, d)
+    def _describe_periodic2d(self, engine_lvl, d, t_local, n, ld):
+        """a level of a PERIODIC_2D kind, IMEX or -- a description that carries theta -- its Newton form: the export and its arguments
+        by hip_lib.LEVEL_2D, the call made here"""
+        tail = ()
+        if d["kind"] == "navierstokes2d":
+            f = d.get("forcing")
+            if f is not None:
+                f = np.ascontiguousarray(f, dtype=np.float64)
+                if f.shape != (int(d["nx"]), int(d["nx"])):
+                    raise MgritHipError(f"Navier-Stokes levels on the HIP engine: forcing of shape {f.shape}, not ({d['nx']}, {d['nx']})")
+            tail = (_ptr(f) if f is not None else C.c_void_p(0),)
+        name, args = hip_lib.level_2d_call(self.h, engine_lvl, t_local.size, _ptr(t_local), ld, d, *tail)
+        check(getattr(self.lib, name)(*args))
 
     def newton_stats(self, lvl):
         """counts of a Newton level (Allen-Cahn PCG, Gray-Scott BiCGStab) since the last call (which resets them)"""
         return hip_lib.newton_stats(self.h, lvl)
 
     _DESCRIBE = {"heat1d": _describe_heat1d, "heat1d_2pts": _describe_heat1d_2pts, "advection1d": _describe_advection1d,
-                 "heat2d": _describe_heat2d, "allencahn2d": _describe_allencahn2d, "grayscott2d": _describe_grayscott2d,
-                 "cahnhilliard2d": _describe_cahnhilliard2d, "burgers2d": _describe_burgers2d,
-                 "navierstokes2d": _describe_navierstokes2d, "ginzburglandau2d": _describe_ginzburglandau2d}
+                 "heat2d": _describe_heat2d, **dict.fromkeys(PERIODIC_2D, _describe_periodic2d)}
 
     def _describe(self, engine_lvl, lvl, t_local):
         """tell the engine what level engine_lvl is: the stepper of level lvl on the time points t_local"""

@@ -192,49 +192,34 @@ def row_permutation(n):
     return perm
 
 
-def level_allencahn2d_newton(h, engine_lvl, n_pts, t_ptr, nx, ld, inv_dx2, inv_eps2, nu, d):
-    """describe an Allen-Cahn level whose Phi is the Newton-PCG step; d: the application's description"""
-    check(load().mgrit_hip_level_allencahn2d_newton(h, engine_lvl, n_pts, t_ptr, nx, ld, inv_dx2, inv_eps2, nu, float(d["theta"]),
-                                                    float(d["newton_tol"]), int(d["newton_maxiter"]), float(d["lin_tol"]),
-                                                    int(d["lin_maxiter"])))
+# The level descriptions of the periodic 2-D kinds, kind -> (the IMEX export, the Newton export or None,
+# the keys of the application's description that follow (h, level, n_pts, t, nx, ld) in the export's argument order, the keys the
+# Newton export takes after those). A description that carries theta is a Newton level's. The C type of a key is its argument's in EXPORTS.
+_NEWTON = ("newton_tol", "newton_maxiter", "lin_tol", "lin_maxiter")
+LEVEL_2D = {
+    "allencahn2d": ("mgrit_hip_level_allencahn2d", "mgrit_hip_level_allencahn2d_newton", ("inv_dx2", "inv_eps2", "nu"), ("theta",) + _NEWTON),
+    "grayscott2d": ("mgrit_hip_level_grayscott2d", "mgrit_hip_level_grayscott2d_newton", ("inv_dx2", "du", "dv", "a", "b"), _NEWTON),
+    "cahnhilliard2d": ("mgrit_hip_level_cahnhilliard2d", None, ("inv_dx2", "eps2", "stab"), ()),
+    "burgers2d": ("mgrit_hip_level_burgers2d", None, ("inv_dx2", "inv_2dx", "nu"), ()),
+    "navierstokes2d": ("mgrit_hip_level_navierstokes2d", None, ("inv_dx2", "inv_2dx", "nu"), ()),      # (+ the forcing plane or NULL)
+    "ginzburglandau2d": ("mgrit_hip_level_ginzburglandau2d", None, ("inv_dx2", "b", "c"), ()),
+}
 
 
-def level_grayscott2d(h, engine_lvl, n_pts, t_ptr, ld, d):
-    """describe a Gray-Scott IMEX level; d: the application's description"""
-    check(load().mgrit_hip_level_grayscott2d(h, engine_lvl, n_pts, t_ptr, int(d["nx"]), ld, float(d["inv_dx2"]), float(d["du"]),
-                                             float(d["dv"]), float(d["a"]), float(d["b"])))
+def level_2d_call(h, engine_lvl, n_pts, t_ptr, ld, d, *tail):
+    """(export name, argument tuple) that describes a periodic 2-D level; d: the application's description, tail: what the export takes
+    behind the description's values (Navier-Stokes: the forcing, nx * nx doubles in natural order, which the library copies, or NULL)"""
+    imex, newton, keys, newton_keys = LEVEL_2D[d["kind"]]
+    name, keys = (newton, keys + newton_keys) if "theta" in d else (imex, keys)
+    types = EXPORTS[name][1][6:]
+    values = tuple((float if t is C.c_double else int)(d[k]) for k, t in zip(keys, types))
+    return name, (h, engine_lvl, n_pts, t_ptr, int(d["nx"]), ld) + values + tail
 
 
-def level_grayscott2d_newton(h, engine_lvl, n_pts, t_ptr, ld, d):
-    """describe a Gray-Scott level whose Phi is the Newton-BiCGStab step; d: the application's description"""
-    check(load().mgrit_hip_level_grayscott2d_newton(h, engine_lvl, n_pts, t_ptr, int(d["nx"]), ld, float(d["inv_dx2"]), float(d["du"]),
-                                                    float(d["dv"]), float(d["a"]), float(d["b"]), float(d["newton_tol"]),
-                                                    int(d["newton_maxiter"]), float(d["lin_tol"]), int(d["lin_maxiter"])))
-
-
-def level_burgers2d(h, engine_lvl, n_pts, t_ptr, ld, d):
-    """describe a Burgers IMEX level; d: the application's description"""
-    check(load().mgrit_hip_level_burgers2d(h, engine_lvl, n_pts, t_ptr, int(d["nx"]), ld, float(d["inv_dx2"]), float(d["inv_2dx"]),
-                                           float(d["nu"])))
-
-
-def level_navierstokes2d(h, engine_lvl, n_pts, t_ptr, ld, d, forcing_ptr):
-    """describe a Navier-Stokes IMEX level; d: the application's description, forcing_ptr: nx * nx doubles in natural
-    order, which the library copies, or NULL"""
-    check(load().mgrit_hip_level_navierstokes2d(h, engine_lvl, n_pts, t_ptr, int(d["nx"]), ld, float(d["inv_dx2"]), float(d["inv_2dx"]),
-                                                float(d["nu"]), forcing_ptr))
-
-
-def level_ginzburglandau2d(h, engine_lvl, n_pts, t_ptr, ld, d):
-    """describe a Ginzburg-Landau IMEX level; d: the application's description"""
-    check(load().mgrit_hip_level_ginzburglandau2d(h, engine_lvl, n_pts, t_ptr, int(d["nx"]), ld, float(d["inv_dx2"]), float(d["b"]),
-                                                  float(d["c"])))
-
-
-def level_cahnhilliard2d(h, engine_lvl, n_pts, t_ptr, ld, d):
-    """describe a Cahn-Hilliard IMEX level; d: the application's description"""
-    check(load().mgrit_hip_level_cahnhilliard2d(h, engine_lvl, n_pts, t_ptr, int(d["nx"]), ld, float(d["inv_dx2"]), float(d["eps2"]),
-                                                float(d["stab"])))
+def level_2d(h, engine_lvl, n_pts, t_ptr, ld, d, *tail):
+    """describe a periodic 2-D level (level_2d_call) and raise on refusal"""
+    name, args = level_2d_call(h, engine_lvl, n_pts, t_ptr, ld, d, *tail)
+    check(getattr(load(), name)(*args))
 
 
 def settle(h, lvl):

@@ -3127,6 +3127,18 @@ void p2d_fill_dinv(const H2DHost &h, double *tab, double shift, double coef) {
         for (int b = 0; b < h.dev.nx; ++b) tab[(size_t)a * h.dev.Mj + b] = 1.0 / (shift + coef * (h.lx[a] + h.ly[b]));
 }
 
+// the two [P][P] tables of a periodic level whose modes carry a pair of factors, natural mode order: (first, second) = f(lam_a + lam_b)
+template <typename Fn>
+void p2d_fill_pair(const H2DHost &h, double *tab, Fn f) {
+    const size_t per = (size_t)h.dev.Mi * h.dev.Mj;
+    for (int a = 0; a < h.dev.nx; ++a)
+        for (int b = 0; b < h.dev.nx; ++b) {
+            const std::pair<double, double> d = f(h.lx[a] + h.ly[b]);
+            tab[(size_t)a * h.dev.Mj + b] = d.first;
+            tab[per + (size_t)a * h.dev.Mj + b] = d.second;
+        }
+}
+
 // D of the level's implicit solve: Heat2D 1 / (1 + theta dt (lx + ly)) in spectral slot order on both axes, 0 where no mode lives;
 // Allen-Cahn IMEX 1 / (1 + dt (lam_a + lam_b)); Gray-Scott [2][P][P], species u then v, 1 / (1 + (dt d_c) (lam_a + lam_b)), the operand
 // order of GrayScott._dinv; Cahn-Hilliard [2][P][P], D1 = 1 / (1 + dt (eps^2 mu^2 + s mu)) then D2 = -(dt mu) D1, mu = lam_a + lam_b, the
@@ -3148,13 +3160,10 @@ int h2d_dinv(mgrit_hip_engine *e, Level &lv, uint64_t dtbits, double **out) {
             p2d_fill_dinv(h, tab + per, 1.0, dt * h.gs.dv);
             break;
         case H2DKind::CAHNHILLIARD_IMEX:
-            for (int a = 0; a < h.dev.nx; ++a)
-                for (int b = 0; b < h.dev.nx; ++b) {
-                    const double mu = h.lx[a] + h.ly[b];
-                    const double d1 = 1.0 / (1.0 + dt * (h.ch.eps2 * mu * mu + h.ch.stab * mu));
-                    tab[(size_t)a * h.dev.Mj + b] = d1;
-                    tab[per + (size_t)a * h.dev.Mj + b] = -(dt * mu) * d1;
-                }
+            p2d_fill_pair(h, tab, [&](double mu) {
+                const double d1 = 1.0 / (1.0 + dt * (h.ch.eps2 * mu * mu + h.ch.stab * mu));
+                return std::make_pair(d1, -(dt * mu) * d1);
+            });
             break;
         case H2DKind::BURGERS_IMEX:
             p2d_fill_dinv(h, tab, 1.0, dt * h.bg.nu);
@@ -3163,14 +3172,11 @@ int h2d_dinv(mgrit_hip_engine *e, Level &lv, uint64_t dtbits, double **out) {
         case H2DKind::NAVIERSTOKES_IMEX: p2d_fill_dinv(h, tab, 1.0, dt * h.ns.nu); break;
         case H2DKind::GINZBURGLANDAU_IMEX: {
             const double bdt = h.gl.b * dt;
-            for (int a = 0; a < h.dev.nx; ++a)
-                for (int b = 0; b < h.dev.nx; ++b) {
-                    const double mu = h.lx[a] + h.ly[b];
-                    const double re = 1.0 + dt * mu, im = bdt * mu;
-                    const double det = re * re + im * im;
-                    tab[(size_t)a * h.dev.Mj + b] = re / det;
-                    tab[per + (size_t)a * h.dev.Mj + b] = im / det;
-                }
+            p2d_fill_pair(h, tab, [&](double mu) {
+                const double re = 1.0 + dt * mu, im = bdt * mu;
+                const double det = re * re + im * im;
+                return std::make_pair(re / det, im / det);
+            });
             break;
         }
         default: p2d_fill_dinv(h, tab, 1.0, dt);   // Allen-Cahn (the Newton kinds have their own tables: newton_dinv)
@@ -3195,125 +3201,104 @@ int ns_sinv(mgrit_hip_engine *e, Level &lv, double **out) {
     return 0;
 }
 
-// The four Hartley products of one batch on a periodic level (mgrit_hip_periodic2d.inc), PRE::operands work slab items per state:
-// the first from src, through W1, W0 (o dinv) and W1 again, the last through the sweep's arithmetic (fin) or into out.
-// FLAGS = false: src is the state slab, the operand of state b its row idx[b], mapped by pre while it is staged.
-// FLAGS = true (the preconditioner of the Newton-PCG steps): src is a work row, idx[b] the item's "CG running" flag -- the products of
-// an item whose flag is 0 return at once --, pre is not applied.
-template <class PRE, bool FLAGS = false>
-int p2d_products(mgrit_hip_engine *e, const H2DHost &h, int count, const PRE &pre, const double *src, const int32_t *idx, const double *dinv,
-                 double *W0, double *W1, double *out, const H2DFin *fin) {
-    constexpr int FIRST = FLAGS ? P2D_WORK_PLAIN : P2D_FIRST, SCALE = FLAGS ? P2D_WORK_SCALE : P2D_SCALE, PLAIN = FLAGS ? P2D_WORK_PLAIN : P2D_PLAIN;
-    const H2DDev &H = h.dev;
-    const int P = H.Mi;
-    const size_t per = (size_t)P * P;
-    const dim3 g(P / 64, P / 64, PRE::operands * count);
-    const H2DFin none{};
-    auto launch = [&](auto kernel, const double *B, double *o, const double *d, const H2DFin &F) {
-        hipLaunchKernelGGL(kernel, g, dim3(256), 0, e->stream, h.T, P, h.KP, H.nx, B, o, d, per, idx, H.ld, pre, H, F);
-    };
-    launch(&p2d_gemm_kernel<FIRST, PRE>, src, W1, nullptr, none);
-    launch(&p2d_gemm_kernel<SCALE, PRE>, W1, W0, dinv, none);
-    launch(&p2d_gemm_kernel<PLAIN, PRE>, W0, W1, nullptr, none);
-    if (fin) launch(&p2d_gemm_kernel<P2D_FIN, PRE>, W1, out, nullptr, *fin);
-    else launch(&p2d_gemm_kernel<PLAIN, PRE>, W1, out, nullptr, none);
-    HIP_TRY(hipGetLastError());
-    return 0;
+// "N planes, nothing left to map": the PRE of a product whose operand is a work slab item of a kind that has no map of its own to
+// apply there -- the kernel stages nothing from a state row in these modes and never calls pre, only PRE::operands / PRE::items tell it
+// how many planes a state has. The one-plane and the two-plane instances that exist are Allen-Cahn's and Gray-Scott's, so these are
+// their types, zeroed: no further instances of p2d_gemm_kernel, no other kernarg layout.
+template <int PLANES>
+std::conditional_t<PLANES == 1, ACPre, GSPre> p2d_planes() {
+    static_assert(PLANES == 1 || PLANES == 2, "one plane or two");
+    return {};
 }
 
-// The products of one Cahn-Hilliard batch, six item-products per state: the first over 2 * count items (u and w(u) of
-// state b staged from row idx[b] into W1 items 2 b, 2 b + 1), the combine product over count states (W1 -> W0 item b, o D1 / D2), then the
-// one-plane products of p2d_gemm_kernel over count items -- W0 -> W1, and W1 through the sweep's arithmetic (fin) or into W0.
-int ch_products(mgrit_hip_engine *e, const H2DHost &h, int count, const CHPre &pre, const double *src, const int32_t *idx, const double *dinv,
-                double *W0, double *W1, const H2DFin *fin) {
-    const H2DDev &H = h.dev;
-    const int P = H.Mi;
-    const size_t per = (size_t)P * P;
-    const dim3 g2(P / 64, P / 64, 2 * count), g1(P / 64, P / 64, count);
-    const H2DFin none{};
-    const ACPre one{0.0, 0};   // (the one-plane instances of the last two products: they stage nothing, pre is not applied)
-    hipLaunchKernelGGL((p2d_gemm_kernel<P2D_FIRST, CHPre>), g2, dim3(256), 0, e->stream, h.T, P, h.KP, H.nx, src, W1, nullptr, per, idx, H.ld, pre, H, none);
-    hipLaunchKernelGGL(p2d_combine_kernel, g1, dim3(256), 0, e->stream, h.T, P, h.KP, W1, W0, dinv, per);
-    hipLaunchKernelGGL((p2d_gemm_kernel<P2D_PLAIN, ACPre>), g1, dim3(256), 0, e->stream, h.T, P, h.KP, H.nx, W0, W1, nullptr, per, idx, H.ld, one, H, none);
-    if (fin) hipLaunchKernelGGL((p2d_gemm_kernel<P2D_FIN, ACPre>), g1, dim3(256), 0, e->stream, h.T, P, h.KP, H.nx, W1, W0, nullptr, per, idx, H.ld, one, H, *fin);
-    else hipLaunchKernelGGL((p2d_gemm_kernel<P2D_PLAIN, ACPre>), g1, dim3(256), 0, e->stream, h.T, P, h.KP, H.nx, W1, W0, nullptr, per, idx, H.ld, one, H, none);
-    HIP_TRY(hipGetLastError());
-    return 0;
+// What the launches of one batch of count states on a periodic level share (mgrit_hip_periodic2d.inc). idx[b]: the row of state b in
+// the slab a P2D_FIRST product stages from (or, in the work modes, the item's "running" flag: the products of an item whose flag is 0
+// return at once).
+struct P2DBatch {
+    mgrit_hip_engine *e;
+    const H2DHost &h;
+    const H2DDev &H;
+    const int count, P;
+    const size_t per;
+    const int32_t *idx;
+    P2DBatch(mgrit_hip_engine *e, const H2DHost &h, int count, const int32_t *idx)
+        : e(e), h(h), H(h.dev), count(count), P(h.dev.Mi), per((size_t)P * P), idx(idx) {}
+    dim3 tiles(int items) const { return dim3(P / 64, P / 64, items * count); }             // the products, items work slab items per state
+    dim3 stencil() const { return dim3(P / BG_TJ, P / BG_TI, count); }                      // bg_rhs_kernel / ns_rhs_kernel, whole items
+    // one Hartley product over items * count work slab items: dst = T src (o table in the SCALE modes), src mapped by pre while it
+    // is staged from the state rows (P2D_FIRST), dst through the sweep's arithmetic (P2D_FIN, fin)
+    template <int MODE, class PRE>
+    void product(const PRE &pre, int items, const double *src, double *dst, const double *table = nullptr, const H2DFin &fin = H2DFin{}) const {
+        hipLaunchKernelGGL((p2d_gemm_kernel<MODE, PRE>), tiles(items), dim3(256), 0, e->stream, h.T, P, h.KP, H.nx, src, dst, table, per, idx, H.ld, pre, H, fin);
+    }
+    // the product that joins the two items of a state mode by mode (p2d_combine_kernel: two into one; p2d_cross_kernel: two into two)
+    template <class KERNEL>
+    void joined(KERNEL kernel, const double *src, double *dst, const double *table) const {
+        hipLaunchKernelGGL(kernel, tiles(1), dim3(256), 0, e->stream, h.T, P, h.KP, src, dst, table, per);
+    }
+    // the last two products of every recipe: W0 -> W1, then W1 through the sweep's arithmetic (fin) or into out
+    template <bool WORK = false, class PRE>
+    int tail(const PRE &pre, int items, double *W0, double *W1, double *out, const H2DFin *fin) const {
+        constexpr int PLAIN = WORK ? P2D_WORK_PLAIN : P2D_PLAIN;
+        product<PLAIN>(pre, items, W0, W1);
+        if (fin) product<P2D_FIN>(pre, items, W1, out, nullptr, *fin);
+        else product<PLAIN>(pre, items, W1, out);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+};
+
+// The four products of Allen-Cahn and Gray-Scott: src -> W1, W1 -> W0 (o dinv), and the tail. WORK = true, the
+// preconditioner of the Newton steps: src is a work row, pre = p2d_planes, B.idx the items' "running" flags.
+template <bool WORK = false, class PRE>
+int p2d_four_products(const P2DBatch &B, const PRE &pre, const double *src, const double *dinv, double *W0, double *W1, double *out, const H2DFin *fin) {
+    B.product<WORK ? P2D_WORK_PLAIN : P2D_FIRST>(pre, PRE::items, src, W1);
+    B.product<WORK ? P2D_WORK_SCALE : P2D_SCALE>(pre, PRE::items, W1, W0, dinv);
+    return B.tail<WORK>(pre, PRE::items, W0, W1, out, fin);
 }
 
-// The products of one Ginzburg-Landau batch, four launches over two work slab items per state: the first over
-// 2 * count items (r and s of state b staged from both planes of row idx[b] into W1 items 2 b, 2 b + 1, GLPre), the cross product over
-// count states (W1 -> W0, both items of a state read and both written, o Da / Db), then the two-plane products of p2d_gemm_kernel over
-// 2 * count items with nothing left to map -- W0 -> W1, and W1 through the sweep's arithmetic (fin) or into W0.
-int gl_products(mgrit_hip_engine *e, const H2DHost &h, int count, const GLPre &pre, const double *src, const int32_t *idx, const double *dinv,
-                double *W0, double *W1, const H2DFin *fin) {
-    const H2DDev &H = h.dev;
-    const int P = H.Mi;
-    const size_t per = (size_t)P * P;
-    const dim3 g2(P / 64, P / 64, 2 * count), g1(P / 64, P / 64, count);
-    const H2DFin none{};
-    const GSPre two{0.0, 0.0, 0.0, 0};   // (the two-plane instances of the last two products, Gray-Scott's: they stage nothing, pre is not applied)
-    hipLaunchKernelGGL((p2d_gemm_kernel<P2D_FIRST, GLPre>), g2, dim3(256), 0, e->stream, h.T, P, h.KP, H.nx, src, W1, nullptr, per, idx, H.ld, pre, H, none);
-    hipLaunchKernelGGL(p2d_cross_kernel, g1, dim3(256), 0, e->stream, h.T, P, h.KP, W1, W0, dinv, per);
-    hipLaunchKernelGGL((p2d_gemm_kernel<P2D_PLAIN, GSPre>), g2, dim3(256), 0, e->stream, h.T, P, h.KP, H.nx, W0, W1, nullptr, per, idx, H.ld, two, H, none);
-    if (fin) hipLaunchKernelGGL((p2d_gemm_kernel<P2D_FIN, GSPre>), g2, dim3(256), 0, e->stream, h.T, P, h.KP, H.nx, W1, W0, nullptr, per, idx, H.ld, two, H, *fin);
-    else hipLaunchKernelGGL((p2d_gemm_kernel<P2D_PLAIN, GSPre>), g2, dim3(256), 0, e->stream, h.T, P, h.KP, H.nx, W1, W0, nullptr, per, idx, H.ld, two, H, none);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// The five launches of one Burgers batch: the stencil pass forms b_u, b_v of state b from row idx[b] into W0 items
-// 2 b, 2 b + 1 (bg_rhs_kernel, whole items, pads zero), then the products of p2d_products over 2 * count work slab items with nothing
-// left to map -- W0 -> W1, W1 -> W0 (o dinv), W0 -> W1, and W1 through the sweep's arithmetic (fin) or into W0.
-int bg_products(mgrit_hip_engine *e, const H2DHost &h, int count, double dt, const double *src, const int32_t *idx, const double *dinv,
-                double *W0, double *W1, const H2DFin *fin) {
-    const H2DDev &H = h.dev;
-    const int P = H.Mi;
-    const size_t per = (size_t)P * P;
-    const dim3 g(P / 64, P / 64, 2 * count);
-    const H2DFin nofin{};
-    const GSPre none{0.0, 0.0, 0.0, 0};   // (the work-slab modes of the products apply no map; its two operands make them two-plane)
-    auto launch = [&](auto kernel, const double *B, double *o, const double *d, const H2DFin &F) {
-        hipLaunchKernelGGL(kernel, g, dim3(256), 0, e->stream, h.T, P, h.KP, H.nx, B, o, d, per, idx, H.ld, none, H, F);
-    };
-    hipLaunchKernelGGL(bg_rhs_kernel, dim3(P / BG_TJ, P / BG_TI, count), dim3(256), 0, e->stream, H.nx, P, src, idx, H.ld, dt, h.bg.inv_2dx, W0, per);
-    launch(&p2d_gemm_kernel<P2D_PLAIN, GSPre>, W0, W1, nullptr, nofin);
-    launch(&p2d_gemm_kernel<P2D_SCALE, GSPre>, W1, W0, dinv, nofin);
-    launch(&p2d_gemm_kernel<P2D_PLAIN, GSPre>, W0, W1, nullptr, nofin);
-    if (fin) launch(&p2d_gemm_kernel<P2D_FIN, GSPre>, W1, W0, nullptr, *fin);
-    else launch(&p2d_gemm_kernel<P2D_PLAIN, GSPre>, W1, W0, nullptr, nofin);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// The nine launches of one Navier-Stokes batch, one work slab item per state. The stream-function solve: w of state b
-// staged from row idx[b] (NSPre, the identity) -> W0, W0 -> W1 (o sinv), W1 -> W0, W0 -> W1 = psi. The stencil pass forms b from the psi
-// items and the state rows into W0 (ns_rhs_kernel, whole items, pads zero). Then the products of p2d_products with nothing left to map:
-// W0 -> W1, W1 -> W0 (o dinv), W0 -> W1, and W1 through the sweep's arithmetic (fin) or into W0. The state rows are read by the first
-// and the fifth launch and written by the ninth only.
-int ns_products(mgrit_hip_engine *e, const H2DHost &h, int count, double dt, const double *src, const int32_t *idx, const double *sinv,
-                const double *dinv, double *W0, double *W1, const H2DFin *fin) {
-    const H2DDev &H = h.dev;
-    const int P = H.Mi;
-    const size_t per = (size_t)P * P;
-    const dim3 g(P / 64, P / 64, count);
-    const H2DFin nofin{};
-    const ACPre one{0.0, 0};   // (the one-plane instances of the work-slab modes: they stage nothing, pre is not applied)
-    auto launch = [&](auto kernel, const double *B, double *o, const double *d, const H2DFin &F) {
-        hipLaunchKernelGGL(kernel, g, dim3(256), 0, e->stream, h.T, P, h.KP, H.nx, B, o, d, per, idx, H.ld, one, H, F);
-    };
-    hipLaunchKernelGGL((p2d_gemm_kernel<P2D_FIRST, NSPre>), g, dim3(256), 0, e->stream, h.T, P, h.KP, H.nx, src, W0, nullptr, per, idx, H.ld, NSPre{}, H, nofin);
-    launch(&p2d_gemm_kernel<P2D_SCALE, ACPre>, W0, W1, sinv, nofin);
-    launch(&p2d_gemm_kernel<P2D_PLAIN, ACPre>, W1, W0, nullptr, nofin);
-    launch(&p2d_gemm_kernel<P2D_PLAIN, ACPre>, W0, W1, nullptr, nofin);
-    hipLaunchKernelGGL(ns_rhs_kernel, dim3(P / BG_TJ, P / BG_TI, count), dim3(256), 0, e->stream, H.nx, P, W1, src, idx, H.ld, h.ns.f, dt, h.ns.inv_2dx, W0, per);
-    launch(&p2d_gemm_kernel<P2D_PLAIN, ACPre>, W0, W1, nullptr, nofin);
-    launch(&p2d_gemm_kernel<P2D_SCALE, ACPre>, W1, W0, dinv, nofin);
-    launch(&p2d_gemm_kernel<P2D_PLAIN, ACPre>, W0, W1, nullptr, nofin);
-    if (fin) launch(&p2d_gemm_kernel<P2D_FIN, ACPre>, W1, W0, nullptr, *fin);
-    else launch(&p2d_gemm_kernel<P2D_PLAIN, ACPre>, W1, W0, nullptr, nofin);
-    HIP_TRY(hipGetLastError());
-    return 0;
+// Phi of one batch of an IMEX kind on the periodic grid, the launch list of the kind's section of DESIGN.md line by line: the rows
+// src[pl.d_in[b]] -> W0, or through the sweep's arithmetic (fin). State b owns the work slab items NI b .. NI b + NI - 1.
+int p2d_imex_products(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const double *src, const double *dinv, double *W0, double *W1,
+                      const H2DFin *fin) {
+    const H2DHost &h = *lv.h2d;
+    const P2DBatch B(e, h, pl.count, pl.d_in);
+    const auto one = p2d_planes<1>();
+    const auto two = p2d_planes<2>();
+    double dt;
+    std::memcpy(&dt, &pl.dtbits, 8);
+    switch (h.kind) {
+    case H2DKind::GRAYSCOTT_IMEX:   // 3.11: both species at once, items 2 b (u) and 2 b + 1 (v), the reaction terms formed while staged
+        return p2d_four_products(B, GSPre{dt, h.gs.a, h.gs.b, 0}, src, dinv, W0, W1, W0, fin);
+    case H2DKind::CAHNHILLIARD_IMEX:   // 3.12: u and w(u) staged from one plane, joined into one item (o D1 / D2), then one plane
+        B.product<P2D_FIRST>(CHPre{1.0 + h.ch.stab, 0}, 2, src, W1);
+        B.joined(p2d_combine_kernel, W1, W0, dinv);
+        return B.tail(one, 1, W0, W1, W0, fin);
+    case H2DKind::BURGERS_IMEX:   // 3.13: the stencil pass forms b_u, b_v into items 2 b, 2 b + 1 (whole items, pads zero)
+        hipLaunchKernelGGL(bg_rhs_kernel, B.stencil(), dim3(256), 0, e->stream, B.H.nx, B.P, src, B.idx, B.H.ld, dt, h.bg.inv_2dx, W0, B.per);
+        B.product<P2D_PLAIN>(two, 2, W0, W1);
+        B.product<P2D_SCALE>(two, 2, W1, W0, dinv);
+        return B.tail(two, 2, W0, W1, W0, fin);
+    case H2DKind::NAVIERSTOKES_IMEX: {   // 3.14: the stream-function solve, the stencil pass on psi and the state rows, the implicit solve
+        double *sinv = nullptr;
+        int rc;
+        if ((rc = ns_sinv(e, lv, &sinv))) return rc;
+        B.product<P2D_FIRST>(NSPre{}, 1, src, W0);
+        B.product<P2D_SCALE>(one, 1, W0, W1, sinv);
+        B.product<P2D_PLAIN>(one, 1, W1, W0);
+        B.product<P2D_PLAIN>(one, 1, W0, W1);   // = psi
+        hipLaunchKernelGGL(ns_rhs_kernel, B.stencil(), dim3(256), 0, e->stream, B.H.nx, B.P, W1, src, B.idx, B.H.ld, h.ns.f, dt, h.ns.inv_2dx, W0, B.per);
+        B.product<P2D_PLAIN>(one, 1, W0, W1);
+        B.product<P2D_SCALE>(one, 1, W1, W0, dinv);
+        return B.tail(one, 1, W0, W1, W0, fin);
+    }
+    case H2DKind::GINZBURGLANDAU_IMEX:   // 3.15: r and s staged from both planes, the cross product (o Da / Db), then two planes
+        B.product<P2D_FIRST>(GLPre{dt, h.gl.c, 0}, 2, src, W1);
+        B.joined(p2d_cross_kernel, W1, W0, dinv);
+        return B.tail(two, 2, W0, W1, W0, fin);
+    default:   // Allen-Cahn, 3.9: the non-linear right-hand side formed while the first product is staged
+        return p2d_four_products(B, ACPre{dt * h.ac.inv_eps2, h.ac.nu}, src, dinv, W0, W1, W0, fin);
+    }
 }
 
 // ---- Newton steps of the periodic levels: Allen-Cahn Newton-PCG, Gray-Scott Newton-BiCGStab (3.11) -----------------
@@ -3432,7 +3417,7 @@ struct ACNBatch {
     }
     int inner() const {   // one CG iteration
         int rc;
-        if ((rc = (p2d_products<ACPre, true>(B.e, B.h, B.pl.count, ACPre{0.0, 0}, r, S.cg, B.dinv, W0, W1, z, nullptr)))) return rc;
+        if ((rc = p2d_four_products<true>(P2DBatch(B.e, B.h, B.pl.count, S.cg), p2d_planes<1>(), r, B.dinv, W0, W1, z, nullptr))) return rc;
         hipLaunchKernelGGL(acn_dot_kernel, B.ge, B.b256, 0, st, A, S, r, z, per);
         reduce<ACN_R_RZ>();
         hipLaunchKernelGGL(acn_dir_kernel, B.ge, B.b256, 0, st, A, S, z, p, per);
@@ -3459,7 +3444,6 @@ struct GSNBatch {
     double *const z, *const t;   // (between the products of z and those of the next y)
     const GSNState S;
     const GSNPar A;
-    const GSPre none{0.0, 0.0, 0.0, 0};   // (the work modes of the products apply no map; its two operands make them two-plane)
     explicit GSNBatch(const NewtonBatch &b)
         : B(b), N(b.h.newton_state), st(b.e->stream), per(b.per), c(b.w.cap), x(b.rows[0]), wr(b.rows[1]), r(b.rows[2]), rhat(b.rows[3]),
           p(b.rows[4]), v(b.rows[5]), s(b.rows[6]), y(b.rows[7]), delta(b.rows[8]), W0(b.rows[9]), W1(b.rows[10]), z(W0), t(W1),
@@ -3478,12 +3462,12 @@ struct GSNBatch {
     int inner() const {   // one BiCGStab iteration
         int rc;
         hipLaunchKernelGGL(gsn_dir_kernel, B.ge, B.b256, 0, st, A, S, r, v, p, per);
-        if ((rc = (p2d_products<GSPre, true>(B.e, B.h, B.pl.count, none, p, S.lin, B.dinv, W0, W1, y, nullptr)))) return rc;
+        if ((rc = p2d_four_products<true>(P2DBatch(B.e, B.h, B.pl.count, S.lin), p2d_planes<2>(), p, B.dinv, W0, W1, y, nullptr))) return rc;
         hipLaunchKernelGGL((gsn_jy_kernel<false>), B.ge, B.b256, 0, st, A, S, x, y, rhat, v, per);
         reduce<GSN_R_SIGMA>();
         hipLaunchKernelGGL(gsn_s_kernel, B.ge, B.b256, 0, st, A, S, r, v, s, per);
         reduce<GSN_R_HALF>();
-        if ((rc = (p2d_products<GSPre, true>(B.e, B.h, B.pl.count, none, s, S.lin, B.dinv, W0, W1, z, nullptr)))) return rc;
+        if ((rc = p2d_four_products<true>(P2DBatch(B.e, B.h, B.pl.count, S.lin), p2d_planes<2>(), s, B.dinv, W0, W1, z, nullptr))) return rc;
         hipLaunchKernelGGL((gsn_jy_kernel<true>), B.ge, B.b256, 0, st, A, S, x, z, s, t, per);
         reduce<GSN_R_OMEGA>();
         hipLaunchKernelGGL(gsn_update_kernel, B.ge, B.b256, 0, st, A, S, y, z, s, t, rhat, delta, r, per);
@@ -3578,23 +3562,7 @@ int h2d_phi_batch(mgrit_hip_engine *e, Level &lv, const BatchPlan &pl, const dou
     double *const W0 = chain ? h.Wc0 : h.W0, *const W1 = chain ? h.Wc1 : h.W1;
     double *dinv = nullptr;
     if ((rc = h2d_dinv(e, lv, pl.dtbits, &dinv))) return rc;
-    if (h.periodic()) {   // IMEX on the periodic grid: four products with the full Hartley table, the non-linear right-hand side formed
-                          // while the first is staged; Gray-Scott once for both species, items 2 b (u) and 2 b + 1 (v) of state b
-        double dt;
-        std::memcpy(&dt, &pl.dtbits, 8);
-        switch (h.kind) {
-        case H2DKind::GRAYSCOTT_IMEX: return p2d_products(e, h, pl.count, GSPre{dt, h.gs.a, h.gs.b, 0}, in_slab, pl.d_in, dinv, W0, W1, W0, fin);
-        case H2DKind::BURGERS_IMEX: return bg_products(e, h, pl.count, dt, in_slab, pl.d_in, dinv, W0, W1, fin);
-        case H2DKind::NAVIERSTOKES_IMEX: {
-            double *sinv = nullptr;
-            if ((rc = ns_sinv(e, lv, &sinv))) return rc;
-            return ns_products(e, h, pl.count, dt, in_slab, pl.d_in, sinv, dinv, W0, W1, fin);
-        }
-        case H2DKind::GINZBURGLANDAU_IMEX: return gl_products(e, h, pl.count, GLPre{dt, h.gl.c, 0}, in_slab, pl.d_in, dinv, W0, W1, fin);
-        case H2DKind::CAHNHILLIARD_IMEX: return ch_products(e, h, pl.count, CHPre{1.0 + h.ch.stab, 0}, in_slab, pl.d_in, dinv, W0, W1, fin);
-        default: return p2d_products(e, h, pl.count, ACPre{dt * h.ac.inv_eps2, h.ac.nu}, in_slab, pl.d_in, dinv, W0, W1, W0, fin);
-        }
-    }
+    if (h.periodic()) return p2d_imex_products(e, lv, pl, in_slab, dinv, W0, W1, fin);
     // W1[j][i'] = x to spectral slots ; W0[i'][j'] = y to spectral slots, o D ; W1[j'][i] = x back ; W0[i][j] = y back = U
     const dim3 fx(H.Mj / 64, H.Mi / 64, pl.count), fy(H.Mi / 64, H.Mj / 64, pl.count);        // (n tiles, slot tiles, items)
     const dim3 ix(H.Mj / 64, h.HPx / 64, pl.count), iy(H.Mi / 64, h.HPy / 64, pl.count);      // (n tiles, i tiles, items)

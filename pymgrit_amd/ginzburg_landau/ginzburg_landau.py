@@ -33,56 +33,15 @@ import numpy as np
 
 from pymgrit_amd.allen_cahn.allen_cahn import hartley_matrix, periodic_laplacian_eigenvalues
 from pymgrit_amd.core.application import Application
-from pymgrit_amd.core.vector import Vector
+from pymgrit_amd.core.plane_vector import TwoPlaneVector
 
 
-class VectorGinzburgLandau2D(Vector):
+class VectorGinzburgLandau2D(TwoPlaneVector):
     """The complex amplitude of one time point as two planes: ``values[0]`` is Re A, ``values[1]`` is Im A, each an nx x nx grid; the
     norm is the 2-norm over all 2 nx^2 values (the 2-norm of A). A device state row is ``[Re A plane | Im A plane]``, which is
     ``values.ravel()``."""
 
-    def __init__(self, nx):
-        super().__init__()
-        self.nx = nx
-        self.values = np.zeros((2, nx, nx))
-
-    def _like(self, values):
-        out = VectorGinzburgLandau2D(self.nx)
-        out.set_values(values)
-        return out
-
-    def __add__(self, other):
-        return self._like(self.get_values() + other.get_values())
-
-    def __sub__(self, other):
-        return self._like(self.get_values() - other.get_values())
-
-    def __mul__(self, other):
-        return self._like(self.get_values() * other)
-
-    def norm(self):
-        return np.linalg.norm(self.values)
-
-    def clone(self):
-        return self._like(self.get_values().copy())
-
-    def clone_zero(self):
-        return VectorGinzburgLandau2D(self.nx)
-
-    def clone_rand(self):
-        return self._like(np.random.rand(2, self.nx, self.nx))
-
-    def set_values(self, values):
-        self.values = values
-
-    def get_values(self):
-        return self.values
-
-    def pack(self):
-        return self.values
-
-    def unpack(self, values):
-        self.values = values
+    CLONE_COPIES = True
 
 
 class GinzburgLandau2D(Application):

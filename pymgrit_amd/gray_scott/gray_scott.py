@@ -55,57 +55,16 @@ from scipy.sparse.linalg import spsolve
 
 from pymgrit_amd.allen_cahn.allen_cahn import hartley_matrix, periodic_laplacian_eigenvalues
 from pymgrit_amd.core.application import Application
-from pymgrit_amd.core.vector import Vector
+from pymgrit_amd.core.plane_vector import TwoPlaneVector
 
 
-class VectorGrayScott2D(Vector):
+class VectorGrayScott2D(TwoPlaneVector):
     """The two species of one time point: ``values[0]`` is u, ``values[1]`` is v, each an nx x nx grid; the norm is the 2-norm over
     all 2 nx^2 values. The reference interleaves the fields (``xa[i, j, field]``, a DMDA with dof = 2); here they are stored as two
     planes because the engine's tile products want a contiguous nx x nx operand per species -- a device state row is
     ``[u plane | v plane]``, which is ``values.ravel()``."""
 
-    def __init__(self, nx):
-        super().__init__()
-        self.nx = nx
-        self.values = np.zeros((2, nx, nx))
-
-    def _like(self, values):
-        out = VectorGrayScott2D(self.nx)
-        out.set_values(values)
-        return out
-
-    def __add__(self, other):
-        return self._like(self.get_values() + other.get_values())
-
-    def __sub__(self, other):
-        return self._like(self.get_values() - other.get_values())
-
-    def __mul__(self, other):
-        return self._like(self.get_values() * other)
-
-    def norm(self):
-        return np.linalg.norm(self.values)
-
-    def clone(self):
-        return self._like(self.get_values().copy())
-
-    def clone_zero(self):
-        return VectorGrayScott2D(self.nx)
-
-    def clone_rand(self):
-        return self._like(np.random.rand(2, self.nx, self.nx))
-
-    def set_values(self, values):
-        self.values = values
-
-    def get_values(self):
-        return self.values
-
-    def pack(self):
-        return self.values
-
-    def unpack(self, values):
-        self.values = values
+    CLONE_COPIES = True
 
 
 class GrayScott(Application):

@@ -18,56 +18,15 @@ from typing import Callable, Union
 import numpy as np
 
 from pymgrit_amd.core.application import Application
-from pymgrit_amd.core.vector import Vector
+from pymgrit_amd.core.plane_vector import OnePlaneVector
 
 
 class NotSeparable2D(Exception):
     """rhs(x, y, t) is not of the form S0(x, y) + S1(x, y) * t"""
 
 
-class VectorHeat2D(Vector):
-    def __init__(self, nx, ny):
-        super().__init__()
-        self.nx, self.ny = nx, ny
-        self.values = np.zeros((self.nx, self.ny))
-
-    def _new(self, values):
-        out = VectorHeat2D(self.nx, self.ny)
-        out.set_values(values)
-        return out
-
-    def __add__(self, other):
-        return self._new(self.get_values() + other.get_values())
-
-    def __sub__(self, other):
-        return self._new(self.get_values() - other.get_values())
-
-    def __mul__(self, other):
-        return self._new(self.get_values() * other)
-
-    def norm(self):
-        return np.linalg.norm(self.values)
-
-    def clone(self):
-        return self._new(self.get_values())
-
-    def clone_zero(self):
-        return VectorHeat2D(self.nx, self.ny)
-
-    def clone_rand(self):
-        return self._new(np.random.rand(self.nx, self.ny))
-
-    def set_values(self, values):
-        self.values = values
-
-    def get_values(self):
-        return self.values
-
-    def pack(self):
-        return self.values
-
-    def unpack(self, values):
-        self.values = values
+class VectorHeat2D(OnePlaneVector):
+    pass
 
 
 def _as_bc(value, name):

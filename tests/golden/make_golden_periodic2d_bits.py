@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Record tests/golden/periodic2d_bits.json: SHA-256 digests of what the periodic 2-D device paths (Allen-Cahn IMEX and Newton-PCG,
-Gray-Scott IMEX) leave in the u, v and g slabs after every sweep of the fixed cases of tests/periodic2d_bits.py, on seeded inputs.
+Gray-Scott IMEX and Newton-BiCGStab, Cahn-Hilliard, Burgers, Navier-Stokes and Ginzburg-Landau IMEX) leave in the u, v and g slabs after every sweep of the fixed cases of tests/periodic2d_bits.py, on seeded inputs.
 Needs a GPU and the built library. tests/test_hip_periodic2d_bits.py recomputes every digest and compares with equality.
 
 The file is the record of the device arithmetic of the commit it was made on: record it BEFORE a change that is meant to keep the bits

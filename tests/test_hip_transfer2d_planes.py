@@ -244,13 +244,13 @@ def test_level_transfer_on_two_plane_levels():
         t0 = np.ascontiguousarray(np.linspace(0, 0.25, 9))
         t1 = np.ascontiguousarray(t0[::2])
         ld = {nx: ((2 * nx * nx + 15) // 16) * 16 for nx in (12, 5, 8, 4)}
-        hip_lib.level_burgers2d(eng, 0, t0.size, ptr(t0), ld[12], Burgers2D(nx=12, t_interval=t0).device_stepper())
-        hip_lib.level_burgers2d(eng, 1, t1.size, ptr(t1), ld[5], Burgers2D(nx=5, t_interval=t1).device_stepper())       # 2 * 5 = 10, not 12
-        hip_lib.level_grayscott2d(eng, 2, t1.size, ptr(t1), ld[8], GrayScott(nx=8, method="IMEX", t_interval=t1).device_stepper())
-        hip_lib.level_grayscott2d_newton(eng, 3, t1.size, ptr(t1), ld[4],
-                                         GrayScott(nx=4, method="IMPL", linear_solver="bicgstab", t_interval=t1).device_stepper())
-        hip_lib.level_burgers2d(eng, 4, t1.size, ptr(t1), ld[4], Burgers2D(nx=4, t_interval=t1).device_stepper())
-        hip_lib.level_burgers2d(eng, 5, t1.size, ptr(t1), ld[4], Burgers2D(nx=4, t_interval=t1).device_stepper())
+        hip_lib.level_2d(eng, 0, t0.size, ptr(t0), ld[12], Burgers2D(nx=12, t_interval=t0).device_stepper())
+        hip_lib.level_2d(eng, 1, t1.size, ptr(t1), ld[5], Burgers2D(nx=5, t_interval=t1).device_stepper())       # 2 * 5 = 10, not 12
+        hip_lib.level_2d(eng, 2, t1.size, ptr(t1), ld[8], GrayScott(nx=8, method="IMEX", t_interval=t1).device_stepper())
+        hip_lib.level_2d(eng, 3, t1.size, ptr(t1), ld[4],
+                         GrayScott(nx=4, method="IMPL", linear_solver="bicgstab", t_interval=t1).device_stepper())
+        hip_lib.level_2d(eng, 4, t1.size, ptr(t1), ld[4], Burgers2D(nx=4, t_interval=t1).device_stepper())
+        hip_lib.level_2d(eng, 5, t1.size, ptr(t1), ld[4], Burgers2D(nx=4, t_interval=t1).device_stepper())
         rc = lib.mgrit_hip_level_transfer(eng, 0, hip_lib.TRANSFER_PERIODIC2D)
         msg = lib.mgrit_hip_last_error().decode()
         assert rc == -1 and "12x12" in msg and "5x5" in msg, (rc, msg)            # MGRIT_HIP_EINVAL with both sizes
