@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "mgrit_hip.h"
+#include "pending_rows.h"
 #include "up2_table.h"
 
 namespace {
@@ -1137,9 +1138,7 @@ __device__ __forceinline__ void stage_other_level(const Smem &sm, const LevelDev
 //          reads it) nor anywhere on a coarsest level that is solved by forward_solve;
 //   bit 1: v^{l+1} -- its only reader is the error correction, which may take the same bits from the fine C-point (identity
 //          transfer); needed where a chunk of the way up starts (that row is being overwritten by the chunk in front of it).
-// A list may be PENDING on its level (Level::held, round 7): mgrit_hip_cf_fas with pre-relaxed C-points has not stored row cend of
-// its intervals -- row cend-1 holds those bits -- and mgrit_hip_ec_relax_res with the same list reads them there; anybody else gets
-// the rows put in place first (check_level, settle_held_kernel).
+// (A list may be PENDING on its level -- the held record of pending_rows.h: row cend of its intervals unstored, row cend-1 holds those bits.)
 struct IntervalsDev {
     const int32_t *cstart, *cend, *cend_coarse, *res_pos, *chunk_first, *chunk_len, *chunk_start_coarse, *keep;
     int n_chunks;
@@ -1164,12 +1163,12 @@ struct IntervalsDev {
 // traffic that the wave waits for, 2 us until the stores of the interval before have drained.)
 // pre: bit 0 = the pre-relaxed rows described above; bit 1 (CFAS_HELD, with bit 0 only) = C'_{j+1} is NOT stored to the fine row ce:
 // row ce-1 holds those very bits and the kernel does not write it, so the next reader of row ce -- ecfr_kernel with ECFR_HELD, or
-// settle_held_kernel in front of anybody else -- takes them from there (Level::held). One row less written per interval.
-// Level::twin of the coarse level (round 12): where the closing C-point goes to BOTH u^{l+1} and v^{l+1} the host may hand these
+// settle_held_kernel in front of anybody else -- takes them from there (the held record). One row less written per interval.
+// the twin record of the coarse level (round 12): where the closing C-point goes to BOTH u^{l+1} and v^{l+1} the host may hand these
 // kernels a keep array with bit 0 cleared at those intervals -- the coarse level's first pass, relax_kernel ROLE_FC, starts its runs
 // from v and rewrites that row of u without reading it. (As a launch flag tested beside `keep` the same choice cost
 // cfasq_kernel<1024, true> two more spilled VGPRs, 8 -> 10, with the flags kept as one scalar or as two: the array costs none.)
-// Lagged C-points (round 13, Level::lag): a level-0 way up that lags (ECFR_LAG) does not store the corrected C-point at all and leaves
+// Lagged C-points (round 13, the lag record): a level-0 way up that lags (ECFR_LAG) does not store the corrected C-point at all and leaves
 // P = Phi_l(F''_last) in the row the uncorrected C-point A was NOT read from -- row ce-1 and row ce in turn. Where it sits in row ce
 // the way down needs no word of it in these kernels: with CFAS_PRE | CFAS_HELD they read level-0 rows ce-1 and cs-1 (cs itself for a
 // first point that is not relaxed) and store none, so the host hands them L.u one row further on and a chunk_start_coarse without
@@ -1361,7 +1360,7 @@ __global__ void __launch_bounds__(TB) ecfr_kernel(LevelDev L, LevelDev Lc, Inter
                                                     double *const *__restrict__ mirror, int mirror_row0) {
     // store_flags = store_f | ECFR_HELD: with ECFR_HELD (store_f = 2 only) the uncorrected closing C-point is read from row ce-1, where
     // cfas_kernel (CFAS_HELD) found it and left it; this kernel overwrites that row only behind the read, by the same lane
-    // ECFR_LAG (RES, store_f = 2 only; Level::lag): the corrected C-point is NOT stored -- it is A + (u^{l+1}_jc - A) of two rows that
+    // ECFR_LAG (RES, store_f = 2 only; the lag record): the corrected C-point is NOT stored -- it is A + (u^{l+1}_jc - A) of two rows that
     // stay as they are, for whoever asks (settle_lag_kernel) -- and P goes to the row A was not read from: row ce when A sits one row
     // back, row ce-1 when it sits in row ce, so the next way down finds P and the next way up finds its A in turn
     const int store_f = store_flags & 3, held = (store_flags >> 2) & 1;   // (wave-uniform launch arguments; held = 0 / 1 rows back)
@@ -1429,7 +1428,7 @@ __global__ void __launch_bounds__(TB) ecfr_kernel(LevelDev L, LevelDev Lc, Inter
     wq.end(t);
 }
 
-// The way up of levels 1 and 0 in ONE pass (round 15, Level::up): ecfr_kernel<FORCE, false, true> with store_f = 2 and ECFR_LAG,
+// The way up of levels 1 and 0 in ONE pass (round 15, the up record): ecfr_kernel<FORCE, false, true> with store_f = 2 and ECFR_LAG,
 // except that u^1 at the interval's closing point jc is not read from a row the level-1 way up (ecf_kernel) has stored but COMPUTED
 // here, in a second vector z that travels through the chunk beside x. code[it] (up2_table.h) says how:
 //   -2      jc is an F-point of the deferred level-1 run list: z = g^1_jc + Phi_1(z) from the z of the interval before (ecf_kernel's
@@ -1442,7 +1441,7 @@ __global__ void __launch_bounds__(TB) ecfr_kernel(LevelDev L, LevelDev Lc, Inter
 // (the one-word `touch` read in front, the row behind); then the m-1 F-steps and the residual Phi of level 0 at ONE call site
 // with z pinned as q is there; then P stored, A read, b = A + (z - A), the residual, x = b -- ecfr_kernel's rows (A from row
 // ce - held, P p_back rows back, the chunk start's A from v^1) and ecfr_kernel's bits. Two vectors live beside every Phi, never
-// three. Nothing is written on level 1 or 2: whoever wants to see u^1 gets ecf_kernel's pass run late (settle_up). 3.25 rows per
+// three. Nothing is written on level 1 or 2: whoever wants to see u^1 gets ecf_kernel's pass run late (the up record, pending_rows.h). 3.25 rows per
 // interval against 5.4 of the two passes.
 // No C-point mirror: a mirrored row carries its padding, and the padding of b here is not the two passes' (the closed-form coarse
 // Phi leaves other values there than ecf_kernel's table form; no reader of a slab sees them, a reader of raw mirror rows would),
@@ -2066,54 +2065,12 @@ struct Level {
     double *blk_qt = nullptr;        // blk_one_kernel (small levels, one launch): the modes transposed; null: the six-launch form
     unsigned *blk_sync = nullptr;    //   its barrier counters (device) ...
     unsigned *blk_err = nullptr;     //   ... and the word a barrier that gave up sets (pinned, host-visible)
-    int held = -1;                   // interval list whose closing C-points mgrit_hip_cf_fas has NOT stored: row cend-1 holds the bits of
-                                     // row cend (cfas_kernel CFAS_HELD). mgrit_hip_ec_relax_res with the same list reads them there
-                                     // and clears this; every other entry point of the level puts the rows in place first (check_level)
-    int held_back = 1;               // ... and how many rows back from cend those bits sit: 1, or 0 behind a lagged way up (row cend itself)
-    // Level::lag (round 13), level 0 only: interval list whose corrected closing C-points the last mgrit_hip_ec_relax_res has NOT stored.
-    // P = Phi(F''_last) sits in row cend-lag_k, the uncorrected C-point A in the other row of the two, u^{l+1} at cend_coarse is intact, and
-    // the corrected value is A + (u^{l+1} - A) (settle_lag_kernel). mgrit_hip_cf_fas with the same list reads P where it is and drops the
-    // record; every other entry point that names this level or the next one gets the rows put in place first (check_level).
-    int lag = -1, lag_k = 0;
-    // Level::up (round 15), kept on level 1: mgrit_hip_ec_relax of run list `up` has launched nothing, because the level-0 way up
-    // of interval list up_ivals that follows it lags and computes u^1 where it needs it (up2_kernel). up_done: that pass has run and
-    // Level::lag of level 0 is pending with u^1 NOT brought up -- it stays at most as long as the lag record. Everybody but the
-    // partner gets ecf_kernel's pass launched late (settle_up, check_level of levels 0 to 2), in front of a settle of the lag record.
-    int up = -1, up_ivals = -1;
-    bool up_done = false;
-    // its waiting rule (lag mode 1): bringing level 1 up behind a fused launch costs the whole deferred pass on top of the fused one,
-    // so every such miss doubles up_wait (up to 64) and the next up_wait ways up of level 1 are not deferred. Like lag_wait it
-    // never shrinks: a caller that has looked keeps paying less often, not more
-    int up_wait = 1, up_skip = 0;
+    // (rows left out because their bits sit elsewhere -- held, twin, lag, up -- are the engine's ledger's: pending_rows.h)
     struct Up2Dev { bool pairs = false; const int32_t *d_code = nullptr, *d_zslot = nullptr, *d_ccode = nullptr; };
     struct IvalsHost { std::vector<int32_t> cend_coarse, chunk_first, chunk_len, chunk_start_coarse; };
     std::vector<IvalsHost> ivals_host;                 // per interval list: what the pairing table is worked out from
     std::map<std::pair<int, int>, Up2Dev> up_tables;  // (run list of level 1, interval list of level 0) -> the pairing table (up2_table.h)
-    // the waiting rule of mode 1: a settle of a lagged list costs 3-5 rows per interval and a lagged cycle saves one, so a list lags only
-    // after lag_wait consecutive way ups as the partner of a deferring way down, and every such settle doubles lag_wait (up to 64)
-    int lag_wait = 2;
-    std::map<int, int> lag_streak;                    // interval list -> consecutive partner way ups with no settle in between
-    std::map<std::pair<int, int>, bool> lag_apart;    // (interval list, pair list) -> the pairs name none of the record's rows
-    std::vector<std::vector<int32_t>> ivals_rows, ivals_cslots;   // per interval list, ascending: fine rows cend-1 / cend, coarse slots cend_coarse
-    std::vector<char> ivals_lag_ok;                   // per interval list: every relaxed C-point a chunk starts from closes an interval of the SAME list
-    // Level::twin (round 12), kept on the COARSE level of a pair: u of the record's slots was not stored by the finer level's pass,
-    // the row of v in the same slot holds its bits. The partner pass -- one that reads no u there and rewrites every such row --
-    // clears it; every other entry point that reaches this level or the level above it gets the rows copied first (check_level,
-    // settle_twin_kernel), and a record that ever had to be settled that way is not deferred again (missed).
-    struct TwinRec {
-        int kind, list;                 // TWIN_CFAS: interval list `list` of the finer level; TWIN_FFAS: its triples list `list`
-        const int32_t *d_slots;         // the slots on the device (the finer level's arrays)
-        std::vector<int32_t> slots;     // ... and on the host, ascending
-        bool missed = false;
-        std::map<int, bool> covered;    // TWIN_CFAS: run list id of this level -> its runs' closing points contain every slot
-        std::map<int, bool> apart;      // pair list id of the finer level -> none of its coarse points is a slot (mgrit_hip_copy_pairs_u_to_v)
-    };
-    std::vector<TwinRec> twin_recs;
-    int twin = -1;                      // pending record (index into twin_recs), -1: none
-    struct BothSlots { std::vector<int32_t> slots; const int32_t *d_slots = nullptr, *d_keep = nullptr; };   // d_keep: the list's keep with bit 0 cleared there
-    std::vector<BothSlots> ivals_both;  // per interval list of THIS level: coarse slots whose closing C-point goes to u AND v (keep == 3)
 };
-enum { TWIN_CFAS = 0, TWIN_FFAS = 1 };
 
 // ghost exchange (mgrit_hip_comm.inc): one direction of one pair of ranks
 enum { LINK_NONE = 0, LINK_RCCL = 1, LINK_MAILBOX = 2 };
@@ -2135,17 +2092,18 @@ struct mgrit_hip_engine {
     int n_levels = 0;
     hipStream_t stream = nullptr;
     std::vector<Level> L;
+    pending::Ledger rows;         // every row a pass has left out because its bits sit elsewhere, per level (pending_rows.h)
     bool timing = false;
     struct TimeRec { int kind, lvl; hipEvent_t ev0, ev1; };
     std::vector<TimeRec> trecs;              // one per timed entry-point call since the last drain
     std::vector<hipEvent_t> ev_pool;         // events of drained records, reused
     hipEvent_t last0 = nullptr, last1 = nullptr;   // events of the most recent timed call (mgrit_hip_last_kernel_ms)
-    bool defer = true;            // mgrit_hip_set_defer / MGRIT_HIP_DEFER: rows whose bits sit in a sibling row are not stored (Level::held)
+    bool defer = true;            // mgrit_hip_set_defer / MGRIT_HIP_DEFER: rows whose bits sit in a sibling row are not stored (pending_rows.h: held)
     int twin_mask = 2;            // mgrit_hip_set_twin / MGRIT_HIP_TWIN: bit 0 = mgrit_hip_cf_fas, bit 1 = mgrit_hip_fas_fused_opts may leave out
-                                  // rows of u^{l+1} whose bits sit in v^{l+1} (Level::twin). Bit 0 is off by default: alone it did not
+                                  // rows of u^{l+1} whose bits sit in v^{l+1} (twin). Bit 0 is off by default: alone it did not
                                   // show a gain beyond run-to-run noise on the flagship shape
-    int lag_mode = 1;             // mgrit_hip_set_lag / MGRIT_HIP_LAG: 0 never, 1 by the waiting rule, 2 every way up that may (Level::lag)
-    int up2_mode = 1;             // mgrit_hip_set_up2 / MGRIT_HIP_UP2: 0 never, 1 the way up of levels 1 and 0 in one pass whenever it lags (Level::up)
+    int lag_mode = 1;             // mgrit_hip_set_lag / MGRIT_HIP_LAG: 0 never, 1 by the waiting rule, 2 every way up that may (lag)
+    int up2_mode = 1;             // mgrit_hip_set_up2 / MGRIT_HIP_UP2: 0 never, 1 the way up of levels 1 and 0 in one pass whenever it lags (up)
     int cfas_form = 1;            // mgrit_hip_set_cfas_form / MGRIT_HIP_CFAS_FORM: 0 always cfas_kernel, 1 cfasq_kernel where it applies
     int cfas_last = -1;           // mgrit_hip_cfas_form: the form level 0's last mgrit_hip_cf_fas launched (-1: none yet)
     int fas_chunk = 0;            // mgrit_hip_set_fas_chunk: -1 fas_fused1_kernel, 0 chunks by the library's rule, n > 0 chunks of n
@@ -2589,7 +2547,7 @@ auto chain2_fn(int fm, bool use_g) {
 }
 
 // the two passes of the six-launch form: the blocks' local solves, and (finish) the second pass from the corrected block ends
-// twin (first pass of a Heat1D level only): the instance that reads the level's current values through BlkDev::cur (Level::twin)
+// twin (first pass of a Heat1D level only): the instance that reads the level's current values through BlkDev::cur (the twin record)
 auto blk_pass_fn(int kind, int fm, bool finish, bool twin = false) {
     auto pass = [&](auto K, auto F) { return finish ? &blk_finish_kernel<K, F> : twin ? &blk_local_kernel<K, F, true> : &blk_local_kernel<K, F>; };
     if (kind == MGRIT_HIP_STEPPER_ADVECTION1D) return pick<0>(fm, [&](auto F) { return pass(IntC<MGRIT_HIP_STEPPER_ADVECTION1D>{}, F); });
@@ -2680,145 +2638,7 @@ int register_lds_limits() {
     return err.empty() ? 0 : fail(MGRIT_HIP_EHIP, "%s", err.c_str());
 }
 
-// Level::held: the rows a deferring mgrit_hip_cf_fas has left out are put in place -- row cend-1 copied to row cend for every
-// interval of the list -- and the record is cleared. Never launched into a stream capture: a captured copy would be replayed
-// in cycles that have nothing pending.
-// back = Level::held_back: 1 = the bits sit in row cend-1 (copied to row cend); 0 = behind a lagged way up they sit in row cend itself,
-// and row cend-1 receives them, so that both rows hold what they hold behind every other settle.
-__global__ void __launch_bounds__(256) settle_held_kernel(double *__restrict__ u, int ld, const int32_t *__restrict__ cend, int n, int back) {
-    for (int it = blockIdx.x; it < n; it += gridDim.x) {
-        const int ce = cend[it];   // 2 <= ce < n_pts (mgrit_hip_intervals_create)
-        const double2 *src = reinterpret_cast<const double2 *>(u + (size_t)(ce - back) * ld);
-        double2 *dst = reinterpret_cast<double2 *>(u + (size_t)(ce - 1 + back) * ld);
-        for (int k = threadIdx.x; k < ld / 2; k += blockDim.x) dst[k] = src[k];
-    }
-}
-
-// Level::lag: the rows a lagging mgrit_hip_ec_relax_res has left out are put in place and the record is cleared. With A the uncorrected
-// closing C-point and P = Phi(F''_last) in rows cend-1 / cend (k = 1: A in row cend, P in row cend-1; k = 0: the other way round), row
-// cend := A + (uc - A) with uc = row cend_coarse of u^{l+1} -- ecfr_kernel's expression on ecfr_kernel's operands, element by element,
-// pad columns included -- and row cend-1 := P: bit for bit what a pass that does not lag leaves. Every lane reads its operands before
-// it writes, so the rows are rewritten in place. Never launched into a stream capture, as settle_held_kernel.
-__global__ void __launch_bounds__(256) settle_lag_kernel(double *__restrict__ u, const double *__restrict__ uc, int ld, int ldc,
-                                                         const int32_t *__restrict__ cend, const int32_t *__restrict__ cend_coarse, int n,
-                                                         int k_lag) {
-    for (int it = blockIdx.x; it < n; it += gridDim.x) {
-        const int ce = cend[it], jc = cend_coarse[it];   // 2 <= ce < n_pts, 0 <= jc < n_pts of the coarse level (mgrit_hip_intervals_create)
-        double2 *r1 = reinterpret_cast<double2 *>(u + (size_t)ce * ld);
-        double2 *r0 = reinterpret_cast<double2 *>(u + (size_t)(ce - 1) * ld);
-        const double2 *rc = reinterpret_cast<const double2 *>(uc + (size_t)jc * ldc);
-        for (int k = threadIdx.x; k < ld / 2; k += blockDim.x) {
-            const double2 a = k_lag ? r1[k] : r0[k], w = rc[k];
-            if (!k_lag) r0[k] = r1[k];
-            r1[k] = make_double2(a.x + (w.x - a.x), a.y + (w.y - a.y));
-        }
-    }
-}
-
-bool capturing(const mgrit_hip_engine *e) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(e->stream, &cs);
-    return cs != hipStreamCaptureStatusNone;
-}
-
-bool has_links(const mgrit_hip_engine *e) {
-    for (const Link &l : e->links)
-        if (l.kind != LINK_NONE) return true;
-    return false;
-}
-
-int settle_held(mgrit_hip_engine *e, int lvl) {
-    Level &lv = e->L[lvl];
-    if (capturing(e)) return fail(MGRIT_HIP_EINVAL, "level %d has unstored C-points pending (interval list %d) inside a stream capture", lvl, lv.held);
-    const int n = lv.ivals_cnt[lv.held];
-    const int rc = launch(&settle_held_kernel, dim3(std::min(n, 4096)), dim3(256), 0, e->stream, lv.dev.u, lv.dev.ld, lv.ivals[lv.held].cend, n,
-                          lv.held_back);
-    if (!rc) {
-        lv.lag_streak[lv.held] = 0;   // (the waiting rule counts way ups with no settle in between)
-        lv.held = -1;
-        lv.held_back = 1;
-    }
-    return rc;
-}
-
-// Level::lag of level 0 (the only level that lags): see settle_lag_kernel. A settle is a miss of the waiting rule.
-int settle_lag(mgrit_hip_engine *e) {
-    Level &lv = e->L[0];
-    if (lv.lag < 0) return 0;
-    if (capturing(e)) return fail(MGRIT_HIP_EINVAL, "level 0 has unstored corrected C-points pending (interval list %d) inside a stream capture", lv.lag);
-    const Level &lc = e->L[1];
-    const int n = lv.ivals_cnt[lv.lag];
-    const IntervalsDev &I = lv.ivals[lv.lag];
-    const int rc = launch(&settle_lag_kernel, dim3(std::min(n, 4096)), dim3(256), 0, e->stream, lv.dev.u, (const double *)lc.dev.u, lv.dev.ld,
-                          lc.dev.ld, I.cend, I.cend_coarse, n, lv.lag_k);
-    if (!rc) {
-        lv.lag_streak[lv.lag] = 0;
-        lv.lag_wait = std::min(2 * lv.lag_wait, 64);
-        lv.lag = -1;
-    }
-    return rc;
-}
-
-// Level::twin: row v of every slot of the pending record copied to row u, the record cleared and marked (it is not deferred again).
-// Never launched into a stream capture, as settle_held_kernel.
-__global__ void __launch_bounds__(256) settle_twin_kernel(double *__restrict__ u, const double *__restrict__ v, int ld,
-                                                          const int32_t *__restrict__ slots, int n) {
-    for (int it = blockIdx.x; it < n; it += gridDim.x) {
-        const int j = slots[it];   // 0 <= j < n_pts (mgrit_hip_intervals_create / mgrit_hip_pairs_create)
-        const double2 *src = reinterpret_cast<const double2 *>(v + (size_t)j * ld);
-        double2 *dst = reinterpret_cast<double2 *>(u + (size_t)j * ld);
-        for (int k = threadIdx.x; k < ld / 2; k += blockDim.x) dst[k] = src[k];
-    }
-}
-
-int settle_twin(mgrit_hip_engine *e, int lvl) {
-    Level &lv = e->L[lvl];
-    if (lv.twin < 0) return 0;
-    Level::TwinRec &rec = lv.twin_recs[lv.twin];
-    if (capturing(e)) return fail(MGRIT_HIP_EINVAL, "level %d has unstored rows of u pending (record %d) inside a stream capture", lvl, lv.twin);
-    const int n = (int)rec.slots.size();
-    const int rc = launch(&settle_twin_kernel, dim3(std::min(n, 4096)), dim3(256), 0, e->stream, lv.dev.u, (const double *)lv.dev.v, lv.dev.ld,
-                          rec.d_slots, n);
-    if (!rc) { rec.missed = true; lv.twin = -1; }
-    return rc;
-}
-
-// the record of (kind, list) on the coarse level lc: found, or made from the slots (ascending on the host)
-int twin_record(Level &lc, int kind, int list, const std::vector<int32_t> &slots, const int32_t *d_slots) {
-    for (size_t i = 0; i < lc.twin_recs.size(); ++i)
-        if (lc.twin_recs[i].kind == kind && lc.twin_recs[i].list == list) return (int)i;
-    Level::TwinRec rec;
-    rec.kind = kind; rec.list = list; rec.d_slots = d_slots; rec.slots = slots;
-    std::sort(rec.slots.begin(), rec.slots.end());
-    lc.twin_recs.push_back(rec);
-    return (int)lc.twin_recs.size() - 1;
-}
-
-// TWIN_KEEP_OWN / TWIN_KEEP_BELOW: the caller leaves the pending record of the level itself / of the next coarser level alone -- it is
-// the record's partner, its producer's own bookkeeping, or it touches no row of either level (list constructors).
-// LAG_KEEP: likewise for Level::lag of level 0 -- mgrit_hip_cf_fas as its partner, list constructors, a pair-list copy of other rows.
-// UP_KEEP: likewise for Level::up of level 1 -- the lagging level-0 way up it waits for, the way down that drops it unread, list
-// constructors. Nobody else: the record needs u^2, g^1 and the uncorrected rows of u^1 as the deferred pass would have found them.
-enum { TWIN_KEEP_OWN = 1, TWIN_KEEP_BELOW = 2, LAG_KEEP = 4, UP_KEEP = 8, KEEP_ALL = 15 };
-
-int settle_up(mgrit_hip_engine *e);   // (behind the launch helpers it needs)
-
-// partner: the interval list whose pending rows (Level::held) the caller reads where they are; any other pending list is settled.
-// Level::twin: an entry point of level lvl may read u of lvl and of lvl + 1, so both levels' records are settled unless twin_keep says
-// otherwise. Level::lag: the record of level 0 speaks of rows of level 0 and of u of level 1, which an entry point of either may read
-// or write, so both settle it unless twin_keep says otherwise.
-int check_level(mgrit_hip_engine *e, int lvl, bool need_set = true, int partner = -1, int twin_keep = 0) {
-    if (!e) return fail(MGRIT_HIP_EINVAL, "null engine");
-    if (lvl < 0 || lvl >= e->n_levels) return fail(MGRIT_HIP_EINVAL, "level %d out of range [0,%d)", lvl, e->n_levels);
-    if (need_set && !e->L[lvl].set) return fail(MGRIT_HIP_EINVAL, "level %d has no stepper", lvl);
-    int rc;
-    if (!(twin_keep & TWIN_KEEP_OWN) && e->L[lvl].twin >= 0 && (rc = settle_twin(e, lvl))) return rc;
-    if (!(twin_keep & TWIN_KEEP_BELOW) && lvl + 1 < e->n_levels && e->L[lvl + 1].twin >= 0 && (rc = settle_twin(e, lvl + 1))) return rc;
-    if (!(twin_keep & UP_KEEP) && lvl <= 2 && (rc = settle_up(e))) return rc;
-    if (!(twin_keep & LAG_KEEP) && lvl <= 1 && e->L[0].lag >= 0 && (rc = settle_lag(e))) return rc;
-    if (e->L[lvl].held >= 0 && e->L[lvl].held != partner) return settle_held(e, lvl);
-    return 0;
-}
+#include "mgrit_hip_pending.inc"
 
 // What the four level descriptors share. Each runs check_level first and level_fresh last, and its own argument checks between the
 // two in its own order (a call with several bad arguments reports the first of them): the 1-D descriptors test ld and the forcing
@@ -4004,9 +3824,7 @@ int no_wide(const Level &a, const Level *b, const char *what) {
 
 int ensure_sched(mgrit_hip_engine *e) {
     if (e->sched) return 0;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(e->stream, &cs);
-    if (cs != hipStreamCaptureStatusNone) return fail(MGRIT_HIP_EINVAL, "first chain / planned launch inside a stream capture");
+    if (capturing(e)) return fail(MGRIT_HIP_EINVAL, "first chain / planned launch inside a stream capture");
     HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->sched), 1024));
     HIP_TRY(hipMemsetAsync(e->sched, 0, 1024, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -4028,34 +3846,6 @@ int ec_relax_launch(mgrit_hip_engine *e, int lvl, const RunList &rl) {
     Timed timed(e, MGRIT_HIP_T_EC_RELAX, lvl);
     return launch(ecf_fn(lf.dev.kind, force_mode(lf), lvl > 0, lf.dev.T), dim3(persistent_grid(lf, rl.n)), dim3(lf.dev.T),
                   smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, rl.d_start, rl.d_len, rl.d_ec, rl.n);
-}
-
-// Level::up of level 1: the deferred ecf_kernel pass is launched exactly as mgrit_hip_ec_relax would have launched it -- u^2, g^1 and
-// the uncorrected rows of u^1 are as that call found them, every entry point that could change one comes through here first. The
-// rows of level 1 are then bit for bit what the two passes leave, and behind a fused launch (up_done) Level::lag of level 0 finds the
-// row of u^1 it speaks of in place: it stays pending for its own partner or settle (check_level settles this record first).
-int settle_up(mgrit_hip_engine *e) {
-    if (e->n_levels < 3 || e->L[1].up < 0) return 0;
-    Level &l1 = e->L[1];
-    if (capturing(e)) return fail(MGRIT_HIP_EINVAL, "level 1 has its way up pending (run list %d) inside a stream capture", l1.up);
-    const int rc = ec_relax_launch(e, 1, l1.runs[l1.up]);
-    if (rc) return rc;
-    if (l1.up_done) {   // a miss: somebody looked at level 1 behind the one-pass way up
-        l1.up_wait = std::min(2 * l1.up_wait, 64);
-        l1.up_skip = l1.up_wait;
-    }
-    l1.up = l1.up_ivals = -1;
-    l1.up_done = false;
-    return 0;
-}
-
-// What ec_relax_res_impl will decide for mgrit_hip_ec_relax_res(e, 0, ivals_id, 2) as the partner of the pending way down: it lags
-bool will_lag(mgrit_hip_engine *e, int ivals_id) {
-    Level &lf = e->L[0];
-    if (ivals_id < 0 || ivals_id >= (int)lf.ivals.size() || lf.held != ivals_id) return false;
-    const auto streak = lf.lag_streak.find(ivals_id);
-    return lf.ivals_lag_ok[ivals_id] && !has_links(e) && !capturing(e) &&
-           (e->lag_mode == 2 || (e->lag_mode == 1 && streak != lf.lag_streak.end() && streak->second >= lf.lag_wait));
 }
 
 // the pairing table of (run list of level 1, interval list of level 0), worked out and uploaded once (up2_table.h)
@@ -4145,7 +3935,7 @@ bool blk_one_launch_enabled() {
     return !(s && std::atoi(s) == 0);
 }
 
-// twin: the caller is the partner of the level's pending record (Level::twin) -- the first pass and the correction of the block ends
+// twin: the caller is the partner of the level's pending twin record -- the first pass and the correction of the block ends
 // read the level's current values from v, and every row the record speaks of is written before the call is over
 int blk_launch(mgrit_hip_engine *e, Level &lv, int phases, bool twin = false) {
     BlkDev bk = lv.blk;
@@ -4199,7 +3989,7 @@ int blk_launch(mgrit_hip_engine *e, Level &lv, int phases, bool twin = false) {
         if ((rc = launch(blk_pass_fn(lv.dev.kind, fm, true), dim3(std::min(bk.B, cap)), block, lds, e->stream, lv.dev, b2))) return rc;
     }
     HIP_TRY(hipGetLastError());
-    if (twin) lv.twin = -1;   // blk_correct_kernel has written every block end (b_end = B on one rank), blk_finish_kernel every interior point
+    if (twin) e->rows.twin_met((int)(&lv - e->L.data()));   // blk_correct_kernel has written every block end (b_end = B on one rank), blk_finish_kernel every interior point
     return 0;
 }
 
@@ -4491,6 +4281,7 @@ int mgrit_hip_create(mgrit_hip_engine **out, int n_levels, void *stream) {
     }
     e->stream = static_cast<hipStream_t>(stream);
     e->L.resize(n_levels);
+    e->rows.L.resize(n_levels);
     for (auto &lv : e->L) lv.arena = &e->arena;
     *out = e;
     return 0;
@@ -4788,13 +4579,7 @@ int mgrit_hip_newton_stats(mgrit_hip_engine *e, int lvl, int64_t out[4]) {
 }
 
 int mgrit_hip_level_bind(mgrit_hip_engine *e, int lvl, double *u, double *v, double *g) {
-    if (e && lvl >= 0 && lvl < e->n_levels) e->L[lvl].twin = -1;   // the slabs the record spoke of are no longer the level's
-    if (e && lvl >= 0 && lvl <= 1 && lvl < e->n_levels) e->L[0].lag = -1;   // (Level::lag speaks of u of level 0 and of level 1)
-    if (e && lvl >= 0 && lvl <= 2 && lvl < e->n_levels && e->n_levels >= 3 && e->L[1].up >= 0) {   // (Level::up speaks of slabs of levels 0 to 2)
-        if (e->L[1].up_done) e->L[0].lag = -1;   // ... and the lag record behind it of a u^1 that is not there
-        e->L[1].up = e->L[1].up_ivals = -1;
-        e->L[1].up_done = false;
-    }
+    if (e && lvl >= 0 && lvl < e->n_levels) e->rows.rebound(lvl);   // the slabs the records spoke of are no longer the level's
     int rc = check_level(e, lvl);
     if (rc) return rc;
     if (!u && e->L[lvl].dev.n_pts > 0) return fail(MGRIT_HIP_EINVAL, "u slab is null");
@@ -4872,9 +4657,7 @@ int mgrit_hip_block_solve_config(mgrit_hip_engine *e, int lvl, int r, int first_
                                  double *uh_out) {
     int rc = check_level(e, lvl);
     if (rc) return rc;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(e->stream, &cs);
-    if (cs != hipStreamCaptureStatusNone) return fail(MGRIT_HIP_EINVAL, "mgrit_hip_block_solve_config inside a stream capture");
+    if (capturing(e)) return fail(MGRIT_HIP_EINVAL, "mgrit_hip_block_solve_config inside a stream capture");
     return blk_config(e, lvl, r, first_real, has_successor, uh_in, uh_out);
 }
 
@@ -4899,11 +4682,8 @@ int mgrit_hip_block_solve_form(mgrit_hip_engine *e, int lvl, int *form_out) {
     return 0;
 }
 
-// Level::twin, the partners of a pending record of level lvl (outside a capture; everybody else has check_level settle it):
-// - of mgrit_hip_cf_fas: the F-C-relaxation of the level whose runs close on every slot of the record -- relax_kernel ROLE_FC starts
-//   its runs from v, reads no u and stores u at every closing point (worked out once per record and run list);
-// - of mgrit_hip_fas_fused_opts: the whole time-parallel solve in its six-launch Heat1D form on one rank, when the record is exactly
-//   the slots the solve steps over (1 .. n_steps): it reads the level's current values from v (BlkDev::cur) and writes every one.
+// The partners of a pending twin record of level lvl (outside a capture): relax_kernel ROLE_FC starts its runs
+// from v, reads no u and stores u at every closing point; the six-launch Heat1D solve reads the level's current values from v (BlkDev::cur)
 static bool twin_blk_form(const Level &lv) {
     return !lv.h2d && lv.blk_state >= 0 && lv.blk.r > 0 && !lv.blk.fourier && !lv.blk_qt && lv.blk.first_real && !lv.blk.project_last;
 }
@@ -4912,27 +4692,14 @@ static bool is_whole_chain(const Level &lv, int lvl, int mode, const RunList &rl
     return mode == MGRIT_HIP_RELAX_CHAIN && lvl > 0 && rl.n == 1 && rl.h_start[0] == 1 && rl.h_len[0] == lv.dev.n_pts - 1;
 }
 static bool twin_partner_fc(mgrit_hip_engine *e, int lvl, int runs_id) {
-    if (!e || lvl < 0 || lvl >= e->n_levels || e->L[lvl].twin < 0 || capturing(e)) return false;
-    Level &lv = e->L[lvl];
-    Level::TwinRec &rec = lv.twin_recs[lv.twin];
-    if (rec.kind != TWIN_CFAS || runs_id < 0 || runs_id >= (int)lv.runs.size()) return false;
-    const auto seen = rec.covered.find(runs_id);
-    if (seen != rec.covered.end()) return seen->second;
-    const RunList &rl = lv.runs[runs_id];
-    std::vector<int32_t> ends(rl.n);
-    for (int r = 0; r < rl.n; ++r) ends[r] = rl.h_start[r] + rl.h_len[r] - 1;
-    std::sort(ends.begin(), ends.end());
-    const bool all = std::includes(ends.begin(), ends.end(), rec.slots.begin(), rec.slots.end());
-    rec.covered[runs_id] = all;
-    return all;
+    if (!e || lvl < 0 || lvl >= e->n_levels || e->rows.L[lvl].twin < 0 || capturing(e)) return false;
+    if (runs_id < 0 || runs_id >= (int)e->L[lvl].runs.size()) return false;
+    const RunList &rl = e->L[lvl].runs[runs_id];
+    return e->rows.twin_partner_fc(lvl, runs_id, rl.n, rl.h_start.data(), rl.h_len.data());
 }
 static bool twin_partner_blk(mgrit_hip_engine *e, int lvl, int phases) {
-    if (!e || lvl < 0 || lvl >= e->n_levels || e->L[lvl].twin < 0 || capturing(e)) return false;
-    const Level &lv = e->L[lvl];
-    const Level::TwinRec &rec = lv.twin_recs[lv.twin];
-    const int n = (int)rec.slots.size();
-    return rec.kind == TWIN_FFAS && phases == 7 && twin_blk_form(lv) && n == lv.blk.n_steps && rec.slots.front() == 1 && rec.slots.back() == n &&
-           std::adjacent_find(rec.slots.begin(), rec.slots.end()) == rec.slots.end();
+    if (!e || lvl < 0 || lvl >= e->n_levels || e->rows.L[lvl].twin < 0 || capturing(e)) return false;
+    return phases == 7 && twin_blk_form(e->L[lvl]) && e->rows.twin_partner_solve(lvl, e->L[lvl].blk.n_steps);
 }
 
 int mgrit_hip_block_solve(mgrit_hip_engine *e, int lvl, int phases) {
@@ -5138,7 +4905,7 @@ int mgrit_hip_relax(mgrit_hip_engine *e, int lvl, int runs_id, int mode, double 
         // persistent grid: as many workgroups as stay resident (LDS- and thread-limited), at most one per run
         rc = launch(relax_fn(lv.dev.kind, force_mode(lv), use_g, role, lv.dev.T), dim3(persistent_grid(lv, rl->n)), dim3(lv.dev.T),
                     smem_bytes(lv.G, lv.dev.kind), e->stream, sched_dev(e, lv), rl->d_start, rl->d_len, rl->n, w, w1);
-        if (!rc && twin_fc) lv.twin = -1;   // the pass has rewritten u of every pending slot from v
+        if (!rc && twin_fc) e->rows.twin_met(lvl);   // the pass has rewritten u of every pending slot from v
         return rc;
     }
 }
@@ -5266,25 +5033,13 @@ static int fas_coarse_half(mgrit_hip_engine *e, int lvl, PairList *pl) {
                   pl->d_coarse, 0);
 }
 
-// Level::lag: a pair list leaves the pending record of level 0 alone when it names none of its rows -- on level 0 neither a fine row
-// cend-1 / cend nor a coarse slot cend_coarse (the injection of the first time point); on level 1 always: rows of u^1 are read
-// there and none written. Worked out once per record list and pair list.
+// a pair list that names none of the pending lag record's rows leaves it alone: the injection of the first time point, any list on level 1
 static int lag_keep_pairs(mgrit_hip_engine *e, int lvl, int pairs_id) {
-    if (!e || lvl < 0 || lvl > 1 || lvl >= e->n_levels || e->L[0].lag < 0) return 0;
+    if (!e || lvl < 0 || lvl > 1 || lvl >= e->n_levels || e->rows.lag < 0) return 0;
     if (lvl == 1) return LAG_KEEP;
-    Level &lf = e->L[0];
-    if (pairs_id < 0 || pairs_id >= (int)lf.pairs.size()) return 0;
-    const auto key = std::make_pair(lf.lag, pairs_id);
-    auto seen = lf.lag_apart.find(key);
-    if (seen == lf.lag_apart.end()) {
-        const PairList &pl = lf.pairs[pairs_id];
-        const std::vector<int32_t> &rows = lf.ivals_rows[lf.lag], &slots = lf.ivals_cslots[lf.lag];
-        bool apart = true;
-        for (int p = 0; p < pl.n && apart; ++p)
-            apart = !std::binary_search(rows.begin(), rows.end(), pl.h_fine[p]) && !std::binary_search(slots.begin(), slots.end(), pl.h_coarse[p]);
-        seen = lf.lag_apart.emplace(key, apart).first;
-    }
-    return seen->second ? LAG_KEEP : 0;
+    if (pairs_id < 0 || pairs_id >= (int)e->L[0].pairs.size()) return 0;
+    const PairList &pl = e->L[0].pairs[pairs_id];
+    return e->rows.lag_keeps_pairs(pairs_id, pl.h_fine, pl.h_coarse) ? LAG_KEEP : 0;
 }
 
 int mgrit_hip_restrict_u(mgrit_hip_engine *e, int lvl, int pairs_id) {
@@ -5499,22 +5254,14 @@ int mgrit_hip_fas_fused_opts(mgrit_hip_engine *e, int lvl, int triples_id, int o
         // the timing kind is the same for both
         if ((opts & MGRIT_HIP_FAS_WITH_F_RELAX) && e->fas_chunk >= 0 && pl->chunks_of >= 0) {
             if (pl->chunks_of == 0) return fail(MGRIT_HIP_EINVAL, "list %d has no chunk view", triples_id);
-            // u^{l+1} stays unstored (Level::twin) where the caller has not said so already and the coarse level is the coarsest one
-            // with the time-parallel solve in its six-launch form on one rank, which then reads the same bits from v: one rank, outside
-            // a capture, a list that is exactly the solve's points and that no other pass ever had to put in place
+            // twin: u^{l+1} stays unstored where the caller has not said so already and the coarse level is the coarsest one with
+            // the six-launch time-parallel solve, which then reads the same bits from v (twin_offer: a list that is exactly its points)
             int twin = -1;
-            if (!(opts & MGRIT_HIP_FAS_SKIP_COARSE_U) && (e->twin_mask & 2) && (lvl + 2 >= e->n_levels || !e->L[lvl + 2].set) && twin_blk_form(lc) && !has_links(e) &&
-                !capturing(e)) {
-                twin = twin_record(lc, TWIN_FFAS, triples_id, pl->h_coarse, pl->d_coarse);
-                const Level::TwinRec &rec = lc.twin_recs[twin];
-                const int n = (int)rec.slots.size();
-                const bool whole = n == lc.blk.n_steps && rec.slots.front() == 1 && rec.slots.back() == n &&
-                                   std::adjacent_find(rec.slots.begin(), rec.slots.end()) == rec.slots.end();
-                if (rec.missed || !whole) twin = -1;
-            }
+            if (!(opts & MGRIT_HIP_FAS_SKIP_COARSE_U) && (e->twin_mask & 2) && (lvl + 2 >= e->n_levels || !e->L[lvl + 2].set) && twin_blk_form(lc) && may_leave_out(e))
+                twin = e->rows.twin_offer(lvl + 1, pending::TWIN_FFAS, triples_id, pl->h_coarse, pl->d_coarse, lc.blk.n_steps);
             rc = launch(ffas_fn(fm, lf.dev.T), dim3(persistent_grid(lf, pl->chunks.n_chunks)), dim3(lf.dev.T), smem_bytes(lf.G, lf.dev.kind),
                         e->stream, sched_dev(e, lf), lc.dev, pl->chunks, (opts & MGRIT_HIP_FAS_SKIP_COARSE_U) | (twin >= 0 ? MGRIT_HIP_FAS_SKIP_COARSE_U : 0));
-            if (!rc && twin >= 0) lc.twin = twin;
+            if (!rc && twin >= 0) e->rows.note_twin(lvl + 1, twin);
             return rc;
         }
         const int kopts = opts | (same_factor_below(lf, lc) ? 4 : 0);
@@ -5528,22 +5275,12 @@ int mgrit_hip_fas_fused_opts(mgrit_hip_engine *e, int lvl, int triples_id, int o
 
 int mgrit_hip_copy_pairs_u_to_v(mgrit_hip_engine *e, int lvl, int pairs_id) {
     PairList *pl;
-    // (Level::twin: a copy of rows that are none of the pending record's slots -- the first point of the level, a ghost -- reads and
-    // writes nothing the record speaks of, and leaves it pending for its partner; worked out once per record and pair list)
+    // (twin: a copy of rows that are none of the pending record's slots -- the first point of the level, a ghost -- leaves it pending)
     int keep = 0;
-    if (e && lvl >= 0 && lvl + 1 < e->n_levels && e->L[lvl + 1].twin >= 0 && pairs_id >= 0 && pairs_id < (int)e->L[lvl].pairs.size()) {
-        Level::TwinRec &rec = e->L[lvl + 1].twin_recs[e->L[lvl + 1].twin];
-        auto seen = rec.apart.find(pairs_id);
-        if (seen == rec.apart.end()) {
-            bool apart = true;
-            for (int32_t j : e->L[lvl].pairs[pairs_id].h_coarse)
-                if (std::binary_search(rec.slots.begin(), rec.slots.end(), j)) { apart = false; break; }
-            seen = rec.apart.emplace(pairs_id, apart).first;
-        }
-        keep = seen->second ? TWIN_KEEP_BELOW : 0;
-    }
-    // (Level::lag: the copy reads u and writes v of level lvl + 1, so of the record's rows it can only read u^1 -- which is intact)
-    if (e && lvl <= 1 && e->n_levels > 0 && e->L[0].lag >= 0) keep |= LAG_KEEP;
+    if (e && lvl >= 0 && lvl + 1 < e->n_levels && e->rows.L[lvl + 1].twin >= 0 && pairs_id >= 0 && pairs_id < (int)e->L[lvl].pairs.size())
+        keep = e->rows.twin_keeps_pairs(lvl + 1, pairs_id, e->L[lvl].pairs[pairs_id].h_coarse) ? TWIN_KEEP_BELOW : 0;
+    // (lag: the copy reads u and writes v of level lvl + 1, so of the record's rows it can only read u^1 -- which is intact)
+    if (e && lvl <= 1 && e->n_levels > 0 && e->rows.lag >= 0) keep |= LAG_KEEP;
     int rc = get_pairs(e, lvl, pairs_id, &pl, keep);
     if (rc) return rc;
     Level &lc = e->L[lvl + 1];
@@ -5639,12 +5376,12 @@ int mgrit_hip_ec_runs_create(mgrit_hip_engine *e, int lvl, int n_runs, const int
     return dev_upload(lv, e->stream, coarse_idx, (size_t)n_runs, &lv.runs[*id_out].d_ec);
 }
 
-// Level::up: the way up of level 1 waits for the level-0 way up that follows it when that one is known to lag (see the record)
+// up: the way up of level 1 waits for the level-0 way up that follows it when that one is known to lag (pending_rows.h)
 static bool up2_defers(mgrit_hip_engine *e, int lvl, int ec_runs_id) {
-    if (lvl != 1 || e->up2_mode != 1 || e->n_levels < 3 || !e->defer || has_links(e) || capturing(e) || e->mirror_cur) return false;
+    if (lvl != 1 || e->up2_mode != 1 || e->n_levels < 3 || !e->defer || !may_leave_out(e) || e->mirror_cur) return false;
     Level &l0 = e->L[0], &l1 = e->L[1], &l2 = e->L[2];
-    const int I = l0.held;
-    if (I < 0 || !will_lag(e, I) || l0.lag >= 0 || l0.ivals[I].n_chunks == 0) return false;
+    const int I = e->rows.held_due_to_lag(e->lag_mode, true);
+    if (I < 0 || l0.ivals[I].n_chunks == 0) return false;
     const int fm = force_mode(l0);
     if (l0.dev.kind != MGRIT_HIP_STEPPER_HEAT1D || l1.dev.kind != MGRIT_HIP_STEPPER_HEAT1D || l0.transfer != MGRIT_HIP_TRANSFER_COPY ||
         l1.transfer != MGRIT_HIP_TRANSFER_COPY || l0.dev.n != l1.dev.n || l1.dev.n != l2.dev.n || l0.dev.T != l1.dev.T || l0.dev.ld != l1.dev.ld ||
@@ -5653,19 +5390,17 @@ static bool up2_defers(mgrit_hip_engine *e, int lvl, int ec_runs_id) {
         return false;
     const Level::Up2Dev *tab = nullptr;
     if (up2_table(e, ec_runs_id, I, &tab) || !tab->pairs) return false;
-    if (e->lag_mode == 1 && l1.up_skip > 0) { --l1.up_skip; return false; }   // (the waiting rule of Level::up)
-    return true;
+    return e->rows.up_takes_turn(e->lag_mode);   // (its waiting rule)
 }
 
 int mgrit_hip_up2_pending(mgrit_hip_engine *e) {
     if (!e) return fail(MGRIT_HIP_DEFERRED_BAD, "null engine");
-    if (e->n_levels < 3 || e->L[1].up < 0) return 0;
-    return e->L[1].up_done ? 2 : 1;
+    return e->rows.up_state();
 }
 
 int mgrit_hip_up2_settle(mgrit_hip_engine *e) {
     if (!e) return fail(MGRIT_HIP_EINVAL, "null engine");
-    return settle_up(e);
+    return settle_pending(e, 0, -1, ONLY_UP);
 }
 
 int mgrit_hip_set_up2(mgrit_hip_engine *e, int mode) {
@@ -5687,9 +5422,7 @@ int mgrit_hip_ec_relax(mgrit_hip_engine *e, int lvl, int ec_runs_id) {
     if ((rc = no_wide(lf, &lc, "fused correction + F-relaxation"))) return rc;
     if (rl->n == 0) return 0;
     if (up2_defers(e, lvl, ec_runs_id)) {   // nothing launched, nothing recorded: the level-0 way up takes this pass along
-        lf.up = ec_runs_id;
-        lf.up_ivals = e->L[0].held;
-        lf.up_done = false;
+        e->rows.note_up_deferred(ec_runs_id);
         return 0;
     }
     return ec_relax_launch(e, lvl, *rl);
@@ -5828,35 +5561,16 @@ int mgrit_hip_intervals_create(mgrit_hip_engine *e, int lvl, int n, const int32_
         return rc;
     d.cstart = p[0]; d.cend = p[1]; d.cend_coarse = p[2]; d.res_pos = p[3]; d.chunk_first = p[4]; d.chunk_len = p[5];
     d.chunk_start_coarse = p[6]; d.keep = p[7]; d.n_chunks = (int)cf.size();
-    // Level::twin: the coarse slots that take the closing C-point in u AND in v -- what a deferring mgrit_hip_cf_fas leaves out of u
-    Level::BothSlots both;
-    for (int i = 0; i < n; ++i)
-        if (kp[i] == 3) both.slots.push_back(cend_coarse[i]);
+    // twin: the coarse slots that take the closing C-point in u AND in v -- what a deferring mgrit_hip_cf_fas leaves out of u
+    pending::Ledger::Both both;
+    std::vector<int32_t> kt;
+    both.slots = pending::Ledger::both_slots(n, kp, cend_coarse, &kt);
     if (!both.slots.empty()) {
-        std::vector<int32_t> kt(kp);
-        for (int32_t &k : kt)
-            if (k == 3) k = 2;
         int32_t *ds = nullptr, *dk = nullptr;
         if ((rc = dev_upload(lv, e->stream, both.slots, &ds)) || (rc = dev_upload(lv, e->stream, kt, &dk))) return rc;
         both.d_slots = ds; both.d_keep = dk;
     }
-    lv.ivals_both.push_back(both);
-    // Level::lag: the rows a record of this list speaks of (what a pair-list copy must stay clear of to leave it pending)
-    std::vector<int32_t> rows, cslots(cend_coarse, cend_coarse + n);
-    for (int i = 0; i < n; ++i) { rows.push_back(cend[i] - 1); rows.push_back(cend[i]); }
-    std::sort(rows.begin(), rows.end());
-    std::sort(cslots.begin(), cslots.end());
-    lv.ivals_rows.push_back(rows);
-    lv.ivals_cslots.push_back(cslots);
-    // ... and whether the list may lag at all: as the record's partner the way down reads a chunk's first C-point where the RECORD
-    // keeps it, so that point must close an interval of this list (a block's list of a planned cycle starts at another list's
-    // closing C-point, a list with gaps likewise: those never lag)
-    std::vector<int32_t> ends(cend, cend + n);
-    std::sort(ends.begin(), ends.end());
-    bool lag_ok = true;
-    for (size_t k = 0; k < cf.size() && lag_ok; ++k)
-        lag_ok = cc[k] < 0 || std::binary_search(ends.begin(), ends.end(), cstart[cf[k]]);
-    lv.ivals_lag_ok.push_back(lag_ok);
+    e->rows.add_intervals(lvl, n, cstart, cend, cend_coarse, cf, cc, both);   // (lag: the rows a record of the list speaks of, and whether it may lag at all)
     lv.ivals_host.push_back(Level::IvalsHost{std::vector<int32_t>(cend_coarse, cend_coarse + n), cf, cl, cc});
     lv.ivals.push_back(d);
     lv.ivals_n.push_back(res_len);
@@ -5881,55 +5595,39 @@ static int fused_level_check(mgrit_hip_engine *e, int lvl, int ivals_id, const c
 }
 
 int mgrit_hip_cf_fas(mgrit_hip_engine *e, int lvl, int ivals_id, int pre_relaxed) {
-    // the partner of a lagging mgrit_hip_ec_relax_res (Level::lag): the same list with pre-relaxed C-points, deferring as below, reads
-    // them in the row the way up left them in and drops the record -- nobody asked for the corrected C-points, and they are gone for good.
-    // Anything else finds the rows put in place by check_level.
-    const bool lag_partner = e && lvl == 0 && pre_relaxed && ivals_id >= 0 && e->n_levels > 0 && e->L[0].lag == ivals_id && e->defer &&
-                             !has_links(e) && !capturing(e);
-    // (Level::up behind a fused way up goes with it: u^1 is not brought up, this pass and the level-1 way down overwrite what they need of it)
-    const bool up_drop = lag_partner && e->n_levels >= 3 && e->L[1].up >= 0 && e->L[1].up_done;
+    const bool may = e && may_leave_out(e);
+    // the partner of the lag record reads P in the row the way up left it in and drops the record: nobody asked for
+    // the corrected C-points. An up record behind a one-pass way up goes with it: this pass and the level-1 way down overwrite u^1
+    const bool lag_partner = may && lvl == 0 && pre_relaxed && ivals_id >= 0 && e->n_levels > 0 && e->rows.lag == ivals_id && e->defer;
+    const bool up_drop = lag_partner && e->rows.up_state() == 2;
     int rc = fused_level_check(e, lvl, ivals_id, "fused C-F-relaxation + FAS residual", true, -1, lag_partner ? (up_drop ? LAG_KEEP | UP_KEEP : LAG_KEEP) : 0);
     if (rc) return rc;
     Level &lf = e->L[lvl], &lc = e->L[lvl + 1];
     const IntervalsDev &I = lf.ivals[ivals_id];
     if (I.n_chunks == 0) return 0;
-    // The closing C-points stay unstored (Level::held) when their bits already sit in the row in front of them (pre_relaxed), on one
-    // rank -- a rank with exchange links hands rows to its neighbours and would pay a settle per cycle --, outside a capture (a
-    // graph would bake the decision into cycles it does not hold for), on every level size (the row saved is HBM traffic on the
-    // levels that stream and a store of 8 KB-128 KB less on those that do not).
-    const bool defer = pre_relaxed && e->defer && !has_links(e) && !capturing(e);
+    const bool defer = pre_relaxed && e->defer && may;   // held: row cend-1 has the bits; on every level size (HBM traffic, or a store of 8-128 KB)
     // One separable term and pre-relaxed C-points (every cycle but the first): the form that keeps the forcing factor in LDS and q
     // in registers (cfasq_kernel; same bits, same rows). Everything else -- no forcing, several terms, the first cycle -- cfas_kernel.
     // Where the coarse level's factor is the same vector, its Phi reads the LDS copy too (form 2).
     const bool q_regs = pre_relaxed && e->cfas_form == 1 && force_mode(lf) == 1;
     const bool coarse_lds = q_regs && same_factor_below(lf, lc);
-    // Rows of u^{l+1} stay unstored (Level::twin of the coarse level) where the same bits go to v^{l+1}: under the same conditions as
-    // above but for pre_relaxed, where the list has such slots at all (none on a coarsest level: its v bit comes from the chunk ends)
-    // and no other pass ever had to put them in place
-    int twin = -1;
-    if ((e->twin_mask & 1) && !has_links(e) && !capturing(e) && !lf.ivals_both[ivals_id].slots.empty()) {
-        const Level::BothSlots &both = lf.ivals_both[ivals_id];
-        twin = twin_record(lc, TWIN_CFAS, ivals_id, both.slots, both.d_slots);
-        if (lc.twin_recs[twin].missed) twin = -1;
-    }
-    // Level::lag, P in row cend itself (lagged(0)): the kernels read one row further on (see the enum above). They store no level-0
+    // twin: where the list has slots that take the same bits in u^{l+1} and v^{l+1} at all (none on a coarsest level: its v bit comes from the chunk ends)
+    const pending::Ledger::Both &both = e->rows.L[lvl].ivals_both[ivals_id];
+    const int twin = (e->twin_mask & 1) && may && !both.slots.empty() ? e->rows.twin_offer(lvl + 1, pending::TWIN_CFAS, ivals_id, both.slots, both.d_slots) : -1;
+    // lag, P in row cend itself (lagged(0)): the kernels read one row further on (see the enum above). They store no level-0
     // row (lag_partner implies defer) and use chunk_start_coarse for its sign alone; chunk_first has no negative entry. Rows read:
     // cend and cstart of the list's intervals, inside the slab; every relaxed cstart a chunk begins with is a cend of the list
     // (ivals_lag_ok: no other list ever lags), so the record holds P in that row too.
-    const bool row_ce = lag_partner && lf.lag_k == 0;
+    const bool row_ce = lag_partner && e->rows.lag_k == 0;
     IntervalsDev It = I;
     LevelDev Lf = sched_dev(e, lf);
     if (row_ce) { Lf.u += Lf.ld; It.chunk_start_coarse = I.chunk_first; }
-    if (twin >= 0) It.keep = lf.ivals_both[ivals_id].d_keep;   // bit 0 cleared where both bits were set
+    if (twin >= 0) It.keep = both.d_keep;   // bit 0 cleared where both bits were set
     Timed timed(e, MGRIT_HIP_T_CF_FAS, lvl);
     rc = launch(q_regs ? cfasq_fn(lf.dev.T, coarse_lds) : cfas_fn(force_mode(lf), lf.dev.T), dim3(persistent_grid(lf, I.n_chunks)),
                 dim3(lf.dev.T), smem_bytes(lf.G, lf.dev.kind), e->stream, Lf, lc.dev, It,
                 !pre_relaxed ? 0 : defer ? (CFAS_PRE | CFAS_HELD) : CFAS_PRE);
-    if (!rc) e->cfas_last = !q_regs ? 0 : coarse_lds ? 2 : 1;
-    if (!rc && defer) { lf.held = ivals_id; lf.held_back = row_ce ? 0 : 1; }
-    if (!rc && lag_partner) lf.lag = -1;
-    if (!rc && up_drop) { lc.up = lc.up_ivals = -1; lc.up_done = false; }
-    if (!rc && twin >= 0) lc.twin = twin;
+    if (!rc) { e->cfas_last = !q_regs ? 0 : coarse_lds ? 2 : 1; e->rows.note_way_down(lvl, ivals_id, defer, row_ce, lag_partner, up_drop, twin); }
     return rc;
 }
 
@@ -5945,11 +5643,11 @@ int mgrit_hip_ec_relax_res_to(mgrit_hip_engine *e, int lvl, int ivals_id, int st
 }
 
 static int ec_relax_res_impl(mgrit_hip_engine *e, int lvl, int ivals_id, int store_all_f, double *out_caller) {
-    // the partner of a deferring mgrit_hip_cf_fas: the same list on level 0 with store_all_f = 2, outside a capture, reads the
-    // pending rows where they are; anything else finds them put in place by check_level
-    const bool partner = e && lvl == 0 && store_all_f == 2 && ivals_id >= 0 && e->n_levels > 0 && e->L[0].held == ivals_id && !capturing(e);
-    // ... and the partner of a deferred level-1 way up (Level::up) that was noted for this very list, when the pass still lags
-    const bool up_partner = partner && e->n_levels >= 3 && e->L[1].up >= 0 && !e->L[1].up_done && e->L[1].up_ivals == ivals_id && !e->mirror_cur && will_lag(e, ivals_id);
+    // the partner of the held record reads the pending rows where they are (it asks for less than may_leave_out: outside a capture),
+    // the partner of an up record noted for this very list takes level 1's way up along when the pass still lags
+    const bool outside = e && lvl == 0 && store_all_f == 2 && !capturing(e), may = outside && !has_links(e);
+    const bool partner = outside && ivals_id >= 0 && e->n_levels > 0 && e->rows.L[0].held == ivals_id;
+    const bool up_partner = partner && e->rows.up_waits_for(ivals_id) && !e->mirror_cur && e->rows.lag_due(ivals_id, 2, e->lag_mode, true, may);
     int rc = fused_level_check(e, lvl, ivals_id, "fused correction + F-relaxation + residual", false, partner ? ivals_id : -1, up_partner ? UP_KEEP : 0);
     if (rc) return rc;
     Level &lf = e->L[lvl], &lc = e->L[lvl + 1];
@@ -5966,29 +5664,23 @@ static int ec_relax_res_impl(mgrit_hip_engine *e, int lvl, int ivals_id, int sto
     double *out = out_caller ? out_caller : e->pinned;
     Timed timed(e, MGRIT_HIP_T_EC_RELAX_RES, lvl);
     double *const *mirror = e->mirror_cur;   // null until mgrit_hip_cpoint_mirror has been called
-    const bool held = lf.held == ivals_id;   // (only as the partner: check_level has settled every other pending list)
-    const int back = held ? lf.held_back : 0;   // rows back from cend where the uncorrected C-point sits
-    // Level::lag: under the conditions of Level::held -- one rank, outside a capture, store_all_f = 2 --, for a list whose chunks start
-    // from its own closing C-points (ivals_lag_ok, mgrit_hip_intervals_create), and by the engine's mode: always
-    // (2), or once the list has been the partner of a deferring way down lag_wait times in a row with no settle in between (1)
-    int &streak = lf.lag_streak[ivals_id];
-    const bool lag = store_all_f == 2 && lf.ivals_lag_ok[ivals_id] && !has_links(e) && !capturing(e) && (e->lag_mode == 2 || (e->lag_mode == 1 && held && streak >= lf.lag_wait));
-    streak = held ? streak + 1 : 0;
+    const bool held = e->rows.L[0].held == ivals_id;   // (only as the partner: check_level has settled every other pending list)
+    const int back = held ? e->rows.L[0].held_back : 0;   // rows back from cend where the uncorrected C-point sits
+    // (the predicate up_partner and up2_defers have asked already)
+    const bool lag = e->rows.lag_due(ivals_id, store_all_f, e->lag_mode, held, may);
+    e->rows.count_way_up(ivals_id, held);
     const Level::Up2Dev *up_tab = nullptr;
-    if (up_partner) {   // (it lags: will_lag is the very predicate of `lag` above)
-        if ((rc = up2_table(e, lc.up, ivals_id, &up_tab))) return rc;
-    }
-    if (up_tab) {   // Level::up: both levels' ways up in one pass, u^1 computed where the pass needs it and stored nowhere
+    if (up_partner && (rc = up2_table(e, e->rows.up, ivals_id, &up_tab))) return rc;   // (it lags)
+    if (up_tab) {   // up: both levels' ways up in one pass, u^1 computed where the pass needs it and stored nowhere
         const Level &l2 = e->L[2];
         rc = launch(up2_fn(force_mode(lf), lf.dev.T, force_mode(lf) == 1 && same_factor_below(lf, lc)), grid, block, smem_bytes(lf.G, lf.dev.kind),
                     e->stream, sched_dev(e, lf), lc.dev, (const double *)l2.dev.u, l2.dev.ld, l2.dev.stream_rows, I, up_tab->d_code, up_tab->d_zslot, up_tab->d_ccode,
                     out, back);
-        if (!rc) lc.up_done = true;
+        if (!rc) e->rows.note_up_fused();
     } else
         rc = launch(ecfr_fn(force_mode(lf), false, lf.dev.T), grid, block, smem_bytes(lf.G, lf.dev.kind), e->stream, sched_dev(e, lf), lc.dev, I,
                     out, store_all_f | (back ? ECFR_HELD : 0) | (lag ? ECFR_LAG : 0), mirror, e->mirror_row0);
-    if (!rc && held) { lf.held = -1; lf.held_back = 1; }   // the pass has read the pending rows and, unless it lags, rewritten row cend and row cend-1 of every interval
-    if (!rc && lag) { lf.lag = ivals_id; lf.lag_k = 1 - back; }
+    if (!rc) e->rows.note_way_up(ivals_id, held, lag, back);   // the pass has read the pending rows and, unless it lags, rewritten row cend and row cend-1 of every interval
     return rc;
 }
 
@@ -6011,9 +5703,7 @@ static int gen_check(mgrit_hip_engine *e, int lvl, int ivals_id, const char *wha
 
 static int gen_reserve(mgrit_hip_engine *e, Level &lf, size_t res_len) {
     if (lf.gen_rows && lf.gen_len >= res_len) return 0;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(e->stream, &cs);
-    if (cs != hipStreamCaptureStatusNone) return fail(MGRIT_HIP_EINVAL, "first whole-level pass of a level inside a stream capture");
+    if (capturing(e)) return fail(MGRIT_HIP_EINVAL, "first whole-level pass of a level inside a stream capture");
     const int rc = slab_regrow(lf, &lf.gen_rows, res_len * (size_t)lf.dev.ld);
     if (!rc) lf.gen_len = res_len;
     return rc;
@@ -6090,23 +5780,21 @@ int mgrit_hip_chain_clock(mgrit_hip_engine *e, double *mhz, double *us_per_step)
     return 0;
 }
 
-int mgrit_hip_deferred(mgrit_hip_engine *e, int lvl) {
+// the getters of the records (pending_rows.h): 0, or the failure of a bad engine / level
+static int record_level(mgrit_hip_engine *e, int lvl) {
     if (!e) return fail(MGRIT_HIP_DEFERRED_BAD, "null engine");
     if (lvl < 0 || lvl >= e->n_levels) return fail(MGRIT_HIP_DEFERRED_BAD, "level %d out of range [0,%d)", lvl, e->n_levels);
-    return e->L[lvl].held;
+    return 0;
 }
+int mgrit_hip_deferred(mgrit_hip_engine *e, int lvl) { const int rc = record_level(e, lvl); return rc ? rc : e->rows.L[lvl].held; }
+int mgrit_hip_twin(mgrit_hip_engine *e, int lvl) { const int rc = record_level(e, lvl); return rc ? rc : e->rows.L[lvl].twin; }
+int mgrit_hip_lagged(mgrit_hip_engine *e, int lvl) { const int rc = record_level(e, lvl); return rc ? rc : lvl == 0 ? e->rows.lag : -1; }   // (level 0 alone lags)
 
 int mgrit_hip_set_defer(mgrit_hip_engine *e, int on) {
     if (!e) return fail(MGRIT_HIP_EINVAL, "null engine");
     if (on != 0 && on != 1) return fail(MGRIT_HIP_EINVAL, "defer %d: 0 = every row stored, 1 = rows held in a sibling row left out", on);
     e->defer = on != 0;   // (a record that is pending stays: its partner or the next entry point of the level deals with it)
     return 0;
-}
-
-int mgrit_hip_twin(mgrit_hip_engine *e, int lvl) {
-    if (!e) return fail(MGRIT_HIP_DEFERRED_BAD, "null engine");
-    if (lvl < 0 || lvl >= e->n_levels) return fail(MGRIT_HIP_DEFERRED_BAD, "level %d out of range [0,%d)", lvl, e->n_levels);
-    return e->L[lvl].twin;
 }
 
 int mgrit_hip_set_twin(mgrit_hip_engine *e, int mask) {
@@ -6118,12 +5806,6 @@ int mgrit_hip_set_twin(mgrit_hip_engine *e, int mask) {
 
 int mgrit_hip_settle(mgrit_hip_engine *e, int lvl) { return check_level(e, lvl, false); }
 
-int mgrit_hip_lagged(mgrit_hip_engine *e, int lvl) {
-    if (!e) return fail(MGRIT_HIP_DEFERRED_BAD, "null engine");
-    if (lvl < 0 || lvl >= e->n_levels) return fail(MGRIT_HIP_DEFERRED_BAD, "level %d out of range [0,%d)", lvl, e->n_levels);
-    return e->L[lvl].lag;
-}
-
 int mgrit_hip_set_lag(mgrit_hip_engine *e, int mode) {
     if (!e) return fail(MGRIT_HIP_EINVAL, "null engine");
     if (mode < 0 || mode > 2) return fail(MGRIT_HIP_EINVAL, "lag mode %d: 0 = never, 1 = by the waiting rule, 2 = every way up that may", mode);
@@ -6134,9 +5816,7 @@ int mgrit_hip_set_lag(mgrit_hip_engine *e, int mode) {
 int mgrit_hip_lag_settle(mgrit_hip_engine *e, int lvl) {
     if (!e) return fail(MGRIT_HIP_EINVAL, "null engine");
     if (lvl < 0 || lvl >= e->n_levels) return fail(MGRIT_HIP_EINVAL, "level %d out of range [0,%d)", lvl, e->n_levels);
-    if (lvl != 0) return 0;
-    const int rc = settle_up(e);   // (Level::up: u^1 first, the lag record reads it)
-    return rc ? rc : settle_lag(e);
+    return lvl != 0 ? 0 : settle_pending(e, 0, -1, ONLY_UP_AND_LAG);   // (u^1 first, the lag record reads it)
 }
 
 int mgrit_hip_set_cfas_form(mgrit_hip_engine *e, int form) {
@@ -6154,19 +5834,12 @@ int mgrit_hip_cfas_form(mgrit_hip_engine *e, int lvl) {
 
 int mgrit_hip_set_stream(mgrit_hip_engine *e, void *stream) {
     if (!e) return fail(MGRIT_HIP_EINVAL, "null engine");
-    // Level::lag outlives the cycle that left it, so a caller that moves the engine to another stream -- to capture the next cycle
-    // there, where nothing can be put in place -- gets the rows put in place on the stream the record's pass ran on, behind it
+    // A lag record (and an up record in front of it) outlives the cycle that left it, so a caller that moves the engine to another stream -- to
+    // capture the next cycle there, where nothing can be put in place -- gets the rows put in place on the stream the record's pass ran on
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (s != e->stream) {
-        const int rc = settle_up(e);   // (Level::up likewise, in front of the lag record that reads u^1)
-        if (rc) return rc;
-    }
-    if (s != e->stream && e->n_levels > 1 && e->L[0].lag >= 0) {
-        const int rc = settle_lag(e);
-        if (rc) return rc;
-    }
-    e->stream = s;
-    return 0;
+    const int rc = s != e->stream ? settle_pending(e, 0, -1, ONLY_UP_AND_LAG) : 0;
+    if (!rc) e->stream = s;
+    return rc;
 }
 
 }  // extern "C"

@@ -54,7 +54,7 @@ struct BlkDev {
     int skip_last_row;   // blk_finish_kernel: the last point has been corrected already (blk_last_kernel, sent to the next rank)
     double *Ws;          // [B][ld] the blocks' propagated defects W_b (row storage order)
     const double *cur;   // the level's current values at the points 1 .. n_steps as blk_correct_kernel and blk_local_kernel<.., TWIN> read
-                         // them (set per launch, blk_launch): the level's u, or its v while u of those rows was left unstored (Level::twin)
+                         // them (set per launch, blk_launch): the level's u, or its v while u of those rows was left unstored (the twin record)
     // Advection1D (periodic; all n Fourier modes, n a power of two): what / C / D / uh_in / uh_out hold complex values
     // [B][n] (re, im interleaved), r = n; tw = the n/2 twiddles (cos, -sin)(2 pi t / n)
     const double2 *tw;
