@@ -3,12 +3,13 @@ shared by tests/golden/make_golden_pending_trace.py, which records tests/golden/
 tests/test_hip_pending_trace.py, which replays every script and compares with equality. Needs a GPU.
 
 A script is a sequence of backend calls the record tests already walk (test_hip_deferred_rows.py, test_hip_twin_rows.py,
-test_hip_lagged_cpoints.py, test_hip_up2.py). Behind EVERY library call of the backend, and behind every step of the script, the
+test_hip_lagged_cpoints.py, test_hip_up2.py); scripts and tests take the solver, the cycles, the guard tables and the finishes from
+heat1d_cycles.py, and no test module is imported here. Behind EVERY library call of the backend, and behind every step of the script, the
 state of the four records is noted: mgrit_hip_deferred(l) and mgrit_hip_twin(l) of every level, mgrit_hip_lagged(0) and
 mgrit_hip_up2_pending. At the end mgrit_hip_settle runs on every level and the raw u, v and g slabs of every level are digested
 (SHA-256). What is kept per script: the number of calls, the digest of the whole trace, the calls at which the state changed
 (readable when the test fails), and the slab digests folded into one (pack, at the end of this file, lays the file out). These are host decisions, so the shapes are small: Heat1D, 3 levels, m = 4,
-nt = 1025, level-0 chunks of 4, forcing on, at the smallest and the largest state size of test_hip_lagged_cpoints.SIZES (one wave per
+nt = 1025, level-0 chunks of 4, forcing on, at the smallest and the largest state size of heat1d_cycles.SIZES (one wave per
 state, 1024 threads; the one-wave coarsest level is solved in one launch and never leaves u of it out), and one four-level script."""
 import hashlib
 import json
@@ -17,25 +18,27 @@ import os
 import numpy as np
 
 import cases
-import test_hip_lagged_cpoints as lagt
-import test_hip_twin_rows as twint
-import test_hip_up2 as up2t
+import heat1d_cycles as hc
 
 GOLDEN_FILE = os.path.join(cases.GOLDEN, "pending_trace.json")
 NT, CHUNK = 1025, 4
-SIZES = (lagt.SIZES[0], lagt.SIZES[-1])
+SIZES = (hc.SIZES[0], hc.SIZES[-1])
 GETTERS = ("mgrit_hip_deferred", "mgrit_hip_twin", "mgrit_hip_lagged", "mgrit_hip_up2_pending")
 
 
-class Tracer:
-    """the backend's library handle with the state of the four records noted behind every call (and the interface of the record
-    tests' own probes, whose helpers the scripts use)"""
+class Traced:
+    """every export but the four getters"""
+
+    def __contains__(self, name):
+        return name.startswith("mgrit_hip_") and name not in GETTERS
+
+
+class Tracer(hc.Probe):
+    """the record tests' probe, watching every call: the state of the four records behind it goes to `trace` (and nothing to `log`)"""
 
     def __init__(self, lib, h, n_levels):
-        self.__dict__.update(_lib=lib, _h=h, _n=n_levels, log=[], trace=[])
-
-    def twins(self):
-        return tuple(self._lib.mgrit_hip_twin(self._h, lvl) for lvl in range(1, self._n))
+        super().__init__(lib, h, Traced(), lambda lib, h, name, args: self.note(name), n_levels)
+        self.trace = []
 
     def state(self):
         lib, h = self._lib, self._h
@@ -46,26 +49,12 @@ class Tracer:
     def note(self, label):
         self.trace.append((label, self.state()))
 
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-        if not name.startswith("mgrit_hip_") or name in GETTERS:
-            return fn
-
-        def call(*args):
-            rc = fn(*args)
-            self.note(name)
-            return rc
-        return call
-
 
 def build(nx, lag=2, up2=1, twin=None, levels=3, **kw):
     env = {"MGRIT_HIP_UP2": str(up2)}
     if twin is not None:
         env["MGRIT_HIP_TWIN"] = str(twin)
-    mg = lagt.build(nx, True, NT, CHUNK, lag, env=env, levels=levels, **kw)
-    be = mg.backend
-    be.lib = Tracer(be.lib._lib, be.h, levels)
-    return mg
+    return hc.lag_build(nx, True, NT, CHUNK, lag, env=env, levels=levels, probe=lambda lib, h: Tracer(lib, h, levels), **kw)
 
 
 def step(mg, label, fn):
@@ -76,7 +65,7 @@ def step(mg, label, fn):
 
 def blind(mg, first, n):
     for it in range(first, first + n):
-        step(mg, f"cycle {it}", lambda: up2t.blind_cycle(mg, it))
+        step(mg, f"cycle {it}", lambda: hc.blind_cycle(mg, it))
 
 
 # ---- the scripts: name -> function of the state size that returns the solver it has driven --------------------------------------
@@ -93,15 +82,15 @@ def s_guard(name, state):
         blind(mg, 0, n)
         rest = None
         if state == "noted":
-            rest = step(mg, "half cycle", lambda: up2t.half_cycle(mg, n))
+            rest = step(mg, "half cycle", lambda: hc.half_cycle(mg, n))
             n += 1
-        step(mg, "guard " + name, lambda: up2t.GUARDS[name](mg))
+        step(mg, "guard " + name, lambda: hc.UP2_GUARDS[name](mg))
         if rest is not None:
             step(mg, "way up of level 0", lambda: mg.backend.ec_relax_res(*rest))
             mg.backend.residual_ready(mg._c_points(0))
             mg.convergence_criterion(iteration=n)
             mg.compute_residual()
-        step(mg, "finish", lambda: up2t.finish(mg, n))
+        step(mg, "finish", lambda: hc.up2_finish(mg, n))
         return mg
     return run
 
@@ -112,7 +101,7 @@ def s_second_way_up_of_level_0(nx):
     step(mg, "second way up", lambda: mg._up(0, mg._level_intervals(0)))
     mg.convergence_criterion(iteration=3)
     mg.compute_residual()
-    step(mg, "finish", lambda: up2t.finish(mg, 2))
+    step(mg, "finish", lambda: hc.up2_finish(mg, 2))
     return mg
 
 
@@ -147,7 +136,7 @@ def s_pairs_lag(call, pairs):
         mg = build(nx)
         blind(mg, 0, 2)
         step(mg, call, lambda: getattr(mg.backend, call)(0, pairs))
-        step(mg, "finish", lambda: up2t.finish(mg, 2))
+        step(mg, "finish", lambda: hc.up2_finish(mg, 2))
         return mg
     return run
 
@@ -156,9 +145,9 @@ def s_pairs_twin(pairs):
     """mgrit_hip_copy_pairs_u_to_v on level 0 with the twin record of level 1 pending"""
     def run(nx):
         mg = build(nx, twin=3)
-        step(mg, "pending", lambda: twint.pending(mg, 1))
+        step(mg, "pending", lambda: hc.twin_pending(mg, 1))
         step(mg, "copy", lambda: mg.backend.copy_pairs_u_to_v(0, pairs))
-        step(mg, "finish", lambda: twint.finish(mg))
+        step(mg, "finish", lambda: hc.twin_finish(mg))
         return mg
     return run
 
@@ -168,12 +157,12 @@ def s_twin(lvl, partner):
     somebody else (an F-C-relaxation of every second interval / the solve phase by phase)"""
     def run(nx):
         mg = build(nx, twin=3)
-        step(mg, "pending", lambda: twint.pending(mg, lvl))
+        step(mg, "pending", lambda: hc.twin_pending(mg, lvl))
         if partner:
             step(mg, "partner", lambda: mg.iteration(lvl=lvl, cycle_type='V', iteration=2, first_f=True))
         else:
-            step(mg, "non-partner", lambda: twint.GUARDS["relax_FC" if lvl == 1 else "block_solve_by_phases"](mg, lvl))
-        step(mg, "cycle", lambda: twint.cycle(mg, 3))
+            step(mg, "non-partner", lambda: (hc.twin_relax('FC') if lvl == 1 else hc.twin_block_solve_by_phases)(mg, lvl))
+        step(mg, "cycle", lambda: hc.twin_cycle(mg, 3))
         return mg
     return run
 
@@ -196,7 +185,7 @@ def s_modes(lag, up2, twin):
     def run(nx):
         mg = build(nx, lag=lag, up2=up2, twin=twin)
         blind(mg, 0, 4)
-        step(mg, "look at the coarse levels", lambda: lagt.coarse_state(mg))
+        step(mg, "look at the coarse levels", lambda: hc.coarse_state(mg))
         blind(mg, 4, 1)
         return mg
     return run
@@ -207,14 +196,14 @@ def s_four_levels(nx):
     for it in range(4):
         blind(mg, it, 1)
         if it % 2:
-            step(mg, "look at the coarse levels", lambda: lagt.coarse_state(mg))
+            step(mg, "look at the coarse levels", lambda: hc.coarse_state(mg))
     return mg
 
 
 def _make_scripts():
     out = {"six_blind_cycles": s_six_blind_cycles, "second_way_up_of_level_0": s_second_way_up_of_level_0,
            "waiting_rule_lag": s_waiting_rule_lag, "waiting_rule_up": s_waiting_rule_up, "stream_switch_lag_pending": s_stream_switch}
-    for name in sorted(up2t.GUARDS):
+    for name in sorted(hc.UP2_GUARDS):
         for state in ("done1", "done0", "noted"):
             out[f"guard_{name}_{state}"] = s_guard(name, state)
     for call in ("copy_pairs_u_to_v", "restrict_u"):

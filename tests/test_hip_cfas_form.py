@@ -9,17 +9,17 @@ nt = 273 (68 intervals: chunks of 16 leave a last chunk of 4) and nt = 1025 (a c
 gives levels this small chunks of ONE interval, so the tests ask for chunks of 4 (or 16): the closing C-point then stays in
 registers as the next interval's start, as on the levels the form is made for."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 import cases
+import heat1d_cycles as hc
+from heat1d_cycles import SIZES, need_gpu, same, raw_cycle as cycle
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-SIZES = (1022, 4097, 16382)       # one wave per state / 512 threads / 1024 threads
 ONE = [(cases.rhs_space, cases.rhs_time)]
 TWO = cases.BDF_FORCING["two"]
 NAME = "mgrit_hip_cf_fas"
@@ -38,24 +38,15 @@ def grids_two_dt():
     return [t, t[::4], t[::16]]
 
 
-class Probe:
-    """the backend's library handle with a note behind every mgrit_hip_cf_fas of level 0: (pre_relaxed, mgrit_hip_cfas_form(level 0)
-    after the call, was the stream capturing)"""
+def note(lib, h, name, args):
+    """behind every mgrit_hip_cf_fas of level 0: (pre_relaxed, mgrit_hip_cfas_form(level 0) after the call, was the stream
+    capturing)"""
+    if args[1] == 0:
+        return int(args[3]), lib.mgrit_hip_cfas_form(h, 0), hc.capturing()
 
-    def __init__(self, lib, h):
-        self.__dict__.update(_lib=lib, _h=h, log=[])
 
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-        if name != NAME:
-            return fn
-
-        def call(*args):
-            rc = fn(*args)
-            if args[1] == 0:
-                self.log.append((int(args[3]), self._lib.mgrit_hip_cfas_form(self._h, 0), bool(torch.cuda.is_current_stream_capturing())))
-            return rc
-        return call
+def probe(lib, h):
+    return hc.Probe(lib, h, (NAME,), note)
 
 
 def per_level(terms, n):
@@ -83,35 +74,10 @@ def specs(nx, terms, tgrids):
 
 def build(nx, terms, tgrids, form, chunk=4, defer=True, comm=None, **kw):
     """a solver whose level-0 passes walk chunks of `chunk` intervals, the form switch set as asked, its library handle probed"""
-    from pymgrit_amd import Mgrit
-    old = os.environ.pop("MGRIT_HIP_DEFER", None)
-    if not defer:
-        os.environ["MGRIT_HIP_DEFER"] = "0"
-    try:
-        mg = Mgrit(problem(nx, terms, tgrids), logging_lvl=30, comm_time=comm, **dict(dict(max_iter=5, tol=0.0), **kw))
-    finally:
-        os.environ.pop("MGRIT_HIP_DEFER", None)
-        if old is not None:
-            os.environ["MGRIT_HIP_DEFER"] = old
-    be = mg.backend
-    assert type(be).__name__ == "HipBackend"
-    assert be.lib.mgrit_hip_set_cfas_form(be.h, form) == 0
-    ids, length = be._intervals_id, chunk
-
-    def intervals_id(lvl, intervals, chunk=None):
-        return ids(lvl, intervals, chunk=length if lvl == 0 and chunk is None else chunk)
-    be._intervals_id = intervals_id
-    be.lib = Probe(be.lib, be.h)
+    mg = hc.build(problem(nx, terms, tgrids), env={"MGRIT_HIP_DEFER": None if defer else "0"}, chunk=chunk, comm=comm, probe=probe,
+                  **dict(dict(max_iter=5, tol=0.0), **kw))
+    assert mg.backend.lib.mgrit_hip_set_cfas_form(mg.backend.h, form) == 0
     return mg
-
-
-def cycle(mg, it):
-    """one cycle with its residual check; what it leaves WITHOUT anything put in place for the look: the raw level-0 slab, the
-    residual sums (the way up's own, fetched), u, v, g of the coarse levels"""
-    mg.iteration(lvl=0, cycle_type=mg.cycle_type, iteration=it, first_f=True)
-    mg.convergence_criterion(iteration=it + 1)
-    return ([mg.backend._U[0].cpu().numpy(), np.asarray(mg.compute_residual())] +
-            [mg.backend.natural(which, lvl) for lvl in (1, 2) for which in "uvg"])
 
 
 def cycles(n, *args, **kw):
@@ -119,14 +85,6 @@ def cycles(n, *args, **kw):
     out = [cycle(mg, it) for it in range(n)]
     out.append([mg.backend.natural("u", 0)])
     return mg, out
-
-
-def same(a, b, what):
-    assert len(a) == len(b), what
-    for k, (x, y) in enumerate(zip(a, b)):
-        assert len(x) == len(y), (what, k)
-        for j, (p, q) in enumerate(zip(x, y)):
-            assert np.array_equal(p, q), (what, "cycle", k, "item", j)
 
 
 def forms(mg):
@@ -138,17 +96,7 @@ def pres(mg):
 
 
 def against_oracle(oracle, mg, out, nx, terms, tgrids, n=5, **kw):
-    """the same cycles by the oracle: the residual history to rounding of the norm, level 0 bit for bit"""
-    op = oracle.OracleProblem(specs(nx, terms, tgrids), variant=1, max_iter=n, tol=0.0, **kw)
-    ref = op.solve()
-    conv = mg.conv[1:n + 1]
-    assert np.max(np.abs(conv - ref) / ref) <= 1e-10, (conv, ref)
-    assert np.array_equal(out[-1][0], op.state("u", 0))
-
-
-def need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU test selected but no GPU visible")
+    hc.against_oracle(oracle, mg, out[-1][0], specs(nx, terms, tgrids), n, **kw)
 
 
 def new_forms(f):
@@ -251,13 +199,9 @@ def test_other_cycle_shapes(oracle, name):
 def test_planned_cycles(blocks):
     """a planned cycle runs launch by launch twice, then as a captured graph: the form is chosen the same way inside a capture"""
     need_gpu()
-    from pymgrit_amd.core.options import options
     tg = grids(257)
-    options.plan_graph = "require"
-    try:
+    with hc.planned_graph():
         runs = [cycles(5, 4097, ONE, tg, form, **({} if blocks == 1 else dict(plan_blocks=blocks))) for form in (0, 1)]
-    finally:
-        options.reset("plan_graph")
     (mg0, off), (mg1, on) = runs
     same(on, off, blocks)
     assert set(forms(mg0)) == {0}
@@ -314,7 +258,7 @@ def test_switch_environment_and_argument_checks(monkeypatch):
     mg = Mgrit(problem(1022, ONE, tg), logging_lvl=30, max_iter=3, tol=0.0)
     monkeypatch.delenv("MGRIT_HIP_CFAS_FORM")
     assert mg.backend.lib.mgrit_hip_cfas_form(mg.backend.h, 0) in (-1, 0)
-    mg.backend.lib = Probe(mg.backend.lib, mg.backend.h)
+    mg.backend.lib = probe(mg.backend.lib, mg.backend.h)
     for it in range(2):
         cycle(mg, it)
     assert forms(mg) == [0, 0] and pres(mg) == [0, 1]

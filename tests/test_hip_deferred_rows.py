@@ -4,82 +4,32 @@ mgrit_hip_deferred). mgrit_hip_cf_fas(pre_relaxed = 1) leaves the closing C-poin
 rows in place first. Everything is compared bit for bit with the same sequence run with the switch off (MGRIT_HIP_DEFER=0), and
 against the oracle. Hierarchy: Heat1D, 3 levels, m = 4, nt = 257 (64 level-0 intervals: chunk starts and a chunk cut, 16 coarsest
 steps) at one state size per kernel instance, and nt = 1025 (a coarsest level of four blocks)."""
+import contextlib
 import ctypes as C
-import os
 
-import numpy as np
 import pytest
 
-import cases
+import heat1d_cycles as hc
+from heat1d_cycles import need_gpu, same, raw_cycle as cycle
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-SIZES = (1022, 4097, 16382)       # one wave per state / 512 threads / 1024 threads
-SHAPES = [(nx, forcing, 257) for nx in SIZES for forcing in (False, True)] + [(1022, True, 1025)]
+SHAPES = [(nx, forcing, 257) for nx in hc.SIZES for forcing in (False, True)] + [(1022, True, 1025)]
 WATCHED = ("mgrit_hip_cf_fas", "mgrit_hip_ec_relax_res")
 
 
-class Probe:
-    """the backend's library handle with a note behind every whole-level pass of level 0: (export, its last integer argument,
-    mgrit_hip_deferred(level 0) after the call, was the stream capturing)"""
-
-    def __init__(self, lib, h):
-        self.__dict__.update(_lib=lib, _h=h, log=[])
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-        if name not in WATCHED:
-            return fn
-
-        def call(*args):
-            rc = fn(*args)
-            if args[1] == 0:
-                self.log.append((name, int(args[3]), self._lib.mgrit_hip_deferred(self._h, 0), bool(torch.cuda.is_current_stream_capturing())))
-            return rc
-        return call
-
-
-def problem(nx, forcing, nt):
-    from pymgrit_amd import Heat1D
-    kw = dict(rhs_separable=[(cases.rhs_space, cases.rhs_time)]) if forcing else {}
-    return [Heat1D(x_start=0, x_end=1, nx=nx, a=1, init_cond=cases.init_cond, t_start=0, t_stop=2, nt=k, **kw)
-            for k in (nt, (nt - 1) // 4 + 1, (nt - 1) // 16 + 1)]
+def note(lib, h, name, args):
+    """behind every whole-level pass of level 0: (export, its last integer argument, mgrit_hip_deferred(level 0) after the call, was
+    the stream capturing)"""
+    if args[1] == 0:
+        return name, int(args[3]), lib.mgrit_hip_deferred(h, 0), hc.capturing()
 
 
 def build(nx, forcing, nt, defer, comm=None, **kw):
-    """a solver whose engine was created with the switch on or off, its library handle probed"""
-    from pymgrit_amd import Mgrit
-    old = os.environ.pop("MGRIT_HIP_DEFER", None)
-    if not defer:
-        os.environ["MGRIT_HIP_DEFER"] = "0"
-    try:
-        mg = Mgrit(problem(nx, forcing, nt), logging_lvl=30, comm_time=comm, **dict(dict(max_iter=5, tol=0.0), **kw))
-    finally:
-        os.environ.pop("MGRIT_HIP_DEFER", None)
-        if old is not None:
-            os.environ["MGRIT_HIP_DEFER"] = old
-    assert type(mg.backend).__name__ == "HipBackend"
-    mg.backend.lib = Probe(mg.backend.lib, mg.backend.h)
-    return mg
-
-
-def coarse_state(mg):
-    return [mg.backend.natural(which, lvl) for lvl in (1, 2) for which in "uvg"]
-
-
-def cycle(mg, it):
-    """one cycle with its residual check; what it leaves WITHOUT anything put in place for the look: the raw level-0 slab, the
-    residual sums (the way up's own, fetched), u, v, g of the coarse levels"""
-    mg.iteration(lvl=0, cycle_type=mg.cycle_type, iteration=it, first_f=True)
-    mg.convergence_criterion(iteration=it + 1)
-    return [mg.backend._U[0].cpu().numpy(), np.asarray(mg.compute_residual())] + coarse_state(mg)
-
-
-def same(a, b, what):
-    assert len(a) == len(b), what
-    for k, (x, y) in enumerate(zip(a, b)):
-        assert np.array_equal(x, y), (what, k)
+    """a solver whose engine was created with the switch on (the variable absent) or off, its library handle probed"""
+    return hc.build(hc.problem(nx, forcing, nt), env={"MGRIT_HIP_DEFER": None if defer else "0"}, comm=comm,
+                    probe=lambda lib, h: hc.Probe(lib, h, WATCHED, note), **dict(dict(max_iter=5, tol=0.0), **kw))
 
 
 def deferred_after(mg, name):
@@ -105,11 +55,6 @@ def off_run(shape):
     return _OFF[shape]
 
 
-def need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU test selected but no GPU visible")
-
-
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"nx{s[0]}_{'forcing' if s[1] else 'plain'}_nt{s[2]}")
 def test_five_cycles_bit_identical_and_deferred(shape, oracle):
     need_gpu()
@@ -123,13 +68,7 @@ def test_five_cycles_bit_identical_and_deferred(shape, oracle):
     assert up == [-1] * 5, up
     assert [mode for n, mode, _, _ in mg.backend.lib.log if n == WATCHED[1]] == [2] * 5
     # ... and against the oracle: the same cycles, the residual history to rounding of the norm, level 0 bit for bit
-    nx, forcing, nt = shape
-    op = oracle.OracleProblem([cases.heat_level_spec(nx, cases.lin(2, k), forcing=forcing) for k in (nt, (nt - 1) // 4 + 1, (nt - 1) // 16 + 1)],
-                              variant=1, max_iter=5, tol=0.0)
-    ref = op.solve()
-    conv = mg.conv[1:6]
-    assert np.max(np.abs(conv - ref) / ref) <= 1e-10, (conv, ref)
-    assert np.array_equal(got[-1][0], op.state("u", 0))
+    hc.against_oracle(oracle, mg, got[-1][0], hc.heat_specs(*shape), 5)
 
 
 def test_store_all_f_never_defers(monkeypatch):
@@ -163,17 +102,13 @@ def test_planned_cycles(blocks):
     """a planned cycle runs launch by launch twice (a block's way down defers, the next block's settles it), then as a captured
     graph, into which nothing is deferred and nothing settled"""
     need_gpu()
-    from pymgrit_amd.core.options import options
     shape = (4097, True, 257)
-    options.plan_graph = "require"
-    try:
+    with hc.planned_graph():
         runs = []
         for defer in (False, True):
             # (one block: planned and captured on request alone, options.plan_graph; a plan_blocks=1 request means program order)
             mg = build(*shape, defer, **({} if blocks == 1 else dict(plan_blocks=blocks)))
             runs.append((mg, [cycle(mg, it) for it in range(5)] + [[mg.backend.natural("u", 0)]]))
-    finally:
-        options.reset("plan_graph")
     (mg_off, off), (mg_on, on) = runs
     for it, (a, b) in enumerate(zip(on, off)):
         same(a, b, (blocks, "cycle", it))
@@ -202,42 +137,8 @@ def finish(mg, extra=()):
     return out + [mg.backend.natural("u", 0)]
 
 
-def g_relax(mode):
-    def run(mg):
-        runs = mg._c_runs(0) if mode == 'C' else mg._f_runs(0)
-        if mode == 'FC':       # not a sweep of level 0: refused, behind the guard
-            from pymgrit_amd.core.hip_lib import MgritHipError
-            with pytest.raises(MgritHipError):
-                mg.backend.relax(0, runs, mode)
-        else:
-            mg.backend.relax(0, runs, mode)
-        return finish(mg)
-    return run
-
-
-def g_residual(mg):
-    return finish(mg, [np.asarray(mg.backend.residual_norms(mg._c_points(0)))])
-
-
-def g_correction_by_hand(mg):
-    mg.error_correction(lvl=0)
-    mg.f_relax(lvl=0)
-    return finish(mg)
-
-
-def g_natural(mg):
-    return finish(mg, [mg.backend.natural("u", 0)])
-
-
-def g_payload(mg):
-    rows = [mg.backend.payload(0, int(i)).cpu().numpy() for i in (4, 8, 255, 256)]
-    return finish(mg, rows)
-
-
-def g_set_natural(mg):
-    x, _ = cases.heat_grid(mg.problem[0].nx + 2)
-    mg.backend.set_natural("u", 0, np.stack([cases.heat_input(x, k) for k in range(len(mg.problem[0].t))]))
-    return finish(mg)
+def guard(action):
+    return lambda mg: finish(mg, action(mg))
 
 
 def g_ecf_route(mg):
@@ -250,9 +151,9 @@ def g_ecf_route(mg):
     return finish(mg)
 
 
-GUARDS = {"relax_F": g_relax('F'), "relax_C": g_relax('C'), "relax_FC": g_relax('FC'), "residual": g_residual,
-          "correction_by_hand": g_correction_by_hand, "natural": g_natural, "payload": g_payload, "set_natural": g_set_natural,
-          "ecf_route": g_ecf_route}
+GUARDS = {"relax_F": guard(hc.relax_level0('F')), "relax_C": guard(hc.relax_level0('C')), "relax_FC": guard(hc.relax_level0('FC')),
+          "residual": guard(hc.residual_norms), "correction_by_hand": guard(hc.correction_by_hand(0)), "natural": guard(hc.natural("u", 0)),
+          "payload": guard(hc.payload(0, (4, 8, 255, 256))), "set_natural": guard(hc.set_natural_level0), "ecf_route": g_ecf_route}
 
 
 @pytest.mark.parametrize("name", sorted(GUARDS))
@@ -272,11 +173,8 @@ def test_guard(name):
 @pytest.mark.parametrize("name", ["sequential", "F_cycle", "cf_iter2"])
 def test_other_cycle_shapes(name):
     need_gpu()
-    from pymgrit_amd.core.options import options
     kw = {"sequential": {}, "F_cycle": dict(cycle_type='F'), "cf_iter2": dict(cf_iter=2)}[name]
-    if name == "sequential":
-        options.coarse_solve = "sequential"
-    try:
+    with hc.sequential_coarse() if name == "sequential" else contextlib.nullcontext():
         runs = []
         for defer in (False, True):
             mg = build(4097, True, 257, defer, **kw)
@@ -287,8 +185,6 @@ def test_other_cycle_shapes(name):
                 assert set(down) == {-1}
             else:
                 assert any(d >= 0 for d in down) == defer, (name, defer, down)
-    finally:
-        options.reset("coarse_solve")
     for it, (a, b) in enumerate(zip(runs[1], runs[0])):
         same(a, b, (name, it))
 

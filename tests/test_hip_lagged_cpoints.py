@@ -6,112 +6,24 @@ sequence run with the switch off (MGRIT_HIP_LAG=0), and against the oracle. Hier
 intervals) at one state size per kernel instance, in chunks of 3, 4 and 16 intervals (chunk starts, a chunk cut, a short last
 chunk), and nt = 1025 (a coarsest level of four blocks)."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-import cases
+import heat1d_cycles as hc
+from heat1d_cycles import DOWN, UP, coarse_state, lagged, need_gpu, problem, same, coarse_cycle as cycle, lag_build as build
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-SIZES = (1022, 4097, 16382)       # one wave per state / 512 threads / 1024 threads
 # (nx, forcing, nt, chunk)
-SHAPES = [(nx, forcing, 257, 4) for nx in SIZES for forcing in (False, True)] + \
+SHAPES = [(nx, forcing, 257, 4) for nx in hc.SIZES for forcing in (False, True)] + \
          [(4097, True, 257, 3), (16382, True, 257, 16), (1022, True, 1025, 16)]
-WATCHED = ("mgrit_hip_cf_fas", "mgrit_hip_ec_relax_res")
-DOWN, UP = WATCHED
 GUARD_SHAPE = (4097, True, 257, 4)
-
-
-class Probe:
-    """the backend's library handle with a note behind every whole-level pass of level 0: (export, its last integer argument,
-    mgrit_hip_lagged(level 0) and mgrit_hip_deferred(level 0) after the call, was the stream capturing)"""
-
-    def __init__(self, lib, h):
-        self.__dict__.update(_lib=lib, _h=h, log=[])
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-        if name not in WATCHED:
-            return fn
-
-        def call(*args):
-            rc = fn(*args)
-            if args[1] == 0:
-                self.log.append((name, int(args[3]), self._lib.mgrit_hip_lagged(self._h, 0), self._lib.mgrit_hip_deferred(self._h, 0),
-                                 bool(torch.cuda.is_current_stream_capturing())))
-            return rc
-        return call
-
-
-def level_nts(nt, levels=3):
-    return [(nt - 1) // 4 ** k + 1 for k in range(levels)]
-
-
-def problem(nx, forcing, nt, levels=3):
-    from pymgrit_amd import Heat1D
-    kw = dict(rhs_separable=[(cases.rhs_space, cases.rhs_time)]) if forcing else {}
-    return [Heat1D(x_start=0, x_end=1, nx=nx, a=1, init_cond=cases.init_cond, t_start=0, t_stop=2, nt=k, **kw) for k in level_nts(nt, levels)]
-
-
-def build(nx, forcing, nt, chunk, lag, env=(), comm=None, levels=3, **kw):
-    """a solver whose engine was created with MGRIT_HIP_LAG = lag (and whatever else env names), whose level-0 passes walk chunks of
-    `chunk` intervals, its library handle probed"""
-    from pymgrit_amd import Mgrit
-    env = dict(env, MGRIT_HIP_LAG=str(lag))
-    old = {k: os.environ.pop(k, None) for k in env}
-    os.environ.update(env)
-    try:
-        mg = Mgrit(problem(nx, forcing, nt, levels), logging_lvl=30, comm_time=comm, **dict(dict(max_iter=6, tol=0.0), **kw))
-    finally:
-        for k, v in old.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
-    be = mg.backend
-    assert type(be).__name__ == "HipBackend"
-    ids, length = be._intervals_id, chunk
-
-    def intervals_id(lvl, intervals, chunk=None):
-        return ids(lvl, intervals, chunk=length if lvl == 0 and chunk is None else chunk)
-    be._intervals_id = intervals_id
-    be.lib = Probe(be.lib, be.h)
-    return mg
-
-
-def lagged(mg):
-    return mg.backend.lib.mgrit_hip_lagged(mg.backend.h, 0)
-
-
-def coarse_state(mg):
-    return [mg.backend.natural(which, lvl) for lvl in range(1, mg.lvl_max) for which in "uvg"]
-
-
-def cycle(mg, it):
-    """one cycle with its residual check; what it leaves WITHOUT a look at level 0, which would have the rows put in place: the
-    residual sums (the way up's own, fetched), u, v, g of the coarse levels"""
-    mg.iteration(lvl=0, cycle_type=mg.cycle_type, iteration=it, first_f=True)
-    mg.convergence_criterion(iteration=it + 1)
-    return [np.asarray(mg.compute_residual())] + coarse_state(mg)
-
-
-def same(a, b, what):
-    assert len(a) == len(b), what
-    for k, (x, y) in enumerate(zip(a, b)):
-        assert np.array_equal(x, y), (what, k)
 
 
 def after(mg, name, col=2):
     return [rec[col] for rec in mg.backend.lib.log if rec[0] == name]
-
-
-def need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU test selected but no GPU visible")
 
 
 _OFF = {}     # shape -> what six cycles with the switch off leave, level 0 looked at behind every one (computed once, never modified)
@@ -156,13 +68,7 @@ def test_six_cycles_bit_identical_and_lagged(shape, oracle):
         assert lagged(mg_n) >= 0
         same([mg_n.backend.natural("u", 0)], off[n - 1][-1:], (shape, "level 0 behind cycle", n))
     # ... and against the oracle: the same cycles, the residual history to rounding of the norm, level 0 bit for bit
-    nx, forcing, nt, _ = shape
-    op = oracle.OracleProblem([cases.heat_level_spec(nx, cases.lin(2, k), forcing=forcing) for k in level_nts(nt)], variant=1, max_iter=6,
-                              tol=0.0)
-    ref = op.solve()
-    conv = mg.conv[1:7]
-    assert np.max(np.abs(conv - ref) / ref) <= 1e-10, (conv, ref)
-    assert np.array_equal(off[5][-1], op.state("u", 0))
+    hc.against_oracle(oracle, mg, off[5][-1], hc.heat_specs(*shape[:3]), 6)
 
 
 def test_mode_0_never_lags():
@@ -201,16 +107,12 @@ def test_planned_cycles(blocks):
     """a planned cycle runs launch by launch twice (a block's way up lags, the next pass of another block has the rows put in place),
     then as a captured graph, into which nothing lags and nothing is settled"""
     need_gpu()
-    from pymgrit_amd.core.options import options
     shape = GUARD_SHAPE
-    options.plan_graph = "require"
-    try:
+    with hc.planned_graph():
         runs = []
         for lag in (0, 2):
             mg = build(*shape, lag, **({} if blocks == 1 else dict(plan_blocks=blocks)))
             runs.append((mg, [cycle(mg, it) for it in range(5)] + [[mg.backend.natural("u", 0)]]))
-    finally:
-        options.reset("plan_graph")
     (mg_off, off), (mg_on, on) = runs
     for it, (a, b) in enumerate(zip(on, off)):
         same(a, b, (blocks, "cycle", it))
@@ -255,12 +157,8 @@ def test_replay_behind_cycles_that_lagged(lag, timed):
     down), mode 1 in the third; one cycle more leaves the other parity. Behind lagged(1) the graph itself reads the right rows, but
     the record would stay pending through the replays and the next look would rebuild row cend from rows the graph has rewritten"""
     need_gpu()
-    from pymgrit_amd.core.options import options
-    options.plan_graph = "require"
-    try:
+    with hc.planned_graph():
         off, on = timed_then_replayed(0, timed), timed_then_replayed(lag, timed)
-    finally:
-        options.reset("plan_graph")
     for k, (a, b) in enumerate(zip(on, off)):
         same(a, b, (lag, timed, k))
 
@@ -269,9 +167,7 @@ def test_two_solves_on_one_solver():
     """mode 2, planned cycles: the second solve() runs the first iteration's plan launch by launch, which lags, and then replays the
     graph of the later iterations"""
     need_gpu()
-    from pymgrit_amd.core.options import options
-    options.plan_graph = "require"
-    try:
+    with hc.planned_graph():
         got = []
         for lag in (0, 2):
             mg = build(*GUARD_SHAPE, lag, max_iter=6)
@@ -283,8 +179,6 @@ def test_two_solves_on_one_solver():
             if lag:
                 assert any(x[4] for x in mg.backend.lib.log) and any(x[0] == UP and x[2] >= 0 for x in mg.backend.lib.log)
             got.append(out)
-    finally:
-        options.reset("plan_graph")
     same(got[1], got[0], "two solves")
 
 
@@ -328,60 +222,14 @@ def finish(mg, n, extra=()):
     return out + [mg.backend.natural("u", 0)]
 
 
-def g_natural(mg, n):
-    return finish(mg, n, [mg.backend.natural("u", 0)])
-
-
-def g_U(mg, n):
-    return finish(mg, n, [mg.backend.U[0].cpu().numpy()])
-
-
-def g_raw_U(mg, n):
-    return finish(mg, n, [mg.backend._U[0].cpu().numpy()])
-
-
-def g_payload(mg, n):
-    return finish(mg, n, [mg.backend.payload(0, int(i)).cpu().numpy() for i in (4, 8, 255, 256)])
-
-
-def g_vector_read(mg, n):
-    return finish(mg, n, [np.asarray(mg.u[0][i].get_values()) for i in (4, 7, 8, 256)])
+def guard(action):
+    return lambda mg, n: finish(mg, n, action(mg))
 
 
 def g_vector_write(mg, n):
     vec = mg.u[1][3]          # (a coarse row: any vector of the right size)
     mg.u[0][8] = vec
     mg.u[0][11] = vec
-    return finish(mg, n)
-
-
-def g_set_natural(mg, n):
-    x, _ = cases.heat_grid(mg.problem[0].nx + 2)
-    mg.backend.set_natural("u", 0, np.stack([cases.heat_input(x, k) for k in range(len(mg.problem[0].t))]))
-    return finish(mg, n)
-
-
-def g_relax(mode):
-    def run(mg, n):
-        runs = mg._c_runs(0) if mode == 'C' else mg._f_runs(0)
-        if mode == 'FC':       # not a sweep of level 0: refused, behind the guard
-            from pymgrit_amd.core.hip_lib import MgritHipError
-            with pytest.raises(MgritHipError):
-                mg.backend.relax(0, runs, mode)
-        else:
-            mg.backend.relax(0, runs, mode)
-        return finish(mg, n)
-    return run
-
-
-def g_residual(mg, n):
-    mg.backend._invalidate()      # (not the sums the way up has left: the residual kernel's own)
-    return finish(mg, n, [np.asarray(mg.backend.residual_norms(mg._c_points(0)))])
-
-
-def g_correction_by_hand(mg, n):
-    mg.error_correction(lvl=0)
-    mg.f_relax(lvl=0)
     return finish(mg, n)
 
 
@@ -394,10 +242,9 @@ def g_relax_level_1(mg, n):
 
 def g_settle(lvl):
     def run(mg, n):
-        from pymgrit_amd.core import hip_lib
-        hip_lib.settle(mg.backend.h, lvl)
+        hc.settle(lvl)(mg)
         assert lagged(mg) == -1
-        return finish(mg, n, [mg.backend._U[0].cpu().numpy()])
+        return finish(mg, n, hc.raw_U((0,))(mg))
     return run
 
 
@@ -407,10 +254,12 @@ def g_second_way_up(mg, n):
     return finish(mg, n, [np.asarray(mg.compute_residual())])
 
 
-GUARDS = {"natural": g_natural, "U": g_U, "raw_U": g_raw_U, "payload": g_payload, "vector_read": g_vector_read,
-          "vector_write": g_vector_write, "set_natural": g_set_natural, "relax_F": g_relax('F'), "relax_C": g_relax('C'),
-          "relax_FC": g_relax('FC'), "residual": g_residual, "correction_by_hand": g_correction_by_hand,
-          "relax_level_1": g_relax_level_1, "settle_0": g_settle(0), "settle_1": g_settle(1), "second_way_up": g_second_way_up}
+GUARDS = {"natural": guard(hc.natural("u", 0)), "U": guard(hc.U((0,))), "raw_U": guard(hc.raw_U((0,))),
+          "payload": guard(hc.payload(0, (4, 8, 255, 256))), "vector_read": guard(hc.vector_read("u", 0, (4, 7, 8, 256))),
+          "vector_write": g_vector_write, "set_natural": guard(hc.set_natural_level0), "relax_F": guard(hc.relax_level0('F')),
+          "relax_C": guard(hc.relax_level0('C')), "relax_FC": guard(hc.relax_level0('FC')), "residual": guard(hc.residual_norms_fresh),
+          "correction_by_hand": guard(hc.correction_by_hand(0)), "relax_level_1": g_relax_level_1, "settle_0": g_settle(0),
+          "settle_1": g_settle(1), "second_way_up": g_second_way_up}
 
 
 @pytest.mark.parametrize("parity", [1, 0])
@@ -489,18 +338,6 @@ def test_switch_and_argument_checks():
     same([mg.backend._U[0].cpu().numpy()], [mg0.backend._U[0].cpu().numpy()], "raw rows behind the lag-only settle")
 
 
-_CHILD = """
-import sys
-sys.path.insert(0, {tests!r})
-import test_hip_lagged_cpoints as t
-from pymgrit_amd import Mgrit
-mg = Mgrit(t.problem(1022, True, 257), logging_lvl=30, max_iter=2, tol=0.0)
-for it in range(2):
-    t.cycle(mg, it)
-print("LAGGED", mg.backend.lib.mgrit_hip_lagged(mg.backend.h, 0))
-"""
-
-
 def test_environment_variable(monkeypatch):
     """MGRIT_HIP_LAG as a child process finds it when its engine is made: 2 lags in the second cycle. Unset, the engine waits (this
     process: nothing lags in the second cycle, and the setter's refusals have left the mode alone)"""
@@ -511,9 +348,5 @@ def test_environment_variable(monkeypatch):
     for it in range(2):
         cycle(mg, it)
     assert mg.backend.lib.mgrit_hip_lagged(mg.backend.h, 0) == -1
-    env = dict(os.environ, MGRIT_HIP_LAG="2")
-    tests = os.path.dirname(os.path.abspath(__file__))
-    env["PYTHONPATH"] = os.pathsep.join([os.path.dirname(tests), tests] + ([env["PYTHONPATH"]] if env.get("PYTHONPATH") else []))
-    out = subprocess.run([sys.executable, "-c", _CHILD.format(tests=tests)], env=env, capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert int(out.stdout.split("LAGGED")[1].split()[0]) >= 0, out.stdout
+    got = hc.child_cycles({"MGRIT_HIP_LAG": "2"}, 2, cycle="coarse_cycle")
+    assert got["lagged"] >= 0, got

@@ -13,7 +13,8 @@ import os
 import numpy as np
 import pytest
 
-import cases
+import heat1d_cycles as hc
+from heat1d_cycles import need_gpu, problem, same, twin_cycle as cycle, twin_finish as finish, twin_pending as pending
 from pymgrit_amd.core import hip_lib
 
 pytestmark = pytest.mark.gpu
@@ -24,84 +25,24 @@ WATCHED = ("mgrit_hip_cf_fas", "mgrit_hip_relax", "mgrit_hip_fas_fused_opts", "m
 RELAX_FC, RELAX_CHAIN = hip_lib.RELAX_FC, hip_lib.RELAX_CHAIN
 
 
-class Probe:
-    """the backend's library handle with a note behind every producer and partner: (export, level, its last integer argument,
-    mgrit_hip_twin of every level > 0 after the call, was the stream capturing)"""
-
-    def __init__(self, lib, h, n_levels):
-        self.__dict__.update(_lib=lib, _h=h, _n=n_levels, log=[])
-
-    def twins(self):
-        return tuple(self._lib.mgrit_hip_twin(self._h, lvl) for lvl in range(1, self._n))
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-        if name not in WATCHED:
-            return fn
-
-        def call(*args):
-            rc = fn(*args)
-            self.log.append((name, int(args[1]), int(args[3]) if len(args) > 3 else int(args[2]), self.twins(),
-                             bool(torch.cuda.is_current_stream_capturing())))
-            return rc
-        return call
-
-
-def level_nts(nt, levels):
-    return [(nt - 1) // 4 ** k + 1 for k in range(levels)]
-
-
-def problem(nx, forcing, nt, levels=3):
-    from pymgrit_amd import Heat1D
-    kw = dict(rhs_separable=[(cases.rhs_space, cases.rhs_time)]) if forcing else {}
-    return [Heat1D(x_start=0, x_end=1, nx=nx, a=1, init_cond=cases.init_cond, t_start=0, t_stop=2, nt=k, **kw) for k in level_nts(nt, levels)]
+def probe(lib, h, n_levels=3):
+    """the library handle with a note behind every producer and partner: (export, level, its last integer argument, mgrit_hip_twin
+    of every level > 0 after the call, was the stream capturing)"""
+    def note(lib, h, name, args):
+        return name, int(args[1]), int(args[3]) if len(args) > 3 else int(args[2]), hc.twins(lib, h, n_levels), hc.capturing()
+    return hc.Probe(lib, h, WATCHED, note, n_levels)
 
 
 def build(nx, forcing, nt, mask, comm=None, levels=3, **kw):
     """a solver whose engine was created with MGRIT_HIP_TWIN = mask, its library handle probed"""
-    from pymgrit_amd import Mgrit
-    old = os.environ.get("MGRIT_HIP_TWIN")
-    os.environ["MGRIT_HIP_TWIN"] = str(mask)
-    try:
-        mg = Mgrit(problem(nx, forcing, nt, levels), logging_lvl=30, comm_time=comm, **dict(dict(max_iter=5, tol=0.0), **kw))
-    finally:
-        os.environ.pop("MGRIT_HIP_TWIN", None)
-        if old is not None:
-            os.environ["MGRIT_HIP_TWIN"] = old
-    assert type(mg.backend).__name__ == "HipBackend"
-    mg.backend.lib = Probe(mg.backend.lib, mg.backend.h, levels)
-    return mg
-
-
-def raw(mg):
-    """copies of the raw slabs of u, v, g of every level, on the device: nothing is put in place for the look"""
-    be = mg.backend
-    return [s[lvl].clone() for lvl in range(mg.lvl_max) for s in (be._U, be.V, be.G) if s[lvl] is not None]
-
-
-def cycle(mg, it):
-    """one cycle with its residual check; what it leaves: the residual sums (the way up's own, fetched) and every raw slab"""
-    mg.iteration(lvl=0, cycle_type=mg.cycle_type, iteration=it, first_f=True)
-    mg.convergence_criterion(iteration=it + 1)
-    assert set(mg.backend.lib.twins()) == {-1}, "a record is pending behind a whole cycle"
-    return [np.asarray(mg.compute_residual())] + raw(mg)
-
-
-def same(a, b, what):
-    assert len(a) == len(b), what
-    for k, (x, y) in enumerate(zip(a, b)):
-        assert torch.equal(x, y) if torch.is_tensor(x) else np.array_equal(x, y), (what, k)
+    return hc.build(problem(nx, forcing, nt, levels), env={"MGRIT_HIP_TWIN": str(mask)}, comm=comm,
+                    probe=lambda lib, h: probe(lib, h, levels), **dict(dict(max_iter=5, tol=0.0), **kw))
 
 
 def after(mg, name, lvl, coarse, arg=None):
     """mgrit_hip_twin(coarse) behind every call of the export on level lvl (with the last integer argument arg)"""
     log = mg if isinstance(mg, list) else mg.backend.lib.log
     return [t[coarse - 1] for n, l, a, t, _ in log if n == name and l == lvl and (arg is None or a == arg)]
-
-
-def need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU test selected but no GPU visible")
 
 
 def five_cycles(shape, mask):
@@ -144,13 +85,7 @@ def test_five_cycles_bit_identical_and_deferred(shape, mask):
 def test_against_the_oracle(shape, oracle):
     need_gpu()
     mg, got = five_cycles(shape, 3)
-    nx, forcing, nt = shape
-    op = oracle.OracleProblem([cases.heat_level_spec(nx, cases.lin(2, k), forcing=forcing) for k in level_nts(nt, 3)], variant=1, max_iter=5,
-                              tol=0.0)
-    ref = op.solve()
-    conv = mg.conv[1:6]
-    assert np.max(np.abs(conv - ref) / ref) <= 1e-10, (conv, ref)
-    assert np.array_equal(got[-1][0], op.state("u", 0))
+    hc.against_oracle(oracle, mg, got[-1][0], hc.heat_specs(*shape), 5)
 
 
 def never(mg):
@@ -175,16 +110,12 @@ def test_loopback_ranks_never_defer():
 
 def test_captured_planned_cycle_never_defers():
     need_gpu()
-    from pymgrit_amd.core.options import options
     shape = (4097, True, 1025)
-    options.plan_graph = "require"
-    try:
+    with hc.planned_graph():
         runs = []
         for mask in (0, 3):
             mg = build(*shape, mask)
             runs.append((mg, [cycle(mg, it) for it in range(5)] + [[mg.backend.natural("u", 0)]]))
-    finally:
-        options.reset("plan_graph")
     (mg_off, off), (mg_on, on) = runs
     for it, (a, b) in enumerate(zip(on, off)):
         same(a, b, ("planned", it))
@@ -197,7 +128,6 @@ def test_captured_planned_cycle_never_defers():
 
 def test_item_by_item_fas_pass_and_sequential_solve_never_defer_the_coarsest_level():
     need_gpu()
-    from pymgrit_amd.core.options import options
     shape = (4097, True, 1025)
     ref = off_run(shape)
     mg = build(*shape, 3)
@@ -206,14 +136,11 @@ def test_item_by_item_fas_pass_and_sequential_solve_never_defer_the_coarsest_lev
     for it, (a, b) in enumerate(zip(got, ref)):
         same(a, b, ("item by item", it))
     assert set(after(mg, WATCHED[2], 1, 2)) == {-1} and all(d >= 0 for d in after(mg, WATCHED[0], 0, 1))
-    options.coarse_solve = "sequential"
-    try:
+    with hc.sequential_coarse():
         runs = []
         for mask in (0, 3):
             mg = build(*shape, mask)
             runs.append((mg, [cycle(mg, it) for it in range(3)]))
-    finally:
-        options.reset("coarse_solve")
     for it, (a, b) in enumerate(zip(runs[1][1], runs[0][1])):
         same(a, b, ("sequential", it))
     mg = runs[1][0]
@@ -222,65 +149,20 @@ def test_item_by_item_fas_pass_and_sequential_solve_never_defer_the_coarsest_lev
 
 
 # ---- the guard: with a record pending, every other way to the rows sees them in place -------------------------------------------
-def pending(mg, lvl):
-    """two cycles, then the way down of a third as far as the pass that fills level lvl: the level waits for its partner"""
-    for it in range(2):
-        cycle(mg, it)
-    mg.backend.begin_cycle()
-    mg._down_level(0, mg._level_intervals(0))
-    if lvl == 2:
-        route, lists = mg._route(1, True)
-        assert route == 'coarse'
-        mg._down_coarse(1, lists)
-
-
-def finish(mg, extra=()):
-    """a whole cycle behind whatever the guard test did, then everything there is to see"""
-    return list(extra) + cycle(mg, 2) + [mg.backend.natural("u", 0)]
-
-
 def g_natural(mg, lvl):
     return finish(mg, [mg.backend.natural("u", lvl)])
-
-
-COARSEST_RUNS = {'F': [(1, 3), (5, 3)], 'C': [(4, 1), (8, 1)], 'FC': [(1, 4), (5, 4)], 'CHAIN': [(1, 10)]}
-
-
-def g_relax(mode):
-    def run(mg, lvl):
-        if lvl == 2:   # the coarsest level has no cycle lists of its own: two intervals' worth by hand, in the mode
-            mg.backend.relax(lvl, COARSEST_RUNS[mode], mode)     # asked for; CHAIN: a part of the forward solve, step by step
-        elif mode == 'FC':   # another run list: every second interval of the level
-            fc_runs = mg._route(1, True)[1][0]
-            mg.backend.relax(1, [(int(s), int(n)) for s, n in list(fc_runs)[::2]], 'FC')
-        else:
-            mg.backend.relax(1, mg._c_runs(1) if mode == 'C' else mg._f_runs(1), mode)
-        return finish(mg)
-    return run
 
 
 def g_level_above(mg, lvl):
     """an entry point of the level above reads the pending level too: the residual of level 0, an F-relaxation of level 1"""
     if lvl == 1:
-        return finish(mg, [np.asarray(mg.backend.residual_norms(mg._c_points(0)))])
-    mg.backend.relax(1, mg._f_runs(1), 'F')
+        return finish(mg, hc.residual_norms(mg))
+    hc.relax(1, 'F')(mg)
     return finish(mg)
 
 
 def g_correction_by_hand(mg, lvl):
     mg.error_correction(lvl=lvl - 1)
-    return finish(mg)
-
-
-def g_block_solve_by_phases(mg, lvl):
-    if lvl == 1:
-        before = mg.backend.lib.twins()
-        mg.backend.block_solve(2, 7)      # (reaches level 2 only: the record of level 1 stays, its partner is still to come)
-        assert mg.backend.lib.twins() == before
-        mg.backend.relax(1, mg._f_runs(1), 'F')
-    else:
-        mg.backend.block_solve(2, 1)
-        mg.backend.block_solve(2, 6)
     return finish(mg)
 
 
@@ -306,7 +188,7 @@ def g_set_natural(which):
     def run(mg, lvl):
         values = mg.backend.natural("v", lvl) * 0.5 + 0.25     # (natural("v") settles nothing: the record is still pending here)
         mg.backend.set_natural(which, lvl, values)
-        return finish(mg, raw(mg))
+        return finish(mg, hc.raw_slabs(mg))
     return run
 
 
@@ -318,12 +200,13 @@ def g_vector_write(which):
     def run(mg, lvl):
         vec = mg.v[lvl][5]          # (a read of v settles nothing)
         (mg.u if which == "u" else mg.v)[lvl][4] = vec
-        return finish(mg, raw(mg))
+        return finish(mg, hc.raw_slabs(mg))
     return run
 
 
-GUARDS = {"natural": g_natural, "relax_F": g_relax('F'), "relax_C": g_relax('C'), "relax_FC": g_relax('FC'), "relax_CHAIN": g_relax('CHAIN'),
-          "residual": g_level_above, "correction_by_hand": g_correction_by_hand, "block_solve_by_phases": g_block_solve_by_phases,
+GUARDS = {"natural": g_natural, "relax_F": hc.twin_relax('F'), "relax_C": hc.twin_relax('C'), "relax_FC": hc.twin_relax('FC'),
+          "relax_CHAIN": hc.twin_relax('CHAIN'),
+          "residual": g_level_above, "correction_by_hand": g_correction_by_hand, "block_solve_by_phases": hc.twin_block_solve_by_phases,
           "second_producer": g_second_producer, "U": g_U, "payload": g_payload, "set_natural_u": g_set_natural("u"),
           "set_natural_v": g_set_natural("v"), "vector_read": g_vector_read, "vector_write_u": g_vector_write("u"),
           "vector_write_v": g_vector_write("v")}
@@ -404,15 +287,7 @@ def test_switch_and_argument_checks():
     # the environment variable: anything but one digit 0..3, or none, leaves the default, which is (A) alone
     for text, want in (("1", (True, False)), ("3", (True, True)), ("0", (False, False)), ("7", (False, True)), ("x", (False, True)),
                        (None, (False, True))):
-        os.environ.pop("MGRIT_HIP_TWIN", None)
-        if text is not None:
-            os.environ["MGRIT_HIP_TWIN"] = text
-        try:
-            from pymgrit_amd import Mgrit
-            m2 = Mgrit(problem(4097, True, 1025), logging_lvl=30, max_iter=1, tol=0.0)
-        finally:
-            os.environ.pop("MGRIT_HIP_TWIN", None)
-        m2.backend.lib = Probe(m2.backend.lib, m2.backend.h, 3)
+        m2 = hc.build(problem(4097, True, 1025), env={"MGRIT_HIP_TWIN": text}, probe=probe, max_iter=1, tol=0.0)
         cycle(m2, 0)
         assert (all(d >= 0 for d in after(m2, WATCHED[0], 0, 1)), all(d >= 0 for d in after(m2, WATCHED[2], 1, 2))) == want, text
 

@@ -1,43 +1,31 @@
 """GPU: the way up of levels 1 and 0 in one pass (include/mgrit_hip.h, mgrit_hip_up2_pending). Where the level-0 way up lags,
 mgrit_hip_ec_relax of level 1 launches nothing and the level-0 pass computes u of level 1 where it needs it (up2_kernel); u of level 1
 is brought up -- by the deferred pass, run late -- only for whoever asks. Everything is compared bit for bit with the same sequence
-run with the switch off (MGRIT_HIP_UP2=0) in the same process, and against the oracle's level 0 and residual history. Hierarchy:
+run with the switch off (MGRIT_HIP_UP2=0) in the same process, and against the oracle's level 0 and residual history. The solver
+is the lag tests' (heat1d_cycles.lag_build) with MGRIT_HIP_UP2 beside MGRIT_HIP_LAG; pending_trace.py scripts the same guards. Hierarchy:
 Heat1D, 3 levels, m = 4, at one state size per kernel instance, with and without forcing, level-0 chunks of 4 and 16 intervals
 (a chunk must start on a C-point of level 1's own coarsening to pair: chunks of 3, and m = (4, 3), do not)."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import cases
-import test_hip_lagged_cpoints as base
-from test_hip_lagged_cpoints import after, coarse_state, cycle, lagged, need_gpu, same, DOWN, UP
+import heat1d_cycles as hc
+from heat1d_cycles import (blind_cycle, coarse_state, half_cycle, lagged, need_gpu, same, coarse_cycle as cycle, up2_finish as finish,
+                           up2_pending as pending, UP2_GUARDS as GUARDS)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 # (nx, forcing, nt, chunk): one wave per state / 512 threads / 1024 threads, each with and without forcing; chunks of 16; a coarsest
 # level that steps sequentially (nt = 257)
-SHAPES = [(nx, forcing, 1025, chunk) for chunk in (4, 16) for nx in base.SIZES for forcing in (False, True)] + [(4097, True, 257, 4)]
+SHAPES = [(nx, forcing, 1025, chunk) for chunk in (4, 16) for nx in hc.SIZES for forcing in (False, True)] + [(4097, True, 257, 4)]
 GUARD_SHAPE = (4097, True, 257, 4)
 
 
 def build(nx, forcing, nt, chunk, up2, lag=2, env=(), **kw):
-    return base.build(nx, forcing, nt, chunk, lag, env=dict(env, MGRIT_HIP_UP2=str(up2)), **kw)
-
-
-def pending(mg):
-    return mg.backend.lib.mgrit_hip_up2_pending(mg.backend.h)
-
-
-def blind_cycle(mg, it):
-    """one cycle with its residual check and no look at any slab: what it leaves pending stays pending"""
-    mg.iteration(lvl=0, cycle_type=mg.cycle_type, iteration=it, first_f=True)
-    mg.convergence_criterion(iteration=it + 1)
-    return [np.asarray(mg.compute_residual())]
+    return hc.lag_build(nx, forcing, nt, chunk, lag, env=dict(env, MGRIT_HIP_UP2=str(up2)), **kw)
 
 
 _OFF = {}     # shape -> what six cycles with the switch off leave (computed once, never modified)
@@ -81,35 +69,23 @@ def test_six_cycles_bit_identical_and_fused(shape, oracle):
         if n == 6:
             same(coarse_state(mg_n), off[5][1:-1], (shape, "coarse levels behind six blind cycles"))
     # ... and against the oracle: the residual history to rounding of the norm, level 0 bit for bit
-    nx, forcing, nt, _ = shape
-    op = oracle.OracleProblem([cases.heat_level_spec(nx, cases.lin(2, k), forcing=forcing) for k in base.level_nts(nt)], variant=1,
-                              max_iter=6, tol=0.0)
-    ref = op.solve()
-    conv = mg.conv[1:7]
-    assert np.max(np.abs(conv - ref) / ref) <= 1e-10, (conv, ref)
-    assert np.array_equal(off[5][-1], op.state("u", 0))
+    hc.against_oracle(oracle, mg, off[5][-1], hc.heat_specs(*shape[:3]), 6)
 
 
 def test_cpoint_followed_by_cpoint():
     """a level-1 run list with a C-point that another C-point follows (m = (4, 1) is no hierarchy: the time grid of level 2 keeps two
     neighbours of level 1): nt = 1025, level 2 = every fourth point of level 1 plus point 5"""
     need_gpu()
-    from pymgrit_amd import Heat1D, Mgrit
+    from pymgrit_amd import Heat1D
     got = []
     for up2 in (0, 1):
-        os.environ["MGRIT_HIP_LAG"], os.environ["MGRIT_HIP_UP2"] = "2", str(up2)
-        try:
-            kw = dict(x_start=0, x_end=1, nx=1022, a=1, init_cond=cases.init_cond, rhs_separable=[(cases.rhs_space, cases.rhs_time)])
-            t0 = np.linspace(0, 2, 1025)
-            t1 = t0[::4]
-            idx2 = np.unique(np.concatenate((np.arange(0, 257, 4), [5])))
-            prob = [Heat1D(t_start=0, t_stop=2, nt=1025, **kw), Heat1D(t_interval=t1, **kw), Heat1D(t_interval=t1[idx2], **kw)]
-            mg = Mgrit(prob, logging_lvl=30, max_iter=6, tol=0.0)
-        finally:
-            os.environ.pop("MGRIT_HIP_LAG"), os.environ.pop("MGRIT_HIP_UP2")
+        kw = dict(x_start=0, x_end=1, nx=1022, a=1, init_cond=cases.init_cond, rhs_separable=[(cases.rhs_space, cases.rhs_time)])
+        t0 = np.linspace(0, 2, 1025)
+        t1 = t0[::4]
+        idx2 = np.unique(np.concatenate((np.arange(0, 257, 4), [5])))
+        prob = [Heat1D(t_start=0, t_stop=2, nt=1025, **kw), Heat1D(t_interval=t1, **kw), Heat1D(t_interval=t1[idx2], **kw)]
+        mg = hc.build(prob, env={"MGRIT_HIP_LAG": "2", "MGRIT_HIP_UP2": str(up2)}, chunk=4, max_iter=6, tol=0.0)
         be = mg.backend
-        ids = be._intervals_id
-        be._intervals_id = lambda lvl, intervals, chunk=None: ids(lvl, intervals, chunk=4 if lvl == 0 and chunk is None else chunk)
         out, seen = [], []
         for it in range(4):
             out += blind_cycle(mg, it)
@@ -129,15 +105,10 @@ def test_does_not_pair(name):
         if name == "chunks_of_3":
             mg = build(4097, True, 257, 3, up2)
         else:
-            from pymgrit_amd import Heat1D, Mgrit
-            os.environ["MGRIT_HIP_LAG"], os.environ["MGRIT_HIP_UP2"] = "2", str(up2)
-            try:
-                kw = dict(x_start=0, x_end=1, nx=1022, a=1, init_cond=cases.init_cond, t_start=0, t_stop=2)
-                mg = Mgrit([Heat1D(nt=nt, **kw) for nt in (769, 193, 65)], logging_lvl=30, max_iter=6, tol=0.0)
-            finally:
-                os.environ.pop("MGRIT_HIP_LAG"), os.environ.pop("MGRIT_HIP_UP2")
-            ids = mg.backend._intervals_id
-            mg.backend._intervals_id = lambda lvl, intervals, chunk=None: ids(lvl, intervals, chunk=4 if lvl == 0 and chunk is None else chunk)
+            from pymgrit_amd import Heat1D
+            kw = dict(x_start=0, x_end=1, nx=1022, a=1, init_cond=cases.init_cond, t_start=0, t_stop=2)
+            mg = hc.build([Heat1D(nt=nt, **kw) for nt in (769, 193, 65)], env={"MGRIT_HIP_LAG": "2", "MGRIT_HIP_UP2": str(up2)}, chunk=4,
+                          max_iter=6, tol=0.0)
         out = []
         for it in range(3):
             out += blind_cycle(mg, it)
@@ -182,9 +153,7 @@ def test_loopback_ranks_never_pending():
 @pytest.mark.parametrize("blocks", [1, 3])
 def test_planned_cycles_never_pending_inside_a_capture(blocks):
     need_gpu()
-    from pymgrit_amd.core.options import options
-    options.plan_graph = "require"
-    try:
+    with hc.planned_graph():
         runs = []
         for up2 in (0, 1):
             mg = build(*GUARD_SHAPE, up2, **({} if blocks == 1 else dict(plan_blocks=blocks)))
@@ -194,8 +163,6 @@ def test_planned_cycles_never_pending_inside_a_capture(blocks):
                 seen.append((pending(mg), any(x[4] for x in mg.backend.lib.log)))
                 out += coarse_state(mg)
             runs.append((out + [mg.backend.natural("u", 0)], seen, mg))
-    finally:
-        options.reset("plan_graph")
     same(runs[1][0], runs[0][0], (blocks, "planned"))
     assert any(c for _, c in runs[1][1]), "no cycle was captured"
     assert all(p == 0 for p, c in runs[1][1] if c), runs[1][1]      # captured and replayed cycles leave nothing pending
@@ -203,59 +170,6 @@ def test_planned_cycles_never_pending_inside_a_capture(blocks):
 
 
 # ---- the guard: with a record pending, every way to a row it needs finds the rows of the two passes -------------------------------
-def half_cycle(mg, it):
-    """a V-cycle up to and including the way up of level 1 (Mgrit.iteration(lvl=0) with the level-0 way up left out), then what is
-    left of it"""
-    real = mg.backend.ec_relax_res
-    skipped = []
-    mg.backend.ec_relax_res = lambda lvl, intervals, base=0: skipped.append((lvl, intervals, base)) if lvl == 0 else real(lvl, intervals, base)
-    try:
-        mg.iteration(lvl=0, cycle_type=mg.cycle_type, iteration=it, first_f=True)
-    finally:
-        mg.backend.ec_relax_res = real
-    assert len(skipped) == 1
-    return skipped[0]
-
-
-def finish(mg, n):
-    out = []
-    for it in range(n, n + 2):
-        out += blind_cycle(mg, it)
-    return out + coarse_state(mg) + [mg.backend.natural("u", 0)]
-
-
-GUARDS = {
-    "natural_u0": lambda mg: [mg.backend.natural("u", 0)],
-    "natural_u1": lambda mg: [mg.backend.natural("u", 1)],
-    "natural_g1": lambda mg: [mg.backend.natural("g", 1)],
-    "natural_u2": lambda mg: [mg.backend.natural("u", 2)],
-    "U": lambda mg: [mg.backend.U[k].cpu().numpy() for k in (0, 1)],
-    "raw_U": lambda mg: [mg.backend._U[k].cpu().numpy() for k in (0, 1, 2)],
-    "payload_0": lambda mg: [mg.backend.payload(0, int(i)).cpu().numpy() for i in (4, 8, 256)],
-    "payload_1": lambda mg: [mg.backend.payload(1, int(i)).cpu().numpy() for i in (3, 4, 5, 64)],
-    "vector_read_1": lambda mg: [np.asarray(mg.u[1][i].get_values()) for i in (3, 4, 5, 64)],
-    "vector_read_g1": lambda mg: [np.asarray(mg.g[1][i].get_values()) for i in (3, 4, 5)],
-    "set_natural_0": lambda mg: mg.backend.set_natural("u", 0, np.stack([cases.heat_input(cases.heat_grid(mg.problem[0].nx + 2)[0], k)
-                                                                          for k in range(len(mg.problem[0].t))])),
-    "relax_F_0": lambda mg: mg.backend.relax(0, mg._f_runs(0), 'F'),
-    "relax_C_0": lambda mg: mg.backend.relax(0, mg._c_runs(0), 'C'),
-    "relax_F_1": lambda mg: mg.backend.relax(1, mg._f_runs(1), 'F'),
-    "relax_C_1": lambda mg: mg.backend.relax(1, mg._c_runs(1), 'C'),
-    "relax_FC_1": lambda mg: mg.backend.relax(1, [(int(s), int(n) + 1) for s, n in mg._f_runs(1)], 'FC'),
-    "relax_F_2": lambda mg: mg.backend.relax(2, [(1, 3)], 'F'),
-    "settle_0": lambda mg: __import__("pymgrit_amd.core.hip_lib", fromlist=["x"]).settle(mg.backend.h, 0),
-    "settle_1": lambda mg: __import__("pymgrit_amd.core.hip_lib", fromlist=["x"]).settle(mg.backend.h, 1),
-    "settle_2": lambda mg: __import__("pymgrit_amd.core.hip_lib", fromlist=["x"]).settle(mg.backend.h, 2),
-    "correction_by_hand_0": lambda mg: (mg.error_correction(lvl=0), mg.f_relax(lvl=0)),
-    "correction_by_hand_1": lambda mg: (mg.error_correction(lvl=1), mg.f_relax(lvl=1)),
-    "second_way_up_1": lambda mg: mg._ec_f_relax(1),
-    "write_g1": lambda mg: mg.g[1].__setitem__(5, mg.g[1][6]),
-    "write_u2": lambda mg: mg.u[2].__setitem__(3, mg.u[2][2]),
-    "set_natural_g1": lambda mg: mg.backend.set_natural("g", 1, 0.5 * mg.backend.natural("g", 1)),
-    "set_natural_u2": lambda mg: mg.backend.set_natural("u", 2, 0.5 * mg.backend.natural("u", 2)),
-}
-
-
 @pytest.mark.parametrize("state", ["done1", "done0", "noted"])
 @pytest.mark.parametrize("name", sorted(GUARDS))
 def test_guard(name, state):
@@ -357,9 +271,7 @@ def test_two_solves_and_replay_behind_deferring_cycles():
     """planned cycles: launch by launch twice (the second defers), captured, replayed -- a replay goes past the engine, so the record is
     settled in front of it --; a second solve() runs its first iteration launch by launch again"""
     need_gpu()
-    from pymgrit_amd.core.options import options
-    options.plan_graph = "require"
-    try:
+    with hc.planned_graph():
         got = []
         for up2 in (0, 1):
             mg = build(*GUARD_SHAPE, up2, max_iter=6)
@@ -369,8 +281,6 @@ def test_two_solves_and_replay_behind_deferring_cycles():
                 out += [np.array(res["conv"]), mg.backend.natural("u", 0)] + coarse_state(mg)
                 assert pending(mg) == 0
             got.append(out)
-    finally:
-        options.reset("plan_graph")
     same(got[1], got[0], "two solves")
 
 
@@ -408,29 +318,8 @@ def test_interface():
     same([mg.backend._U[k].cpu().numpy() for k in (0, 1)], [mg0.backend._U[k].cpu().numpy() for k in (0, 1)], "raw rows behind the settle")
 
 
-_CHILD = """
-import sys
-sys.path.insert(0, {tests!r})
-import test_hip_up2 as t
-from pymgrit_amd import Mgrit
-mg = Mgrit(t.base.problem(1022, True, 1025), logging_lvl=30, max_iter=2, tol=0.0)
-ids = mg.backend._intervals_id
-mg.backend._intervals_id = lambda lvl, intervals, chunk=None: ids(lvl, intervals, chunk=4 if lvl == 0 and chunk is None else chunk)
-for it in range(2):
-    t.blind_cycle(mg, it)
-print("PENDING", mg.backend.lib.mgrit_hip_up2_pending(mg.backend.h))
-"""
-
-
 @pytest.mark.parametrize("value,expected", [("0", 0), ("1", 2), (None, 2)])
 def test_environment_variable(value, expected):
     need_gpu()
-    env = dict(os.environ, MGRIT_HIP_LAG="2")
-    env.pop("MGRIT_HIP_UP2", None)
-    if value is not None:
-        env["MGRIT_HIP_UP2"] = value
-    tests = os.path.dirname(os.path.abspath(__file__))
-    env["PYTHONPATH"] = os.pathsep.join([os.path.dirname(tests), tests] + ([env["PYTHONPATH"]] if env.get("PYTHONPATH") else []))
-    out = subprocess.run([sys.executable, "-c", _CHILD.format(tests=tests)], env=env, capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert int(out.stdout.split("PENDING")[1].split()[0]) == expected, out.stdout
+    got = hc.child_cycles({"MGRIT_HIP_LAG": "2", "MGRIT_HIP_UP2": value}, 2, nt=1025, chunk=4)
+    assert got["up2_pending"] == expected, got
