@@ -13,16 +13,15 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
 
 def build_problem(case_name, mode):
     import cases
+    import dist_cases
     if case_name.startswith("h2d:"):
         prob, opts = cases.h2d_solve_problem(case_name[4:])
         return prob, None, opts
     if case_name.startswith("at:"):      # AT-MGRIT: (problem, transfer, options incl. the distance k under "_at_k")
-        import test_at_mgrit as at
-        nx, nts, k, opts = at.CASES[case_name[3:]]
-        return at.heat(nx, nts, mode == "plugin"), None, dict(opts, _at_k=k)
+        nx, nts, k, opts = dist_cases.AT_CASES[case_name[3:]]
+        return dist_cases.at_heat(nx, nts, mode == "plugin"), None, dict(opts, _at_k=k)
     if case_name.startswith("lc:"):      # local stopping criteria on several ranks (tests/test_local_conv.py)
-        import test_local_conv as lc
-        make, opts = lc._ranks_problem(case_name[3:])
+        make, opts = dist_cases.local_conv_ranks_problem(case_name[3:])
         prob = make()
         if mode != "plugin":
             for p in prob:

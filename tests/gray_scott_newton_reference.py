@@ -29,11 +29,30 @@ residual / (1 - dt mu), and rounding to float64 adds at most EPS / 2 norm_2(x).
 ``ReferenceGrayScottNewton`` overrides ``step`` with this Phi, which sends a hierarchy to the plugin path. It records, since the last
 ``reset_record()``, the box of every input and result (``box``), the largest long-double residual norm of a returned float64 state
 (``worst_residual``) and the largest norm_2 of a result (``worst_norm``): what the tolerances of the device tests are made of.
+
+The tolerance of the tests (``tau``, ``e_g``, ``exit_criterion`` and the allowances below, shared by the CPU and the GPU tests) between
+two states x, y that both claim to solve F = 0 for the same input, nothing of it measured on the code under test but
+its own residual, which is evaluated here in long double by the reference's code:
+
+    tau = (norm_2(F(x)) + norm_2(F(y))) / (1 - dt mu) + EPS norm_2(x),
+
+mu from the largest |u|, |v| over both states and the input (the segment between them lies in that box). On its own this is an
+inequality any two points of the box satisfy; what gives it teeth is the exit criterion asserted beside it: max|F(x)| < newton_tol +
+E_g for the step's result, E_g the rounding of the step's own evaluation of g:
+
+    E_g = C_G EPS S,   S = 2 R + dt (8 max(du, dv) R / dx^2 + R^3 + max(|a| (1 + R), |b| R)),   R the largest |value| of x and w,
+
+S the sum of the magnitudes of the terms of one value of g. Operation count of gsn_residual_kernel per value of the u plane (the v
+plane takes fewer), half an EPS each on a quantity of magnitude <= S: stencil 3 additions, the subtraction of 4 u and the scaling by
+1 / dx^2 (5 roundings); v v, u (v v), 1 - u, a (1 - u) and their difference (5); the fma's with du and with dt and the subtraction of w
+(3); 1 / dx^2 itself arrives rounded three times (L / nx, its square, the reciprocal), relative 1.5 EPS, where the reference forms it in
+long double (3 more): C_G = 8. The numpy step does not fuse its three multiply-adds: C_G = 9.5 on the host.
 """
 import numpy as np
 import scipy.sparse as sp
 from scipy.sparse.linalg import splu
 
+import cases
 from pymgrit_amd import GrayScott, VectorGrayScott2D
 
 LD = np.longdouble
@@ -143,3 +162,62 @@ class ReferenceGrayScottNewton(GrayScott):
         ret = VectorGrayScott2D(self.nx)
         ret.set_values(x)
         return ret
+
+
+# ---- the allowances of the tests (module docstring) --------------------------------------------------------------------------------
+C_G_DEVICE, C_G_HOST = 8.0, 9.5
+PARS = {"du=100dv": dict(du=1.0, dv=0.01, a=0.09, b=0.086, L=2.0), "du=dv": dict(du=0.5, dv=0.5, a=0.04, b=0.1, L=2.0)}
+
+
+def par_of(app):
+    return (app.du, app.dv, app.a, app.b, app.L)
+
+
+def norm2(a):
+    return float(np.sqrt(np.sum(np.asarray(a, dtype=LD) ** 2)))
+
+
+def margin(app, dt, *states):
+    """1 - dt mu on the box of the states given ([2][nx][nx] each, or rows [u plane | v plane])"""
+    U = max(float(np.abs(np.asarray(s).reshape(-1, 2, app.nx ** 2)[:, 0]).max()) for s in states)
+    V = max(float(np.abs(np.asarray(s).reshape(-1, 2, app.nx ** 2)[:, 1]).max()) for s in states)
+    m = 1.0 - dt * mu(app.a, app.b, U, V)
+    assert m > 0.0, ("outside the regime where the step has one solution", dt, U, V)
+    return m
+
+
+def e_g(app, dt, R, c_g):
+    """E_g of the module docstring: the rounding of one value of the step's own g"""
+    S = 2.0 * R + dt * (8.0 * max(app.du, app.dv) * R / app.dx ** 2 + R ** 3 + max(abs(app.a) * (1.0 + R), abs(app.b) * R))
+    return c_g * EPS * S
+
+
+def tau(app, w, dt, x, y):
+    """the tolerance of the module docstring between x and y for the input w"""
+    fx, fy = (norm2(residual(s, w, dt, app.nx, par_of(app))) for s in (x, y))
+    return (fx + fy) / margin(app, dt, x, y, w) + EPS * float(np.linalg.norm(x))
+
+
+def exit_criterion(app, w, dt, x, c_g):
+    """(max|F(x)| in long double, newton_tol + E_g)"""
+    g = float(np.abs(residual(x, w, dt, app.nx, par_of(app))).max())
+    return g, app.newton_tol + e_g(app, dt, float(max(np.abs(x).max(), np.abs(w).max())), c_g)
+
+
+def history_allowance(ref_mg, rconv, norm_u, tau_phi):
+    """|conv - reference conv| per iteration k (from 0): 1e-10 reference + 64 EPS norm(u), the project's rule for two exact steppers
+    (tests/cases.py), + (k + 1) sqrt(points) tau_phi for two steppers that each stop at their own Newton test: a point's residual holds
+    one Phi, which differs by at most tau_phi, and the deviation of the states it is formed from grows by at most as much per iteration
+    where the iteration contracts (it converges: asserted by the callers)"""
+    n_pts = len(ref_mg.t[0])
+    return 1e-10 * rconv + cases.BLK_K * EPS * norm_u + (np.arange(len(rconv)) + 1.0) * np.sqrt(n_pts) * tau_phi
+
+
+def tau_phi_a_priori(app, dt, ref_apps, c_g):
+    """tau with the residuals replaced by what each side guarantees: the step under test max|g| < newton_tol + E_g on 2 nx^2 values,
+    the reference its recorded long-double residual; the box from the reference's record, widened by 5 % (u) and 10 % (v)"""
+    U, V = 1.05 * max(r.box[0] for r in ref_apps), 1.1 * max(r.box[1] for r in ref_apps)
+    m = 1.0 - dt * mu(app.a, app.b, U, V)
+    assert m > 0.0, (dt, U, V)
+    res = np.sqrt(2.0) * app.nx * (app.newton_tol + e_g(app, dt, max(U, V), c_g)) + max(r.worst_residual for r in ref_apps)
+    return res / m + EPS * max(r.worst_norm for r in ref_apps)

@@ -28,6 +28,12 @@ of b can amount to, and it bounds norm_F(b) and norm_F(x).
 ``ReferenceHeat2D`` overrides ``step`` with this Phi and describes no device stepper, which sends a hierarchy to the plugin path:
 ``Mgrit([ReferenceHeat2D(..) ..])`` is then the reference for every sweep -- the driver's own operand orders applied to an independently
 computed Phi.
+
+The coefficients the tests choose (``coefficient``, ``make_app`` below), two per shape:
+  mild:  a such that 4 theta dt (fx + fy) = 8, i.e. theta dt lambda <= 8 for every mode: every mode keeps at least 1 / 9 of its weight,
+         so a wrong table entry or eigenvalue of ANY mode shows in the result;
+  stiff: the suite's own cases.H2D_A = 3.5 (dt lambda_max of order 1e4 at 66x67: only the low modes survive the step).
+Forward Euler: a such that 4 dt (fx + fy) = 0.9 (stable).
 """
 import functools
 
@@ -35,6 +41,7 @@ import numpy as np
 import scipy.sparse as sp
 from scipy.sparse.linalg import splu
 
+import cases
 from pymgrit_amd.heat.heat_2d import Heat2D, VectorHeat2D
 
 LD = np.longdouble
@@ -156,3 +163,21 @@ class ReferenceHeat2D(Heat2D):
 
     def device_stepper(self):
         return None
+
+
+# ---- the applications of the tests (module docstring) ------------------------------------------------------------------------------
+def coefficient(nx, ny, method, dt, which):
+    """the diffusion coefficient a of the docstring for a step of size dt"""
+    if which == "stiff":
+        return cases.H2D_A
+    per_a = 1.0 / (cases.H2D_X_END / (nx - 1)) ** 2 + 1.0 / (cases.H2D_Y_END / (ny - 1)) ** 2       # (fx + fy) / a
+    if method == "FE":
+        return 0.9 / (4.0 * dt * per_a)
+    return 8.0 / (4.0 * {"BE": 1.0, "CN": 0.5}[method] * dt * per_a)
+
+
+def make_app(nx, ny, t, method, a, forcing, with_bc, cls=None):
+    if forcing == "general":
+        assert with_bc
+        return cases.h2d_general_app(nx, ny, t, method, a, cls=cls)
+    return cases.h2d_app(nx, ny, t, method, with_bc, a, forcing=forcing == "separable", cls=cls)

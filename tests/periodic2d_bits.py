@@ -13,7 +13,8 @@ What the cases are chosen for -- the smallest shapes at which the tile product o
   nx = 4 (one tile, KP = 32 > nx), 33 (K crosses one 32-step, pads inside the tile), 66 (two tiles per axis, P = 128, the last tile
   mostly pad), Gray-Scott also 97 (KP = P); Newton-PCG (IMPL and CN) also nx = 20 with nu = 4; Gray-Scott Newton-BiCGStab nx = 4, 33;
   Navier-Stokes at nx = 33 also with a forcing plane on every level;
-  every kind with the application parameters, the ragged time grid and the ranges of the random states of its own test_hip_<kind>.py;
+  every kind with the application parameters, the ragged time grid and the ranges of the random states of its entry in the kinds
+  table (tests/periodic2d_kinds.py), which its own test_hip_<kind>.py takes them from as well -- no test module is imported here;
   points (17, 9, 5) on a ragged time grid (several D tables per level, a plan grouped by step size), weight_c = 1.3;
   f_relax, c_relax, fas_residual per level, forward_solve on the coarsest level (batches of one on the chain's work buffers, or the
   Newton chain rows), compute_residual, and one solve of two iterations with the jump criterion (h2d_rowsq_kernel with H2D_OP_JUMP);
@@ -27,14 +28,9 @@ import zlib
 import numpy as np
 
 import cases
-import test_hip_burgers as bg
-import test_hip_cahn_hilliard as ch
-import test_hip_ginzburg_landau as gl
-import test_hip_gray_scott_newton as gsn
-import test_hip_navier_stokes as ns
-from test_hip_allen_cahn import _lists
-from test_hip_allen_cahn_newton import H, RAGGED_GRIDS
-from test_hip_gray_scott import _ragged
+from navier_stokes_reference import kolmogorov
+from periodic2d_kinds import GSN_RAGGED, KINDS, TWO_SIZES, dyadic
+from periodic2d_sweeps import draw, lists as _lists
 
 GOLDEN_FILE = os.path.join(cases.GOLDEN, "periodic2d_bits.json")
 WEIGHT_C = 1.3
@@ -43,36 +39,32 @@ ALL_SWEEPS = ("f_relax", "c_relax", "fas_residual", "forward_solve", "compute_re
 
 
 def _make_cases():
+    """every case from the kinds table (periodic2d_kinds.py): the kind's parameters, its ragged grid by2_3lvl, its dyadic step"""
     out = {}
-    ragged = RAGGED_GRIDS["by2_3lvl"]
+
+    def case(name, kind, nx, par=None, grids=None, sweeps=ALL_SWEEPS, **more):
+        out[name] = dict(app=kind, nx=nx, par=KINDS[kind].par(nx) if par is None else par,
+                         grids=KINDS[kind].ragged(nx)["by2_3lvl"] if grids is None else grids, sweeps=sweeps, **more)
     for nx in (4, 33, 66):
-        out[f"allencahn_imex_nx{nx}"] = dict(app="allencahn", nx=nx, par=dict(nu=2, method="IMEX"), grids=ragged, sweeps=ALL_SWEEPS)
+        case(f"allencahn_imex_nx{nx}", "allencahn", nx)
     for nx in (4, 33, 66, 97):
-        out[f"grayscott_imex_nx{nx}"] = dict(app="grayscott", nx=nx, par=dict(method="IMEX"), grids=_ragged(nx, "by2_3lvl"), sweeps=ALL_SWEEPS)
+        case(f"grayscott_imex_nx{nx}", "grayscott", nx)
     for method in ("IMPL", "CN"):
         for nx, nu in ((4, 2), (33, 2), (66, 2), (20, 4)):
-            out[f"allencahn_{method.lower()}_nx{nx}_nu{nu}"] = dict(app="allencahn", nx=nx, par=dict(nu=nu, method=method, linear_solver="pcg"),
-                                                                   grids=ragged, sweeps=ALL_SWEEPS)
-    for nx in (4, 33, 66):      # the IMEX kinds that came after, each as its own test builds it
-        out[f"cahnhilliard_imex_nx{nx}"] = dict(app="cahnhilliard", nx=nx, par=dict(L=nx / 16.0, eps=0.1, stab=2.0), grids=ch.RAGGED_GRIDS["by2_3lvl"], sweeps=ALL_SWEEPS)
-        out[f"burgers_imex_nx{nx}"] = dict(app="burgers", nx=nx, par=dict(nu=bg.NU, L=nx / 16), grids=bg._ragged("by2_3lvl"), sweeps=ALL_SWEEPS)
-        out[f"navierstokes_imex_nx{nx}"] = dict(app="navierstokes", nx=nx, par=dict(nu=ns.NU, L=nx / 16), grids=ns._ragged("by2_3lvl"), sweeps=ALL_SWEEPS)
-        out[f"ginzburglandau_imex_nx{nx}"] = dict(app="ginzburglandau", nx=nx, par=dict(b=gl.B, c=gl.CC, L=float(nx)), grids=gl._ragged("by2_3lvl"),
-                                                  sweeps=ALL_SWEEPS)
-    out["navierstokes_imex_nx33_forcing"] = dict(app="navierstokes", nx=33, par=dict(nu=ns.NU, L=33 / 16, forcing=ns.kolmogorov(33)),
-                                                 grids=ns._ragged("by2_3lvl"), sweeps=ALL_SWEEPS)
+            case(f"allencahn_{method.lower()}_nx{nx}_nu{nu}", "allencahn", nx, par=dict(nu=nu, method=method, **KINDS["allencahn"].newton))
+    for nx in (4, 33, 66):      # the IMEX kinds that came after
+        for kind in ("cahnhilliard", "burgers", "navierstokes", "ginzburglandau"):
+            case(f"{kind}_imex_nx{nx}", kind, nx)
+    case("navierstokes_imex_nx33_forcing", "navierstokes", 33, par=dict(KINDS["navierstokes"].par(33), forcing=kolmogorov(33)))
     for nx in (4, 33):
-        out[f"grayscott_impl_nx{nx}"] = dict(app="grayscott", nx=nx, par=dict(method="IMPL", linear_solver="bicgstab"),
-                                             grids=gsn.RAGGED_GRIDS["by2_3lvl"], sweeps=ALL_SWEEPS)
-    # more than one batch per sweep, the grids of the test_sweeps_of_more_than_one_batch tests
-    two_sizes = np.concatenate((H * np.arange(2051.0), H * np.array([2052.0, 2054.0])))      # dt groups of 1025 and 1 items
-    dyadic = 2.0 ** -7 * np.arange(1027.0)                                                   # one dt group of 513 states
-    out["grayscott_imex_nx4_batches"] = dict(app="grayscott", nx=4, par=dict(method="IMEX"), grids=[dyadic, dyadic[::2]],
-                                             sweeps=STORED_STATE_SWEEPS, levels=[0])
-    out["allencahn_imex_nx4_batches"] = dict(app="allencahn", nx=4, par=dict(nu=2, method="IMEX"), grids=[two_sizes, two_sizes[::2]],
-                                             sweeps=STORED_STATE_SWEEPS, levels=[0])
-    out["allencahn_impl_nx4_batches"] = dict(app="allencahn", nx=4, par=dict(nu=2, method="IMPL", linear_solver="pcg"),
-                                             grids=[two_sizes, two_sizes[::2]], sweeps=STORED_STATE_SWEEPS, levels=[0])
+        case(f"grayscott_impl_nx{nx}", "grayscott", nx, par=dict(KINDS["grayscott"].newton), grids=GSN_RAGGED["by2_3lvl"])
+    # more than one batch per sweep, the grids of the test_sweeps_of_more_than_one_batch tests: for Gray-Scott one dt group of 513
+    # states, for Allen-Cahn dt groups of 1025 and 1 items
+    batches = dict(sweeps=STORED_STATE_SWEEPS, levels=[0])
+    case("grayscott_imex_nx4_batches", "grayscott", 4, grids=dyadic("grayscott", 1027), **batches)
+    case("allencahn_imex_nx4_batches", "allencahn", 4, grids=[TWO_SIZES, TWO_SIZES[::2]], **batches)
+    case("allencahn_impl_nx4_batches", "allencahn", 4, par=dict(nu=2, method="IMPL", **KINDS["allencahn"].newton), grids=[TWO_SIZES, TWO_SIZES[::2]],
+         **batches)
     return out
 
 
@@ -86,8 +78,7 @@ def _sha(a, dtype=np.float64):
 def _hierarchy(spec, **opts):
     import pymgrit_amd
     from pymgrit_amd import Mgrit
-    app = getattr(pymgrit_amd, {"allencahn": "AllenCahn", "grayscott": "GrayScott", "cahnhilliard": "CahnHilliard", "burgers": "Burgers2D",
-                                "navierstokes": "NavierStokes2D", "ginzburglandau": "GinzburgLandau2D"}[spec["app"]])
+    app = getattr(pymgrit_amd, KINDS[spec["app"]].cls)
     mg = Mgrit([app(nx=spec["nx"], t_interval=np.asarray(t), **spec["par"]) for t in spec["grids"]], nested_iteration=False, logging_lvl=30, **opts)
     assert type(mg.backend).__name__ == "HipBackend"
     return mg
@@ -101,18 +92,13 @@ def run_case(name):
     inputs = hashlib.sha256()
     for t in mg.t:
         inputs.update(np.ascontiguousarray(t, dtype=np.float64).tobytes())
-    top, n, digests = mg.lvl_max - 1, spec["nx"] ** 2, {}
+    top, digests = mg.lvl_max - 1, {}
     newton = "linear_solver" in spec["par"]
 
     def fresh():
         for lvl in range(mg.lvl_max):
             for which, lst in _lists(mg, lvl):
-                if spec["app"] == "grayscott":      # [u plane | v plane], u in [0, 1], v in [0, 0.5]; Newton: g small and signed
-                    hi = (0.01, 0.005) if newton and which == "g" else (1.0, 0.5)
-                    lo = (-0.01, -0.005) if newton and which == "g" else (0.0, 0.0)
-                    val = np.concatenate([rng.uniform(lo[c], hi[c], size=(len(lst), n)) for c in range(2)], axis=1)
-                else:                               # one plane, or [plane | plane] of Burgers and Ginzburg-Landau
-                    val = rng.uniform(-1.0, 1.0, size=(len(lst), n * (2 if spec["app"] in ("burgers", "ginzburglandau") else 1)))
+                val = draw(spec["app"], rng, which, len(lst), spec["nx"], newton)      # the kind's ranges (periodic2d_kinds.py)
                 inputs.update(val.tobytes())
                 mg.backend.set_natural(which, lvl, val)
 

@@ -57,7 +57,7 @@ def test_config5_scale_sweeps_bit_exact(oracle):
     """config 5 spatial sizes (8192 -> 4096 -> 2048 periodic points), short time grid, every sweep vs the oracle"""
     import torch
     assert torch.cuda.is_available()
-    from test_hip_parity import assert_state_equal, randomize
+    from parity_cases import assert_state_equal, randomize
     from pymgrit_amd import Advection1D, GridTransferAdvection, Mgrit
     t0 = np.linspace(0, 2.0 * 32 / 32768, 33)
     ts, nxs = [t0, t0[::2], t0[::4]], [8193, 4097, 2049]

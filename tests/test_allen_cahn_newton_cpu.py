@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import cases
-from test_allen_cahn_cpu import ARR as ARR_OLD, EPS, META as META_OLD, apply_step, check_history
+from allen_cahn_fixtures import ARR as ARR_OLD, EPS, META as META_OLD, apply_step, check_history
 
 META = cases.load_json("allen_cahn_newton.json")
 ARR = np.load(cases.GOLDEN + "/allen_cahn_newton.npz")
@@ -54,9 +54,8 @@ def test_the_fixtures_meet_the_rule():
 
 
 @pytest.mark.parametrize("name", sorted(SOLVES))
-def test_pcg_plugin_path_solves_match_the_reference_histories(name, caplog, monkeypatch):
+def test_pcg_plugin_path_solves_match_the_reference_histories(name, caplog):
     from pymgrit_amd import AllenCahn, Mgrit
-    import test_allen_cahn_cpu
 
     class HostAllenCahn(AllenCahn):
         def step(self, u_start, t_start, t_stop):
@@ -70,9 +69,7 @@ def test_pcg_plugin_path_solves_match_the_reference_histories(name, caplog, monk
     assert type(mg.backend).__name__ == "PluginBackend"
     conv = mg.solve()["conv"]
     u = np.array([np.asarray(v.get_values()) for v in mg.u[0]])
-    # check_history reads the reference history by name from test_allen_cahn_cpu.META["solve"]: the new records are shown to it there
-    monkeypatch.setitem(test_allen_cahn_cpu.META["solve"], name, rec)
-    check_history(name, conv, cases.spacetime_norm(u))
+    check_history(name, conv, cases.spacetime_norm(u), ref=rec["conv"])
     last = arr["last_" + name]
     assert np.abs(u[-1] - last).max() <= 1e-9 * np.abs(last).max()
 

@@ -5,29 +5,12 @@ import numpy as np
 import pytest
 
 import cases
+from dist_cases import AT_CASES as CASES, at_heat as heat, launch
 from mock_comm import run_ranks
-from pymgrit_amd import AtMgrit, Dahlquist, Heat1D, simple_setup_problem
+from parity_cases import assert_state_equal, randomize
+from pymgrit_amd import AtMgrit, Dahlquist, simple_setup_problem
 
 GOLD = cases.load_json("at_mgrit.json")
-
-CASES = {   # name -> (nx, nts, k, options)
-    "heat_nx33_k1": (33, [65, 17, 5], 1, dict(tol=1e-9, max_iter=8)),
-    "heat_nx33_k2": (33, [65, 17, 5], 2, dict(tol=1e-9, max_iter=8)),
-    "heat_nx33_k3": (33, [65, 17, 5], 3, dict(tol=1e-9, max_iter=8)),
-    "heat_nx33_k5": (33, [65, 17, 5], 5, dict(tol=1e-9, max_iter=8)),
-    "heat_nx33_k3_nonested_F": (33, [129, 33, 9], 3, dict(tol=1e-9, max_iter=8, nested_iteration=False, cycle_type='F')),
-    "heat_nx33_2lvl_k4_w13": (33, [65, 17], 4, dict(tol=1e-9, max_iter=8, weight_c=1.3)),
-    "heat_nx33_k2_jump": (33, [65, 17, 5], 2, dict(tol=1e-9, max_iter=8, conv_crit=1)),
-}
-
-
-def heat(nx, nts, host_only, x_end=1.0):
-    prob = [Heat1D(x_start=0, x_end=x_end, nx=nx, a=1, init_cond=cases.init_cond,
-                   rhs_separable=[(cases.rhs_space, cases.rhs_time)], t_start=0, t_stop=2, nt=nt) for nt in nts]
-    if host_only:
-        for p in prob:
-            p.device_stepper = lambda: None
-    return prob
 
 
 def check(mg, g):
@@ -145,7 +128,6 @@ def test_hip_truncated_solve_is_bit_exact_on_wide_states(oracle):
     torch = pytest.importorskip("torch")
     if not torch.cuda.is_available():
         pytest.fail("GPU test selected but no GPU visible")
-    from test_hip_parity import assert_state_equal, randomize
     for nx, k in ((2050, 3), (5000, 7)):
         grids = [cases.lin(2, 33), cases.lin(2, 17)]
         mg = AtMgrit(problem=heat(nx, [33, 17], False), k=k, logging_lvl=30, nested_iteration=False)
@@ -165,7 +147,6 @@ def test_hip_several_ranks_equal_one_rank(name, world):
     torch = pytest.importorskip("torch")
     if not torch.cuda.is_available():
         pytest.fail("GPU test selected but no GPU visible")
-    from test_distributed import launch
     conv1, u1 = launch(1, "at:" + name, mode="hip")
     conv, u = launch(world, "at:" + name, mode="hip", backend="gloo")
     assert np.array_equal(conv, conv1), (conv, conv1)
@@ -174,7 +155,6 @@ def test_hip_several_ranks_equal_one_rank(name, world):
 
 @pytest.mark.parametrize("name,world", [("heat_nx33_k3", 3), ("heat_nx33_k2_jump", 2)])
 def test_several_processes_equal_one_on_the_host_path(name, world):
-    from test_distributed import launch
     conv1, u1 = launch(1, "at:" + name)
     conv, u = launch(world, "at:" + name)
     assert np.array_equal(conv, conv1) and np.array_equal(u, u1)
@@ -190,7 +170,6 @@ def test_hip_truncated_solve_on_every_device_stepper(oracle, what):
     if not torch.cuda.is_available():
         pytest.fail("GPU test selected but no GPU visible")
     from pymgrit_amd import Advection1D
-    from test_hip_parity import assert_state_equal, randomize
     for k in (1, 3, 6):
         if what.startswith("heat2d"):
             prob = [cases.h2d_app(19, 23, t, what[-2:], True, cases.H2D_A) for t in cases.h2d_grids([33, 9])]

@@ -2,45 +2,16 @@
 (tests/cahn_hilliard_reference.py: sparse LU start, iterative refinement in long double, its own forward error bound asserted), the
 constructor, the device description, the package exports, the grid transfer, and the properties of the scheme (mass, energy, fixed points).
 
-Tolerance of one Phi in the Hartley form, nothing measured on the code under test. EPS = 2^-52; a rounding is at most EPS / 2 relative.
-  * products: a product with an orthogonal n x n matrix is off by at most n EPS times the operand's 2-norm (the rule of
-    test_allen_cahn_cpu.py). T u T and T w T: 2 nx EPS (norm_F(u) + d2max norm_F(w)) once scaled by |D1| <= 1, |D2| <= d2max; the two
-    products back act on z = (T u T) o D1 + (T w T) o D2, norm_F(z) <= norm_F(u) + d2max norm_F(w): 2 nx EPS of that. Together
-    4 nx EPS bnorm, bnorm = norm_F(u) + d2max norm_F(|u|^3 + (1 + s) |u|), d2max = max over the modes of dt mu / (1 + dt (eps^2 mu^2 + s mu)).
-  * pointwise map w = (u u) u - c1 u: four roundings on terms bounded by |u|^3 + (1 + s) |u|, and c1 = 1 + s rounded: 2.5 EPS.
-  * tables. lam_k = (4 / dx^2) sin^2(pi k / nx): argument, sine, square and scale give at most 4 EPS where the mode matters (for k beyond
-    nx / 2 the sine's relative error grows like the argument's cotangent, but those modes mirror k' = nx - k and the D tables depend on
-    them through dt (eps^2 mu^2 + s mu) / (1 + ..), which is small where lam is); mu: 4.5; eps^2 mu mu: 10.5; the sum with s mu, the
-    product with dt, 1 +, the reciprocal: D1 to 12.5 EPS. D2 = -(dt mu) D1: 4.5 + 12.5 + 1 = 18 EPS. The device tables are formed from
-    long-double eigenvalues and are closer; both stay inside.
-  * the two table multiplications and the addition: 0.5 EPS each.
-  Sum: 4 nx + 2.5 + 12.5 + 18 + 1.5 = 4 nx + 34.5; C(nx) = 4 nx + 36.
-  * reference_phi: EPS bnorm (its asserted forward error bound, rounding to float64 included).
+The tolerance of one Phi in the Hartley form, C(nx) EPS bnorm with C(nx) = 4 nx + 36, is derived in tests/cahn_hilliard_reference.py beside
+the functions that evaluate it (c_of, d2max, b_norm); reference_phi gets EPS bnorm, its asserted forward error bound.
 """
 import numpy as np
 import pytest
 
 import cases
+from cahn_hilliard_reference import b_norm, c_of
 
 EPS = cases.EPS
-
-
-def c_of(nx):
-    """C(nx) of the module docstring"""
-    return 4 * nx + 36
-
-
-def d2max(app, dt):
-    """max over the modes of dt mu / (1 + dt (eps^2 mu^2 + s mu)), the eigenvalues from their definition"""
-    lam = (4.0 / app.dx ** 2) * np.sin(np.pi * np.arange(app.nx) / app.nx) ** 2
-    mu = lam[:, None] + lam[None, :]
-    return float(np.max(dt * mu / (1.0 + dt * (app.eps ** 2 * mu * mu + app.stab * mu))))
-
-
-def b_norm(app, rows, dt):
-    """bnorm of the module docstring for the inputs among rows (one state per row), the largest"""
-    rows = np.abs(np.atleast_2d(rows))
-    return float(np.max(np.linalg.norm(rows, axis=1) + d2max(app, dt) * np.linalg.norm(rows ** 3 + (1.0 + app.stab) * rows, axis=1)))
 
 
 def apply_step(app, u, dt):

@@ -2,85 +2,10 @@
 exchange schedule as the multi-GPU runs, on the plugin path. The reference is bit-identical for every P with uniform
 coarsening; so must we be: residual history and every solution vector equal the single-rank run
 bit for bit. The HIP twin of this test (two ranks sharing one GPU, gloo transport) lives in test_hip_distributed.py."""
-import os
-import socket
-import subprocess
-import sys
-import tempfile
-
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
-_ONE_RANK = {}     # results of one-rank launches, the baseline several tests compare their sharded runs with
-
-
-def launch(world, case, mode="plugin", backend="gloo", timeout=600, depth=None, slow_rank=None, no_groups_rank=None,
-           per_rank=False):
-    # a one-rank run is a pure function of (case, mode, lag, the library's / package's environment switches): computed once per
-    # session (every launch is a fresh process: a second or two of start-up each on the GPU box)
-    memo = None
-    if world == 1 and slow_rank is None and no_groups_rank is None:
-        memo = (case, mode, depth, per_rank, tuple(sorted((k, v) for k, v in os.environ.items() if k.startswith(("MGRIT_", "PYMGRIT_")))))
-        if memo in _ONE_RANK:
-            return _ONE_RANK[memo]
-    res = _launch(world, case, mode, backend, timeout, depth, slow_rank, no_groups_rank, per_rank)
-    if memo is not None:
-        _ONE_RANK[memo] = res
-    return res
-
-
-def _launch(world, case, mode, backend, timeout, depth, slow_rank, no_groups_rank, per_rank):
-    out = tempfile.mkdtemp(prefix=f"mgrit_{case}_{world}_")
-    port = free_port()
-    env = dict(os.environ)
-    env.pop("MGRIT_TEST_PIPELINE_DEPTH", None)
-    env.pop("MGRIT_TEST_SLOW_RANK", None)
-    if depth is not None:
-        env["MGRIT_TEST_PIPELINE_DEPTH"] = str(depth)
-    if slow_rank is not None:
-        env["MGRIT_TEST_SLOW_RANK"] = str(slow_rank)
-    env.pop("PYMGRIT_AMD_NO_EXTRA_GROUPS", None)
-    if no_groups_rank is not None:
-        env["PYMGRIT_AMD_NO_EXTRA_GROUPS"] = "1"
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "dist_worker.py"), str(r), str(world), str(port), case,
-                               mode, out, backend], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=env)
-             for r in range(world)]
-    logs = []
-    try:
-        for p in procs:
-            o, _ = p.communicate(timeout=timeout)
-            logs.append(o.decode(errors="replace"))
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    bad = [r for r, p in enumerate(procs) if p.returncode != 0]
-    if bad:
-        # a rank that only saw its peer disappear is an echo of the real failure: show the root cause first
-        root = [r for r in bad if "Connection closed by peer" not in logs[r]] or bad
-        raise AssertionError(f"ranks {bad} failed; rank {root[0]}:\n{logs[root[0]][-3000:]}")
-    res = [np.load(os.path.join(out, f"rank{r}.npz")) for r in range(world)]
-    if per_rank:     # local criteria: every rank has its own residual history
-        return [(r["conv"], r["u"]) for r in res]
-    conv = res[0]["conv"]
-    for r in res[1:]:
-        assert np.array_equal(r["conv"], conv), "every rank must hold the same residual history"
-    t = np.concatenate([r["t"] for r in res])
-    u = np.concatenate([r["u"] for r in res if r["u"].size], axis=0)
-    assert np.all(np.diff(t) > 0), "owned blocks must tile the time grid in rank order"
-    return conv, u
-
+from dist_cases import launch
 
 CASES = [
     ("dahlquist_config1", [2, 3]),              # nt=101, m=2: aligned and unaligned splits

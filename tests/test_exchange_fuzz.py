@@ -12,6 +12,7 @@ import os
 import numpy as np
 import pytest
 
+import cases
 from fuzz_cases import N_CASES, SEED0, random_case
 from mock_comm import run_ranks
 from pymgrit_amd import Dahlquist, Mgrit
@@ -22,15 +23,6 @@ with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ex
 
 def make(grids):
     return [Dahlquist(t_interval=np.asarray(g)) for g in grids]
-
-
-def uniform(grids):
-    """every level is every m-th point of the finer one (mgrit.py:116-129 warns otherwise)"""
-    for fine, coarse in zip(grids, grids[1:]):
-        m = (len(fine) - 1) // max(len(coarse) - 1, 1)
-        if (len(fine) - 1) % max(len(coarse) - 1, 1) or not np.array_equal(fine[::m], coarse):
-            return False
-    return True
 
 
 @pytest.mark.parametrize("seed", range(N_CASES))
@@ -57,7 +49,7 @@ def test_sharded_equals_the_reference_at_the_same_rank_count(seed):
         assert len(conv) == len(want["conv"]) and np.allclose(conv, want["conv"], rtol=1e-14, atol=0), \
             (tag, rank, conv, want["conv"])
         assert np.array_equal(np.array(vals), np.array(want["u"])), (tag, rank)
-    if opts["conv_crit"] in (0, 1) and uniform(grids):
+    if opts["conv_crit"] in (0, 1) and cases.uniform_coarsening(grids):
         one = Mgrit(make(grids), logging_lvl=30, **opts)
         assert np.array_equal(one.solve()["conv"], res[0][0]), tag
         u1 = np.array([float(one.u[0][i].get_values()) for i in range(len(grids[0]))])

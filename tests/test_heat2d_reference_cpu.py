@@ -25,7 +25,7 @@ import numpy as np
 import pytest
 
 import cases
-from heat2d_reference import ReferenceHeat2D, babs_norm, phi_bound, reference_phi
+from heat2d_reference import ReferenceHeat2D, babs_norm, coefficient, make_app, phi_bound, reference_phi
 
 SHAPES = [(3, 3), (4, 3), (20, 17), (66, 67), (129, 130), (131, 132), (5, 200), (200, 5), (259, 258)]
 FE_SHAPES = [(4, 3), (20, 17), (66, 67)]
@@ -36,23 +36,6 @@ PERTURBATION = 1e-10
 
 def _ids(shapes):
     return [f"{nx}x{ny}" for nx, ny in shapes]
-
-
-def coefficient(nx, ny, method, dt, which):
-    """the diffusion coefficient a of the docstring for a step of size dt"""
-    if which == "stiff":
-        return cases.H2D_A
-    per_a = 1.0 / (cases.H2D_X_END / (nx - 1)) ** 2 + 1.0 / (cases.H2D_Y_END / (ny - 1)) ** 2       # (fx + fy) / a
-    if method == "FE":
-        return 0.9 / (4.0 * dt * per_a)
-    return 8.0 / (4.0 * {"BE": 1.0, "CN": 0.5}[method] * dt * per_a)
-
-
-def make_app(nx, ny, t, method, a, forcing, with_bc, cls=None):
-    if forcing == "general":
-        assert with_bc
-        return cases.h2d_general_app(nx, ny, t, method, a, cls=cls)
-    return cases.h2d_app(nx, ny, t, method, with_bc, a, forcing=forcing == "separable", cls=cls)
 
 
 @functools.lru_cache(maxsize=None)

@@ -3,7 +3,7 @@ the plugin path (the host ``step``), single steps against the reference fixtures
 reference's residual histories. The oracle has no Allen-Cahn variant, so nothing here is bit for bit against another implementation:
 the host step of this file is the same formula as the device's. The second implementation the device path is held against is the
 transform-free long-double solve of tests/allen_cahn_reference.py, in tests/test_hip_allen_cahn_reference.py (size edges, other
-exponents, several step sizes per level, sweeps of more than one batch). The bounds are derived (test_allen_cahn_cpu.py states them):
+exponents, several step sizes per level, sweeps of more than one batch). The bounds are derived (allen_cahn_fixtures.py states them):
 
   per Phi, one evaluation:                 norm_F(error) <= (4 nx + 8) eps norm_F(b)
   two independent evaluations (host, device):   twice that                                                          = TOL
@@ -20,53 +20,21 @@ import numpy as np
 import pytest
 
 import cases
-from periodic2d_sweeps import compare as _compare, host_state as _host_state, lists as _lists, row_norm as _row_norm, set_states as _set_states
-from test_allen_cahn_cpu import ARR, EPS, META, check_history, ours_bound, reference_bound, step_input
+from allen_cahn_fixtures import ARR, EPS, META, check_history, ours_bound, reference_bound, step_input
+from periodic2d_kinds import KINDS
+from periodic2d_sweeps import (ALL_SWEEPS, bounds_of, chain, check_every_sweep_twice, compare as _compare, host_class, host_state as _host_state, pair,
+                               random_states, row_norm as _row_norm, run_sweeps, set_states as _set_states, uniform as _uniform)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-T_SWEEP = 0.002     # sweeps: nt = 17 / 9 / 5 on [0, T_SWEEP], coarsening factor 2 -- every Phi of a relaxation acts on a stored state
-
-
-def _host_class():
-    from pymgrit_amd import AllenCahn
-
-    class HostAllenCahn(AllenCahn):     # overriding step sends the hierarchy to the plugin path
-        def step(self, u_start, t_start, t_stop):
-            return super().step(u_start, t_start, t_stop)
-    return HostAllenCahn
+# sweeps: nt = 17 / 9 / 5 on [0, T_SWEEP], coarsening factor 2 -- every Phi of a relaxation acts on a stored state
+T_SWEEP = KINDS["allencahn"].t_sweep(None)
+BOUNDS = bounds_of("allencahn", "host")     # TOL of the module docstring: 2 (4 nx + 8) EPS bnorm with the level's largest c
 
 
 def _pair(nx, nts, t_stop, nu=2, **opts):
-    from pymgrit_amd import AllenCahn, Mgrit
-    opts.setdefault("nested_iteration", False)
-    dev = Mgrit([AllenCahn(nx=nx, nu=nu, method="IMEX", t_start=0, t_stop=t_stop, nt=nt) for nt in nts], logging_lvl=30, **opts)
-    host = Mgrit([_host_class()(nx=nx, nu=nu, method="IMEX", t_start=0, t_stop=t_stop, nt=nt) for nt in nts], logging_lvl=30, **opts)
-    assert type(dev.backend).__name__ == "HipBackend" and type(host.backend).__name__ == "PluginBackend"
-    return dev, host
-
-
-def _random_states(host, seed, zero_g=False):
-    rng = np.random.default_rng(seed)
-    out = {}
-    for lvl in range(host.lvl_max):
-        for name, lst in _lists(host, lvl):
-            n = host.problem[lvl].nx ** 2
-            out[(name, lvl)] = np.zeros((len(lst), n)) if (zero_g and name == "g") else rng.uniform(-1.0, 1.0, size=(len(lst), n))
-    return out
-
-
-def _b_norm(app, rows, c):
-    rows = np.abs(np.atleast_2d(rows))
-    return float(np.max(np.linalg.norm(rows + c * np.abs(rows * (1.0 - rows ** app.nu)), axis=1)))
-
-
-def _tol(host, lvl, rows):
-    """TOL of the level for inputs among rows"""
-    app = host.problem[lvl]
-    c = float(np.max(np.diff(host.t[lvl]))) / app.eps ** 2
-    return 2 * (4 * app.nx + 8) * EPS * _b_norm(app, rows, c)
+    return pair("allencahn", nx, _uniform(nts, t_stop), par=dict(nu=nu), **opts)
 
 
 SIZES = [9, 20, 63, 64, 66, 130, 200]
@@ -75,52 +43,9 @@ SIZES = [9, 20, 63, 64, 66, 130, 200]
 @pytest.mark.parametrize("nx", SIZES)
 def test_every_sweep_matches_the_plugin_path(nx):
     assert torch.cuda.is_available()
-    nts = (17, 9, 5)
     for w in (1.0, 1.3):
-        dev, host = _pair(nx, nts, T_SWEEP, weight_c=w)
-        top = dev.lvl_max - 1
-        seed = 100 * nx
-
-        def fresh():
-            nonlocal seed
-            seed += 1
-            st = _random_states(host, seed)
-            _set_states(dev, host, st)
-            return st
-
-        for lvl in range(top):
-            st = fresh()
-            slack = 8 * EPS * 3 * _row_norm(*st.values())
-            dev.f_relax(lvl); host.f_relax(lvl)
-            _compare(dev, host, lvl, _tol(host, lvl, st[("u", lvl)]) + slack, "f_relax")
-            st = fresh()
-            dev.c_relax(lvl); host.c_relax(lvl)
-            _compare(dev, host, lvl, max(1.0, w) * _tol(host, lvl, st[("u", lvl)]) + slack * (abs(w) + abs(1 - w)), f"c_relax w={w}")
-            st = fresh()
-            dev.fas_residual(lvl); host.fas_residual(lvl)
-            # g of the coarse level: one Phi of the fine level, one of the coarse level on restricted (= copied) rows of the fine u
-            _compare(dev, host, lvl + 1, _tol(host, lvl, st[("u", lvl)]) + _tol(host, lvl + 1, st[("u", lvl)]) + slack, "fas_residual")
-        # forward solve on the coarsest level: the chained bound
-        st = fresh()
-        dev.forward_solve(top); host.forward_solve(top)
-        app, t = host.problem[top], host.t[top]
-        uh = _host_state(host, "u", top)
-        e = 0.0
-        for k in range(1, len(t)):
-            c = (t[k] - t[k - 1]) / app.eps ** 2
-            R = float(np.abs(uh[k - 1]).max())
-            lip = max(abs(1 + c), abs(1 + c * (1 - (app.nu + 1) * R ** app.nu)))
-            e = lip * e + 2 * (4 * nx + 8) * EPS * _b_norm(app, uh[k - 1], c) + 8 * EPS * 3 * _row_norm(uh, st[("g", top)])
-        _compare(dev, host, top, e, "forward_solve")
-        for lvl in range(top - 1, -1, -1):
-            st = fresh()
-            dev.error_correction(lvl); host.error_correction(lvl)
-            _compare(dev, host, lvl, 8 * EPS * 3 * _row_norm(*st.values()), "error_correction")
-        st = fresh()
-        got, ref = np.asarray(dev.compute_residual()), np.asarray(host.compute_residual())
-        allowed = _tol(host, 0, st[("u", 0)]) + 8 * EPS * 3 * _row_norm(st[("u", 0)]) + (nx * nx + 2) * EPS * ref
-        print(f"residual norms: worst deviation {np.abs(got - ref).max():.3e}, allowed {allowed.min():.3e}")
-        assert got.shape == ref.shape and np.all(np.abs(got - ref) <= allowed), np.abs(got - ref).max()
+        dev, host = _pair(nx, (17, 9, 5), T_SWEEP, weight_c=w)
+        run_sweeps(dev, host, BOUNDS, w, 100 * nx + 1, ALL_SWEEPS)
 
 
 @pytest.mark.parametrize("nx", [20, 63, 130])
@@ -128,25 +53,7 @@ def test_a_sweep_run_twice_gives_the_same_bits(nx):
     """a race in the fused prologue / epilogues would show here, where a tolerance would hide it"""
     assert torch.cuda.is_available()
     dev, host = _pair(nx, (17, 9, 5), T_SWEEP, weight_c=1.3)
-    st = _random_states(host, nx)
-    top = dev.lvl_max - 1
-    sweeps = [("f_relax", lambda l=l: dev.f_relax(l)) for l in range(top)] + [("c_relax", lambda l=l: dev.c_relax(l)) for l in range(top)] + \
-             [("fas_residual", lambda l=l: dev.fas_residual(l)) for l in range(top)] + [("forward_solve", lambda: dev.forward_solve(top))]
-    for name, run in sweeps:
-        out = []
-        for rep in range(2):
-            for (which, lvl), val in st.items():
-                dev.backend.set_natural(which, lvl, val)
-            run()
-            out.append({key: dev.backend.natural(*key) for key in st})
-        for key in st:
-            assert np.array_equal(out[0][key], out[1][key]), (name, key)
-    res = []
-    for rep in range(2):
-        for (which, lvl), val in st.items():
-            dev.backend.set_natural(which, lvl, val)
-        res.append(np.asarray(dev.compute_residual()))
-    assert np.array_equal(res[0], res[1])
+    check_every_sweep_twice(dev, random_states("allencahn", host, nx), residual=True)
 
 
 @pytest.mark.parametrize("name", sorted(META["steps"]))
@@ -206,16 +113,11 @@ def test_long_coarsest_level_is_solved_step_by_step(monkeypatch):
         finally:
             options.reset("coarse_solve")
         assert dev.backend.block_r[1] == 0 and dev.backend.block_solve_form(1) == 0
-    st = _random_states(host, 7, zero_g=True)     # g = 0: plain time stepping, the states stay within [-1, 1]
+    st = random_states("allencahn", host, 7, zero_g=True)     # g = 0: plain time stepping, the states stay within [-1, 1]
     _set_states(dev, host, st)
     dev.forward_solve(1); host.forward_solve(1)
-    app, t, uh = host.problem[1], host.t[1], _host_state(host, "u", 1)
-    e = 0.0
-    for k in range(1, len(t)):
-        c = (t[k] - t[k - 1]) / app.eps ** 2
-        R = float(np.abs(uh[k - 1]).max())
-        lip = max(abs(1 + c), abs(1 + c * (1 - (app.nu + 1) * R ** app.nu)))
-        e = lip * e + 2 * (4 * nx + 8) * EPS * _b_norm(app, uh[k - 1], c) + 8 * EPS * 3 * _row_norm(uh)
+    uh = _host_state(host, "u", 1)
+    e = chain(BOUNDS, host, host.problem[1], host.t[1], uh, 8 * EPS * 3 * _row_norm(uh))
     _compare(dev, host, 1, e, "forward_solve, 64 steps")
     dev2, host2 = _pair(nx, nts, t_stop, max_iter=2, tol=0.0)
     conv, hconv = dev2.solve()["conv"], host2.solve()["conv"]
@@ -229,7 +131,7 @@ def test_output_fcn_and_cf_iter():
     seen = []
     prob = [AllenCahn(nx=20, method="IMEX", t_start=0, t_stop=META["t_stop"], nt=nt) for nt in (33, 9)]
     mg = Mgrit(prob, logging_lvl=30, cf_iter=2, max_iter=3, tol=0.0, output_fcn=lambda s: seen.append(float(s.u[0][-1].norm())))
-    hprob = [_host_class()(nx=20, method="IMEX", t_start=0, t_stop=META["t_stop"], nt=nt) for nt in (33, 9)]
+    hprob = [host_class(AllenCahn)(nx=20, method="IMEX", t_start=0, t_stop=META["t_stop"], nt=nt) for nt in (33, 9)]
     hseen = []
     hmg = Mgrit(hprob, logging_lvl=30, cf_iter=2, max_iter=3, tol=0.0, output_fcn=lambda s: hseen.append(float(s.u[0][-1].norm())))
     conv, hconv = mg.solve()["conv"], hmg.solve()["conv"]

@@ -25,21 +25,20 @@ Sweeps: SLACK = 8 EPS * 3 * the largest row norm involved for the sweep's own ar
 interval) e_k = Lip e_(k-1) + tau + SLACK, Lip = (1 + (1 - theta) / theta * fac / eps^2) / (1 - fac / eps^2), as test_hip_allen_cahn_reference.py
 does for IMEX. Every comparison covers all rows of a list. Each sweep prints its worst error / allowed ("RATIO" lines).
 """
-import collections
 import ctypes as C
-import logging
 import types
 
 import numpy as np
 import pytest
 
+import allen_cahn_fixtures
 import cases
-import test_allen_cahn_cpu
-from allen_cahn_newton_reference import ReferenceAllenCahnNewton, reference_phi, residual
-from periodic2d_sweeps import (ALL_SWEEPS, compare as _compare, intervals as _intervals, report as _report, row_norm as _row_norm, run_sweeps,
-                               set_states as _set_states, tol, uniform as _uniform)
-from test_allen_cahn_cpu import EPS, apply_step, check_history
-from test_hip_allen_cahn import T_SWEEP, _random_states
+from allen_cahn_fixtures import EPS, apply_step, check_history
+from allen_cahn_newton_reference import residual
+from periodic2d_kinds import KINDS, TWO_SIZES
+from periodic2d_sweeps import (ALL_SWEEPS, both_weights, check_one_phi, distinct_steps, dt_groups, host_class, intervals as _intervals, pair,
+                               compare as _compare, random_states, report as _report, row_norm as _row_norm, run_sweeps, set_states as _set_states, tol,
+                               uniform as _uniform)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -47,18 +46,17 @@ torch = pytest.importorskip("torch")
 META = cases.load_json("allen_cahn_newton.json")
 ARR = np.load(cases.GOLDEN + "/allen_cahn_newton.npz")
 THETA = {"IMPL": 1.0, "CN": 0.5}
+T_SWEEP = KINDS["allencahn"].t_sweep(None)
+RAGGED_GRIDS = KINDS["allencahn"].ragged(None)      # largest step 6e-4: fac / eps^2 <= 0.375
 
 
 def _pair(nx, grids, method, nu=2, app=None, **opts):
     """(device Mgrit, plugin Mgrit over ReferenceAllenCahnNewton) on the same hierarchy"""
-    from pymgrit_amd import AllenCahn, Mgrit
-    opts.setdefault("nested_iteration", False)
-    dev = Mgrit([AllenCahn(nx=nx, nu=nu, method=method, linear_solver="pcg", **(app or {}), **g) for g in grids], logging_lvl=30, **opts)
-    ref = Mgrit([ReferenceAllenCahnNewton(nx=nx, nu=nu, method=method, **g) for g in grids], logging_lvl=30, **opts)
-    assert type(dev.backend).__name__ == "HipBackend" and type(ref.backend).__name__ == "PluginBackend"
-    for a, b in zip(dev.t, ref.t):
-        assert np.array_equal(a, b)
-    return dev, ref
+    return pair("allencahn", nx, grids, side="reference", newton=True, par=dict(nu=nu, method=method), dev_par=app, **opts)
+
+
+def _random_states(ref, seed):
+    return random_states("allencahn", ref, seed)
 
 
 def _c_g(nu):
@@ -97,35 +95,25 @@ BOUNDS = types.SimpleNamespace(random_states=_random_states, phi_term=lambda ref
                                coarse_rows=lambda ref, st, lvl: st[("u", lvl)], weight_in_key=False, after=_no_item_at_newton_maxiter)
 
 
-def _tol(ref, lvl, rows):
-    return tol(BOUNDS, ref, lvl, rows)
-
-
 # ---- every sweep at the edge sizes of the new kernels ------------------------------------------------------------------------------
 @pytest.mark.parametrize("method", ["IMPL", "CN"])
 @pytest.mark.parametrize("nx,nu", [(4, 2), (33, 2), (66, 2), (20, 4)])
 def test_every_sweep_at_the_size_edges(nx, nu, method):
     """nx = 4: the stencil wraps onto itself; 33: odd, 1089 values, no multiple of a wave; 66: past one 64-tile; nu = 4 at nx = 20"""
     assert torch.cuda.is_available()
-    record = {}
-    for w in (1.0, 1.3):
-        dev, ref = _pair(nx, _uniform((17, 9, 5), T_SWEEP), method, nu=nu, weight_c=w)
+
+    def check(dev):
         d = dev.problem[0].device_stepper()
         assert d["theta"] == THETA[method] and d["nu"] == nu
-        run_sweeps(dev, ref, BOUNDS, w, 100 * nx + (7 if w != 1.0 else 0), ALL_SWEEPS, record=record)
-    _report(f"size_edges[nx={nx},nu={nu},{method}]", record)
+    both_weights(lambda w: _pair(nx, _uniform((17, 9, 5), T_SWEEP), method, nu=nu, weight_c=w), BOUNDS, 100 * nx, 100 * nx + 7,
+                 f"size_edges[nx={nx},nu={nu},{method}]", sweeps13=ALL_SWEEPS, check=check)
 
 
 def test_one_f_relaxation_at_a_larger_grid():
     assert torch.cuda.is_available()
     nx = 129
     dev, ref = _pair(nx, _uniform((5, 3), 2.0 ** -9), "IMPL")      # steps of 2^-11: fac / eps^2 = 0.31
-    st = _random_states(ref, nx)
-    _set_states(dev, ref, st)
-    dev.f_relax(0); ref.f_relax(0)
-    allowed = _tol(ref, 0, st[("u", 0)]) + 8 * EPS * 3 * _row_norm(*st.values())
-    worst = _compare(dev, ref, 0, allowed, "f_relax")
-    print(f"RATIO larger_grid[nx={nx}] f_relax: worst error/allowed {worst / allowed:.4f}")
+    check_one_phi(dev, ref, BOUNDS, nx, f"larger_grid[nx={nx}]")
     stats = dev.backend.newton_stats(0)
     print(f"nx={nx}: {stats}")
     assert stats["phi"] == 2 and stats["at_newton_maxiter"] == 0 and stats["newton_iterations"] >= 2
@@ -149,7 +137,7 @@ def test_mixed_convergence_in_one_batch(method):
     _set_states(dev, ref, st)
     dev.backend.newton_stats(0)
     dev.f_relax(0); ref.f_relax(0)
-    allowed = _tol(ref, 0, st[("u", 0)][0::2]) + 8 * EPS * 3 * _row_norm(*st.values())
+    allowed = tol(BOUNDS, ref, 0, st[("u", 0)][0::2]) + 8 * EPS * 3 * _row_norm(*st.values())
     worst = _compare(dev, ref, 0, allowed, "f_relax, mixed batch")
     print(f"RATIO mixed_batch[{method}] f_relax: worst error/allowed {worst / allowed:.4f}")
     got = dev.backend.natural("u", 0)
@@ -195,40 +183,30 @@ def test_an_item_is_the_same_bits_alone_and_among_others(method):
 
 
 # ---- several step sizes per level --------------------------------------------------------------------------------------------------
-RAGGED = np.concatenate(([0.0], np.cumsum(1e-4 * np.array([1, 1, 1.5, .5, 2, 1, 1, .75, 1, 1, 1, 1.25, 3, 1, 1, 1]))))
-RAGGED_GRIDS = {"by2_3lvl": [RAGGED, RAGGED[::2], RAGGED[::4]], "by4_2lvl": [RAGGED, RAGGED[::4]]}      # largest step 6e-4: fac / eps^2 <= 0.375
-
-
 @pytest.mark.parametrize("method", ["IMPL", "CN"])
 @pytest.mark.parametrize("grid", sorted(RAGGED_GRIDS))
 def test_every_sweep_with_several_step_sizes_per_level(grid, method):
     assert torch.cuda.is_available()
-    nx, record = 20, {}
-    for w in (1.0, 1.3):
-        dev, ref = _pair(nx, _intervals(RAGGED_GRIDS[grid]), method, weight_c=w)
+    nx = 20
+
+    def check(dev):
         for t in dev.t:
-            assert len(set(np.diff(np.asarray(t, dtype=np.float64)).view(np.int64).tolist())) >= 3
+            assert distinct_steps(t) >= 3
             assert THETA[method] * np.max(np.diff(t)) / 0.04 ** 2 < 1.0
-        run_sweeps(dev, ref, BOUNDS, w, 500 * nx + (3 if w != 1.0 else 0), ALL_SWEEPS, record=record)
-    _report(f"step_sizes[{grid},{method}]", record)
+    both_weights(lambda w: _pair(nx, _intervals(RAGGED_GRIDS[grid]), method, weight_c=w), BOUNDS, 500 * nx, 500 * nx + 3,
+                 f"step_sizes[{grid},{method}]", sweeps13=ALL_SWEEPS, check=check)
 
 
 # ---- sweeps of more than H2D_MAX_BATCH items ---------------------------------------------------------------------------------------
-H = 2.0 ** -17
-
-
 def test_sweeps_of_more_than_one_batch():
     """2050 steps H, then two steps 2 H: a dt group of 1025 items (a plan of 1024 and one of 1, each cut into Newton batches) and a
     second group of 1 in one sweep"""
     assert torch.cuda.is_available()
     nx, w = 9, 1.3
-    t = np.concatenate((H * np.arange(2051.0), H * np.array([2052.0, 2054.0])))
-    dev, ref = _pair(nx, _intervals([t, t[::2]]), "IMPL", weight_c=w)
-    t = np.asarray(dev.t[0])
-    assert len(t) == 2053 and len(dev.t[1]) == 1027
-    for pts in (np.arange(1, len(t), 2), np.arange(2, len(t), 2)):      # F-points, relaxed C-points
-        groups = sorted(collections.Counter((t[pts] - t[pts - 1]).view(np.int64).tolist()).values())
-        assert len(pts) >= 1025 and groups == [1, 1025], groups
+    dev, ref = _pair(nx, _intervals([TWO_SIZES, TWO_SIZES[::2]]), "IMPL", weight_c=w)
+    assert len(dev.t[0]) == 2053 and len(dev.t[1]) == 1027
+    for groups in dt_groups(dev.t[0]):      # F-points, relaxed C-points
+        assert sum(groups) >= 1025 and groups == [1, 1025], groups
     dev.backend.newton_stats(0)
     record = run_sweeps(dev, ref, BOUNDS, w, 77, ("f_relax",), levels=[0])
     assert dev.backend.newton_stats(0)["phi"] == 0      # (run_sweeps has read the counts: the call resets them)
@@ -315,22 +293,21 @@ def test_the_exit_criterion_holds_for_the_returned_rows(method):
 
 
 # ---- solves ------------------------------------------------------------------------------------------------------------------------
-SOLVES = {**META["solve"], "impl_2lvl_V": test_allen_cahn_cpu.META["solve"]["impl_2lvl_V"]}
+SOLVES = {**META["solve"], "impl_2lvl_V": allen_cahn_fixtures.META["solve"]["impl_2lvl_V"]}
 
 
 @pytest.mark.parametrize("name", sorted(SOLVES))
-def test_solves_match_the_reference_histories(name, monkeypatch):
+def test_solves_match_the_reference_histories(name):
     from pymgrit_amd import AllenCahn, Mgrit
     assert torch.cuda.is_available()
     rec = SOLVES[name]
-    last = (ARR if name in META["solve"] else test_allen_cahn_cpu.ARR)["last_" + name].ravel()
+    last = (ARR if name in META["solve"] else allen_cahn_fixtures.ARR)["last_" + name].ravel()
     prob = [AllenCahn(nx=rec["nx"], method=rec["method"], linear_solver="pcg", t_start=0, t_stop=META["t_stop"], nt=nt) for nt in rec["nts"]]
     dev = Mgrit(prob, logging_lvl=30, **rec["opts"])
     assert type(dev.backend).__name__ == "HipBackend"
     conv = dev.solve()["conv"]
     u = dev.backend.natural("u", 0)
-    monkeypatch.setitem(test_allen_cahn_cpu.META["solve"], name, rec)      # check_history looks the reference history up there
-    check_history(name, conv, cases.spacetime_norm(u))
+    check_history(name, conv, cases.spacetime_norm(u), ref=rec["conv"])
     print(f"RATIO solve[{name}] last state: relative deviation {np.abs(u[-1] - last).max() / np.abs(last).max():.3e} (allowed 1e-9)")
     assert np.abs(u[-1] - last).max() <= 1e-9 * np.abs(last).max()
     stats = [dev.backend.newton_stats(lvl) for lvl in range(dev.lvl_max)]
@@ -342,9 +319,7 @@ def test_an_imex_coarse_level_under_an_impl_fine_level():
     from pymgrit_amd import AllenCahn, Mgrit
     assert torch.cuda.is_available()
 
-    class HostAllenCahn(AllenCahn):     # overriding step sends the hierarchy to the plugin path
-        def step(self, u_start, t_start, t_stop):
-            return super().step(u_start, t_start, t_stop)
+    HostAllenCahn = host_class(AllenCahn)
 
     def prob(cls):
         return [cls(nx=32, method="IMPL", linear_solver="pcg", t_start=0, t_stop=META["t_stop"], nt=33),

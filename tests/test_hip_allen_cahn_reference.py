@@ -25,65 +25,33 @@ Tolerances: those of test_hip_allen_cahn.py with ONE device evaluation instead o
                e_k = Lip_k e_(k-1) + the step's per-Phi term + SLACK, Lip_k as in test_hip_allen_cahn.py.
 Every comparison covers all rows of a list. Each sweep prints its worst error / allowed ("RATIO" lines).
 """
-import collections
-import types
-
 import numpy as np
 import pytest
 
-import cases
-from allen_cahn_reference import ReferenceAllenCahn
-from periodic2d_sweeps import (ALL_SWEEPS, STORED_STATE_SWEEPS, compare as _compare, distinct_steps as _distinct_steps, host_state as _host_state,
-                               intervals as _intervals, ratio as _ratio, report as _report, row_norm as _row_norm, run_sweeps,
-                               set_states as _set_states, tol, uniform as _uniform)      # (_ratio: for test_hip_heat2d_reference.py)
-from test_allen_cahn_cpu import EPS
-from test_hip_allen_cahn import T_SWEEP, _b_norm, _random_states
+from periodic2d_kinds import AC_BATCH_GRIDS as BATCH_GRIDS, AC_BATCH_GROUPS as BATCH_GROUPS, KINDS
+from periodic2d_sweeps import (ALL_SWEEPS, EPS, STORED_STATE_SWEEPS, both_weights, bounds_of, check_history, check_one_phi, check_ragged,
+                               compare as _compare, distinct_steps as _distinct_steps, dt_groups, intervals as _intervals, pair, report as _report,
+                               row_norm as _row_norm, run_sweeps, set_states as _set_states, tol, uniform as _uniform)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
+T_SWEEP = KINDS["allencahn"].t_sweep(None)
+RAGGED_GRIDS = KINDS["allencahn"].ragged(None)
+BOUNDS = bounds_of("allencahn", "reference")      # (the formulas of the module docstring take c = dt / eps^2)
+
 
 def _pair(nx, grids, nu=2, **opts):
     """(device Mgrit, plugin Mgrit over ReferenceAllenCahn) on the same hierarchy"""
-    from pymgrit_amd import AllenCahn, Mgrit
-    opts.setdefault("nested_iteration", False)
-    dev = Mgrit([AllenCahn(nx=nx, nu=nu, method="IMEX", **g) for g in grids], logging_lvl=30, **opts)
-    ref = Mgrit([ReferenceAllenCahn(nx=nx, nu=nu, method="IMEX", **g) for g in grids], logging_lvl=30, **opts)
-    assert type(dev.backend).__name__ == "HipBackend" and type(ref.backend).__name__ == "PluginBackend"
-    for a, b in zip(dev.t, ref.t):
-        assert np.array_equal(a, b)
-    return dev, ref
-
-
-def _phi_term(app, rows, c):
-    """one device evaluation and the reference's rounding: (4 nx + 8) EPS bnorm + EPS bnorm"""
-    return ((4 * app.nx + 8) + 1) * EPS * _b_norm(app, rows, c)
-
-
-def _lip(app, c, rows):
-    R = float(np.abs(rows).max())
-    return max(abs(1 + c), abs(1 + c * (1 - (app.nu + 1) * R ** app.nu)))
-
-
-# the formulas above take c = dt / eps^2
-BOUNDS = types.SimpleNamespace(random_states=_random_states, phi_term=lambda ref, app, rows, dt: _phi_term(app, rows, dt / app.eps ** 2),
-                               lip=lambda app, dt, rows: _lip(app, dt / app.eps ** 2, rows), values_per_state=lambda app: app.nx * app.nx,
-                               coarse_rows=lambda ref, st, lvl: st[("u", lvl)], weight_in_key=False)
-
-
-def _tol(ref, lvl, rows):
-    return tol(BOUNDS, ref, lvl, rows)
+    return pair("allencahn", nx, grids, side="reference", par=dict(nu=nu), **opts)
 
 
 # ---- a. every sweep at the size edges of the tile product --------------------------------------------------------------------------
 @pytest.mark.parametrize("nx", [4, 33, 96, 97, 129])
 def test_every_sweep_at_the_size_edges(nx):
     assert torch.cuda.is_available()
-    record = {}
-    for w in (1.0, 1.3):
-        dev, ref = _pair(nx, _uniform((17, 9, 5), T_SWEEP), weight_c=w)
-        run_sweeps(dev, ref, BOUNDS, w, 100 * nx + (7 if w != 1.0 else 0), ALL_SWEEPS, record=record)
-    _report(f"size_edges[nx={nx}]", record)
+    both_weights(lambda w: _pair(nx, _uniform((17, 9, 5), T_SWEEP), weight_c=w), BOUNDS, 100 * nx, 100 * nx + 7, f"size_edges[nx={nx}]",
+                 sweeps13=ALL_SWEEPS)
 
 
 # ---- b. every sweep for other exponents --------------------------------------------------------------------------------------------
@@ -91,33 +59,22 @@ def test_every_sweep_at_the_size_edges(nx):
 @pytest.mark.parametrize("nx", [20, 66])
 def test_every_sweep_for_other_exponents(nx, nu):
     assert torch.cuda.is_available()
-    record = {}
-    for w in (1.0, 1.3):
-        dev, ref = _pair(nx, _uniform((17, 9, 5), T_SWEEP), nu=nu, weight_c=w)
+    sweeps = ALL_SWEEPS if nu % 2 == 0 else STORED_STATE_SWEEPS
+
+    def check(dev):
         assert dev.problem[0].device_stepper()["nu"] == nu
-        run_sweeps(dev, ref, BOUNDS, w, 1000 * nx + 10 * nu + (5 if w != 1.0 else 0), ALL_SWEEPS if nu % 2 == 0 else STORED_STATE_SWEEPS, record=record)
-    _report(f"exponents[nx={nx},nu={nu}]", record)
+    both_weights(lambda w: _pair(nx, _uniform((17, 9, 5), T_SWEEP), nu=nu, weight_c=w), BOUNDS, 1000 * nx + 10 * nu, 1000 * nx + 10 * nu + 5,
+                 f"exponents[nx={nx},nu={nu}]", sweeps=sweeps, sweeps13=sweeps, check=check)
 
 
 # ---- c. several step sizes per level -----------------------------------------------------------------------------------------------
-RAGGED = np.concatenate(([0.0], np.cumsum(1e-4 * np.array([1, 1, 1.5, .5, 2, 1, 1, .75, 1, 1, 1, 1.25, 3, 1, 1, 1]))))
-RAGGED_GRIDS = {"by2_3lvl": [RAGGED, RAGGED[::2], RAGGED[::4]], "by4_2lvl": [RAGGED, RAGGED[::4]]}
-
-
 @pytest.mark.parametrize("nu", [2, 4])
 @pytest.mark.parametrize("nx", [20, 66])
 @pytest.mark.parametrize("grid", sorted(RAGGED_GRIDS))
 def test_every_sweep_with_several_step_sizes_per_level(grid, nx, nu):
     assert torch.cuda.is_available()
-    record = {}
-    for w in (1.0, 1.3):
-        dev, ref = _pair(nx, _intervals(RAGGED_GRIDS[grid]), nu=nu, weight_c=w)
-        for t in dev.t:
-            assert _distinct_steps(t) >= 3 and len(set(np.round(np.diff(t) / 1e-4, 6))) >= 3, np.diff(t)
-        if grid == "by4_2lvl":      # the three F-points of one interval do not share one D table (steps 1, 1, 1.5 and 2, 1, 1 of 1e-4)
-            assert sum(len(set(np.round(np.diff(dev.t[0][a:a + 4]) / 1e-4, 6))) >= 2 for a in range(0, 16, 4)) >= 2
-        run_sweeps(dev, ref, BOUNDS, w, 500 * nx + 10 * nu + (3 if w != 1.0 else 0), ALL_SWEEPS, record=record)
-    _report(f"step_sizes[{grid},nx={nx},nu={nu}]", record)
+    both_weights(lambda w: _pair(nx, _intervals(RAGGED_GRIDS[grid]), nu=nu, weight_c=w), BOUNDS, 500 * nx + 10 * nu, 500 * nx + 10 * nu + 3,
+                 f"step_sizes[{grid},nx={nx},nu={nu}]", sweeps13=ALL_SWEEPS, check=lambda dev: check_ragged(dev, grid, unit=1e-4))
 
 
 @pytest.mark.parametrize("nu", [2, 4])
@@ -128,37 +85,10 @@ def test_solve_with_several_step_sizes_per_level(nx, nu):
     dev, ref = _pair(nx, _intervals(RAGGED_GRIDS["by2_3lvl"]), nu=nu, max_iter=3, tol=0.0)
     for t in dev.t:
         assert _distinct_steps(t) >= 3
-    conv, rconv = np.asarray(dev.solve()["conv"]), np.asarray(ref.solve()["conv"])
-    u = dev.backend.natural("u", 0)
-    norm_u = cases.spacetime_norm(u)
-    assert len(conv) == len(rconv) == 3
-    dev_ref = np.abs(conv - rconv)
-    print(f"RATIO solve[nx={nx},nu={nu}] conv: largest deviation {np.max(dev_ref) / (EPS * norm_u):.2f} units of eps*norm(u) "
-          f"(allowed {cases.BLK_K} beyond 1e-10 relative)")
-    assert np.all(dev_ref <= 1e-10 * rconv + cases.BLK_K * EPS * norm_u), (conv, rconv)
-    last = _host_state(ref, "u", 0)[-1]
-    print(f"RATIO solve[nx={nx},nu={nu}] last state: relative deviation {np.abs(u[-1] - last).max() / np.abs(last).max():.3e}")
-    assert np.abs(u[-1] - last).max() <= 1e-9 * np.abs(last).max()
+    check_history(dev, ref, f"solve[nx={nx},nu={nu}]", 3)
 
 
 # ---- d. sweeps that split into several batches -------------------------------------------------------------------------------------
-H = 2.0 ** -17          # 7.6e-6: every t_k = k H and every difference is exact, one bit pattern of dt
-BATCH_GRIDS = {
-    # as nt = / linspace: a dozen bit patterns of dt per level, the largest group has some 620 items (one launch each)
-    "linspace_2051": lambda: _uniform((2051, 1026), 2050e-5),
-    "cumsum_2051": lambda: _levels_by2(np.concatenate(([0.0], np.cumsum([1e-5] * 2048 + [2e-5] * 2)))),
-    # exact steps: 1025 F-points / C-points of one dt = a batch of 1024 and one of 1
-    "dyadic_2051": lambda: _levels_by2(H * np.arange(2051.0)),
-    # 2050 steps H, then two steps 2 H: a full batch, a remainder of 1 and a second dt group in one sweep
-    "dyadic_2053_two_sizes": lambda: _levels_by2(np.concatenate((H * np.arange(2051.0), H * np.array([2052.0, 2054.0])))),
-}
-BATCH_GROUPS = {"dyadic_2051": [1025], "dyadic_2053_two_sizes": [1, 1025]}      # sizes of the dt groups among the level-0 F-points
-
-
-def _levels_by2(t):
-    return _intervals([t, t[::2]])
-
-
 @pytest.mark.parametrize("grid", sorted(BATCH_GRIDS))
 def test_sweeps_of_more_than_one_batch(grid):
     assert torch.cuda.is_available()
@@ -166,10 +96,9 @@ def test_sweeps_of_more_than_one_batch(grid):
     dev, ref = _pair(nx, BATCH_GRIDS[grid](), weight_c=w)
     t = np.asarray(dev.t[0])
     assert len(t) in (2051, 2053) and len(dev.t[1]) == (len(t) + 1) // 2
-    for pts in (np.arange(1, len(t), 2), np.arange(2, len(t), 2)):      # F-points, relaxed C-points
-        groups = sorted(collections.Counter((t[pts] - t[pts - 1]).view(np.int64).tolist()).values())
-        print(f"{grid}: dt groups of {len(pts)} points: {groups}")
-        assert len(pts) >= 1025
+    for groups in dt_groups(t):      # F-points, relaxed C-points
+        print(f"{grid}: dt groups of {sum(groups)} points: {groups}")
+        assert sum(groups) >= 1025
         if grid in BATCH_GROUPS:
             assert groups == BATCH_GROUPS[grid], groups
     record = run_sweeps(dev, ref, BOUNDS, w, 77, STORED_STATE_SWEEPS, levels=[0])
@@ -181,12 +110,7 @@ def test_sweeps_of_more_than_one_batch(grid):
 def test_one_phi_at_larger_grids(nx):
     assert torch.cuda.is_available()
     dev, ref = _pair(nx, _uniform((5, 3), 2.0 ** -9))      # (steps of 2^-11, exact: one factorisation on the reference side)
-    st = _random_states(ref, nx)
-    _set_states(dev, ref, st)
-    dev.f_relax(0); ref.f_relax(0)
-    allowed = _tol(ref, 0, st[("u", 0)]) + 8 * EPS * 3 * _row_norm(*st.values())
-    worst = _compare(dev, ref, 0, allowed, "f_relax")
-    print(f"RATIO larger_grids[nx={nx}] f_relax: worst error/allowed {worst / allowed:.4f}")
+    check_one_phi(dev, ref, BOUNDS, nx, f"larger_grids[nx={nx}]")
 
 
 # ---- f. constants ------------------------------------------------------------------------------------------------------------------
@@ -195,13 +119,13 @@ def test_constant_rows_are_returned():
     assert torch.cuda.is_available()
     nx = 33
     dev, ref = _pair(nx, _uniform((17, 9, 5), T_SWEEP))
-    st = _random_states(ref, 5)
+    st = BOUNDS.random_states(ref, 5)
     const = np.array([0.0, 1.0, -1.0])[(np.arange(17) // 2) % 3]          # the C-point 2 k and the F-point behind it: the same constant
     st[("u", 0)] = np.repeat(const[:, None], nx * nx, axis=1)
     st[("u", 0)][1::2] = 0.5                                               # (what F-relaxation has to overwrite)
     _set_states(dev, ref, st)
     dev.f_relax(0); ref.f_relax(0)
-    allowed = _tol(ref, 0, st[("u", 0)][0::2]) + 8 * EPS * 3 * _row_norm(*st.values())
+    allowed = tol(BOUNDS, ref, 0, st[("u", 0)][0::2]) + 8 * EPS * 3 * _row_norm(*st.values())
     worst = _compare(dev, ref, 0, allowed, "f_relax, constant rows")
     got = dev.backend.natural("u", 0)
     err = float(np.max(np.linalg.norm(got - const[:, None], axis=1)))

@@ -189,15 +189,14 @@ def _from_worker(name):
 def _allen_cahn():
     """the small solve of tests/test_hip_allen_cahn.py (test_output_fcn_and_cf_iter)"""
     from pymgrit_amd import AllenCahn
-    from test_allen_cahn_cpu import META
+    from allen_cahn_fixtures import META
     return ([AllenCahn(nx=20, method="IMEX", t_start=0, t_stop=META["t_stop"], nt=nt) for nt in (33, 9)], None,
             dict(cf_iter=2, max_iter=3, tol=0.0))
 
 
 def _general_forcing():
     """forcing_rows on Heat1D levels (tests/test_hip_forcing.py)"""
-    from test_hip_forcing import problem
-    return problem(65, [cases.lin(2, 65), cases.lin(2, 17), cases.lin(2, 5)]), None, dict(max_iter=3, tol=0.0)
+    return cases.general_forcing_problem(65, [cases.lin(2, 65), cases.lin(2, 17), cases.lin(2, 5)]), None, dict(max_iter=3, tol=0.0)
 
 
 def _general_forcing_heat2d():

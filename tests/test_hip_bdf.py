@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import cases
-from test_hip_parity import _need_gpu, assert_state_equal, randomize
+from parity_cases import need_gpu as _need_gpu, assert_state_equal, randomize
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")

@@ -81,7 +81,7 @@ def test_rank_rule_library_equals_oracle(oracle):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name,kind,nx,grids,forcing", SHAPES, ids=[s[0] for s in SHAPES])
 def test_forward_solve_bit_exact(oracle, name, kind, nx, grids, forcing):
-    from test_hip_parity import _need_gpu, assert_state_equal, make_pair, randomize
+    from parity_cases import need_gpu as _need_gpu, assert_state_equal, make_pair, randomize
     _need_gpu()
     mg, op = make_pair(oracle, kind, nx, grids, **({"forcing": forcing} if kind == "heat" else {}))
     lvl = mg.lvl_max - 1
@@ -108,7 +108,7 @@ def test_one_launch_form_equals_the_phase_launches(oracle, monkeypatch, nx, grid
     """small Heat1D levels (one group of values, <= 128 blocks, <= 64 modes, one rank) run the three phases of the solve as ONE
     launch with device-wide barriers (blk_one_kernel): the same bits as the per-phase launches (MGRIT_HIP_BLK_ONE=0), solve after
     solve on the same engine (the barrier counters are reused) and through whole cycles; wider levels keep the phases"""
-    from test_hip_parity import _need_gpu, make_pair, randomize
+    from parity_cases import need_gpu as _need_gpu, make_pair, randomize
     _need_gpu()
     mg1, op = make_pair(oracle, "heat", nx, grids, forcing=forcing)
     monkeypatch.setenv("MGRIT_HIP_BLK_ONE", "0")
@@ -135,7 +135,7 @@ def test_sequential_form_on_request(oracle):
     """options.coarse_solve = 'sequential' keeps the step-by-step chain: bit for bit the oracle's step-by-step result, and within
     rounding of the time-parallel one"""
     from pymgrit_amd.core.options import options
-    from test_hip_parity import _need_gpu, assert_state_equal, make_pair, randomize
+    from parity_cases import need_gpu as _need_gpu, assert_state_equal, make_pair, randomize
     _need_gpu()
     grids = _grids(513, (4,))
     try:

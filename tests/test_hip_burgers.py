@@ -33,144 +33,64 @@ Tolerances, nothing in them measured on the device (test_burgers_cpu.py derives 
                norm(delta b) <= (1 + dt (R / dx) (sqrt(2) sqrt(2) + 2)) norm(delta) = (1 + 4 dt R / dx) norm(delta).
 Every comparison covers all rows of a list. Each sweep prints its worst error / allowed ("RATIO" lines).
 """
-import collections
-import ctypes as C
 import types
 
 import numpy as np
 import pytest
 
 import cases
-from burgers_reference import ReferenceBurgers2D
-from periodic2d_sweeps import (ALL_SWEEPS, STORED_STATE_SWEEPS, compare as _compare, distinct_steps as _distinct_steps, intervals as _intervals,
-                               lists as _lists, report as _report, row_norm as _row_norm, run_sweeps, set_states as _set_states, tol,
+from periodic2d_kinds import KINDS, dyadic
+from periodic2d_sweeps import (STORED_STATE_SWEEPS, both_weights, bounds_of, check_history, check_jump_criterion, check_level_0_twice,
+                               check_level_entry_point, check_one_phi, check_ragged, compare as _compare, dt_groups, f_relaxed_rows,
+                               intervals as _intervals, pair, report as _report, row_norm as _row_norm, run_sweeps, set_states as _set_states, tol,
                                uniform as _uniform)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 EPS = cases.EPS
-NU = 0.1
-T_SWEEP = 0.004
+KIND = KINDS["burgers"]
+T_SWEEP = KIND.t_sweep(None)
+BOUNDS = {side: bounds_of("burgers", side) for side in ("host", "reference")}
 
 
-def _coef(nx):
-    return 4 * nx + 12
-
-
-def _host_class():
-    from pymgrit_amd import Burgers2D
-
-    class HostBurgers2D(Burgers2D):     # overriding step sends the hierarchy to the plugin path
-        def step(self, u_start, t_start, t_stop):
-            return super().step(u_start, t_start, t_stop)
-    return HostBurgers2D
-
-
-def _pair(nx, grids, side="host", par=None, **opts):
+def _pair(nx, grids, side="host", **opts):
     """(device Mgrit, plugin Mgrit over HostBurgers2D or ReferenceBurgers2D) on the same hierarchy"""
-    from pymgrit_amd import Burgers2D, Mgrit
-    opts.setdefault("nested_iteration", False)
-    par = dict(nu=NU, L=nx / 16) if par is None else par
-    cls = {"host": _host_class(), "reference": ReferenceBurgers2D}[side]
-    dev = Mgrit([Burgers2D(nx=nx, **par, **g) for g in grids], logging_lvl=30, **opts)
-    ref = Mgrit([cls(nx=nx, **par, **g) for g in grids], logging_lvl=30, **opts)
-    assert type(dev.backend).__name__ == "HipBackend" and type(ref.backend).__name__ == "PluginBackend"
-    for a, b in zip(dev.t, ref.t):
-        assert np.array_equal(a, b)
-    return dev, ref
-
-
-def _random_states(ref, seed):
-    """per list and level [n_pts][2 nx^2], uniform in [-1, 1]"""
-    rng = np.random.default_rng(seed)
-    return {(name, lvl): rng.uniform(-1.0, 1.0, size=(len(lst), 2 * ref.problem[lvl].nx ** 2))
-            for lvl in range(ref.lvl_max) for name, lst in _lists(ref, lvl)}
-
-
-def _majorant(app, rows, dt):
-    """the largest row majorant, both planes joined (module docstring)"""
-    nx = app.nx
-    w = np.abs(np.atleast_2d(rows)).reshape(-1, 2, nx, nx)
-    u, v = w[:, 0], w[:, 1]
-    m2 = 0.0
-    for c in (u, v):
-        m = c + dt * app.inv_2dx * (u * (np.roll(c, -1, 1) + np.roll(c, 1, 1)) + v * (np.roll(c, -1, 2) + np.roll(c, 1, 2)))
-        m2 = m2 + np.sum(m * m, axis=(1, 2))
-    return float(np.sqrt(np.max(m2)))
-
-
-def _phi_term(app, rows, dt):
-    against_reference = isinstance(app, ReferenceBurgers2D)
-    return (_coef(app.nx) + 1 if against_reference else 2 * _coef(app.nx)) * EPS * _majorant(app, rows, dt)
-
-
-def _lip(app, dt, rows):
-    return 1.0 + 4.0 * dt * float(np.abs(rows).max()) / app.dx
-
-
-BOUNDS = types.SimpleNamespace(random_states=_random_states, phi_term=lambda ref, app, rows, dt: _phi_term(app, rows, dt), lip=_lip,
-                               values_per_state=lambda app: 2 * app.nx ** 2, coarse_rows=lambda ref, st, lvl: st[("u", lvl)], weight_in_key=True)
-
-
-def _tol(ref, lvl, rows):
-    return tol(BOUNDS, ref, lvl, rows)
+    return pair("burgers", nx, grids, side=side, **opts)
 
 
 # ---- a. every sweep at the size edges ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("nx", [4, 33, 66, 97])
 def test_every_sweep_at_the_size_edges(nx):
     assert torch.cuda.is_available()
-    record = {}
-    for w, sweeps in ((1.0, ALL_SWEEPS), (1.3, ("c_relax",))):      # (the weight enters the C-relaxation only)
-        dev, ref = _pair(nx, _uniform((17, 9, 5), T_SWEEP), weight_c=w)
+
+    def check(dev):
         assert dev.problem[0].dx == 1.0 / 16
-        run_sweeps(dev, ref, BOUNDS, w, 100 * nx + (7 if w != 1.0 else 0), sweeps, record=record)
-    _report(f"size_edges[nx={nx}]", record)
+    both_weights(lambda w: _pair(nx, _uniform((17, 9, 5), T_SWEEP), weight_c=w), BOUNDS["host"], 100 * nx, 100 * nx + 7, f"size_edges[nx={nx}]",
+                 check=check)
 
 
 # ---- b. several step sizes per level -----------------------------------------------------------------------------------------------
-RAGGED = np.concatenate(([0.0], np.cumsum(np.array([1, 1, 1.5, .5, 2, 1, 1, .75, 1, 1, 1, 1.25, 3, 1, 1, 1]))))
-
-
-def _ragged(grid):
-    t = RAGGED * 2.0 ** -12      # 18 units: [0, 0.0044]; at most 6.25 units per coarse step, dt / dx = 0.024
-    return {"by2_3lvl": [t, t[::2], t[::4]], "by4_2lvl": [t, t[::4]]}[grid]
-
-
 @pytest.mark.parametrize("side", ["host", "reference"])
 @pytest.mark.parametrize("grid", ["by2_3lvl", "by4_2lvl"])
 def test_every_sweep_with_several_step_sizes_per_level(grid, side):
     assert torch.cuda.is_available()
-    nx, record = 33, {}
-    for w, sweeps in ((1.0, ALL_SWEEPS), (1.3, ("c_relax",))):
-        dev, ref = _pair(nx, _intervals(_ragged(grid)), side=side, weight_c=w)
-        for t in dev.t:
-            assert _distinct_steps(t) >= 3, np.diff(t)
-        if grid == "by4_2lvl":      # the three F-points of one interval do not share one D table
-            assert sum(_distinct_steps(dev.t[0][a:a + 4]) >= 2 for a in range(0, 16, 4)) >= 2
-        run_sweeps(dev, ref, BOUNDS, w, 500 * nx + (3 if w != 1.0 else 0), sweeps, record=record)
-    _report(f"step_sizes[{grid},{side}]", record)
+    nx = 33
+    both_weights(lambda w: _pair(nx, _intervals(KIND.ragged(nx)[grid]), side=side, weight_c=w), BOUNDS[side], 500 * nx, 500 * nx + 3,
+                 f"step_sizes[{grid},{side}]", check=lambda dev: check_ragged(dev, grid))
 
 
 # ---- c. a dt group larger than one batch -------------------------------------------------------------------------------------------
-def _dyadic_1027():
-    """1027 points with the exact step 2^-18 (every t_k = k 2^-18 and every difference is exact: one bit pattern of dt; [0, 0.0039])"""
-    t = 2.0 ** -18 * np.arange(1027.0)
-    return [t, t[::2]]
-
-
 def test_sweeps_of_more_than_one_batch():
-    """513 F-points and 513 relaxed C-points, each one dt group = a batch of 512 states (1024 work slab items) and a batch of 1"""
+    """1027 points with the exact step 2^-18 (every t_k = k 2^-18 and every difference is exact: one bit pattern of dt; [0, 0.0039]):
+    513 F-points and 513 relaxed C-points, each one dt group = a batch of 512 states (1024 work slab items) and a batch of 1"""
     assert torch.cuda.is_available()
     nx, w = 4, 1.3
-    dev, ref = _pair(nx, _intervals(_dyadic_1027()), weight_c=w)
-    t = np.asarray(dev.t[0])
-    assert len(t) == 1027 and len(dev.t[1]) == 514
-    for pts in (np.arange(1, len(t), 2), np.arange(2, len(t), 2)):      # F-points, relaxed C-points
-        groups = sorted(collections.Counter((t[pts] - t[pts - 1]).view(np.int64).tolist()).values())
+    dev, ref = _pair(nx, _intervals(dyadic("burgers", 1027)), weight_c=w)
+    assert len(dev.t[0]) == 1027 and len(dev.t[1]) == 514
+    for groups in dt_groups(dev.t[0]):      # F-points, relaxed C-points
         assert groups == [513] and 513 > 1024 // 2, groups
-    record = run_sweeps(dev, ref, BOUNDS, w, 77, STORED_STATE_SWEEPS, levels=[0])
+    record = run_sweeps(dev, ref, BOUNDS["host"], w, 77, STORED_STATE_SWEEPS, levels=[0])
     _report("batches[dyadic_1027]", record)
 
 
@@ -179,12 +99,7 @@ def test_one_phi_at_a_larger_grid():
     assert torch.cuda.is_available()
     nx = 129
     dev, ref = _pair(nx, _uniform((5, 3), 2.0 ** -8))      # (steps of 2^-10, exact)
-    st = _random_states(ref, nx)
-    _set_states(dev, ref, st)
-    dev.f_relax(0); ref.f_relax(0)
-    allowed = _tol(ref, 0, st[("u", 0)]) + 8 * EPS * 3 * _row_norm(*st.values())
-    worst = _compare(dev, ref, 0, allowed, "f_relax")
-    print(f"RATIO larger_grid[nx={nx}] f_relax: worst error/allowed {worst / allowed:.4f}")
+    check_one_phi(dev, ref, BOUNDS["host"], nx, f"larger_grid[nx={nx}]")
 
 
 # ---- e. the fixed point and the y-independent state ----------------------------------------------------------------------------------
@@ -197,14 +112,14 @@ def test_constant_and_y_independent_rows():
     nx = 33
     dev, ref = _pair(nx, _uniform((17, 9, 5), T_SWEEP))
     n = nx * nx
-    st = _random_states(ref, 5)
+    st = BOUNDS["host"].random_states(ref, 5)
     const = np.concatenate((np.full(n, 0.75), np.full(n, -1.25)))
     f = np.random.default_rng(11).uniform(-1.0, 1.0, size=nx)
     yind = np.concatenate((np.repeat(f, nx), np.zeros(n)))      # u[i][j] = f[i]: axis 0 is x
     st[("u", 0)][0::4], st[("u", 0)][2::4] = const, yind
     _set_states(dev, ref, st)
     dev.f_relax(0); ref.f_relax(0)
-    allowed = _tol(ref, 0, st[("u", 0)][0::2]) + 8 * EPS * 3 * _row_norm(*st.values())
+    allowed = tol(BOUNDS["host"], ref, 0, st[("u", 0)][0::2]) + 8 * EPS * 3 * _row_norm(*st.values())
     worst = _compare(dev, ref, 0, allowed, "f_relax, constant and y-independent rows")
     got = dev.backend.natural("u", 0)
     err = float(np.max(np.linalg.norm(got[1::4] - const, axis=1)))
@@ -220,17 +135,8 @@ def test_constant_and_y_independent_rows():
 # ---- f. the same bits ----------------------------------------------------------------------------------------------------------------
 def test_a_sweep_run_twice_gives_the_same_bits():
     assert torch.cuda.is_available()
-    nx = 33
-    dev, ref = _pair(nx, _uniform((17, 9, 5), T_SWEEP))
-    st = _random_states(ref, 21)
-    for sweep in ("f_relax", "c_relax"):
-        slabs = []
-        for _ in range(2):
-            _set_states(dev, ref, st)
-            getattr(dev, sweep)(0)
-            slabs.append(dev.backend.U[0].clone())
-        assert torch.equal(slabs[0], slabs[1]), sweep
-    assert not torch.equal(slabs[0][1], slabs[0][3])      # (rows of different states differ)
+    dev, ref = _pair(33, _uniform((17, 9, 5), T_SWEEP))
+    check_level_0_twice(dev, ref, BOUNDS["host"].random_states(ref, 21))
 
 
 def test_a_rows_bits_do_not_depend_on_its_batch():
@@ -238,19 +144,11 @@ def test_a_rows_bits_do_not_depend_on_its_batch():
     512 and the batch of 1): the same row, bit for bit"""
     assert torch.cuda.is_available()
     nx = 4
-    big, ref_big = _pair(nx, _intervals(_dyadic_1027()))
-    t7 = 2.0 ** -18 * np.arange(7.0)
-    small, ref_small = _pair(nx, _intervals([t7, t7[::2]]))
+    big, ref_big = _pair(nx, _intervals(dyadic("burgers", 1027)))
+    small, ref_small = _pair(nx, _intervals(dyadic("burgers", 7)))
     state = np.random.default_rng(3).uniform(-1.0, 1.0, size=2 * nx * nx)
-    rows = {}
-    for name, dev, ref, at in (("small", small, ref_small, (0,)), ("big", big, ref_big, (0, 1024))):
-        st = _random_states(ref, 9)
-        for i in at:
-            st[("u", 0)][i] = state
-        _set_states(dev, ref, st)
-        dev.f_relax(0)
-        U = dev.backend.U[0]
-        rows[name] = [U[i + 1].clone() for i in at]
+    rows = {name: f_relaxed_rows(dev, ref, BOUNDS["host"].random_states(ref, 9), state, at)
+            for name, dev, ref, at in (("small", small, ref_small, (0,)), ("big", big, ref_big, (0, 1024)))}
     assert torch.equal(rows["small"][0], rows["big"][0]) and torch.equal(rows["small"][0], rows["big"][1])
     assert not torch.equal(rows["small"][0][:2 * nx * nx], torch.from_numpy(state).to(rows["small"][0].device))
 
@@ -268,27 +166,14 @@ def test_solve_matches_the_plugin_path(cycle):
     """from the initial guess on (nx = 12, nu = 0.05, [0, 0.25], nt 17 / 9 / 5): residual histories by the rule of tests/cases.py"""
     assert torch.cuda.is_available()
     dev, ref = _pair(12, _solve_grids(), cycle_type=cycle, max_iter=6, tol=1e-10, nested_iteration=True, **SOLVE)
-    conv, rconv = np.asarray(dev.solve()["conv"]), np.asarray(ref.solve()["conv"])
-    u = dev.backend.natural("u", 0)
-    norm_u = cases.spacetime_norm(u)
-    assert len(conv) == len(rconv) >= 2, (conv, rconv)
-    dev_ref = np.abs(conv - rconv)
-    print(f"RATIO solve[{cycle}] conv ({len(conv)} iterations): largest deviation {np.max(dev_ref) / (EPS * norm_u):.2f} units of "
-          f"eps*norm(u) (allowed {cases.BLK_K} beyond 1e-10 relative)")
-    assert np.all(dev_ref <= 1e-10 * rconv + cases.BLK_K * EPS * norm_u), (conv, rconv)
-    last = np.asarray(ref.u[0][-1].get_values()).ravel()
-    print(f"RATIO solve[{cycle}] last state: relative deviation {np.abs(u[-1] - last).max() / np.abs(last).max():.3e}")
+    check_history(dev, ref, f"solve[{cycle}]", last_state=False)
 
 
 def test_jump_criterion_matches_the_plugin_path():
     """conv_crit = 1: the norms of u_i - previous u_i over both planes, three iterations from the initial guess; the same rule"""
     assert torch.cuda.is_available()
     dev, ref = _pair(12, _solve_grids(), conv_crit=1, max_iter=3, tol=0.0, **SOLVE)
-    conv, rconv = np.asarray(dev.solve()["conv"]), np.asarray(ref.solve()["conv"])
-    norm_u = cases.spacetime_norm(dev.backend.natural("u", 0))
-    assert len(conv) == len(rconv) == 3 and np.all(rconv[:2] > 0.0), (conv, rconv)
-    print(f"RATIO solve[jump] conv: largest deviation {np.max(np.abs(conv - rconv)) / (EPS * norm_u):.2f} units of eps*norm(u)")
-    assert np.all(np.abs(conv - rconv) <= 1e-10 * rconv + cases.BLK_K * EPS * norm_u), (conv, rconv)
+    check_jump_criterion(dev, ref, 2)
 
 
 # ---- what is refused ---------------------------------------------------------------------------------------------------------------
@@ -331,31 +216,14 @@ def test_level_entry_point_refuses_bad_arguments():
     """mgrit_hip_level_burgers2d through raw ctypes: negative codes with a message, and what follows from the level's kind"""
     assert torch.cuda.is_available()
     from pymgrit_amd.core import hip_lib
-    lib = hip_lib.load()
-    EINVAL, EUNSUPPORTED = -1, -4
-    bg, cfg, msg = lib.mgrit_hip_level_burgers2d, lib.mgrit_hip_block_solve_config, lib.mgrit_hip_last_error
-    eng = C.c_void_p()
-    assert lib.mgrit_hip_create(C.byref(eng), 3, C.c_void_p(torch.cuda.current_stream().cuda_stream)) == 0
-    try:
-        t9 = np.ascontiguousarray(np.linspace(0.0, 0.01, 9))
-        tp, null = C.c_void_p(t9.ctypes.data), C.c_void_p(0)
-        ok = (20, 800, 256.0, 8.0, 0.1)      # nx, ld, 1 / dx^2, 1 / (2 dx), nu
-        assert bg(None, 0, 9, tp, *ok) < 0 and bg(eng, 5, 9, tp, *ok) < 0 and bg(eng, -1, 9, tp, *ok) < 0
-        assert bg(eng, 0, 9, tp, 3, 32, 256.0, 8.0, 0.1) == EUNSUPPORTED and b"Burgers grid" in msg()
-        assert bg(eng, 0, 9, tp, 2049, 2 * 2049 * 2049 + 14, 256.0, 8.0, 0.1) == EUNSUPPORTED and b"Burgers grid" in msg()
-        assert bg(eng, 0, 9, tp, 20, 400, 256.0, 8.0, 0.1) == EINVAL and b"2*nx*nx" in msg()      # one plane's worth
-        assert bg(eng, 0, 9, tp, 20, 808, 256.0, 8.0, 0.1) == EINVAL                                # not a multiple of 16
-        for bad in ((20, 800, 256.0, 8.0, 0.0), (20, 800, 256.0, 8.0, -0.1), (20, 800, 256.0, 8.0, float("nan")), (20, 800, 256.0, 8.0, float("inf")),
-                    (20, 800, 0.0, 8.0, 0.1), (20, 800, 256.0, 0.0, 0.1), (20, 800, 256.0, float("inf"), 0.1)):
-            assert bg(eng, 0, 9, tp, *bad) == EINVAL and b"Burgers parameters" in msg(), bad
-        assert bg(eng, 0, 9, null, *ok) == EINVAL and bg(eng, 0, -1, tp, *ok) == EINVAL
-        assert bg(eng, 0, 9, tp, *ok) == 0 and bg(eng, 1, 9, tp, *ok) == 0
-        assert bg(eng, 0, 9, tp, *ok) < 0 and b"already" in msg()                # already described
-        # non-linear Phi: no time-parallel forward solve (r > 0 refused, the rule r < 0 leaves it step by step)
-        assert cfg(eng, 1, 4, 1, 0, null, null) == EUNSUPPORTED
-        assert cfg(eng, 1, -1, 1, 0, null, null) == 0
-        # no spatial transfer joins two such levels; the copy does
-        assert lib.mgrit_hip_level_transfer(eng, 0, hip_lib.TRANSFER_PERIODIC2D) == EUNSUPPORTED
+    ok = (20, 800, 256.0, 8.0, 0.1)      # nx, ld, 1 / dx^2, 1 / (2 dx), nu
+
+    def transfers(lib, eng, fn, tp, msg):      # no spatial transfer joins two such levels; the copy does
+        assert lib.mgrit_hip_level_transfer(eng, 0, hip_lib.TRANSFER_PERIODIC2D) == -4
         assert lib.mgrit_hip_level_transfer(eng, 0, hip_lib.TRANSFER_COPY) == 0
-    finally:
-        assert lib.mgrit_hip_destroy(eng) == 0
+    check_level_entry_point(
+        "mgrit_hip_level_burgers2d", 3, 5, 0.01, ok, small=(3, 32) + ok[2:], large=(2049, 2 * 2049 * 2049 + 14) + ok[2:],
+        short=(20, 400) + ok[2:], odd=(20, 808) + ok[2:],      # one plane's worth; not a multiple of 16
+        bad=((20, 800, 256.0, 8.0, 0.0), (20, 800, 256.0, 8.0, -0.1), (20, 800, 256.0, 8.0, float("nan")), (20, 800, 256.0, 8.0, float("inf")),
+             (20, 800, 0.0, 8.0, 0.1), (20, 800, 256.0, 0.0, 0.1), (20, 800, 256.0, float("inf"), 0.1)),
+        grid_msg=b"Burgers grid", ld_msg=b"2*nx*nx", bad_msg=b"Burgers parameters", describe=[(0, ok), (1, ok)], then=transfers)

@@ -4,7 +4,7 @@ show here; tests/test_hip_cahn_hilliard_reference.py holds the device path again
 tests/cahn_hilliard_reference.py with the machinery of this file. Then solves, the jump criterion, a spatially coarsened hierarchy,
 the mass, and everything that is refused.
 
-Tolerances, none measured on the device (test_cahn_hilliard_cpu.py derives C(nx) = 4 nx + 36 and bnorm):
+Tolerances, none measured on the device (cahn_hilliard_reference.py derives C(nx) = 4 nx + 36 and bnorm):
   per Phi, one evaluation:          norm_F(error) <= C(nx) EPS bnorm,   bnorm = norm_F(u) + d2max norm_F(|u|^3 + (1 + s) |u|) of the
                                     input rows, d2max = max over the modes of dt mu / (1 + dt (eps^2 mu^2 + s mu)) at the level's LARGEST
                                     dt (D2 grows with dt)
@@ -20,177 +20,22 @@ absrow(A) = 1 + dt (64 eps^2 / dx^4 + 8 s / dx^2) = 1 + 4.6e4 dt stays near 25 a
 range in which the reference certifies its own error (cahn_hilliard_reference.py), while D2 reaches 0.09 -- the w path carries a tenth
 of the result, six orders above the tolerances.
 """
-import collections
-import ctypes as C
 import types
 
 import numpy as np
 import pytest
 
 import cases
-from periodic2d_sweeps import (ALL_SWEEPS, STORED_STATE_SWEEPS, compare as _compare, distinct_steps as _distinct_steps, host_state as _host_state,
-                               intervals as _intervals, lists as _lists, report as _report, row_norm as _row_norm, run_sweeps,
-                               set_states as _set_states, tol, uniform as _uniform)
-from test_cahn_hilliard_cpu import EPS, b_norm, c_of, d2max
+from cahn_hilliard_reference import b_norm, c_of
+from cahn_hilliard_cases import (BOUNDS, RAGGED_GRIDS, T_SWEEP, ch_pair as _pair, check_constant_rows, check_one_phi_at_larger_grids, check_several_step_sizes,
+                                 check_size_edges, check_split_at_the_batch_cap)
+from periodic2d_sweeps import (ALL_SWEEPS, check_every_sweep_twice, check_history, check_level_entry_point, intervals as _intervals, report as _report,
+                               row_norm as _row_norm, run_sweeps, uniform as _uniform)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-T_SWEEP = 0.002     # sweeps: nt = 17 / 9 / 5 on [0, T_SWEEP], coarsening factor 2 -- every Phi of a relaxation acts on a stored state
-RAGGED = np.concatenate(([0.0], np.cumsum(1e-4 * np.array([1, 1, 1.5, .5, 2, 1, 1, .75, 1, 1, 1, 1.25, 3, 1, 1, 1]))))   # the grid of
-RAGGED_GRIDS = {"by2_3lvl": [RAGGED, RAGGED[::2], RAGGED[::4]], "by4_2lvl": [RAGGED, RAGGED[::4]]}                       # the Allen-Cahn reference test
-H = 2.0 ** -17      # every t_k = k H and every difference is exact: one bit pattern of dt
-
-
-def _host_class():
-    from pymgrit_amd import CahnHilliard
-
-    class HostCahnHilliard(CahnHilliard):     # overriding step sends the hierarchy to the plugin path
-        def step(self, u_start, t_start, t_stop):
-            return super().step(u_start, t_start, t_stop)
-    return HostCahnHilliard
-
-
-def _reference_class():
-    from cahn_hilliard_reference import ReferenceCahnHilliard
-    return ReferenceCahnHilliard
-
-
-# the other side of a comparison: its class, and the per-Phi allowance in units of EPS bnorm beyond the device's own C(nx)
-SIDES = {"host": (_host_class, lambda nx: c_of(nx)), "reference": (_reference_class, lambda nx: 1)}
-
-
-def _app_args(nx, **over):
-    args = dict(nx=nx, L=nx / 16.0, eps=0.1, stab=2.0)
-    args.update(over)
-    return args
-
-
-def _pair(side, nxs, grids, transfer=None, app=None, **opts):
-    """(device Mgrit, plugin Mgrit over the side's class) on the same hierarchy; nxs: one nx, or one per level (on one square: L is the
-    finest level's nx / 16); app: eps, stab, mean, amplitude other than this file's"""
-    from pymgrit_amd import CahnHilliard, Mgrit
-    opts.setdefault("nested_iteration", False)
-    nxs = [nxs] * len(grids) if np.isscalar(nxs) else list(nxs)
-    if transfer is not None:
-        opts["transfer"] = transfer
-    app = dict(app or {}, L=nxs[0] / 16.0)
-    dev = Mgrit([CahnHilliard(**_app_args(nx, **app), **g) for nx, g in zip(nxs, grids)], logging_lvl=30, **opts)
-    other = Mgrit([SIDES[side][0]()(**_app_args(nx, **app), **g) for nx, g in zip(nxs, grids)], logging_lvl=30, **opts)
-    assert type(dev.backend).__name__ == "HipBackend" and type(other.backend).__name__ == "PluginBackend"
-    for a, b in zip(dev.t, other.t):
-        assert np.array_equal(a, b)
-    other.side = side
-    return dev, other
-
-
-def _random_states(host, seed):
-    rng = np.random.default_rng(seed)
-    return {(name, lvl): rng.uniform(-1.0, 1.0, size=(len(lst), host.problem[lvl].nx ** 2))
-            for lvl in range(host.lvl_max) for name, lst in _lists(host, lvl)}
-
-
-def _phi_term(host, app, rows, dt):
-    """the device's evaluation and the other side's: (C(nx) + the side's units) EPS bnorm"""
-    return (c_of(app.nx) + SIDES[host.side][1](app.nx)) * EPS * b_norm(app, rows, dt)
-
-
-def _lip(app, dt, rows):
-    R = float(np.abs(rows).max())
-    return 1.0 + d2max(app, dt) * max(1.0 + app.stab, abs(3.0 * R * R - (1.0 + app.stab)))
-
-
-# fas_residual: the coarse level's Phi acts on the restricted rows of the fine u (full weighting has non-negative weights that sum to 1:
-# values stay in [-1, 1], a row norm does not grow beyond the fine row's)
-BOUNDS = types.SimpleNamespace(random_states=_random_states, phi_term=_phi_term, lip=_lip, values_per_state=lambda app: app.nx * app.nx,
-                               coarse_rows=lambda host, st, lvl: _host_state(host, "v", lvl + 1), weight_in_key=False)
-
-
-def _tol(host, lvl, rows):
-    return tol(BOUNDS, host, lvl, rows)
-
-
-# ---- the cases, shared with test_hip_cahn_hilliard_reference.py ---------------------------------------------------------------------
-def check_size_edges(side, nx):
-    """every sweep with weight_c = 1; C-relaxation, the one sweep the weight enters, with 1.3 as well"""
-    record = {}
-    dev, host = _pair(side, nx, _uniform((17, 9, 5), T_SWEEP), weight_c=1.0)
-    run_sweeps(dev, host, BOUNDS, 1.0, 100 * nx, ALL_SWEEPS, record=record)
-    dev, host = _pair(side, nx, _uniform((17, 9, 5), T_SWEEP), weight_c=1.3)
-    run_sweeps(dev, host, BOUNDS, 1.3, 100 * nx + 50, ("c_relax",), record=record)
-    _report(f"size_edges[{side},nx={nx}]", record)
-
-
-def check_several_step_sizes(side, grid, nx):
-    record = {}
-    for w in (1.0, 1.3):
-        dev, host = _pair(side, nx, _intervals(RAGGED_GRIDS[grid]), weight_c=w)
-        for t in dev.t:
-            assert _distinct_steps(t) >= 3 and len(set(np.round(np.diff(t) / 1e-4, 6))) >= 3, np.diff(t)
-        if grid == "by4_2lvl":      # the three F-points of one interval do not share one pair of D tables
-            assert sum(len(set(np.round(np.diff(dev.t[0][a:a + 4]) / 1e-4, 6))) >= 2 for a in range(0, 16, 4)) >= 2
-        run_sweeps(dev, host, BOUNDS, w, 500 * nx + (3 if w != 1.0 else 0), ALL_SWEEPS if w == 1.0 else ("c_relax",), record=record)
-    _report(f"step_sizes[{side},{grid},nx={nx}]", record)
-
-
-def check_split_at_the_batch_cap(side):
-    """2051 points with the exact step 2^-17: 1025 F-points and 1025 relaxed C-points, each ONE dt group -- a state owns two work slab
-    items through the first two products, so a launch holds 512 states: batches of 512, 512 and 1"""
-    nx, w = 8, 1.3
-    t = H * np.arange(2051.0)
-    dev, host = _pair(side, nx, _intervals([t, t[::2]]), weight_c=w)
-    t = np.asarray(dev.t[0])
-    assert len(t) == 2051 and len(dev.t[1]) == 1026
-    for pts in (np.arange(1, len(t), 2), np.arange(2, len(t), 2)):      # F-points, relaxed C-points
-        groups = sorted(collections.Counter((t[pts] - t[pts - 1]).view(np.int64).tolist()).values())
-        assert groups == [1025] and 1025 > 2 * 512, groups
-    record = run_sweeps(dev, host, BOUNDS, w, 77, STORED_STATE_SWEEPS, levels=[0])
-    _report(f"batches[{side},dyadic_2051]", record)
-
-
-def check_one_phi_at_larger_grids(side, nx):
-    dev, host = _pair(side, nx, _uniform((5, 3), 2.0 ** -9))      # (steps of 2^-11, exact)
-    st = _random_states(host, nx)
-    _set_states(dev, host, st)
-    dev.f_relax(0); host.f_relax(0)
-    allowed = _tol(host, 0, st[("u", 0)]) + 8 * EPS * 3 * _row_norm(*st.values())
-    worst = _compare(dev, host, 0, allowed, "f_relax")
-    print(f"RATIO larger_grids[{side},nx={nx}] f_relax: worst error/allowed {worst / allowed:.4f}")
-
-
-def check_constant_rows(side):
-    """u = 0, +0.5, -0.5: w is constant, only mode (0, 0) is non-zero, D1 = 1 and D2 = 0 there: Phi(u) = u. Zeros bit for bit"""
-    nx = 33
-    dev, host = _pair(side, nx, _uniform((17, 9, 5), T_SWEEP))
-    st = _random_states(host, 5)
-    const = np.array([0.0, 0.5, -0.5])[(np.arange(17) // 2) % 3]          # the C-point 2 k and the F-point behind it: the same constant
-    st[("u", 0)] = np.repeat(const[:, None], nx * nx, axis=1)
-    st[("u", 0)][1::2] = 0.25                                              # (what F-relaxation has to overwrite)
-    _set_states(dev, host, st)
-    dev.f_relax(0); host.f_relax(0)
-    allowed = _tol(host, 0, st[("u", 0)][0::2]) + 8 * EPS * 3 * _row_norm(*st.values())
-    worst = _compare(dev, host, 0, allowed, "f_relax, constant rows")
-    got = dev.backend.natural("u", 0)
-    err = float(np.max(np.linalg.norm(got - const[:, None], axis=1)))
-    print(f"RATIO constants[{side}] f_relax: worst error/allowed {max(worst, err) / allowed:.4f}")
-    assert err <= allowed, (err, allowed)
-    for i in np.flatnonzero(const == 0.0):
-        assert np.array_equal(got[i], np.zeros(nx * nx)), i
-
-
-def check_history(dev, host, what, iterations):
-    conv, hconv = np.asarray(dev.solve()["conv"]), np.asarray(host.solve()["conv"])
-    u = dev.backend.natural("u", 0)
-    norm_u = cases.spacetime_norm(u)
-    assert len(conv) == len(hconv) == iterations, (conv, hconv)
-    dev_host = np.abs(conv - hconv)
-    print(f"RATIO {what} conv: largest deviation {np.max(dev_host) / (EPS * norm_u):.2f} units of eps*norm(u) "
-          f"(allowed {cases.BLK_K} beyond 1e-10 relative)")
-    assert np.all(dev_host <= 1e-10 * hconv + cases.BLK_K * EPS * norm_u), (conv, hconv)
-    last = _host_state(host, "u", 0)[-1]
-    print(f"RATIO {what} last state: relative deviation {np.abs(u[-1] - last).max() / np.abs(last).max():.3e}")
-    assert np.abs(u[-1] - last).max() <= 1e-9 * np.abs(last).max()
-    return u
+EPS = cases.EPS
 
 
 # ---- against the host step ---------------------------------------------------------------------------------------------------------
@@ -229,19 +74,7 @@ def test_a_sweep_run_twice_gives_the_same_bits(nx):
     """a race in the staging of the two items or in the combine product's two passes through LDS would show here"""
     assert torch.cuda.is_available()
     dev, host = _pair("host", nx, _uniform((17, 9, 5), T_SWEEP), weight_c=1.3)
-    st = _random_states(host, nx)
-    top = dev.lvl_max - 1
-    sweeps = [("f_relax", lambda l=l: dev.f_relax(l)) for l in range(top)] + [("c_relax", lambda l=l: dev.c_relax(l)) for l in range(top)] + \
-             [("fas_residual", lambda l=l: dev.fas_residual(l)) for l in range(top)] + [("forward_solve", lambda: dev.forward_solve(top))]
-    for name, run in sweeps:
-        out = []
-        for rep in range(2):
-            for (which, lvl), val in st.items():
-                dev.backend.set_natural(which, lvl, val)
-            run()
-            out.append({key: dev.backend.natural(*key) for key in st})
-        for key in st:
-            assert np.array_equal(out[0][key], out[1][key]), (name, key)
+    check_every_sweep_twice(dev, BOUNDS["host"].random_states(host, nx))
 
 
 @pytest.mark.parametrize("cycle", ["V", "F"])
@@ -268,7 +101,7 @@ def test_spatially_coarsened_hierarchy():
     for w in (1.0, 1.3):
         dev, host = _pair("host", (16, 8), _uniform((17, 9), T_SWEEP), transfer=[GridTransferCahnHilliard()], weight_c=w)
         assert dev.backend._device_transfer(0) and dev.problem[1].dx == 2 * dev.problem[0].dx
-        run_sweeps(dev, host, BOUNDS, w, 900 + (3 if w != 1.0 else 0), ALL_SWEEPS, record=record)
+        run_sweeps(dev, host, BOUNDS["host"], w, 900 + (3 if w != 1.0 else 0), ALL_SWEEPS, record=record)
     _report("coarsened[16->8]", record)
     dev, host = _pair("host", (16, 8), _uniform((17, 9), 0.01), transfer=[GridTransferCahnHilliard()], app=dict(eps=0.05), max_iter=3, tol=0.0)
     check_history(dev, host, "solve[16->8]", 3)
@@ -339,40 +172,26 @@ def test_level_entry_point_refuses_bad_arguments():
     """mgrit_hip_level_cahnhilliard2d through raw ctypes: negative codes with a message, and what follows from the level's kind"""
     assert torch.cuda.is_available()
     from pymgrit_amd.core import hip_lib
-    lib = hip_lib.load()
     EINVAL, EUNSUPPORTED = -1, -4
-    ch, ac, cfg, msg = lib.mgrit_hip_level_cahnhilliard2d, lib.mgrit_hip_level_allencahn2d, lib.mgrit_hip_block_solve_config, lib.mgrit_hip_last_error
-    eng = C.c_void_p()
-    assert lib.mgrit_hip_create(C.byref(eng), 5, C.c_void_p(torch.cuda.current_stream().cuda_stream)) == 0
-    try:
-        t9 = np.ascontiguousarray(np.linspace(0.0, 1e-3, 9))
-        tp, null = C.c_void_p(t9.ctypes.data), C.c_void_p(0)
-        ok = (20, 400, 400.0, 0.0025, 2.0)
-        assert ch(None, 0, 9, tp, *ok) < 0 and ch(eng, 6, 9, tp, *ok) < 0 and ch(eng, -1, 9, tp, *ok) < 0
-        assert ch(eng, 0, 9, tp, 3, 16, 9.0, 0.0025, 2.0) == EUNSUPPORTED and b"Cahn-Hilliard grid" in msg()
-        assert ch(eng, 0, 9, tp, 2049, 2049 * 2049 + 15, 400.0, 0.0025, 2.0) == EUNSUPPORTED
-        assert ch(eng, 0, 9, tp, 20, 384, 400.0, 0.0025, 2.0) == EINVAL and b"nx*nx" in msg()      # shorter than a state
-        assert ch(eng, 0, 9, tp, 20, 408, 400.0, 0.0025, 2.0) == EINVAL                            # not a multiple of 16
-        for bad in ((20, 400, 0.0, 0.0025, 2.0), (20, 400, 400.0, 0.0, 2.0), (20, 400, 400.0, -1.0, 2.0), (20, 400, 400.0, 0.0025, -0.5),
-                    (20, 400, float("inf"), 0.0025, 2.0), (20, 400, 400.0, float("nan"), 2.0), (20, 400, 400.0, float("inf"), 2.0),
-                    (20, 400, 400.0, 0.0025, float("nan")), (20, 400, 400.0, 0.0025, float("inf"))):
-            assert ch(eng, 0, 9, tp, *bad) == EINVAL and b"bad Cahn-Hilliard parameters" in msg(), bad
-        assert ch(eng, 0, 9, null, *ok) == EINVAL and ch(eng, 0, -1, tp, *ok) == EINVAL
-        assert ch(eng, 0, 9, tp, *ok) == 0 and ch(eng, 1, 9, tp, 10, 112, 100.0, 0.0025, 0.0) == 0      # (stab = 0 is allowed)
-        assert ch(eng, 0, 9, tp, *ok) < 0 and b"already" in msg()                # already described
-        # non-linear Phi: no time-parallel forward solve (r > 0 refused, the rule r < 0 leaves it step by step)
-        assert cfg(eng, 1, 4, 1, 0, null, null) == EUNSUPPORTED
-        assert cfg(eng, 1, -1, 1, 0, null, null) == 0
+    ok = (20, 400, 400.0, 0.0025, 2.0)
+
+    def transfers(lib, eng, ch, tp, msg):
         # the periodic transfer joins two Cahn-Hilliard levels with n_fine = 2 n_coarse, and the copy joins equal ones
         assert lib.mgrit_hip_level_transfer(eng, 0, hip_lib.TRANSFER_PERIODIC2D) == 0
         assert lib.mgrit_hip_level_transfer(eng, 0, hip_lib.TRANSFER_COPY) == EINVAL and b"equal DOFs" in msg()
         assert ch(eng, 2, 9, tp, 12, 144, 144.0, 0.0025, 2.0) == 0
         assert lib.mgrit_hip_level_transfer(eng, 1, hip_lib.TRANSFER_PERIODIC2D) == EINVAL and b"n_fine = 2*n_coarse" in msg()
         # never a Cahn-Hilliard level with an Allen-Cahn level, in either order: the refusal of the other pairings, verbatim
-        assert ac(eng, 3, 9, tp, 8, 64, 64.0, 625.0, 2) == 0 and ch(eng, 4, 9, tp, 4, 16, 16.0, 0.0025, 2.0) == 0
+        assert lib.mgrit_hip_level_allencahn2d(eng, 3, 9, tp, 8, 64, 64.0, 625.0, 2) == 0 and ch(eng, 4, 9, tp, 4, 16, 16.0, 0.0025, 2.0) == 0
         for lvl in (2, 3):      # Cahn-Hilliard 12 over Allen-Cahn 8 (the kind is looked at first), Allen-Cahn 8 over Cahn-Hilliard 4
             assert lib.mgrit_hip_level_transfer(eng, lvl, hip_lib.TRANSFER_PERIODIC2D) == EUNSUPPORTED
             assert b"the periodic 2-D transfer joins two Allen-Cahn levels" in msg()
         assert lib.mgrit_hip_level_transfer(eng, 2, hip_lib.TRANSFER_HEAT2D) == EUNSUPPORTED
-    finally:
-        assert lib.mgrit_hip_destroy(eng) == 0
+    check_level_entry_point(
+        "mgrit_hip_level_cahnhilliard2d", 5, 6, 1e-3, ok, small=(3, 16, 9.0, 0.0025, 2.0), large=(2049, 2049 * 2049 + 15) + ok[2:], large_says_grid=False,
+        short=(20, 384) + ok[2:], odd=(20, 408) + ok[2:],      # shorter than a state; not a multiple of 16
+        bad=((20, 400, 0.0, 0.0025, 2.0), (20, 400, 400.0, 0.0, 2.0), (20, 400, 400.0, -1.0, 2.0), (20, 400, 400.0, 0.0025, -0.5),
+             (20, 400, float("inf"), 0.0025, 2.0), (20, 400, 400.0, float("nan"), 2.0), (20, 400, 400.0, float("inf"), 2.0),
+             (20, 400, 400.0, 0.0025, float("nan")), (20, 400, 400.0, 0.0025, float("inf"))),
+        grid_msg=b"Cahn-Hilliard grid", ld_msg=b"nx*nx", bad_msg=b"bad Cahn-Hilliard parameters",
+        describe=[(0, ok), (1, (10, 112, 100.0, 0.0025, 0.0))], then=transfers)      # (stab = 0 is allowed)

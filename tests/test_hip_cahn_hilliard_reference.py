@@ -2,7 +2,7 @@
 SAME hierarchy on the plugin path over ``ReferenceCahnHilliard`` (tests/cahn_hilliard_reference.py), whose step is a transform-free solve
 of (I + dt (eps^2 Lh^2 - s Lh)) x = u + dt Lh w refined in long double. It shares neither the Hartley table nor the eigenvalues nor the
 D tables nor the code of w with the device or the host step, so a mistake common to those two (test_hip_cahn_hilliard.py compares exactly
-those two) shows here. The cases and the machinery are those of test_hip_cahn_hilliard.py, whose docstring states the tolerances; here
+those two) shows here. The cases are those of test_hip_cahn_hilliard.py (tests/cahn_hilliard_cases.py), whose docstring states the tolerances; here
 a Phi is allowed C(nx) EPS bnorm for the device and EPS bnorm for the reference, which asserts its own forward error bound on every call.
 
   a. the size edges of the tile product: nx = 4 (smallest grid), 33 / 97 (just past a K step of 32), 96 (KP = 96 < P = 128), 129 (just
@@ -15,8 +15,9 @@ a Phi is allowed C(nx) EPS bnorm for the device and EPS bnorm for the reference,
 """
 import pytest
 
-from test_hip_cahn_hilliard import (RAGGED_GRIDS, T_SWEEP, _pair, _uniform, check_constant_rows, check_history, check_one_phi_at_larger_grids,
-                                    check_several_step_sizes, check_size_edges, check_split_at_the_batch_cap)
+from cahn_hilliard_cases import (RAGGED_GRIDS, T_SWEEP, ch_pair as _pair, check_constant_rows, check_one_phi_at_larger_grids, check_several_step_sizes,
+                                 check_size_edges, check_split_at_the_batch_cap)
+from periodic2d_sweeps import check_history, intervals as _intervals, uniform as _uniform
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -54,7 +55,6 @@ def test_constant_rows_are_returned():
 def test_solve_matches_the_reference_hierarchy():
     """three iterations from the initial state on the ragged grid (several D tables per sweep): histories by the project's rule"""
     assert torch.cuda.is_available()
-    from test_hip_cahn_hilliard import _intervals
     dev, ref = _pair("reference", 20, _intervals(RAGGED_GRIDS["by2_3lvl"]), max_iter=3, tol=0.0)
     check_history(dev, ref, "solve[reference,ragged]", 3)
     dev, ref = _pair("reference", 16, _uniform((17, 9, 5), T_SWEEP), max_iter=3, tol=0.0, cycle_type="F")

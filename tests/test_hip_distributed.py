@@ -4,7 +4,7 @@ same schedule runs over RCCL). Sharded runs must equal the single-rank GPU run b
 import numpy as np
 import pytest
 
-from test_distributed import launch
+from dist_cases import launch
 
 pytestmark = pytest.mark.gpu
 

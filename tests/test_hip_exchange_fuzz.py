@@ -12,7 +12,6 @@ import pytest
 import cases
 from fuzz_cases import N_CASES, SEED0, random_case
 from mock_comm import run_ranks
-from test_exchange_fuzz import uniform
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -67,7 +66,7 @@ def test_hip_ranks_equal_host_ranks(seed):
         assert np.allclose(conv, conv_h, rtol=RTOL, atol=floor), (tag, rank, conv, conv_h)
         scale = max(float(np.max(np.abs(vals_h))) if len(vals_h) else 0.0, 1e-300)
         assert len(vals) == len(vals_h) and all(np.max(np.abs(a - b)) <= RTOL * scale for a, b in zip(vals, vals_h)), (tag, rank)
-    if opts["conv_crit"] in (0, 1) and uniform(grids):
+    if opts["conv_crit"] in (0, 1) and cases.uniform_coarsening(grids):
         one = Mgrit(heat(grids, nx, True), logging_lvl=30, **opts)
         one.solve()
         assert np.array_equal(one.conv, got[0][0]), (tag, one.conv, got[0][0])

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import cases
-from test_hip_parity import _need_gpu, assert_state_equal, heat_problem, make_pair, randomize
+from parity_cases import need_gpu as _need_gpu, assert_state_equal, heat_problem, make_pair, randomize
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")

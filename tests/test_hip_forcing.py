@@ -11,19 +11,13 @@ torch = pytest.importorskip("torch")
 RESTATED = cases.load_json("solve_restated.json")
 
 
-def problem(nx, grids):
-    from pymgrit_amd import Heat1D
-    return [Heat1D(x_start=0, x_end=1, nx=nx, a=1, init_cond=cases.init_cond, rhs=cases.general_rhs, t_interval=np.asarray(t))
-            for t in grids]
-
-
 def test_general_forcing_solve(oracle):
     if not torch.cuda.is_available():
         pytest.fail("GPU test selected but no GPU visible")
     from pymgrit_amd import Mgrit
     c = cases.restated_cases()["superlu_general_forcing"]
     grids = [s["t"] for s in c["levels"]]
-    prob = problem(65, grids)
+    prob = cases.general_forcing_problem(65, grids)
     assert prob[0].device_stepper()["forcing_rows"] is not None          # detected as not separable
     mg = Mgrit(prob, logging_lvl=30, **c["opts"])
     assert mg.backend.name == "hip"
@@ -46,7 +40,7 @@ def test_general_forcing_wide_and_sweeps(oracle, nx, cycle):
         pytest.fail("GPU test selected but no GPU visible")
     from pymgrit_amd import Mgrit
     grids = [cases.lin(2, 65), cases.lin(2, 17), cases.lin(2, 5)]
-    mg = Mgrit(problem(nx, grids), logging_lvl=30, max_iter=3, tol=0.0, cycle_type=cycle)
+    mg = Mgrit(cases.general_forcing_problem(nx, grids), logging_lvl=30, max_iter=3, tol=0.0, cycle_type=cycle)
     conv = mg.solve()["conv"]
     op = oracle.OracleProblem([cases.heat_level_spec_general(nx, t) for t in grids], variant=1, max_iter=3, tol=0.0,
                               cycle_type=cycle)
@@ -67,5 +61,5 @@ def test_replaced_rhs_is_used():
     for p in a:
         p.rhs = cases.general_rhs
     conv_a = Mgrit(a, logging_lvl=30, max_iter=3, tol=0.0).solve()["conv"]
-    conv_b = Mgrit(problem(65, grids), logging_lvl=30, max_iter=3, tol=0.0).solve()["conv"]
+    conv_b = Mgrit(cases.general_forcing_problem(65, grids), logging_lvl=30, max_iter=3, tol=0.0).solve()["conv"]
     assert np.array_equal(conv_a, conv_b)

@@ -71,7 +71,7 @@ def random_case(seed):
 
 
 def run_case(oracle, seed):
-    from test_hip_parity import make_pair
+    from parity_cases import make_pair
     kind, nx, grids, forcing, opts, transfer = random_case(seed)
     nested = opts.pop("nested_iteration")
     mg, op = make_pair(oracle, kind, nx, grids, transfer=transfer, forcing=forcing, nested_iteration=False, **opts)

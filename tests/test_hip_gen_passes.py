@@ -51,7 +51,7 @@ def test_general_passes_bit_identical_to_the_sweeps(case):
 
 def _by_hand(mg, op, lvl_pairs, top):
     """a cycle by hand: the general passes on the device, the reference's sweeps on the oracle"""
-    from test_hip_parity import assert_state_equal
+    from parity_cases import assert_state_equal
     be = mg.backend
     for lvl in lvl_pairs:
         iv = mg._gen_intervals(lvl)
@@ -90,7 +90,7 @@ def test_config5_scale_passes_bit_exact(oracle):
     """config 5's spatial sizes (8192 -> 4096 -> 2048 periodic points, 8 / 4 / 2 groups of lanes), short time grid"""
     if not torch.cuda.is_available():
         pytest.fail("GPU test selected but no GPU visible")
-    from test_hip_parity import randomize
+    from parity_cases import randomize
     from pymgrit_amd import Advection1D, GridTransferAdvection, Mgrit
     t0 = np.linspace(0, 2.0 * 64 / 32768, 65)
     ts, nxs = [t0, t0[::2], t0[::4]], [8193, 4097, 2049]
@@ -109,7 +109,7 @@ def test_periodic_passes_with_ragged_coarse_sizes(oracle, nxs):
     zero there). 100 -> 50, 20 -> 10, 4000 -> 2000 -> 1000 -> 500, 2064 -> 1032 (two groups), 40 -> 20 -> 10 unknowns"""
     if not torch.cuda.is_available():
         pytest.fail("GPU test selected but no GPU visible")
-    from test_hip_parity import randomize
+    from parity_cases import randomize
     from pymgrit_amd import Advection1D, GridTransferAdvection, Mgrit
     t0 = np.linspace(0, 0.05, 2 ** (len(nxs) + 2) + 1)
     ts = [t0[::2 ** k] for k in range(len(nxs))]
@@ -127,7 +127,7 @@ def test_heat_full_weighting_passes_bit_exact(oracle, nxs):
     unknowns: the neighbour values of the restriction cross lanes and waves), separable forcing"""
     if not torch.cuda.is_available():
         pytest.fail("GPU test selected but no GPU visible")
-    from test_hip_parity import randomize
+    from parity_cases import randomize
     from pymgrit_amd import GridTransferHeat, Heat1D, Mgrit
     t0 = cases.lin(0.05, 33)
     ts = [t0[::2 ** k] for k in range(len(nxs))]

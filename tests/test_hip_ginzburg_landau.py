@@ -35,145 +35,74 @@ Tolerances, nothing in them measured on the device (test_ginzburg_landau_cpu.py 
 Every comparison covers all rows of a list. Each sweep prints its worst error / allowed ("RATIO" lines); the MI355X values are in
 DESIGN.md 3.15.
 """
-import collections
-import ctypes as C
 import types
 
 import numpy as np
 import pytest
 
 import cases
-from ginzburg_landau_reference import ALLOWANCE, LD, ReferenceGinzburgLandau2D
-from periodic2d_sweeps import (ALL_SWEEPS, STORED_STATE_SWEEPS, compare as _compare, distinct_steps as _distinct_steps, intervals as _intervals,
-                               lists as _lists, report as _report, row_norm as _row_norm, run_sweeps, set_states as _set_states, tol,
+from ginzburg_landau_reference import LD
+from periodic2d_kinds import KINDS, dyadic, gl_coef as _coef, gl_majorant as _majorant
+from periodic2d_sweeps import (ALL_SWEEPS, STORED_STATE_SWEEPS, both_weights, bounds_of, check_history, check_jump_criterion, check_level_0_twice,
+                               check_level_entry_point, check_one_phi, check_ragged, compare as _compare, dt_groups, f_relaxed_rows,
+                               intervals as _intervals, pair, report as _report, row_norm as _row_norm, run_sweeps, set_states as _set_states, tol,
                                uniform as _uniform)
-from test_hip_transfer2d import _fill, _one_step_size, _raw, solve as _solve
+from transfer2d_cases import fill as _fill, one_step_size as _one_step_size, raw as _raw, solve as _solve
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 EPS = cases.EPS
-B, CC = 1.5, -0.8
-T_SWEEP = 0.5
+KIND = KINDS["ginzburglandau"]
+B, CC = KIND.par(1)["b"], KIND.par(1)["c"]
+T_SWEEP = KIND.t_sweep(None)
+BOUNDS = {side: bounds_of("ginzburglandau", side) for side in ("host", "reference")}
 
 
-def _coef(nx):
-    return 4 * nx + 25      # C(nx) of test_ginzburg_landau_cpu.py, valid for rr sqrt(1 + b^2) <= 1 / 4
-
-
-def _host_class():
-    from pymgrit_amd import GinzburgLandau2D
-
-    class HostGinzburgLandau2D(GinzburgLandau2D):     # overriding step sends the hierarchy to the plugin path
-        def step(self, u_start, t_start, t_stop):
-            return super().step(u_start, t_start, t_stop)
-    return HostGinzburgLandau2D
-
-
-def _pair(nx, grids, side="host", par=None, per_phi_bounds=True, **opts):
+def _pair(nx, grids, side="host", per_phi_bounds=True, **opts):
     """(device Mgrit, plugin Mgrit over HostGinzburgLandau2D or ReferenceGinzburgLandau2D) on the same hierarchy. per_phi_bounds: the
     comparison uses the per-Phi tolerance, so every step must lie in the range C(nx) is derived for (the solve tests below compare
     residual histories by the rule of tests/cases.py instead)"""
-    from pymgrit_amd import GinzburgLandau2D, Mgrit
-    opts.setdefault("nested_iteration", False)
-    par = dict(b=B, c=CC, L=float(nx)) if par is None else par
-    cls = {"host": _host_class(), "reference": ReferenceGinzburgLandau2D}[side]
-    dev = Mgrit([GinzburgLandau2D(nx=nx, **par, **g) for g in grids], logging_lvl=30, **opts)
-    ref = Mgrit([cls(nx=nx, **par, **g) for g in grids], logging_lvl=30, **opts)
-    assert type(dev.backend).__name__ == "HipBackend" and type(ref.backend).__name__ == "PluginBackend"
-    for a, b, app in zip(dev.t, ref.t, ref.problem):
-        assert np.array_equal(a, b)
-        assert not per_phi_bounds or float(np.max(np.diff(a))) / app.dx ** 2 * np.sqrt(1.0 + app.b ** 2) <= 0.25
+    dev, ref = pair("ginzburglandau", nx, grids, side=side, **opts)
+    for t, app in zip(dev.t, ref.problem):
+        assert not per_phi_bounds or float(np.max(np.diff(t))) / app.dx ** 2 * np.sqrt(1.0 + app.b ** 2) <= 0.25
     return dev, ref
-
-
-def _random_states(ref, seed):
-    """per list and level [n_pts][2 nx^2], uniform in [-1, 1]"""
-    rng = np.random.default_rng(seed)
-    return {(name, lvl): rng.uniform(-1.0, 1.0, size=(len(lst), 2 * ref.problem[lvl].nx ** 2))
-            for lvl in range(ref.lvl_max) for name, lst in _lists(ref, lvl)}
-
-
-def _majorant(app, rows, dt):
-    """the largest row majorant over both planes (module docstring)"""
-    w = np.abs(np.atleast_2d(rows)).reshape(-1, 2, app.nx * app.nx)
-    x, y = w[:, 0], w[:, 1]
-    q = x * x + y * y
-    c = abs(app.c)
-    R = x + dt * (x + q * (x + c * y))
-    S = y + dt * (y + q * (c * x + y))
-    return float(np.sqrt(np.max(np.sum(R * R, axis=1) + np.sum(S * S, axis=1))))
-
-
-def _phi_term(app, rows, dt):
-    against_reference = isinstance(app, ReferenceGinzburgLandau2D)
-    return (_coef(app.nx) + ALLOWANCE if against_reference else 2 * _coef(app.nx)) * EPS * _majorant(app, rows, dt)
-
-
-def _lip(app, dt, rows):
-    w = np.atleast_2d(rows).reshape(-1, 2, app.nx * app.nx)
-    R2 = float(np.max(w[:, 0] ** 2 + w[:, 1] ** 2))
-    return 1.0 + dt * (1.0 + 3.0 * np.sqrt(1.0 + app.c ** 2) * R2 * (1.0 + 1e-6))
-
-
-BOUNDS = types.SimpleNamespace(random_states=_random_states, phi_term=lambda ref, app, rows, dt: _phi_term(app, rows, dt), lip=_lip,
-                               values_per_state=lambda app: 2 * app.nx ** 2, coarse_rows=lambda ref, st, lvl: st[("u", lvl)], weight_in_key=True)
-
-
-def _tol(ref, lvl, rows):
-    return tol(BOUNDS, ref, lvl, rows)
 
 
 # ---- a. every sweep at the size edges ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("nx,side", [(4, "host"), (33, "host"), (66, "host"), (97, "host"), (33, "reference")])
 def test_every_sweep_at_the_size_edges(nx, side):
     assert torch.cuda.is_available()
-    record = {}
-    for w, sweeps in ((1.0, ALL_SWEEPS), (1.3, ("c_relax",))):      # (the weight enters the C-relaxation only)
-        dev, ref = _pair(nx, _uniform((17, 9, 5), T_SWEEP), side=side, weight_c=w)
+
+    def check(dev):
         assert dev.problem[0].dx == 1.0
-        run_sweeps(dev, ref, BOUNDS, w, 100 * nx + (7 if w != 1.0 else 0), sweeps, record=record)
-    _report(f"size_edges[nx={nx},{side}]", record)
+    both_weights(lambda w: _pair(nx, _uniform((17, 9, 5), T_SWEEP), side=side, weight_c=w), BOUNDS[side], 100 * nx, 100 * nx + 7,
+                 f"size_edges[nx={nx},{side}]", check=check)
 
 
 @pytest.mark.parametrize("par", [dict(b=0.0, c=0.0), dict(b=-2.0, c=0.5)])
 def test_every_sweep_with_other_coefficients(par):
     """the real-coefficient limit (Db = 0: the cross product reduces to two scaled products) and a pair of the other signs"""
     assert torch.cuda.is_available()
-    nx, record = 33, {}
+    nx = 33
     dev, ref = _pair(nx, _uniform((17, 9, 5), 0.4), par=dict(L=float(nx), **par))
-    run_sweeps(dev, ref, BOUNDS, 1.0, 4242, ALL_SWEEPS, record=record)
+    record = run_sweeps(dev, ref, BOUNDS["host"], 1.0, 4242, ALL_SWEEPS)
     _report(f"coefficients[b={par['b']},c={par['c']}]", record)
 
 
 # ---- b. several step sizes per level -----------------------------------------------------------------------------------------------
-RAGGED = np.concatenate(([0.0], np.cumsum(np.array([1, 1, 1.5, .5, 2, 1, 1, .75, 1, 1, 1, 1.25, 3, 1, 1, 1]))))
-
-
-def _ragged(grid):
-    t = RAGGED * 2.0 ** -6      # 18 units: [0, 0.28]; at most 6.25 units = 0.098 per coarse step
-    return {"by2_3lvl": [t, t[::2], t[::4]], "by4_2lvl": [t, t[::4]]}[grid]
-
-
 @pytest.mark.parametrize("grid", ["by2_3lvl", "by4_2lvl"])
 def test_every_sweep_with_several_step_sizes_per_level(grid):
     assert torch.cuda.is_available()
-    nx, record = 33, {}
-    for w, sweeps in ((1.0, ALL_SWEEPS), (1.3, ("c_relax",))):
-        dev, ref = _pair(nx, _intervals(_ragged(grid)), weight_c=w)
-        for t in dev.t:
-            assert _distinct_steps(t) >= 3, np.diff(t)
-        if grid == "by4_2lvl":      # the three F-points of one interval do not share one table
-            assert sum(_distinct_steps(dev.t[0][a:a + 4]) >= 2 for a in range(0, 16, 4)) >= 2
-        run_sweeps(dev, ref, BOUNDS, w, 500 * nx + (3 if w != 1.0 else 0), sweeps, record=record)
-    _report(f"step_sizes[{grid}]", record)
+    nx = 33
+    both_weights(lambda w: _pair(nx, _intervals(KIND.ragged(nx)[grid]), weight_c=w), BOUNDS["host"], 500 * nx, 500 * nx + 3, f"step_sizes[{grid}]",
+                 check=lambda dev: check_ragged(dev, grid))
 
 
 # ---- c. dt groups larger than one launch -------------------------------------------------------------------------------------------
 def _dyadic(n_pts):
     """n_pts points with the exact step 2^-13 (every t_k = k 2^-13 and every difference is exact: one bit pattern of dt; [0, 0.26])"""
-    t = 2.0 ** -13 * np.arange(float(n_pts))
-    return [t, t[::2]]
+    return dyadic("ginzburglandau", n_pts)
 
 
 @pytest.mark.parametrize("states", [513, 1025])
@@ -182,12 +111,10 @@ def test_sweeps_of_more_than_one_launch(states):
     assert torch.cuda.is_available()
     nx, w = 9, 1.3
     dev, ref = _pair(nx, _intervals(_dyadic(2 * states + 1)), weight_c=w)
-    t = np.asarray(dev.t[0])
-    assert len(t) == 2 * states + 1 and len(dev.t[1]) == states + 1
-    for pts in (np.arange(1, len(t), 2), np.arange(2, len(t), 2)):      # F-points, relaxed C-points
-        groups = sorted(collections.Counter((t[pts] - t[pts - 1]).view(np.int64).tolist()).values())
+    assert len(dev.t[0]) == 2 * states + 1 and len(dev.t[1]) == states + 1
+    for groups in dt_groups(dev.t[0]):      # F-points, relaxed C-points
         assert groups == [states] and states % 512 == 1 and states > 1024 // 2, groups
-    record = run_sweeps(dev, ref, BOUNDS, w, 77, STORED_STATE_SWEEPS, levels=[0])
+    record = run_sweeps(dev, ref, BOUNDS["host"], w, 77, STORED_STATE_SWEEPS, levels=[0])
     _report(f"launches[{states} states]", record)
 
 
@@ -196,12 +123,7 @@ def test_one_phi_at_a_larger_grid():
     assert torch.cuda.is_available()
     nx = 129
     dev, ref = _pair(nx, _uniform((5, 3), 2.0 ** -3))      # (steps of 2^-5, exact)
-    st = _random_states(ref, nx)
-    _set_states(dev, ref, st)
-    dev.f_relax(0); ref.f_relax(0)
-    allowed = _tol(ref, 0, st[("u", 0)]) + 8 * EPS * 3 * _row_norm(*st.values())
-    worst = _compare(dev, ref, 0, allowed, "f_relax")
-    print(f"RATIO larger_grid[nx={nx}] f_relax: worst error/allowed {worst / allowed:.4f}")
+    check_one_phi(dev, ref, BOUNDS["host"], nx, f"larger_grid[nx={nx}]")
 
 
 # ---- e. known answers ------------------------------------------------------------------------------------------------------------------
@@ -216,7 +138,7 @@ def test_known_answers_on_the_device():
     dev, ref = _pair(nx, _uniform((17, 9, 5), T_SWEEP))
     app, n = ref.problem[0], nx * nx
     dt = float(dev.t[0][1] - dev.t[0][0])
-    st = _random_states(ref, 5)
+    st = BOUNDS["host"].random_states(ref, 5)
     const = np.concatenate((np.full(n, 0.75), np.full(n, -0.5)))
     i1, i2 = np.meshgrid(np.arange(nx), np.arange(nx), indexing="ij")
 
@@ -234,7 +156,7 @@ def test_known_answers_on_the_device():
     _set_states(dev, ref, st)
     dev.f_relax(0); ref.f_relax(0)
     slack = 8 * EPS * 3 * _row_norm(*st.values())
-    worst = _compare(dev, ref, 0, _tol(ref, 0, st[("u", 0)][0::2]) + slack, "f_relax, known answers")
+    worst = _compare(dev, ref, 0, tol(BOUNDS["host"], ref, 0, st[("u", 0)][0::2]) + slack, "f_relax, known answers")
     got = dev.backend.natural("u", 0)
     assert np.array_equal(got[1::8], np.zeros_like(got[1::8]))
     m = 0.75 ** 2 + 0.5 ** 2
@@ -256,17 +178,8 @@ def test_known_answers_on_the_device():
 # ---- f. the same bits ----------------------------------------------------------------------------------------------------------------
 def test_a_sweep_run_twice_gives_the_same_bits():
     assert torch.cuda.is_available()
-    nx = 33
-    dev, ref = _pair(nx, _uniform((17, 9, 5), T_SWEEP))
-    st = _random_states(ref, 21)
-    for sweep in ("f_relax", "c_relax"):
-        slabs = []
-        for _ in range(2):
-            _set_states(dev, ref, st)
-            getattr(dev, sweep)(0)
-            slabs.append(dev.backend.U[0].clone())
-        assert torch.equal(slabs[0], slabs[1]), sweep
-    assert not torch.equal(slabs[0][1], slabs[0][3])      # (rows of different states differ)
+    dev, ref = _pair(33, _uniform((17, 9, 5), T_SWEEP))
+    check_level_0_twice(dev, ref, BOUNDS["host"].random_states(ref, 21))
 
 
 def test_a_rows_bits_do_not_depend_on_its_launch():
@@ -277,15 +190,8 @@ def test_a_rows_bits_do_not_depend_on_its_launch():
     big, ref_big = _pair(nx, _intervals(_dyadic(2051)))
     small, ref_small = _pair(nx, _intervals(_dyadic(7)))
     state = np.random.default_rng(3).uniform(-1.0, 1.0, size=2 * nx * nx)
-    rows = {}
-    for name, dev, ref, at in (("small", small, ref_small, (0,)), ("big", big, ref_big, (0, 2 * 511, 2 * 512, 2 * 1024))):
-        st = _random_states(ref, 9)
-        for i in at:
-            st[("u", 0)][i] = state
-        _set_states(dev, ref, st)
-        dev.f_relax(0)
-        U = dev.backend.U[0]
-        rows[name] = [U[i + 1].clone() for i in at]
+    rows = {name: f_relaxed_rows(dev, ref, BOUNDS["host"].random_states(ref, 9), state, at)
+            for name, dev, ref, at in (("small", small, ref_small, (0,)), ("big", big, ref_big, (0, 2 * 511, 2 * 512, 2 * 1024)))}
     for r in rows["big"]:
         assert torch.equal(rows["small"][0], r)
     assert not torch.equal(rows["small"][0][:2 * nx * nx], torch.from_numpy(state).to(rows["small"][0].device))
@@ -382,28 +288,15 @@ def test_v_cycle_solve_matches_the_plugin_path():
     """from the initial guess on (nx = 12, L = 12, [0, 2], nt 17 / 9 / 5) to 1e-10: residual histories by the rule of tests/cases.py"""
     assert torch.cuda.is_available()
     dev, ref = _pair(12, _solve_grids(), cycle_type="V", max_iter=8, tol=1e-10, nested_iteration=True, **SOLVE)
-    conv, rconv = np.asarray(dev.solve()["conv"]), np.asarray(ref.solve()["conv"])
-    u = dev.backend.natural("u", 0)
-    norm_u = cases.spacetime_norm(u)
-    assert len(conv) == len(rconv) >= 2 and rconv[-1] < 1e-10 and conv[-1] < 1e-10, (conv, rconv)
-    dev_ref = np.abs(conv - rconv)
-    print(f"RATIO solve[V] conv ({len(conv)} iterations): largest deviation {np.max(dev_ref) / (EPS * norm_u):.2f} units of "
-          f"eps*norm(u) (allowed {cases.BLK_K} beyond 1e-10 relative)")
-    assert np.all(dev_ref <= 1e-10 * rconv + cases.BLK_K * EPS * norm_u), (conv, rconv)
-    last = np.asarray(ref.u[0][-1].get_values()).ravel()
-    print(f"RATIO solve[V] last state: relative deviation {np.abs(u[-1] - last).max() / np.abs(last).max():.3e}")
-    assert np.abs(u[-1] - last).max() <= 1e-9 * np.abs(last).max()
+    conv, rconv, _ = check_history(dev, ref, "solve[V]")
+    assert rconv[-1] < 1e-10 and conv[-1] < 1e-10, (conv, rconv)
 
 
 def test_jump_criterion_matches_the_plugin_path():
     """conv_crit = 1: the norms of u_i - previous u_i over both planes, three iterations from the initial guess; the same rule"""
     assert torch.cuda.is_available()
     dev, ref = _pair(12, _solve_grids(), conv_crit=1, max_iter=3, tol=0.0, **SOLVE)
-    conv, rconv = np.asarray(dev.solve()["conv"]), np.asarray(ref.solve()["conv"])
-    norm_u = cases.spacetime_norm(dev.backend.natural("u", 0))
-    assert len(conv) == len(rconv) == 3 and np.all(rconv[:2] > 0.0), (conv, rconv)
-    print(f"RATIO solve[jump] conv: largest deviation {np.max(np.abs(conv - rconv)) / (EPS * norm_u):.2f} units of eps*norm(u)")
-    assert np.all(np.abs(conv - rconv) <= 1e-10 * rconv + cases.BLK_K * EPS * norm_u), (conv, rconv)
+    check_jump_criterion(dev, ref, 2)
 
 
 # ---- i. what is refused ---------------------------------------------------------------------------------------------------------------
@@ -450,32 +343,15 @@ def test_level_entry_point_refuses_bad_arguments():
     """mgrit_hip_level_ginzburglandau2d through raw ctypes: negative codes with a message, and what follows from the level's kind"""
     assert torch.cuda.is_available()
     from pymgrit_amd.core import hip_lib
-    lib = hip_lib.load()
-    EINVAL, EUNSUPPORTED = -1, -4
-    gl, cfg, msg = lib.mgrit_hip_level_ginzburglandau2d, lib.mgrit_hip_block_solve_config, lib.mgrit_hip_last_error
-    eng = C.c_void_p()
-    assert lib.mgrit_hip_create(C.byref(eng), 3, C.c_void_p(torch.cuda.current_stream().cuda_stream)) == 0
-    try:
-        t9 = np.ascontiguousarray(np.linspace(0.0, 0.5, 9))
-        tp, null = C.c_void_p(t9.ctypes.data), C.c_void_p(0)
-        ok = (20, 800, 1.0, 1.5, -0.8)      # nx, ld, 1 / dx^2, b, c
-        assert gl(None, 0, 9, tp, *ok) < 0 and gl(eng, 5, 9, tp, *ok) < 0 and gl(eng, -1, 9, tp, *ok) < 0
-        assert gl(eng, 0, 9, tp, 3, 32, 1.0, 1.5, -0.8) == EUNSUPPORTED and b"Ginzburg-Landau grid" in msg()
-        assert gl(eng, 0, 9, tp, 2049, 2 * 2049 * 2049 + 14, 1.0, 1.5, -0.8) == EUNSUPPORTED and b"Ginzburg-Landau grid" in msg()
-        assert gl(eng, 0, 9, tp, 20, 400, 1.0, 1.5, -0.8) == EINVAL and b"2*nx*nx" in msg()      # one plane's worth
-        assert gl(eng, 0, 9, tp, 20, 808, 1.0, 1.5, -0.8) == EINVAL                                # not a multiple of 16
-        for bad in ((20, 800, 0.0, 1.5, -0.8), (20, 800, -1.0, 1.5, -0.8), (20, 800, float("inf"), 1.5, -0.8), (20, 800, float("nan"), 1.5, -0.8),
-                    (20, 800, 1.0, float("nan"), -0.8), (20, 800, 1.0, float("inf"), -0.8), (20, 800, 1.0, 1.5, float("nan")),
-                    (20, 800, 1.0, 1.5, -float("inf"))):
-            assert gl(eng, 0, 9, tp, *bad) == EINVAL and b"Ginzburg-Landau parameters" in msg(), bad
-        assert gl(eng, 0, 9, null, *ok) == EINVAL and gl(eng, 0, -1, tp, *ok) == EINVAL
-        assert gl(eng, 0, 9, tp, *ok) == 0 and gl(eng, 1, 9, tp, *ok) == 0
-        assert gl(eng, 0, 9, tp, *ok) < 0 and b"already" in msg()                # already described
-        # non-linear Phi: no time-parallel forward solve (r > 0 refused, the rule r < 0 leaves it step by step)
-        assert cfg(eng, 1, 4, 1, 0, null, null) == EUNSUPPORTED
-        assert cfg(eng, 1, -1, 1, 0, null, null) == 0
-        # two levels of one nx: the periodic 2-D transfer is not theirs, the copy is
-        assert lib.mgrit_hip_level_transfer(eng, 0, hip_lib.TRANSFER_PERIODIC2D) == EUNSUPPORTED
+    ok = (20, 800, 1.0, 1.5, -0.8)      # nx, ld, 1 / dx^2, b, c
+
+    def transfers(lib, eng, fn, tp, msg):      # two levels of one nx: the periodic 2-D transfer is not theirs, the copy is
+        assert lib.mgrit_hip_level_transfer(eng, 0, hip_lib.TRANSFER_PERIODIC2D) == -4
         assert lib.mgrit_hip_level_transfer(eng, 0, hip_lib.TRANSFER_COPY) == 0
-    finally:
-        assert lib.mgrit_hip_destroy(eng) == 0
+    check_level_entry_point(
+        "mgrit_hip_level_ginzburglandau2d", 3, 5, 0.5, ok, small=(3, 32) + ok[2:], large=(2049, 2 * 2049 * 2049 + 14) + ok[2:],
+        short=(20, 400) + ok[2:], odd=(20, 808) + ok[2:],      # one plane's worth; not a multiple of 16
+        bad=((20, 800, 0.0, 1.5, -0.8), (20, 800, -1.0, 1.5, -0.8), (20, 800, float("inf"), 1.5, -0.8), (20, 800, float("nan"), 1.5, -0.8),
+             (20, 800, 1.0, float("nan"), -0.8), (20, 800, 1.0, float("inf"), -0.8), (20, 800, 1.0, 1.5, float("nan")),
+             (20, 800, 1.0, 1.5, -float("inf"))),
+        grid_msg=b"Ginzburg-Landau grid", ld_msg=b"2*nx*nx", bad_msg=b"Ginzburg-Landau parameters", describe=[(0, ok), (1, ok)], then=transfers)

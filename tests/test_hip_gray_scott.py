@@ -31,121 +31,57 @@ Tolerances, nothing in them measured on the device (test_gray_scott_cpu.py state
 Every comparison covers all rows of a list. Each sweep prints its worst error / allowed ("RATIO" lines). Largest ratio of the first
 run on an MI355X: see DESIGN.md 3.11.
 """
-import collections
-import ctypes as C
 import types
 
 import numpy as np
 import pytest
 
 import cases
-from gray_scott_reference import ReferenceGrayScott
-from periodic2d_sweeps import (ALL_SWEEPS, STORED_STATE_SWEEPS, compare as _compare, distinct_steps as _distinct_steps, host_state as _host_state,
-                               intervals as _intervals, lists as _lists, report as _report, row_norm as _row_norm, run_sweeps,
-                               set_states as _set_states, tol, uniform as _uniform)
+from periodic2d_kinds import KINDS, dyadic
+from periodic2d_sweeps import (STORED_STATE_SWEEPS, both_weights, bounds_of, check_history, check_jump_criterion, check_level_entry_point,
+                               check_one_phi, check_ragged, compare as _compare, dt_groups, intervals as _intervals, pair, report as _report,
+                               row_norm as _row_norm, run_sweeps, set_states as _set_states, tol, uniform as _uniform)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 EPS = cases.EPS
+KIND = KINDS["grayscott"]
+BOUNDS = bounds_of("grayscott", "reference")
 
 
-def _t_sweep(nx):
-    """[0, T] with 16 fine steps of r = dt du / dx^2 = 2 (du = 1, L = 2): r = 8 on the coarsest of the three levels; dt = 0.5 at nx = 4"""
-    return 16 * 2.0 * (2.0 / nx) ** 2
-
-
-def _pair(nx, grids, par=None, **opts):
+def _pair(nx, grids, **opts):
     """(device Mgrit, plugin Mgrit over ReferenceGrayScott) on the same hierarchy"""
-    from pymgrit_amd import GrayScott, Mgrit
-    opts.setdefault("nested_iteration", False)
-    par = par or {}
-    dev = Mgrit([GrayScott(nx=nx, method="IMEX", **par, **g) for g in grids], logging_lvl=30, **opts)
-    ref = Mgrit([ReferenceGrayScott(nx=nx, method="IMEX", **par, **g) for g in grids], logging_lvl=30, **opts)
-    assert type(dev.backend).__name__ == "HipBackend" and type(ref.backend).__name__ == "PluginBackend"
-    for a, b in zip(dev.t, ref.t):
-        assert np.array_equal(a, b)
-    return dev, ref
+    return pair("grayscott", nx, grids, side="reference", **opts)
 
 
-def _random_states(ref, seed):
-    """per list and level [n_pts][2 nx^2]: u plane uniform in [0, 1], v plane uniform in [0, 0.5]"""
-    rng = np.random.default_rng(seed)
-    out = {}
-    for lvl in range(ref.lvl_max):
-        for name, lst in _lists(ref, lvl):
-            n = ref.problem[lvl].nx ** 2
-            out[(name, lvl)] = np.concatenate((rng.uniform(0.0, 1.0, size=(len(lst), n)), rng.uniform(0.0, 0.5, size=(len(lst), n))), axis=1)
-    return out
-
-
-def _phi_term(app, rows, dt):
-    """one device evaluation and the reference's rounding, the two species in quadrature (module docstring)"""
-    rows = np.abs(np.atleast_2d(rows))
-    n = app.nx ** 2
-    u, v = rows[:, :n], rows[:, n:]
-    bu = float(np.max(np.linalg.norm(u + dt * (abs(app.a) * np.abs(1.0 - u) + u * v * v), axis=1)))
-    bv = float(np.max(np.linalg.norm(v + dt * (u * v * v + abs(app.b) * v), axis=1)))
-    return ((4 * app.nx + 8) + 1) * EPS * float(np.hypot(bu, bv))
-
-
-def _lip(app, dt, rows):
-    R2 = float(np.abs(rows).max()) ** 2
-    return float(np.linalg.norm([[1 + dt * (abs(app.a) + R2), 2 * dt * R2], [dt * R2, 1 + dt * (2 * R2 + abs(app.b))]]))
-
-
-BOUNDS = types.SimpleNamespace(random_states=_random_states, phi_term=lambda ref, app, rows, dt: _phi_term(app, rows, dt), lip=_lip,
-                               values_per_state=lambda app: 2 * app.nx ** 2, coarse_rows=lambda ref, st, lvl: st[("u", lvl)], weight_in_key=True)
-
-
-def _tol(ref, lvl, rows):
-    return tol(BOUNDS, ref, lvl, rows)
+def _default_ratio(dev):
+    assert dev.problem[0].du == 100 * dev.problem[0].dv
 
 
 # ---- a. every sweep at the size edges of the tile product --------------------------------------------------------------------------
 @pytest.mark.parametrize("nx", [4, 33, 96, 97, 129])
 def test_every_sweep_at_the_size_edges(nx):
     assert torch.cuda.is_available()
-    record = {}
-    for w, sweeps in ((1.0, ALL_SWEEPS), (1.3, ("c_relax",))):      # (the weight enters the C-relaxation only)
-        dev, ref = _pair(nx, _uniform((17, 9, 5), _t_sweep(nx)), weight_c=w)
-        assert dev.problem[0].du == 100 * dev.problem[0].dv
-        run_sweeps(dev, ref, BOUNDS, w, 100 * nx + (7 if w != 1.0 else 0), sweeps, record=record)
-    _report(f"size_edges[nx={nx}]", record)
+    both_weights(lambda w: _pair(nx, _uniform((17, 9, 5), KIND.t_sweep(nx)), weight_c=w), BOUNDS, 100 * nx, 100 * nx + 7, f"size_edges[nx={nx}]",
+                 check=_default_ratio)
 
 
 def test_every_sweep_with_equal_diffusion_coefficients():
     """du = dv: with the default du = 100 dv beside it (above), a table taken for the wrong species shows in one of the two"""
     assert torch.cuda.is_available()
-    nx, record = 33, {}
-    for w, sweeps in ((1.0, ALL_SWEEPS), (1.3, ("c_relax",))):
-        dev, ref = _pair(nx, _uniform((17, 9, 5), _t_sweep(nx)), par=dict(du=0.5, dv=0.5, a=0.04, b=0.1), weight_c=w)
-        run_sweeps(dev, ref, BOUNDS, w, 4242 + (7 if w != 1.0 else 0), sweeps, record=record)
-    _report("equal_diffusion[nx=33]", record)
+    nx = 33
+    both_weights(lambda w: _pair(nx, _uniform((17, 9, 5), KIND.t_sweep(nx)), par=dict(du=0.5, dv=0.5, a=0.04, b=0.1), weight_c=w), BOUNDS,
+                 4242, 4242 + 7, "equal_diffusion[nx=33]")
 
 
 # ---- b. several step sizes per level -----------------------------------------------------------------------------------------------
-RAGGED = np.concatenate(([0.0], np.cumsum(np.array([1, 1, 1.5, .5, 2, 1, 1, .75, 1, 1, 1, 1.25, 3, 1, 1, 1]))))
-
-
-def _ragged(nx, grid):
-    t = RAGGED * 0.5 * (2.0 / nx) ** 2      # unit step: r = dt du / dx^2 = 0.5; at most 6.25 units per coarse step
-    return {"by2_3lvl": [t, t[::2], t[::4]], "by4_2lvl": [t, t[::4]]}[grid]
-
-
 @pytest.mark.parametrize("nx", [20, 66])
 @pytest.mark.parametrize("grid", ["by2_3lvl", "by4_2lvl"])
 def test_every_sweep_with_several_step_sizes_per_level(grid, nx):
     assert torch.cuda.is_available()
-    record = {}
-    for w, sweeps in ((1.0, ALL_SWEEPS), (1.3, ("c_relax",))):
-        dev, ref = _pair(nx, _intervals(_ragged(nx, grid)), weight_c=w)
-        for t in dev.t:
-            assert _distinct_steps(t) >= 3, np.diff(t)
-        if grid == "by4_2lvl":      # the three F-points of one interval do not share one pair of D tables
-            assert sum(_distinct_steps(dev.t[0][a:a + 4]) >= 2 for a in range(0, 16, 4)) >= 2
-        run_sweeps(dev, ref, BOUNDS, w, 500 * nx + (3 if w != 1.0 else 0), sweeps, record=record)
-    _report(f"step_sizes[{grid},nx={nx}]", record)
+    both_weights(lambda w: _pair(nx, _intervals(KIND.ragged(nx)[grid]), weight_c=w), BOUNDS, 500 * nx, 500 * nx + 3, f"step_sizes[{grid},nx={nx}]",
+                 check=lambda dev: check_ragged(dev, grid))
 
 
 # ---- c. a dt group larger than one batch -------------------------------------------------------------------------------------------
@@ -153,13 +89,10 @@ def test_sweeps_of_more_than_one_batch():
     """1027 points with the exact step 2^-7 (every t_k = k 2^-7 and every difference is exact: one bit pattern of dt): 513 F-points and
     513 relaxed C-points, each one dt group = a batch of 512 states (1024 work slab items) and a batch of 1"""
     assert torch.cuda.is_available()
-    nx, w, h = 4, 1.3, 2.0 ** -7
-    t = h * np.arange(1027.0)
-    dev, ref = _pair(nx, _intervals([t, t[::2]]), weight_c=w)
-    t = np.asarray(dev.t[0])
-    assert len(t) == 1027 and len(dev.t[1]) == 514
-    for pts in (np.arange(1, len(t), 2), np.arange(2, len(t), 2)):      # F-points, relaxed C-points
-        groups = sorted(collections.Counter((t[pts] - t[pts - 1]).view(np.int64).tolist()).values())
+    nx, w = 4, 1.3
+    dev, ref = _pair(nx, _intervals(dyadic("grayscott", 1027)), weight_c=w)
+    assert len(dev.t[0]) == 1027 and len(dev.t[1]) == 514
+    for groups in dt_groups(dev.t[0]):      # F-points, relaxed C-points
         assert groups == [513] and 513 > 1024 // 2, groups
     record = run_sweeps(dev, ref, BOUNDS, w, 77, STORED_STATE_SWEEPS, levels=[0])
     _report("batches[dyadic_1027]", record)
@@ -170,12 +103,7 @@ def test_sweeps_of_more_than_one_batch():
 def test_one_phi_at_larger_grids(nx):
     assert torch.cuda.is_available()
     dev, ref = _pair(nx, _uniform((5, 3), 2.0 ** -9))      # (steps of 2^-11, exact: one factorisation per species; r = 8)
-    st = _random_states(ref, nx)
-    _set_states(dev, ref, st)
-    dev.f_relax(0); ref.f_relax(0)
-    allowed = _tol(ref, 0, st[("u", 0)]) + 8 * EPS * 3 * _row_norm(*st.values())
-    worst = _compare(dev, ref, 0, allowed, "f_relax")
-    print(f"RATIO larger_grids[nx={nx}] f_relax: worst error/allowed {worst / allowed:.4f}")
+    check_one_phi(dev, ref, BOUNDS, nx, f"larger_grids[nx={nx}]")
 
 
 # ---- e. the fixed point and a constant state ---------------------------------------------------------------------------------------
@@ -184,15 +112,15 @@ def test_fixed_point_and_constant_rows():
     plane, so Phi = b = (0.5 + dt (a / 2 - 1 / 32), 0.25 + dt (1 / 32 - b / 4))."""
     assert torch.cuda.is_available()
     nx = 33
-    dev, ref = _pair(nx, _uniform((17, 9, 5), _t_sweep(nx)))
+    dev, ref = _pair(nx, _uniform((17, 9, 5), KIND.t_sweep(nx)))
     app, n, dt = ref.problem[0], nx * nx, float(ref.t[0][1] - ref.t[0][0])
-    st = _random_states(ref, 5)
+    st = BOUNDS.random_states(ref, 5)
     fixed = np.concatenate((np.ones(n), np.zeros(n)))
     const = np.concatenate((np.full(n, 0.5), np.full(n, 0.25)))
     st[("u", 0)][0::4], st[("u", 0)][2::4] = fixed, const      # C-points 0, 4, .. the fixed point, 2, 6, .. the constant state
     _set_states(dev, ref, st)
     dev.f_relax(0); ref.f_relax(0)
-    allowed = _tol(ref, 0, st[("u", 0)][0::2]) + 8 * EPS * 3 * _row_norm(*st.values())
+    allowed = tol(BOUNDS, ref, 0, st[("u", 0)][0::2]) + 8 * EPS * 3 * _row_norm(*st.values())
     worst = _compare(dev, ref, 0, allowed, "f_relax, fixed point and constant rows")
     got = dev.backend.natural("u", 0)
     want_const = np.concatenate((np.full(n, 0.5 + dt * (app.a * 0.5 - 0.5 * 0.0625)), np.full(n, 0.25 + dt * (0.5 * 0.0625 - app.b * 0.25))))
@@ -208,16 +136,7 @@ def test_solve_matches_the_reference_hierarchy(cycle):
     """from the initial guess on (nx = 20, [0, 6], nt 65 / 17 / 5): residual histories by the rule of tests/cases.py"""
     assert torch.cuda.is_available()
     dev, ref = _pair(20, _uniform((65, 17, 5), 6.0), cycle_type=cycle, max_iter=6, tol=1e-9, nested_iteration=True)
-    conv, rconv = np.asarray(dev.solve()["conv"]), np.asarray(ref.solve()["conv"])
-    u = dev.backend.natural("u", 0)
-    norm_u = cases.spacetime_norm(u)
-    assert len(conv) == len(rconv) >= 2, (conv, rconv)
-    dev_ref = np.abs(conv - rconv)
-    print(f"RATIO solve[{cycle}] conv ({len(conv)} iterations): largest deviation {np.max(dev_ref) / (EPS * norm_u):.2f} units of "
-          f"eps*norm(u) (allowed {cases.BLK_K} beyond 1e-10 relative)")
-    assert np.all(dev_ref <= 1e-10 * rconv + cases.BLK_K * EPS * norm_u), (conv, rconv)
-    last = _host_state(ref, "u", 0)[-1]
-    print(f"RATIO solve[{cycle}] last state: relative deviation {np.abs(u[-1] - last).max() / np.abs(last).max():.3e}")
+    check_history(dev, ref, f"solve[{cycle}]", last_state=False)
 
 
 def test_jump_criterion_matches_the_reference_hierarchy():
@@ -225,11 +144,7 @@ def test_jump_criterion_matches_the_reference_hierarchy():
     initial guess; the same rule as for the residual histories"""
     assert torch.cuda.is_available()
     dev, ref = _pair(20, _uniform((33, 17, 9), 4.0), conv_crit=1, max_iter=3, tol=0.0)
-    conv, rconv = np.asarray(dev.solve()["conv"]), np.asarray(ref.solve()["conv"])
-    norm_u = cases.spacetime_norm(dev.backend.natural("u", 0))
-    assert len(conv) == len(rconv) == 3 and np.all(rconv > 0.0), (conv, rconv)
-    print(f"RATIO solve[jump] conv: largest deviation {np.max(np.abs(conv - rconv)) / (EPS * norm_u):.2f} units of eps*norm(u)")
-    assert np.all(np.abs(conv - rconv) <= 1e-10 * rconv + cases.BLK_K * EPS * norm_u), (conv, rconv)
+    check_jump_criterion(dev, ref, 3)
 
 
 # ---- what is refused ---------------------------------------------------------------------------------------------------------------
@@ -270,31 +185,14 @@ def test_level_entry_point_refuses_bad_arguments():
     """mgrit_hip_level_grayscott2d through raw ctypes: negative codes with a message, and what follows from the level's kind"""
     assert torch.cuda.is_available()
     from pymgrit_amd.core import hip_lib
-    lib = hip_lib.load()
-    EINVAL, EUNSUPPORTED = -1, -4
-    gs, cfg, msg = lib.mgrit_hip_level_grayscott2d, lib.mgrit_hip_block_solve_config, lib.mgrit_hip_last_error
-    eng = C.c_void_p()
-    assert lib.mgrit_hip_create(C.byref(eng), 3, C.c_void_p(torch.cuda.current_stream().cuda_stream)) == 0
-    try:
-        t9 = np.ascontiguousarray(np.linspace(0.0, 1.0, 9))
-        tp, null = C.c_void_p(t9.ctypes.data), C.c_void_p(0)
-        ok = (20, 800, 100.0, 1.0, 0.01, 0.09, 0.086)
-        assert gs(None, 0, 9, tp, *ok) < 0 and gs(eng, 5, 9, tp, *ok) < 0 and gs(eng, -1, 9, tp, *ok) < 0
-        assert gs(eng, 0, 9, tp, 3, 32, 100.0, 1.0, 0.01, 0.09, 0.086) == EUNSUPPORTED and b"Gray-Scott grid" in msg()
-        assert gs(eng, 0, 9, tp, 2049, 2 * 2049 * 2049 + 14, 100.0, 1.0, 0.01, 0.09, 0.086) == EUNSUPPORTED
-        assert gs(eng, 0, 9, tp, 20, 400, 100.0, 1.0, 0.01, 0.09, 0.086) == EINVAL and b"2*nx*nx" in msg()      # one plane's worth
-        assert gs(eng, 0, 9, tp, 20, 808, 100.0, 1.0, 0.01, 0.09, 0.086) == EINVAL                                # not a multiple of 16
-        for bad in ((20, 800, 0.0, 1.0, 0.01, 0.09, 0.086), (20, 800, 100.0, 0.0, 0.01, 0.09, 0.086), (20, 800, 100.0, 1.0, -0.01, 0.09, 0.086),
-                    (20, 800, 100.0, 1.0, 0.01, float("nan"), 0.086), (20, 800, 100.0, 1.0, 0.01, 0.09, float("inf"))):
-            assert gs(eng, 0, 9, tp, *bad) == EINVAL and b"Gray-Scott parameters" in msg(), bad
-        assert gs(eng, 0, 9, null, *ok) == EINVAL and gs(eng, 0, -1, tp, *ok) == EINVAL
-        assert gs(eng, 0, 9, tp, *ok) == 0 and gs(eng, 1, 9, tp, *ok) == 0
-        assert gs(eng, 0, 9, tp, *ok) < 0 and b"already" in msg()                # already described
-        # non-linear Phi: no time-parallel forward solve (r > 0 refused, the rule r < 0 leaves it step by step)
-        assert cfg(eng, 1, 4, 1, 0, null, null) == EUNSUPPORTED
-        assert cfg(eng, 1, -1, 1, 0, null, null) == 0
-        # no spatial transfer joins two such levels; the copy does
-        assert lib.mgrit_hip_level_transfer(eng, 0, hip_lib.TRANSFER_PERIODIC2D) == EUNSUPPORTED
+    ok = (20, 800, 100.0, 1.0, 0.01, 0.09, 0.086)
+
+    def transfers(lib, eng, fn, tp, msg):      # no spatial transfer joins two such levels; the copy does
+        assert lib.mgrit_hip_level_transfer(eng, 0, hip_lib.TRANSFER_PERIODIC2D) == -4
         assert lib.mgrit_hip_level_transfer(eng, 0, hip_lib.TRANSFER_COPY) == 0
-    finally:
-        assert lib.mgrit_hip_destroy(eng) == 0
+    check_level_entry_point(
+        "mgrit_hip_level_grayscott2d", 3, 5, 1.0, ok, small=(3, 32) + ok[2:], large=(2049, 2 * 2049 * 2049 + 14) + ok[2:], large_says_grid=False,
+        short=(20, 400) + ok[2:], odd=(20, 808) + ok[2:],      # one plane's worth; not a multiple of 16
+        bad=((20, 800, 0.0, 1.0, 0.01, 0.09, 0.086), (20, 800, 100.0, 0.0, 0.01, 0.09, 0.086), (20, 800, 100.0, 1.0, -0.01, 0.09, 0.086),
+             (20, 800, 100.0, 1.0, 0.01, float("nan"), 0.086), (20, 800, 100.0, 1.0, 0.01, 0.09, float("inf"))),
+        grid_msg=b"Gray-Scott grid", ld_msg=b"2*nx*nx", bad_msg=b"Gray-Scott parameters", describe=[(0, ok), (1, ok)], then=transfers)

@@ -9,14 +9,14 @@ well. Every level of every hierarchy has max dt <= 0.25: dt mu(1.05, 0.55) = 0.2
 solution (gray_scott_newton_reference.py derives mu; the coarsest dt = 2 at nx = 4 of the IMEX tests' _t_sweep is the two-root case and
 is not used). The box is not assumed: every tolerance takes it from the data and asserts dt mu < 1.
 
-Tolerances, nothing of them measured on the device but its own residual in long double (test_gray_scott_newton_cpu.py states them):
+Tolerances, nothing of them measured on the device but its own residual in long double (gray_scott_newton_reference.py states them):
 
   a Phi that a sweep's row holds (F-relaxation, C-relaxation, forward_solve on every level: row = w (g + Phi) + (1 - w) old, so Phi is
       recovered from the row in long double by subtracting the same g and old on both sides; on level 0 the row IS Phi):
       tau = (norm_2(F(x_dev)) + norm_2(F(x_ref))) / (1 - dt mu) + EPS norm_2(x), both residuals in long double by the reference's code,
       each for its own side's input, mu from the largest |u|, |v| over both Phi and both inputs. Any two points of the box satisfy
       this; it gets its teeth from the exit criterion asserted beside it for every such Phi, max|F(x_dev)| < newton_tol + E_g + E_add:
-      E_g = C_G EPS S from the operation count of gsn_residual_kernel (C_G = 8; test_gray_scott_newton_cpu.py), E_add the sweep's own
+      E_g = C_G EPS S from the operation count of gsn_residual_kernel (C_G = 8; gray_scott_newton_reference.py), E_add the sweep's own
       roundings between the device's Phi and the recovered one (_measured; zero where the row is Phi).
   a Phi that is not recoverable (fas_residual: the coarse g mixes one Phi of each level; compute_residual: only the norm of Phi - u is
       seen): the same tau with the two residuals replaced by what each side guarantees -- the device sqrt(2) nx (newton_tol + E_g) by
@@ -30,18 +30,18 @@ Tolerances, nothing of them measured on the device but its own residual in long 
 Every comparison covers all rows of a list. Each sweep prints its worst error / allowed ("RATIO" lines); the largest ratio of the first
 run on an MI355X is in DESIGN.md 3.11.
 """
-import collections
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import cases
-from gray_scott_newton_reference import LD, ReferenceGrayScottNewton, mu, residual
-from periodic2d_sweeps import (ALL_SWEEPS, STORED_STATE_SWEEPS, compare as _compare, host_state as _host_state, intervals as _intervals,
-                               lists as _lists, ratio as _ratio, report as _report, row_norm as _row_norm, set_states as _set_states)
-from test_gray_scott_newton_cpu import (C_G_DEVICE, PARS, e_g, exit_criterion, history_allowance, margin, norm2, par_of, tau,
-                                        tau_phi_a_priori)
+from gray_scott_newton_reference import (C_G_DEVICE, LD, PARS, e_g, exit_criterion, history_allowance, margin, mu, norm2, par_of, residual, tau,
+                                         tau_phi_a_priori)
+from periodic2d_kinds import GSN_RAGGED as RAGGED_GRIDS, dyadic
+from periodic2d_sweeps import (STORED_STATE_SWEEPS, both_weights, compare as _compare, distinct_steps, dt_groups, host_state as _host_state,
+                               intervals as _intervals, pair, random_states, ratio as _ratio, report as _report, row_norm as _row_norm,
+                               set_states as _set_states)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -57,27 +57,15 @@ def _uniform(nts, t_stop=1.0):
 
 def _pair(nx, grids, par=None, app=None, **opts):
     """(device Mgrit, plugin Mgrit over ReferenceGrayScottNewton) on the same hierarchy"""
-    from pymgrit_amd import GrayScott, Mgrit
-    opts.setdefault("nested_iteration", False)
-    par = par or {}
-    dev = Mgrit([GrayScott(nx=nx, method="IMPL", linear_solver="bicgstab", **par, **(app or {}), **g) for g in grids], logging_lvl=30, **opts)
-    ref = Mgrit([ReferenceGrayScottNewton(nx=nx, **par, **g) for g in grids], logging_lvl=30, **opts)
-    assert type(dev.backend).__name__ == "HipBackend" and type(ref.backend).__name__ == "PluginBackend"
-    for a, b in zip(dev.t, ref.t):
-        assert np.array_equal(a, b) and np.max(np.diff(a)) <= 0.25
+    dev, ref = pair("grayscott", nx, grids, side="reference", newton=True, par=par, dev_par=app, **opts)
+    for t in dev.t:
+        assert np.max(np.diff(t)) <= 0.25
     return dev, ref
 
 
 def _random_states(ref, seed):
     """per list and level [n_pts][2 nx^2]: states in the box, right-hand sides small and signed (module docstring)"""
-    rng = np.random.default_rng(seed)
-    out = {}
-    for lvl in range(ref.lvl_max):
-        for name, lst in _lists(ref, lvl):
-            n = ref.problem[lvl].nx ** 2
-            lo, hi = ((-0.01, -0.005), (0.01, 0.005)) if name == "g" else ((0.0, 0.0), (1.0, 0.5))
-            out[(name, lvl)] = np.concatenate([rng.uniform(lo[c], hi[c], size=(len(lst), n)) for c in range(2)], axis=1)
-    return out
+    return random_states("grayscott", ref, seed, newton=True)
 
 
 def _reset(ref):
@@ -198,27 +186,26 @@ def _run_sweeps(dev, ref, w, seed, sweeps, levels=None, record=None):
     return record
 
 
+def _run(dev, ref, bounds, w, seed, sweeps, record):
+    return _run_sweeps(dev, ref, w, seed, sweeps, record=record)
+
+
 # ---- every sweep at the edge sizes of the new kernels ------------------------------------------------------------------------------
 @pytest.mark.parametrize("nx", [4, 33, 66])
 def test_every_sweep_at_the_size_edges(nx):
     """nx = 4: the stencil wraps onto itself, one workgroup per item; 33: odd, 1089 points, no multiple of a wave; 66: past one 64-tile"""
     assert torch.cuda.is_available()
-    record = {}
-    for w, sweeps in ((1.0, ALL_SWEEPS), (1.3, ("c_relax",))):      # (the weight enters the C-relaxation only)
-        dev, ref = _pair(nx, _uniform((9, 5, 3), 0.5), weight_c=w)      # coarsest step 0.25
+
+    def check(dev):
         assert dev.problem[0].du == 100 * dev.problem[0].dv and dev.problem[0].device_stepper()["theta"] == 1.0
-        _run_sweeps(dev, ref, w, 100 * nx + (7 if w != 1.0 else 0), sweeps, record=record)
-    _report(f"size_edges[nx={nx}]", record)
+    both_weights(lambda w: _pair(nx, _uniform((9, 5, 3), 0.5), weight_c=w), None, 100 * nx, 100 * nx + 7, f"size_edges[nx={nx}]",      # coarsest step 0.25
+                 check=check, run=_run)
 
 
 def test_every_sweep_with_equal_diffusion_coefficients():
     """du = dv: with the default du = 100 dv beside it (above), a table or a coefficient taken for the wrong species shows in one of the two"""
     assert torch.cuda.is_available()
-    record = {}
-    for w, sweeps in ((1.0, ALL_SWEEPS), (1.3, ("c_relax",))):
-        dev, ref = _pair(20, _uniform((17, 9, 5)), par=PARS["du=dv"], weight_c=w)
-        _run_sweeps(dev, ref, w, 4242 + (7 if w != 1.0 else 0), sweeps, record=record)
-    _report("equal_diffusion[nx=20]", record)
+    both_weights(lambda w: _pair(20, _uniform((17, 9, 5)), par=PARS["du=dv"], weight_c=w), None, 4242, 4242 + 7, "equal_diffusion[nx=20]", run=_run)
 
 
 # ---- one observable Phi: the measured tau and the exit criterion -------------------------------------------------------------------
@@ -322,22 +309,16 @@ def test_an_item_is_the_same_bits_alone_and_among_others():
 
 
 # ---- several step sizes per level --------------------------------------------------------------------------------------------------
-RAGGED = 0.039 * np.concatenate(([0.0], np.cumsum(np.array([1, 1, 1.5, .5, 2, 1, 1, .75, 1, 1, 1, 1.25, 3, 1, 1, 1]))))
-RAGGED_GRIDS = {"by2_3lvl": [RAGGED, RAGGED[::2], RAGGED[::4]], "by4_2lvl": [RAGGED, RAGGED[::4]]}      # largest step 6.25 units = 0.244
-
-
 @pytest.mark.parametrize("grid", sorted(RAGGED_GRIDS))
 def test_every_sweep_with_several_step_sizes_per_level(grid):
     """batch_make_plans groups a sweep's items by the bit pattern of dt, one [2][P][P] preconditioner table per group; coarsening 4 puts
     the three F-points of one interval into different groups"""
     assert torch.cuda.is_available()
-    record = {}
-    for w, sweeps in ((1.0, ALL_SWEEPS), (1.3, ("c_relax",))):
-        dev, ref = _pair(20, _intervals(RAGGED_GRIDS[grid]), weight_c=w)
+
+    def check(dev):      # (the ragged grid's largest step is 6.25 units = 0.244)
         for t in dev.t:
-            assert len(set(np.diff(np.asarray(t, dtype=np.float64)).view(np.int64).tolist())) >= 3
-        _run_sweeps(dev, ref, w, 10000 + (3 if w != 1.0 else 0), sweeps, record=record)
-    _report(f"step_sizes[{grid}]", record)
+            assert distinct_steps(t) >= 3
+    both_weights(lambda w: _pair(20, _intervals(RAGGED_GRIDS[grid]), weight_c=w), None, 10000, 10000 + 3, f"step_sizes[{grid}]", check=check, run=_run)
 
 
 # ---- a dt group larger than the Newton batch cap -----------------------------------------------------------------------------------
@@ -346,13 +327,10 @@ def test_sweeps_of_more_than_one_batch():
     of 100 states, which the Newton arm cuts into a batch of GSN_MAX_BATCH = 93 and one of 7 -- the index lists, the sweep's arithmetic
     and the row sums of the residual offset per batch"""
     assert torch.cuda.is_available()
-    nx, w, h = 4, 1.3, 2.0 ** -7
-    t = h * np.arange(201.0)
-    dev, ref = _pair(nx, _intervals([t, t[::2]]), weight_c=w)
-    t = np.asarray(dev.t[0])
-    assert len(t) == 201 and len(dev.t[1]) == 101
-    for pts in (np.arange(1, len(t), 2), np.arange(2, len(t), 2)):      # F-points, relaxed C-points
-        groups = sorted(collections.Counter((t[pts] - t[pts - 1]).view(np.int64).tolist()).values())
+    nx, w = 4, 1.3
+    dev, ref = _pair(nx, _intervals(dyadic("grayscott", 201)), weight_c=w)
+    assert len(dev.t[0]) == 201 and len(dev.t[1]) == 101
+    for groups in dt_groups(dev.t[0]):      # F-points, relaxed C-points
         assert groups == [100] and GSN_MAX_BATCH == 93 and 100 > GSN_MAX_BATCH, groups
     record = _run_sweeps(dev, ref, w, 77, STORED_STATE_SWEEPS, levels=[0])
     _report("batches[dyadic_201]", record)
@@ -412,7 +390,7 @@ def test_the_caps_equal_the_host_step(lin_maxiter):
 # ---- solves ------------------------------------------------------------------------------------------------------------------------
 def test_solve_matches_the_reference_hierarchy():
     """from the initial guess on (nx = 20, [0, 1], nt 17 / 9 / 5, newton_tol = 1e-12 on the device): the residual histories by
-    history_allowance (test_gray_scott_newton_cpu.py)"""
+    history_allowance (gray_scott_newton_reference.py)"""
     assert torch.cuda.is_available()
     dev, ref = _pair(20, _uniform((17, 9, 5)), app=dict(newton_tol=1e-12), max_iter=8, tol=1e-9, nested_iteration=True)
     conv, rconv = np.asarray(dev.solve()["conv"]), np.asarray(ref.solve()["conv"])

@@ -168,12 +168,11 @@ def test_reference_unit_test_kats_on_gpu():
     """reference tests/heat/test_heat_2d.py:230-293 through the GPU engine: one step of a 1-level hierarchy"""
     from pymgrit_amd import Mgrit
     from pymgrit_amd.heat.heat_2d import Heat2D
-    from test_heat2d_cpu import REF_KAT
     for method in ("BE", "CN", "FE"):
         app = Heat2D(a=1, x_start=0, x_end=1, y_start=3, y_end=4, nx=5, ny=5, method=method, rhs=lambda x, y, t: 2 * x * y,
                      t_start=0, t_stop=1, nt=11)
         mg = Mgrit([app], logging_lvl=30)   # nested iteration on one level = time stepping
-        np.testing.assert_almost_equal(mg.u[0][1].get_values(), np.array(REF_KAT[method]))
+        np.testing.assert_almost_equal(mg.u[0][1].get_values(), np.array(cases.H2D_REF_KAT[method]))
 
 
 def test_config4_size_properties():

@@ -17,7 +17,7 @@ oracle bit for bit; the oracle restates the device's algorithm) shows here. What
 
 The coefficient is "mild" wherever the method is implicit: a such that 4 theta dt (fx + fy) = 8 for the largest step in use, so every mode
 keeps at least 1 / 9 of its weight and a wrong entry for ANY mode shows (with the suite's a = 3.5 the step damps the high modes to
-nothing and such a check is blind to them; tests/test_heat2d_reference_cpu.py shows both). Forward Euler: 4 dt (fx + fy) = 0.9.
+nothing and such a check is blind to them; tests/test_heat2d_reference_cpu.py shows both; heat2d_reference.coefficient). Forward Euler: 4 dt (fx + fy) = 0.9.
 
 Tolerances, nothing measured on the device (heat2d_reference.phi_bound states the per-Phi term):
   per Phi:       ((2 mi + 2 mj + 8) + 1) EPS norm_F(babs)  (theta > 0),   (8 + 1) EPS norm_F(babs)  (theta = 0),
@@ -32,22 +32,19 @@ Tolerances, nothing measured on the device (heat2d_reference.phi_bound states th
                  stepped form.
 Every comparison covers all rows of a list. Each sweep prints its worst error / allowed ("RATIO" lines).
 """
-import collections
-
 import numpy as np
 import pytest
 
 import cases
-from heat2d_reference import EPS, ReferenceHeat2D, babs_norm, phi_bound
-from test_heat2d_reference_cpu import coefficient, make_app
-from test_hip_allen_cahn import _compare, _host_state, _lists, _row_norm, _set_states
-from test_hip_allen_cahn_reference import BATCH_GRIDS, BATCH_GROUPS, H, RAGGED_GRIDS, _distinct_steps, _ratio, _report
+from heat2d_reference import EPS, ReferenceHeat2D, babs_norm, coefficient, make_app, phi_bound
+from periodic2d_kinds import AC_BATCH_GRIDS as BATCH_GRIDS, AC_BATCH_GROUPS as BATCH_GROUPS, H, KINDS
+from periodic2d_sweeps import (ALL_SWEEPS, STORED_STATE_SWEEPS, compare as _compare, distinct_steps as _distinct_steps, dt_groups, host_state as _host_state,
+                               lists as _lists, ratio as _ratio, report as _report, row_norm as _row_norm, set_states as _set_states)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-ALL_SWEEPS = ("f_relax", "c_relax", "fas_residual", "forward_solve", "error_correction", "compute_residual")
-STORED_STATE_SWEEPS = ("f_relax", "c_relax", "fas_residual", "compute_residual")
+RAGGED_GRIDS = KINDS["allencahn"].ragged(None)      # the ragged grids and the batch grids of the Allen-Cahn reference test
 UNIFORM = cases.h2d_grids([17, 9, 5])
 
 
@@ -228,10 +225,9 @@ def test_sweeps_of_more_than_one_batch(grid):
     dev, ref = _pair(nx, ny, ts, weight_c=w)
     t = np.asarray(dev.t[0])
     assert len(t) in (2051, 2053) and len(dev.t[1]) == (len(t) + 1) // 2 and t[1] - t[0] == H
-    for pts in (np.arange(1, len(t), 2), np.arange(2, len(t), 2)):      # F-points, relaxed C-points
-        groups = sorted(collections.Counter((t[pts] - t[pts - 1]).view(np.int64).tolist()).values())
-        print(f"{grid}: dt groups of {len(pts)} points: {groups}")
-        assert len(pts) >= 1025 and groups == BATCH_GROUPS[grid], groups
+    for groups in dt_groups(t):      # F-points, relaxed C-points
+        print(f"{grid}: dt groups of {sum(groups)} points: {groups}")
+        assert sum(groups) >= 1025 and groups == BATCH_GROUPS[grid], groups
     record = _run_sweeps(dev, ref, w, 77, STORED_STATE_SWEEPS, levels=[0])
     _report(f"batches[{grid}]", record)
 

@@ -163,7 +163,7 @@ def test_workgroup_size_instances_match_the_oracle(oracle, forcing, nx):
     """levels of one group of values (n <= 1024) launch the cycle's sweeps compiled for ONE wave per workgroup (TB = 64 instances of
     relax<FC>, ecf, cfas, ecfr, fas_fused1: no spill code, the single-group form of Phi), levels of up to 8192 values the instances
     compiled for 512 threads (no VGPR spills): whole V- and F-cycles through them equal the oracle"""
-    from test_hip_parity import _need_gpu, assert_state_equal, make_pair, randomize
+    from parity_cases import need_gpu as _need_gpu, assert_state_equal, make_pair, randomize
     _need_gpu()
     nt = 257 if nx <= 1024 else 65
     grids = [cases.lin(2, nt), cases.lin(2, nt)[::4], cases.lin(2, nt)[::16]]

@@ -24,7 +24,7 @@ inside the reference solver's certificate. What the cases are chosen for:
   k. a V-cycle solve to 1e-10 against the plugin path over the host step;
   l. what is refused.
 
-Tolerances, nothing in them measured on the device (test_navier_stokes_cpu.py derives C(nx) = 4 nx + 17 and the majorant M = M1 + M2,
+Tolerances, nothing in them measured on the device (navier_stokes_reference.py derives C(nx) = 4 nx + 17 and the majorant M = M1 + M2,
 M1 the stencil's own terms on |w| and the reference's |psi|, M2 = dt (norm(w) / (lam_1 dx)) (max |wx| + max |wy|) the propagated psi error):
   per Phi:     device against host 2 C(nx) EPS M (each side C(nx) EPS M), device against reference (C(nx) + ALLOWANCE) EPS M, M the
                largest over the rows;
@@ -41,7 +41,6 @@ M1 the stencil's own terms on |w| and the reference's |psi|, M2 = dt (norm(w) / 
                orders below 1e-6 R; the same factor covers U, which is evaluated from the reference's long-double psi rounded.
 Every comparison covers all rows of a list. Each sweep prints its worst error / allowed ("RATIO" lines).
 """
-import collections
 import ctypes as C
 import types
 
@@ -49,119 +48,47 @@ import numpy as np
 import pytest
 
 import cases
-from navier_stokes_reference import ALLOWANCE, ReferenceNavierStokes2D, stream_function
-from periodic2d_sweeps import (ALL_SWEEPS, STORED_STATE_SWEEPS, compare as _compare, distinct_steps as _distinct_steps, intervals as _intervals,
-                               lists as _lists, report as _report, row_norm as _row_norm, run_sweeps, set_states as _set_states, tol,
-                               uniform as _uniform)
-from test_navier_stokes_cpu import C as _coef, kolmogorov, lam_1, majorant
+from navier_stokes_reference import C as _coef, kolmogorov, majorant
+from periodic2d_kinds import KINDS, dyadic
+from periodic2d_sweeps import (ALL_SWEEPS, STORED_STATE_SWEEPS, both_weights, bounds_of, check_level_0_twice, check_level_entry_point, check_one_phi,
+                               check_ragged, compare as _compare, distinct_steps as _distinct_steps, dt_groups, f_relaxed_rows,
+                               host_class, intervals as _intervals, pair, report as _report, row_norm as _row_norm, run_sweeps,
+                               set_states as _set_states, tol, uniform as _uniform)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 EPS = cases.EPS
-NU = 0.1
-T_SWEEP = 0.004
+KIND = KINDS["navierstokes"]
+NU = KIND.par(16)["nu"]
+T_SWEEP = KIND.t_sweep(None)
+BOUNDS = {side: bounds_of("navierstokes", side) for side in ("host", "reference")}
 
 
-def _host_class():
-    from pymgrit_amd import NavierStokes2D
-
-    class HostNavierStokes2D(NavierStokes2D):     # overriding step sends the hierarchy to the plugin path
-        def step(self, u_start, t_start, t_stop):
-            return super().step(u_start, t_start, t_stop)
-    return HostNavierStokes2D
-
-
-def _pair(nx, grids, side="host", forcing=None, nxs=None, **opts):
+def _pair(nx, grids, side="host", forcing=None, **opts):
     """(device Mgrit, plugin Mgrit over HostNavierStokes2D or ReferenceNavierStokes2D) on the same hierarchy; forcing: one per level"""
-    from pymgrit_amd import Mgrit, NavierStokes2D
-    opts.setdefault("nested_iteration", False)
-    forcing = [None] * len(grids) if forcing is None else forcing
-    nxs = [nx] * len(grids) if nxs is None else nxs
-    cls = {"host": _host_class(), "reference": ReferenceNavierStokes2D}[side]
-    dev = Mgrit([NavierStokes2D(nx=n, nu=NU, L=nx / 16, forcing=f, **g) for n, g, f in zip(nxs, grids, forcing)], logging_lvl=30, **opts)
-    ref = Mgrit([cls(nx=n, nu=NU, L=nx / 16, forcing=f, **g) for n, g, f in zip(nxs, grids, forcing)], logging_lvl=30, **opts)
-    assert type(dev.backend).__name__ == "HipBackend" and type(ref.backend).__name__ == "PluginBackend"
-    for a, b in zip(dev.t, ref.t):
-        assert np.array_equal(a, b)
-    return dev, ref
-
-
-def _random_states(ref, seed, mean=0.0):
-    """per list and level [n_pts][nx^2], uniform in [-1, 1] (+ mean)"""
-    rng = np.random.default_rng(seed)
-    return {(name, lvl): rng.uniform(-1.0, 1.0, size=(len(lst), ref.problem[lvl].nx ** 2)) + mean
-            for lvl in range(ref.lvl_max) for name, lst in _lists(ref, lvl)}
-
-
-def _majorant(app, rows, dt):
-    """the largest row majorant M1 + M2 (test_navier_stokes_cpu.majorant: the reference's psi, this suite's own formula)"""
-    return max(majorant(row, dt, app.nx, app.L, app.forcing) for row in np.atleast_2d(rows))
-
-
-def _phi_term(app, rows, dt):
-    against_reference = isinstance(app, ReferenceNavierStokes2D)
-    return (_coef(app.nx) + ALLOWANCE if against_reference else 2 * _coef(app.nx)) * EPS * _majorant(app, rows, dt)
-
-
-def _lip(app, dt, rows):
-    nx, dx = app.nx, app.dx
-    U = 0.0
-    for row in np.atleast_2d(rows):
-        psi = stream_function(row, nx, app.L).astype(np.float64)
-        U = max(U, float(np.abs(np.roll(psi, -1, 0) - np.roll(psi, 1, 0)).max()) / (2 * dx),
-                float(np.abs(np.roll(psi, -1, 1) - np.roll(psi, 1, 1)).max()) / (2 * dx))
-    R = float(np.abs(rows).max())
-    return 1.0 + 2.0 * dt * (1.0 + 1e-6) * (U / dx + R / (lam_1(nx, app.L) * dx ** 2))
-
-
-def _bounds(mean=0.0):
-    return types.SimpleNamespace(random_states=lambda ref, seed: _random_states(ref, seed, mean),
-                                 phi_term=lambda ref, app, rows, dt: _phi_term(app, rows, dt), lip=_lip,
-                                 values_per_state=lambda app: app.nx ** 2, coarse_rows=lambda ref, st, lvl: st[("u", lvl)], weight_in_key=True)
-
-
-BOUNDS = _bounds()
-
-
-def _tol(ref, lvl, rows):
-    return tol(BOUNDS, ref, lvl, rows)
+    return pair("navierstokes", nx, grids, side=side, levels=[dict(forcing=f) for f in forcing or [None] * len(grids)], **opts)
 
 
 # ---- a. every sweep at the size edges ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("nx", [4, 33, 66, 97])
 def test_every_sweep_at_the_size_edges(nx):
     assert torch.cuda.is_available()
-    record = {}
-    for w, sweeps in ((1.0, ALL_SWEEPS), (1.3, ("c_relax",))):      # (the weight enters the C-relaxation only)
-        dev, ref = _pair(nx, _uniform((17, 9, 5), T_SWEEP), weight_c=w)
+
+    def check(dev):
         assert dev.problem[0].dx == 1.0 / 16
-        run_sweeps(dev, ref, BOUNDS, w, 100 * nx + (7 if w != 1.0 else 0), sweeps, record=record)
-    _report(f"size_edges[nx={nx}]", record)
+    both_weights(lambda w: _pair(nx, _uniform((17, 9, 5), T_SWEEP), weight_c=w), BOUNDS["host"], 100 * nx, 100 * nx + 7, f"size_edges[nx={nx}]",
+                 check=check)
 
 
 # ---- b. several step sizes per level -----------------------------------------------------------------------------------------------
-RAGGED = np.concatenate(([0.0], np.cumsum(np.array([1, 1, 1.5, .5, 2, 1, 1, .75, 1, 1, 1, 1.25, 3, 1, 1, 1]))))
-
-
-def _ragged(grid):
-    t = RAGGED * 2.0 ** -12      # 18 units: [0, 0.0044]; at most 6.25 units per coarse step, dt = 0.0015
-    return {"by2_3lvl": [t, t[::2], t[::4]], "by4_2lvl": [t, t[::4]]}[grid]
-
-
 @pytest.mark.parametrize("side", ["host", "reference"])
 @pytest.mark.parametrize("grid", ["by2_3lvl", "by4_2lvl"])
 def test_every_sweep_with_several_step_sizes_per_level(grid, side):
     assert torch.cuda.is_available()
-    nx, record = 33, {}
-    for w, sweeps in ((1.0, ALL_SWEEPS), (1.3, ("c_relax",))):
-        dev, ref = _pair(nx, _intervals(_ragged(grid)), side=side, weight_c=w)
-        for t in dev.t:
-            assert _distinct_steps(t) >= 3, np.diff(t)
-        if grid == "by4_2lvl":      # the three F-points of one interval do not share one D table
-            assert sum(_distinct_steps(dev.t[0][a:a + 4]) >= 2 for a in range(0, 16, 4)) >= 2
-        run_sweeps(dev, ref, BOUNDS, w, 500 * nx + (3 if w != 1.0 else 0), sweeps, record=record)
-    _report(f"step_sizes[{grid},{side}]", record)
+    nx = 33
+    both_weights(lambda w: _pair(nx, _intervals(KIND.ragged(nx)[grid]), side=side, weight_c=w), BOUNDS[side], 500 * nx, 500 * nx + 3,
+                 f"step_sizes[{grid},{side}]", check=lambda dev: check_ragged(dev, grid))
 
 
 # ---- c. a dt group larger than one batch -------------------------------------------------------------------------------------------
@@ -171,8 +98,7 @@ BATCH_CAP = 1024      # states of a launch: H2D_MAX_BATCH work slab items, one p
 def _dyadic(n_states):
     """2 n_states + 1 points with the exact step 2^-19 (every t_k = k 2^-19 and every difference is exact: one bit pattern of dt;
     at most [0, 0.0039]): n_states F-points and n_states relaxed C-points"""
-    t = 2.0 ** -19 * np.arange(2.0 * n_states + 1)
-    return [t, t[::2]]
+    return dyadic("navierstokes", 2 * n_states + 1)
 
 
 @pytest.mark.parametrize("n_states", [513, 1025])
@@ -181,13 +107,11 @@ def test_sweeps_of_one_dt_group(n_states):
     assert torch.cuda.is_available()
     nx, w = 4, 1.3
     dev, ref = _pair(nx, _intervals(_dyadic(n_states)), weight_c=w)
-    t = np.asarray(dev.t[0])
-    assert len(t) == 2 * n_states + 1 and len(dev.t[1]) == n_states + 1
-    for pts in (np.arange(1, len(t), 2), np.arange(2, len(t), 2)):      # F-points, relaxed C-points
-        groups = sorted(collections.Counter((t[pts] - t[pts - 1]).view(np.int64).tolist()).values())
+    assert len(dev.t[0]) == 2 * n_states + 1 and len(dev.t[1]) == n_states + 1
+    for groups in dt_groups(dev.t[0]):      # F-points, relaxed C-points
         assert groups == [n_states], groups
     assert (n_states > BATCH_CAP) == (n_states == 1025) and 1025 == BATCH_CAP + 1
-    record = run_sweeps(dev, ref, BOUNDS, w, 77, STORED_STATE_SWEEPS, levels=[0])
+    record = run_sweeps(dev, ref, BOUNDS["host"], w, 77, STORED_STATE_SWEEPS, levels=[0])
     _report(f"batches[{n_states} states]", record)
 
 
@@ -196,12 +120,7 @@ def test_one_phi_at_a_larger_grid():
     assert torch.cuda.is_available()
     nx = 129
     dev, ref = _pair(nx, _uniform((5, 3), 2.0 ** -8))      # (steps of 2^-10, exact)
-    st = _random_states(ref, nx)
-    _set_states(dev, ref, st)
-    dev.f_relax(0); ref.f_relax(0)
-    allowed = _tol(ref, 0, st[("u", 0)]) + 8 * EPS * 3 * _row_norm(*st.values())
-    worst = _compare(dev, ref, 0, allowed, "f_relax")
-    print(f"RATIO larger_grid[nx={nx}] f_relax: worst error/allowed {worst / allowed:.4f}")
+    check_one_phi(dev, ref, BOUNDS["host"], nx, f"larger_grid[nx={nx}]")
 
 
 # ---- e. the known answers ------------------------------------------------------------------------------------------------------------
@@ -214,7 +133,7 @@ def test_known_answers():
     nx, k = 33, 2
     dev, ref = _pair(nx, _uniform((17, 9, 5), T_SWEEP))
     app, dt = ref.problem[0], float(np.max(np.diff(ref.t[0])))
-    st = _random_states(ref, 5)
+    st = BOUNDS["host"].random_states(ref, 5)
     X = 2 * np.pi * np.arange(nx) / nx
     const = np.full(nx * nx, 5.0)
     tg = (2.0 * np.cos(k * X)[:, None] * np.cos(k * X)[None, :]).ravel()
@@ -224,7 +143,7 @@ def test_known_answers():
     _set_states(dev, ref, st)
     dev.f_relax(0); ref.f_relax(0)
     slack = 8 * EPS * 3 * _row_norm(*st.values())
-    allowed = _tol(ref, 0, st[("u", 0)][0::2]) + slack
+    allowed = tol(BOUNDS["host"], ref, 0, st[("u", 0)][0::2]) + slack
     worst = _compare(dev, ref, 0, allowed, "f_relax, known answers")
     got = dev.backend.natural("u", 0)
     assert np.all(np.isfinite(got))
@@ -249,15 +168,7 @@ def test_a_sweep_run_twice_gives_the_same_bits():
     assert torch.cuda.is_available()
     nx = 33
     dev, ref = _pair(nx, _uniform((17, 9, 5), T_SWEEP), forcing=[kolmogorov(nx)] * 3)
-    st = _random_states(ref, 21)
-    for sweep in ("f_relax", "c_relax"):
-        slabs = []
-        for _ in range(2):
-            _set_states(dev, ref, st)
-            getattr(dev, sweep)(0)
-            slabs.append(dev.backend.U[0].clone())
-        assert torch.equal(slabs[0], slabs[1]), sweep
-    assert not torch.equal(slabs[0][1], slabs[0][3])      # (rows of different states differ)
+    check_level_0_twice(dev, ref, BOUNDS["host"].random_states(ref, 21))
 
 
 def test_a_rows_bits_do_not_depend_on_its_batch():
@@ -265,18 +176,11 @@ def test_a_rows_bits_do_not_depend_on_its_batch():
     the first and the last of 1025 (the batch of 1024 and the batch of 1): the same row, bit for bit"""
     assert torch.cuda.is_available()
     nx = 4
-    t7 = 2.0 ** -19 * np.arange(7.0)
     state = np.random.default_rng(3).uniform(-1.0, 1.0, size=nx * nx)
     rows = []
-    for grids, at in ((_intervals([t7, t7[::2]]), (0,)), (_intervals(_dyadic(513)), (0, 1024)), (_intervals(_dyadic(1025)), (0, 2048))):
-        dev, ref = _pair(nx, grids)
-        st = _random_states(ref, 9)
-        for i in at:
-            st[("u", 0)][i] = state
-        _set_states(dev, ref, st)
-        dev.f_relax(0)
-        U = dev.backend.U[0]
-        rows += [U[i + 1].clone() for i in at]
+    for n_pts, at in ((7, (0,)), (2 * 513 + 1, (0, 1024)), (2 * 1025 + 1, (0, 2048))):
+        dev, ref = _pair(nx, _intervals(dyadic("navierstokes", n_pts)))
+        rows += f_relaxed_rows(dev, ref, BOUNDS["host"].random_states(ref, 9), state, at)
     assert len(rows) == 5 and all(torch.equal(rows[0], r) for r in rows[1:])
     assert not torch.equal(rows[0][:nx * nx], torch.from_numpy(state).to(rows[0].device))
 
@@ -292,7 +196,7 @@ def test_every_sweep_with_a_forcing(levels):
     forcing = [f, f, f] if levels == "every level" else [f, None, f]
     for side in ("host", "reference"):
         dev, ref = _pair(nx, _uniform((17, 9, 5), T_SWEEP), side=side, forcing=forcing)
-        run_sweeps(dev, ref, BOUNDS, 1.0, 900 + len(side), ALL_SWEEPS, record=record)
+        run_sweeps(dev, ref, BOUNDS[side], 1.0, 900 + len(side), ALL_SWEEPS, record=record)
     _report(f"forcing[{levels}]", record)
 
 
@@ -303,7 +207,7 @@ def test_every_sweep_on_states_with_mean_5(side):
     assert torch.cuda.is_available()
     nx = 33
     dev, ref = _pair(nx, _uniform((17, 9, 5), T_SWEEP), side=side)
-    record = run_sweeps(dev, ref, _bounds(mean=5.0), 1.0, 1234, ALL_SWEEPS)
+    record = run_sweeps(dev, ref, bounds_of("navierstokes", side, mean=5.0), 1.0, 1234, ALL_SWEEPS)
     _report(f"mean_5[{side}]", record)
 
 
@@ -359,10 +263,10 @@ def test_v_cycle_solve_matches_the_plugin_path():
     test_hip_transfer2d.py::test_heat2d_against_the_plugin_path. (Spatial coarsening 12 -> 6 converges by 0.4 per cycle only on the
     plugin path: it is covered bit for bit above, not solved to 1e-10 here)"""
     assert torch.cuda.is_available()
-    from pymgrit_amd import Mgrit
+    from pymgrit_amd import Mgrit, NavierStokes2D
     out = {}
     for host in (True, False):
-        prob = _coarsened((12, 12, 12), (33, 17, 9), 1.0, cls=_host_class() if host else None, forcing=0.1, nu=0.05, L=2 * np.pi)
+        prob = _coarsened((12, 12, 12), (33, 17, 9), 1.0, cls=host_class(NavierStokes2D) if host else None, forcing=0.1, nu=0.05, L=2 * np.pi)
         mg = Mgrit(problem=prob, logging_lvl=30, tol=1e-10, max_iter=12)
         conv = np.asarray(mg.solve()["conv"])
         assert (type(mg.backend).__name__ == "HipBackend") != host
@@ -410,36 +314,14 @@ def test_level_entry_point_refuses_bad_arguments():
     periodic 2-D transfer joins two Navier-Stokes levels and refuses a Navier-Stokes level above an Allen-Cahn level by name"""
     assert torch.cuda.is_available()
     from pymgrit_amd.core import hip_lib
-    lib = hip_lib.load()
     EINVAL, EUNSUPPORTED = -1, -4
-    ns, cfg, msg = lib.mgrit_hip_level_navierstokes2d, lib.mgrit_hip_block_solve_config, lib.mgrit_hip_last_error
-    eng = C.c_void_p()
-    assert lib.mgrit_hip_create(C.byref(eng), 4, C.c_void_p(torch.cuda.current_stream().cuda_stream)) == 0
-    try:
-        t9 = np.ascontiguousarray(np.linspace(0.0, 0.01, 9))
-        tp, null = C.c_void_p(t9.ctypes.data), C.c_void_p(0)
-        f20, f10 = np.ascontiguousarray(kolmogorov(20)), np.ascontiguousarray(kolmogorov(10))
-        bad_f = f20.copy()
-        bad_f[7, 3] = np.inf
-        ok = (20, 400, 256.0, 8.0, 0.1)      # nx, ld, 1 / dx^2, 1 / (2 dx), nu
-        assert ns(None, 0, 9, tp, *ok, null) < 0 and ns(eng, 5, 9, tp, *ok, null) < 0 and ns(eng, -1, 9, tp, *ok, null) < 0
-        assert ns(eng, 0, 9, tp, 3, 16, 256.0, 8.0, 0.1, null) == EUNSUPPORTED and b"Navier-Stokes grid" in msg()
-        assert ns(eng, 0, 9, tp, 2049, 2049 * 2049 + 15, 256.0, 8.0, 0.1, null) == EUNSUPPORTED and b"Navier-Stokes grid" in msg()
-        assert ns(eng, 0, 9, tp, 20, 384, 256.0, 8.0, 0.1, null) == EINVAL and b"nx*nx" in msg()      # too short
-        assert ns(eng, 0, 9, tp, 20, 408, 256.0, 8.0, 0.1, null) == EINVAL                            # not a multiple of 16
-        for bad in ((20, 400, 256.0, 8.0, 0.0), (20, 400, 256.0, 8.0, -0.1), (20, 400, 256.0, 8.0, float("nan")), (20, 400, 256.0, 8.0, float("inf")),
-                    (20, 400, 0.0, 8.0, 0.1), (20, 400, 256.0, 0.0, 0.1), (20, 400, 256.0, float("inf"), 0.1)):
-            assert ns(eng, 0, 9, tp, *bad, null) == EINVAL and b"Navier-Stokes parameters" in msg(), bad
-        assert ns(eng, 0, 9, tp, *ok, C.c_void_p(bad_f.ctypes.data)) == EINVAL and b"forcing is not finite at value 143" in msg()
-        assert ns(eng, 0, 9, null, *ok, null) == EINVAL
-        assert ns(eng, 0, -1, tp, *ok, null) == EINVAL
-        assert ns(eng, 0, 9, tp, *ok, C.c_void_p(f20.ctypes.data)) == 0
-        assert ns(eng, 1, 9, tp, 10, 112, 64.0, 4.0, 0.1, C.c_void_p(f10.ctypes.data)) == 0
-        assert ns(eng, 2, 9, tp, 10, 112, 64.0, 4.0, 0.1, null) == 0
-        assert ns(eng, 0, 9, tp, *ok, null) < 0 and b"already" in msg()                # already described
-        # non-linear Phi: no time-parallel forward solve (r > 0 refused, the rule r < 0 leaves it step by step)
-        assert cfg(eng, 1, 4, 1, 0, null, null) == EUNSUPPORTED
-        assert cfg(eng, 1, -1, 1, 0, null, null) == 0
+    null = C.c_void_p(0)
+    f20, f10 = np.ascontiguousarray(kolmogorov(20)), np.ascontiguousarray(kolmogorov(10))
+    bad_f = f20.copy()
+    bad_f[7, 3] = np.inf
+    ok = (20, 400, 256.0, 8.0, 0.1)      # nx, ld, 1 / dx^2, 1 / (2 dx), nu
+
+    def transfers(lib, eng, fn, tp, msg):
         # the periodic transfer joins two such levels of sizes 2 n and n, the copy two of one size; not the Heat2D transfer
         assert lib.mgrit_hip_level_transfer(eng, 0, hip_lib.TRANSFER_PERIODIC2D) == 0
         assert lib.mgrit_hip_level_transfer(eng, 1, hip_lib.TRANSFER_COPY) == 0
@@ -450,5 +332,12 @@ def test_level_entry_point_refuses_bad_arguments():
         assert lib.mgrit_hip_level_transfer(eng, 2, hip_lib.TRANSFER_PERIODIC2D) == EUNSUPPORTED
         assert b"the periodic 2-D transfer joins two Allen-Cahn levels" in msg()
         assert lib.mgrit_hip_level_transfer(eng, 0, hip_lib.TRANSFER_PERIODIC2D) == 0
-    finally:
-        assert lib.mgrit_hip_destroy(eng) == 0
+    check_level_entry_point(
+        "mgrit_hip_level_navierstokes2d", 4, 5, 0.01, ok, tail=(null,), small=(3, 16) + ok[2:], large=(2049, 2049 * 2049 + 15) + ok[2:],
+        short=(20, 384) + ok[2:], odd=(20, 408) + ok[2:],      # too short; not a multiple of 16
+        bad=((20, 400, 256.0, 8.0, 0.0), (20, 400, 256.0, 8.0, -0.1), (20, 400, 256.0, 8.0, float("nan")), (20, 400, 256.0, 8.0, float("inf")),
+             (20, 400, 0.0, 8.0, 0.1), (20, 400, 256.0, 0.0, 0.1), (20, 400, 256.0, float("inf"), 0.1)),
+        also_invalid=[(ok + (C.c_void_p(bad_f.ctypes.data),), b"forcing is not finite at value 143")],
+        grid_msg=b"Navier-Stokes grid", ld_msg=b"nx*nx", bad_msg=b"Navier-Stokes parameters",
+        describe=[(0, ok + (C.c_void_p(f20.ctypes.data),)), (1, (10, 112, 64.0, 4.0, 0.1, C.c_void_p(f10.ctypes.data))), (2, (10, 112, 64.0, 4.0, 0.1, null))],
+        then=transfers)

@@ -1,8 +1,9 @@
 """The periodic 2-D device paths (Allen-Cahn IMEX and Newton-PCG, Gray-Scott IMEX and Newton-BiCGStab, Cahn-Hilliard, Burgers,
 Navier-Stokes and Ginzburg-Landau IMEX) against the bits recorded in
 tests/golden/periodic2d_bits.json by tests/golden/make_golden_periodic2d_bits.py: every sweep of the fixed cases of
-tests/periodic2d_bits.py (its docstring says what they are chosen for) leaves the same bytes in every slab, the same residual norms
-and the same Newton / CG counts. Equality only: no tolerance, no case skipped. The tests beside this one (test_hip_allen_cahn*.py,
+tests/periodic2d_bits.py (its docstring says what they are chosen for; their parameters, grids and the ranges of their states come
+from the kinds table, tests/periodic2d_kinds.py) leaves the same bytes in every slab, the same residual norms and the same Newton /
+CG counts. The digest of the inputs covers every state uploaded, so a changed table entry fails here as a changed input. Equality only: no tolerance, no case skipped. The tests beside this one (test_hip_allen_cahn*.py,
 test_hip_gray_scott*.py, test_hip_cahn_hilliard.py, test_hip_burgers.py, test_hip_navier_stokes.py, test_hip_ginzburg_landau.py) say that the arithmetic is right; this one says that it has not moved."""
 import pytest
 

@@ -11,10 +11,12 @@ import numpy as np
 import pytest
 
 import cases
-from test_allen_cahn_cpu import EPS
+from transfer2d_cases import fill as _fill, one_step_size as _one_step_size, raw as _raw, solve
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
+
+EPS = cases.EPS
 
 T_SWEEP = 0.002     # as tests/test_hip_allen_cahn.py
 
@@ -44,10 +46,6 @@ def _classes():
     return {"heat": (GridTransferHeat2D, Heat2DViaPython), "ac": (GridTransferAllenCahn, AllenCahnViaPython)}
 
 
-def _one_step_size(t):
-    return len(set(np.diff(np.asarray(t, dtype=np.float64)).view(np.int64).tolist())) == 1
-
-
 def heat_problem(shapes, nt0, strides, method="BE", host=False):
     from pymgrit_amd.heat.heat_2d import Heat2D
     t0 = np.linspace(0, 1, nt0)
@@ -69,13 +67,6 @@ def transfers(kind, n_levels, via_python, copies=()):
     from pymgrit_amd import GridTransferCopy
     lib, py = _classes()[kind]
     return [GridTransferCopy() if lvl in copies else (py if via_python else lib)() for lvl in range(n_levels - 1)]
-
-
-def solve(prob, tr, solver=None, **opts):
-    from pymgrit_amd import Mgrit
-    mg = (solver or Mgrit)(problem=prob, transfer=tr, logging_lvl=30, **opts)
-    conv = np.asarray(mg.solve()["conv"])
-    return conv, mg
 
 
 def both(kind, make_problem, n_levels, copies=(), solver=None, **opts):
@@ -139,21 +130,6 @@ def test_at_mgrit_bit_identical():
 
 
 # ---- the sweeps alone ----------------------------------------------------------------------------------------------------------------
-def _fill(mg, seed):
-    rng = np.random.default_rng(seed)
-    b = mg.backend
-    for lvl in range(mg.lvl_max):
-        for name, slabs in (("u", b._U), ("v", b.V), ("g", b.G)):
-            if slabs[lvl] is not None:
-                b.set_natural(name, lvl, rng.uniform(-1.0, 1.0, size=(slabs[lvl].shape[0], b.n[lvl])))
-
-
-def _raw(mg, name, lvl):
-    b = mg.backend
-    b.sync()
-    return {"u": b._U, "v": b.V, "g": b.G}[name][lvl].cpu().numpy()
-
-
 @pytest.mark.parametrize("kind,fine,coarse", [("heat", (5, 7), (3, 4)), ("heat", (67, 35), (34, 18)), ("ac", (66, 66), (33, 33))])
 def test_sweeps_alone_equal_the_python_methods(kind, fine, coarse):
     from pymgrit_amd import Mgrit

@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 import cases
-from test_hip_transfer2d import _fill, _one_step_size, _raw, solve
+from transfer2d_cases import fill as _fill, one_step_size as _one_step_size, raw as _raw, solve
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import cases
-from test_hip_parity import assert_state_equal, make_pair, randomize
+from parity_cases import assert_state_equal, make_pair, randomize
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -110,7 +110,7 @@ def test_wide_states_on_ranks(oracle):
     assert torch.cuda.is_available()
     from pymgrit_amd import Mgrit
     from pymgrit_amd.core.comm import run_loopback_ranks
-    from test_hip_parity import heat_problem
+    from parity_cases import heat_problem
     grids = [cases.lin(2, 33), cases.lin(2, 9), cases.lin(2, 3)]
 
     def target(comm):

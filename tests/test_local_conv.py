@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import cases
+from dist_cases import launch, local_conv_ranks_problem
 from pymgrit_amd import Dahlquist, Heat1D, Mgrit, simple_setup_problem
 
 GOLD = cases.load_json("local_conv.json")
@@ -64,34 +65,13 @@ def test_heat_local_criterion_hip_path(crit):
 RANKS = cases.load_json("local_conv_ranks.json")
 
 
-def _ranks_problem(name):
-    if name.startswith("dahlquist"):
-        return (lambda: simple_setup_problem(Dahlquist(t_start=0, t_stop=5, nt=101), level=3, coarsening=2)), dict(tol=1e-10, conv_crit=2)
-    table = {
-        "heat_crit2_V": ([65, 17, 5], dict(tol=1e-7, max_iter=12, conv_crit=2)),
-        "heat_crit3_V": ([65, 17, 5], dict(tol=1e-7, max_iter=12, conv_crit=3)),
-        "heat_crit2_F_nonested": ([65, 17, 5], dict(tol=1e-7, max_iter=12, conv_crit=2, cycle_type='F', nested_iteration=False)),
-        "heat_crit2_maxiter": ([65, 17, 5], dict(tol=1e-14, max_iter=3, conv_crit=2)),
-        "heat_crit2_2lvl_cf2": ([65, 9], dict(tol=1e-7, max_iter=12, conv_crit=2, cf_iter=2)),
-    }
-    nts, opts = table[name]
-
-    def make():
-        prob = [Heat1D(x_start=0, x_end=1, nx=33, a=1, init_cond=cases.init_cond, rhs_separable=[(cases.rhs_space, cases.rhs_time)],
-                       t_start=0, t_stop=2, nt=nt) for nt in nts]
-        for p in prob:
-            p.device_stepper = lambda: None
-        return prob
-    return make, opts
-
-
 @pytest.mark.parametrize("key", sorted(RANKS))
 def test_local_criterion_on_several_ranks_matches_the_reference(key):
     """ranks leave the solve loop in different iterations (mgrit.py:434-455,648-691): per rank the residual history (its
     length = the iteration in which the rank left) and sampled solution values of the reference's own multi-rank run"""
     from mock_comm import run_ranks
     name, size = key.rsplit("_P", 1)
-    make, opts = _ranks_problem(name)
+    make, opts = local_conv_ranks_problem(name)
 
     def target(comm):
         mg = Mgrit(make(), comm_time=comm, logging_lvl=30, **opts)
@@ -119,7 +99,6 @@ def _check_against_reference(res, key):
 @pytest.mark.parametrize("key", ["heat_crit2_V_P3", "heat_crit3_V_P2"])
 def test_local_criterion_over_torch_distributed(key):
     """the same protocol over real process groups (gloo): per-link communicators, pickled verdicts, staged sends"""
-    from test_distributed import launch
     name, size = key.rsplit("_P", 1)
     _check_against_reference(launch(int(size), "lc:" + name, per_rank=True, timeout=120), key)
 
@@ -131,6 +110,5 @@ def test_local_criterion_on_several_ranks_hip_path(key):
     torch = pytest.importorskip("torch")
     if not torch.cuda.is_available():
         pytest.fail("GPU test selected but no GPU visible")
-    from test_distributed import launch
     name, size = key.rsplit("_P", 1)
     _check_against_reference(launch(int(size), "lc:" + name, mode="hip", backend="gloo", per_rank=True, timeout=300), key)
